@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
                     [--workload auto|cornell|mesh1m|meshN] [--depth D] [--resolution WxH] [--spp S] [--scaling strong|weak]
+                    [--dump-outputs DIR]
 
 One step = one pass of the hot path over one batch of the workload: `spp_per_step` samples per pixel of this rank's
 tiles (ray generation -> CWBVH closest hit -> shading / NEE -> CWBVH any hit -> accumulate), everything resident in HBM.
@@ -120,7 +121,18 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU and no rendering: launcher, process group (gloo), shard bookkeeping, gather and the JSON line only "
                          "(what the CPU tests exercise); the line says dry_run and reports no throughput")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed step computed to DIR/<name>.npy (float32 / float64, "
+                         "<= 64 MB in all): the radiance sum of that step's samples, re-rendered on a cleared sum after the clock has stopped "
+                         "(see dump_outputs); the inputs are seeded, so two builds can be compared file for file")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs: a dry run renders nothing")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -146,6 +158,19 @@ def self_launch(args):
     for l in lines:
         print(l, flush=True)
     return run.returncode
+
+
+def ensure_built():
+    """__graft_entry__.build() where this user can write the tree: it brings stale native libraries up to date, and it takes its lock
+    file in the tree.  A tree this user cannot write (a checkout built beforehand by its owner) is measured as it was built; the
+    import fails loudly when libcrt.so is missing there."""
+    import __graft_entry__ as g
+    lock = os.path.join(ROOT, ".build.lock")
+    if os.access(ROOT, os.W_OK) and (not os.path.exists(lock) or os.access(lock, os.W_OK)):
+        g.build()
+    else:
+        log(f"[bench] {ROOT} is read-only for this user: measuring the libraries as built")
+    import caitlynrenderer_amd  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ workloads
@@ -356,10 +381,35 @@ def live_pmc(workloads, budget_s=330.0):
         shutil.rmtree(top, ignore_errors=True)
 
 
-def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials=None, device_built=None, accel=None, sbvh_flags=0):
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_SAMPLE_PIXELS = 1 << 21         # pixels kept (fixed seed) when the whole frame would exceed the limit: 2 Mi x (12 + 8) bytes = 42 MB
+
+
+def dump_outputs(dirpath, frame):
+    """--dump-outputs: `frame` is the (H, W, 3) float32 radiance sum of the last timed step's samples, what crt_read_sum hands a
+    caller.  Written whole as radiance_sum.npy when it fits DUMP_LIMIT_BYTES; a larger frame is reduced to a fixed sample of
+    DUMP_SAMPLE_PIXELS pixels (numpy seed 0, the same for every run of the same resolution): radiance_sum_sample.npy (n, 3) float32
+    and radiance_sum_sample_pixel.npy (n,) float64, the row-major pixel index of each row.  Returns {file name: shape}."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    H, W, _ = frame.shape
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        files = {"radiance_sum": np.ascontiguousarray(frame, np.float32)}
+    else:
+        pix = np.sort(np.random.default_rng(0).choice(H * W, DUMP_SAMPLE_PIXELS, replace=False))
+        files = {"radiance_sum_sample": np.ascontiguousarray(frame.reshape(H * W, 3)[pix], np.float32),
+                 "radiance_sum_sample_pixel": pix.astype(np.float64)}
+    assert sum(a.nbytes for a in files.values()) <= DUMP_LIMIT_BYTES
+    for k, a in files.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+    return {k + ".npy": list(a.shape) for k, a in files.items()}
+
+
+def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials=None, device_built=None, accel=None, sbvh_flags=0, dump_dir=None):
     """Measure one workload: returns the dict of the bench line for it (rank 0) or None (other ranks).
     device_built = "lbvh" | "ploc<r>" | "sah": the scene is built by crt_scene_create itself from the source-order arrays
-    (BVH2, CWBVH and records produced in HBM) instead of from host-built trees."""
+    (BVH2, CWBVH and records produced in HBM) instead of from host-built trees.
+    dump_dir: after everything measured, the last timed step once more on a cleared sum, written there by dump_outputs."""
     import numpy as np
     import caitlynrenderer_amd as cr
     from caitlynrenderer_amd import tiles
@@ -624,6 +674,22 @@ def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials
             out["sum_rows_match_oracle"] = rows_match_oracle(scene, step, Wu, spp, rvs, data, name, device_built, materials or args.materials, cam, W, H, depth, accel)
         if cpu_base and not args.no_cpu_baseline and accel == "cwbvh":
             out["cpu_baseline"] = cpu_baseline(data, cam, W, H, depth, rvs[1 + Wu * spp:1 + (Wu + 1) * spp], cs)
+    if takes_part and dump_dir:
+        # what the last timed step computed: its frames once more, exactly as the timed region ran them, on a cleared sum (the sum at the
+        # end of the timed region also holds the settle frames, and how many of those ran depends on the wall clock)
+        scene.set_option("timing", 0)
+        scene.reset()
+        step(Wu + K - 1)
+        scene.sync()
+        if use_dist:
+            read_back()
+            torch.cuda.synchronize()
+            frame = tiles.untile_gathered(recv.view(world, -1).cpu().numpy(), W, H, tile, world) if rank == 0 else None
+        else:
+            frame = scene.read_sum()
+        if ctx.rank == 0:
+            out["outputs"] = {"dir": dump_dir, "files": dump_outputs(dump_dir, frame),
+                              "what": f"radiance sum of timed step {K} of {K} (frames {1 + (Wu + K - 1) * spp}..{(Wu + K) * spp} of the seeded sequence)"}
     if takes_part:
         scene.close()
     return out
@@ -867,8 +933,7 @@ def main():
         os.environ.setdefault("CRT_BUILD_THREADS", str(max(1, (os.cpu_count() or 8) // max(1, local_world))))
     ctx.init()
     if not args.dry_run:
-        import __graft_entry__ as g
-        g.build()
+        ensure_built()
 
     N = len(ctx.one_proc_ids) if ctx.one_proc_ids else ctx.world
     auto = args.workload == "auto"
@@ -894,7 +959,8 @@ def main():
     else:
         if N > 1 and args.builder == "auto" and not args.device_built and name != "cornell":
             args.device_built = "sah"          # every rank's crt_scene_create builds the tree on its own GPU: no host SBVH build in the N > 1 path
-        head = run_block(ctx, name, W, H, args.depth, spp, True, N == 1 and not args.device_built, scaling, device_built=args.device_built)
+        head = run_block(ctx, name, W, H, args.depth, spp, True, N == 1 and not args.device_built, scaling, device_built=args.device_built,
+                         dump_dir=args.dump_outputs)
         extra = {}
         if auto and not args.no_extra and args.accel == "cwbvh":
             if N == 1:
@@ -929,7 +995,7 @@ def main():
         out = {"metric": METRIC.replace("1920x1080", f"{W}x{H}"), "value": head["value"], "unit": head["unit"], "n_gpus": N, "steps": args.steps,
                "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": head["scaling"],
                "vs_baseline": None, "dtype": "f32", "data": "synthetic", "config": head["config"], "roofline": head["roofline"]}
-        for k in ("step_ms_spread", "cpu_baseline", "gather_ms", "rank_device_ms_per_step", "sum_rows_match_oracle", "collective"):
+        for k in ("step_ms_spread", "cpu_baseline", "gather_ms", "rank_device_ms_per_step", "sum_rows_match_oracle", "collective", "outputs"):
             if k in head:
                 out[k] = head[k]
         if head.get("dry_run"):

@@ -9,7 +9,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference"
 
 
 def pytest_configure(config):
@@ -50,7 +49,7 @@ def vectors():
 
 
 class _Cam:
-    """crt_camera rebuilt from the fixture (no /root/reference on the GPU box)."""
+    """crt_camera rebuilt from the fixture."""
 
     def __init__(self, cr, d):
         from caitlynrenderer_amd._lib import crt_camera
@@ -146,14 +145,9 @@ def numpy_brute_force(mesh, rays):
     return tri, tt, uu, vv
 
 
-def have_reference():
-    return os.path.isdir(os.path.join(REFERENCE, "Models"))
-
-
 def write_obj(mesh, path, mtl_name="scene.mtl", map_kd=None):
     """Write a Mesh back as OBJ + MTL text (v//vn faces, or v/vt/vn when the mesh has texcoords; %.9g so every
-    float32 survives the round trip); lets the C++ example and the loader tests run on the GPU box, where
-    /root/reference does not exist.  map_kd: {material index: texture file name} -> `map_Kd` lines."""
+    float32 survives the round trip); lets the C++ example and the loader tests read scenes as OBJ files.  map_kd: {material index: texture file name} -> `map_Kd` lines."""
     import os
     lines = [f"mtllib {mtl_name}"]
     for v in mesh.vertices + mesh.vertex_min:

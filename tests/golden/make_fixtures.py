@@ -1,5 +1,5 @@
-"""Regenerates the committed fixtures under tests/golden/.  Run in the BUILD container only
-(it reads /root/reference/Models/cornell-box.obj, which does not exist on the GPU box):
+"""Regenerates the committed fixtures under tests/golden/ from tests/golden/cornell-box.obj (+ .mtl), the reference's own
+Models/cornell-box data files stored as fixtures:
 
     python tests/golden/make_fixtures.py
 
@@ -29,7 +29,7 @@ import caitlynrenderer_amd as cr                                  # noqa: E402
 from caitlynrenderer_amd.meshgen import tessellated_cornell       # noqa: E402
 from oracle import binding as ob                                  # noqa: E402
 
-REF_OBJ = "/root/reference/Models/cornell-box.obj"
+REF_OBJ = os.path.join(HERE, "cornell-box.obj")
 CAM_POS, CAM_LOOK, CAM_FOV = (-2.755610, 2.745992, 7.58545), (-2.755610, 2.745992, 6.58545), 40.0   # Scene.h:468
 
 

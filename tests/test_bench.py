@@ -89,3 +89,59 @@ def test_without_a_gpu_the_real_bench_refuses():
         pytest.skip("GPU present")
     run = _run(["--steps", "1", "--warmup", "0"])
     assert run.returncode != 0 and "needs a GPU" in run.stderr and run.stdout.strip() == ""
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("crt_bench_dump", BENCH)
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: a frame that fits 64 MB is written whole (float32); a larger one as the same seeded pixel sample every time, with
+    its pixel indices (float64), still within 64 MB in all."""
+    import numpy as np
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    small = rng.random((1080, 1920, 3), dtype=np.float32)
+    assert bench.dump_outputs(str(tmp_path / "a"), small) == {"radiance_sum.npy": [1080, 1920, 3]}
+    got = np.load(tmp_path / "a" / "radiance_sum.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = rng.random((2160, 3840, 3), dtype=np.float32)
+    files = {}
+    for d in ("b", "c"):
+        files[d] = bench.dump_outputs(str(tmp_path / d), big)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 64 * 10 ** 6
+    assert files["b"] == files["c"] == {"radiance_sum_sample.npy": [1 << 21, 3], "radiance_sum_sample_pixel.npy": [1 << 21]}
+    vals, pix = np.load(tmp_path / "b" / "radiance_sum_sample.npy"), np.load(tmp_path / "b" / "radiance_sum_sample_pixel.npy")
+    assert vals.dtype == np.float32 and pix.dtype == np.float64
+    assert np.array_equal(pix, np.load(tmp_path / "c" / "radiance_sum_sample_pixel.npy")) and np.all(np.diff(pix) > 0)
+    assert np.array_equal(vals, big.reshape(-1, 3)[pix.astype(np.int64)])
+
+
+def test_steps_below_one_are_refused(tmp_path):
+    run = _run(["--steps", "0", "--dry-run"], cwd=str(tmp_path))
+    assert run.returncode != 0 and "--steps" in run.stderr and run.stdout.strip() == ""
+
+
+def test_a_built_tree_this_user_cannot_write_is_measured_as_built(tmp_path):
+    """A checkout built beforehand by its owner and read by another user: bench.py loads the libraries as they were built instead of
+    failing in build() (which takes its lock file in the tree), and writes nothing there."""
+    import shutil
+    if os.geteuid() == 0:
+        pytest.skip("root writes through missing write permissions")
+    tree = tmp_path / "tree"
+    shutil.copytree(ROOT, tree, ignore=shutil.ignore_patterns(".git", "__pycache__", ".build.lock"))
+    dirs = [dp for dp, _, _ in os.walk(tree)]
+    for dp in dirs:
+        os.chmod(dp, 0o555)
+    try:
+        run = subprocess.run([sys.executable, "-c", "import bench; bench.ensure_built(); print('loaded')"], cwd=str(tree),
+                             capture_output=True, text=True, timeout=300)
+        assert run.returncode == 0 and run.stdout.strip() == "loaded", run.stderr[-3000:]
+        assert "read-only" in run.stderr and not (tree / ".build.lock").exists()
+    finally:
+        for dp in dirs:
+            os.chmod(dp, 0o755)

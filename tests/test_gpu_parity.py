@@ -2128,6 +2128,40 @@ def test_bench_one_process_several_devices(tmp_path):
     assert d["roofline"]["counters"]["primary_rays"] == 4 * 3840 * 2160         # the counters describe one STEP: 4 samples of every pixel
 
 
+def test_bench_dump_outputs_hold_the_last_timed_step(ob, tmp_path):
+    """`bench.py --dump-outputs DIR`: radiance_sum.npy is the sum of the LAST timed step's samples (frames 1 + (W + K - 1) spp .. (W + K) spp
+    of the seeded sequence), equal to the oracle's sum of the same frames on the same tree; --steps sets the timed steps."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+    import caitlynrenderer_amd as cr
+    from conftest import ROOT
+    W, H, K, Wu, spp = 320, 180, 3, 1, 4
+    out_dir = tmp_path / "dump"
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "mesh8", "--resolution", f"{W}x{H}",
+                          "--steps", str(K), "--warmup", str(Wu), "--spp", str(spp), "--no-cpu-baseline", "--settle-ms", "0",
+                          "--dump-outputs", str(out_dir)], capture_output=True, text=True, cwd=str(tmp_path), timeout=600)
+    assert run.returncode == 0, run.stderr[-2000:]
+    d = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == K and d["ms_per_step"] > 0 and d["outputs"]["files"] == {"radiance_sum.npy": [H, W, 3]}
+    got = np.load(out_dir / "radiance_sum.npy")
+    assert got.dtype == np.float32 and got.shape == (H, W, 3)
+    spec = importlib.util.spec_from_file_location("crt_bench_t", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    data, cam, _, _ = bench.build_workload("mesh8")                     # the bench's own scene and camera
+    rnd = cr.Rnd()
+    rvs = [(rnd.randf2(), rnd.randf2()) for _ in range((Wu + K) * spp + 1)]
+    orc = ob.Oracle(data, W, H, 1, cam)
+    ref = np.zeros((H, W, 3), np.float32)
+    for rx, ry in rvs[1 + (Wu + K - 1) * spp:1 + (Wu + K) * spp]:
+        orc.render_frame(rx, ry, ref)
+    err = np.abs(got - ref)
+    assert ref.max() > 0 and (err <= 1e-5 + 1e-4 * np.abs(ref)).all(), err.max()
+
+
 def test_short_reciprocal_and_square_root_are_exact_on_every_float(tmp_path):
     """rt_math.hpp computes 1 / x as v_rcp_f32 + one Newton step and sqrt(x) as v_rsq_f32 + one Newton step for 2^-100 <= |x| <= 2^100 and says
     the bits are those of the IEEE division / sqrtf the floating-point contract asks for.  A float has 2^32 values: the two

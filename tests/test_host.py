@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE, ROOT, have_reference
+from conftest import GOLDEN, ROOT
 
 
 def test_host_rng_known_answers(cr, ob, survey):
@@ -67,10 +67,10 @@ def test_camera_matches_reference_construction(cr, survey):
     np.testing.assert_allclose(M @ M.T, np.eye(3), atol=1e-6)
 
 
-@pytest.mark.skipif(not have_reference(), reason="reference data files only exist in the build container")
 def test_loader_on_reference_cornell(cr, survey, cornell):
+    """tests/golden/cornell-box.obj (+ .mtl): the reference's own Models/cornell-box data files, stored as fixtures."""
     cam = cr.Camera((-2.755610, 2.745992, 7.58545), (-2.755610, 2.745992, 6.58545), 40.0)
-    m = cr.Mesh.read_object(os.path.join(REFERENCE, "Models", "cornell-box.obj"), cam)
+    m = cr.Mesh.read_object(os.path.join(GOLDEN, "cornell-box.obj"), cam)
     ka = survey["cornell_load"]
     assert (m.vertices.shape[0], m.normals.shape[0], m.triangles.shape[0], m.materials.shape[0], m.lights.shape[0]) == \
         (ka["counts"]["vertices"], ka["counts"]["normals"], ka["counts"]["triangles"], ka["counts"]["materials"], ka["counts"]["lights"])
