@@ -83,6 +83,10 @@ SYMBOLS = {
     "crt_trace_device": (_I, [_P, _P, _SZ, _P, _I, _P, _I]),
     "crt_resolve_device": (_I, [_P, C.c_float, C.POINTER(C.c_void_p), _I]),
     "crt_get_launch_times": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
+    "crt_update_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
+    "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),
+    "crt_last_update_ms": (_I, [_P, C.POINTER(_F), C.POINTER(_F)]),
+    "crt_debug_read_accel": (_I, [_P, _I, _P, _SZ, C.POINTER(_SZ)]),
     "crt_debug_read_queue": (_I, [_P, _I, _U32, _P, _SZ, C.POINTER(_SZ)]),
     "crt_debug_time_graph": (_I, [_P, _U32, _P, _U32, C.POINTER(_F), C.POINTER(_F)]),
     "crt_debug_launch_form": (_I, [_P, C.POINTER(C.c_int32)]),
@@ -122,6 +126,8 @@ SYMBOLS = {
     "crt_cwbvh_child_bvh2": (_P, [_P]),
     "crt_cwbvh_depth": (_U32, [_P]),
     "crt_cwbvh_free": (None, [_P]),
+    "crt_bvh2_refit": (_I, [_P, _SZ, _P, _SZ, _P, _SZ]),
+    "crt_cwbvh_refit": (_I, [_P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_load_obj": (_I, [C.c_char_p, C.POINTER(_F), C.POINTER(_P)]),
     "crt_mesh_counts": (_SZ, [_P] + [C.POINTER(_SZ)] * 6),
     "crt_mesh_vertices": (_P, [_P]),

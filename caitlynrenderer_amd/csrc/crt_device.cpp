@@ -73,6 +73,32 @@ uint32_t morton2(uint32_t x, uint32_t y) {
 
 }  // namespace
 
+// What crt_update_vertices keeps between updates, allocated by a scene's first update: a scene that never updates holds none of it.
+struct RefitState {
+    int device = 0;
+    float* d_verts = nullptr;                // the host form's upload of the positions
+    uint32_t* d_check = nullptr;             // k_check_vertices: non-finite flag, max keys, complemented min keys
+    uint32_t* h_check = nullptr;             // pinned
+    uint32_t* d_order8 = nullptr;            // node8 indices level by level, root level first; level8[l] = first entry of level l (+ end)
+    uint32_t* d_order2 = nullptr;            // the same for the BVH2
+    std::vector<uint32_t> level8, level2;
+    float* d_box8 = nullptr;                 // the float box of every node8 (6 floats), which its parent's slot reads
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    std::vector<hipEvent_t> ev_peer;         // per peer, on its device: "the peer's stream is done with the old scene"
+    bool have_times = false, times_pending = false;
+    float device_ms = 0.f, wall_ms = 0.f;
+    ~RefitState() {
+        (void)hipSetDevice(device);
+        void* ptrs[] = {d_verts, d_check, d_order8, d_order2, d_box8};
+        for (void* p : ptrs) if (p) (void)hipFree(p);
+        if (h_check) (void)hipHostFree(h_check);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+        for (hipEvent_t e : ev_peer) if (e) (void)hipEventDestroy(e);
+        (void)hipSetDevice(device);
+    }
+};
+
 struct crt_scene {
     int device = 0;
     int n_cu = 256;
@@ -94,6 +120,8 @@ struct crt_scene {
     float4* d_bvh2 = nullptr;            // FlatNode array as uploaded by the reference (only when desc.bvh was given)
     float4* d_tris2 = nullptr;           // intersection records in BVH2 leaf-slot order
     uint32_t bvh2_stack = 0;             // BVH2 depth + 2
+    size_t n_vertices = 0, n_normals = 0, n_slots = 0;   // as created (n_slots: the leaf-order triangle array); crt_update_vertices checks against them
+    RefitState* refit = nullptr;         // crt_update_vertices' state, from the first update on
 
     // shard + frame buffers
     uint32_t rank = 0, world = 1, tile = 16;   // 16x16: four waves per tile — fine enough for the cost-sorted schedule (1 M triangles: 0.273 ms at 64, 0.257 at 16)
@@ -267,6 +295,7 @@ struct crt_scene {
         drop_peers();
         hipSetDevice(device);
         if (stream) hipStreamSynchronize(stream);
+        delete refit;
         if (shares_scene)                    // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
@@ -495,6 +524,7 @@ static int init_scene_common(crt_scene* s, const crt_scene_desc* d) {
     if (const char* e = std::getenv("CRT_TIMING")) s->timing = (uint32_t)std::max(0, std::atoi(e));
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return (fail(CRT_ERR_HIP, "hipStreamCreate failed"));
     s->width = d->width; s->height = d->height; s->max_depth = d->max_depth; s->n_lights = (uint32_t)d->n_lights;
+    s->n_vertices = d->n_vertices; s->n_normals = d->n_normals; s->n_slots = d->n_triangles;
     if (d->n_vertices) {
         for (int k = 0; k < 3; ++k) s->bounds_lo[k] = s->bounds_hi[k] = d->vertices[k];
         for (size_t i = 1; i < d->n_vertices; ++i)
@@ -2264,6 +2294,233 @@ int crt_trace(crt_scene* s, const crt_ray* rays, size_t n, crt_hit* hits, int mo
     HIPCHK(hipMemcpyAsync(hits, s->d_t_hits, n * sizeof(crt_hit), hipMemcpyDeviceToHost, s->stream));
     if (stats) HIPCHK(hipMemcpyAsync(stats, s->d_t_stats, n * sizeof(crt_ray_stats), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- crt_update_vertices --
+// New positions for an unchanged topology: the CWBVH (node8 boxes re-quantised), the BVH2 and the records of both walks are refitted in
+// place on the scene's device (refit.hip), one launch per tree level, deepest first.  The frame path reads none of the state kept for
+// this, and a scene that never updates allocates none of it.
+
+// the node indices of a tree level by level (root level first): parent links and depths on the device, the counting sort on the host.
+// Once per scene, at its first update.
+static int discover_levels(crt_scene* s, bool node8, uint32_t n, uint32_t** d_order, std::vector<uint32_t>& level) {
+    int32_t* d_parent = nullptr;
+    uint8_t* d_depth = nullptr;
+    struct Guard { void* a; void* b; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } g{nullptr, nullptr};
+    int rc;
+    if ((rc = dev_alloc(&d_parent, n))) return rc;
+    g.a = d_parent;
+    if ((rc = dev_alloc(&d_depth, n))) return rc;
+    g.b = d_depth;
+    HIPCHK(hipMemsetAsync(d_parent, 0xff, (size_t)n * sizeof(int32_t), s->stream));
+    if (node8) crt::launch_node8_parents(s->d_nodes, (uint32_t)CRT_NODE_ROWS, n, d_parent, s->stream);
+    else       crt::launch_bvh2_parents(s->d_bvh2, n, d_parent, s->stream);
+    crt::launch_depths(d_parent, n, d_depth, s->stream);
+    std::vector<uint8_t> depth(n);
+    HIPCHK(hipMemcpyAsync(depth.data(), d_depth, n, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    std::vector<uint32_t> count(257, 0);
+    for (uint32_t i = 0; i < n; ++i) ++count[depth[i] + 1u];
+    uint32_t levels = 0;
+    for (uint32_t d = 0; d < 256; ++d) if (count[d + 1]) levels = d + 1;
+    level.assign(levels + 1, 0);
+    for (uint32_t d = 0; d < levels; ++d) level[d + 1] = level[d] + count[d + 1];
+    std::vector<uint32_t> order(n), cursor(level.begin(), level.end() - 1);
+    for (uint32_t i = 0; i < n; ++i) order[cursor[depth[i]]++] = i;
+    if ((rc = dev_alloc(d_order, n))) return rc;
+    HIPCHK(hipMemcpy(*d_order, order.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return CRT_OK;
+}
+
+static int ensure_refit_state(crt_scene* s) {
+    if (s->refit) return CRT_OK;
+    std::unique_ptr<RefitState> owner(new (std::nothrow) RefitState);
+    RefitState* r = owner.get();
+    if (!r) return fail(CRT_ERR_NOMEM, "crt_update_vertices: out of memory");
+    r->device = s->device;
+    int rc;
+    if ((rc = dev_alloc(&r->d_check, 8))) return rc;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_check), 8 * sizeof(uint32_t)));
+    HIPCHK(hipEventCreate(&r->ev_a));
+    HIPCHK(hipEventCreate(&r->ev_b));
+    if ((rc = dev_alloc(&r->d_box8, 6 * (size_t)s->info.n_nodes8))) return rc;
+    if ((rc = discover_levels(s, true, (uint32_t)s->info.n_nodes8, &r->d_order8, r->level8))) return rc;
+    if (s->d_bvh2 && (rc = discover_levels(s, false, (uint32_t)s->info.n_bvh2_nodes, &r->d_order2, r->level2))) return rc;
+    s->refit = owner.release();
+    return CRT_OK;
+}
+
+static size_t scene_buf_bytes(const crt_scene* s, const void* member) {
+    const size_t off = (size_t)(reinterpret_cast<const char*>(member) - reinterpret_cast<const char*>(s));
+    for (const auto& b : s->scene_bufs) if (b.first == off) return b.second;
+    return 0;
+}
+
+static float key_to_float(uint32_t key) {
+    const uint32_t b = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+}
+
+// d_verts: device positions (the scene's own upload or the caller's); normals / lights: host arrays or null
+static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, size_t n_vertices, const float* normals, size_t n_normals,
+                       const crt_light* lights, size_t n_lights, int sync) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!s || (!h_verts && !d_user)) return fail(CRT_ERR_INVALID, "crt_update_vertices: null argument");
+    if (s->primary) return fail(CRT_ERR_INVALID, "crt_update_vertices: not on a replica");
+    if (n_vertices != s->n_vertices) return fail(CRT_ERR_INVALID, "crt_update_vertices: n_vertices differs from the count given at create");
+    if (normals && n_normals != s->n_normals) return fail(CRT_ERR_INVALID, "crt_update_vertices: n_normals differs from the count given at create");
+    if (lights && n_lights != s->n_lights) return fail(CRT_ERR_INVALID, "crt_update_vertices: n_lights differs from the count given at create");
+    if (normals)
+        for (size_t i = 0; i < 3 * n_normals; ++i)
+            if (!std::isfinite(normals[i])) return fail(CRT_ERR_INVALID, "crt_update_vertices: a normal is not finite");
+    HIPCHK(hipSetDevice(s->device));
+    int rc = ensure_refit_state(s);
+    if (rc) return rc;
+    RefitState* r = s->refit;
+    hipStream_t st = s->stream;
+    const uint32_t nv = (uint32_t)n_vertices;
+    const float* verts = d_user;
+    if (h_verts) {
+        if (!r->d_verts && (rc = dev_alloc(&r->d_verts, 3 * n_vertices))) return rc;
+        HIPCHK(hipMemcpyAsync(r->d_verts, h_verts, 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice, st));
+        verts = r->d_verts;
+    }
+    // validation before anything is written: the one host wait of the call
+    HIPCHK(hipMemsetAsync(r->d_check, 0, 8 * sizeof(uint32_t), st));
+    crt::launch_check_vertices(verts, nv, r->d_check, st);
+    HIPCHK(hipMemcpyAsync(r->h_check, r->d_check, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (r->h_check[0]) return fail(CRT_ERR_INVALID, "crt_update_vertices: a vertex coordinate is not finite or exceeds 1e18");
+
+    // every stream that reads the scene's buffers is done with the old scene before they change (its own stream is, by order)
+    r->ev_peer.resize(s->peers.size(), nullptr);
+    for (size_t k = 0; k < s->peers.size(); ++k) {
+        crt_scene* p = s->peers[k];
+        HIPCHK(hipSetDevice(p->device));
+        if (!r->ev_peer[k]) HIPCHK(hipEventCreateWithFlags(&r->ev_peer[k], hipEventDisableTiming));
+        HIPCHK(hipEventRecord(r->ev_peer[k], p->stream));
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(hipStreamWaitEvent(st, r->ev_peer[k], 0));
+    }
+    if (normals && n_normals) HIPCHK(hipMemcpyAsync(s->d_normals, normals, 3 * n_normals * sizeof(float), hipMemcpyHostToDevice, st));
+    if (lights && n_lights) HIPCHK(hipMemcpyAsync(s->d_lights, lights, n_lights * sizeof(crt_light), hipMemcpyHostToDevice, st));
+
+    HIPCHK(hipEventRecord(r->ev_a, st));
+    const uint32_t n8 = (uint32_t)s->info.n_nodes8, n_tris8 = (uint32_t)s->info.n_tris8, n_slots = (uint32_t)s->n_slots;
+    crt::launch_refit_records(s->d_tris, (uint32_t)CRT_TRI_ROWS, n_tris8, s->d_triangles, n_slots, verts, 0, st);
+    if (s->d_tris2) crt::launch_refit_records(s->d_tris2, 3u, n_slots, s->d_triangles, n_slots, verts, 1, st);
+    if (s->d_bvh2)
+        for (size_t l = r->level2.size() - 1; l-- > 0;)
+            crt::launch_refit_bvh2_level(s->d_bvh2, (uint32_t)s->info.n_bvh2_nodes, r->d_order2 + r->level2[l], r->level2[l + 1] - r->level2[l],
+                                         s->d_triangles, n_slots, verts, st);
+    for (size_t l = r->level8.size() - 1; l-- > 0;)
+        crt::launch_refit_node8_level(s->d_nodes, (uint32_t)CRT_NODE_ROWS, n8, r->d_order8 + r->level8[l], r->level8[l + 1] - r->level8[l], s->d_tris,
+                                      (uint32_t)CRT_TRI_ROWS, n_tris8, s->d_triangles, n_slots, verts, r->d_box8, st);
+    if (s->d_planes) crt::launch_expand_planes(s->d_nodes, (uint32_t)CRT_NODE_ROWS, s->d_planes, n8, st);
+    if (hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, "crt_update_vertices: refit launch failed");
+    HIPCHK(hipEventRecord(r->ev_b, st));
+
+    // the new bounds (ray_bins / sort_shadow cell grid), a new tile-cost measurement, and the sum cleared as crt_reset does
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) { hi[k] = key_to_float(r->h_check[1 + k]); lo[k] = key_to_float(~r->h_check[4 + k]); }
+    auto refresh = [&](crt_scene* x) -> int {
+        for (int k = 0; k < 3; ++k) { x->bounds_lo[k] = lo[k]; x->bounds_hi[k] = hi[k]; }
+        x->tile_state = crt_scene::TILES_WANT;
+        const int erc = ensure_frame(x);
+        if (erc) return erc;
+        HIPCHK(hipMemsetAsync(x->d_sum, 0, 3 * (size_t)std::max<uint32_t>(x->n_local_pixels, 1) * sizeof(float), x->stream));
+        return CRT_OK;
+    };
+    if ((rc = refresh(s))) return rc;
+    // replicas: on this GPU they share the refitted buffers and only wait for them; on another GPU they receive them by peer copy
+    for (crt_scene* p : s->peers) {
+        HIPCHK(hipSetDevice(p->device));
+        HIPCHK(hipStreamWaitEvent(p->stream, r->ev_b, 0));
+        if (!p->shares_scene) {
+            void* const* bufs[] = {(void* const*)&s->d_nodes, (void* const*)&s->d_tris, (void* const*)&s->d_tris2, (void* const*)&s->d_bvh2,
+                                   (void* const*)&s->d_normals, (void* const*)&s->d_lights};
+            for (void* const* b : bufs) {
+                const size_t off = (size_t)(reinterpret_cast<const char*>(b) - reinterpret_cast<const char*>(s));
+                void* dst = *reinterpret_cast<void**>(reinterpret_cast<char*>(p) + off);
+                const size_t bytes = scene_buf_bytes(s, b);
+                if (*b && dst && bytes) HIPCHK(hipMemcpyPeerAsync(dst, p->device, *b, s->device, bytes, p->stream));
+            }
+            if (p->d_planes) crt::launch_expand_planes(p->d_nodes, (uint32_t)CRT_NODE_ROWS, p->d_planes, n8, p->stream);
+        }
+        if ((rc = refresh(p))) { (void)hipSetDevice(s->device); return rc; }
+    }
+    HIPCHK(hipSetDevice(s->device));
+    r->have_times = true;
+    r->times_pending = true;
+    if (sync) {
+        HIPCHK(hipStreamSynchronize(st));
+        for (crt_scene* p : s->peers) { HIPCHK(hipSetDevice(p->device)); HIPCHK(hipStreamSynchronize(p->stream)); }
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(hipEventElapsedTime(&r->device_ms, r->ev_a, r->ev_b));
+        r->times_pending = false;
+    }
+    r->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return CRT_OK;
+}
+
+extern "C" {
+
+int crt_update_vertices(crt_scene* s, const float* vertices, size_t n_vertices, const float* normals, size_t n_normals, const crt_light* lights,
+                        size_t n_lights) {
+    if (!vertices) return fail(CRT_ERR_INVALID, "crt_update_vertices: null vertices");
+    try {
+        return update_impl(s, vertices, nullptr, n_vertices, normals, n_normals, lights, n_lights, 1);
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_update_vertices: ") + e.what());
+    }
+}
+
+int crt_update_vertices_device(crt_scene* s, const void* d_vertices, size_t n_vertices, int sync) {
+    if (!d_vertices) return fail(CRT_ERR_INVALID, "crt_update_vertices_device: null vertices");
+    try {
+        return update_impl(s, nullptr, static_cast<const float*>(d_vertices), n_vertices, nullptr, 0, nullptr, 0, sync);
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_update_vertices_device: ") + e.what());
+    }
+}
+
+int crt_last_update_ms(crt_scene* s, float* device_ms, float* wall_ms) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_last_update_ms: null scene");
+    RefitState* r = s->refit;
+    if (!r || !r->have_times) return fail(CRT_ERR_INVALID, "crt_last_update_ms: no update yet");
+    if (r->times_pending) {
+        HIPCHK(hipSetDevice(s->device));
+        HIPCHK(hipEventSynchronize(r->ev_b));
+        HIPCHK(hipEventElapsedTime(&r->device_ms, r->ev_a, r->ev_b));
+        r->times_pending = false;
+    }
+    if (device_ms) *device_ms = r->device_ms;
+    if (wall_ms) *wall_ms = r->wall_ms;
+    return CRT_OK;
+}
+
+int crt_debug_read_accel(crt_scene* s, int which, void* dst, size_t cap_bytes, size_t* n_out) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_debug_read_accel: null scene");
+    const void* src = nullptr;
+    size_t n = 0, item = 0, pitch = 0;
+    switch (which) {
+        case 0: src = s->d_nodes; n = s->info.n_nodes8; item = sizeof(crt_node8); pitch = (size_t)CRT_NODE_ROWS * 16; break;
+        case 1: src = s->d_tris; n = s->info.n_tris8; item = 48; pitch = (size_t)CRT_TRI_ROWS * 16; break;
+        case 2: src = s->d_bvh2; n = src ? s->info.n_bvh2_nodes : 0; item = sizeof(crt_flatnode); pitch = item; break;
+        case 3: src = s->d_tris2; n = src ? s->n_slots : 0; item = 48; pitch = item; break;
+        default: return fail(CRT_ERR_INVALID, "crt_debug_read_accel: which must be 0..3");
+    }
+    if (n_out) *n_out = n;
+    if (!dst || n == 0) return CRT_OK;
+    if (cap_bytes < n * item) return fail(CRT_ERR_INVALID, "crt_debug_read_accel: destination too small");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy2D(dst, item, src, pitch, item, n, hipMemcpyDeviceToHost));
     return CRT_OK;
 }
 

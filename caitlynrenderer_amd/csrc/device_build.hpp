@@ -71,6 +71,24 @@ void launch_gather_slots(const crt_triangle* d_in, const uint32_t* d_tri_order, 
 void launch_gather_records(const crt_triangle* d_in, const uint32_t* d_tri_order, const int32_t* d_tri_slots, const float* d_verts, uint32_t n_tris8,
                            float4* d_recs, hipStream_t stream);
 
+// ---- refit of a scene's trees and records to new vertex positions (refit.hip, crt_update_vertices) ----
+// d_out[0] |= 1 when a coordinate is not finite or exceeds 1e18; d_out[1..3] = ordered keys of the max x, y, z; d_out[4..6] = the
+// complements of the min keys.  d_out (7 words) must be zeroed before the launch.
+void launch_check_vertices(const float* d_verts, uint32_t n_vertices, uint32_t* d_out, hipStream_t stream);
+// level discovery: parent links (d_parent preset to -1) and the depth of every node (root 0)
+void launch_node8_parents(const void* d_nodes, uint32_t node_rows, uint32_t n8, int32_t* d_parent, hipStream_t stream);
+void launch_bvh2_parents(const void* d_flat, uint32_t n2, int32_t* d_parent, hipStream_t stream);
+void launch_depths(const int32_t* d_parent, uint32_t n, uint8_t* d_depth, hipStream_t stream);
+// records at `rows` float4 per item, regathered in place (slot in e1.w, or record i = slot i when slot_order) from the leaf-order triangles
+void launch_refit_records(void* d_recs, uint32_t rows, uint32_t n, const void* d_tris, uint32_t n_slots, const float* d_verts, int slot_order,
+                          hipStream_t stream);
+// one level of each tree (d_order: its node indices); call deepest level first.  d_box8: 6 floats per node8, the float box the parent reads
+void launch_refit_bvh2_level(void* d_flat, uint32_t n2, const uint32_t* d_order, uint32_t count, const void* d_tris, uint32_t n_slots,
+                             const float* d_verts, hipStream_t stream);
+void launch_refit_node8_level(void* d_nodes, uint32_t node_rows, uint32_t n8, const uint32_t* d_order, uint32_t count, const void* d_recs,
+                              uint32_t tri_rows, uint32_t n_tris8, const void* d_tris, uint32_t n_slots, const float* d_verts, float* d_box8,
+                              hipStream_t stream);
+
 // ---- code-object warm-up (crt_warmup) ----
 // HIP loads a code object the first time one of its kernels is looked up; each of these asks for the attributes of its
 // translation unit's kernels, which loads that unit's code object on the current device (~ms each) without launching anything.

@@ -177,6 +177,13 @@ class SBVH:
     def count_leaf(self):
         return int((self.flat_nodes[:, 7] != 0).sum())
 
+    def refit(self, vertices):
+        """crt_bvh2_refit: new boxes for new vertex positions (same count and triangles), topology unchanged; updates flat_nodes in place."""
+        verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        check(lib().crt_bvh2_refit(_ptr(self.flat_nodes), self.flat_nodes.shape[0], _ptr(self.triangles), self.triangles.shape[0],
+                                   _ptr(verts), verts.shape[0]))
+        return self
+
     def depth(self):
         """Deepest leaf level, root = 0 (children follow parents in BFS order)."""
         n = self.flat_nodes.shape[0]
@@ -223,4 +230,13 @@ class CWBVH:
             self.depth = int(L.crt_cwbvh_depth(h))
         finally:
             L.crt_cwbvh_free(h)
+        return self
+
+    def refit(self, leaf_triangles, vertices):
+        """crt_cwbvh_refit: the node8 boxes re-quantised for new vertex positions; leaf_triangles = the BVH2's leaf-order triangles
+        (SBVH.triangles).  Updates nodes in place; meta, imask and the base indices stay."""
+        tris = np.ascontiguousarray(leaf_triangles, dtype=np.int32).reshape(-1, 12)
+        verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        check(lib().crt_cwbvh_refit(_ptr(self.nodes), self.nodes.shape[0], _ptr(self.tri_slots), self.tri_slots.shape[0], _ptr(tris),
+                                    tris.shape[0], _ptr(verts), verts.shape[0]))
         return self

@@ -30,7 +30,7 @@ def pcg_hash_np(x):
     return (((word >> np.uint64(22)) ^ word) & m).astype(np.uint32)
 
 
-def tessellated_cornell(base, n):
+def tessellated_cornell(base, n, amplitude=0.02):
     tris = base.triangles
     assert tris.shape[0] % 2 == 0, "base mesh must be fan-triangulated quads"
     verts64 = base.vertices.astype(np.float64)
@@ -59,7 +59,7 @@ def tessellated_cornell(base, n):
         P = (one - S) * (one - T) * p00 + S * (one - T) * p10 + S * T * p11 + (one - S) * T * p01     # float32 throughout
         idx = n_vertices + np.arange((n + 1) * (n + 1), dtype=np.int64).reshape(n + 1, n + 1).T   # idx[i, j] = base + j*(n+1) + i
         h = pcg_hash_np((idx.astype(np.uint64) ^ np.uint64(0x1234)) & np.uint64(0xFFFFFFFF)).astype(np.float64)
-        disp = 0.02 * (h / 4294967296.0 - 0.5)
+        disp = amplitude * (h / 4294967296.0 - 0.5)    # amplitude: the same hashed field scaled (animated-geometry tests / tools/refit_probe.py)
         interior = np.zeros((n + 1, n + 1), bool)
         interior[1:n, 1:n] = True
         N = base.normals[int(vn[0])].astype(np.float64) if vn[3] == 1 else np.cross(P10 - P00, P01 - P00)

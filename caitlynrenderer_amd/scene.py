@@ -217,6 +217,35 @@ class Scene:
         check(lib().crt_debug_step_hist(self._h, _ptr(h)))
         return h[:65].copy(), h[65:].copy()
 
+    def update_vertices(self, vertices, normals=None, lights=None):
+        """crt_update_vertices: new positions (same count), optionally new normals / lights; refits the trees and records on the
+        device and clears the sum (frame_count restarts)."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        l = None if lights is None else np.ascontiguousarray(lights, dtype=np.float32).reshape(-1, 18)
+        check(lib().crt_update_vertices(self._h, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0],
+                                        _ptr(l), 0 if l is None else l.shape[0]))
+        self.frame_count = 0
+
+    def update_vertices_device(self, ptr, n, sync=True):
+        """crt_update_vertices_device: positions already on the scene's device (ptr = device address of n x 3 float32)."""
+        check(lib().crt_update_vertices_device(self._h, C.c_void_p(int(ptr)), int(n), int(bool(sync))))
+        self.frame_count = 0
+
+    def last_update_ms(self):
+        """(device ms of the last update's refit kernels, host wall ms of the call)"""
+        d, w = C.c_float(), C.c_float()
+        check(lib().crt_last_update_ms(self._h, C.byref(d), C.byref(w)))
+        return d.value, w.value
+
+    def debug_read_accel(self, which):
+        """crt_debug_read_accel: 0 node8 (n,80) u8, 1 CWBVH-order records (n,12) f32, 2 BVH2 (n,8) f32, 3 slot-order records (n,12) f32."""
+        n = C.c_size_t()
+        check(lib().crt_debug_read_accel(self._h, int(which), None, 0, C.byref(n)))
+        out = np.zeros((n.value, 80), np.uint8) if which == 0 else np.zeros((n.value, 8 if which == 2 else 12), np.float32)
+        check(lib().crt_debug_read_accel(self._h, int(which), _ptr(out), out.nbytes, C.byref(n)))
+        return out
+
     def set_shard(self, rank, world, tile=16):
         check(lib().crt_set_shard(self._h, int(rank), int(world), int(tile)))
 

@@ -274,6 +274,30 @@ int crt_trace(crt_scene* s, const crt_ray* rays, size_t n, crt_hit* hits, int mo
  * on the scene's stream unless sync != 0. */
 int crt_trace_device(crt_scene* s, const void* d_rays, size_t n, void* d_hits, int mode, void* d_stats, int sync);
 
+/* Animated geometry (no reference counterpart: the reference uploads its scene once, Scene.h:1000-1062; DXR / OptiX call this an
+ * update build).  New positions for the scene's vertices; triangles, materials, textures and the tree topology are unchanged.
+ * n_vertices must equal the count given at create; normals (n_normals == create's) and lights (n_lights == create's) may be NULL =
+ * unchanged.  Refits the CWBVH (node8 boxes re-quantised), the BVH2 if the scene kept one, the intersection records of both walks
+ * and the float planes if they exist, on the scene's device, one launch per tree level; clears the accumulated sum like crt_reset and
+ * has the tile order measured again.  Every coordinate is checked first (finite, |x| <= 1e18, as crt_scene_create): a bad one or a
+ * wrong count returns CRT_ERR_INVALID and leaves the scene as it was.  The tree keeps its topology, so its quality decays as the
+ * geometry moves away from the positions it was built for ("Refit").  crt_triangle.vn with w == 0 (the loader's
+ * truncated geometric normal, Scene.h:849-852) is caller data and stays as given.  Under crt_set_devices every replica follows:
+ * replicas on this GPU share the refitted buffers, replicas on other GPUs receive them by peer copy.  The first call allocates
+ * the refit's own state (~2.7 MB at 1 M triangles plus the host form's vertex buffer); a scene that never calls it has none. */
+int crt_update_vertices(crt_scene* s, const float* vertices, size_t n_vertices,
+                        const float* normals, size_t n_normals, const crt_light* lights, size_t n_lights);
+/* the same with the positions already in HBM on the scene's device (e.g. written by the caller's skinning kernel); waits once on the
+ * host for the check of the coordinates, then runs asynchronously on the scene's stream unless sync != 0 (d_vertices must stay valid
+ * until then) */
+int crt_update_vertices_device(crt_scene* s, const void* d_vertices, size_t n_vertices, int sync);
+/* device ms of the last update's refit kernels and host wall ms of the call (CRT_ERR_INVALID before the first update) */
+int crt_last_update_ms(crt_scene* s, float* device_ms, float* wall_ms);
+/* test hook: the device-resident tree and records as the walks see them, unpadded: which 0 = node8 (80 B each), 1 = records in
+ * CWBVH order (48 B), 2 = BVH2 FlatNodes (32 B; none when the scene has no BVH2), 3 = records in slot order (48 B).
+ * dst may be NULL to query the count. */
+int crt_debug_read_accel(crt_scene* s, int which, void* dst, size_t cap_bytes, size_t* n_out);
+
 /* the duration in ms of every launch that carried events since the spans were last restarted (options "timing", "timing_accumulate"),
  * in launch order; ms may be NULL to query the count */
 int crt_get_launch_times(crt_scene* s, float* ms, size_t cap, size_t* n_out);
@@ -439,6 +463,17 @@ const int32_t*   crt_cwbvh_tri_slots(const crt_cwbvh*);  /* CWBVH order -> BVH2 
 const int32_t*   crt_cwbvh_child_bvh2(const crt_cwbvh*);
 uint32_t crt_cwbvh_depth(const crt_cwbvh*);
 void crt_cwbvh_free(crt_cwbvh*);
+
+/* Host refits [host]: in place, new boxes from new vertex positions, topology unchanged — the reference implementation the
+ * device refit of crt_update_vertices is compared with (same bytes).  BVH2: leaf boxes are the unions of the full vertex boxes
+ * of their slots' triangles (spatial-split duplicates get the full box), inner boxes the union of their two children.  CWBVH:
+ * leaf slots likewise from tri_slots, inner slots from their child node8; every node8 is re-encoded with the converter's
+ * pick_exponent / quant_lo / quant_hi against the union of its slot boxes; meta, imask and both base indices stay.
+ * leaf_tris are the triangles in BVH2 leaf order (crt_sbvh_triangles).  Non-finite vertices -> CRT_ERR_INVALID, nothing written. */
+int crt_bvh2_refit(crt_flatnode* nodes, size_t n_nodes, const crt_triangle* leaf_tris, size_t n_slots,
+                   const float* vertices, size_t n_vertices);
+int crt_cwbvh_refit(crt_node8* nodes, size_t n_nodes8, const int32_t* tri_slots, size_t n_tris8,
+                    const crt_triangle* leaf_tris, size_t n_slots, const float* vertices, size_t n_vertices);
 
 /* OBJ/MTL loader, Caitlyn/Scene.h:742-926 Read_Object (+ ReadMtl :507-596; textures
  * not loaded) [host].  Applies the -vertex_min translation (:915-925) to vertices,
