@@ -8,6 +8,7 @@ from . import _lib
 from ._lib import CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_CLOSEST, CRT_TRACE_TIE_LOWEST_ID, CrtError
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, pcg_hash
 from .scene import HIT_DT, RAY_DT, STATS_DT, Scene, SceneData
+from .instances import INSTANCE_DT, InstancedScene, instance_inverse, instance_world_box, instances_array
 
 _lib.lib()   # fail loudly at import time if the HIP extension is missing
 
@@ -22,5 +23,6 @@ def warmup():
     _lib.check(_lib.lib().crt_warmup())
 
 
-__all__ = ["has_experiments", "warmup", "Scene", "SceneData", "Camera", "Mesh", "SBVH", "CWBVH", "Rnd", "pcg_hash", "CrtError",
+__all__ = ["has_experiments", "warmup", "Scene", "SceneData", "InstancedScene", "INSTANCE_DT", "instances_array", "instance_inverse",
+           "instance_world_box", "Camera", "Mesh", "SBVH", "CWBVH", "Rnd", "pcg_hash", "CrtError",
            "RAY_DT", "HIT_DT", "STATS_DT", "CRT_TRACE_CLOSEST", "CRT_TRACE_ANY", "CRT_TRACE_BVH2", "CRT_TRACE_TIE_LOWEST_ID"]

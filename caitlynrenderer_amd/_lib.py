@@ -15,6 +15,7 @@ CRT_ABI_VERSION = int(os.environ.get("CRT_LIB_ABI", "6"))      # CRT_LIB_ABI: wi
 CRT_OK, CRT_ERR_INVALID, CRT_ERR_NO_DEVICE, CRT_ERR_HIP, CRT_ERR_IO, CRT_ERR_LIMIT, CRT_ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6
 CRT_TRACE_CLOSEST, CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_TIE_LOWEST_ID = 0, 1, 2, 4
 CRT_BUILD_LBVH_ON_DEVICE = 1
+CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
 
 
 class CrtError(RuntimeError):
@@ -63,6 +64,22 @@ class crt_bvh_info(C.Structure):
                 ("build_lbvh_device_ms", C.c_float), ("build_convert_device_ms", C.c_float)]
 
 
+class crt_blas_desc(C.Structure):
+    _fields_ = [("vertices", C.c_void_p), ("n_vertices", C.c_size_t), ("triangles", C.c_void_p), ("n_triangles", C.c_size_t)]
+
+
+class crt_instance(C.Structure):
+    _fields_ = [("object_to_world", C.c_float * 12), ("mesh", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class crt_instances_info(C.Structure):
+    _fields_ = [("n_meshes", C.c_uint32), ("n_instances", C.c_uint32), ("capacity", C.c_uint32), ("stack_entries", C.c_uint32),
+                ("tlas_nodes8", C.c_uint32), ("tlas_depth8", C.c_uint32), ("max_blas_depth8", C.c_uint32), ("stack_overflows", C.c_uint32),
+                ("blas_nodes8", C.c_uint64), ("blas_tris", C.c_uint64), ("blas_bytes", C.c_uint64), ("tlas_bytes", C.c_uint64),
+                ("instance_bytes", C.c_uint64), ("tlas_build_bytes", C.c_uint64), ("set_device_ms", C.c_float), ("set_wall_ms", C.c_float), ("create_wall_ms", C.c_float),
+                ("reserved_f", C.c_float)]
+
+
 # every symbol include/crt.h declares: name -> (restype, argtypes)
 _P, _SZ, _I, _U32, _F = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_float
 SYMBOLS = {
@@ -87,6 +104,16 @@ SYMBOLS = {
     "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),
     "crt_last_update_ms": (_I, [_P, C.POINTER(_F), C.POINTER(_F)]),
     "crt_debug_read_accel": (_I, [_P, _I, _P, _SZ, C.POINTER(_SZ)]),
+    "crt_instances_create": (_I, [C.POINTER(crt_blas_desc), _U32, _P, _U32, _U32, _U32, C.POINTER(_P)]),
+    "crt_instances_set": (_I, [_P, _P, _U32]),
+    "crt_instances_set_device": (_I, [_P, _P, _U32, _I]),
+    "crt_instances_trace": (_I, [_P, _P, _SZ, _P, _P, _I, _P]),
+    "crt_instances_trace_device": (_I, [_P, _P, _SZ, _P, _P, _I, _P, _I]),
+    "crt_instances_get_info": (_I, [_P, C.POINTER(crt_instances_info)]),
+    "crt_instances_debug_read": (_I, [_P, _I, _P, _SZ, C.POINTER(_SZ)]),
+    "crt_instances_destroy": (_I, [_P]),
+    "crt_instance_inverse": (_I, [_P, _P]),
+    "crt_instance_world_box": (_I, [_P, _P, _P]),
     "crt_debug_read_queue": (_I, [_P, _I, _U32, _P, _SZ, C.POINTER(_SZ)]),
     "crt_debug_time_graph": (_I, [_P, _U32, _P, _U32, C.POINTER(_F), C.POINTER(_F)]),
     "crt_debug_launch_form": (_I, [_P, C.POINTER(C.c_int32)]),

@@ -617,7 +617,8 @@ struct Warmer {
     std::atomic<int> rc{0};                        // first failure of a background load (crt_warmup reports it; a first use then loads again and fails loudly itself)
     static int load_all() {
         int e;
-        if ((e = crt::warm_rt_kernels()) || (e = crt::warm_lbvh_kernels()) || (e = crt::warm_cwbvh_kernels()) || (e = crt::warm_scene_build_kernels())) return e;
+        if ((e = crt::warm_rt_kernels()) || (e = crt::warm_lbvh_kernels()) || (e = crt::warm_cwbvh_kernels()) || (e = crt::warm_scene_build_kernels()) ||
+            (e = crt::warm_instance_kernels())) return e;
         return 0;
     }
     void start(int device) {                       // returns at once

@@ -1,0 +1,433 @@
+// Instanced scenes (include/crt.h crt_instances_*): one bottom-level CWBVH per mesh, built once on the device by the
+// scene builders (lbvh.hip, cwbvh_device.hip, scene_build.hip), and a top-level CWBVH over the instances' world boxes, rebuilt on the
+// device (binned SAH over boxes, then the same converter) at create and at every set.  All node8s live in ONE array (the TLAS region first,
+// sized for `capacity`, then every BLAS with its child / triangle bases rebased) and all triangle records in ONE array, so the walk
+// (instances.hip k_trace_instances) addresses any node with one 32-bit index off one base.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/crt.h"
+#include "crt_error.hpp"
+#include "device_build.hpp"
+#include "host/instance_math.hpp"
+#include "instances.hpp"
+#include "rt_kernels.hpp"
+
+using crt::fail;
+
+#define IHIPCHK(expr)                                                                            \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail(CRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
+    } while (0)
+
+static_assert(sizeof(crt_instance) == 64, "crt_instance is 64 bytes");
+
+struct crt_instances {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint32_t n_meshes = 0, capacity = 0, n_instances = 0;
+    uint32_t tlas_cap_nodes = 0, n_tlas8 = 0, tlas_depth8 = 0, max_blas_depth8 = 0, stack_entries = 2;
+    uint64_t blas_nodes8 = 0, blas_tris = 0;
+    uint4* d_nodes = nullptr;             // TLAS region (tlas_cap_nodes) + every BLAS
+    float4* d_tris = nullptr;             // every BLAS's records
+    float4* d_inst = nullptr;             // live instance records in TLAS leaf order (capacity x 4 rows)
+    float* d_w2o = nullptr;               // live world_to_object, instance order (capacity x 12)
+    float* d_wbox = nullptr;              // live world boxes, instance order (capacity x 6)
+    float* d_mesh_box = nullptr;          // 6 per mesh
+    uint32_t* d_mesh_root = nullptr;      // BLAS root node per mesh
+    // a set's staging: nothing here is read by the walk, so a refused set leaves the scene as it was
+    uint32_t* d_in = nullptr;             // host-given instances (capacity x 16 words)
+    float4* d_rec = nullptr;              // records in instance order
+    float* d_box = nullptr;
+    float* d_w2o_stage = nullptr;
+    crt_node8* d_t8_stage = nullptr;      // the converter's output (tlas_cap_nodes)
+    uint32_t* d_flag = nullptr;
+    uint32_t* d_overflow = nullptr;
+    crt::DeviceArena arena;               // TLAS build: BVH2, leaf order, CWBVH slots, builder temporaries (sized for capacity)
+    crt_flatnode* d_flat = nullptr;
+    uint32_t* d_tri_order = nullptr;
+    int32_t* d_tri_slots = nullptr;
+    size_t arena_mark = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float set_device_ms = 0.f, set_wall_ms = 0.f, build_wall_ms = 0.f;
+    // crt_instances_trace's device copies of the host rays
+    void* d_t_rays = nullptr; void* d_t_hits = nullptr; void* d_t_inst = nullptr; void* d_t_stats = nullptr;
+    size_t t_cap = 0;
+
+    ~crt_instances() {
+        void* bufs[] = {d_nodes, d_tris, d_inst, d_w2o, d_wbox, d_mesh_box, d_mesh_root, d_in, d_rec, d_box, d_w2o_stage, d_flag, d_overflow,
+                        d_t8_stage, d_t_rays, d_t_hits, d_t_inst, d_t_stats};
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (void* p : bufs) if (p) (void)hipFree(p);
+        arena.release();
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+int require_gpu() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+        return fail(CRT_ERR_NO_DEVICE, "no HIP device visible: the traversal path has no CPU fallback");
+    return CRT_OK;
+}
+
+template <typename T>
+int alloc(T** p, size_t count) {
+    *p = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+uint32_t gpu_flags_of(uint32_t build_flags) {
+    return (build_flags & CRT_BUILD_SAH) ? (CRT_GPU_BUILD_SAH | (build_flags & 0xff00u))
+           : (build_flags & CRT_BUILD_PLOC) ? (CRT_GPU_BUILD_PLOC | (build_flags & 0xff00u)) : 0u;
+}
+
+// One mesh: LBVH / PLOC / SAH BVH2 -> CWBVH -> records, as crt_scene_create's build-on-device path.  *d_nodes8 and *d_recs are the
+// caller's to free.
+int build_blas(const crt_blas_desc& m, uint32_t gpu_flags, hipStream_t st, crt_node8** d_nodes8, float4** d_recs, uint32_t* n8, uint32_t* depth8) {
+    const uint32_t n = (uint32_t)m.n_triangles, n2 = 2u * n - 1u;
+    crt::DeviceArena arena;
+    auto P = crt::DeviceArena::padded;
+    const size_t tmp = std::max(crt::lbvh_tmp_bytes(n, gpu_flags), crt::cwbvh_tmp_bytes(n2, n));
+    hipError_t he = arena.reserve(P(m.n_vertices * 12) + P((size_t)n * sizeof(crt_triangle)) + P((size_t)n2 * sizeof(crt_flatnode)) + 2 * P((size_t)n * 4) + tmp);
+    if (he != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("crt_instances_create: hipMalloc: ") + hipGetErrorString(he));
+    float* d_verts = arena.take<float>(m.n_vertices * 3);
+    crt_triangle* d_in = arena.take<crt_triangle>(n);
+    crt_flatnode* d_flat = arena.take<crt_flatnode>(n2);
+    uint32_t* d_order = arena.take<uint32_t>(n);
+    int32_t* d_slots = arena.take<int32_t>(n);
+    const size_t mark = arena.used;
+    IHIPCHK(hipMemcpyAsync(d_verts, m.vertices, m.n_vertices * 12, hipMemcpyHostToDevice, st));
+    IHIPCHK(hipMemcpyAsync(d_in, m.triangles, (size_t)n * sizeof(crt_triangle), hipMemcpyHostToDevice, st));
+    uint32_t depth2 = 0;
+    float ms = 0.f;
+    int rc = crt::lbvh_build_on_device(reinterpret_cast<const int32_t*>(d_in), 12, d_verts, n, gpu_flags, arena, d_flat, d_order, &depth2, &ms, st);
+    if (rc) return fail(rc, std::string("crt_instances_create: BLAS build failed: ") + crt_last_error());
+    arena.used = mark;
+    rc = crt::cwbvh_convert_on_device(d_flat, n2, n, arena, d_slots, d_nodes8, nullptr, n8, depth8, &ms, st);
+    if (rc) return fail(rc, std::string("crt_instances_create: BLAS BVH2 -> CWBVH failed: ") + crt_last_error());
+    if ((rc = alloc(d_recs, (size_t)n * 3))) { (void)hipFree(*d_nodes8); *d_nodes8 = nullptr; return rc; }
+    crt::launch_gather_records(d_in, d_order, d_slots, d_verts, n, *d_recs, st);
+    IHIPCHK(hipStreamSynchronize(st));                // before the arena goes
+    IHIPCHK(hipGetLastError());
+    return CRT_OK;
+}
+
+// Validate + prepare n instances from DEVICE memory, then rebuild the TLAS.  Nothing the walk reads changes before every check passed.
+int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n > s->capacity) return fail(CRT_ERR_INVALID, "crt_instances_set: more instances than the capacity given at create");
+    hipStream_t st = s->stream;
+    IHIPCHK(hipEventRecord(s->ev0, st));
+    if (n > 0) {
+        IHIPCHK(hipMemsetAsync(s->d_flag, 0, 4, st));
+        crt::InstPrepArgs pa{};
+        pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = s->n_meshes; pa.mesh_box = s->d_mesh_box; pa.mesh_root = s->d_mesh_root;
+        pa.rec = s->d_rec; pa.box = s->d_box; pa.w2o = s->d_w2o_stage; pa.flag = s->d_flag;
+        crt::launch_instance_prep(pa, st);
+        uint32_t flag = 0;
+        IHIPCHK(hipMemcpyAsync(&flag, s->d_flag, 4, hipMemcpyDeviceToHost, st));
+        IHIPCHK(hipStreamSynchronize(st));
+        IHIPCHK(hipGetLastError());
+        if (flag)
+            return fail(CRT_ERR_INVALID, std::string("crt_instances_set: ") +
+                                             ((flag & 1u) ? "a matrix is not finite, or singular, or its inverse is not finite"
+                                              : (flag & 2u) ? "a mesh index is out of range" : "a world box exceeds 1e18"));
+        // the TLAS over the world boxes
+        s->arena.used = s->arena_mark;
+        uint32_t n8 = 0, depth8 = 0;
+        float ms = 0.f;
+        int rc;
+        if (n == 1) {
+            crt::launch_single_leaf(s->d_box, s->d_flat, s->d_tri_order, st);
+        } else {
+            uint32_t depth2 = 0;
+            rc = crt::sah_build_from_boxes_on_device(s->d_box, n, CRT_GPU_BUILD_SAH, s->arena, s->d_flat, s->d_tri_order, &depth2, &ms, st);
+            if (rc) return fail(rc, std::string("crt_instances_set: TLAS build failed: ") + crt_last_error());
+            s->arena.used = s->arena_mark;
+        }
+        // into the staging node buffer sized for `capacity` at create: no allocation (and no device-wide hipFree) per set
+        crt_node8* d_t8 = nullptr;
+        rc = crt::cwbvh_convert_on_device(s->d_flat, n == 1 ? 1u : 2u * n - 1u, n, s->arena, s->d_tri_slots, &d_t8, nullptr, &n8, &depth8, &ms, st,
+                                          s->d_t8_stage, s->tlas_cap_nodes);
+        if (rc) return fail(rc, std::string("crt_instances_set: TLAS BVH2 -> CWBVH failed: ") + crt_last_error());
+        struct Free { void* p; ~Free() { if (p) (void)hipFree(p); } } t8_guard{d_t8 == s->d_t8_stage ? nullptr : d_t8};
+        const uint32_t stack = std::max<uint32_t>(2u, depth8 + s->max_blas_depth8);
+        if (stack > CRT_INST_STACK_ENTRIES)
+            return fail(CRT_ERR_LIMIT, "crt_instances_set: TLAS depth + deepest BLAS exceed the walk's stack (" + std::to_string(stack) + " > " +
+                                           std::to_string(CRT_INST_STACK_ENTRIES) + " entries)");
+        if (n8 > s->tlas_cap_nodes) return fail(CRT_ERR_HIP, "crt_instances_set: TLAS larger than its region");
+        // everything checked: publish (the TLAS starts at node 0, its leaves index the instance records: no rebase)
+        IHIPCHK(hipMemcpyAsync(s->d_nodes, d_t8, (size_t)n8 * sizeof(crt_node8), hipMemcpyDeviceToDevice, st));
+        crt::launch_gather_instances(s->d_rec, s->d_tri_order, s->d_tri_slots, n, s->d_inst, st);
+        IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+        IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+        IHIPCHK(hipStreamSynchronize(st));            // the publication is done when the call returns
+        s->n_tlas8 = n8; s->tlas_depth8 = depth8; s->stack_entries = stack;
+    } else {
+        s->n_tlas8 = 0; s->tlas_depth8 = 0; s->stack_entries = 2;
+    }
+    s->n_instances = n;
+    IHIPCHK(hipEventRecord(s->ev1, st));
+    IHIPCHK(hipGetLastError());
+    IHIPCHK(hipEventSynchronize(s->ev1));
+    IHIPCHK(hipEventElapsedTime(&s->set_device_ms, s->ev0, s->ev1));
+    s->set_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instance* instances, uint32_t n_instances, uint32_t capacity,
+                uint32_t build_flags, crt_instances** out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!out) return fail(CRT_ERR_INVALID, "crt_instances_create: null out");
+    *out = nullptr;
+    if (!meshes || n_meshes == 0) return fail(CRT_ERR_INVALID, "crt_instances_create: no mesh");
+    if (n_instances && !instances) return fail(CRT_ERR_INVALID, "crt_instances_create: null instances");
+    if (capacity == 0) capacity = n_instances;
+    if (capacity < n_instances) return fail(CRT_ERR_INVALID, "crt_instances_create: capacity below n_instances");
+    if (capacity > (1u << 24)) return fail(CRT_ERR_LIMIT, "crt_instances_create: capacity above 2^24 instances");
+    std::vector<float> mesh_box(6 * (size_t)n_meshes);
+    uint64_t tris_total = 0;
+    for (uint32_t k = 0; k < n_meshes; ++k) {
+        const crt_blas_desc& m = meshes[k];
+        if (!m.vertices || !m.triangles || m.n_vertices == 0 || m.n_triangles == 0)
+            return fail(CRT_ERR_INVALID, "crt_instances_create: mesh " + std::to_string(k) + " is empty");
+        if (2ull * m.n_triangles >= (1ull << 29)) return fail(CRT_ERR_LIMIT, "crt_instances_create: a mesh has 2^28 triangles or more");
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (size_t i = 0; i < m.n_triangles; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const int32_t vi = m.triangles[i].v[j];
+                if (vi < 0 || (size_t)vi >= m.n_vertices) return fail(CRT_ERR_INVALID, "crt_instances_create: vertex index out of range");
+                for (int a = 0; a < 3; ++a) {
+                    const float x = m.vertices[3 * (size_t)vi + a];
+                    if (!(std::fabs(x) <= 1e18f)) return fail(CRT_ERR_INVALID, "crt_instances_create: a vertex coordinate is not finite or exceeds 1e18");
+                    lo[a] = std::min(lo[a], x); hi[a] = std::max(hi[a], x);
+                }
+            }
+        for (int a = 0; a < 3; ++a) { mesh_box[6 * (size_t)k + a] = lo[a]; mesh_box[6 * (size_t)k + 3 + a] = hi[a]; }
+        tris_total += m.n_triangles;
+    }
+    int rc = require_gpu();
+    if (rc) return rc;
+    std::unique_ptr<crt_instances> owner(new (std::nothrow) crt_instances);
+    crt_instances* s = owner.get();
+    if (!s) return fail(CRT_ERR_NOMEM, "crt_instances_create: out of memory");
+    IHIPCHK(hipGetDevice(&s->device));
+    IHIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    IHIPCHK(hipEventCreate(&s->ev0));
+    IHIPCHK(hipEventCreate(&s->ev1));
+    s->n_meshes = n_meshes; s->capacity = capacity;
+    s->tlas_cap_nodes = std::max<uint32_t>(capacity, 1u);          // a CWBVH over c >= 1 leaves has at most max(1, c - 1) node8s
+    hipStream_t st = s->stream;
+
+    // every mesh once, then ONE node array (TLAS region first) and ONE record array
+    struct Blas { crt_node8* nodes = nullptr; float4* recs = nullptr; uint32_t n8 = 0, depth8 = 0; };
+    std::vector<Blas> blas(n_meshes);
+    struct FreeAll { std::vector<Blas>& b; ~FreeAll() { for (auto& x : b) { if (x.nodes) (void)hipFree(x.nodes); if (x.recs) (void)hipFree(x.recs); } } } free_all{blas};
+    const uint32_t gflags = gpu_flags_of(build_flags);
+    uint64_t nodes_total = s->tlas_cap_nodes;
+    for (uint32_t k = 0; k < n_meshes; ++k) {
+        if ((rc = build_blas(meshes[k], gflags, st, &blas[k].nodes, &blas[k].recs, &blas[k].n8, &blas[k].depth8))) return rc;
+        nodes_total += blas[k].n8;
+        s->max_blas_depth8 = std::max(s->max_blas_depth8, blas[k].depth8);
+    }
+    // one 32-bit byte offset per node / record fetch (rt_traverse.hpp node_rows / tri_rows)
+    if (nodes_total * CRT_NODE_ROWS * 16 >= (1ull << 32) || tris_total * CRT_TRI_ROWS * 16 >= (1ull << 32))
+        return fail(CRT_ERR_LIMIT, "crt_instances_create: the packed node or record array exceeds 4 GiB");
+    if (CRT_NODE_ROWS != 5 || CRT_TRI_ROWS != 3) return fail(CRT_ERR_LIMIT, "crt_instances_create: needs the packed row strides (5 / 3)");
+    if ((rc = alloc(&s->d_nodes, nodes_total * 5))) return rc;
+    if ((rc = alloc(&s->d_tris, tris_total * 3))) return rc;
+    std::vector<uint32_t> roots(n_meshes);
+    uint64_t node_off = s->tlas_cap_nodes, tri_off = 0;
+    for (uint32_t k = 0; k < n_meshes; ++k) {
+        IHIPCHK(hipMemcpyAsync(s->d_nodes + 5 * node_off, blas[k].nodes, (size_t)blas[k].n8 * sizeof(crt_node8), hipMemcpyDeviceToDevice, st));
+        IHIPCHK(hipMemcpyAsync(s->d_tris + 3 * tri_off, blas[k].recs, meshes[k].n_triangles * 48, hipMemcpyDeviceToDevice, st));
+        crt::launch_rebase_nodes(s->d_nodes + 5 * node_off, blas[k].n8, (uint32_t)node_off, (uint32_t)tri_off, st);
+        roots[k] = (uint32_t)node_off;
+        node_off += blas[k].n8; tri_off += meshes[k].n_triangles;
+    }
+    s->blas_nodes8 = nodes_total - s->tlas_cap_nodes; s->blas_tris = tris_total;
+    if ((rc = alloc(&s->d_mesh_box, mesh_box.size()))) return rc;
+    if ((rc = alloc(&s->d_mesh_root, n_meshes))) return rc;
+    IHIPCHK(hipMemcpyAsync(s->d_mesh_box, mesh_box.data(), mesh_box.size() * 4, hipMemcpyHostToDevice, st));
+    IHIPCHK(hipMemcpyAsync(s->d_mesh_root, roots.data(), n_meshes * 4, hipMemcpyHostToDevice, st));
+    const size_t C = capacity;
+    if ((rc = alloc(&s->d_inst, C * 4)) || (rc = alloc(&s->d_w2o, C * 12)) || (rc = alloc(&s->d_wbox, C * 6)) || (rc = alloc(&s->d_in, C * 16)) ||
+        (rc = alloc(&s->d_rec, C * 4)) || (rc = alloc(&s->d_box, C * 6)) || (rc = alloc(&s->d_w2o_stage, C * 12)) || (rc = alloc(&s->d_flag, 1)) ||
+        (rc = alloc(&s->d_overflow, 1)) || (rc = alloc(&s->d_t8_stage, s->tlas_cap_nodes)))
+        return rc;
+    IHIPCHK(hipMemsetAsync(s->d_overflow, 0, 4, st));
+    // the TLAS build's space for `capacity` instances, reserved once
+    const size_t cn = std::max<size_t>(C, 2), cn2 = 2 * cn - 1;
+    auto P = crt::DeviceArena::padded;
+    const size_t tmp = std::max(crt::lbvh_tmp_bytes(cn, CRT_GPU_BUILD_SAH), crt::cwbvh_tmp_bytes(cn2, cn));
+    hipError_t he = s->arena.reserve(P(cn2 * sizeof(crt_flatnode)) + 2 * P(cn * 4) + tmp);
+    if (he != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("crt_instances_create: hipMalloc: ") + hipGetErrorString(he));
+    s->d_flat = s->arena.take<crt_flatnode>(cn2);
+    s->d_tri_order = s->arena.take<uint32_t>(cn);
+    s->d_tri_slots = s->arena.take<int32_t>(cn);
+    s->arena_mark = s->arena.used;
+    IHIPCHK(hipStreamSynchronize(st));
+    IHIPCHK(hipGetLastError());
+    if (n_instances) {
+        IHIPCHK(hipMemcpyAsync(s->d_in, instances, (size_t)n_instances * sizeof(crt_instance), hipMemcpyHostToDevice, st));
+        if ((rc = set_impl(s, s->d_in, n_instances))) return fail(rc, std::string("crt_instances_create: ") + crt_last_error());
+    }
+    s->build_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = owner.release();
+    return CRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crt_instance_inverse(const float object_to_world[12], float world_to_object[12]) {
+    if (!object_to_world || !world_to_object) return fail(CRT_ERR_INVALID, "crt_instance_inverse: null argument");
+    if (!crt::instance_inverse(object_to_world, world_to_object))
+        return fail(CRT_ERR_INVALID, "crt_instance_inverse: the matrix is not finite, or singular, or its inverse is not finite");
+    return CRT_OK;
+}
+
+int crt_instance_world_box(const float object_to_world[12], const float box[6], float out[6]) {
+    if (!object_to_world || !box || !out) return fail(CRT_ERR_INVALID, "crt_instance_world_box: null argument");
+    crt::instance_world_box(object_to_world, box, out);
+    return CRT_OK;
+}
+
+int crt_instances_create(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instance* instances, uint32_t n_instances, uint32_t capacity,
+                         uint32_t build_flags, crt_instances** out) {
+    try {
+        return create_impl(meshes, n_meshes, instances, n_instances, capacity, build_flags, out);
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_instances_create: ") + e.what());
+    }
+}
+
+int crt_instances_set(crt_instances* s, const crt_instance* instances, uint32_t n_instances) {
+    if (!s || (n_instances && !instances)) return fail(CRT_ERR_INVALID, "crt_instances_set: null argument");
+    if (n_instances > s->capacity) return fail(CRT_ERR_INVALID, "crt_instances_set: more instances than the capacity given at create");
+    IHIPCHK(hipSetDevice(s->device));
+    if (n_instances) IHIPCHK(hipMemcpyAsync(s->d_in, instances, (size_t)n_instances * sizeof(crt_instance), hipMemcpyHostToDevice, s->stream));
+    return set_impl(s, s->d_in, n_instances);
+}
+
+int crt_instances_set_device(crt_instances* s, const void* d_instances, uint32_t n_instances, int sync) {
+    if (!s || (n_instances && !d_instances)) return fail(CRT_ERR_INVALID, "crt_instances_set_device: null argument");
+    IHIPCHK(hipSetDevice(s->device));
+    (void)sync;                                   // a set checks its instances on the host before it publishes anything: it always returns done
+    return set_impl(s, d_instances, n_instances);
+}
+
+int crt_instances_trace_device(crt_instances* s, const void* d_rays, size_t n, void* d_hits, void* d_instance_of_hit, int mode, void* d_stats, int sync) {
+    if (!s || (n && (!d_rays || !d_hits))) return fail(CRT_ERR_INVALID, "crt_instances_trace_device: null argument");
+    if (mode != CRT_TRACE_CLOSEST && mode != CRT_TRACE_ANY)
+        return fail(CRT_ERR_INVALID, "crt_instances_trace_device: mode must be CRT_TRACE_CLOSEST or CRT_TRACE_ANY");
+    if (n >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_instances_trace_device: too many rays for one launch");
+    IHIPCHK(hipSetDevice(s->device));
+    if (n == 0) return CRT_OK;
+    crt::InstTraceArgs a{};
+    a.nodes = s->d_nodes; a.tris = s->d_tris; a.inst = s->d_inst;
+    a.rays = static_cast<const float4*>(d_rays); a.hits = static_cast<float4*>(d_hits);
+    a.inst_out = static_cast<int32_t*>(d_instance_of_hit); a.stats = static_cast<uint32_t*>(d_stats);
+    a.n = (uint32_t)n; a.n_instances = s->n_instances; a.stack_entries = s->stack_entries;
+    a.refill_min = 8; a.tri_min = 2;              // crt_trace's defaults (options refill_min, tri_min)
+    a.overflow = s->d_overflow;
+    // k_trace's grid: every XCD group's share of 4096-ray units, in 1024-ray chunks
+    const uint64_t share = ((n + 4095) / 4096 + 7) / 8 * 4096;
+    const uint32_t chunks = (uint32_t)std::max<uint64_t>(8, 8 * ((share + 1023) / 1024));
+    crt::launch_trace_instances(a, mode, d_stats != nullptr, chunks, s->stream);
+    IHIPCHK(hipGetLastError());
+    if (sync) IHIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_instances_trace(crt_instances* s, const crt_ray* rays, size_t n, crt_hit* hits, int32_t* instance_of_hit, int mode, crt_ray_stats* stats) {
+    if (!s || (n && (!rays || !hits))) return fail(CRT_ERR_INVALID, "crt_instances_trace: null argument");
+    if (mode != CRT_TRACE_CLOSEST && mode != CRT_TRACE_ANY)
+        return fail(CRT_ERR_INVALID, "crt_instances_trace: mode must be CRT_TRACE_CLOSEST or CRT_TRACE_ANY");
+    IHIPCHK(hipSetDevice(s->device));
+    if (n == 0) return CRT_OK;
+    if (n > s->t_cap) {
+        void* bufs[] = {s->d_t_rays, s->d_t_hits, s->d_t_inst, s->d_t_stats};
+        for (void* p : bufs) if (p) (void)hipFree(p);
+        s->d_t_rays = s->d_t_hits = s->d_t_inst = s->d_t_stats = nullptr;
+        s->t_cap = 0;
+        IHIPCHK(hipMalloc(&s->d_t_rays, n * sizeof(crt_ray)));
+        IHIPCHK(hipMalloc(&s->d_t_hits, n * sizeof(crt_hit)));
+        IHIPCHK(hipMalloc(&s->d_t_inst, n * 4));
+        IHIPCHK(hipMalloc(&s->d_t_stats, n * sizeof(crt_ray_stats)));
+        s->t_cap = n;
+    }
+    IHIPCHK(hipMemcpyAsync(s->d_t_rays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, s->stream));
+    int rc = crt_instances_trace_device(s, s->d_t_rays, n, s->d_t_hits, s->d_t_inst, mode, stats ? s->d_t_stats : nullptr, 0);
+    if (rc) return rc;
+    IHIPCHK(hipMemcpyAsync(hits, s->d_t_hits, n * sizeof(crt_hit), hipMemcpyDeviceToHost, s->stream));
+    if (instance_of_hit) IHIPCHK(hipMemcpyAsync(instance_of_hit, s->d_t_inst, n * 4, hipMemcpyDeviceToHost, s->stream));
+    if (stats) IHIPCHK(hipMemcpyAsync(stats, s->d_t_stats, n * sizeof(crt_ray_stats), hipMemcpyDeviceToHost, s->stream));
+    IHIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_instances_get_info(crt_instances* s, crt_instances_info* out) {
+    if (!s || !out) return fail(CRT_ERR_INVALID, "crt_instances_get_info: null argument");
+    IHIPCHK(hipSetDevice(s->device));
+    IHIPCHK(hipStreamSynchronize(s->stream));
+    crt_instances_info i{};
+    i.n_meshes = s->n_meshes; i.n_instances = s->n_instances; i.capacity = s->capacity; i.stack_entries = s->stack_entries;
+    i.tlas_nodes8 = s->n_tlas8; i.tlas_depth8 = s->tlas_depth8; i.max_blas_depth8 = s->max_blas_depth8;
+    IHIPCHK(hipMemcpy(&i.stack_overflows, s->d_overflow, 4, hipMemcpyDeviceToHost));
+    i.blas_nodes8 = s->blas_nodes8; i.blas_tris = s->blas_tris;
+    i.blas_bytes = s->blas_nodes8 * sizeof(crt_node8) + s->blas_tris * 48;
+    i.tlas_bytes = (uint64_t)s->tlas_cap_nodes * sizeof(crt_node8);
+    i.instance_bytes = (uint64_t)s->capacity * (64 + 48 + 24 + 64 + 64 + 24 + 48);   // live records, matrices, boxes + the set's staging
+    i.tlas_build_bytes = (uint64_t)s->arena.cap + (uint64_t)s->tlas_cap_nodes * sizeof(crt_node8);   // the TLAS builder's arena + node staging
+    i.set_device_ms = s->set_device_ms; i.set_wall_ms = s->set_wall_ms; i.create_wall_ms = s->build_wall_ms;
+    *out = i;
+    return CRT_OK;
+}
+
+int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_bytes, size_t* n_out) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_instances_debug_read: null handle");
+    const void* src = nullptr;
+    size_t n = 0, item = 0;
+    switch (which) {
+        case 0: src = s->d_w2o; n = s->n_instances; item = 48; break;
+        case 1: src = s->d_wbox; n = s->n_instances; item = 24; break;
+        case 2: src = s->d_nodes; n = s->n_tlas8; item = sizeof(crt_node8); break;
+        case 3: src = s->d_inst; n = s->n_instances; item = 64; break;
+        default: return fail(CRT_ERR_INVALID, "crt_instances_debug_read: which must be 0..3");
+    }
+    if (n_out) *n_out = n;
+    if (!dst || n == 0) return CRT_OK;
+    if (cap_bytes < n * item) return fail(CRT_ERR_INVALID, "crt_instances_debug_read: destination too small");
+    IHIPCHK(hipSetDevice(s->device));
+    IHIPCHK(hipStreamSynchronize(s->stream));
+    IHIPCHK(hipMemcpy(dst, src, n * item, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+int crt_instances_destroy(crt_instances* s) {
+    if (!s) return CRT_OK;
+    (void)hipSetDevice(s->device);
+    delete s;
+    return CRT_OK;
+}
+
+}  // extern "C"

@@ -226,14 +226,15 @@ size_t cwbvh_tmp_bytes(size_t n2, size_t ns) {
 
 int cwbvh_convert_on_device(const crt_flatnode* d_bvh2, uint32_t n2, uint32_t ns, DeviceArena& tmp, int32_t* d_tri_slots,
                             crt_node8** d_nodes_out, int32_t** d_child_bvh2_out, uint32_t* n8_out, uint32_t* depth_out, float* device_ms,
-                            hipStream_t st) {
+                            hipStream_t st, crt_node8* d_nodes_into, uint32_t into_cap) {
     *d_nodes_out = nullptr;
     if (d_child_bvh2_out) *d_child_bvh2_out = nullptr;
     const uint32_t cap8 = n2 / 2u + 1u;            // every node8 stands for a distinct interior BVH2 node (or the root)
     crt_node8* d_nodes = nullptr; int32_t* d_child_bvh2 = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool own_nodes = true;
     auto cleanup = [&]() {
-        if (d_nodes) (void)hipFree(d_nodes);
+        if (d_nodes && own_nodes) (void)hipFree(d_nodes);
         if (d_child_bvh2) (void)hipFree(d_child_bvh2);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -333,7 +334,8 @@ int cwbvh_convert_on_device(const crt_flatnode* d_bvh2, uint32_t n2, uint32_t ns
     CW_HIPCHK(hipMemcpyAsync(t.B, &root_place[2], 4, hipMemcpyHostToDevice, st));
     for (uint32_t l = 0; l < depth; ++l)
         hipLaunchKernelGGL(k_place, grid_for(level_begin[l + 1] - level_begin[l]), dim3(256), 0, st, t, level_begin[l], level_begin[l + 1]);
-    CW_HIPCHK(hipMalloc(&d_nodes, (size_t)n8 * sizeof(crt_node8)));
+    if (d_nodes_into && n8 <= into_cap) { d_nodes = d_nodes_into; own_nodes = false; }
+    else CW_HIPCHK(hipMalloc(&d_nodes, (size_t)n8 * sizeof(crt_node8)));
     if (d_child_bvh2_out) CW_HIPCHK(hipMalloc(&d_child_bvh2, (size_t)n8 * 8 * 4));
     hipLaunchKernelGGL(k_emit, grid_for(n8), dim3(256), 0, st, d_bvh2, dec, d_nprims, t, n8, ns, d_nodes, d_tri_slots, d_child_bvh2, d_seen, d_flags);
     hipLaunchKernelGGL(k_cover, grid_for(ns), dim3(256), 0, st, d_seen, ns, d_flags);

@@ -45,14 +45,19 @@ struct DeviceArena {
 size_t lbvh_tmp_bytes(size_t n_tris, uint32_t flags);
 int lbvh_build_on_device(const int32_t* d_vidx, uint32_t stride, const float* d_verts, uint32_t n_tris, uint32_t flags, DeviceArena& tmp,
                          crt_flatnode* d_flat, uint32_t* d_tri_order, uint32_t* depth_out, float* device_ms, hipStream_t stream);
+// the binned-SAH build (CRT_GPU_BUILD_SAH) over n >= 2 caller-given leaf boxes (6 floats each: lo, hi; finite, |x| <= 1e18) instead of
+// triangles; temporaries: lbvh_tmp_bytes(n, CRT_GPU_BUILD_SAH).  d_tri_order: leaf slot -> box index.
+int sah_build_from_boxes_on_device(const float* d_boxes, uint32_t n, uint32_t flags, DeviceArena& tmp, crt_flatnode* d_flat, uint32_t* d_tri_order,
+                                   uint32_t* depth_out, float* device_ms, hipStream_t stream);
 
 // ---- BVH2 -> CWBVH (cwbvh_device.hip) ----
-// d_tri_slots (n_slots) is caller-owned; *d_nodes_out is hipMalloc'ed here once the node count is known (caller frees);
+// d_tri_slots (n_slots) is caller-owned; *d_nodes_out is hipMalloc'ed here once the node count is known (caller frees) — unless the
+// caller passes d_nodes_into with room for into_cap node8s and the tree fits: then *d_nodes_out == d_nodes_into and nothing is allocated.
 // d_child_bvh2_out may be null (the debug child map is then not produced).  Same bytes as the host converter.
 size_t cwbvh_tmp_bytes(size_t n_bvh2_nodes, size_t n_slots);
 int cwbvh_convert_on_device(const crt_flatnode* d_bvh2, uint32_t n_nodes, uint32_t n_slots, DeviceArena& tmp, int32_t* d_tri_slots,
                             crt_node8** d_nodes_out, int32_t** d_child_bvh2_out, uint32_t* n8_out, uint32_t* depth_out, float* device_ms,
-                            hipStream_t stream);
+                            hipStream_t stream, crt_node8* d_nodes_into = nullptr, uint32_t into_cap = 0);
 
 // ---- scene assembly on the device (scene_build.hip) ----
 // Index validation of the uploaded crt_triangle array (what crt_scene_create checks on the host for host-built scenes):
@@ -95,5 +100,6 @@ void launch_refit_node8_level(void* d_nodes, uint32_t node_rows, uint32_t n8, co
 int warm_lbvh_kernels();
 int warm_cwbvh_kernels();
 int warm_scene_build_kernels();
+int warm_instance_kernels();
 
 }  // namespace crt

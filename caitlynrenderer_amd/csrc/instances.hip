@@ -1,0 +1,274 @@
+// HIP kernels of instanced scenes (include/crt.h crt_instances_*): per-instance preparation (validation, inverse, world
+// box, record), the packing of the BLASes into one node array, and the two-level walk k_trace_instances.
+//
+// The walk is ONE loop with ONE stack per lane.  TLAS and BLAS nodes are the same node8 format in the same array, so a wave whose lanes
+// are at different levels still runs a single node step together.  A TLAS leaf's "triangles" are instances: the instance step pushes
+// what the lane still has pending at the TLAS level (inner hits, the rest of the leaf), then a return marker, moves the ray into object
+// space and continues at the BLAS root.  Popping the marker restores the world ray, which the lane keeps in registers.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "instances.hpp"
+#include "rt_kernels.hpp"
+#include "rt_math.hpp"
+#include "rt_traverse.hpp"
+#include "host/instance_math.hpp"
+
+namespace crt {
+
+__global__ void __launch_bounds__(256) k_instance_prep(InstPrepArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t* src = a.in + 16 * (size_t)i;
+    float m[12];
+    for (int k = 0; k < 12; ++k) m[k] = __uint_as_float(src[k]);
+    const uint32_t mesh = src[12];
+    uint32_t bad = 0;
+    float w[12];
+    if (!instance_inverse(m, w)) bad |= 1u;
+    if (mesh >= a.n_meshes) bad |= 2u;
+    float box[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (!bad) {
+        instance_world_box(m, a.mesh_box + 6 * (size_t)mesh, box);
+        for (int k = 0; k < 6; ++k) if (!(fabsf(box[k]) <= 1e18f)) bad |= 4u;      // the builder's coordinate bound (lbvh.hip CRT_MAX_COORD)
+    }
+    if (bad) { atomicOr(a.flag, bad); return; }
+    float4* r = a.rec + 4 * (size_t)i;
+    r[0] = make_float4(w[0], w[1], w[2], w[3]);
+    r[1] = make_float4(w[4], w[5], w[6], w[7]);
+    r[2] = make_float4(w[8], w[9], w[10], w[11]);
+    r[3] = make_float4(__uint_as_float(a.mesh_root[mesh]), __uint_as_float(i), __uint_as_float(instance_is_identity(m) ? 1u : 0u), 0.f);
+    for (int k = 0; k < 6; ++k) a.box[6 * (size_t)i + k] = box[k];
+    for (int k = 0; k < 12; ++k) a.w2o[12 * (size_t)i + k] = w[k];
+}
+
+__global__ void __launch_bounds__(256) k_rebase_nodes(uint4* __restrict__ nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    uint4 r = nodes[5 * (size_t)i + 1];
+    r.x += node_off;
+    r.y += tri_off;
+    nodes[5 * (size_t)i + 1] = r;
+}
+
+__global__ void k_single_leaf(const float* __restrict__ box, crt_flatnode* __restrict__ flat, uint32_t* __restrict__ tri_order) {
+    if (threadIdx.x != 0) return;
+    crt_flatnode f;
+    for (int k = 0; k < 3; ++k) { f.bmin[k] = box[k]; f.bmax[k] = box[3 + k]; }
+    f.bmin[3] = 0.f;        // first slot
+    f.bmax[3] = 1.f;        // one primitive: a leaf
+    flat[0] = f;
+    tri_order[0] = 0u;
+}
+
+__global__ void __launch_bounds__(256) k_gather_instances(const float4* __restrict__ rec, const uint32_t* __restrict__ order, const int32_t* __restrict__ slots,
+                                                          uint32_t n, float4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t src = order[slots[i]];
+    for (int k = 0; k < 4; ++k) out[4 * (size_t)i + k] = rec[4 * (size_t)src + k];
+}
+
+// direction-dependent part of a walk's ray: octant and clamped reciprocal (traverse() / walk_pool's prologue)
+__device__ __forceinline__ void ray_setup(vec3 d, vec3& inv, bool& negx, bool& negy, bool& negz, uint32_t& oct4) {
+    const vec3 dc = V3(clamp_dir(d.x), clamp_dir(d.y), clamp_dir(d.z));
+    negx = dc.x < 0.0f; negy = dc.y < 0.0f; negz = dc.z < 0.0f;
+    oct4 = (negx ? 0u : 0x04040404u) | (negy ? 0u : 0x02020202u) | (negz ? 0u : 0x01010101u);
+    inv = V3(rcp_ieee(dc.x), rcp_ieee(dc.y), rcp_ieee(dc.z));
+}
+
+// One lane per ray, pools of 64 rays per wave with lane refill (k_trace's mapping with crt_trace's default pool of 64: each 256-ray slot
+// of the index space is walked by four single-wave workgroups), one loop and one LDS stack over both levels.  Stack entries: a node group (top byte set), the rest of a TLAS leaf (low 24 bits only) or the return marker (y == 0).
+template <bool ANY, bool STATS>
+__global__ void __launch_bounds__(64) k_trace_instances(InstTraceArgs a) {
+    extern __shared__ uint2 s_lds[];          // [level][lane] of the workgroup's one wave
+    const WaveId wid = wave_id(false, false, 2u);
+    const uint32_t lane = wid.lane;
+    uint2* const stk = s_lds + lane;
+    const int stack_entries = (int)a.stack_entries;
+    CRT_CHUNK_LOOP(it) {
+        const uint32_t v = static_pool_chunk<true>(wid, nullptr, a.n, it);
+        if (v == CRT_NO_WORK) break;
+        uint32_t next = dense_pool_first(v, wid.wave) + wid.sub * 64u;
+        if (next >= a.n) continue;
+        const uint32_t end = next + 64u < a.n ? next + 64u : a.n;
+        uint32_t idx = 0, nn = 0, nt = 0, inst_cur = 0;
+        vec3 wo = V3(0.f, 0.f, 0.f), wd = V3(0.f, 0.f, 1.f), o = wo, d = wd, inv = V3(0.f, 0.f, 0.f);
+        bool negx = false, negy = false, negz = false, in_blas = false;
+        uint32_t oct4 = 0;
+        float best_t = 0.f, best_u = 0.f, best_v = 0.f;
+        int best_id = -1, best_inst = -1;
+        int sp = 0;
+        uint2 cur = make_uint2(0u, 0u), tg = make_uint2(0u, 0u);
+        for (;;) {
+            bool busy = tg.y != 0u || (cur.y & 0xff000000u) != 0u;
+            if (next < end) {
+                const unsigned long long idle = __ballot(!busy);
+                const uint32_t n_idle = (uint32_t)__builtin_popcountll(idle);
+                if (n_idle >= a.refill_min || n_idle == 64u) {
+                    const uint32_t got = end - next < n_idle ? end - next : n_idle;
+                    const uint32_t rank = (uint32_t)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
+                    if (!busy && rank < got) {
+                        idx = next + rank;
+                        const float4 r0 = a.rays[2 * (size_t)idx], r1 = a.rays[2 * (size_t)idx + 1];
+                        wo = V3(r0.x, r0.y, r0.z); wd = V3(r1.x, r1.y, r1.z);
+                        o = wo; d = wd;
+                        best_t = r0.w; best_u = 0.f; best_v = 0.f; best_id = -1; best_inst = -1;
+                        nn = 0; nt = 0; sp = 0; in_blas = false;
+                        busy = true;
+                        // a non-finite origin hits nothing (traverse()); no instance: every ray misses
+                        const bool finite = __builtin_isfinite(o.x) && __builtin_isfinite(o.y) && __builtin_isfinite(o.z);
+                        ray_setup(d, inv, negx, negy, negz, oct4);
+                        cur = (finite && a.n_instances != 0u) ? make_uint2(0u, 0x80000000u) : make_uint2(0u, 0u);
+                        tg = make_uint2(0u, 0u);
+                    }
+                    next += got;
+                }
+            }
+            if (__ballot(busy) == 0ull) break;        // pool drained and every lane finished
+
+            // one step per iteration: a node step (TLAS or BLAS: the same code) or a leaf step (a triangle test, or entering an instance),
+            // with walk_pool's vote between the two
+            const bool has_tri = busy && tg.y != 0u;
+            const bool can_node = busy && !has_tri && (cur.y & 0xff000000u);
+            const uint32_t n_tri = (uint32_t)__builtin_popcountll(__ballot(has_tri));
+            const uint32_t n_node = (uint32_t)__builtin_popcountll(__ballot(can_node));
+            const bool node_phase = n_node != 0u && n_node >= a.tri_min * n_tri;
+            bool finished = false;
+            if (node_phase) {
+                if (can_node) {
+                    const uint32_t hits_imask = cur.y;
+                    const int off = 31 - __builtin_clz(hits_imask);
+                    const uint32_t nbase = cur.x;
+                    cur.y &= ~(1u << off);
+                    if (cur.y & 0xff000000u) { if (sp < stack_entries) { stk[sp * 64] = cur; ++sp; } else atomicAdd(a.overflow, 1u); }
+                    const uint32_t slot = (uint32_t)(off - 24) ^ (oct4 & 0xffu);
+                    const uint32_t nidx = nbase + (uint32_t)__builtin_popcount(hits_imask & ~(0xffffffffu << slot));
+                    const uint4* np = node_rows(a.nodes, nidx);
+                    const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3], n4 = np[4];
+                    if (STATS) ++nn;
+                    const uint32_t hitmask = node8_intersect(n0, n1, n2, n3, n4, o, inv, negx, negy, negz, oct4, best_t);
+                    cur.x = n1.x;
+                    tg.x = n1.y;
+                    cur.y = (hitmask & 0xff000000u) | (n0.w >> 24);
+                    tg.y = hitmask & 0x00ffffffu;
+                }
+            } else if (has_tri) {
+                const int b = 31 - __builtin_clz(tg.y);
+                tg.y &= ~(1u << b);
+                const uint32_t ti = tg.x + (uint32_t)b;
+                if (in_blas) {
+                    const float4* tp = tri_rows(a.tris, ti);
+                    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+                    if (STATS) ++nt;
+                    float u, vv, t;
+                    if (mt_test(ta, tb, tc, o, d, u, vv, t)) {
+                        if (ANY) {
+                            if (t < best_t) { best_inst = (int)inst_cur; finished = true; tg.y = 0u; }
+                        } else {
+                            // nearest t, then lowest instance, then lowest triangle id: independent of the order the TLAS hands out instances
+                            const int id = __float_as_int(ta.w);
+                            bool take = t < best_t;
+                            if (t == best_t && best_inst >= 0) take = (int)inst_cur < best_inst || ((int)inst_cur == best_inst && id < best_id);
+                            if (take) { best_t = t; best_u = u; best_v = vv; best_id = id; best_inst = (int)inst_cur; }
+                        }
+                    }
+                } else {
+                    // an instance: into its object space (fp32, no fma, direction not renormalised: t is the same parameter in both spaces)
+                    const float4* ip = a.inst + 4 * (size_t)ti;
+                    const float4 w0 = ip[0], w1 = ip[1], w2 = ip[2], w3 = ip[3];
+                    vec3 oo = wo, od = wd;
+                    if (__float_as_uint(w3.z) == 0u) {
+                        oo = V3(((w0.x * wo.x + w0.y * wo.y) + w0.z * wo.z) + w0.w, ((w1.x * wo.x + w1.y * wo.y) + w1.z * wo.z) + w1.w,
+                                ((w2.x * wo.x + w2.y * wo.y) + w2.z * wo.z) + w2.w);
+                        od = V3((w0.x * wd.x + w0.y * wd.y) + w0.z * wd.z, (w1.x * wd.x + w1.y * wd.y) + w1.z * wd.z, (w2.x * wd.x + w2.y * wd.y) + w2.z * wd.z);
+                    }
+                    // an object origin that is not finite hits nothing in this instance (traverse()): the instance is skipped
+                    if (__builtin_isfinite(oo.x) && __builtin_isfinite(oo.y) && __builtin_isfinite(oo.z)) {
+                        const int need = ((cur.y & 0xff000000u) ? 1 : 0) + (tg.y ? 1 : 0) + 1;
+                        if (sp + need <= stack_entries) {
+                            if (cur.y & 0xff000000u) { stk[sp * 64] = cur; ++sp; }
+                            if (tg.y) { stk[sp * 64] = tg; ++sp; }
+                            stk[sp * 64] = make_uint2(0u, 0u);      // return marker
+                            ++sp;
+                            o = oo; d = od;
+                            ray_setup(d, inv, negx, negy, negz, oct4);
+                            in_blas = true;
+                            inst_cur = __float_as_uint(w3.y);
+                            cur = make_uint2(__float_as_uint(w3.x), 0x80000000u);
+                            tg = make_uint2(0u, 0u);
+                        } else {
+                            atomicAdd(a.overflow, 1u);
+                        }
+                    }
+                }
+            }
+            // a lane with neither a leaf group nor inner hits left pops its stack (through a return marker: back to the world ray), or is done
+            if (busy && !finished && tg.y == 0u && !(cur.y & 0xff000000u)) {
+                for (;;) {
+                    if (sp == 0) { finished = true; break; }
+                    --sp;
+                    const uint2 e = stk[sp * 64];
+                    if (e.y == 0u) {
+                        o = wo; d = wd;
+                        ray_setup(d, inv, negx, negy, negz, oct4);
+                        in_blas = false;
+                        continue;
+                    }
+                    if (e.y & 0xff000000u) cur = e;
+                    else { tg = e; cur = make_uint2(0u, 0u); }
+                    break;
+                }
+            }
+            if (finished) {
+                const bool hit = best_inst >= 0;
+                float4 h;
+                h.x = ANY ? 0.f : (hit ? best_t : 0.f);
+                h.y = ANY ? 0.f : best_u;
+                h.z = ANY ? 0.f : best_v;
+                h.w = __int_as_float(ANY ? (hit ? 0 : -1) : (hit ? best_id : -1));
+                a.hits[idx] = h;
+                if (a.inst_out) a.inst_out[idx] = hit ? best_inst : -1;
+                if (STATS) a.stats[idx] = ((nt > 65535u ? 65535u : nt) << 16) | (nn > 65535u ? 65535u : nn);
+                cur = make_uint2(0u, 0u); tg = make_uint2(0u, 0u); sp = 0; in_blas = false;
+            }
+        }
+    }
+}
+
+static inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255u) / 256u)); }
+
+void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream) {
+    if (a.n) hipLaunchKernelGGL(k_instance_prep, grid_for(a.n), dim3(256), 0, stream, a);
+}
+void launch_rebase_nodes(void* d_nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off, hipStream_t stream) {
+    if (n8) hipLaunchKernelGGL(k_rebase_nodes, grid_for(n8), dim3(256), 0, stream, static_cast<uint4*>(d_nodes), n8, node_off, tri_off);
+}
+void launch_single_leaf(const float* d_box, crt_flatnode* d_flat, uint32_t* d_tri_order, hipStream_t stream) {
+    hipLaunchKernelGGL(k_single_leaf, dim3(1), dim3(64), 0, stream, d_box, d_flat, d_tri_order);
+}
+void launch_gather_instances(const float4* d_rec, const uint32_t* d_tri_order, const int32_t* d_tri_slots, uint32_t n, float4* d_out, hipStream_t stream) {
+    if (n) hipLaunchKernelGGL(k_gather_instances, grid_for(n), dim3(256), 0, stream, d_rec, d_tri_order, d_tri_slots, n, d_out);
+}
+void launch_trace_instances(const InstTraceArgs& a, int any, bool stats, uint32_t chunks, hipStream_t stream) {
+    const dim3 g(chunks * 16u), b(64);                      // sixteen single-wave workgroups per 1024-ray chunk: 64-ray pools (wave_id)
+    const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
+    if (any) {
+        if (stats) hipLaunchKernelGGL((k_trace_instances<true, true>), g, b, lds, stream, a);
+        else       hipLaunchKernelGGL((k_trace_instances<true, false>), g, b, lds, stream, a);
+    } else {
+        if (stats) hipLaunchKernelGGL((k_trace_instances<false, true>), g, b, lds, stream, a);
+        else       hipLaunchKernelGGL((k_trace_instances<false, false>), g, b, lds, stream, a);
+    }
+}
+
+// crt_warmup: load this translation unit's code object on the current device (device_build.hpp)
+int warm_instance_kernels() {
+    hipFuncAttributes at;
+    hipError_t e;
+    if ((e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_trace_instances<false, false>))) != hipSuccess) return (int)e;
+    if ((e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_instance_prep))) != hipSuccess) return (int)e;
+    return 0;
+}
+
+}  // namespace crt

@@ -1,0 +1,46 @@
+// Kernel argument blocks and launchers of instanced scenes (instances.hip), shared with crt_instances.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/crt.h"
+
+namespace crt {
+
+// Traversal-stack entries of the two-level walk: TLAS depth + deepest BLAS depth; create and set refuse more.
+#define CRT_INST_STACK_ENTRIES 40
+
+struct InstTraceArgs {
+    const uint4* nodes;        // ONE node8 array (5 x 16 B each): the TLAS from node 0, then every BLAS (child / triangle bases rebased)
+    const float4* tris;        // ONE record array (3 x 16 B each): every BLAS's records, (v0 | id in its mesh) (e1 | slot) (e2 | material)
+    const float4* inst;        // 4 x 16 B per TLAS leaf slot: world_to_object rows 0..2, (BLAS root node, instance index, identity, 0)
+    const float4* rays;        // crt_ray
+    float4* hits;              // crt_hit
+    int32_t* inst_out;         // instance of the hit, -1 = miss (may be null)
+    uint32_t* stats;           // optional: nodes | tris << 16
+    uint32_t n, n_instances, stack_entries, refill_min, tri_min;
+    uint32_t* overflow;        // += 1 per dropped stack push (never happens for a depth create / set accepted)
+};
+
+struct InstPrepArgs {
+    const uint32_t* in;        // crt_instance array, 16 words each
+    uint32_t n, n_meshes;
+    const float* mesh_box;     // 6 floats per mesh: the exact float box of its vertices
+    const uint32_t* mesh_root; // BLAS root node of each mesh in the shared node array
+    float4* rec;               // 4 rows per instance, instance order
+    float* box;                // 6 floats per instance: world box
+    float* w2o;                // 12 floats per instance: world_to_object
+    uint32_t* flag;            // |= 1 matrix not finite / singular / inverse not finite, 2 mesh index out of range, 4 world box beyond 1e18
+};
+
+void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream);
+// node8 i: child_base_index += node_off, triangle_base_index += tri_off
+void launch_rebase_nodes(void* d_nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off, hipStream_t stream);
+// the BVH2 of ONE box: a leaf root holding slot 0
+void launch_single_leaf(const float* d_box, crt_flatnode* d_flat, uint32_t* d_tri_order, hipStream_t stream);
+// out[i] = rec[tri_order[tri_slots[i]]] (4 rows): the instance records in CWBVH leaf order
+void launch_gather_instances(const float4* d_rec, const uint32_t* d_tri_order, const int32_t* d_tri_slots, uint32_t n, float4* d_out, hipStream_t stream);
+// `chunks`: 1024-ray chunks of the dense index space (k_trace's mapping), a multiple of 8
+void launch_trace_instances(const InstTraceArgs& a, int any, bool stats, uint32_t chunks, hipStream_t stream);
+
+}  // namespace crt

@@ -1104,7 +1104,8 @@ static size_t sah_tmp_bytes(size_t n, uint32_t flags) {
            P(std::max<size_t>(scan, 16)) + 4096;
 }
 
-static int sah_build_on_device(const int32_t* d_vidx, uint32_t stride, const float* d_verts, uint32_t n, uint32_t flags, DeviceArena& tmp, crt_flatnode* d_flat,
+// d_boxes == null: the triangles' boxes from k_tri_bounds; else the caller's leaf boxes (6 floats each, finite, |x| <= 1e18)
+static int sah_build_on_device(const int32_t* d_vidx, uint32_t stride, const float* d_verts, const float* d_boxes, uint32_t n, uint32_t flags, DeviceArena& tmp, crt_flatnode* d_flat,
                                uint32_t* d_tri_order, uint32_t* depth_out, float* device_ms, hipStream_t stream) {
     const uint32_t small = sah_small_of(flags);
     const size_t n_nodes = 2 * (size_t)n - 1, cap = (size_t)n / small + 4;
@@ -1154,7 +1155,8 @@ static int sah_build_on_device(const int32_t* d_vidx, uint32_t stride, const flo
     LB_HIPCHK(hipMemsetAsync(d_bad, 0, 4, stream));
     const dim3 gt((n + 255u) / 256u);
     LB_HIPCHK(hipEventRecord(ev0, stream));
-    hipLaunchKernelGGL(k_tri_bounds, dim3(std::min<uint32_t>(gt.x, 1024u)), dim3(256), 0, stream, d_vidx, stride, d_verts, n, d_leaf_box, d_scene);
+    if (!d_boxes) hipLaunchKernelGGL(k_tri_bounds, dim3(std::min<uint32_t>(gt.x, 1024u)), dim3(256), 0, stream, d_vidx, stride, d_verts, n, d_leaf_box, d_scene);
+    const float* leaf = d_boxes ? d_boxes : d_leaf_box;
     uint32_t* idx = d_tri_order; uint32_t* idx2 = d_idx2;
     uint32_t* pw = d_pw0; uint32_t* pw2 = d_pw1;
     SahWork* work = d_w0; SahWork* next = d_w1;
@@ -1174,12 +1176,12 @@ static int sah_build_on_device(const int32_t* d_vidx, uint32_t stride, const flo
     uint32_t bound = 1, sync_from = 0;
     while (((size_t)small << sync_from) < (size_t)n) ++sync_from;
     while (m > 0) {
-        hipLaunchKernelGGL(k_sah_cbounds, gc, dim3(256), 0, stream, idx, pw, n, d_leaf_box, work);
-        hipLaunchKernelGGL(k_sah_bin, gc, dim3(256), 0, stream, idx, pw, n, d_leaf_box, work, d_bins);
+        hipLaunchKernelGGL(k_sah_cbounds, gc, dim3(256), 0, stream, idx, pw, n, leaf, work);
+        hipLaunchKernelGGL(k_sah_bin, gc, dim3(256), 0, stream, idx, pw, n, leaf, work, d_bins);
         SahLists lists{d_counters, next, d_small, (uint32_t)cap, n / 2u + 2u, d_bad};
         hipLaunchKernelGGL(k_sah_sweep, dim3((bound + 3u) / 4u), dim3(256), 0, stream, work, d_bins, nd, lists, small);
         hipLaunchKernelGGL(k_sah_advance, dim3(1), dim3(1), 0, stream, d_counters);
-        hipLaunchKernelGGL(k_sah_flags, gt, dim3(256), 0, stream, idx, pw, n, d_leaf_box, work, d_fl);
+        hipLaunchKernelGGL(k_sah_flags, gt, dim3(256), 0, stream, idx, pw, n, leaf, work, d_fl);
         LB_HIPCHK(rocprim::exclusive_scan(d_tmp3, scan_bytes, d_fl, d_scan, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
         hipLaunchKernelGGL(k_sah_scatter, gt, dim3(256), 0, stream, idx, pw, n, work, d_fl, d_scan, idx2, pw2);
         std::swap(idx, idx2); std::swap(pw, pw2); std::swap(work, next);
@@ -1199,16 +1201,16 @@ static int sah_build_on_device(const int32_t* d_vidx, uint32_t stride, const flo
         hipLaunchKernelGGL(k_sah_small_counts, dim3((n_small + 255u) / 256u), dim3(256), 0, stream, d_small, n_small, d_fl);
         LB_HIPCHK(rocprim::exclusive_scan(d_tmp3, scan_bytes, d_fl, d_scan, 0u, (size_t)n_small, rocprim::plus<uint32_t>(), stream));
         const dim3 gs((n_small + 63u) / 64u);
-        if (small <= 8u) hipLaunchKernelGGL(k_sah_small<8>, gs, dim3(64), 0, stream, d_small, n_small, idx, d_leaf_box, nd, d_scan, nodes);
-        else if (small <= 16u) hipLaunchKernelGGL(k_sah_small<16>, gs, dim3(64), 0, stream, d_small, n_small, idx, d_leaf_box, nd, d_scan, nodes);
-        else hipLaunchKernelGGL(k_sah_small<SAH_SMALL>, gs, dim3(64), 0, stream, d_small, n_small, idx, d_leaf_box, nd, d_scan, nodes);
+        if (small <= 8u) hipLaunchKernelGGL(k_sah_small<8>, gs, dim3(64), 0, stream, d_small, n_small, idx, leaf, nd, d_scan, nodes);
+        else if (small <= 16u) hipLaunchKernelGGL(k_sah_small<16>, gs, dim3(64), 0, stream, d_small, n_small, idx, leaf, nd, d_scan, nodes);
+        else hipLaunchKernelGGL(k_sah_small<SAH_SMALL>, gs, dim3(64), 0, stream, d_small, n_small, idx, leaf, nd, d_scan, nodes);
     }
     if (idx != d_tri_order) LB_HIPCHK(hipMemcpyAsync(d_tri_order, idx, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
     const dim3 gn((uint32_t)((n_nodes + 255) / 256));
     hipLaunchKernelGGL(k_ploc_bfs_keys, gn, dim3(256), 0, stream, nd.parent2, (uint32_t)n_nodes, d_bkeys, d_ids, d_bad);
     LB_HIPCHK(rocprim::radix_sort_pairs(d_tmp2, sort2, d_bkeys, d_bkeys2, d_ids, d_order, n_nodes, 0, 64, stream));
     hipLaunchKernelGGL(k_bfs_pos, gn, dim3(256), 0, stream, d_order, (uint32_t)n_nodes, d_pos);
-    hipLaunchKernelGGL(k_sah_flatten, gn, dim3(256), 0, stream, d_order, d_pos, nd, d_tri_order, d_leaf_box, (uint32_t)n_nodes, d_flat, d_bad);
+    hipLaunchKernelGGL(k_sah_flatten, gn, dim3(256), 0, stream, d_order, d_pos, nd, d_tri_order, leaf, (uint32_t)n_nodes, d_flat, d_bad);
     hipLaunchKernelGGL(k_level_starts, gn, dim3(256), 0, stream, d_bkeys2, (uint32_t)n_nodes, d_levels, (uint32_t)kMaxLevels, 56u);
     uint32_t bad = 0;
     unsigned long long deepest_key = 0;
@@ -1244,7 +1246,7 @@ static int sah_build_on_device(const int32_t* d_vidx, uint32_t stride, const flo
 int lbvh_build_on_device(const int32_t* d_vidx, uint32_t stride, const float* d_verts, uint32_t n_tris_u, uint32_t flags, DeviceArena& tmp,
                          crt_flatnode* d_flat, uint32_t* d_tri_order, uint32_t* depth_out, float* device_ms, hipStream_t stream) {
     if ((flags & CRT_GPU_BUILD_SAH) && n_tris_u > 1u)
-        return sah_build_on_device(d_vidx, stride, d_verts, n_tris_u, flags, tmp, d_flat, d_tri_order, depth_out, device_ms, stream);
+        return sah_build_on_device(d_vidx, stride, d_verts, nullptr, n_tris_u, flags, tmp, d_flat, d_tri_order, depth_out, device_ms, stream);
     if ((flags & CRT_GPU_BUILD_PLOC) && n_tris_u > 1u)
         return ploc_build_on_device(d_vidx, stride, d_verts, n_tris_u, flags, tmp, d_flat, d_tri_order, depth_out, device_ms, stream);
     const size_t n_tris = n_tris_u;
@@ -1326,6 +1328,14 @@ int lbvh_build_on_device(const int32_t* d_vidx, uint32_t stride, const float* d_
     if (device_ms) *device_ms = ms;
     if (depth_out) *depth_out = n_levels - 1u;           // the deepest level holds leaves only
     return CRT_OK;
+}
+
+// The binned-SAH build over caller-given leaf boxes (the TLAS of an instanced scene, crt_instances_*): the same kernels the triangle build
+// runs after k_tri_bounds, on the boxes as given.
+int sah_build_from_boxes_on_device(const float* d_boxes, uint32_t n, uint32_t flags, DeviceArena& tmp, crt_flatnode* d_flat, uint32_t* d_tri_order,
+                                   uint32_t* depth_out, float* device_ms, hipStream_t stream) {
+    if (n < 2u) return fail(CRT_ERR_INVALID, "sah: a box build needs at least two boxes");
+    return sah_build_on_device(nullptr, 0u, nullptr, d_boxes, n, flags | CRT_GPU_BUILD_SAH, tmp, d_flat, d_tri_order, depth_out, device_ms, stream);
 }
 
 // crt_warmup: load this translation unit's code object on the current device (device_build.hpp)

@@ -1,0 +1,132 @@
+"""Instanced scenes: one bottom-level CWBVH per mesh, built once on the device, under a top-level CWBVH over transformed instances that
+is rebuilt on the device at every `set` (include/crt.h crt_instances_*).  Ray queries only: no frames."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_TRACE_CLOSEST, check, crt_blas_desc, crt_instances_info, lib
+from .host import _ptr
+from .scene import HIT_DT, RAY_DT, STATS_DT
+
+INSTANCE_DT = np.dtype([("object_to_world", "<f4", 12), ("mesh", "<u4"), ("reserved", "<u4", 3)])      # crt_instance, 64 B
+
+
+def instances_array(matrices, meshes):
+    """crt_instance records from (n, 3, 4) or (n, 12) object_to_world matrices (row-major, world = A p + t) and n mesh indices."""
+    m = np.asarray(matrices, np.float32).reshape(-1, 12)
+    out = np.zeros(m.shape[0], INSTANCE_DT)
+    out["object_to_world"] = m
+    out["mesh"] = np.asarray(meshes, np.uint32).reshape(-1)
+    return out
+
+
+def _build_flags(builder):
+    f = CRT_BUILD_LBVH_ON_DEVICE
+    if builder.startswith("ploc"):
+        f |= CRT_BUILD_PLOC | ((int(builder[4:]) if len(builder) > 4 else 0) << 8)
+    elif builder.startswith("sah"):
+        f |= CRT_BUILD_SAH | ((int(builder[3:]) if len(builder) > 3 else 0) << 8)
+    elif builder != "lbvh":
+        raise ValueError(f"unknown builder {builder!r}")
+    return f
+
+
+def instance_inverse(object_to_world):
+    """crt_instance_inverse [host]: world_to_object (12 floats) of a 3x4 object_to_world."""
+    m = np.ascontiguousarray(object_to_world, np.float32).reshape(12)
+    w = np.empty(12, np.float32)
+    check(lib().crt_instance_inverse(_ptr(m), _ptr(w)))
+    return w
+
+
+def instance_world_box(object_to_world, box):
+    """crt_instance_world_box [host]: the padded world box (lo[3], hi[3]) of an object box (lo[3], hi[3])."""
+    m = np.ascontiguousarray(object_to_world, np.float32).reshape(12)
+    b = np.ascontiguousarray(box, np.float32).reshape(6)
+    out = np.empty(6, np.float32)
+    check(lib().crt_instance_world_box(_ptr(m), _ptr(b), _ptr(out)))
+    return out
+
+
+class InstancedScene:
+    """meshes: Mesh objects (or (vertices, triangles) pairs, triangles (n, 12) int32 or (n, 3)); instances: an INSTANCE_DT array
+    (instances_array); capacity: the most instances a later `set` may hold (default: len(instances)); builder: "sah", "ploc", "lbvh"."""
+
+    def __init__(self, meshes, instances, capacity=None, builder="sah"):
+        self._h = C.c_void_p()
+        descs = (crt_blas_desc * len(meshes))()
+        self._keep = []
+        for k, m in enumerate(meshes):
+            v, t = (m.vertices, m.triangles) if hasattr(m, "vertices") else m
+            v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+            t = np.asarray(t, np.int32)
+            if t.ndim == 2 and t.shape[1] == 3:
+                t = np.concatenate([t, np.zeros((t.shape[0], 9), np.int32)], 1)
+            t = np.ascontiguousarray(t, np.int32).reshape(-1, 12)
+            self._keep += [v, t]
+            descs[k].vertices, descs[k].n_vertices = _ptr(v), v.shape[0]
+            descs[k].triangles, descs[k].n_triangles = _ptr(t), t.shape[0]
+        inst = np.ascontiguousarray(instances, INSTANCE_DT)
+        cap = inst.shape[0] if capacity is None else int(capacity)
+        check(lib().crt_instances_create(descs, len(meshes), _ptr(inst), inst.shape[0], cap, _build_flags(builder), C.byref(self._h)))
+        self._keep = []
+
+    def set(self, instances):
+        inst = np.ascontiguousarray(instances, INSTANCE_DT)
+        check(lib().crt_instances_set(self._h, _ptr(inst), inst.shape[0]))
+
+    def set_device(self, ptr, n, sync=True):
+        """instances already in device memory (e.g. a torch uint8 / float tensor of n * 64 bytes: pass tensor.data_ptr())."""
+        check(lib().crt_instances_set_device(self._h, C.c_void_p(ptr), int(n), 1 if sync else 0))
+
+    def trace(self, rays, mode=CRT_TRACE_CLOSEST, stats=False):
+        """-> (hits HIT_DT, instance ids int32 (-1 = miss)[, stats STATS_DT])"""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DT)
+        n = rays.shape[0]
+        hits, ids = np.empty(n, HIT_DT), np.empty(n, np.int32)
+        st = np.zeros(n, STATS_DT) if stats else None
+        check(lib().crt_instances_trace(self._h, _ptr(rays), n, _ptr(hits), _ptr(ids), int(mode), _ptr(st) if stats else None))
+        return (hits, ids, st) if stats else (hits, ids)
+
+    def trace_device(self, d_rays, n, d_hits, d_instance_ids=None, mode=CRT_TRACE_CLOSEST, d_stats=None, sync=True):
+        """device pointers (e.g. torch tensors' data_ptr()) of n crt_ray / crt_hit / int32 / crt_ray_stats records"""
+        check(lib().crt_instances_trace_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_hits),
+                                               C.c_void_p(d_instance_ids) if d_instance_ids else None, int(mode),
+                                               C.c_void_p(d_stats) if d_stats else None, 1 if sync else 0))
+
+    def _read(self, which, dtype, width):
+        n = C.c_size_t()
+        check(lib().crt_instances_debug_read(self._h, which, None, 0, C.byref(n)))
+        out = np.empty((n.value, width), dtype)
+        if n.value:
+            check(lib().crt_instances_debug_read(self._h, which, _ptr(out), out.nbytes, C.byref(n)))
+        return out
+
+    def world_to_object(self):
+        """(n, 12) float32: the device-computed inverse of every instance, instance order"""
+        return self._read(0, np.float32, 12)
+
+    def world_boxes(self):
+        return self._read(1, np.float32, 6)
+
+    def tlas_nodes(self):
+        return self._read(2, np.uint8, 80)
+
+    def info(self):
+        st = crt_instances_info()
+        check(lib().crt_instances_get_info(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def close(self):
+        if self._h:
+            lib().crt_instances_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+__all__ = ["InstancedScene", "INSTANCE_DT", "instances_array", "instance_inverse", "instance_world_box"]

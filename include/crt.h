@@ -408,10 +408,85 @@ int crt_warmup(void);
 /* 1 when the library carries the experimental kernel variants (built with -DCRT_EXPERIMENTS), else 0 */
 int crt_has_experiments(void);
 
+/* ------------------------------------------- instanced scenes (needs GPU) -- */
+
+/* Many copies of a mesh and rigid objects that move (no reference counterpart; DXR / Vulkan RT / OptiX call the two levels BLAS and
+ * TLAS).  A crt_instances handle is separate from crt_scene: it has no framebuffer, camera or frame path, only ray queries.
+ *
+ * A mesh as a bottom-level structure: positions and triangles in SOURCE order (a triangle's id is its index); only crt_triangle.v[0..2]
+ * are read. */
+typedef struct crt_blas_desc { const float* vertices; size_t n_vertices; const crt_triangle* triangles; size_t n_triangles; } crt_blas_desc;
+/* One instance: world = A * p + t, object_to_world row-major 3x4 (m[r*4 + c], column 3 = t); mesh = index into the create's meshes.
+ * 64 bytes. */
+typedef struct crt_instance { float object_to_world[12]; uint32_t mesh; uint32_t reserved[3]; } crt_instance;
+typedef struct crt_instances crt_instances;
+typedef struct crt_instances_info {
+    uint32_t n_meshes, n_instances, capacity;
+    uint32_t stack_entries;                   /* traversal-stack entries a ray may use: TLAS depth + deepest BLAS depth */
+    uint32_t tlas_nodes8, tlas_depth8, max_blas_depth8;
+    uint32_t stack_overflows;                 /* dropped stack pushes since create (0 unless something is wrong) */
+    uint64_t blas_nodes8, blas_tris;          /* every mesh once, whatever the instance count */
+    uint64_t blas_bytes, tlas_bytes, instance_bytes;   /* device bytes: BLAS nodes + records; TLAS region for `capacity`; per-instance buffers */
+    uint64_t tlas_build_bytes;                /* device bytes kept for the sets: the TLAS builder's temporaries and node staging for `capacity` */
+    float set_device_ms, set_wall_ms;         /* the last create / set: device time of its kernels, host wall time of the call */
+    float create_wall_ms, reserved_f;
+} crt_instances_info;
+
+/* Builds every mesh ONCE on the device with crt_scene_create's build-on-device path (build_flags: CRT_BUILD_* as crt_scene_desc; the
+ * CRT_BUILD_LBVH_ON_DEVICE bit is implied), packs all BLAS node8s behind a TLAS region sized for `capacity` (0 = n_instances) into one
+ * array and all triangle records into another, then sets the n_instances instances (crt_instances_set).  n_instances may be 0: every
+ * ray then misses.  One mesh shared by many instances costs the memory of one. */
+int crt_instances_create(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instance* instances, uint32_t n_instances,
+                         uint32_t capacity, uint32_t build_flags, crt_instances** out);
+/* New instances (n <= capacity; the count may change, 0 allowed).  Every instance is checked on the device first: a non-finite matrix,
+ * a singular one or one whose inverse is not finite, a mesh index out of range, a world box beyond 1e18, or n > capacity returns
+ * CRT_ERR_INVALID and leaves the previous instances tracing exactly as before.  Then per instance: world_to_object, the world box and
+ * the record; the TLAS is rebuilt on the device from the world boxes (binned SAH, then the CWBVH converter).  TLAS depth + deepest BLAS
+ * depth beyond the walk's stack (40 entries) returns CRT_ERR_LIMIT, also leaving the previous state.  Synchronous. */
+int crt_instances_set(crt_instances* s, const crt_instance* instances, uint32_t n_instances);
+/* the same with the crt_instance array in HBM on the handle's device (e.g. written by the caller's animation kernel); the check runs
+ * on the device, the host waits once for its verdict.  Returns when the set is done (sync is accepted for symmetry with the other
+ * *_device calls). */
+int crt_instances_set_device(crt_instances* s, const void* d_instances, uint32_t n_instances, int sync);
+/* Closest- or any-hit queries (mode CRT_TRACE_CLOSEST or CRT_TRACE_ANY; anything else is CRT_ERR_INVALID) over host rays.
+ * hits[i].tri = the triangle id within the mesh of instance_of_hit[i] (-1 and -1 on a miss); instance_of_hit and stats may be NULL.
+ * Numerical contract (tests/test_instances.py holds the kernel to it bit for bit):
+ *   - world_to_object (crt_instance_inverse) is computed in double and rounded once to float: the adjugate of A divided by det(A),
+ *     det expanded along the first row in the order written, translation 0 - (W_A . t) from the unrounded entries (0 -, so that the
+ *     identity maps to the identity bits).
+ *   - the object ray, each component in fp32 without fma: o'_r = ((W_r0*o.x + W_r1*o.y) + W_r2*o.z) + W_r3,
+ *     d'_r = (W_r0*d.x + W_r1*d.y) + W_r2*d.z; d' is NOT renormalised, so t is the same parameter in both spaces and tmax carries over.
+ *     An instance whose object_to_world is bitwise the identity uses o' = o, d' = d (signs of zeros kept: exactly a flat trace).
+ *   - inside a mesh the crt_trace contract holds unchanged (CWBVH walk, Moller-Trumbore, clamped slab directions); an origin that is not
+ *     finite, in world or in object space, hits nothing there.
+ *   - closest hit = the minimum of (t, instance index, triangle id), lexicographically, over all hits with 0 <= t < tmax: independent of
+ *     the order the TLAS visits instances.  Any hit: tri = 0 / -1 as crt_trace, instance_of_hit = SOME instance with a hit in [0, tmax).
+ *   - world boxes: the 8 corners of the mesh's float vertex box through object_to_world in double, widened by 2^-16 of the largest
+ *     absolute coordinate and rounded outward (crt_instance_world_box; DESIGN.md §11 sizes the margin).  The TLAS tests the WORLD ray
+ *     against these boxes while the hit is found on the rounded OBJECT ray, so the margin must cover that rounding.  It does when
+ *     cond_inf(A) * (2 |o|_inf + B + |t|_inf) <= 51 B, B = the largest absolute coordinate of the instance's exact world box, t its
+ *     translation.  EXCEPTION: beyond that bound (a ray from far away relative to B, e.g. a small instance near the origin seen from
+ *     ~1000x its size, or a badly conditioned A) a grazing hit within a few ulps of the box's surface can be culled by the TLAS, and
+ *     the closest / any hit above then misses it.
+ *   - stats: nodes = TLAS + BLAS node8 steps, tris = triangle tests, each clamped at 65535. */
+int crt_instances_trace(crt_instances* s, const crt_ray* rays, size_t n, crt_hit* hits, int32_t* instance_of_hit, int mode, crt_ray_stats* stats);
+/* the same with DEVICE pointers; asynchronous on the handle's stream unless sync != 0 */
+int crt_instances_trace_device(crt_instances* s, const void* d_rays, size_t n, void* d_hits, void* d_instance_of_hit, int mode, void* d_stats, int sync);
+int crt_instances_get_info(crt_instances* s, crt_instances_info* out);
+/* test hook: which 0 = world_to_object (12 floats per instance, instance order), 1 = world boxes (6 floats: lo, hi), 2 = TLAS node8s
+ * (80 B), 3 = instance records in TLAS leaf order (64 B: world_to_object rows, then BLAS root node, instance index, identity flag, 0).
+ * dst may be NULL to query the count. */
+int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_bytes, size_t* n_out);
+int crt_instances_destroy(crt_instances* s);
+
 /* --------------------------------------------------- host side ([host]) ----- */
 
 /* Caitlyn/Camera.h:7-19 Camera(pos, lookAt, fovDeg) + updateCamera :48-58 [host] */
 int crt_camera_look_at(const float pos[3], const float look_at[3], float fov_deg, crt_camera* out);
+/* The instance arithmetic of crt_instances_* on the host, bit for bit what the device computes: world_to_object of object_to_world
+ * (CRT_ERR_INVALID for a non-finite or singular matrix or a non-finite inverse), and the world box (lo[3], hi[3]) of an object box. */
+int crt_instance_inverse(const float object_to_world[12], float world_to_object[12]);
+int crt_instance_world_box(const float object_to_world[12], const float box[6], float out[6]);
 
 /* Caitlyn/Rnd.h:21-40 PCG_Hash / randf2 (state starts at 1, Rnd.h:7) [host] */
 uint32_t crt_pcg_hash(uint32_t x);
