@@ -16,6 +16,7 @@ CRT_OK, CRT_ERR_INVALID, CRT_ERR_NO_DEVICE, CRT_ERR_HIP, CRT_ERR_IO, CRT_ERR_LIM
 CRT_TRACE_CLOSEST, CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_TIE_LOWEST_ID = 0, 1, 2, 4
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
+CRT_INSTANCES_UPDATABLE = 1 << 16
 
 
 class CrtError(RuntimeError):
@@ -111,6 +112,9 @@ SYMBOLS = {
     "crt_instances_trace_device": (_I, [_P, _P, _SZ, _P, _P, _I, _P, _I]),
     "crt_instances_get_info": (_I, [_P, C.POINTER(crt_instances_info)]),
     "crt_instances_debug_read": (_I, [_P, _I, _P, _SZ, C.POINTER(_SZ)]),
+    "crt_instances_update_meshes": (_I, [_P, _P, _U32, _P, _P]),
+    "crt_instances_update_meshes_device": (_I, [_P, _P, _U32, _P, _P, _I]),
+    "crt_instances_last_update": (_I, [_P, C.POINTER(_F), C.POINTER(_F), C.POINTER(C.c_uint64)]),
     "crt_instances_destroy": (_I, [_P]),
     "crt_instance_inverse": (_I, [_P, _P]),
     "crt_instance_world_box": (_I, [_P, _P, _P]),

@@ -19,6 +19,7 @@
 #include "device_build.hpp"
 #include "host/instance_math.hpp"
 #include "instances.hpp"
+#include "instances_refit.hpp"
 #include "rt_kernels.hpp"
 
 using crt::fail;
@@ -31,6 +32,40 @@ using crt::fail;
     } while (0)
 
 static_assert(sizeof(crt_instance) == 64, "crt_instance is 64 bytes");
+
+// What crt_instances_update_meshes keeps (CRT_INSTANCES_UPDATABLE handles only).  Nothing here is read by the walk.
+struct InstUpdateState {
+    std::vector<uint32_t> nv, nt, tri_off;            // per mesh: vertices, triangles, first triangle in the index / record arrays
+    std::vector<uint64_t> v_off;                      // per mesh: first vertex of its host-form staging
+    std::vector<uint32_t> n_levels, level_first;      // per mesh: node8 depth levels and the index of its first entry in `level_start`
+    std::vector<uint32_t> level_start;                // per mesh, per level (+ end): position in d_order of the level's first node8
+    std::vector<float> mesh_box;                      // host copy of d_mesh_box
+    std::vector<float> box_stage;                     // the staged mesh boxes of the call in progress
+    std::vector<uint8_t> table;                       // the call's tables (InstRefitMesh, chunk starts, segments), uploaded at once
+    uint32_t max_levels = 0;
+    uint32_t* d_order = nullptr;                      // every BLAS node8 (global index), per mesh, level by level from the root
+    float* d_box8 = nullptr;                          // 6 floats per BLAS node8: its float box, which its parent's slot reads
+    int32_t* d_src_idx = nullptr;                     // 3 vertex indices per triangle, source order, mesh after mesh
+    uint32_t* d_live = nullptr;                       // the last accepted crt_instance array (capacity x 64 B)
+    float* d_mesh_box_stage = nullptr;                // 6 floats per mesh
+    float* d_vstage = nullptr;                        // the host form's positions, every mesh
+    uint32_t* d_check = nullptr;                      // 8 words per mesh of a call
+    uint32_t* h_check = nullptr;                      // pinned
+    uint8_t* d_table = nullptr;
+    size_t table_cap = 0;
+    uint64_t bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool have_times = false;
+    float device_ms = 0.f, wall_ms = 0.f;
+
+    ~InstUpdateState() {
+        void* bufs[] = {d_order, d_box8, d_src_idx, d_live, d_mesh_box_stage, d_vstage, d_check, d_table};
+        for (void* p : bufs) if (p) (void)hipFree(p);
+        if (h_check) (void)hipHostFree(h_check);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
 
 struct crt_instances {
     int device = 0;
@@ -63,11 +98,13 @@ struct crt_instances {
     // crt_instances_trace's device copies of the host rays
     void* d_t_rays = nullptr; void* d_t_hits = nullptr; void* d_t_inst = nullptr; void* d_t_stats = nullptr;
     size_t t_cap = 0;
+    std::unique_ptr<InstUpdateState> upd;     // CRT_INSTANCES_UPDATABLE only
 
     ~crt_instances() {
         void* bufs[] = {d_nodes, d_tris, d_inst, d_w2o, d_wbox, d_mesh_box, d_mesh_root, d_in, d_rec, d_box, d_w2o_stage, d_flag, d_overflow,
                         d_t8_stage, d_t_rays, d_t_hits, d_t_inst, d_t_stats};
         if (stream) (void)hipStreamSynchronize(stream);
+        upd.reset();
         for (void* p : bufs) if (p) (void)hipFree(p);
         arena.release();
         if (ev0) (void)hipEventDestroy(ev0);
@@ -129,6 +166,68 @@ int build_blas(const crt_blas_desc& m, uint32_t gpu_flags, hipStream_t st, crt_n
     return CRT_OK;
 }
 
+// The TLAS of n instances (crt_instance array in DEVICE memory) into staging: the prep kernel (the host waits once for its verdict) against
+// the mesh boxes d_mesh_box, the SAH build over the world boxes, the converter into the node staging buffer, the stack bound.  Nothing the
+// walk reads changes here.  `who` prefixes the messages.
+struct TlasStage {
+    crt_instances* s = nullptr;
+    crt_node8* d_t8 = nullptr;
+    uint32_t n8 = 0, depth8 = 0, stack = 2;
+    ~TlasStage() { if (s && d_t8 && d_t8 != s->d_t8_stage) (void)hipFree(d_t8); }
+};
+
+int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const float* d_mesh_box, const std::string& who, TlasStage& ts) {
+    hipStream_t st = s->stream;
+    ts.s = s;
+    IHIPCHK(hipMemsetAsync(s->d_flag, 0, 4, st));
+    crt::InstPrepArgs pa{};
+    pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = s->n_meshes; pa.mesh_box = d_mesh_box; pa.mesh_root = s->d_mesh_root;
+    pa.rec = s->d_rec; pa.box = s->d_box; pa.w2o = s->d_w2o_stage; pa.flag = s->d_flag;
+    crt::launch_instance_prep(pa, st);
+    uint32_t flag = 0;
+    IHIPCHK(hipMemcpyAsync(&flag, s->d_flag, 4, hipMemcpyDeviceToHost, st));
+    IHIPCHK(hipStreamSynchronize(st));
+    IHIPCHK(hipGetLastError());
+    if (flag)
+        return fail(CRT_ERR_INVALID, who + ((flag & 1u) ? "a matrix is not finite, or singular, or its inverse is not finite"
+                                            : (flag & 2u) ? "a mesh index is out of range" : "a world box exceeds 1e18"));
+    // the TLAS over the world boxes
+    s->arena.used = s->arena_mark;
+    float ms = 0.f;
+    int rc;
+    if (n == 1) {
+        crt::launch_single_leaf(s->d_box, s->d_flat, s->d_tri_order, st);
+    } else {
+        uint32_t depth2 = 0;
+        rc = crt::sah_build_from_boxes_on_device(s->d_box, n, CRT_GPU_BUILD_SAH, s->arena, s->d_flat, s->d_tri_order, &depth2, &ms, st);
+        if (rc) return fail(rc, who + "TLAS build failed: " + crt_last_error());
+        s->arena.used = s->arena_mark;
+    }
+    // into the staging node buffer sized for `capacity` at create: no allocation (and no device-wide hipFree) per set
+    rc = crt::cwbvh_convert_on_device(s->d_flat, n == 1 ? 1u : 2u * n - 1u, n, s->arena, s->d_tri_slots, &ts.d_t8, nullptr, &ts.n8, &ts.depth8, &ms, st,
+                                      s->d_t8_stage, s->tlas_cap_nodes);
+    if (rc) return fail(rc, who + "TLAS BVH2 -> CWBVH failed: " + crt_last_error());
+    ts.stack = std::max<uint32_t>(2u, ts.depth8 + s->max_blas_depth8);
+    if (ts.stack > CRT_INST_STACK_ENTRIES)
+        return fail(CRT_ERR_LIMIT, who + "TLAS depth + deepest BLAS exceed the walk's stack (" + std::to_string(ts.stack) + " > " +
+                                       std::to_string(CRT_INST_STACK_ENTRIES) + " entries)");
+    if (ts.n8 > s->tlas_cap_nodes) return fail(CRT_ERR_HIP, who + "TLAS larger than its region");
+    return CRT_OK;
+}
+
+// everything checked: publish the staged TLAS (it starts at node 0, its leaves index the instance records: no rebase), records, matrices
+// and boxes; an updatable handle keeps the instances themselves (d_src, when it is not that copy already) for its updates.  Enqueued only.
+int publish_tlas(crt_instances* s, const void* d_src, uint32_t n, const TlasStage& ts) {
+    hipStream_t st = s->stream;
+    IHIPCHK(hipMemcpyAsync(s->d_nodes, ts.d_t8, (size_t)ts.n8 * sizeof(crt_node8), hipMemcpyDeviceToDevice, st));
+    crt::launch_gather_instances(s->d_rec, s->d_tri_order, s->d_tri_slots, n, s->d_inst, st);
+    IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+    IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+    if (s->upd && d_src != s->upd->d_live)
+        IHIPCHK(hipMemcpyAsync(s->upd->d_live, d_src, (size_t)n * sizeof(crt_instance), hipMemcpyDeviceToDevice, st));
+    return CRT_OK;
+}
+
 // Validate + prepare n instances from DEVICE memory, then rebuild the TLAS.  Nothing the walk reads changes before every check passed.
 int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -136,50 +235,12 @@ int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
     hipStream_t st = s->stream;
     IHIPCHK(hipEventRecord(s->ev0, st));
     if (n > 0) {
-        IHIPCHK(hipMemsetAsync(s->d_flag, 0, 4, st));
-        crt::InstPrepArgs pa{};
-        pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = s->n_meshes; pa.mesh_box = s->d_mesh_box; pa.mesh_root = s->d_mesh_root;
-        pa.rec = s->d_rec; pa.box = s->d_box; pa.w2o = s->d_w2o_stage; pa.flag = s->d_flag;
-        crt::launch_instance_prep(pa, st);
-        uint32_t flag = 0;
-        IHIPCHK(hipMemcpyAsync(&flag, s->d_flag, 4, hipMemcpyDeviceToHost, st));
-        IHIPCHK(hipStreamSynchronize(st));
-        IHIPCHK(hipGetLastError());
-        if (flag)
-            return fail(CRT_ERR_INVALID, std::string("crt_instances_set: ") +
-                                             ((flag & 1u) ? "a matrix is not finite, or singular, or its inverse is not finite"
-                                              : (flag & 2u) ? "a mesh index is out of range" : "a world box exceeds 1e18"));
-        // the TLAS over the world boxes
-        s->arena.used = s->arena_mark;
-        uint32_t n8 = 0, depth8 = 0;
-        float ms = 0.f;
-        int rc;
-        if (n == 1) {
-            crt::launch_single_leaf(s->d_box, s->d_flat, s->d_tri_order, st);
-        } else {
-            uint32_t depth2 = 0;
-            rc = crt::sah_build_from_boxes_on_device(s->d_box, n, CRT_GPU_BUILD_SAH, s->arena, s->d_flat, s->d_tri_order, &depth2, &ms, st);
-            if (rc) return fail(rc, std::string("crt_instances_set: TLAS build failed: ") + crt_last_error());
-            s->arena.used = s->arena_mark;
-        }
-        // into the staging node buffer sized for `capacity` at create: no allocation (and no device-wide hipFree) per set
-        crt_node8* d_t8 = nullptr;
-        rc = crt::cwbvh_convert_on_device(s->d_flat, n == 1 ? 1u : 2u * n - 1u, n, s->arena, s->d_tri_slots, &d_t8, nullptr, &n8, &depth8, &ms, st,
-                                          s->d_t8_stage, s->tlas_cap_nodes);
-        if (rc) return fail(rc, std::string("crt_instances_set: TLAS BVH2 -> CWBVH failed: ") + crt_last_error());
-        struct Free { void* p; ~Free() { if (p) (void)hipFree(p); } } t8_guard{d_t8 == s->d_t8_stage ? nullptr : d_t8};
-        const uint32_t stack = std::max<uint32_t>(2u, depth8 + s->max_blas_depth8);
-        if (stack > CRT_INST_STACK_ENTRIES)
-            return fail(CRT_ERR_LIMIT, "crt_instances_set: TLAS depth + deepest BLAS exceed the walk's stack (" + std::to_string(stack) + " > " +
-                                           std::to_string(CRT_INST_STACK_ENTRIES) + " entries)");
-        if (n8 > s->tlas_cap_nodes) return fail(CRT_ERR_HIP, "crt_instances_set: TLAS larger than its region");
-        // everything checked: publish (the TLAS starts at node 0, its leaves index the instance records: no rebase)
-        IHIPCHK(hipMemcpyAsync(s->d_nodes, d_t8, (size_t)n8 * sizeof(crt_node8), hipMemcpyDeviceToDevice, st));
-        crt::launch_gather_instances(s->d_rec, s->d_tri_order, s->d_tri_slots, n, s->d_inst, st);
-        IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
-        IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+        TlasStage ts;
+        int rc = stage_tlas(s, d_src, n, s->d_mesh_box, "crt_instances_set: ", ts);
+        if (rc) return rc;
+        if ((rc = publish_tlas(s, d_src, n, ts))) return rc;
         IHIPCHK(hipStreamSynchronize(st));            // the publication is done when the call returns
-        s->n_tlas8 = n8; s->tlas_depth8 = depth8; s->stack_entries = stack;
+        s->n_tlas8 = ts.n8; s->tlas_depth8 = ts.depth8; s->stack_entries = ts.stack;
     } else {
         s->n_tlas8 = 0; s->tlas_depth8 = 0; s->stack_entries = 2;
     }
@@ -189,6 +250,208 @@ int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
     IHIPCHK(hipEventSynchronize(s->ev1));
     IHIPCHK(hipEventElapsedTime(&s->set_device_ms, s->ev0, s->ev1));
     s->set_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// CRT_INSTANCES_UPDATABLE: the refit state, once at create.  Level discovery runs on each BLAS as built (bases not rebased yet: parent
+// links and depths by refit.hip's kernels), the counting sort by depth on the host; the order holds global node indices.
+int init_update_state(crt_instances* s, const crt_blas_desc* meshes, const std::vector<crt_node8*>& blas_nodes, const std::vector<uint32_t>& blas_n8,
+                      const std::vector<uint32_t>& roots, const std::vector<float>& mesh_box) {
+    std::unique_ptr<InstUpdateState> u(new (std::nothrow) InstUpdateState);
+    if (!u) return fail(CRT_ERR_NOMEM, "crt_instances_create: out of memory");
+    hipStream_t st = s->stream;
+    const uint32_t M = s->n_meshes;
+    const uint64_t n8_all = s->blas_nodes8, tris_all = s->blas_tris;
+    u->nv.resize(M); u->nt.resize(M); u->tri_off.resize(M); u->v_off.resize(M); u->n_levels.resize(M); u->level_first.resize(M);
+    u->mesh_box = mesh_box;
+    uint64_t v_total = 0, t_off = 0;
+    std::vector<int32_t> idx(3 * tris_all);
+    for (uint32_t k = 0; k < M; ++k) {
+        u->nv[k] = (uint32_t)meshes[k].n_vertices; u->nt[k] = (uint32_t)meshes[k].n_triangles; u->tri_off[k] = (uint32_t)t_off;
+        u->v_off[k] = v_total;
+        for (size_t i = 0; i < meshes[k].n_triangles; ++i)
+            for (int j = 0; j < 3; ++j) idx[3 * (t_off + i) + j] = meshes[k].triangles[i].v[j];
+        v_total += meshes[k].n_vertices; t_off += meshes[k].n_triangles;
+    }
+    if (v_total >= (1ull << 32) / 12) return fail(CRT_ERR_LIMIT, "crt_instances_create: more vertices than an updatable handle stages");
+    int rc;
+    if ((rc = alloc(&u->d_src_idx, idx.size())) || (rc = alloc(&u->d_order, n8_all)) || (rc = alloc(&u->d_box8, 6 * n8_all)) ||
+        (rc = alloc(&u->d_live, 16 * (size_t)s->capacity)) || (rc = alloc(&u->d_mesh_box_stage, 6 * (size_t)M)) ||
+        (rc = alloc(&u->d_vstage, 3 * v_total)) || (rc = alloc(&u->d_check, 8 * (size_t)M)))
+        return rc;
+    IHIPCHK(hipHostMalloc(reinterpret_cast<void**>(&u->h_check), 8 * (size_t)M * sizeof(uint32_t)));
+    IHIPCHK(hipEventCreate(&u->ev0));
+    IHIPCHK(hipEventCreate(&u->ev1));
+    IHIPCHK(hipMemcpyAsync(u->d_src_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
+    IHIPCHK(hipMemsetAsync(u->d_box8, 0, 24 * n8_all, st));
+    // levels: parents and depths of every BLAS into one temporary pair
+    int32_t* d_parent = nullptr;
+    uint8_t* d_depth = nullptr;
+    struct Guard { void* a; void* b; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } g{nullptr, nullptr};
+    if ((rc = alloc(&d_parent, n8_all))) return rc;
+    g.a = d_parent;
+    if ((rc = alloc(&d_depth, n8_all))) return rc;
+    g.b = d_depth;
+    IHIPCHK(hipMemsetAsync(d_parent, 0xff, n8_all * 4, st));
+    uint64_t off = 0;
+    for (uint32_t k = 0; k < M; ++k) {
+        crt::launch_node8_parents(blas_nodes[k], 5u, blas_n8[k], d_parent + off, st);
+        crt::launch_depths(d_parent + off, blas_n8[k], d_depth + off, st);
+        off += blas_n8[k];
+    }
+    std::vector<uint8_t> depth(n8_all);
+    IHIPCHK(hipMemcpyAsync(depth.data(), d_depth, n8_all, hipMemcpyDeviceToHost, st));
+    IHIPCHK(hipStreamSynchronize(st));
+    IHIPCHK(hipGetLastError());
+    std::vector<uint32_t> order(n8_all);
+    off = 0;
+    for (uint32_t k = 0; k < M; ++k) {
+        std::vector<uint32_t> count(257, 0);
+        for (uint32_t i = 0; i < blas_n8[k]; ++i) ++count[depth[off + i] + 1u];
+        uint32_t levels = 0;
+        for (uint32_t d = 0; d < 256; ++d) if (count[d + 1]) levels = d + 1;
+        u->n_levels[k] = levels;
+        u->level_first[k] = (uint32_t)u->level_start.size();
+        std::vector<uint32_t> cursor(levels + 1, (uint32_t)off);
+        for (uint32_t d = 0; d < levels; ++d) cursor[d + 1] = cursor[d] + count[d + 1];
+        u->level_start.insert(u->level_start.end(), cursor.begin(), cursor.end());
+        for (uint32_t i = 0; i < blas_n8[k]; ++i) order[cursor[depth[off + i]]++] = roots[k] + i;
+        u->max_levels = std::max(u->max_levels, levels);
+        off += blas_n8[k];
+    }
+    IHIPCHK(hipMemcpyAsync(u->d_order, order.data(), n8_all * 4, hipMemcpyHostToDevice, st));
+    // the call's tables: InstRefitMesh, chunk starts and record segments per mesh, level segments per mesh and level
+    auto A = [](size_t b) { return (b + 15) & ~size_t(15); };
+    u->table_cap = A(M * sizeof(crt::InstRefitMesh)) + A(M * 4) + A(M * sizeof(crt::InstRefitSeg)) +
+                   (size_t)M * u->max_levels * sizeof(crt::InstRefitSeg);
+    if ((rc = alloc(&u->d_table, u->table_cap))) return rc;
+    IHIPCHK(hipStreamSynchronize(st));            // before the host arrays go
+    u->bytes = 4 * n8_all + 24 * n8_all + 12 * tris_all + 64 * (uint64_t)s->capacity + 24 * (uint64_t)M + 12 * v_total + 32 * (uint64_t)M +
+               u->table_cap;
+    s->upd = std::move(u);
+    return CRT_OK;
+}
+
+float key_to_float(uint32_t key) {
+    const uint32_t b = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+}
+
+// New positions for n distinct meshes (h_verts: host arrays, or d_verts: device arrays).  Order: check + mesh boxes on the
+// device (one host wait), the prep of the live instances and the TLAS into staging against the staged mesh boxes, and only then the BLAS
+// refit in place and the publication.  A refused call has written nothing the walk reads.
+int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* const* h_verts, const void* const* d_verts, const size_t* n_vertices,
+                const std::string& who) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s) return fail(CRT_ERR_INVALID, who + "null handle");
+    InstUpdateState* u = s->upd.get();
+    if (!u) return fail(CRT_ERR_INVALID, who + "the handle was created without CRT_INSTANCES_UPDATABLE");
+    if (n && (!ids || !n_vertices || (!h_verts && !d_verts))) return fail(CRT_ERR_INVALID, who + "null argument");
+    if (n > s->n_meshes) return fail(CRT_ERR_INVALID, who + "more meshes than the handle holds");
+    std::vector<char> seen(s->n_meshes, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t m = ids[k];
+        if (m >= s->n_meshes) return fail(CRT_ERR_INVALID, who + "mesh index " + std::to_string(m) + " is out of range");
+        if (seen[m]) return fail(CRT_ERR_INVALID, who + "mesh index " + std::to_string(m) + " is repeated");
+        seen[m] = 1;
+        if (h_verts ? !h_verts[k] : !d_verts[k]) return fail(CRT_ERR_INVALID, who + "null vertices");
+        if (n_vertices[k] != u->nv[m]) return fail(CRT_ERR_INVALID, who + "n_vertices of mesh " + std::to_string(m) + " differs from the count given at create");
+    }
+    if (n == 0) return CRT_OK;
+    IHIPCHK(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    // the call's tables
+    auto A = [](size_t b) { return (b + 15) & ~size_t(15); };
+    const size_t o_chunk = A(n * sizeof(crt::InstRefitMesh)), o_rseg = o_chunk + A(n * 4), o_lseg = o_rseg + A(n * sizeof(crt::InstRefitSeg));
+    u->table.assign(o_lseg + (size_t)n * u->max_levels * sizeof(crt::InstRefitSeg), 0);
+    auto* tm = reinterpret_cast<crt::InstRefitMesh*>(u->table.data());
+    auto* tc = reinterpret_cast<uint32_t*>(u->table.data() + o_chunk);
+    auto* tr = reinterpret_cast<crt::InstRefitSeg*>(u->table.data() + o_rseg);
+    auto* tl = reinterpret_cast<crt::InstRefitSeg*>(u->table.data() + o_lseg);
+    uint32_t chunks = 0, recs = 0, levels = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t m = ids[k];
+        const float* v = nullptr;
+        if (h_verts) {
+            float* dst = u->d_vstage + 3 * u->v_off[m];
+            IHIPCHK(hipMemcpyAsync(dst, h_verts[k], (size_t)u->nv[m] * 12, hipMemcpyHostToDevice, st));
+            v = dst;
+        } else {
+            v = static_cast<const float*>(d_verts[k]);
+        }
+        tm[k] = crt::InstRefitMesh{v, u->nv[m], u->nt[m], u->tri_off[m], 0u};
+        tc[k] = chunks;
+        chunks += (std::max(u->nv[m], u->nt[m]) + crt::kCheckChunk - 1) / crt::kCheckChunk;
+        tr[k] = crt::InstRefitSeg{recs, u->tri_off[m], k, 0u};
+        recs += u->nt[m];
+        levels = std::max(levels, u->n_levels[m]);
+    }
+    // level L: a segment per mesh that reaches it
+    std::vector<uint32_t> lseg_at(levels + 1, 0), lcount(levels, 0);
+    uint32_t n_lseg = 0;
+    for (uint32_t L = 0; L < levels; ++L) {
+        lseg_at[L] = n_lseg;
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t m = ids[k];
+            if (u->n_levels[m] <= L) continue;
+            const uint32_t a = u->level_start[u->level_first[m] + L], b = u->level_start[u->level_first[m] + L + 1];
+            tl[n_lseg++] = crt::InstRefitSeg{lcount[L], a, k, 0u};
+            lcount[L] += b - a;
+        }
+    }
+    lseg_at[levels] = n_lseg;
+    IHIPCHK(hipMemcpyAsync(u->d_table, u->table.data(), u->table.size(), hipMemcpyHostToDevice, st));
+    const auto* d_tm = reinterpret_cast<const crt::InstRefitMesh*>(u->d_table);
+    const auto* d_tc = reinterpret_cast<const uint32_t*>(u->d_table + o_chunk);
+    const auto* d_tr = reinterpret_cast<const crt::InstRefitSeg*>(u->d_table + o_rseg);
+    const auto* d_tl = reinterpret_cast<const crt::InstRefitSeg*>(u->d_table + o_lseg);
+
+    // 1. the coordinates and the new mesh boxes: the one wait for a verdict before the TLAS build
+    IHIPCHK(hipEventRecord(u->ev0, st));
+    IHIPCHK(hipMemsetAsync(u->d_check, 0, (size_t)n * 32, st));
+    crt::launch_inst_check(d_tm, d_tc, n, chunks, u->d_src_idx, u->d_check, st);
+    IHIPCHK(hipMemcpyAsync(u->h_check, u->d_check, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+    IHIPCHK(hipStreamSynchronize(st));
+    IHIPCHK(hipGetLastError());
+    u->box_stage = u->mesh_box;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t* c = u->h_check + 8 * (size_t)k;
+        if (c[0]) return fail(CRT_ERR_INVALID, who + "a vertex coordinate of mesh " + std::to_string(ids[k]) + " is not finite or exceeds 1e18");
+        for (int a = 0; a < 3; ++a) {
+            u->box_stage[6 * (size_t)ids[k] + a] = key_to_float(~c[4 + a]);
+            u->box_stage[6 * (size_t)ids[k] + 3 + a] = key_to_float(c[1 + a]);
+        }
+    }
+    IHIPCHK(hipMemcpyAsync(u->d_mesh_box_stage, u->box_stage.data(), u->box_stage.size() * 4, hipMemcpyHostToDevice, st));
+    // 2. + 3. the live instances against the staged boxes, and their TLAS, into staging
+    const uint32_t ni = s->n_instances;
+    TlasStage ts;
+    if (ni > 0) {
+        const int rc = stage_tlas(s, u->d_live, ni, u->d_mesh_box_stage, who, ts);
+        if (rc) return rc;
+    }
+    // 4. the BLAS refit in place (records first: the leaf slots read only their id words), then the publication
+    crt::launch_inst_refit_records(s->d_tris, (uint32_t)s->blas_tris, d_tr, n, recs, d_tm, u->d_src_idx, st);
+    const uint32_t n_nodes = s->tlas_cap_nodes + (uint32_t)s->blas_nodes8;
+    for (uint32_t L = levels; L-- > 0;)
+        crt::launch_inst_refit_node8_level(s->d_nodes, s->tlas_cap_nodes, n_nodes, u->d_order, d_tl + lseg_at[L], lseg_at[L + 1] - lseg_at[L],
+                                           lcount[L], s->d_tris, (uint32_t)s->blas_tris, d_tm, u->d_src_idx, u->d_box8, st);
+    if (hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, who + "refit launch failed");
+    if (ni > 0) {
+        const int rc = publish_tlas(s, u->d_live, ni, ts);
+        if (rc) return rc;
+    }
+    IHIPCHK(hipMemcpyAsync(s->d_mesh_box, u->d_mesh_box_stage, u->box_stage.size() * 4, hipMemcpyDeviceToDevice, st));
+    IHIPCHK(hipEventRecord(u->ev1, st));
+    IHIPCHK(hipStreamSynchronize(st));
+    IHIPCHK(hipGetLastError());
+    if (ni > 0) { s->n_tlas8 = ts.n8; s->tlas_depth8 = ts.depth8; s->stack_entries = ts.stack; }
+    u->mesh_box.swap(u->box_stage);
+    IHIPCHK(hipEventElapsedTime(&u->device_ms, u->ev0, u->ev1));
+    u->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    u->have_times = true;
     return CRT_OK;
 }
 
@@ -254,12 +517,15 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     if ((rc = alloc(&s->d_nodes, nodes_total * 5))) return rc;
     if ((rc = alloc(&s->d_tris, tris_total * 3))) return rc;
     std::vector<uint32_t> roots(n_meshes);
+    std::vector<crt_node8*> blas_nodes(n_meshes);
+    std::vector<uint32_t> blas_n8(n_meshes);
     uint64_t node_off = s->tlas_cap_nodes, tri_off = 0;
     for (uint32_t k = 0; k < n_meshes; ++k) {
         IHIPCHK(hipMemcpyAsync(s->d_nodes + 5 * node_off, blas[k].nodes, (size_t)blas[k].n8 * sizeof(crt_node8), hipMemcpyDeviceToDevice, st));
         IHIPCHK(hipMemcpyAsync(s->d_tris + 3 * tri_off, blas[k].recs, meshes[k].n_triangles * 48, hipMemcpyDeviceToDevice, st));
         crt::launch_rebase_nodes(s->d_nodes + 5 * node_off, blas[k].n8, (uint32_t)node_off, (uint32_t)tri_off, st);
         roots[k] = (uint32_t)node_off;
+        blas_nodes[k] = blas[k].nodes; blas_n8[k] = blas[k].n8;
         node_off += blas[k].n8; tri_off += meshes[k].n_triangles;
     }
     s->blas_nodes8 = nodes_total - s->tlas_cap_nodes; s->blas_tris = tris_total;
@@ -285,6 +551,7 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     s->arena_mark = s->arena.used;
     IHIPCHK(hipStreamSynchronize(st));
     IHIPCHK(hipGetLastError());
+    if ((build_flags & CRT_INSTANCES_UPDATABLE) && (rc = init_update_state(s, meshes, blas_nodes, blas_n8, roots, mesh_box))) return rc;
     if (n_instances) {
         IHIPCHK(hipMemcpyAsync(s->d_in, instances, (size_t)n_instances * sizeof(crt_instance), hipMemcpyHostToDevice, st));
         if ((rc = set_impl(s, s->d_in, n_instances))) return fail(rc, std::string("crt_instances_create: ") + crt_last_error());
@@ -412,7 +679,9 @@ int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_
         case 1: src = s->d_wbox; n = s->n_instances; item = 24; break;
         case 2: src = s->d_nodes; n = s->n_tlas8; item = sizeof(crt_node8); break;
         case 3: src = s->d_inst; n = s->n_instances; item = 64; break;
-        default: return fail(CRT_ERR_INVALID, "crt_instances_debug_read: which must be 0..3");
+        case 4: src = s->d_nodes + 5 * (size_t)s->tlas_cap_nodes; n = s->blas_nodes8; item = sizeof(crt_node8); break;
+        case 5: src = s->d_tris; n = s->blas_tris; item = 48; break;
+        default: return fail(CRT_ERR_INVALID, "crt_instances_debug_read: which must be 0..5");
     }
     if (n_out) *n_out = n;
     if (!dst || n == 0) return CRT_OK;
@@ -420,6 +689,36 @@ int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_
     IHIPCHK(hipSetDevice(s->device));
     IHIPCHK(hipStreamSynchronize(s->stream));
     IHIPCHK(hipMemcpy(dst, src, n * item, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+int crt_instances_update_meshes(crt_instances* s, const uint32_t* mesh_ids, uint32_t n, const float* const* vertices, const size_t* n_vertices) {
+    if (n && !vertices) return fail(CRT_ERR_INVALID, "crt_instances_update_meshes: null vertices");
+    try {
+        return update_impl(s, mesh_ids, n, vertices, nullptr, n_vertices, "crt_instances_update_meshes: ");
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_instances_update_meshes: ") + e.what());
+    }
+}
+
+int crt_instances_update_meshes_device(crt_instances* s, const uint32_t* mesh_ids, uint32_t n, const void* const* d_vertices, const size_t* n_vertices,
+                                       int sync) {
+    if (n && !d_vertices) return fail(CRT_ERR_INVALID, "crt_instances_update_meshes_device: null vertices");
+    (void)sync;                                   // the TLAS rebuild waits on the host: an update always returns done, as a set does
+    try {
+        return update_impl(s, mesh_ids, n, nullptr, d_vertices, n_vertices, "crt_instances_update_meshes_device: ");
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_instances_update_meshes_device: ") + e.what());
+    }
+}
+
+int crt_instances_last_update(crt_instances* s, float* device_ms, float* wall_ms, uint64_t* state_bytes) {
+    if (state_bytes) *state_bytes = (s && s->upd) ? s->upd->bytes : 0;
+    if (!s) return fail(CRT_ERR_INVALID, "crt_instances_last_update: null handle");
+    if (!s->upd) return fail(CRT_ERR_INVALID, "crt_instances_last_update: the handle was created without CRT_INSTANCES_UPDATABLE");
+    if (!s->upd->have_times) return fail(CRT_ERR_INVALID, "crt_instances_last_update: no update yet");
+    if (device_ms) *device_ms = s->upd->device_ms;
+    if (wall_ms) *wall_ms = s->upd->wall_ms;
     return CRT_OK;
 }
 

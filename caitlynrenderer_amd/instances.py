@@ -1,10 +1,12 @@
 """Instanced scenes: one bottom-level CWBVH per mesh, built once on the device, under a top-level CWBVH over transformed instances that
-is rebuilt on the device at every `set` (include/crt.h crt_instances_*).  Ray queries only: no frames."""
+is rebuilt on the device at every `set` (include/crt.h crt_instances_*).  An updatable scene also moves the vertices of its
+meshes: a GPU refit of their BLASes and a TLAS rebuild per update.  Ray queries only: no frames."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_TRACE_CLOSEST, check, crt_blas_desc, crt_instances_info, lib
+from ._lib import (CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_INSTANCES_UPDATABLE, CRT_TRACE_CLOSEST, check, crt_blas_desc,
+                   crt_instances_info, lib)
 from .host import _ptr
 from .scene import HIT_DT, RAY_DT, STATS_DT
 
@@ -50,9 +52,10 @@ def instance_world_box(object_to_world, box):
 
 class InstancedScene:
     """meshes: Mesh objects (or (vertices, triangles) pairs, triangles (n, 12) int32 or (n, 3)); instances: an INSTANCE_DT array
-    (instances_array); capacity: the most instances a later `set` may hold (default: len(instances)); builder: "sah", "ploc", "lbvh"."""
+    (instances_array); capacity: the most instances a later `set` may hold (default: len(instances)); builder: "sah", "ploc", "lbvh";
+    updatable: keep the refit state of update_meshes (CRT_INSTANCES_UPDATABLE)."""
 
-    def __init__(self, meshes, instances, capacity=None, builder="sah"):
+    def __init__(self, meshes, instances, capacity=None, builder="sah", updatable=False):
         self._h = C.c_void_p()
         descs = (crt_blas_desc * len(meshes))()
         self._keep = []
@@ -68,7 +71,8 @@ class InstancedScene:
             descs[k].triangles, descs[k].n_triangles = _ptr(t), t.shape[0]
         inst = np.ascontiguousarray(instances, INSTANCE_DT)
         cap = inst.shape[0] if capacity is None else int(capacity)
-        check(lib().crt_instances_create(descs, len(meshes), _ptr(inst), inst.shape[0], cap, _build_flags(builder), C.byref(self._h)))
+        flags = _build_flags(builder) | (CRT_INSTANCES_UPDATABLE if updatable else 0)
+        check(lib().crt_instances_create(descs, len(meshes), _ptr(inst), inst.shape[0], cap, flags, C.byref(self._h)))
         self._keep = []
 
     def set(self, instances):
@@ -78,6 +82,31 @@ class InstancedScene:
     def set_device(self, ptr, n, sync=True):
         """instances already in device memory (e.g. a torch uint8 / float tensor of n * 64 bytes: pass tensor.data_ptr())."""
         check(lib().crt_instances_set_device(self._h, C.c_void_p(ptr), int(n), 1 if sync else 0))
+
+    def update_meshes(self, vertices_by_mesh):
+        """{mesh index: (n, 3) float32 positions in the create's order}: one crt_instances_update_meshes call for all of them."""
+        ids = np.array(list(vertices_by_mesh.keys()), np.uint32)
+        vs = [np.ascontiguousarray(v, np.float32).reshape(-1, 3) for v in vertices_by_mesh.values()]
+        ptrs = (C.c_void_p * max(len(vs), 1))(*[v.ctypes.data for v in vs])
+        counts = np.array([v.shape[0] for v in vs], np.uint64)
+        check(lib().crt_instances_update_meshes(self._h, _ptr(ids), len(vs), ptrs, _ptr(counts)))
+
+    def update_mesh(self, k, vertices):
+        self.update_meshes({k: vertices})
+
+    def update_meshes_device(self, ptrs_by_mesh, sync=True):
+        """{mesh index: (device pointer, n_vertices)}: positions already in device memory (e.g. a torch float32 tensor's data_ptr())."""
+        ids = np.array(list(ptrs_by_mesh.keys()), np.uint32)
+        items = list(ptrs_by_mesh.values())
+        ptrs = (C.c_void_p * max(len(items), 1))(*[int(p) for p, _ in items])
+        counts = np.array([int(nv) for _, nv in items], np.uint64)
+        check(lib().crt_instances_update_meshes_device(self._h, _ptr(ids), len(items), ptrs, _ptr(counts), 1 if sync else 0))
+
+    def last_update(self):
+        """{device_ms, wall_ms, state_bytes} of the last update (crt_instances_last_update)"""
+        d, w, b = C.c_float(), C.c_float(), C.c_uint64()
+        check(lib().crt_instances_last_update(self._h, C.byref(d), C.byref(w), C.byref(b)))
+        return {"device_ms": d.value, "wall_ms": w.value, "state_bytes": b.value}
 
     def trace(self, rays, mode=CRT_TRACE_CLOSEST, stats=False):
         """-> (hits HIT_DT, instance ids int32 (-1 = miss)[, stats STATS_DT])"""
@@ -111,6 +140,18 @@ class InstancedScene:
 
     def tlas_nodes(self):
         return self._read(2, np.uint8, 80)
+
+    def instance_records(self):
+        """(n, 16) float32: the instance records in TLAS leaf order (row 3: BLAS root node, instance index, identity flag as uint32 bits)"""
+        return self._read(3, np.float32, 16)
+
+    def blas_nodes(self):
+        """(n, 80) uint8: every BLAS node8 of the packed array (after the TLAS region; child / triangle bases rebased)"""
+        return self._read(4, np.uint8, 80)
+
+    def blas_records(self):
+        """(n, 12) float32: every BLAS record, (v0 | id) (e1 | slot) (e2 | w); the w words are int32 bits"""
+        return self._read(5, np.float32, 12)
 
     def info(self):
         st = crt_instances_info()

@@ -438,6 +438,9 @@ typedef struct crt_instances_info {
  * ray then misses.  One mesh shared by many instances costs the memory of one. */
 int crt_instances_create(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instance* instances, uint32_t n_instances,
                          uint32_t capacity, uint32_t build_flags, crt_instances** out);
+/* crt_instances_create's build_flags only (bits 0..15 are crt_scene_desc's): keep the state crt_instances_update_meshes needs.  Without
+ * it a handle allocates nothing for updates and every update returns CRT_ERR_INVALID. */
+enum { CRT_INSTANCES_UPDATABLE = 1u << 16 };
 /* New instances (n <= capacity; the count may change, 0 allowed).  Every instance is checked on the device first: a non-finite matrix,
  * a singular one or one whose inverse is not finite, a mesh index out of range, a world box beyond 1e18, or n > capacity returns
  * CRT_ERR_INVALID and leaves the previous instances tracing exactly as before.  Then per instance: world_to_object, the world box and
@@ -473,8 +476,29 @@ int crt_instances_trace(crt_instances* s, const crt_ray* rays, size_t n, crt_hit
 /* the same with DEVICE pointers; asynchronous on the handle's stream unless sync != 0 */
 int crt_instances_trace_device(crt_instances* s, const void* d_rays, size_t n, void* d_hits, void* d_instance_of_hit, int mode, void* d_stats, int sync);
 int crt_instances_get_info(crt_instances* s, crt_instances_info* out);
+/* Moving meshes under an updatable handle (CRT_INSTANCES_UPDATABLE): new positions for n DISTINCT meshes in one call,
+ * vertices[k] = float xyz of mesh mesh_ids[k] in the create's order, n_vertices[k] = the create's count.  The topology is kept: within
+ * each updated BLAS the node8 boxes are re-quantised (byte-identical to crt_cwbvh_refit of that BLAS with its bases un-rebased) and the
+ * records get new v0, e1, e2 (make_record's fp32 subtractions; the w words stay).  The mesh box becomes the box of the vertices its
+ * triangles reference, under the total order of the floats (-0 below +0, for lo and hi alike; create keeps the value seen first of two
+ * equal zeros, so the two agree whenever the mesh box has no signed-zero tie).  Every instance of an updated mesh gets its new world box
+ * (crt_instance_world_box), and the TLAS is rebuilt from all boxes as crt_instances_set does; instances, world_to_object and the other
+ * meshes stay.  All or nothing: a coordinate that is not finite or exceeds 1e18 (any of the n arrays' vertices), a wrong count, a mesh
+ * index out of range or repeated, a null pointer, a handle without CRT_INSTANCES_UPDATABLE, or a world box beyond 1e18 returns
+ * CRT_ERR_INVALID; TLAS depth + deepest BLAS beyond the walk's 40 entries returns CRT_ERR_LIMIT.  Either way nothing the walk reads has
+ * changed and the previous geometry traces on bit for bit.  Closest hits after an update to V equal those of a fresh crt_instances_create
+ * from V (the minimum of (t, instance, id) does not depend on the tree), the grazing-margin exception above aside.  Synchronous. */
+int crt_instances_update_meshes(crt_instances* s, const uint32_t* mesh_ids, uint32_t n, const float* const* vertices, const size_t* n_vertices);
+/* the same with the positions in HBM on the handle's device (mesh_ids, n_vertices and the pointer array itself are host memory).  Returns
+ * when the update is done; sync is accepted for symmetry. */
+int crt_instances_update_meshes_device(crt_instances* s, const uint32_t* mesh_ids, uint32_t n, const void* const* d_vertices, const size_t* n_vertices,
+                                       int sync);
+/* device ms and host wall ms of the last update (CRT_ERR_INVALID before the first one) and the device bytes the refit state holds
+ * (filled for an updatable handle even then; 0 otherwise).  Any pointer may be NULL. */
+int crt_instances_last_update(crt_instances* s, float* device_ms, float* wall_ms, uint64_t* state_bytes);
 /* test hook: which 0 = world_to_object (12 floats per instance, instance order), 1 = world boxes (6 floats: lo, hi), 2 = TLAS node8s
- * (80 B), 3 = instance records in TLAS leaf order (64 B: world_to_object rows, then BLAS root node, instance index, identity flag, 0).
+ * (80 B), 3 = instance records in TLAS leaf order (64 B: world_to_object rows, then BLAS root node, instance index, identity flag, 0),
+ * 4 = every BLAS node8 (80 B; the packed region after the TLAS region, bases rebased), 5 = every BLAS record (48 B).
  * dst may be NULL to query the count. */
 int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_bytes, size_t* n_out);
 int crt_instances_destroy(crt_instances* s);
