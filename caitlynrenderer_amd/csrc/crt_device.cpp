@@ -24,6 +24,7 @@
 #include "device_build.hpp"
 #include "host/cwbvh.hpp"
 #include "host/flatnode_link.hpp"
+#include "host/refit_core.hpp"
 #include "rt_kernels.hpp"
 
 using crt::fail;
@@ -79,9 +80,11 @@ struct RefitState {
     float* d_verts = nullptr;                // the host form's upload of the positions
     uint32_t* d_check = nullptr;             // k_check_vertices: non-finite flag, max keys, complemented min keys
     uint32_t* h_check = nullptr;             // pinned
-    uint32_t* d_order8 = nullptr;            // node8 indices level by level, root level first; level8[l] = first entry of level l (+ end)
-    uint32_t* d_order2 = nullptr;            // the same for the BVH2
-    std::vector<uint32_t> level8, level2;
+    uint32_t* d_order = nullptr;             // node8 indices level by level, root level first, then the BVH2's the same way
+    std::vector<uint32_t> level8, level2;    // level8[l] = position in d_order of node8 level l (+ end); level2 the same for the BVH2
+    crt::RefitMesh* d_mesh = nullptr;        // the scene as one refit mesh (its vertex pointer changes between calls) ...
+    crt::RefitMesh* h_mesh = nullptr;        // ... sent from here, pinned
+    crt::RefitSeg* d_seg = nullptr;          // the one segment of every launch: entries from 0, items from 0, mesh 0
     float* d_box8 = nullptr;                 // the float box of every node8 (6 floats), which its parent's slot reads
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
     std::vector<hipEvent_t> ev_peer;         // per peer, on its device: "the peer's stream is done with the old scene"
@@ -89,9 +92,10 @@ struct RefitState {
     float device_ms = 0.f, wall_ms = 0.f;
     ~RefitState() {
         (void)hipSetDevice(device);
-        void* ptrs[] = {d_verts, d_check, d_order8, d_order2, d_box8};
+        void* ptrs[] = {d_verts, d_check, d_order, d_box8, d_mesh, d_seg};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         if (h_check) (void)hipHostFree(h_check);
+        if (h_mesh) (void)hipHostFree(h_mesh);
         if (ev_a) (void)hipEventDestroy(ev_a);
         if (ev_b) (void)hipEventDestroy(ev_b);
         for (hipEvent_t e : ev_peer) if (e) (void)hipEventDestroy(e);
@@ -2305,37 +2309,6 @@ int crt_trace(crt_scene* s, const crt_ray* rays, size_t n, crt_hit* hits, int mo
 // place on the scene's device (refit.hip), one launch per tree level, deepest first.  The frame path reads none of the state kept for
 // this, and a scene that never updates allocates none of it.
 
-// the node indices of a tree level by level (root level first): parent links and depths on the device, the counting sort on the host.
-// Once per scene, at its first update.
-static int discover_levels(crt_scene* s, bool node8, uint32_t n, uint32_t** d_order, std::vector<uint32_t>& level) {
-    int32_t* d_parent = nullptr;
-    uint8_t* d_depth = nullptr;
-    struct Guard { void* a; void* b; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } g{nullptr, nullptr};
-    int rc;
-    if ((rc = dev_alloc(&d_parent, n))) return rc;
-    g.a = d_parent;
-    if ((rc = dev_alloc(&d_depth, n))) return rc;
-    g.b = d_depth;
-    HIPCHK(hipMemsetAsync(d_parent, 0xff, (size_t)n * sizeof(int32_t), s->stream));
-    if (node8) crt::launch_node8_parents(s->d_nodes, (uint32_t)CRT_NODE_ROWS, n, d_parent, s->stream);
-    else       crt::launch_bvh2_parents(s->d_bvh2, n, d_parent, s->stream);
-    crt::launch_depths(d_parent, n, d_depth, s->stream);
-    std::vector<uint8_t> depth(n);
-    HIPCHK(hipMemcpyAsync(depth.data(), d_depth, n, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    std::vector<uint32_t> count(257, 0);
-    for (uint32_t i = 0; i < n; ++i) ++count[depth[i] + 1u];
-    uint32_t levels = 0;
-    for (uint32_t d = 0; d < 256; ++d) if (count[d + 1]) levels = d + 1;
-    level.assign(levels + 1, 0);
-    for (uint32_t d = 0; d < levels; ++d) level[d + 1] = level[d] + count[d + 1];
-    std::vector<uint32_t> order(n), cursor(level.begin(), level.end() - 1);
-    for (uint32_t i = 0; i < n; ++i) order[cursor[depth[i]]++] = i;
-    if ((rc = dev_alloc(d_order, n))) return rc;
-    HIPCHK(hipMemcpy(*d_order, order.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return CRT_OK;
-}
-
 static int ensure_refit_state(crt_scene* s) {
     if (s->refit) return CRT_OK;
     std::unique_ptr<RefitState> owner(new (std::nothrow) RefitState);
@@ -2348,8 +2321,16 @@ static int ensure_refit_state(crt_scene* s) {
     HIPCHK(hipEventCreate(&r->ev_a));
     HIPCHK(hipEventCreate(&r->ev_b));
     if ((rc = dev_alloc(&r->d_box8, 6 * (size_t)s->info.n_nodes8))) return rc;
-    if ((rc = discover_levels(s, true, (uint32_t)s->info.n_nodes8, &r->d_order8, r->level8))) return rc;
-    if (s->d_bvh2 && (rc = discover_levels(s, false, (uint32_t)s->info.n_bvh2_nodes, &r->d_order2, r->level2))) return rc;
+    if ((rc = dev_alloc(&r->d_mesh, 1)) || (rc = dev_alloc(&r->d_seg, 1))) return rc;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_mesh), sizeof(crt::RefitMesh)));
+    HIPCHK(hipMemsetAsync(r->d_seg, 0, sizeof(crt::RefitSeg), s->stream));
+    // the levels of both trees, found once (parent links and depths on the device, a counting sort of the depths on the host)
+    const crt::RefitTree trees[2] = {{s->d_nodes, false, (uint32_t)CRT_NODE_ROWS, (uint32_t)s->info.n_nodes8, 0u},
+                                     {s->d_bvh2, true, 0u, (uint32_t)s->info.n_bvh2_nodes, 0u}};
+    std::vector<std::vector<uint32_t>> level;
+    if ((rc = crt::discover_levels(trees, s->d_bvh2 ? 2 : 1, s->stream, &r->d_order, level))) return rc;
+    r->level8 = std::move(level[0]);
+    if (s->d_bvh2) r->level2 = std::move(level[1]);
     s->refit = owner.release();
     return CRT_OK;
 }
@@ -2358,13 +2339,6 @@ static size_t scene_buf_bytes(const crt_scene* s, const void* member) {
     const size_t off = (size_t)(reinterpret_cast<const char*>(member) - reinterpret_cast<const char*>(s));
     for (const auto& b : s->scene_bufs) if (b.first == off) return b.second;
     return 0;
-}
-
-static float key_to_float(uint32_t key) {
-    const uint32_t b = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-    float f;
-    std::memcpy(&f, &b, 4);
-    return f;
 }
 
 // d_verts: device positions (the scene's own upload or the caller's); normals / lights: host arrays or null
@@ -2397,6 +2371,10 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
     HIPCHK(hipMemcpyAsync(r->h_check, r->d_check, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (r->h_check[0]) return fail(CRT_ERR_INVALID, "crt_update_vertices: a vertex coordinate is not finite or exceeds 1e18");
+    // the scene as one refit mesh: d_triangles in leaf-slot order, keyed by the slot in e1.w.  The stream is idle here, so the previous
+    // call's copy of h_mesh is done; the refit launches read it after this copy, in stream order.
+    *r->h_mesh = crt::RefitMesh{verts, reinterpret_cast<const int32_t*>(s->d_triangles), 12u, (uint32_t)s->n_slots, 1u, nv};
+    HIPCHK(hipMemcpyAsync(r->d_mesh, r->h_mesh, sizeof(crt::RefitMesh), hipMemcpyHostToDevice, st));
 
     // every stream that reads the scene's buffers is done with the old scene before they change (its own stream is, by order)
     r->ev_peer.resize(s->peers.size(), nullptr);
@@ -2413,22 +2391,22 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
 
     HIPCHK(hipEventRecord(r->ev_a, st));
     const uint32_t n8 = (uint32_t)s->info.n_nodes8, n_tris8 = (uint32_t)s->info.n_tris8, n_slots = (uint32_t)s->n_slots;
-    crt::launch_refit_records(s->d_tris, (uint32_t)CRT_TRI_ROWS, n_tris8, s->d_triangles, n_slots, verts, 0, st);
-    if (s->d_tris2) crt::launch_refit_records(s->d_tris2, 3u, n_slots, s->d_triangles, n_slots, verts, 1, st);
+    crt::launch_refit_records(s->d_tris, (uint32_t)CRT_TRI_ROWS, n_tris8, r->d_seg, 1u, n_tris8, r->d_mesh, st);
+    if (s->d_tris2) crt::launch_refit_records(s->d_tris2, 3u, n_slots, r->d_seg, 1u, n_slots, r->d_mesh, st);
     if (s->d_bvh2)
         for (size_t l = r->level2.size() - 1; l-- > 0;)
-            crt::launch_refit_bvh2_level(s->d_bvh2, (uint32_t)s->info.n_bvh2_nodes, r->d_order2 + r->level2[l], r->level2[l + 1] - r->level2[l],
+            crt::launch_refit_bvh2_level(s->d_bvh2, (uint32_t)s->info.n_bvh2_nodes, r->d_order + r->level2[l], r->level2[l + 1] - r->level2[l],
                                          s->d_triangles, n_slots, verts, st);
     for (size_t l = r->level8.size() - 1; l-- > 0;)
-        crt::launch_refit_node8_level(s->d_nodes, (uint32_t)CRT_NODE_ROWS, n8, r->d_order8 + r->level8[l], r->level8[l + 1] - r->level8[l], s->d_tris,
-                                      (uint32_t)CRT_TRI_ROWS, n_tris8, s->d_triangles, n_slots, verts, r->d_box8, st);
+        crt::launch_refit_node8_level(s->d_nodes, (uint32_t)CRT_NODE_ROWS, 0u, n8, r->d_order + r->level8[l], r->d_seg, 1u, r->level8[l + 1] - r->level8[l],
+                                      s->d_tris, (uint32_t)CRT_TRI_ROWS, n_tris8, r->d_mesh, r->d_box8, st);
     if (s->d_planes) crt::launch_expand_planes(s->d_nodes, (uint32_t)CRT_NODE_ROWS, s->d_planes, n8, st);
     if (hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, "crt_update_vertices: refit launch failed");
     HIPCHK(hipEventRecord(r->ev_b, st));
 
     // the new bounds (ray_bins / sort_shadow cell grid), a new tile-cost measurement, and the sum cleared as crt_reset does
     float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { hi[k] = key_to_float(r->h_check[1 + k]); lo[k] = key_to_float(~r->h_check[4 + k]); }
+    for (int k = 0; k < 3; ++k) { hi[k] = crt::rf::key_to_float(r->h_check[1 + k]); lo[k] = crt::rf::key_to_float(~r->h_check[4 + k]); }
     auto refresh = [&](crt_scene* x) -> int {
         for (int k = 0; k < 3; ++k) { x->bounds_lo[k] = lo[k]; x->bounds_hi[k] = hi[k]; }
         x->tile_state = crt_scene::TILES_WANT;

@@ -18,8 +18,8 @@
 #include "crt_error.hpp"
 #include "device_build.hpp"
 #include "host/instance_math.hpp"
+#include "host/refit_core.hpp"
 #include "instances.hpp"
-#include "instances_refit.hpp"
 #include "rt_kernels.hpp"
 
 using crt::fail;
@@ -37,11 +37,10 @@ static_assert(sizeof(crt_instance) == 64, "crt_instance is 64 bytes");
 struct InstUpdateState {
     std::vector<uint32_t> nv, nt, tri_off;            // per mesh: vertices, triangles, first triangle in the index / record arrays
     std::vector<uint64_t> v_off;                      // per mesh: first vertex of its host-form staging
-    std::vector<uint32_t> n_levels, level_first;      // per mesh: node8 depth levels and the index of its first entry in `level_start`
-    std::vector<uint32_t> level_start;                // per mesh, per level (+ end): position in d_order of the level's first node8
+    std::vector<std::vector<uint32_t>> level;         // per mesh, per level (+ end): position in d_order of the level's first node8
     std::vector<float> mesh_box;                      // host copy of d_mesh_box
     std::vector<float> box_stage;                     // the staged mesh boxes of the call in progress
-    std::vector<uint8_t> table;                       // the call's tables (InstRefitMesh, chunk starts, segments), uploaded at once
+    std::vector<uint8_t> table;                       // the call's tables (RefitMesh, chunk starts, segments), uploaded at once
     uint32_t max_levels = 0;
     uint32_t* d_order = nullptr;                      // every BLAS node8 (global index), per mesh, level by level from the root
     float* d_box8 = nullptr;                          // 6 floats per BLAS node8: its float box, which its parent's slot reads
@@ -253,8 +252,8 @@ int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
     return CRT_OK;
 }
 
-// CRT_INSTANCES_UPDATABLE: the refit state, once at create.  Level discovery runs on each BLAS as built (bases not rebased yet: parent
-// links and depths by refit.hip's kernels), the counting sort by depth on the host; the order holds global node indices.
+// CRT_INSTANCES_UPDATABLE: the refit state, once at create.  Level discovery runs on each BLAS as built (bases not rebased yet); the order
+// holds global node indices.
 int init_update_state(crt_instances* s, const crt_blas_desc* meshes, const std::vector<crt_node8*>& blas_nodes, const std::vector<uint32_t>& blas_n8,
                       const std::vector<uint32_t>& roots, const std::vector<float>& mesh_box) {
     std::unique_ptr<InstUpdateState> u(new (std::nothrow) InstUpdateState);
@@ -262,7 +261,7 @@ int init_update_state(crt_instances* s, const crt_blas_desc* meshes, const std::
     hipStream_t st = s->stream;
     const uint32_t M = s->n_meshes;
     const uint64_t n8_all = s->blas_nodes8, tris_all = s->blas_tris;
-    u->nv.resize(M); u->nt.resize(M); u->tri_off.resize(M); u->v_off.resize(M); u->n_levels.resize(M); u->level_first.resize(M);
+    u->nv.resize(M); u->nt.resize(M); u->tri_off.resize(M); u->v_off.resize(M);
     u->mesh_box = mesh_box;
     uint64_t v_total = 0, t_off = 0;
     std::vector<int32_t> idx(3 * tris_all);
@@ -275,7 +274,7 @@ int init_update_state(crt_instances* s, const crt_blas_desc* meshes, const std::
     }
     if (v_total >= (1ull << 32) / 12) return fail(CRT_ERR_LIMIT, "crt_instances_create: more vertices than an updatable handle stages");
     int rc;
-    if ((rc = alloc(&u->d_src_idx, idx.size())) || (rc = alloc(&u->d_order, n8_all)) || (rc = alloc(&u->d_box8, 6 * n8_all)) ||
+    if ((rc = alloc(&u->d_src_idx, idx.size())) || (rc = alloc(&u->d_box8, 6 * n8_all)) ||
         (rc = alloc(&u->d_live, 16 * (size_t)s->capacity)) || (rc = alloc(&u->d_mesh_box_stage, 6 * (size_t)M)) ||
         (rc = alloc(&u->d_vstage, 3 * v_total)) || (rc = alloc(&u->d_check, 8 * (size_t)M)))
         return rc;
@@ -284,59 +283,19 @@ int init_update_state(crt_instances* s, const crt_blas_desc* meshes, const std::
     IHIPCHK(hipEventCreate(&u->ev1));
     IHIPCHK(hipMemcpyAsync(u->d_src_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
     IHIPCHK(hipMemsetAsync(u->d_box8, 0, 24 * n8_all, st));
-    // levels: parents and depths of every BLAS into one temporary pair
-    int32_t* d_parent = nullptr;
-    uint8_t* d_depth = nullptr;
-    struct Guard { void* a; void* b; ~Guard() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } g{nullptr, nullptr};
-    if ((rc = alloc(&d_parent, n8_all))) return rc;
-    g.a = d_parent;
-    if ((rc = alloc(&d_depth, n8_all))) return rc;
-    g.b = d_depth;
-    IHIPCHK(hipMemsetAsync(d_parent, 0xff, n8_all * 4, st));
-    uint64_t off = 0;
-    for (uint32_t k = 0; k < M; ++k) {
-        crt::launch_node8_parents(blas_nodes[k], 5u, blas_n8[k], d_parent + off, st);
-        crt::launch_depths(d_parent + off, blas_n8[k], d_depth + off, st);
-        off += blas_n8[k];
-    }
-    std::vector<uint8_t> depth(n8_all);
-    IHIPCHK(hipMemcpyAsync(depth.data(), d_depth, n8_all, hipMemcpyDeviceToHost, st));
-    IHIPCHK(hipStreamSynchronize(st));
-    IHIPCHK(hipGetLastError());
-    std::vector<uint32_t> order(n8_all);
-    off = 0;
-    for (uint32_t k = 0; k < M; ++k) {
-        std::vector<uint32_t> count(257, 0);
-        for (uint32_t i = 0; i < blas_n8[k]; ++i) ++count[depth[off + i] + 1u];
-        uint32_t levels = 0;
-        for (uint32_t d = 0; d < 256; ++d) if (count[d + 1]) levels = d + 1;
-        u->n_levels[k] = levels;
-        u->level_first[k] = (uint32_t)u->level_start.size();
-        std::vector<uint32_t> cursor(levels + 1, (uint32_t)off);
-        for (uint32_t d = 0; d < levels; ++d) cursor[d + 1] = cursor[d] + count[d + 1];
-        u->level_start.insert(u->level_start.end(), cursor.begin(), cursor.end());
-        for (uint32_t i = 0; i < blas_n8[k]; ++i) order[cursor[depth[off + i]]++] = roots[k] + i;
-        u->max_levels = std::max(u->max_levels, levels);
-        off += blas_n8[k];
-    }
-    IHIPCHK(hipMemcpyAsync(u->d_order, order.data(), n8_all * 4, hipMemcpyHostToDevice, st));
-    // the call's tables: InstRefitMesh, chunk starts and record segments per mesh, level segments per mesh and level
+    std::vector<crt::RefitTree> trees(M);
+    for (uint32_t k = 0; k < M; ++k) trees[k] = crt::RefitTree{blas_nodes[k], false, 5u, blas_n8[k], roots[k]};
+    if ((rc = crt::discover_levels(trees.data(), M, st, &u->d_order, u->level))) return rc;
+    for (const auto& l : u->level) u->max_levels = std::max(u->max_levels, (uint32_t)l.size() - 1u);
+    // the call's tables: RefitMesh, chunk starts and record segments per mesh, level segments per mesh and level
     auto A = [](size_t b) { return (b + 15) & ~size_t(15); };
-    u->table_cap = A(M * sizeof(crt::InstRefitMesh)) + A(M * 4) + A(M * sizeof(crt::InstRefitSeg)) +
-                   (size_t)M * u->max_levels * sizeof(crt::InstRefitSeg);
+    u->table_cap = A(M * sizeof(crt::RefitMesh)) + A(M * 4) + A(M * sizeof(crt::RefitSeg)) + (size_t)M * u->max_levels * sizeof(crt::RefitSeg);
     if ((rc = alloc(&u->d_table, u->table_cap))) return rc;
     IHIPCHK(hipStreamSynchronize(st));            // before the host arrays go
     u->bytes = 4 * n8_all + 24 * n8_all + 12 * tris_all + 64 * (uint64_t)s->capacity + 24 * (uint64_t)M + 12 * v_total + 32 * (uint64_t)M +
                u->table_cap;
     s->upd = std::move(u);
     return CRT_OK;
-}
-
-float key_to_float(uint32_t key) {
-    const uint32_t b = (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key;
-    float f;
-    std::memcpy(&f, &b, 4);
-    return f;
 }
 
 // New positions for n distinct meshes (h_verts: host arrays, or d_verts: device arrays).  Order: check + mesh boxes on the
@@ -364,12 +323,12 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
     hipStream_t st = s->stream;
     // the call's tables
     auto A = [](size_t b) { return (b + 15) & ~size_t(15); };
-    const size_t o_chunk = A(n * sizeof(crt::InstRefitMesh)), o_rseg = o_chunk + A(n * 4), o_lseg = o_rseg + A(n * sizeof(crt::InstRefitSeg));
-    u->table.assign(o_lseg + (size_t)n * u->max_levels * sizeof(crt::InstRefitSeg), 0);
-    auto* tm = reinterpret_cast<crt::InstRefitMesh*>(u->table.data());
+    const size_t o_chunk = A(n * sizeof(crt::RefitMesh)), o_rseg = o_chunk + A(n * 4), o_lseg = o_rseg + A(n * sizeof(crt::RefitSeg));
+    u->table.assign(o_lseg + (size_t)n * u->max_levels * sizeof(crt::RefitSeg), 0);
+    auto* tm = reinterpret_cast<crt::RefitMesh*>(u->table.data());
     auto* tc = reinterpret_cast<uint32_t*>(u->table.data() + o_chunk);
-    auto* tr = reinterpret_cast<crt::InstRefitSeg*>(u->table.data() + o_rseg);
-    auto* tl = reinterpret_cast<crt::InstRefitSeg*>(u->table.data() + o_lseg);
+    auto* tr = reinterpret_cast<crt::RefitSeg*>(u->table.data() + o_rseg);
+    auto* tl = reinterpret_cast<crt::RefitSeg*>(u->table.data() + o_lseg);
     uint32_t chunks = 0, recs = 0, levels = 0;
     for (uint32_t k = 0; k < n; ++k) {
         const uint32_t m = ids[k];
@@ -381,12 +340,13 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
         } else {
             v = static_cast<const float*>(d_verts[k]);
         }
-        tm[k] = crt::InstRefitMesh{v, u->nv[m], u->nt[m], u->tri_off[m], 0u};
+        // a BLAS as a refit mesh: its slice of the source-order index array, keyed by the source id in v0.w
+        tm[k] = crt::RefitMesh{v, u->d_src_idx + 3 * (size_t)u->tri_off[m], 3u, u->nt[m], 0u, u->nv[m]};
         tc[k] = chunks;
         chunks += (std::max(u->nv[m], u->nt[m]) + crt::kCheckChunk - 1) / crt::kCheckChunk;
-        tr[k] = crt::InstRefitSeg{recs, u->tri_off[m], k, 0u};
+        tr[k] = crt::RefitSeg{recs, u->tri_off[m], k, 0u};
         recs += u->nt[m];
-        levels = std::max(levels, u->n_levels[m]);
+        levels = std::max(levels, (uint32_t)u->level[m].size() - 1u);
     }
     // level L: a segment per mesh that reaches it
     std::vector<uint32_t> lseg_at(levels + 1, 0), lcount(levels, 0);
@@ -395,23 +355,23 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
         lseg_at[L] = n_lseg;
         for (uint32_t k = 0; k < n; ++k) {
             const uint32_t m = ids[k];
-            if (u->n_levels[m] <= L) continue;
-            const uint32_t a = u->level_start[u->level_first[m] + L], b = u->level_start[u->level_first[m] + L + 1];
-            tl[n_lseg++] = crt::InstRefitSeg{lcount[L], a, k, 0u};
-            lcount[L] += b - a;
+            const std::vector<uint32_t>& lm = u->level[m];
+            if (lm.size() <= L + 1u) continue;
+            tl[n_lseg++] = crt::RefitSeg{lcount[L], lm[L], k, 0u};
+            lcount[L] += lm[L + 1] - lm[L];
         }
     }
     lseg_at[levels] = n_lseg;
     IHIPCHK(hipMemcpyAsync(u->d_table, u->table.data(), u->table.size(), hipMemcpyHostToDevice, st));
-    const auto* d_tm = reinterpret_cast<const crt::InstRefitMesh*>(u->d_table);
+    const auto* d_tm = reinterpret_cast<const crt::RefitMesh*>(u->d_table);
     const auto* d_tc = reinterpret_cast<const uint32_t*>(u->d_table + o_chunk);
-    const auto* d_tr = reinterpret_cast<const crt::InstRefitSeg*>(u->d_table + o_rseg);
-    const auto* d_tl = reinterpret_cast<const crt::InstRefitSeg*>(u->d_table + o_lseg);
+    const auto* d_tr = reinterpret_cast<const crt::RefitSeg*>(u->d_table + o_rseg);
+    const auto* d_tl = reinterpret_cast<const crt::RefitSeg*>(u->d_table + o_lseg);
 
     // 1. the coordinates and the new mesh boxes: the one wait for a verdict before the TLAS build
     IHIPCHK(hipEventRecord(u->ev0, st));
     IHIPCHK(hipMemsetAsync(u->d_check, 0, (size_t)n * 32, st));
-    crt::launch_inst_check(d_tm, d_tc, n, chunks, u->d_src_idx, u->d_check, st);
+    crt::launch_check_meshes(d_tm, d_tc, n, chunks, u->d_check, st);
     IHIPCHK(hipMemcpyAsync(u->h_check, u->d_check, (size_t)n * 32, hipMemcpyDeviceToHost, st));
     IHIPCHK(hipStreamSynchronize(st));
     IHIPCHK(hipGetLastError());
@@ -420,8 +380,8 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
         const uint32_t* c = u->h_check + 8 * (size_t)k;
         if (c[0]) return fail(CRT_ERR_INVALID, who + "a vertex coordinate of mesh " + std::to_string(ids[k]) + " is not finite or exceeds 1e18");
         for (int a = 0; a < 3; ++a) {
-            u->box_stage[6 * (size_t)ids[k] + a] = key_to_float(~c[4 + a]);
-            u->box_stage[6 * (size_t)ids[k] + 3 + a] = key_to_float(c[1 + a]);
+            u->box_stage[6 * (size_t)ids[k] + a] = crt::rf::key_to_float(~c[4 + a]);
+            u->box_stage[6 * (size_t)ids[k] + 3 + a] = crt::rf::key_to_float(c[1 + a]);
         }
     }
     IHIPCHK(hipMemcpyAsync(u->d_mesh_box_stage, u->box_stage.data(), u->box_stage.size() * 4, hipMemcpyHostToDevice, st));
@@ -433,11 +393,11 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
         if (rc) return rc;
     }
     // 4. the BLAS refit in place (records first: the leaf slots read only their id words), then the publication
-    crt::launch_inst_refit_records(s->d_tris, (uint32_t)s->blas_tris, d_tr, n, recs, d_tm, u->d_src_idx, st);
+    crt::launch_refit_records(s->d_tris, 3u, (uint32_t)s->blas_tris, d_tr, n, recs, d_tm, st);
     const uint32_t n_nodes = s->tlas_cap_nodes + (uint32_t)s->blas_nodes8;
     for (uint32_t L = levels; L-- > 0;)
-        crt::launch_inst_refit_node8_level(s->d_nodes, s->tlas_cap_nodes, n_nodes, u->d_order, d_tl + lseg_at[L], lseg_at[L + 1] - lseg_at[L],
-                                           lcount[L], s->d_tris, (uint32_t)s->blas_tris, d_tm, u->d_src_idx, u->d_box8, st);
+        crt::launch_refit_node8_level(s->d_nodes, 5u, s->tlas_cap_nodes, n_nodes, u->d_order, d_tl + lseg_at[L], lseg_at[L + 1] - lseg_at[L], lcount[L],
+                                      s->d_tris, 3u, (uint32_t)s->blas_tris, d_tm, u->d_box8, st);
     if (hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, who + "refit launch failed");
     if (ni > 0) {
         const int rc = publish_tlas(s, u->d_live, ni, ts);

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/crt.h"
 
 namespace crt {
@@ -76,23 +78,55 @@ void launch_gather_slots(const crt_triangle* d_in, const uint32_t* d_tri_order, 
 void launch_gather_records(const crt_triangle* d_in, const uint32_t* d_tri_order, const int32_t* d_tri_slots, const float* d_verts, uint32_t n_tris8,
                            float4* d_recs, hipStream_t stream);
 
-// ---- refit of a scene's trees and records to new vertex positions (refit.hip, crt_update_vertices) ----
-// d_out[0] |= 1 when a coordinate is not finite or exceeds 1e18; d_out[1..3] = ordered keys of the max x, y, z; d_out[4..6] = the
-// complements of the min keys.  d_out (7 words) must be zeroed before the launch.
+// ---- refit to new vertex positions, same topology (refit.hip): crt_update_vertices and crt_instances_update_meshes ----
+// One refitted tree's geometry.  Index entry e holds a triangle's three vertex indices at idx[stride * e + 0..2]; a record names its entry
+// in the w word of row key_row.  Scene: d_triangles (crt_triangle, stride 12), the slot in e1.w.  BLAS: its slice of the source-order
+// index array (stride 3), the source id in v0.w.
+struct RefitMesh {
+    const float* verts;        // xyz per vertex
+    const int32_t* idx;
+    uint32_t stride;           // ints per entry
+    uint32_t n_idx;            // valid entries
+    uint32_t key_row;          // 0: v0.w, 1: e1.w
+    uint32_t n_vertices;
+};
+static_assert(sizeof(RefitMesh) == 32, "RefitMesh is 32 bytes");
+
+// a run of entries of one mesh: entries [start, next start) of a launch are items first .. of the array it covers (records, or positions
+// in the level order); a launch finds its entry's segment by a binary search over the starts
+struct RefitSeg { uint32_t start, first, mesh, pad; };
+
+// one tree for discover_levels: a node8 array of node_rows 16-byte rows per node, or a BVH2 (crt_flatnode array)
+struct RefitTree {
+    const void* d_nodes;
+    bool bvh2;
+    uint32_t node_rows, n;
+    uint32_t base;             // added to the tree's local node indices in the order
+};
+// The node indices of every tree level by level, root level first: parent links and depths on the device (at most 255 levels), a counting
+// sort by depth on the host.  *d_order (hipMalloc'ed here, caller frees) holds the trees one after another; level[t][l] is the position in
+// it of tree t's level l (+ end).  Synchronises the stream.
+int discover_levels(const RefitTree* trees, size_t n_trees, hipStream_t stream, uint32_t** d_order, std::vector<std::vector<uint32_t>>& level);
+
+// d_out[0] |= 1 when a coordinate is not finite or exceeds 1e18; d_out[1..3] = ordered keys (rf::order_key) of the max x, y, z; d_out[4..6] =
+// the complements of the min keys.  d_out (7 words) must be zeroed before the launch.  Scene: the bounds of all vertices.
 void launch_check_vertices(const float* d_verts, uint32_t n_vertices, uint32_t* d_out, hipStream_t stream);
-// level discovery: parent links (d_parent preset to -1) and the depth of every node (root 0)
-void launch_node8_parents(const void* d_nodes, uint32_t node_rows, uint32_t n8, int32_t* d_parent, hipStream_t stream);
-void launch_bvh2_parents(const void* d_flat, uint32_t n2, int32_t* d_parent, hipStream_t stream);
-void launch_depths(const int32_t* d_parent, uint32_t n, uint8_t* d_depth, hipStream_t stream);
-// records at `rows` float4 per item, regathered in place (slot in e1.w, or record i = slot i when slot_order) from the leaf-order triangles
-void launch_refit_records(void* d_recs, uint32_t rows, uint32_t n, const void* d_tris, uint32_t n_slots, const float* d_verts, int slot_order,
-                          hipStream_t stream);
-// one level of each tree (d_order: its node indices); call deepest level first.  d_box8: 6 floats per node8, the float box the parent reads
+constexpr uint32_t kCheckChunk = 4096;      // vertices and triangles per block of the mesh check
+// The n meshes of a call: every coordinate checked as above, every index below n_vertices, and the box of the referenced vertices.
+// One block per chunk: d_chunk_start[k] = first block of mesh k (d_chunk_start[0] = 0); d_out: 8 words per mesh, zeroed before the launch.
+void launch_check_meshes(const RefitMesh* d_meshes, const uint32_t* d_chunk_start, uint32_t n, uint32_t n_chunks, uint32_t* d_out,
+                         hipStream_t stream);
+// records at `rows` float4 per item: entries [0, count) of the segments, regathered in place from their mesh's index entry
+void launch_refit_records(void* d_recs, uint32_t rows, uint32_t n_recs, const RefitSeg* d_segs, uint32_t n_segs, uint32_t count,
+                          const RefitMesh* d_meshes, hipStream_t stream);
+// one level of each tree (d_order: its node indices); call deepest level first
 void launch_refit_bvh2_level(void* d_flat, uint32_t n2, const uint32_t* d_order, uint32_t count, const void* d_tris, uint32_t n_slots,
                              const float* d_verts, hipStream_t stream);
-void launch_refit_node8_level(void* d_nodes, uint32_t node_rows, uint32_t n8, const uint32_t* d_order, uint32_t count, const void* d_recs,
-                              uint32_t tri_rows, uint32_t n_tris8, const void* d_tris, uint32_t n_slots, const float* d_verts, float* d_box8,
-                              hipStream_t stream);
+// one node8 level: entries [0, count) of the segments are positions in d_order, whose nodes lie in [node_base, n_nodes); d_box8: 6 floats
+// per node8 (index node - node_base), the float box the parent's slot reads
+void launch_refit_node8_level(void* d_nodes, uint32_t node_rows, uint32_t node_base, uint32_t n_nodes, const uint32_t* d_order,
+                              const RefitSeg* d_segs, uint32_t n_segs, uint32_t count, const void* d_recs, uint32_t tri_rows, uint32_t n_recs,
+                              const RefitMesh* d_meshes, float* d_box8, hipStream_t stream);
 
 // ---- code-object warm-up (crt_warmup) ----
 // HIP loads a code object the first time one of its kernels is looked up; each of these asks for the attributes of its

@@ -16,7 +16,15 @@ namespace rf {
 CRT_HD float tmin(float a, float b) { return a < b ? a : b < a ? b : (cw::f2u(a) >> 31) ? a : b; }
 CRT_HD float tmax(float a, float b) { return a > b ? a : b > a ? b : (cw::f2u(a) >> 31) ? b : a; }
 
-constexpr float kEmpty = 3.4028235e38f;    // lo of an empty box (hi = -kEmpty): neutral under tmin / tmax of finite values
+// ordered key of a finite float: unsigned compare of keys == float compare (-0 below +0, as tmin / tmax); the device checks reduce
+// their bounds as keys, and key_to_float gives the float back
+CRT_HD uint32_t order_key(float f) {
+    const uint32_t b = cw::f2u(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+CRT_HD float key_to_float(uint32_t key) { return cw::u2f((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); }
+
+constexpr float kEmpty = 3.4028235e38f;   // lo of an empty box (hi = -kEmpty): neutral under tmin / tmax of finite values
 
 struct Box { float lo[3], hi[3]; };
 CRT_HD Box empty_box() { return Box{{kEmpty, kEmpty, kEmpty}, {-kEmpty, -kEmpty, -kEmpty}}; }

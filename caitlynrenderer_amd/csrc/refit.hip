@@ -1,11 +1,16 @@
-// Refit kernels of crt_update_vertices: new vertex positions, same topology.  The BVH2, the CWBVH and both record arrays are
-// rewritten in place from the new vertices, one launch per tree level, deepest first (the kernel boundary orders the levels,
-// as in lbvh.hip k_refit_level).  Every box and quantised plane comes from host/refit_core.hpp, which the host refits
-// (crt_bvh2_refit / crt_cwbvh_refit) use too: the device output is byte-identical to theirs.
+// Refit kernels of crt_update_vertices and crt_instances_update_meshes (§12): new vertex positions, same topology.  The
+// trees and record arrays are rewritten in place, one launch per tree level, deepest first (the kernel boundary orders the levels, as in
+// lbvh.hip k_refit_level).  The records and node8 kernels serve both callers: each refitted tree is a RefitMesh (device_build.hpp), and a
+// per-launch segment table maps an entry to its mesh and item, so one launch covers every mesh of an instanced call and a scene is the
+// one-mesh, one-segment case.  Every box and quantised plane comes from host/refit_core.hpp, which the host refits (crt_bvh2_refit /
+// crt_cwbvh_refit) use too: the device output is byte-identical to theirs.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <string>
+#include <vector>
 
+#include "crt_error.hpp"
 #include "device_build.hpp"
 #include "host/flatnode_link.hpp"
 #include "host/refit_core.hpp"
@@ -15,35 +20,81 @@ namespace {
 
 using rf::Box;
 
-// ordered key of a finite float: unsigned compare of keys == float compare (-0 below +0, as rf::tmin / tmax)
-__device__ __forceinline__ uint32_t order_key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+// the last k in [0, n) with start[k] <= x (start[0] == 0 <= x)
+__device__ __forceinline__ uint32_t find_segment(const uint32_t* __restrict__ start, uint32_t stride, uint32_t n, uint32_t x) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (start[(size_t)mid * stride] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ RefitSeg segment_of(const RefitSeg* __restrict__ segs, uint32_t n_segs, uint32_t j) {
+    return segs[find_segment(&segs[0].start, 4u, n_segs, j)];
 }
 
-// out[0] |= 1 when a coordinate is not finite or exceeds 1e18 (crt_scene_create's rule); out[1..3] = max keys of x, y, z;
-// out[4..6] = complemented min keys (so that one zeroing memset and atomicMax serve both)
-__global__ void k_check_vertices(const float* __restrict__ v, uint32_t n, uint32_t* __restrict__ out) {
-    uint32_t bad = 0, hi[3] = {0u, 0u, 0u}, lo_c[3] = {0u, 0u, 0u};
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        for (int k = 0; k < 3; ++k) {
-            const float c = v[3 * (size_t)i + k];
-            if (!(c <= 1.0e18f && c >= -1.0e18f)) { bad = 1u; continue; }
-            const uint32_t key = order_key(c);
-            hi[k] = max(hi[k], key);
-            lo_c[k] = max(lo_c[k], ~key);
-        }
+// ---- checks ----
+// crt_scene_create's rule for a coordinate: finite and |x| <= 1e18
+__device__ __forceinline__ bool coord_ok(float c) { return c <= 1.0e18f && c >= -1.0e18f; }
+__device__ __forceinline__ void grow_keys(uint32_t hi[3], uint32_t lo_c[3], int a, float c) {
+    const uint32_t key = rf::order_key(c);
+    hi[a] = max(hi[a], key);
+    lo_c[a] = max(lo_c[a], ~key);
+}
+// a wave's verdict and bounds, published by its first lane: out[0] |= 1 on a bad item; out[1..3] max keys; out[4..6] complemented min keys
+// (so that one zeroing memset and atomicMax serve both)
+__device__ __forceinline__ void publish_check(uint32_t bad, uint32_t hi[3], uint32_t lo_c[3], uint32_t* out) {
     for (int m = 32; m >= 1; m >>= 1) {
         bad |= __shfl_xor(bad, m);
-        for (int k = 0; k < 3; ++k) { hi[k] = max(hi[k], (uint32_t)__shfl_xor((int)hi[k], m)); lo_c[k] = max(lo_c[k], (uint32_t)__shfl_xor((int)lo_c[k], m)); }
+        for (int a = 0; a < 3; ++a) { hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], m)); lo_c[a] = max(lo_c[a], (uint32_t)__shfl_xor((int)lo_c[a], m)); }
     }
     if ((threadIdx.x & 63u) == 0u) {
         if (bad) atomicOr(out, 1u);
-        for (int k = 0; k < 3; ++k) { atomicMax(out + 1 + k, hi[k]); atomicMax(out + 4 + k, lo_c[k]); }
+        for (int a = 0; a < 3; ++a) { atomicMax(out + 1 + a, hi[a]); atomicMax(out + 4 + a, lo_c[a]); }
     }
 }
 
-// ---- level discovery (once per scene, at its first update) ----
+// scene: the bounds of ALL vertices (they feed the ray_bins / sort_shadow cell grid)
+__global__ void k_check_vertices(const float* __restrict__ v, uint32_t n, uint32_t* __restrict__ out) {
+    uint32_t bad = 0, hi[3] = {0u, 0u, 0u}, lo_c[3] = {0u, 0u, 0u};
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        for (int a = 0; a < 3; ++a) {
+            const float c = v[3 * (size_t)i + a];
+            if (!coord_ok(c)) { bad = 1u; continue; }
+            grow_keys(hi, lo_c, a, c);
+        }
+    publish_check(bad, hi, lo_c, out);
+}
+
+constexpr uint32_t kCheckItems = kCheckChunk / 256;      // vertices / triangles per thread and chunk
+
+// instanced meshes: one block = one chunk of one mesh of the call.  Thread items: vertex i (its coordinates) and index entry i (its three
+// indices below n_vertices, and the keys of the vertices they reference: the mesh box covers the referenced vertices only).  out: 8 words
+// per mesh.
+__global__ __launch_bounds__(256) void k_check_meshes(const RefitMesh* __restrict__ meshes, const uint32_t* __restrict__ chunk_start, uint32_t n,
+                                                      uint32_t* __restrict__ out) {
+    const uint32_t k = find_segment(chunk_start, 1u, n, blockIdx.x);
+    const RefitMesh m = meshes[k];
+    const uint32_t base = (blockIdx.x - chunk_start[k]) * kCheckChunk;
+    uint32_t bad = 0, hi[3] = {0u, 0u, 0u}, lo_c[3] = {0u, 0u, 0u};
+    for (uint32_t r = 0; r < kCheckItems; ++r) {
+        const uint32_t i = base + r * 256u + threadIdx.x;
+        if (i < m.n_vertices)
+            for (int a = 0; a < 3; ++a)
+                if (!coord_ok(m.verts[3 * (size_t)i + a])) bad = 1u;
+        if (i < m.n_idx) {
+            const int32_t* t = m.idx + (size_t)m.stride * i;
+            for (int j = 0; j < 3; ++j) {
+                const uint32_t v = (uint32_t)t[j];
+                if (v >= m.n_vertices) { bad = 1u; continue; }
+                for (int a = 0; a < 3; ++a) grow_keys(hi, lo_c, a, m.verts[3 * (size_t)v + a]);
+            }
+        }
+    }
+    publish_check(bad, hi, lo_c, out + 8 * (size_t)k);
+}
+
+// ---- level discovery ----
 __global__ void k_node8_parents(const uint4* __restrict__ nodes, uint32_t node_rows, uint32_t n8, int32_t* __restrict__ parent) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n8) return;
@@ -63,7 +114,7 @@ __global__ void k_bvh2_parents(const crt_flatnode* __restrict__ flat, uint32_t n
     const uint32_t l = (uint32_t)link_of(f.bmin[3]);
     if (l > i && l + 1u < n2) { parent[l] = (int32_t)i; parent[l + 1u] = (int32_t)i; }
 }
-// depth of every node by climbing its parent links (root = 0; at most 255 levels, both trees are far shallower)
+// depth of every node by climbing its parent links (root = 0; at most 255 levels, the trees are far shallower)
 __global__ void k_depths(const int32_t* __restrict__ parent, uint32_t n, uint8_t* __restrict__ depth) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -73,27 +124,31 @@ __global__ void k_depths(const int32_t* __restrict__ parent, uint32_t n, uint8_t
 }
 
 // ---- per update ----
-// records: rows (v0 | id) (e1 | slot) (e2 | material) regathered from the slot in e1.w and the leaf-order triangle array, with the two
-// fp32 subtractions of scene_build.hip make_record; the w words stay.  slot_order: record i is slot i (the BVH2 walk's array).
-__global__ void k_refit_records(float4* __restrict__ recs, uint32_t rows, uint32_t n, const int4* __restrict__ tris, uint32_t n_slots,
-                                const float* __restrict__ verts, int slot_order) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// records: rows (v0 | w) (e1 | w) (e2 | w) regathered from the index entry the key word names, with the two fp32 subtractions of
+// scene_build.hip make_record; the w words stay
+__global__ __launch_bounds__(256) void k_refit_records(float4* __restrict__ recs, uint32_t rows, uint32_t n_recs, const RefitSeg* __restrict__ segs,
+                                                       uint32_t n_segs, uint32_t count, const RefitMesh* __restrict__ meshes) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const RefitSeg sg = segment_of(segs, n_segs, j);
+    const uint32_t i = sg.first + (j - sg.start);
+    if (i >= n_recs) return;
+    const RefitMesh m = meshes[sg.mesh];
     float4* r = recs + (size_t)i * rows;
     float4 a = r[0], b = r[1], c = r[2];
-    const uint32_t slot = slot_order ? i : (uint32_t)__float_as_int(b.w);
-    if (slot >= n_slots) return;
-    const int4 t = tris[3 * (size_t)slot];
-    const float* v0 = verts + 3 * (size_t)(uint32_t)t.x;
-    const float* v1 = verts + 3 * (size_t)(uint32_t)t.y;
-    const float* v2 = verts + 3 * (size_t)(uint32_t)t.z;
+    const uint32_t e = (uint32_t)__float_as_int(m.key_row ? b.w : a.w);
+    if (e >= m.n_idx) return;
+    const int32_t* t = m.idx + (size_t)m.stride * e;
+    const float* v0 = m.verts + 3 * (size_t)(uint32_t)t[0];
+    const float* v1 = m.verts + 3 * (size_t)(uint32_t)t[1];
+    const float* v2 = m.verts + 3 * (size_t)(uint32_t)t[2];
     a.x = v0[0]; a.y = v0[1]; a.z = v0[2];
     b.x = v1[0] - v0[0]; b.y = v1[1] - v0[1]; b.z = v1[2] - v0[2];
     c.x = v2[0] - v0[0]; c.y = v2[1] - v0[1]; c.z = v2[2] - v0[2];
     r[0] = a; r[1] = b; r[2] = c;
 }
 
-// one BVH2 level: leaves from their slot ranges, inner nodes from their two children (the deeper level, final by now)
+// one BVH2 level (scenes only): leaves from their slot ranges, inner nodes from their two children (the deeper level, final by now)
 __global__ void k_refit_bvh2_level(crt_flatnode* __restrict__ flat, uint32_t n2, const uint32_t* __restrict__ order, uint32_t count,
                                    const int4* __restrict__ tris, uint32_t n_slots, const float* __restrict__ verts) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -123,18 +178,22 @@ __device__ __forceinline__ float swz(float v) { return __int_as_float(__builtin_
 
 constexpr uint32_t kNodesPerBlock = 32;      // 8 lanes per node8, 256 threads
 
-// one node8 level: eight adjacent lanes per node, one per slot.  A lane builds its slot's box (leaf: the vertex boxes of its triangles;
-// inner: the child node8's float box, written by the previous launch), the node box is reduced across the eight lanes, and every lane
-// quantises its own slot against it.  meta, imask, child and triangle bases stay; so do the planes of empty slots.
-__global__ __launch_bounds__(256) void k_refit_node8_level(uint4* __restrict__ nodes, uint32_t node_rows, uint32_t n8, const uint32_t* __restrict__ order,
-                                                           uint32_t count, const float4* __restrict__ recs, uint32_t tri_rows, uint32_t n_tris8,
-                                                           const int4* __restrict__ tris, uint32_t n_slots, const float* __restrict__ verts,
-                                                           float2* __restrict__ box8) {
+// one node8 level: eight adjacent lanes per node, one per slot.  A lane builds its slot's box (leaf: the vertex boxes of its records' index
+// entries; inner: the child node8's float box, written by the previous launch), the node box is reduced across the eight lanes, and every
+// lane quantises its own slot against it.  Nodes are indices into the whole node array (an instanced scene's BLAS bases are rebased
+// already); box8 is indexed from node_base.  meta, imask, child and triangle bases stay; so do the planes of empty slots.
+__global__ __launch_bounds__(256) void k_refit_node8_level(uint4* __restrict__ nodes, uint32_t node_rows, uint32_t node_base, uint32_t n_nodes,
+                                                           const uint32_t* __restrict__ order, const RefitSeg* __restrict__ segs, uint32_t n_segs,
+                                                           uint32_t count, const float4* __restrict__ recs, uint32_t tri_rows, uint32_t n_recs,
+                                                           const RefitMesh* __restrict__ meshes, float2* __restrict__ box8) {
     __shared__ uint4 q_rows[kNodesPerBlock][3];
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t j = t >> 3, s = t & 7u, local = threadIdx.x >> 3;
-    const bool valid = j < count;
-    const uint32_t node = valid ? order[j] : 0u;
+    bool valid = j < count;
+    RefitSeg sg{0u, 0u, 0u, 0u};
+    if (valid) sg = segment_of(segs, n_segs, j);
+    const uint32_t node = valid ? order[sg.first + (j - sg.start)] : 0u;
+    valid = valid && node >= node_base && node < n_nodes;
     uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;
     if (valid) { r0 = nodes[(size_t)node * node_rows]; r1 = nodes[(size_t)node * node_rows + 1]; }
     if (valid && s < 3u) q_rows[local][s] = nodes[(size_t)node * node_rows + 2u + s];
@@ -144,19 +203,21 @@ __global__ __launch_bounds__(256) void k_refit_node8_level(uint4* __restrict__ n
     if (valid && meta) {
         if ((imask >> s) & 1u) {
             const uint32_t c = r1.x + (uint32_t)__builtin_popcount(imask & ((1u << s) - 1u));
-            if (c < n8) {
-                const float2 x0 = box8[3 * (size_t)c], x1 = box8[3 * (size_t)c + 1], x2 = box8[3 * (size_t)c + 2];
+            if (c >= node_base && c < n_nodes) {
+                const size_t cb = 3 * (size_t)(c - node_base);
+                const float2 x0 = box8[cb], x1 = box8[cb + 1], x2 = box8[cb + 2];
                 b = Box{{x0.x, x0.y, x1.x}, {x1.y, x2.x, x2.y}};
             }
         } else {
+            const RefitMesh m = meshes[sg.mesh];
             const uint32_t first = r1.y + (uint32_t)rf::leaf_offset(meta), cnt = (uint32_t)rf::leaf_count(meta);
             for (uint32_t k = 0; k < cnt; ++k) {
-                if (first + k >= n_tris8) break;
-                const uint32_t slot = (uint32_t)__float_as_int(recs[(size_t)(first + k) * tri_rows + 1].w);
-                if (slot >= n_slots) continue;
-                const int4 tr = tris[3 * (size_t)slot];
-                const int32_t v[3] = {tr.x, tr.y, tr.z};
-                rf::grow_triangle(b, v, verts);
+                if (first + k >= n_recs) break;
+                const uint32_t e = (uint32_t)__float_as_int(recs[(size_t)(first + k) * tri_rows + m.key_row].w);
+                if (e >= m.n_idx) continue;
+                const int32_t* tr = m.idx + (size_t)m.stride * e;
+                const int32_t v[3] = {tr[0], tr[1], tr[2]};
+                rf::grow_triangle(b, v, m.verts);
             }
         }
     }
@@ -167,6 +228,12 @@ __global__ __launch_bounds__(256) void k_refit_node8_level(uint4* __restrict__ n
     float p[3], scale[3];
     uint8_t e[3];
     rf::node_frame(u, p, e, scale);
+    if (valid && s == 0u) {                           // the box the parent level reads (the next launch)
+        const size_t nb = 3 * (size_t)(node - node_base);
+        box8[nb] = make_float2(u.lo[0], u.lo[1]);
+        box8[nb + 1] = make_float2(u.lo[2], u.hi[0]);
+        box8[nb + 2] = make_float2(u.hi[1], u.hi[2]);
+    }
     __syncthreads();                                  // the original plane rows are in LDS
     if (valid && meta) {
         uint8_t q[6];
@@ -181,45 +248,86 @@ __global__ __launch_bounds__(256) void k_refit_node8_level(uint4* __restrict__ n
     if (s == 0u) {
         dst[0] = make_uint4(__float_as_uint(p[0]), __float_as_uint(p[1]), __float_as_uint(p[2]),
                             (uint32_t)e[0] | ((uint32_t)e[1] << 8) | ((uint32_t)e[2] << 16) | (imask << 24));
-        box8[3 * (size_t)node] = make_float2(u.lo[0], u.lo[1]);
-        box8[3 * (size_t)node + 1] = make_float2(u.lo[2], u.hi[0]);
-        box8[3 * (size_t)node + 2] = make_float2(u.hi[1], u.hi[2]);
     }
 }
 
-inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255u) / 256u ? (n + 255u) / 256u : 1u)); }
+inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)std::max<uint64_t>(1u, (n + 255u) / 256u)); }
 
 }  // namespace
+
+int discover_levels(const RefitTree* trees, size_t n_trees, hipStream_t stream, uint32_t** d_order, std::vector<std::vector<uint32_t>>& level) {
+    *d_order = nullptr;
+    uint64_t n_all = 0;
+    for (size_t t = 0; t < n_trees; ++t) n_all += trees[t].n;
+    DeviceArena tmp;
+    hipError_t he = tmp.reserve(DeviceArena::padded(4 * n_all) + DeviceArena::padded(n_all));
+    if (he != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("refit level discovery: hipMalloc: ") + hipGetErrorString(he));
+    int32_t* d_parent = tmp.take<int32_t>(n_all);
+    uint8_t* d_depth = tmp.take<uint8_t>(n_all);
+    std::vector<uint8_t> depth(n_all);
+    if ((he = hipMemsetAsync(d_parent, 0xff, 4 * n_all, stream)) != hipSuccess)
+        return fail(CRT_ERR_HIP, std::string("refit level discovery: ") + hipGetErrorString(he));
+    uint64_t off = 0;
+    for (size_t t = 0; t < n_trees; ++t) {
+        const RefitTree& x = trees[t];
+        if (x.bvh2) hipLaunchKernelGGL(k_bvh2_parents, grid_for(x.n), dim3(256), 0, stream, static_cast<const crt_flatnode*>(x.d_nodes), x.n, d_parent + off);
+        else hipLaunchKernelGGL(k_node8_parents, grid_for(x.n), dim3(256), 0, stream, static_cast<const uint4*>(x.d_nodes), x.node_rows, x.n, d_parent + off);
+        hipLaunchKernelGGL(k_depths, grid_for(x.n), dim3(256), 0, stream, d_parent + off, x.n, d_depth + off);
+        off += x.n;
+    }
+    if ((he = hipMemcpyAsync(depth.data(), d_depth, n_all, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (he = hipStreamSynchronize(stream)) != hipSuccess || (he = hipGetLastError()) != hipSuccess)
+        return fail(CRT_ERR_HIP, std::string("refit level discovery: ") + hipGetErrorString(he));
+    std::vector<uint32_t> order(n_all);
+    level.assign(n_trees, {});
+    off = 0;
+    for (size_t t = 0; t < n_trees; ++t) {
+        const RefitTree& x = trees[t];
+        std::vector<uint32_t> count(257, 0);
+        for (uint32_t i = 0; i < x.n; ++i) ++count[depth[off + i] + 1u];
+        uint32_t levels = 0;
+        for (uint32_t d = 0; d < 256; ++d) if (count[d + 1]) levels = d + 1;
+        std::vector<uint32_t>& start = level[t];
+        start.assign(levels + 1, (uint32_t)off);
+        for (uint32_t d = 0; d < levels; ++d) start[d + 1] = start[d] + count[d + 1];
+        std::vector<uint32_t> cursor(start.begin(), start.end() - 1);
+        for (uint32_t i = 0; i < x.n; ++i) order[cursor[depth[off + i]]++] = x.base + i;
+        off += x.n;
+    }
+    if ((he = hipMalloc(reinterpret_cast<void**>(d_order), std::max<uint64_t>(n_all, 1) * 4)) != hipSuccess)
+        return fail(CRT_ERR_NOMEM, std::string("refit level discovery: hipMalloc: ") + hipGetErrorString(he));
+    if ((he = hipMemcpyAsync(*d_order, order.data(), n_all * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (he = hipStreamSynchronize(stream)) != hipSuccess)               // before the host order goes
+        return fail(CRT_ERR_HIP, std::string("refit level discovery: ") + hipGetErrorString(he));
+    return CRT_OK;
+}
 
 void launch_check_vertices(const float* d_verts, uint32_t n_vertices, uint32_t* d_out, hipStream_t stream) {
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024u, (n_vertices + 255u) / 256u + 1u);
     hipLaunchKernelGGL(k_check_vertices, dim3(blocks), dim3(256), 0, stream, d_verts, n_vertices, d_out);
 }
-void launch_node8_parents(const void* d_nodes, uint32_t node_rows, uint32_t n8, int32_t* d_parent, hipStream_t stream) {
-    hipLaunchKernelGGL(k_node8_parents, grid_for(n8), dim3(256), 0, stream, static_cast<const uint4*>(d_nodes), node_rows, n8, d_parent);
+void launch_check_meshes(const RefitMesh* d_meshes, const uint32_t* d_chunk_start, uint32_t n, uint32_t n_chunks, uint32_t* d_out,
+                         hipStream_t stream) {
+    if (n && n_chunks) hipLaunchKernelGGL(k_check_meshes, dim3(n_chunks), dim3(256), 0, stream, d_meshes, d_chunk_start, n, d_out);
 }
-void launch_bvh2_parents(const void* d_flat, uint32_t n2, int32_t* d_parent, hipStream_t stream) {
-    hipLaunchKernelGGL(k_bvh2_parents, grid_for(n2), dim3(256), 0, stream, static_cast<const crt_flatnode*>(d_flat), n2, d_parent);
-}
-void launch_depths(const int32_t* d_parent, uint32_t n, uint8_t* d_depth, hipStream_t stream) {
-    hipLaunchKernelGGL(k_depths, grid_for(n), dim3(256), 0, stream, d_parent, n, d_depth);
-}
-void launch_refit_records(void* d_recs, uint32_t rows, uint32_t n, const void* d_tris, uint32_t n_slots, const float* d_verts, int slot_order,
-                          hipStream_t stream) {
-    hipLaunchKernelGGL(k_refit_records, grid_for(n), dim3(256), 0, stream, static_cast<float4*>(d_recs), rows, n, static_cast<const int4*>(d_tris), n_slots,
-                       d_verts, slot_order);
+void launch_refit_records(void* d_recs, uint32_t rows, uint32_t n_recs, const RefitSeg* d_segs, uint32_t n_segs, uint32_t count,
+                          const RefitMesh* d_meshes, hipStream_t stream) {
+    if (n_segs && count)
+        hipLaunchKernelGGL(k_refit_records, grid_for(count), dim3(256), 0, stream, static_cast<float4*>(d_recs), rows, n_recs, d_segs, n_segs, count,
+                           d_meshes);
 }
 void launch_refit_bvh2_level(void* d_flat, uint32_t n2, const uint32_t* d_order, uint32_t count, const void* d_tris, uint32_t n_slots,
                              const float* d_verts, hipStream_t stream) {
     hipLaunchKernelGGL(k_refit_bvh2_level, grid_for(count), dim3(256), 0, stream, static_cast<crt_flatnode*>(d_flat), n2, d_order, count,
                        static_cast<const int4*>(d_tris), n_slots, d_verts);
 }
-void launch_refit_node8_level(void* d_nodes, uint32_t node_rows, uint32_t n8, const uint32_t* d_order, uint32_t count, const void* d_recs,
-                              uint32_t tri_rows, uint32_t n_tris8, const void* d_tris, uint32_t n_slots, const float* d_verts, float* d_box8,
-                              hipStream_t stream) {
-    hipLaunchKernelGGL(k_refit_node8_level, grid_for((uint64_t)count * 8u), dim3(256), 0, stream, static_cast<uint4*>(d_nodes), node_rows, n8, d_order,
-                       count, static_cast<const float4*>(d_recs), tri_rows, n_tris8, static_cast<const int4*>(d_tris), n_slots, d_verts,
-                       reinterpret_cast<float2*>(d_box8));
+void launch_refit_node8_level(void* d_nodes, uint32_t node_rows, uint32_t node_base, uint32_t n_nodes, const uint32_t* d_order,
+                              const RefitSeg* d_segs, uint32_t n_segs, uint32_t count, const void* d_recs, uint32_t tri_rows, uint32_t n_recs,
+                              const RefitMesh* d_meshes, float* d_box8, hipStream_t stream) {
+    if (n_segs && count)
+        hipLaunchKernelGGL(k_refit_node8_level, grid_for((uint64_t)count * 8u), dim3(256), 0, stream, static_cast<uint4*>(d_nodes), node_rows,
+                           node_base, n_nodes, d_order, d_segs, n_segs, count, static_cast<const float4*>(d_recs), tri_rows, n_recs, d_meshes,
+                           reinterpret_cast<float2*>(d_box8));
 }
 
 }  // namespace crt
