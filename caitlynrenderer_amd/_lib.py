@@ -108,6 +108,8 @@ SYMBOLS = {
     "crt_instances_create": (_I, [C.POINTER(crt_blas_desc), _U32, _P, _U32, _U32, _U32, C.POINTER(_P)]),
     "crt_instances_set": (_I, [_P, _P, _U32]),
     "crt_instances_set_device": (_I, [_P, _P, _U32, _I]),
+    "crt_instances_refit": (_I, [_P, _P, _U32]),
+    "crt_instances_refit_device": (_I, [_P, _P, _U32, _I]),
     "crt_instances_trace": (_I, [_P, _P, _SZ, _P, _P, _I, _P]),
     "crt_instances_trace_device": (_I, [_P, _P, _SZ, _P, _P, _I, _P, _I]),
     "crt_instances_get_info": (_I, [_P, C.POINTER(crt_instances_info)]),

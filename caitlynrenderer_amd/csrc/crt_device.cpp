@@ -2373,7 +2373,7 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
     if (r->h_check[0]) return fail(CRT_ERR_INVALID, "crt_update_vertices: a vertex coordinate is not finite or exceeds 1e18");
     // the scene as one refit mesh: d_triangles in leaf-slot order, keyed by the slot in e1.w.  The stream is idle here, so the previous
     // call's copy of h_mesh is done; the refit launches read it after this copy, in stream order.
-    *r->h_mesh = crt::RefitMesh{verts, reinterpret_cast<const int32_t*>(s->d_triangles), 12u, (uint32_t)s->n_slots, 1u, nv};
+    *r->h_mesh = crt::RefitMesh{verts, reinterpret_cast<const int32_t*>(s->d_triangles), 12u, (uint32_t)s->n_slots, 7u, nv};
     HIPCHK(hipMemcpyAsync(r->d_mesh, r->h_mesh, sizeof(crt::RefitMesh), hipMemcpyHostToDevice, st));
 
     // every stream that reads the scene's buffers is done with the old scene before they change (its own stream is, by order)

@@ -1,6 +1,7 @@
 // Instanced scenes (include/crt.h crt_instances_*): one bottom-level CWBVH per mesh, built once on the device by the
 // scene builders (lbvh.hip, cwbvh_device.hip, scene_build.hip), and a top-level CWBVH over the instances' world boxes, rebuilt on the
-// device (binned SAH over boxes, then the same converter) at create and at every set.  All node8s live in ONE array (the TLAS region first,
+// device (binned SAH over boxes, then the same converter) at create and at every set, or refitted in place by crt_instances_refit
+// (DESIGN.md §13).  All node8s live in ONE array (the TLAS region first,
 // sized for `capacity`, then every BLAS with its child / triangle bases rebased) and all triangle records in ONE array, so the walk
 // (instances.hip k_trace_instances) addresses any node with one 32-bit index off one base.
 #include <hip/hip_runtime.h>
@@ -94,6 +95,15 @@ struct crt_instances {
     size_t arena_mark = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float set_device_ms = 0.f, set_wall_ms = 0.f, build_wall_ms = 0.f;
+    // crt_instances_refit: the live TLAS as a refit mesh over d_box.  Its levels are found at the first refit after each
+    // TLAS build; the rest is reserved at create, so that later refits allocate nothing
+    bool tlas_levels_ok = false;
+    std::vector<uint32_t> tlas_level;     // per level, root first (+ end): position in d_tlas_order of its first node8
+    uint32_t* d_tlas_order = nullptr;     // the live TLAS's node8s level by level (discover_levels)
+    float* d_tlas_box8 = nullptr;         // 6 floats per TLAS node8: its float box, which its parent's slot reads
+    int32_t* d_box_idx = nullptr;         // (2i, 2i + 1, 2i) per instance: instance i's world box as a triangle of d_box
+    uint8_t* d_tlas_table = nullptr;      // the TLAS's RefitMesh, then one RefitSeg per level
+    std::vector<uint8_t> tlas_table;
     // crt_instances_trace's device copies of the host rays
     void* d_t_rays = nullptr; void* d_t_hits = nullptr; void* d_t_inst = nullptr; void* d_t_stats = nullptr;
     size_t t_cap = 0;
@@ -101,7 +111,7 @@ struct crt_instances {
 
     ~crt_instances() {
         void* bufs[] = {d_nodes, d_tris, d_inst, d_w2o, d_wbox, d_mesh_box, d_mesh_root, d_in, d_rec, d_box, d_w2o_stage, d_flag, d_overflow,
-                        d_t8_stage, d_t_rays, d_t_hits, d_t_inst, d_t_stats};
+                        d_t8_stage, d_t_rays, d_t_hits, d_t_inst, d_t_stats, d_tlas_order, d_tlas_box8, d_box_idx, d_tlas_table};
         if (stream) (void)hipStreamSynchronize(stream);
         upd.reset();
         for (void* p : bufs) if (p) (void)hipFree(p);
@@ -175,9 +185,10 @@ struct TlasStage {
     ~TlasStage() { if (s && d_t8 && d_t8 != s->d_t8_stage) (void)hipFree(d_t8); }
 };
 
-int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const float* d_mesh_box, const std::string& who, TlasStage& ts) {
+// n >= 1 instances (DEVICE memory) through the prep kernel against the mesh boxes d_mesh_box, into the set's staging (d_rec, d_box,
+// d_w2o_stage), and the host's one wait for its verdict.  Shared by sets, updates and refits; the walk reads none of it.
+int prep_instances(crt_instances* s, const void* d_src, uint32_t n, const float* d_mesh_box, const std::string& who) {
     hipStream_t st = s->stream;
-    ts.s = s;
     IHIPCHK(hipMemsetAsync(s->d_flag, 0, 4, st));
     crt::InstPrepArgs pa{};
     pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = s->n_meshes; pa.mesh_box = d_mesh_box; pa.mesh_root = s->d_mesh_root;
@@ -190,10 +201,17 @@ int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const float* d_m
     if (flag)
         return fail(CRT_ERR_INVALID, who + ((flag & 1u) ? "a matrix is not finite, or singular, or its inverse is not finite"
                                             : (flag & 2u) ? "a mesh index is out of range" : "a world box exceeds 1e18"));
+    return CRT_OK;
+}
+
+int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const float* d_mesh_box, const std::string& who, TlasStage& ts) {
+    hipStream_t st = s->stream;
+    ts.s = s;
+    int rc = prep_instances(s, d_src, n, d_mesh_box, who);
+    if (rc) return rc;
     // the TLAS over the world boxes
     s->arena.used = s->arena_mark;
     float ms = 0.f;
-    int rc;
     if (n == 1) {
         crt::launch_single_leaf(s->d_box, s->d_flat, s->d_tri_order, st);
     } else {
@@ -218,6 +236,7 @@ int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const float* d_m
 // and boxes; an updatable handle keeps the instances themselves (d_src, when it is not that copy already) for its updates.  Enqueued only.
 int publish_tlas(crt_instances* s, const void* d_src, uint32_t n, const TlasStage& ts) {
     hipStream_t st = s->stream;
+    s->tlas_levels_ok = false;                    // a new topology: the next refit finds its levels
     IHIPCHK(hipMemcpyAsync(s->d_nodes, ts.d_t8, (size_t)ts.n8 * sizeof(crt_node8), hipMemcpyDeviceToDevice, st));
     crt::launch_gather_instances(s->d_rec, s->d_tri_order, s->d_tri_slots, n, s->d_inst, st);
     IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
@@ -247,6 +266,62 @@ int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
     IHIPCHK(hipEventRecord(s->ev1, st));
     IHIPCHK(hipGetLastError());
     IHIPCHK(hipEventSynchronize(s->ev1));
+    IHIPCHK(hipEventElapsedTime(&s->set_device_ms, s->ev0, s->ev1));
+    s->set_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// The levels of the live TLAS (n_instances >= 1), once per TLAS build, and its refit tables: the TLAS is a RefitMesh over the staged
+// world boxes (2 vertices per instance, the triples of d_box_idx) whose records, the instance records, name their instance in row 3 .y.
+int find_tlas_levels(crt_instances* s) {
+    hipStream_t st = s->stream;
+    if (s->d_tlas_order) { (void)hipFree(s->d_tlas_order); s->d_tlas_order = nullptr; }
+    const crt::RefitTree tree{s->d_nodes, false, 5u, s->n_tlas8, 0u};
+    std::vector<std::vector<uint32_t>> level;
+    int rc = crt::discover_levels(&tree, 1, st, &s->d_tlas_order, level);
+    if (rc) return rc;
+    if (level[0].size() - 1 > 255) return fail(CRT_ERR_HIP, "crt_instances_refit: TLAS deeper than 255 levels");
+    s->tlas_level = level[0];
+    const uint32_t n = s->n_instances, levels = (uint32_t)s->tlas_level.size() - 1u;
+    s->tlas_table.assign(sizeof(crt::RefitMesh) + levels * sizeof(crt::RefitSeg), 0);
+    *reinterpret_cast<crt::RefitMesh*>(s->tlas_table.data()) = crt::RefitMesh{s->d_box, s->d_box_idx, 3u, n, 13u, 2u * n};
+    auto* seg = reinterpret_cast<crt::RefitSeg*>(s->tlas_table.data() + sizeof(crt::RefitMesh));
+    for (uint32_t L = 0; L < levels; ++L) seg[L] = crt::RefitSeg{0u, s->tlas_level[L], 0u, 0u};
+    IHIPCHK(hipMemcpyAsync(s->d_tlas_table, s->tlas_table.data(), s->tlas_table.size(), hipMemcpyHostToDevice, st));
+    s->tlas_levels_ok = true;
+    return CRT_OK;
+}
+
+// Same instances, new transforms: the prep into staging (the one wait for a verdict), then the live TLAS refitted in place
+// deepest level first, each leaf slot's record renewed from the instance it holds, and the matrices and boxes published.  Reads nothing of
+// the last attempted build (d_flat, d_tri_order, d_tri_slots, d_t8_stage): a set refused with CRT_ERR_LIMIT has rebuilt them, while the
+// live TLAS is the one before it.
+int refit_impl(crt_instances* s, const void* d_src, uint32_t n, const std::string& who) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n != s->n_instances)
+        return fail(CRT_ERR_INVALID, who + "n_instances (" + std::to_string(n) + ") differs from the live count (" + std::to_string(s->n_instances) + ")");
+    hipStream_t st = s->stream;
+    IHIPCHK(hipEventRecord(s->ev0, st));
+    if (n > 0) {
+        int rc = prep_instances(s, d_src, n, s->d_mesh_box, who);
+        if (rc) return rc;
+        if (!s->tlas_levels_ok && (rc = find_tlas_levels(s))) return rc;
+        const auto* d_mesh = reinterpret_cast<const crt::RefitMesh*>(s->d_tlas_table);
+        const auto* d_seg = reinterpret_cast<const crt::RefitSeg*>(s->d_tlas_table + sizeof(crt::RefitMesh));
+        const std::vector<uint32_t>& lv = s->tlas_level;
+        for (size_t L = lv.size() - 1; L-- > 0;)
+            crt::launch_refit_node8_level(s->d_nodes, 5u, 0u, s->n_tlas8, s->d_tlas_order, d_seg + L, 1u, lv[L + 1] - lv[L], s->d_inst, 4u, n, d_mesh,
+                                          s->d_tlas_box8, st);
+        crt::launch_regather_instances(s->d_rec, n, s->d_inst, st);
+        IHIPCHK(hipGetLastError());
+        IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+        IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+        if (s->upd && d_src != s->upd->d_live)
+            IHIPCHK(hipMemcpyAsync(s->upd->d_live, d_src, (size_t)n * sizeof(crt_instance), hipMemcpyDeviceToDevice, st));
+    }
+    IHIPCHK(hipEventRecord(s->ev1, st));
+    IHIPCHK(hipEventSynchronize(s->ev1));             // the publication is done when the call returns
+    IHIPCHK(hipGetLastError());
     IHIPCHK(hipEventElapsedTime(&s->set_device_ms, s->ev0, s->ev1));
     s->set_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
@@ -341,7 +416,7 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
             v = static_cast<const float*>(d_verts[k]);
         }
         // a BLAS as a refit mesh: its slice of the source-order index array, keyed by the source id in v0.w
-        tm[k] = crt::RefitMesh{v, u->d_src_idx + 3 * (size_t)u->tri_off[m], 3u, u->nt[m], 0u, u->nv[m]};
+        tm[k] = crt::RefitMesh{v, u->d_src_idx + 3 * (size_t)u->tri_off[m], 3u, u->nt[m], 3u, u->nv[m]};
         tc[k] = chunks;
         chunks += (std::max(u->nv[m], u->nt[m]) + crt::kCheckChunk - 1) / crt::kCheckChunk;
         tr[k] = crt::RefitSeg{recs, u->tri_off[m], k, 0u};
@@ -496,8 +571,10 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     const size_t C = capacity;
     if ((rc = alloc(&s->d_inst, C * 4)) || (rc = alloc(&s->d_w2o, C * 12)) || (rc = alloc(&s->d_wbox, C * 6)) || (rc = alloc(&s->d_in, C * 16)) ||
         (rc = alloc(&s->d_rec, C * 4)) || (rc = alloc(&s->d_box, C * 6)) || (rc = alloc(&s->d_w2o_stage, C * 12)) || (rc = alloc(&s->d_flag, 1)) ||
-        (rc = alloc(&s->d_overflow, 1)) || (rc = alloc(&s->d_t8_stage, s->tlas_cap_nodes)))
+        (rc = alloc(&s->d_overflow, 1)) || (rc = alloc(&s->d_t8_stage, s->tlas_cap_nodes)) || (rc = alloc(&s->d_tlas_box8, 6 * (size_t)s->tlas_cap_nodes)) ||
+        (rc = alloc(&s->d_box_idx, C * 3)) || (rc = alloc(&s->d_tlas_table, sizeof(crt::RefitMesh) + 255 * sizeof(crt::RefitSeg))))
         return rc;
+    crt::launch_box_triples(s->d_box_idx, capacity, st);
     IHIPCHK(hipMemsetAsync(s->d_overflow, 0, 4, st));
     // the TLAS build's space for `capacity` instances, reserved once
     const size_t cn = std::max<size_t>(C, 2), cn2 = 2 * cn - 1;
@@ -560,6 +637,31 @@ int crt_instances_set_device(crt_instances* s, const void* d_instances, uint32_t
     IHIPCHK(hipSetDevice(s->device));
     (void)sync;                                   // a set checks its instances on the host before it publishes anything: it always returns done
     return set_impl(s, d_instances, n_instances);
+}
+
+int crt_instances_refit(crt_instances* s, const crt_instance* instances, uint32_t n_instances) {
+    if (!s || (n_instances && !instances)) return fail(CRT_ERR_INVALID, "crt_instances_refit: null argument");
+    if (n_instances != s->n_instances)
+        return fail(CRT_ERR_INVALID, "crt_instances_refit: n_instances (" + std::to_string(n_instances) + ") differs from the live count (" +
+                                         std::to_string(s->n_instances) + ")");
+    IHIPCHK(hipSetDevice(s->device));
+    if (n_instances) IHIPCHK(hipMemcpyAsync(s->d_in, instances, (size_t)n_instances * sizeof(crt_instance), hipMemcpyHostToDevice, s->stream));
+    try {
+        return refit_impl(s, s->d_in, n_instances, "crt_instances_refit: ");
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_instances_refit: ") + e.what());
+    }
+}
+
+int crt_instances_refit_device(crt_instances* s, const void* d_instances, uint32_t n_instances, int sync) {
+    if (!s || (n_instances && !d_instances)) return fail(CRT_ERR_INVALID, "crt_instances_refit_device: null argument");
+    IHIPCHK(hipSetDevice(s->device));
+    (void)sync;                                   // the check's verdict waits on the host: a refit always returns done, as a set does
+    try {
+        return refit_impl(s, d_instances, n_instances, "crt_instances_refit_device: ");
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_instances_refit_device: ") + e.what());
+    }
 }
 
 int crt_instances_trace_device(crt_instances* s, const void* d_rays, size_t n, void* d_hits, void* d_instance_of_hit, int mode, void* d_stats, int sync) {

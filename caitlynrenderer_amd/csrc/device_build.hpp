@@ -78,16 +78,17 @@ void launch_gather_slots(const crt_triangle* d_in, const uint32_t* d_tri_order, 
 void launch_gather_records(const crt_triangle* d_in, const uint32_t* d_tri_order, const int32_t* d_tri_slots, const float* d_verts, uint32_t n_tris8,
                            float4* d_recs, hipStream_t stream);
 
-// ---- refit to new vertex positions, same topology (refit.hip): crt_update_vertices and crt_instances_update_meshes ----
+// ---- refit to new positions, same topology (refit.hip): crt_update_vertices, crt_instances_update_meshes, crt_instances_refit ----
 // One refitted tree's geometry.  Index entry e holds a triangle's three vertex indices at idx[stride * e + 0..2]; a record names its entry
-// in the w word of row key_row.  Scene: d_triangles (crt_triangle, stride 12), the slot in e1.w.  BLAS: its slice of the source-order
-// index array (stride 3), the source id in v0.w.
+// in its 32-bit word key_word.  Scene: d_triangles (crt_triangle, stride 12), the slot in e1.w.  BLAS: its slice of the source-order
+// index array (stride 3), the source id in v0.w.  TLAS: the world boxes as 2 vertices each, the triples of launch_box_triples, the
+// instance index in row 3 .y of the instance record (4 rows: node8 level kernel only).
 struct RefitMesh {
     const float* verts;        // xyz per vertex
     const int32_t* idx;
     uint32_t stride;           // ints per entry
     uint32_t n_idx;            // valid entries
-    uint32_t key_row;          // 0: v0.w, 1: e1.w
+    uint32_t key_word;         // 3: v0.w, 7: e1.w, 13: row 3 .y
     uint32_t n_vertices;
 };
 static_assert(sizeof(RefitMesh) == 32, "RefitMesh is 32 bytes");
@@ -116,9 +117,11 @@ constexpr uint32_t kCheckChunk = 4096;      // vertices and triangles per block 
 // One block per chunk: d_chunk_start[k] = first block of mesh k (d_chunk_start[0] = 0); d_out: 8 words per mesh, zeroed before the launch.
 void launch_check_meshes(const RefitMesh* d_meshes, const uint32_t* d_chunk_start, uint32_t n, uint32_t n_chunks, uint32_t* d_out,
                          hipStream_t stream);
-// records at `rows` float4 per item: entries [0, count) of the segments, regathered in place from their mesh's index entry
+// records at `rows` float4 per item: entries [0, count) of the segments, regathered in place from their mesh's index entry (key_word 3 or 7)
 void launch_refit_records(void* d_recs, uint32_t rows, uint32_t n_recs, const RefitSeg* d_segs, uint32_t n_segs, uint32_t count,
                           const RefitMesh* d_meshes, hipStream_t stream);
+// d_idx[3i .. 3i + 2] = (2i, 2i + 1, 2i), i < n: a box array (lo, hi per item) as a refit mesh of 2n vertices
+void launch_box_triples(int32_t* d_idx, uint32_t n, hipStream_t stream);
 // one level of each tree (d_order: its node indices); call deepest level first
 void launch_refit_bvh2_level(void* d_flat, uint32_t n2, const uint32_t* d_order, uint32_t count, const void* d_tris, uint32_t n_slots,
                              const float* d_verts, hipStream_t stream);

@@ -69,6 +69,15 @@ __global__ void __launch_bounds__(256) k_gather_instances(const float4* __restri
     for (int k = 0; k < 4; ++k) out[4 * (size_t)i + k] = rec[4 * (size_t)src + k];
 }
 
+// crt_instances_refit: each leaf slot of the live TLAS takes the new record of the instance it already holds (row 3 .y), in place
+__global__ void __launch_bounds__(256) k_regather_instances(const float4* __restrict__ rec, uint32_t n, float4* __restrict__ inst) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t src = __float_as_uint(inst[4 * (size_t)i + 3].y);
+    if (src >= n) return;
+    for (int k = 0; k < 4; ++k) inst[4 * (size_t)i + k] = rec[4 * (size_t)src + k];
+}
+
 // direction-dependent part of a walk's ray: octant and clamped reciprocal (traverse() / walk_pool's prologue)
 __device__ __forceinline__ void ray_setup(vec3 d, vec3& inv, bool& negx, bool& negy, bool& negz, uint32_t& oct4) {
     const vec3 dc = V3(clamp_dir(d.x), clamp_dir(d.y), clamp_dir(d.z));
@@ -249,6 +258,9 @@ void launch_single_leaf(const float* d_box, crt_flatnode* d_flat, uint32_t* d_tr
 }
 void launch_gather_instances(const float4* d_rec, const uint32_t* d_tri_order, const int32_t* d_tri_slots, uint32_t n, float4* d_out, hipStream_t stream) {
     if (n) hipLaunchKernelGGL(k_gather_instances, grid_for(n), dim3(256), 0, stream, d_rec, d_tri_order, d_tri_slots, n, d_out);
+}
+void launch_regather_instances(const float4* d_rec, uint32_t n, float4* d_inst, hipStream_t stream) {
+    if (n) hipLaunchKernelGGL(k_regather_instances, grid_for(n), dim3(256), 0, stream, d_rec, n, d_inst);
 }
 void launch_trace_instances(const InstTraceArgs& a, int any, bool stats, uint32_t chunks, hipStream_t stream) {
     const dim3 g(chunks * 16u), b(64);                      // sixteen single-wave workgroups per 1024-ray chunk: 64-ray pools (wave_id)

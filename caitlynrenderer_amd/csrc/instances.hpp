@@ -40,6 +40,8 @@ void launch_rebase_nodes(void* d_nodes, uint32_t n8, uint32_t node_off, uint32_t
 void launch_single_leaf(const float* d_box, crt_flatnode* d_flat, uint32_t* d_tri_order, hipStream_t stream);
 // out[i] = rec[tri_order[tri_slots[i]]] (4 rows): the instance records in CWBVH leaf order
 void launch_gather_instances(const float4* d_rec, const uint32_t* d_tri_order, const int32_t* d_tri_slots, uint32_t n, float4* d_out, hipStream_t stream);
+// in place, i < n: inst[i] = rec[inst[i] row 3 .y] (4 rows): the live TLAS leaf order kept, each record renewed (crt_instances_refit)
+void launch_regather_instances(const float4* d_rec, uint32_t n, float4* d_inst, hipStream_t stream);
 // `chunks`: 1024-ray chunks of the dense index space (k_trace's mapping), a multiple of 8
 void launch_trace_instances(const InstTraceArgs& a, int any, bool stats, uint32_t chunks, hipStream_t stream);
 

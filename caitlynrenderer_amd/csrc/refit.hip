@@ -1,4 +1,5 @@
-// Refit kernels of crt_update_vertices and crt_instances_update_meshes (§12): new vertex positions, same topology.  The
+// Refit kernels of crt_update_vertices, crt_instances_update_meshes (§12) and crt_instances_refit (§13): new vertex
+// positions or instance boxes, same topology.  The
 // trees and record arrays are rewritten in place, one launch per tree level, deepest first (the kernel boundary orders the levels, as in
 // lbvh.hip k_refit_level).  The records and node8 kernels serve both callers: each refitted tree is a RefitMesh (device_build.hpp), and a
 // per-launch segment table maps an entry to its mesh and item, so one launch covers every mesh of an instanced call and a scene is the
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256) void k_refit_records(float4* __restrict__ recs
     const RefitMesh m = meshes[sg.mesh];
     float4* r = recs + (size_t)i * rows;
     float4 a = r[0], b = r[1], c = r[2];
-    const uint32_t e = (uint32_t)__float_as_int(m.key_row ? b.w : a.w);
+    const uint32_t e = (uint32_t)__float_as_int(m.key_word < 4u ? a.w : b.w);      // scenes and BLASes: v0.w or e1.w
     if (e >= m.n_idx) return;
     const int32_t* t = m.idx + (size_t)m.stride * e;
     const float* v0 = m.verts + 3 * (size_t)(uint32_t)t[0];
@@ -213,7 +214,7 @@ __global__ __launch_bounds__(256) void k_refit_node8_level(uint4* __restrict__ n
             const uint32_t first = r1.y + (uint32_t)rf::leaf_offset(meta), cnt = (uint32_t)rf::leaf_count(meta);
             for (uint32_t k = 0; k < cnt; ++k) {
                 if (first + k >= n_recs) break;
-                const uint32_t e = (uint32_t)__float_as_int(recs[(size_t)(first + k) * tri_rows + m.key_row].w);
+                const uint32_t e = reinterpret_cast<const uint32_t*>(recs)[4 * (size_t)(first + k) * tri_rows + m.key_word];
                 if (e >= m.n_idx) continue;
                 const int32_t* tr = m.idx + (size_t)m.stride * e;
                 const int32_t v[3] = {tr[0], tr[1], tr[2]};
@@ -249,6 +250,15 @@ __global__ __launch_bounds__(256) void k_refit_node8_level(uint4* __restrict__ n
         dst[0] = make_uint4(__float_as_uint(p[0]), __float_as_uint(p[1]), __float_as_uint(p[2]),
                             (uint32_t)e[0] | ((uint32_t)e[1] << 8) | ((uint32_t)e[2] << 16) | (imask << 24));
     }
+}
+
+// the TLAS as a refit mesh: instance i's world box (lo, hi) is vertices 2i and 2i + 1 of the box array, its triangle (2i, 2i + 1, 2i)
+__global__ void k_box_triples(int32_t* __restrict__ idx, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    idx[3 * (size_t)i] = (int32_t)(2u * i);
+    idx[3 * (size_t)i + 1] = (int32_t)(2u * i + 1u);
+    idx[3 * (size_t)i + 2] = (int32_t)(2u * i);
 }
 
 inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)std::max<uint64_t>(1u, (n + 255u) / 256u)); }
@@ -309,6 +319,9 @@ void launch_check_vertices(const float* d_verts, uint32_t n_vertices, uint32_t* 
 void launch_check_meshes(const RefitMesh* d_meshes, const uint32_t* d_chunk_start, uint32_t n, uint32_t n_chunks, uint32_t* d_out,
                          hipStream_t stream) {
     if (n && n_chunks) hipLaunchKernelGGL(k_check_meshes, dim3(n_chunks), dim3(256), 0, stream, d_meshes, d_chunk_start, n, d_out);
+}
+void launch_box_triples(int32_t* d_idx, uint32_t n, hipStream_t stream) {
+    if (n) hipLaunchKernelGGL(k_box_triples, grid_for(n), dim3(256), 0, stream, d_idx, n);
 }
 void launch_refit_records(void* d_recs, uint32_t rows, uint32_t n_recs, const RefitSeg* d_segs, uint32_t n_segs, uint32_t count,
                           const RefitMesh* d_meshes, hipStream_t stream) {

@@ -1,6 +1,7 @@
 """Instanced scenes: one bottom-level CWBVH per mesh, built once on the device, under a top-level CWBVH over transformed instances that
-is rebuilt on the device at every `set` (include/crt.h crt_instances_*).  An updatable scene also moves the vertices of its
-meshes: a GPU refit of their BLASes and a TLAS rebuild per update.  Ray queries only: no frames."""
+is rebuilt on the device at every `set` (include/crt.h crt_instances_*) or refitted in place by `refit`, which moves the
+instances and keeps the TLAS's topology (§13).  An updatable scene also moves the vertices of its meshes: a GPU refit of their BLASes and a
+TLAS rebuild per update.  Ray queries only: no frames."""
 import ctypes as C
 
 import numpy as np
@@ -82,6 +83,15 @@ class InstancedScene:
     def set_device(self, ptr, n, sync=True):
         """instances already in device memory (e.g. a torch uint8 / float tensor of n * 64 bytes: pass tensor.data_ptr())."""
         check(lib().crt_instances_set_device(self._h, C.c_void_p(ptr), int(n), 1 if sync else 0))
+
+    def refit(self, instances):
+        """same count, new matrices (and meshes): the TLAS refitted in place, its topology kept (crt_instances_refit)"""
+        inst = np.ascontiguousarray(instances, INSTANCE_DT)
+        check(lib().crt_instances_refit(self._h, _ptr(inst), inst.shape[0]))
+
+    def refit_device(self, ptr, n, sync=True):
+        """refit from instances already in device memory (n * 64 bytes at ptr)"""
+        check(lib().crt_instances_refit_device(self._h, C.c_void_p(ptr), int(n), 1 if sync else 0))
 
     def update_meshes(self, vertices_by_mesh):
         """{mesh index: (n, 3) float32 positions in the create's order}: one crt_instances_update_meshes call for all of them."""

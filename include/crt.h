@@ -428,7 +428,7 @@ typedef struct crt_instances_info {
     uint64_t blas_nodes8, blas_tris;          /* every mesh once, whatever the instance count */
     uint64_t blas_bytes, tlas_bytes, instance_bytes;   /* device bytes: BLAS nodes + records; TLAS region for `capacity`; per-instance buffers */
     uint64_t tlas_build_bytes;                /* device bytes kept for the sets: the TLAS builder's temporaries and node staging for `capacity` */
-    float set_device_ms, set_wall_ms;         /* the last create / set: device time of its kernels, host wall time of the call */
+    float set_device_ms, set_wall_ms;         /* the last create / set / refit: device time of its kernels, host wall time of the call */
     float create_wall_ms, reserved_f;
 } crt_instances_info;
 
@@ -451,6 +451,21 @@ int crt_instances_set(crt_instances* s, const crt_instance* instances, uint32_t 
  * on the device, the host waits once for its verdict.  Returns when the set is done (sync is accepted for symmetry with the other
  * *_device calls). */
 int crt_instances_set_device(crt_instances* s, const void* d_instances, uint32_t n_instances, int sync);
+/* Moving instances without a TLAS rebuild (the top-level update of DXR / Vulkan RT / OptiX): n_instances must equal the
+ * live count, and each instance may change its matrix and its mesh.  The TLAS keeps its topology (the same node8s, the same leaf slots,
+ * each leaf slot the same instance index); only the node8 origins, exponents and quantised boxes are refitted, on the device, to the new
+ * world boxes.  The checks are those of a set, run on the device first (finite and non-singular matrix, finite inverse, mesh in range,
+ * world box within 1e18): a failed one, a count other than the live count or a null pointer returns CRT_ERR_INVALID, and nothing the
+ * walk reads has changed.  CRT_ERR_LIMIT cannot happen (the stack bound is TLAS depth + deepest BLAS, and a refit changes neither).
+ * world_to_object, the world boxes and the instance records are the bits a crt_instances_set of the same array produces; closest hits
+ * (t, u, v, tri, instance) equal those of such a set bit for bit, the grazing-margin exception of crt_instances_trace aside, since the
+ * closest hit does not depend on the tree.  Per-ray node counts may differ, and the walk slows as the instances move away from the
+ * placement the TLAS was built for: call crt_instances_set to rebuild.  An updatable handle keeps the refitted array as its live
+ * instances (crt_instances_update_meshes starts from it).  The first refit after a create, set or update finds the TLAS's levels (one
+ * more host wait and a temporary allocation); later refits allocate nothing.  Synchronous, with one host wait for the verdict; the
+ * device form's sync is accepted for symmetry.  crt_instances_info's set_device_ms / set_wall_ms then describe the refit. */
+int crt_instances_refit(crt_instances* s, const crt_instance* instances, uint32_t n_instances);
+int crt_instances_refit_device(crt_instances* s, const void* d_instances, uint32_t n_instances, int sync);
 /* Closest- or any-hit queries (mode CRT_TRACE_CLOSEST or CRT_TRACE_ANY; anything else is CRT_ERR_INVALID) over host rays.
  * hits[i].tri = the triangle id within the mesh of instance_of_hit[i] (-1 and -1 on a miss); instance_of_hit and stats may be NULL.
  * Numerical contract (tests/test_instances.py holds the kernel to it bit for bit):
