@@ -5,7 +5,7 @@ include/crt.h); this package is the thin host-side mirror of the reference's Sce
 SBVH / CWBVH interface plus tile sharding helpers.  Importing it without a built libcrt.so fails.
 """
 from . import _lib
-from ._lib import CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_CLOSEST, CRT_TRACE_TIE_LOWEST_ID, CrtError
+from ._lib import CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_CLOSEST, CRT_TRACE_INSTANCE_MASK, CRT_TRACE_TIE_LOWEST_ID, CrtError
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, pcg_hash
 from .scene import HIT_DT, RAY_DT, STATS_DT, Scene, SceneData
 from .instances import INSTANCE_DT, InstancedScene, instance_inverse, instance_world_box, instances_array
@@ -25,4 +25,5 @@ def warmup():
 
 __all__ = ["has_experiments", "warmup", "Scene", "SceneData", "InstancedScene", "INSTANCE_DT", "instances_array", "instance_inverse",
            "instance_world_box", "Camera", "Mesh", "SBVH", "CWBVH", "Rnd", "pcg_hash", "CrtError",
-           "RAY_DT", "HIT_DT", "STATS_DT", "CRT_TRACE_CLOSEST", "CRT_TRACE_ANY", "CRT_TRACE_BVH2", "CRT_TRACE_TIE_LOWEST_ID"]
+           "RAY_DT", "HIT_DT", "STATS_DT", "CRT_TRACE_CLOSEST", "CRT_TRACE_ANY", "CRT_TRACE_BVH2", "CRT_TRACE_TIE_LOWEST_ID",
+           "CRT_TRACE_INSTANCE_MASK"]

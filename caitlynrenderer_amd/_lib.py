@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("CRT_LIB") or os.path.join(_HERE, "libcrt.so")
 CRT_ABI_VERSION = int(os.environ.get("CRT_LIB_ABI", "6"))      # CRT_LIB_ABI: with CRT_LIB, an older build of the library measured beside this one (tools/ab_run.sh)
 CRT_OK, CRT_ERR_INVALID, CRT_ERR_NO_DEVICE, CRT_ERR_HIP, CRT_ERR_IO, CRT_ERR_LIMIT, CRT_ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6
 CRT_TRACE_CLOSEST, CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_TIE_LOWEST_ID = 0, 1, 2, 4
+CRT_TRACE_INSTANCE_MASK = 8              # crt_instances_trace only: the low 8 bits of crt_ray.pad are the ray's instance mask
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
 CRT_INSTANCES_UPDATABLE = 1 << 16
@@ -70,7 +71,7 @@ class crt_blas_desc(C.Structure):
 
 
 class crt_instance(C.Structure):
-    _fields_ = [("object_to_world", C.c_float * 12), ("mesh", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+    _fields_ = [("object_to_world", C.c_float * 12), ("mesh", C.c_uint32), ("mask", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class crt_instances_info(C.Structure):

@@ -104,6 +104,12 @@ struct crt_instances {
     int32_t* d_box_idx = nullptr;         // (2i, 2i + 1, 2i) per instance: instance i's world box as a triangle of d_box
     uint8_t* d_tlas_table = nullptr;      // the TLAS's RefitMesh, then one RefitSeg per level
     std::vector<uint8_t> tlas_table;
+    // masked traces: 8 B per TLAS node8, byte i = OR of the masks under meta slot i.  Stale after every publish and refit;
+    // the next masked trace or debug read recomputes them on the stream (ensure_child_masks).  Reserved at create
+    bool cmask_ok = false;
+    uint2* d_cmask = nullptr;             // tlas_cap_nodes x 8 B
+    uint32_t* d_cm_parent = nullptr;      // tlas_cap_nodes: (parent node << 3 | meta slot) of each TLAS node8
+    uint32_t* d_cm_leaf = nullptr;        // capacity: (node << 3 | meta slot) of the leaf slot holding each instance record
     // crt_instances_trace's device copies of the host rays
     void* d_t_rays = nullptr; void* d_t_hits = nullptr; void* d_t_inst = nullptr; void* d_t_stats = nullptr;
     size_t t_cap = 0;
@@ -111,7 +117,8 @@ struct crt_instances {
 
     ~crt_instances() {
         void* bufs[] = {d_nodes, d_tris, d_inst, d_w2o, d_wbox, d_mesh_box, d_mesh_root, d_in, d_rec, d_box, d_w2o_stage, d_flag, d_overflow,
-                        d_t8_stage, d_t_rays, d_t_hits, d_t_inst, d_t_stats, d_tlas_order, d_tlas_box8, d_box_idx, d_tlas_table};
+                        d_t8_stage, d_t_rays, d_t_hits, d_t_inst, d_t_stats, d_tlas_order, d_tlas_box8, d_box_idx, d_tlas_table, d_cmask, d_cm_parent,
+                        d_cm_leaf};
         if (stream) (void)hipStreamSynchronize(stream);
         upd.reset();
         for (void* p : bufs) if (p) (void)hipFree(p);
@@ -237,6 +244,7 @@ int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const float* d_m
 int publish_tlas(crt_instances* s, const void* d_src, uint32_t n, const TlasStage& ts) {
     hipStream_t st = s->stream;
     s->tlas_levels_ok = false;                    // a new topology: the next refit finds its levels
+    s->cmask_ok = false;
     IHIPCHK(hipMemcpyAsync(s->d_nodes, ts.d_t8, (size_t)ts.n8 * sizeof(crt_node8), hipMemcpyDeviceToDevice, st));
     crt::launch_gather_instances(s->d_rec, s->d_tri_order, s->d_tri_slots, n, s->d_inst, st);
     IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
@@ -313,6 +321,7 @@ int refit_impl(crt_instances* s, const void* d_src, uint32_t n, const std::strin
             crt::launch_refit_node8_level(s->d_nodes, 5u, 0u, s->n_tlas8, s->d_tlas_order, d_seg + L, 1u, lv[L + 1] - lv[L], s->d_inst, 4u, n, d_mesh,
                                           s->d_tlas_box8, st);
         crt::launch_regather_instances(s->d_rec, n, s->d_inst, st);
+        s->cmask_ok = false;                      // the records may carry new masks
         IHIPCHK(hipGetLastError());
         IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
         IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
@@ -324,6 +333,17 @@ int refit_impl(crt_instances* s, const void* d_src, uint32_t n, const std::strin
     IHIPCHK(hipGetLastError());
     IHIPCHK(hipEventElapsedTime(&s->set_device_ms, s->ev0, s->ev1));
     s->set_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// The TLAS child masks of the live TLAS and records, if stale: two launches on the handle's stream, ordered before whatever the caller
+// enqueues next there (the masked walk, a debug read).  No host wait, no allocation.
+int ensure_child_masks(crt_instances* s) {
+    if (s->cmask_ok) return CRT_OK;
+    if (s->n_instances)
+        crt::launch_tlas_child_masks(s->d_nodes, s->n_tlas8, s->d_inst, s->n_instances, s->d_cm_parent, s->d_cm_leaf, s->d_cmask, s->stream);
+    IHIPCHK(hipGetLastError());
+    s->cmask_ok = true;
     return CRT_OK;
 }
 
@@ -572,7 +592,8 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     if ((rc = alloc(&s->d_inst, C * 4)) || (rc = alloc(&s->d_w2o, C * 12)) || (rc = alloc(&s->d_wbox, C * 6)) || (rc = alloc(&s->d_in, C * 16)) ||
         (rc = alloc(&s->d_rec, C * 4)) || (rc = alloc(&s->d_box, C * 6)) || (rc = alloc(&s->d_w2o_stage, C * 12)) || (rc = alloc(&s->d_flag, 1)) ||
         (rc = alloc(&s->d_overflow, 1)) || (rc = alloc(&s->d_t8_stage, s->tlas_cap_nodes)) || (rc = alloc(&s->d_tlas_box8, 6 * (size_t)s->tlas_cap_nodes)) ||
-        (rc = alloc(&s->d_box_idx, C * 3)) || (rc = alloc(&s->d_tlas_table, sizeof(crt::RefitMesh) + 255 * sizeof(crt::RefitSeg))))
+        (rc = alloc(&s->d_box_idx, C * 3)) || (rc = alloc(&s->d_tlas_table, sizeof(crt::RefitMesh) + 255 * sizeof(crt::RefitSeg))) ||
+        (rc = alloc(&s->d_cmask, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_parent, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_leaf, C)))
         return rc;
     crt::launch_box_triples(s->d_box_idx, capacity, st);
     IHIPCHK(hipMemsetAsync(s->d_overflow, 0, 4, st));
@@ -666,22 +687,26 @@ int crt_instances_refit_device(crt_instances* s, const void* d_instances, uint32
 
 int crt_instances_trace_device(crt_instances* s, const void* d_rays, size_t n, void* d_hits, void* d_instance_of_hit, int mode, void* d_stats, int sync) {
     if (!s || (n && (!d_rays || !d_hits))) return fail(CRT_ERR_INVALID, "crt_instances_trace_device: null argument");
-    if (mode != CRT_TRACE_CLOSEST && mode != CRT_TRACE_ANY)
-        return fail(CRT_ERR_INVALID, "crt_instances_trace_device: mode must be CRT_TRACE_CLOSEST or CRT_TRACE_ANY");
+    const int base = mode & ~CRT_TRACE_INSTANCE_MASK;
+    if (base != CRT_TRACE_CLOSEST && base != CRT_TRACE_ANY)
+        return fail(CRT_ERR_INVALID, "crt_instances_trace_device: mode must be CRT_TRACE_CLOSEST or CRT_TRACE_ANY, optionally | CRT_TRACE_INSTANCE_MASK");
+    const bool masked = (mode & CRT_TRACE_INSTANCE_MASK) != 0;
     if (n >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_instances_trace_device: too many rays for one launch");
     IHIPCHK(hipSetDevice(s->device));
     if (n == 0) return CRT_OK;
-    crt::InstTraceArgs a{};
+    crt::InstMaskTraceArgs a{};
     a.nodes = s->d_nodes; a.tris = s->d_tris; a.inst = s->d_inst;
     a.rays = static_cast<const float4*>(d_rays); a.hits = static_cast<float4*>(d_hits);
     a.inst_out = static_cast<int32_t*>(d_instance_of_hit); a.stats = static_cast<uint32_t*>(d_stats);
     a.n = (uint32_t)n; a.n_instances = s->n_instances; a.stack_entries = s->stack_entries;
     a.refill_min = 8; a.tri_min = 2;              // crt_trace's defaults (options refill_min, tri_min)
     a.overflow = s->d_overflow;
+    a.child_masks = s->d_cmask; a.n_tlas8 = s->n_tlas8;
+    if (masked) { const int rc = ensure_child_masks(s); if (rc) return rc; }
     // k_trace's grid: every XCD group's share of 4096-ray units, in 1024-ray chunks
     const uint64_t share = ((n + 4095) / 4096 + 7) / 8 * 4096;
     const uint32_t chunks = (uint32_t)std::max<uint64_t>(8, 8 * ((share + 1023) / 1024));
-    crt::launch_trace_instances(a, mode, d_stats != nullptr, chunks, s->stream);
+    crt::launch_trace_instances(a, base, d_stats != nullptr, masked, chunks, s->stream);
     IHIPCHK(hipGetLastError());
     if (sync) IHIPCHK(hipStreamSynchronize(s->stream));
     return CRT_OK;
@@ -689,8 +714,9 @@ int crt_instances_trace_device(crt_instances* s, const void* d_rays, size_t n, v
 
 int crt_instances_trace(crt_instances* s, const crt_ray* rays, size_t n, crt_hit* hits, int32_t* instance_of_hit, int mode, crt_ray_stats* stats) {
     if (!s || (n && (!rays || !hits))) return fail(CRT_ERR_INVALID, "crt_instances_trace: null argument");
-    if (mode != CRT_TRACE_CLOSEST && mode != CRT_TRACE_ANY)
-        return fail(CRT_ERR_INVALID, "crt_instances_trace: mode must be CRT_TRACE_CLOSEST or CRT_TRACE_ANY");
+    const int base = mode & ~CRT_TRACE_INSTANCE_MASK;
+    if (base != CRT_TRACE_CLOSEST && base != CRT_TRACE_ANY)
+        return fail(CRT_ERR_INVALID, "crt_instances_trace: mode must be CRT_TRACE_CLOSEST or CRT_TRACE_ANY, optionally | CRT_TRACE_INSTANCE_MASK");
     IHIPCHK(hipSetDevice(s->device));
     if (n == 0) return CRT_OK;
     if (n > s->t_cap) {
@@ -725,7 +751,8 @@ int crt_instances_get_info(crt_instances* s, crt_instances_info* out) {
     i.blas_nodes8 = s->blas_nodes8; i.blas_tris = s->blas_tris;
     i.blas_bytes = s->blas_nodes8 * sizeof(crt_node8) + s->blas_tris * 48;
     i.tlas_bytes = (uint64_t)s->tlas_cap_nodes * sizeof(crt_node8);
-    i.instance_bytes = (uint64_t)s->capacity * (64 + 48 + 24 + 64 + 64 + 24 + 48);   // live records, matrices, boxes + the set's staging
+    i.instance_bytes = (uint64_t)s->capacity * (64 + 48 + 24 + 64 + 64 + 24 + 48)    // live records, matrices, boxes + the set's staging
+                       + (uint64_t)s->tlas_cap_nodes * (8 + 4) + (uint64_t)s->capacity * 4;   // TLAS child masks + their parent / leaf links
     i.tlas_build_bytes = (uint64_t)s->arena.cap + (uint64_t)s->tlas_cap_nodes * sizeof(crt_node8);   // the TLAS builder's arena + node staging
     i.set_device_ms = s->set_device_ms; i.set_wall_ms = s->set_wall_ms; i.create_wall_ms = s->build_wall_ms;
     *out = i;
@@ -743,12 +770,14 @@ int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_
         case 3: src = s->d_inst; n = s->n_instances; item = 64; break;
         case 4: src = s->d_nodes + 5 * (size_t)s->tlas_cap_nodes; n = s->blas_nodes8; item = sizeof(crt_node8); break;
         case 5: src = s->d_tris; n = s->blas_tris; item = 48; break;
-        default: return fail(CRT_ERR_INVALID, "crt_instances_debug_read: which must be 0..5");
+        case 6: src = s->d_cmask; n = s->n_instances ? s->n_tlas8 : 0; item = 8; break;
+        default: return fail(CRT_ERR_INVALID, "crt_instances_debug_read: which must be 0..6");
     }
     if (n_out) *n_out = n;
     if (!dst || n == 0) return CRT_OK;
     if (cap_bytes < n * item) return fail(CRT_ERR_INVALID, "crt_instances_debug_read: destination too small");
     IHIPCHK(hipSetDevice(s->device));
+    if (which == 6) { const int rc = ensure_child_masks(s); if (rc) return rc; }
     IHIPCHK(hipStreamSynchronize(s->stream));
     IHIPCHK(hipMemcpy(dst, src, n * item, hipMemcpyDeviceToHost));
     return CRT_OK;

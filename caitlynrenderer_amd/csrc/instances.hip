@@ -5,8 +5,11 @@
 // are at different levels still runs a single node step together.  A TLAS leaf's "triangles" are instances: the instance step pushes
 // what the lane still has pending at the TLAS level (inner hits, the rest of the leaf), then a return marker, moves the ray into object
 // space and continues at the BLAS root.  Popping the marker restores the world ray, which the lane keeps in registers.
+// The masked walk (MASK) culls TLAS children whose instances are all hidden from the ray and skips hidden instances.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "instances.hpp"
 #include "rt_kernels.hpp"
@@ -37,7 +40,8 @@ __global__ void __launch_bounds__(256) k_instance_prep(InstPrepArgs a) {
     r[0] = make_float4(w[0], w[1], w[2], w[3]);
     r[1] = make_float4(w[4], w[5], w[6], w[7]);
     r[2] = make_float4(w[8], w[9], w[10], w[11]);
-    r[3] = make_float4(__uint_as_float(a.mesh_root[mesh]), __uint_as_float(i), __uint_as_float(instance_is_identity(m) ? 1u : 0u), 0.f);
+    r[3] = make_float4(__uint_as_float(a.mesh_root[mesh]), __uint_as_float(i), __uint_as_float(instance_is_identity(m) ? 1u : 0u),
+                       __uint_as_float(src[13] & 0xffu));       // crt_instance.mask: bits 8..31 are ignored
     for (int k = 0; k < 6; ++k) a.box[6 * (size_t)i + k] = box[k];
     for (int k = 0; k < 12; ++k) a.w2o[12 * (size_t)i + k] = w[k];
 }
@@ -78,6 +82,59 @@ __global__ void __launch_bounds__(256) k_regather_instances(const float4* __rest
     for (int k = 0; k < 4; ++k) inst[4 * (size_t)i + k] = rec[4 * (size_t)src + k];
 }
 
+// TLAS child masks, pass 1, one thread per live TLAS node8: its 8 bytes zeroed, and the link (node << 3 | meta slot) of each child
+// written: to parent[] for an inner child, to leaf_of[] for every instance position a leaf slot holds.  The root's parent is ~0.
+__global__ void __launch_bounds__(256) k_tlas_links(const uint4* __restrict__ nodes, uint32_t n8, uint32_t n, uint32_t* __restrict__ parent,
+                                                    uint32_t* __restrict__ leaf_of, uint2* __restrict__ child_masks) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    const uint4 n0 = nodes[5 * (size_t)i], n1 = nodes[5 * (size_t)i + 1];
+    child_masks[i] = make_uint2(0u, 0u);
+    if (i == 0) parent[0] = 0xffffffffu;
+    const uint32_t imask = n0.w >> 24;
+    for (uint32_t slot = 0; slot < 8u; ++slot) {
+        const uint32_t meta = ((slot < 4u ? n1.z : n1.w) >> (8u * (slot & 3u))) & 0xffu;
+        const uint32_t link = (i << 3) | slot;
+        if ((imask >> slot) & 1u) {
+            // the walk's child index: child base + the inner slots below this one
+            const uint32_t c = n1.x + (uint32_t)__builtin_popcount(imask & ((1u << slot) - 1u));
+            if (c < n8) parent[c] = link;
+        } else if (meta) {
+            // a leaf slot: (meta >> 5) unary count of instance positions from triangle base + (meta & 31)
+            const uint32_t first = n1.y + (meta & 0x1fu), cnt = (uint32_t)__builtin_popcount(meta >> 5);
+            for (uint32_t k = 0; k < cnt; ++k)
+                if (first + k < n) leaf_of[first + k] = link;
+        }
+    }
+}
+
+// TLAS child masks, pass 2, one thread per instance position: its mask ORed into the slot that holds it and up through its ancestors.
+// Only the bits the OR newly set travel on: a bit already present was set by a thread that carries it up itself.
+__global__ void __launch_bounds__(256) k_tlas_mask_up(const float4* __restrict__ inst, uint32_t n, uint32_t n8, const uint32_t* __restrict__ parent,
+                                                      const uint32_t* __restrict__ leaf_of, uint32_t* __restrict__ words) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    uint32_t m = __float_as_uint(inst[4 * (size_t)p + 3].w) & 0xffu;
+    uint32_t link = leaf_of[p];
+    for (uint32_t up = 0; m != 0u && link != 0xffffffffu && up < 64u; ++up) {      // 64: beyond any TLAS depth the stack admits
+        const uint32_t node = link >> 3, sh = 8u * (link & 3u);
+        if (node >= n8) break;
+        const uint32_t old = atomicOr(words + 2u * node + ((link >> 2) & 1u), m << sh);
+        m &= ~(old >> sh);
+        link = parent[node];
+    }
+}
+
+// the ray's mask against one TLAS node8's child masks: bit i set iff byte i of cm meets rmask (rmask <= 0xff)
+__device__ __forceinline__ uint32_t child_keep(uint2 cm, uint32_t rmask) {
+    const uint32_t r4 = rmask * 0x01010101u;
+    uint32_t lo = cm.x & r4, hi = cm.y & r4;
+    lo = (((lo & 0x7f7f7f7fu) + 0x7f7f7f7fu) | lo) & 0x80808080u;      // 0x80 in each non-zero byte, no carry between bytes
+    hi = (((hi & 0x7f7f7f7fu) + 0x7f7f7f7fu) | hi) & 0x80808080u;
+    // bits 0, 8, 16, 24 times 2^21 + 2^14 + 2^7 + 1 land on bits 21..24 without carries
+    return ((((lo >> 7) * 0x00204081u) >> 21) & 0xfu) | (((((hi >> 7) * 0x00204081u) >> 21) & 0xfu) << 4);
+}
+
 // direction-dependent part of a walk's ray: octant and clamped reciprocal (traverse() / walk_pool's prologue)
 __device__ __forceinline__ void ray_setup(vec3 d, vec3& inv, bool& negx, bool& negy, bool& negz, uint32_t& oct4) {
     const vec3 dc = V3(clamp_dir(d.x), clamp_dir(d.y), clamp_dir(d.z));
@@ -88,8 +145,10 @@ __device__ __forceinline__ void ray_setup(vec3 d, vec3& inv, bool& negx, bool& n
 
 // One lane per ray, pools of 64 rays per wave with lane refill (k_trace's mapping with crt_trace's default pool of 64: each 256-ray slot
 // of the index space is walked by four single-wave workgroups), one loop and one LDS stack over both levels.  Stack entries: a node group (top byte set), the rest of a TLAS leaf (low 24 bits only) or the return marker (y == 0).
-template <bool ANY, bool STATS>
-__global__ void __launch_bounds__(64) k_trace_instances(InstTraceArgs a) {
+// MASK: the low 8 bits of the ray's pad word are its mask; a TLAS step culls the children whose child mask does not meet it, and the
+// instance step skips an instance whose mask does not, before it transforms the ray.  Without MASK every such test folds away.
+template <bool ANY, bool STATS, bool MASK>
+__global__ void __launch_bounds__(64) k_trace_instances(std::conditional_t<MASK, InstMaskTraceArgs, InstTraceArgs> a) {
     extern __shared__ uint2 s_lds[];          // [level][lane] of the workgroup's one wave
     const WaveId wid = wave_id(false, false, 2u);
     const uint32_t lane = wid.lane;
@@ -101,7 +160,7 @@ __global__ void __launch_bounds__(64) k_trace_instances(InstTraceArgs a) {
         uint32_t next = dense_pool_first(v, wid.wave) + wid.sub * 64u;
         if (next >= a.n) continue;
         const uint32_t end = next + 64u < a.n ? next + 64u : a.n;
-        uint32_t idx = 0, nn = 0, nt = 0, inst_cur = 0;
+        uint32_t idx = 0, nn = 0, nt = 0, inst_cur = 0, rmask = 0;
         vec3 wo = V3(0.f, 0.f, 0.f), wd = V3(0.f, 0.f, 1.f), o = wo, d = wd, inv = V3(0.f, 0.f, 0.f);
         bool negx = false, negy = false, negz = false, in_blas = false;
         uint32_t oct4 = 0;
@@ -121,6 +180,7 @@ __global__ void __launch_bounds__(64) k_trace_instances(InstTraceArgs a) {
                         idx = next + rank;
                         const float4 r0 = a.rays[2 * (size_t)idx], r1 = a.rays[2 * (size_t)idx + 1];
                         wo = V3(r0.x, r0.y, r0.z); wd = V3(r1.x, r1.y, r1.z);
+                        if (MASK) rmask = __float_as_uint(r1.w) & 0xffu;
                         o = wo; d = wd;
                         best_t = r0.w; best_u = 0.f; best_v = 0.f; best_id = -1; best_inst = -1;
                         nn = 0; nt = 0; sp = 0; in_blas = false;
@@ -156,7 +216,9 @@ __global__ void __launch_bounds__(64) k_trace_instances(InstTraceArgs a) {
                     const uint4* np = node_rows(a.nodes, nidx);
                     const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3], n4 = np[4];
                     if (STATS) ++nn;
-                    const uint32_t hitmask = node8_intersect(n0, n1, n2, n3, n4, o, inv, negx, negy, negz, oct4, best_t);
+                    uint32_t keep = 0xffu;
+                    if constexpr (MASK) { if (nidx < a.n_tlas8) keep = child_keep(a.child_masks[nidx], rmask); }
+                    const uint32_t hitmask = node8_intersect(n0, n1, n2, n3, n4, o, inv, negx, negy, negz, oct4, best_t, keep);
                     cur.x = n1.x;
                     tg.x = n1.y;
                     cur.y = (hitmask & 0xff000000u) | (n0.w >> 24);
@@ -186,14 +248,15 @@ __global__ void __launch_bounds__(64) k_trace_instances(InstTraceArgs a) {
                     // an instance: into its object space (fp32, no fma, direction not renormalised: t is the same parameter in both spaces)
                     const float4* ip = a.inst + 4 * (size_t)ti;
                     const float4 w0 = ip[0], w1 = ip[1], w2 = ip[2], w3 = ip[3];
+                    const bool visible = !MASK || (__float_as_uint(w3.w) & rmask) != 0u;      // a hidden instance: skipped untransformed
                     vec3 oo = wo, od = wd;
-                    if (__float_as_uint(w3.z) == 0u) {
+                    if (visible && __float_as_uint(w3.z) == 0u) {
                         oo = V3(((w0.x * wo.x + w0.y * wo.y) + w0.z * wo.z) + w0.w, ((w1.x * wo.x + w1.y * wo.y) + w1.z * wo.z) + w1.w,
                                 ((w2.x * wo.x + w2.y * wo.y) + w2.z * wo.z) + w2.w);
                         od = V3((w0.x * wd.x + w0.y * wd.y) + w0.z * wd.z, (w1.x * wd.x + w1.y * wd.y) + w1.z * wd.z, (w2.x * wd.x + w2.y * wd.y) + w2.z * wd.z);
                     }
                     // an object origin that is not finite hits nothing in this instance (traverse()): the instance is skipped
-                    if (__builtin_isfinite(oo.x) && __builtin_isfinite(oo.y) && __builtin_isfinite(oo.z)) {
+                    if (visible && __builtin_isfinite(oo.x) && __builtin_isfinite(oo.y) && __builtin_isfinite(oo.z)) {
                         const int need = ((cur.y & 0xff000000u) ? 1 : 0) + (tg.y ? 1 : 0) + 1;
                         if (sp + need <= stack_entries) {
                             if (cur.y & 0xff000000u) { stk[sp * 64] = cur; ++sp; }
@@ -262,23 +325,37 @@ void launch_gather_instances(const float4* d_rec, const uint32_t* d_tri_order, c
 void launch_regather_instances(const float4* d_rec, uint32_t n, float4* d_inst, hipStream_t stream) {
     if (n) hipLaunchKernelGGL(k_regather_instances, grid_for(n), dim3(256), 0, stream, d_rec, n, d_inst);
 }
-void launch_trace_instances(const InstTraceArgs& a, int any, bool stats, uint32_t chunks, hipStream_t stream) {
+void launch_tlas_child_masks(const void* d_nodes, uint32_t n8, const float4* d_inst, uint32_t n, uint32_t* d_parent, uint32_t* d_leaf_of,
+                             uint2* d_child_masks, hipStream_t stream) {
+    if (!n8 || !n) return;
+    hipLaunchKernelGGL(k_tlas_links, grid_for(n8), dim3(256), 0, stream, static_cast<const uint4*>(d_nodes), n8, n, d_parent, d_leaf_of, d_child_masks);
+    hipLaunchKernelGGL(k_tlas_mask_up, grid_for(n), dim3(256), 0, stream, d_inst, n, n8, d_parent, d_leaf_of, reinterpret_cast<uint32_t*>(d_child_masks));
+}
+template <bool MASK>
+static void launch_trace_instances_t(const std::conditional_t<MASK, InstMaskTraceArgs, InstTraceArgs>& a, int any, bool stats, dim3 g, dim3 b, size_t lds,
+                                     hipStream_t stream) {
+    if (any) {
+        if (stats) hipLaunchKernelGGL((k_trace_instances<true, true, MASK>), g, b, lds, stream, a);
+        else       hipLaunchKernelGGL((k_trace_instances<true, false, MASK>), g, b, lds, stream, a);
+    } else {
+        if (stats) hipLaunchKernelGGL((k_trace_instances<false, true, MASK>), g, b, lds, stream, a);
+        else       hipLaunchKernelGGL((k_trace_instances<false, false, MASK>), g, b, lds, stream, a);
+    }
+}
+void launch_trace_instances(const InstMaskTraceArgs& a, int any, bool stats, bool mask, uint32_t chunks, hipStream_t stream) {
     const dim3 g(chunks * 16u), b(64);                      // sixteen single-wave workgroups per 1024-ray chunk: 64-ray pools (wave_id)
     const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
-    if (any) {
-        if (stats) hipLaunchKernelGGL((k_trace_instances<true, true>), g, b, lds, stream, a);
-        else       hipLaunchKernelGGL((k_trace_instances<true, false>), g, b, lds, stream, a);
-    } else {
-        if (stats) hipLaunchKernelGGL((k_trace_instances<false, true>), g, b, lds, stream, a);
-        else       hipLaunchKernelGGL((k_trace_instances<false, false>), g, b, lds, stream, a);
-    }
+    if (mask) launch_trace_instances_t<true>(a, any, stats, g, b, lds, stream);
+    else      launch_trace_instances_t<false>(static_cast<const InstTraceArgs&>(a), any, stats, g, b, lds, stream);
 }
 
 // crt_warmup: load this translation unit's code object on the current device (device_build.hpp)
 int warm_instance_kernels() {
     hipFuncAttributes at;
     hipError_t e;
-    if ((e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_trace_instances<false, false>))) != hipSuccess) return (int)e;
+    if ((e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_trace_instances<false, false, false>))) != hipSuccess) return (int)e;
+    if ((e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_trace_instances<false, false, true>))) != hipSuccess) return (int)e;
+    if ((e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_tlas_mask_up))) != hipSuccess) return (int)e;
     if ((e = hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_instance_prep))) != hipSuccess) return (int)e;
     return 0;
 }

@@ -21,13 +21,19 @@ struct InstTraceArgs {
     uint32_t n, n_instances, stack_entries, refill_min, tri_min;
     uint32_t* overflow;        // += 1 per dropped stack push (never happens for a depth create / set accepted)
 };
+// The masked walk's arguments (CRT_TRACE_INSTANCE_MASK).  A type of its own, so that the unmasked kernels keep their
+// argument block, and with it their code, exactly as before.
+struct InstMaskTraceArgs : InstTraceArgs {
+    const uint2* child_masks;  // 8 B per TLAS node8: byte i = OR of the masks of every instance under meta slot i
+    uint32_t n_tlas8;          // live TLAS node8s: node steps below this index are TLAS steps
+};
 
 struct InstPrepArgs {
     const uint32_t* in;        // crt_instance array, 16 words each
     uint32_t n, n_meshes;
     const float* mesh_box;     // 6 floats per mesh: the exact float box of its vertices
     const uint32_t* mesh_root; // BLAS root node of each mesh in the shared node array
-    float4* rec;               // 4 rows per instance, instance order
+    float4* rec;               // 4 rows per instance, instance order (row 3: BLAS root, instance index, identity flag, mask & 0xff)
     float* box;                // 6 floats per instance: world box
     float* w2o;                // 12 floats per instance: world_to_object
     uint32_t* flag;            // |= 1 matrix not finite / singular / inverse not finite, 2 mesh index out of range, 4 world box beyond 1e18
@@ -42,7 +48,12 @@ void launch_single_leaf(const float* d_box, crt_flatnode* d_flat, uint32_t* d_tr
 void launch_gather_instances(const float4* d_rec, const uint32_t* d_tri_order, const int32_t* d_tri_slots, uint32_t n, float4* d_out, hipStream_t stream);
 // in place, i < n: inst[i] = rec[inst[i] row 3 .y] (4 rows): the live TLAS leaf order kept, each record renewed (crt_instances_refit)
 void launch_regather_instances(const float4* d_rec, uint32_t n, float4* d_inst, hipStream_t stream);
-// `chunks`: 1024-ray chunks of the dense index space (k_trace's mapping), a multiple of 8
-void launch_trace_instances(const InstTraceArgs& a, int any, bool stats, uint32_t chunks, hipStream_t stream);
+// TLAS child masks of the live TLAS (n8 node8s from node 0 of d_nodes, n >= 1 instance records in leaf order): per node8 its 8 bytes
+// zeroed and the links (node << 3 | meta slot) of its children written, then each instance's mask ORed into every ancestor slot.
+// parent: n8 words, leaf_of: n words.  Enqueued only.
+void launch_tlas_child_masks(const void* d_nodes, uint32_t n8, const float4* d_inst, uint32_t n, uint32_t* d_parent, uint32_t* d_leaf_of,
+                             uint2* d_child_masks, hipStream_t stream);
+// `chunks`: 1024-ray chunks of the dense index space (k_trace's mapping), a multiple of 8; mask: CRT_TRACE_INSTANCE_MASK walk
+void launch_trace_instances(const InstMaskTraceArgs& a, int any, bool stats, bool mask, uint32_t chunks, hipStream_t stream);
 
 }  // namespace crt

@@ -31,9 +31,11 @@ __device__ __forceinline__ float ubyte_f(uint32_t x, int j) { return (float)((x 
 // operand selects by inline assembly (v_lshlrev_b32_sdwa: child_bits << bit_index in one instruction per child, the exponent bytes
 // likewise): 223 instructions per visit instead of 230 and SLOWER — 13,120 vs 13,660 Mray/s, 4 segments 5,357 vs 5,402, Cornell
 // 45,250 vs 44,640: an SDWA instruction costs more issue time than the two plain ones it replaces.
+// keep: bit i clear = meta slot i is culled whatever its box (the masked instanced walk's TLAS steps); every other caller
+// leaves the default 0xff, which folds away and leaves their code as it was.
 __device__ __forceinline__ uint32_t node8_intersect(const uint4 n0, const uint4 n1, const uint4 n2, const uint4 n3,
                                                     const uint4 n4, vec3 o, vec3 inv, bool negx, bool negy, bool negz,
-                                                    uint32_t oct4, float max_t) {
+                                                    uint32_t oct4, float max_t, uint32_t keep = 0xffu) {
     const vec3 p = V3(__uint_as_float(n0.x), __uint_as_float(n0.y), __uint_as_float(n0.z));
     const uint32_t e_imask = n0.w;
     const vec3 adj_inv = V3(__uint_as_float((e_imask & 0xffu) << 23) * inv.x,
@@ -64,7 +66,7 @@ __device__ __forceinline__ uint32_t node8_intersect(const uint4 n0, const uint4 
             const float tmaxz = __builtin_fmaf(ubyte_f(zmax, j), adj_inv.z, adj_o.z);
             const float tmin = __builtin_fmaxf(__builtin_fmaxf(tminx, tminy), __builtin_fmaxf(tminz, 0.0f));
             const float tmax = __builtin_fminf(__builtin_fminf(tmaxx, tmaxy), __builtin_fminf(tmaxz, max_t));
-            if (tmin <= tmax) {
+            if (tmin <= tmax && ((keep >> (4 * i + j)) & 1u)) {
                 const uint32_t child_bits = (child_bits4 >> (8 * j)) & 0xffu;
                 const uint32_t bit_index = (bit_index4 >> (8 * j)) & 0xffu;
                 hit_mask |= child_bits << bit_index;

@@ -1,25 +1,29 @@
 """Instanced scenes: one bottom-level CWBVH per mesh, built once on the device, under a top-level CWBVH over transformed instances that
 is rebuilt on the device at every `set` (include/crt.h crt_instances_*) or refitted in place by `refit`, which moves the
 instances and keeps the TLAS's topology (§13).  An updatable scene also moves the vertices of its meshes: a GPU refit of their BLASes and a
-TLAS rebuild per update.  Ray queries only: no frames."""
+TLAS rebuild per update.  Instances carry 8-bit visibility masks that a masked trace ANDs with each ray's (§14).  Ray
+queries only: no frames."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import (CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_INSTANCES_UPDATABLE, CRT_TRACE_CLOSEST, check, crt_blas_desc,
-                   crt_instances_info, lib)
+from ._lib import (CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_INSTANCES_UPDATABLE, CRT_TRACE_CLOSEST, CRT_TRACE_INSTANCE_MASK,
+                   check, crt_blas_desc, crt_instances_info, lib)
 from .host import _ptr
 from .scene import HIT_DT, RAY_DT, STATS_DT
 
-INSTANCE_DT = np.dtype([("object_to_world", "<f4", 12), ("mesh", "<u4"), ("reserved", "<u4", 3)])      # crt_instance, 64 B
+INSTANCE_DT = np.dtype([("object_to_world", "<f4", 12), ("mesh", "<u4"), ("mask", "<u4"), ("reserved", "<u4", 2)])      # crt_instance, 64 B
 
 
-def instances_array(matrices, meshes):
-    """crt_instance records from (n, 3, 4) or (n, 12) object_to_world matrices (row-major, world = A p + t) and n mesh indices."""
+def instances_array(matrices, meshes, masks=None):
+    """crt_instance records from (n, 3, 4) or (n, 12) object_to_world matrices (row-major, world = A p + t), n mesh indices and, optionally,
+    n visibility masks (bits 0..7; read by masked traces only).  Without masks the mask words stay 0."""
     m = np.asarray(matrices, np.float32).reshape(-1, 12)
     out = np.zeros(m.shape[0], INSTANCE_DT)
     out["object_to_world"] = m
     out["mesh"] = np.asarray(meshes, np.uint32).reshape(-1)
+    if masks is not None:
+        out["mask"] = np.asarray(masks, np.uint32).reshape(-1)
     return out
 
 
@@ -118,17 +122,24 @@ class InstancedScene:
         check(lib().crt_instances_last_update(self._h, C.byref(d), C.byref(w), C.byref(b)))
         return {"device_ms": d.value, "wall_ms": w.value, "state_bytes": b.value}
 
-    def trace(self, rays, mode=CRT_TRACE_CLOSEST, stats=False):
-        """-> (hits HIT_DT, instance ids int32 (-1 = miss)[, stats STATS_DT])"""
+    def trace(self, rays, mode=CRT_TRACE_CLOSEST, stats=False, ray_mask=None):
+        """-> (hits HIT_DT, instance ids int32 (-1 = miss)[, stats STATS_DT]).  ray_mask: None (masks ignored), or an int or a per-ray
+        uint8 array, written into a copy of the rays' pad words, and the trace sees only the instances whose mask meets it
+        (CRT_TRACE_INSTANCE_MASK)."""
         rays = np.ascontiguousarray(rays, dtype=RAY_DT)
         n = rays.shape[0]
+        if ray_mask is not None:
+            rays = rays.copy()
+            rays["pad"] = np.broadcast_to(np.asarray(ray_mask).astype(np.uint32) & 0xff, (n,))
+            mode = int(mode) | CRT_TRACE_INSTANCE_MASK
         hits, ids = np.empty(n, HIT_DT), np.empty(n, np.int32)
         st = np.zeros(n, STATS_DT) if stats else None
         check(lib().crt_instances_trace(self._h, _ptr(rays), n, _ptr(hits), _ptr(ids), int(mode), _ptr(st) if stats else None))
         return (hits, ids, st) if stats else (hits, ids)
 
     def trace_device(self, d_rays, n, d_hits, d_instance_ids=None, mode=CRT_TRACE_CLOSEST, d_stats=None, sync=True):
-        """device pointers (e.g. torch tensors' data_ptr()) of n crt_ray / crt_hit / int32 / crt_ray_stats records"""
+        """device pointers (e.g. torch tensors' data_ptr()) of n crt_ray / crt_hit / int32 / crt_ray_stats records; mode may carry
+        CRT_TRACE_INSTANCE_MASK (the rays' pad words then hold their masks)"""
         check(lib().crt_instances_trace_device(self._h, C.c_void_p(d_rays), int(n), C.c_void_p(d_hits),
                                                C.c_void_p(d_instance_ids) if d_instance_ids else None, int(mode),
                                                C.c_void_p(d_stats) if d_stats else None, 1 if sync else 0))
@@ -162,6 +173,11 @@ class InstancedScene:
     def blas_records(self):
         """(n, 12) float32: every BLAS record, (v0 | id) (e1 | slot) (e2 | w); the w words are int32 bits"""
         return self._read(5, np.float32, 12)
+
+    def tlas_child_masks(self):
+        """(n_tlas8, 8) uint8: per TLAS node8, per meta slot, the OR of the masks of every instance under that child (recomputed first if
+        stale)"""
+        return self._read(6, np.uint8, 8)
 
     def info(self):
         st = crt_instances_info()

@@ -416,9 +416,10 @@ int crt_has_experiments(void);
  * A mesh as a bottom-level structure: positions and triangles in SOURCE order (a triangle's id is its index); only crt_triangle.v[0..2]
  * are read. */
 typedef struct crt_blas_desc { const float* vertices; size_t n_vertices; const crt_triangle* triangles; size_t n_triangles; } crt_blas_desc;
-/* One instance: world = A * p + t, object_to_world row-major 3x4 (m[r*4 + c], column 3 = t); mesh = index into the create's meshes.
- * 64 bytes. */
-typedef struct crt_instance { float object_to_world[12]; uint32_t mesh; uint32_t reserved[3]; } crt_instance;
+/* One instance: world = A * p + t, object_to_world row-major 3x4 (m[r*4 + c], column 3 = t); mesh = index into the create's meshes;
+ * mask bits 0..7 = the instance's visibility mask, read by CRT_TRACE_INSTANCE_MASK traces only (bits 8..31 and reserved are ignored).
+ * 64 bytes, mask at offset 52. */
+typedef struct crt_instance { float object_to_world[12]; uint32_t mesh; uint32_t mask; uint32_t reserved[2]; } crt_instance;
 typedef struct crt_instances crt_instances;
 typedef struct crt_instances_info {
     uint32_t n_meshes, n_instances, capacity;
@@ -466,7 +467,12 @@ int crt_instances_set_device(crt_instances* s, const void* d_instances, uint32_t
  * device form's sync is accepted for symmetry.  crt_instances_info's set_device_ms / set_wall_ms then describe the refit. */
 int crt_instances_refit(crt_instances* s, const crt_instance* instances, uint32_t n_instances);
 int crt_instances_refit_device(crt_instances* s, const void* d_instances, uint32_t n_instances, int sync);
-/* Closest- or any-hit queries (mode CRT_TRACE_CLOSEST or CRT_TRACE_ANY; anything else is CRT_ERR_INVALID) over host rays.
+/* crt_instances_trace's mode bit (instanced traces only; crt_trace refuses it): instance visibility masks (as DXR /
+ * Vulkan RT / OptiX).  The low 8 bits of a ray's pad word are its mask; an instance is visible to the ray iff (mask & ray mask) != 0,
+ * so an instance of mask 0 is never hit by a masked ray and a ray of mask 0 hits nothing. */
+enum { CRT_TRACE_INSTANCE_MASK = 8 };
+/* Closest- or any-hit queries (mode CRT_TRACE_CLOSEST or CRT_TRACE_ANY, optionally | CRT_TRACE_INSTANCE_MASK; anything else is
+ * CRT_ERR_INVALID) over host rays.
  * hits[i].tri = the triangle id within the mesh of instance_of_hit[i] (-1 and -1 on a miss); instance_of_hit and stats may be NULL.
  * Numerical contract (tests/test_instances.py holds the kernel to it bit for bit):
  *   - world_to_object (crt_instance_inverse) is computed in double and rounded once to float: the adjugate of A divided by det(A),
@@ -486,7 +492,14 @@ int crt_instances_refit_device(crt_instances* s, const void* d_instances, uint32
  *     translation.  EXCEPTION: beyond that bound (a ray from far away relative to B, e.g. a small instance near the origin seen from
  *     ~1000x its size, or a badly conditioned A) a grazing hit within a few ulps of the box's surface can be culled by the TLAS, and
  *     the closest / any hit above then misses it.
- *   - stats: nodes = TLAS + BLAS node8 steps, tris = triangle tests, each clamped at 65535. */
+ *   - stats: nodes = TLAS + BLAS node8 steps, tris = triangle tests, each clamped at 65535.
+ * With CRT_TRACE_INSTANCE_MASK the rules above hold over the instances visible to each ray only: the closest hit is the minimum of
+ * (t, instance index, triangle id) over the visible instances, an any hit reports some visible instance, and the grazing-margin exception
+ * applies unchanged.  A TLAS child whose instances are all hidden from the ray is not entered, and a hidden instance is skipped before
+ * its ray is transformed: stats count only the steps actually taken.  Without the bit, masks are ignored and the results, instance ids
+ * and stats are those of the same call before masks existed.  Sets, refits (e.g. the same matrices with new masks: showing and hiding
+ * instances without a TLAS rebuild) and updates (which keep the live masks) all carry them; the first masked trace after any of them
+ * first recomputes the TLAS's per-child masks on the handle's stream (two small kernels, no host wait). */
 int crt_instances_trace(crt_instances* s, const crt_ray* rays, size_t n, crt_hit* hits, int32_t* instance_of_hit, int mode, crt_ray_stats* stats);
 /* the same with DEVICE pointers; asynchronous on the handle's stream unless sync != 0 */
 int crt_instances_trace_device(crt_instances* s, const void* d_rays, size_t n, void* d_hits, void* d_instance_of_hit, int mode, void* d_stats, int sync);
@@ -512,8 +525,9 @@ int crt_instances_update_meshes_device(crt_instances* s, const uint32_t* mesh_id
  * (filled for an updatable handle even then; 0 otherwise).  Any pointer may be NULL. */
 int crt_instances_last_update(crt_instances* s, float* device_ms, float* wall_ms, uint64_t* state_bytes);
 /* test hook: which 0 = world_to_object (12 floats per instance, instance order), 1 = world boxes (6 floats: lo, hi), 2 = TLAS node8s
- * (80 B), 3 = instance records in TLAS leaf order (64 B: world_to_object rows, then BLAS root node, instance index, identity flag, 0),
- * 4 = every BLAS node8 (80 B; the packed region after the TLAS region, bases rebased), 5 = every BLAS record (48 B).
+ * (80 B), 3 = instance records in TLAS leaf order (64 B: world_to_object rows, then BLAS root node, instance index, identity flag, mask & 0xff),
+ * 4 = every BLAS node8 (80 B; the packed region after the TLAS region, bases rebased), 5 = every BLAS record (48 B), 6 = the TLAS child
+ * masks (8 B per TLAS node8, byte i = the OR of the masks & 0xff of every instance under meta slot i; recomputed first if stale).
  * dst may be NULL to query the count. */
 int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_bytes, size_t* n_out);
 int crt_instances_destroy(crt_instances* s);
