@@ -484,7 +484,9 @@ enum { CRT_TRACE_INSTANCE_MASK = 8 };
  *   - inside a mesh the crt_trace contract holds unchanged (CWBVH walk, Moller-Trumbore, clamped slab directions); an origin that is not
  *     finite, in world or in object space, hits nothing there.
  *   - closest hit = the minimum of (t, instance index, triangle id), lexicographically, over all hits with 0 <= t < tmax: independent of
- *     the order the TLAS visits instances.  Any hit: tri = 0 / -1 as crt_trace, instance_of_hit = SOME instance with a hit in [0, tmax).
+ *     the order the TLAS visits instances.  EXCEPTION (equal t only): once a hit at t is held, a BLAS box whose computed entry distance
+ *     rounds above t is culled, so an equal-t hit inside it (coincident geometry in two instances) is not compared and the instance
+ *     found first keeps the hit.  Any hit: tri = 0 / -1 as crt_trace, instance_of_hit = SOME instance with a hit in [0, tmax).
  *   - world boxes: the 8 corners of the mesh's float vertex box through object_to_world in double, widened by 2^-16 of the largest
  *     absolute coordinate and rounded outward (crt_instance_world_box; DESIGN.md §11 sizes the margin).  The TLAS tests the WORLD ray
  *     against these boxes while the hit is found on the rounded OBJECT ray, so the margin must cover that rounding.  It does when

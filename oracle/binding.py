@@ -37,6 +37,12 @@ class orc_scene(C.Structure):
                 ("albedo_textures", C.c_void_p), ("tex_width", C.c_int32), ("tex_height", C.c_int32), ("n_textures", C.c_int32)]
 
 
+class orc_instances(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("inst", C.c_void_p), ("tris", C.c_void_p), ("child_masks", C.c_void_p),
+                ("n_nodes", C.c_size_t), ("n_tris", C.c_size_t), ("n_instances", C.c_uint32), ("n_tlas8", C.c_uint32),
+                ("stack_entries", C.c_uint32)]
+
+
 def build(force=False):
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < os.path.getmtime(os.path.join(_HERE, "oracle.c")):
         subprocess.check_call(["make", "-C", _HERE, "-s"])
@@ -66,6 +72,9 @@ def lib():
         l.orc_render_rows.argtypes = [C.POINTER(orc_scene), C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.c_int]
         l.orc_resolve.restype = None
         l.orc_resolve.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]
+        l.orc_trace_instances.restype = C.c_int
+        l.orc_trace_instances.argtypes = [C.POINTER(orc_instances), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int]
         l.orc_hardware_threads.restype = C.c_int
         fp = C.POINTER(C.c_float)
         l.orc_disney_eval_test.restype = None
@@ -153,6 +162,80 @@ class Oracle:
         cnt = (C.c_uint64 * 4)()
         lib().orc_render_rows(C.byref(self.s), accel, tie, float(np.float32(rx)), float(np.float32(ry)), _p(sum_buf), cnt, int(y0), int(y1))
         return [int(x) for x in cnt]
+
+
+INSTANCE_MASK = 8          # == CRT_TRACE_INSTANCE_MASK
+
+
+def tlas_child_masks(tlas_nodes, instance_records):
+    """(n_tlas8, 8) uint8: per TLAS node8 and meta slot, the OR of the masks (instance record row 3 .w & 0xff) of every instance below
+    that slot.  A plain recursive OR over the tree; byte i of a node is its i-th meta slot."""
+    nodes = np.ascontiguousarray(tlas_nodes, np.uint8).reshape(-1, 80)
+    masks = np.ascontiguousarray(instance_records, np.float32).reshape(-1, 16)[:, 15].view(np.uint32) & 0xff
+    n8 = nodes.shape[0]
+    out = np.zeros((n8, 8), np.uint8)
+    done = np.zeros(n8, bool)
+
+    def fill(i):
+        if done[i]:
+            return
+        nd = nodes[i]
+        child_base = int(nd[16:20].view(np.uint32)[0])
+        inst_base = int(nd[20:24].view(np.uint32)[0])
+        imask = int(nd[15])
+        for slot in range(8):
+            meta = int(nd[24 + slot])
+            if (imask >> slot) & 1:
+                c = child_base + bin(imask & ((1 << slot) - 1)).count("1")
+                assert c < n8, "inner child outside the TLAS"
+                fill(c)
+                out[i, slot] = np.bitwise_or.reduce(out[c])
+            elif meta:
+                first, cnt = inst_base + (meta & 31), bin(meta >> 5).count("1")
+                m = 0
+                for k in range(first, first + cnt):
+                    m |= int(masks[k])
+                out[i, slot] = m
+        done[i] = True
+
+    if n8 and masks.shape[0]:
+        fill(0)
+    return out
+
+
+def trace_instances(tlas_nodes, instance_records, blas_nodes, blas_records, rays, tlas_region, stack_entries, mode=CLOSEST,
+                    child_masks=None, threads=1):
+    """CPU two-level walk (orc_trace_instances) over an instanced scene given as crt_instances_debug_read returns it: TLAS node8s (read 2),
+    instance records (read 3), BLAS node8s with rebased bases (read 4), BLAS records (read 5).  The packed node array is rebuilt with the
+    BLASes at node `tlas_region` (the TLAS region's size in node8s), where their rebased bases point.  mode: CLOSEST or ANY, | INSTANCE_MASK
+    for a masked walk (the rays' pad words hold their masks; child_masks default to tlas_child_masks of the records).
+    -> (hits HIT_DT, instance ids int32, stats STATS_DT, max stack depth uint32, refused pushes uint32) per ray."""
+    tlas = np.ascontiguousarray(tlas_nodes, np.uint8).reshape(-1, 80)
+    blas = np.ascontiguousarray(blas_nodes, np.uint8).reshape(-1, 80)
+    inst = np.ascontiguousarray(instance_records, np.float32).reshape(-1, 16)
+    recs = np.ascontiguousarray(blas_records, np.float32).reshape(-1, 12)
+    assert tlas.shape[0] <= tlas_region, (tlas.shape[0], tlas_region)
+    nodes = np.zeros((tlas_region + blas.shape[0], 80), np.uint8)
+    nodes[:tlas.shape[0]] = tlas
+    nodes[tlas_region:] = blas
+    if mode & INSTANCE_MASK and child_masks is None:
+        child_masks = tlas_child_masks(tlas, inst)
+    cm = None if child_masks is None else np.ascontiguousarray(child_masks, np.uint8).reshape(-1, 8)
+    if cm is not None:
+        assert cm.shape[0] == tlas.shape[0]
+    s = orc_instances()
+    s.nodes, s.inst, s.tris, s.child_masks = _p(nodes), _p(inst), _p(recs), _p(cm)
+    s.n_nodes, s.n_tris, s.n_instances, s.n_tlas8 = nodes.shape[0], recs.shape[0], inst.shape[0], tlas.shape[0]
+    s.stack_entries = int(stack_entries)
+    rays = np.ascontiguousarray(rays, dtype=RAY_DT)
+    n = rays.shape[0]
+    hits, ids = np.empty(n, HIT_DT), np.empty(n, np.int32)
+    st, depth, refused = np.zeros(n, STATS_DT), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    if n:
+        rc = lib().orc_trace_instances(C.byref(s), int(mode), _p(rays), n, _p(hits), _p(ids), _p(st), _p(depth), _p(refused),
+                                       max(1, min(int(threads), 16)))
+        assert rc == 0, f"orc_trace_instances: {'bad argument' if rc < 0 else 'an index outside the arrays'}"
+    return hits, ids, st, depth, refused
 
 
 def resolve(sum_buf, inv_count):

@@ -171,13 +171,16 @@ typedef struct { uint32_t nodes, tris; } cnt_t;
 static inline int orig_id(const orc_scene* s, int slot) { return s->tri_orig_ids ? s->tri_orig_ids[slot] : slot; }
 
 /* path_trace.fs:322-374 (exact operation order). */
+static inline int mt_edges(v3 v0, v3 v1, v3 v2, v3 o, v3 d, float* u, float* v, float* t);
 static inline int mt_test(const orc_scene* s, v3 o, v3 d, int slot, float* u, float* v, float* t) {
     const int32_t* ti = s->triangles + 12 * (size_t)slot;
     v3 v0 = ld3(s->vertices + 3 * (size_t)ti[0]);
     v3 v1 = ld3(s->vertices + 3 * (size_t)ti[1]);
     v3 v2 = ld3(s->vertices + 3 * (size_t)ti[2]);
-    v1 = sub(v1, v0);
-    v2 = sub(v2, v0);
+    return mt_edges(v0, sub(v1, v0), sub(v2, v0), o, d, u, v, t);
+}
+/* the same test on v0 and the edges v1 = v1 - v0, v2 = v2 - v0 (an intersection record's rows) */
+static inline int mt_edges(v3 v0, v3 v1, v3 v2, v3 o, v3 d, float* u, float* v, float* t) {
     v3 pv = cross3(d, v2);
     v3 tv = sub(o, v0);
     v3 qv = cross3(tv, v1);
@@ -337,8 +340,9 @@ static inline uint32_t oct_inv4(v3 d) {
 static inline uint32_t sign_extend_s8x4(uint32_t x) { return ((x >> 7) & 0x01010101u) * 0xffu; }
 
 /* cwbvh.fs:376-446 with: far plane = min(min()), tmin clamped to 0, tmax clamped to max_t,
- * child hit iff tmin <= tmax.  t = fmaf(q, 2^e*invdir, (p-o)*invdir). */
-static uint32_t node8_intersect(const uint8_t* n, v3 o, int negx, int negy, int negz, v3 inv, uint32_t oct4, float max_t) {
+ * child hit iff tmin <= tmax.  t = fmaf(q, 2^e*invdir, (p-o)*invdir).
+ * keep: bit i clear = meta slot i is culled whatever its box (the masked instanced walk's TLAS steps); every other caller passes 0xff. */
+static uint32_t node8_intersect(const uint8_t* n, v3 o, int negx, int negy, int negz, v3 inv, uint32_t oct4, float max_t, uint32_t keep) {
     v3 p = V(ld_f32(n), ld_f32(n + 4), ld_f32(n + 8));
     uint32_t e_imask = ld_u32(n + 12);
     v3 adj_inv = V(u2f((e_imask & 0xffu) << 23) * inv.x, u2f(((e_imask >> 8) & 0xffu) << 23) * inv.y,
@@ -366,7 +370,7 @@ static uint32_t node8_intersect(const uint8_t* n, v3 o, int negx, int negy, int 
             float tmaxz = fmaf((float)((zmax >> (8 * j)) & 0xffu), adj_inv.z, adj_o.z);
             float tmin = fmaxf(fmaxf(tminx, tminy), fmaxf(tminz, 0.0f));
             float tmax = fminf(fminf(tmaxx, tmaxy), fminf(tmaxz, max_t));
-            if (tmin <= tmax) {
+            if (tmin <= tmax && ((keep >> (4 * i + j)) & 1u)) {
                 uint32_t child_bits = (child_bits4 >> (8 * j)) & 0xffu;
                 uint32_t bit_index = (bit_index4 >> (8 * j)) & 0xffu;
                 hit_mask |= child_bits << bit_index;
@@ -416,7 +420,7 @@ static int bvh8_walk(const orc_scene* s, v3 o, v3 d, float tmax_in, int any, rec
             uint32_t node_index = base + rel;
             const uint8_t* n = s->bvh8 + 80 * (size_t)node_index;
             c->nodes++;
-            uint32_t hitmask = node8_intersect(n, o, negx, negy, negz, inv, oct4, max_t);
+            uint32_t hitmask = node8_intersect(n, o, negx, negy, negz, inv, oct4, max_t, 0xffu);
             uint32_t imask = n[15];
             cur_x = ld_u32(n + 16);
             tri_x = ld_u32(n + 20);
@@ -444,6 +448,183 @@ static int bvh8_walk(const orc_scene* s, v3 o, v3 d, float tmax_in, int any, rec
         }
     }
     return rec ? rec->slot >= 0 : 0;
+}
+
+/* --------------------------------------------------------- instanced scenes -- */
+
+/* The two-level walk of crt_instances_trace (include/crt.h), one ray at a time.  What the kernel does per lane:
+ * a step is a leaf step while the leaf group (tg) has bits left, else a node step while the node group (cur) has inner bits left; then,
+ * with neither left, a pop.  A TLAS leaf "triangle" is an instance: entering it pushes the rest of the node group, the rest of the leaf
+ * group and a return marker, in that order, and only if all of them fit in stack_entries; popping the marker restores the world ray.
+ * The kernel's wave-level vote between node and leaf steps decides only WHEN a lane steps, never which step it takes, so hits, the
+ * reported instance and the counts of each ray are those of this scalar walk. */
+#define ORC_INST_STACK 64
+
+typedef struct { uint32_t x, y; } u2;
+
+static inline void walk_setup(v3 d, v3* inv, int* negx, int* negy, int* negz, uint32_t* oct4) {
+    const v3 dc = V(clamp_dir(d.x), clamp_dir(d.y), clamp_dir(d.z));
+    *negx = dc.x < 0.0f; *negy = dc.y < 0.0f; *negz = dc.z < 0.0f;
+    *oct4 = oct_inv4(dc);
+    *inv = V(1.0f / dc.x, 1.0f / dc.y, 1.0f / dc.z);
+}
+
+static inline int finite3(v3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
+
+/* keep mask of TLAS node `node` for ray mask rmask: bit i set iff the OR of the masks under meta slot i meets rmask */
+static inline uint32_t slot_keep(const uint8_t* cm, uint32_t rmask) {
+    uint32_t keep = 0;
+    for (int i = 0; i < 8; ++i)
+        if (cm[i] & rmask) keep |= 1u << i;
+    return keep;
+}
+
+/* returns 0, or 1 when the arrays index outside themselves (a malformed scene: the walk stops there) */
+static int inst_walk(const orc_instances* s, int any, int masked, const orc_ray* r, orc_hit* hit, int32_t* inst_of_hit, cnt_t* c,
+                     uint32_t* max_depth, uint32_t* refused) {
+    u2 stk[ORC_INST_STACK];
+    const int stack_entries = (int)s->stack_entries;
+    const v3 wo = ld3(r->o), wd = ld3(r->d);
+    const uint32_t rmask = masked ? (r->pad & 0xffu) : 0u;
+    v3 o = wo, d = wd, inv;
+    int negx, negy, negz, in_blas = 0, sp = 0, bad = 0;
+    uint32_t oct4, inst_cur = 0;
+    float best_t = r->tmax, best_u = 0.f, best_v = 0.f;
+    int best_id = -1, best_inst = -1;
+    walk_setup(d, &inv, &negx, &negy, &negz, &oct4);
+    /* a non-finite origin hits nothing; no instance: every ray misses */
+    u2 cur = {0u, (finite3(wo) && s->n_instances) ? 0x80000000u : 0u}, tg = {0u, 0u};
+    *max_depth = 0; *refused = 0;
+    for (;;) {
+        if (tg.y) {
+            const int b = msb(tg.y);
+            tg.y &= ~(1u << b);
+            const uint32_t ti = tg.x + (uint32_t)b;
+            if (in_blas) {
+                if (ti >= s->n_tris) { bad = 1; break; }
+                const float* rec = s->tris + 12 * (size_t)ti;
+                float u, v, t;
+                c->tris++;
+                if (mt_edges(ld3(rec), ld3(rec + 4), ld3(rec + 8), o, d, &u, &v, &t)) {
+                    int32_t id;
+                    memcpy(&id, rec + 3, 4);
+                    if (any) {
+                        if (t < best_t) { best_inst = (int)inst_cur; break; }
+                    } else {
+                        /* the lexicographic minimum of (t, instance, id); t < tmax for the first hit */
+                        int better = t < best_t;
+                        if (t == best_t && best_inst >= 0)
+                            better = (int)inst_cur < best_inst || ((int)inst_cur == best_inst && id < best_id);
+                        if (better) { best_t = t; best_u = u; best_v = v; best_id = id; best_inst = (int)inst_cur; }
+                    }
+                }
+            } else {
+                if (ti >= s->n_instances) { bad = 1; break; }
+                const float* w = s->inst + 16 * (size_t)ti;
+                uint32_t w3[4];
+                memcpy(w3, w + 12, 16);             /* BLAS root, instance index, identity flag, mask */
+                const int visible = !masked || (w3[3] & rmask) != 0u;
+                if (visible) {
+                    v3 oo = wo, od = wd;
+                    if (w3[2] == 0u) {
+                        oo = V(((w[0] * wo.x + w[1] * wo.y) + w[2] * wo.z) + w[3], ((w[4] * wo.x + w[5] * wo.y) + w[6] * wo.z) + w[7],
+                               ((w[8] * wo.x + w[9] * wo.y) + w[10] * wo.z) + w[11]);
+                        od = V((w[0] * wd.x + w[1] * wd.y) + w[2] * wd.z, (w[4] * wd.x + w[5] * wd.y) + w[6] * wd.z,
+                               (w[8] * wd.x + w[9] * wd.y) + w[10] * wd.z);
+                    }
+                    if (finite3(oo)) {
+                        const int need = ((cur.y & 0xff000000u) ? 1 : 0) + (tg.y ? 1 : 0) + 1;
+                        if (sp + need <= stack_entries) {
+                            if (cur.y & 0xff000000u) stk[sp++] = cur;
+                            if (tg.y) stk[sp++] = tg;
+                            stk[sp].x = 0u; stk[sp].y = 0u;         /* return marker */
+                            ++sp;
+                            if ((uint32_t)sp > *max_depth) *max_depth = (uint32_t)sp;
+                            o = oo; d = od;
+                            walk_setup(d, &inv, &negx, &negy, &negz, &oct4);
+                            in_blas = 1;
+                            inst_cur = w3[1];
+                            cur.x = w3[0]; cur.y = 0x80000000u;
+                            tg.x = 0u; tg.y = 0u;
+                        } else {
+                            ++*refused;
+                        }
+                    }
+                }
+            }
+        } else if (cur.y & 0xff000000u) {
+            const uint32_t hits_imask = cur.y;
+            const int off = msb(hits_imask);
+            const uint32_t nbase = cur.x;
+            cur.y &= ~(1u << off);
+            if (cur.y & 0xff000000u) {
+                if (sp < stack_entries) {
+                    stk[sp++] = cur;
+                    if ((uint32_t)sp > *max_depth) *max_depth = (uint32_t)sp;
+                } else {
+                    ++*refused;
+                }
+            }
+            const uint32_t slot = (uint32_t)(off - 24) ^ (oct4 & 0xffu);
+            const uint32_t nidx = nbase + (uint32_t)__builtin_popcount(hits_imask & ~(0xffffffffu << slot));
+            if (nidx >= s->n_nodes) { bad = 1; break; }
+            const uint8_t* n = s->nodes + 80 * (size_t)nidx;
+            c->nodes++;
+            uint32_t keep = 0xffu;
+            if (masked && nidx < s->n_tlas8) keep = slot_keep(s->child_masks + 8 * (size_t)nidx, rmask);
+            const uint32_t hitmask = node8_intersect(n, o, negx, negy, negz, inv, oct4, best_t, keep);
+            cur.x = ld_u32(n + 16);
+            tg.x = ld_u32(n + 20);
+            cur.y = (hitmask & 0xff000000u) | n[15];
+            tg.y = hitmask & 0x00ffffffu;
+        }
+        if (!tg.y && !(cur.y & 0xff000000u)) {
+            int done = 0;
+            for (;;) {
+                if (sp == 0) { done = 1; break; }
+                const u2 e = stk[--sp];
+                if (e.y == 0u) {                            /* return marker: back to the world ray */
+                    o = wo; d = wd;
+                    walk_setup(d, &inv, &negx, &negy, &negz, &oct4);
+                    in_blas = 0;
+                    continue;
+                }
+                if (e.y & 0xff000000u) cur = e;
+                else { tg = e; cur.x = 0u; cur.y = 0u; }
+                break;
+            }
+            if (done) break;
+        }
+    }
+    const int h = best_inst >= 0;
+    hit->t = any ? 0.f : (h ? best_t : 0.f);
+    hit->u = any ? 0.f : best_u;
+    hit->v = any ? 0.f : best_v;
+    hit->tri = any ? (h ? 0 : -1) : (h ? best_id : -1);
+    *inst_of_hit = h ? best_inst : -1;
+    return bad;
+}
+
+typedef struct {
+    const orc_instances* s; int any, masked;
+    const orc_ray* rays; orc_hit* hits; int32_t* inst; orc_ray_stats* stats; uint32_t* depth; uint32_t* refused;
+    size_t i0, i1; int bad;
+} inst_job;
+
+static void* inst_worker(void* arg) {
+    inst_job* j = (inst_job*)arg;
+    for (size_t i = j->i0; i < j->i1; ++i) {
+        cnt_t c = {0, 0};
+        uint32_t depth, refused;
+        j->bad |= inst_walk(j->s, j->any, j->masked, j->rays + i, j->hits + i, j->inst + i, &c, &depth, &refused);
+        if (j->stats) {
+            j->stats[i].nodes = (uint16_t)(c.nodes > 65535 ? 65535 : c.nodes);
+            j->stats[i].tris = (uint16_t)(c.tris > 65535 ? 65535 : c.tris);
+        }
+        if (j->depth) j->depth[i] = depth;
+        if (j->refused) j->refused[i] = refused;
+    }
+    return NULL;
 }
 
 /* --------------------------------------------------------- dispatch helpers -- */
@@ -505,6 +686,35 @@ void orc_trace(const orc_scene* s, int accel, int mode, int tie, const orc_ray* 
     if (n_threads == 1) { trace_worker(&jobs[0]); return; }
     for (int t = 0; t < n_threads; ++t) pthread_create(&th[t], NULL, trace_worker, &jobs[t]);
     for (int t = 0; t < n_threads; ++t) pthread_join(th[t], NULL);
+}
+
+int orc_trace_instances(const orc_instances* s, int mode, const orc_ray* rays, size_t n, orc_hit* hits, int32_t* instance_of_hit,
+                        orc_ray_stats* stats, uint32_t* max_depth, uint32_t* refused, int n_threads) {
+    const int base = mode & ~ORC_INSTANCE_MASK;
+    if (base != ORC_CLOSEST && base != ORC_ANY) return -1;
+    if (s->stack_entries > ORC_INST_STACK) return -1;
+    if ((mode & ORC_INSTANCE_MASK) && s->n_tlas8 && !s->child_masks) return -1;
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 64) n_threads = 64;
+    inst_job jobs[64];
+    pthread_t th[64];
+    size_t chunk = (n + (size_t)n_threads - 1) / (size_t)n_threads;
+    for (int t = 0; t < n_threads; ++t) {
+        size_t a = chunk * (size_t)t, b = a + chunk;
+        if (a > n) a = n;
+        if (b > n) b = n;
+        inst_job j = {s, base == ORC_ANY, (mode & ORC_INSTANCE_MASK) != 0, rays, hits, instance_of_hit, stats, max_depth, refused, a, b, 0};
+        jobs[t] = j;
+    }
+    if (n_threads == 1) {
+        inst_worker(&jobs[0]);
+    } else {
+        for (int t = 0; t < n_threads; ++t) pthread_create(&th[t], NULL, inst_worker, &jobs[t]);
+        for (int t = 0; t < n_threads; ++t) pthread_join(th[t], NULL);
+    }
+    int bad = 0;
+    for (int t = 0; t < n_threads; ++t) bad |= jobs[t].bad;
+    return bad ? 1 : 0;
 }
 
 /* ---------------------------------------------------------- ray generation -- */

@@ -59,6 +59,24 @@ float    orc_randf2(uint32_t* state);                          /* Rnd.h:36-40 */
 void orc_trace(const orc_scene* s, int accel, int mode, int tie, const orc_ray* rays, size_t n,
                orc_hit* hits, orc_ray_stats* stats, int n_threads);
 
+/* Instanced scenes (include/crt.h crt_instances_*): the arrays the two-level walk reads, as crt_instances_debug_read returns them,
+ * with the node8s packed as on the device: TLAS from node 0, the BLASes behind the TLAS region, their bases rebased. */
+typedef struct orc_instances {
+    const uint8_t* nodes;           /* 80 bytes per node8, n_nodes of them                                   */
+    const float*   inst;            /* 16 floats per instance record, TLAS leaf order (debug read 3)         */
+    const float*   tris;            /* 12 floats per BLAS record: (v0 | id) (e1 | slot) (e2 | w)              */
+    const uint8_t* child_masks;     /* 8 bytes per TLAS node8: OR of the masks under each meta slot; masked walks only */
+    size_t   n_nodes, n_tris;
+    uint32_t n_instances, n_tlas8, stack_entries;
+} orc_instances;
+enum { ORC_INSTANCE_MASK = 8 };     /* == CRT_TRACE_INSTANCE_MASK */
+
+/* mode = ORC_CLOSEST or ORC_ANY, optionally | ORC_INSTANCE_MASK (the low 8 bits of a ray's pad word are its mask).
+ * instance_of_hit: -1 on a miss.  stats, max_depth (the most stack entries the ray held) and refused (pushes and instance entries
+ * that did not fit in stack_entries) may be NULL.  Returns 0; 1 if the arrays index outside themselves; -1 for a bad argument. */
+int orc_trace_instances(const orc_instances* s, int mode, const orc_ray* rays, size_t n, orc_hit* hits, int32_t* instance_of_hit,
+                        orc_ray_stats* stats, uint32_t* max_depth, uint32_t* refused, int n_threads);
+
 /* primary rays of one frame (path_trace.fs:1026-1047); jitter=0 gives pixel centres */
 void orc_primary_rays(const orc_scene* s, float rx, float ry, int jitter, orc_ray* out);
 
