@@ -1,18 +1,24 @@
 #!/usr/bin/env python3
 """bench.py — Mray/s of the HIP ray/BVH-traversal hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
                     [--workload auto|cornell|mesh1m|meshN] [--depth D] [--resolution WxH] [--spp S] [--scaling strong|weak]
                     [--dump-outputs DIR]
 
 One step = one pass of the hot path over one batch of the workload: `spp_per_step` samples per pixel of this rank's
 tiles (ray generation -> CWBVH closest hit -> shading / NEE -> CWBVH any hit -> accumulate), everything resident in HBM.
 
+A plain run does what the headline figure needs: it builds the workload, counts one step's visits, settles and warms up, times
+the K steps, writes --dump-outputs when asked and prints the line (its roofline from those counters, the timed launches and the
+committed counter passes).  What takes runs of its own comes with --full only: the rocprofv3 --pmc passes, the event-timed
+single-sample tail (roofline.frame_device_ms), the spread of steps re-rendered one by one, the oracle row check, the CPU baseline,
+the extras and, at N > 1, the frame rendered by rank 0 alone.
+
 Workloads (BASELINE.json `configs`, made concrete in SURVEY.md §8d):
   N = 1, --workload auto (the default):
     value / roofline / cpu_baseline  = configs[2]: the 1,004,672-triangle mesh, CWBVH, 4 spp per step, 1920x1080, primary + shadow —
                                        the workload BASELINE.json's targets (>= 1 Gray/s, >= 50 % roofline) are quoted on;
-    "extras" (compact: value, ms_per_step, launch_ms, frac, algorithmic_gbps, traffic):
+    --full adds "extras" (compact: value, ms_per_step, launch_ms, frac, algorithmic_gbps, traffic):
       "cornell"            configs[1]: Cornell box, CWBVH, 1 spp primary + shadow, 1920x1080 (one launch per frame);
       "gpu_tree"           configs[2] over a tree built on the GPU (binned SAH, everything assembled in HBM by crt_scene_create);
       "d2"                 configs[2]'s mesh with 2 path segments: the other reading of the metric's "primary + 1 bounce" (the headline is
@@ -24,7 +30,8 @@ Workloads (BASELINE.json `configs`, made concrete in SURVEY.md §8d):
                            Cache, so its traffic figure is HBM traffic (1 segment and 4 segments).
   N > 1, --workload auto: configs[4]: ONE fixed 3840x2160 frame of the 1 M-triangle mesh, 4 spp per step, its 16x16 tiles dealt
     to the N ranks (strong scaling, no data-path collective), one RCCL gather of the per-tile radiance to rank 0 inside the timed
-    region; the line carries gather_ms, per-rank device time, the same frame rendered by rank 0 alone and the efficiency against it.
+    region; the line carries gather_ms, per-rank device time and, with --full, the same frame rendered by rank 0 alone and the
+    efficiency against it.
     `--scaling weak` keeps the round-1 behaviour (the frame grows with N, ~1920x1080 pixels per rank).
   An explicit --workload measures just that one (used by the profiling scripts).
 
@@ -40,13 +47,13 @@ Prints ONE JSON line (< 8 KB) on rank 0 with the driver's keys plus
       straight-line blocks counted in the ISA — / its mean HIP-event duration (blocks that render tile shards side by side on several
       streams — `config.streams` > 1 — take the step's wall time / its launches per shard instead: the time a segment of the WHOLE
       frame takes); peak = 1024 SIMDs x 2.4 GHz / 2 cycles.  `issue_busy`, `lane_util` and their product `counter_frac` come from
-      rocprofv3 --pmc passes this invocation runs itself as child processes before its own first GPU call (`traffic_source: "live"`;
-      --no-live-pmc or a missing rocprofv3: the committed passes of profiles/pmc_traffic.json, "committed"); frac <= counter_frac by
+      rocprofv3 --pmc passes a --full invocation runs itself as child processes before its own first GPU call (`traffic_source: "live"`;
+      a plain run, --no-live-pmc or a missing rocprofv3: the committed passes of profiles/pmc_traffic.json, "committed"); frac <= counter_frac by
       construction, `non_traversal_share` = 1 - frac / counter_frac is the ray's shell (ray generation, shading, NEE, bounce
       sampling) plus the loop's bookkeeping.  `traffic` = L2<->fabric bytes per launch, (2 FETCH_SIZE + WRITE_SIZE) x 1024 from the
       same passes; `hbm_frac` = traffic / time / 8 TB/s (HBM traffic proper only for the scene that exceeds the Infinity Cache).
       Definitions and the script that recomputes every figure: tools/roofline.py, profiles/isa_counts.json.
-  "cpu_baseline": the CPU oracle on the same workload, bounded sample, rank 0, N = 1.
+  "cpu_baseline" (--full): the CPU oracle on the same workload, bounded sample, rank 0, N = 1.
 """
 import argparse
 import json
@@ -98,17 +105,20 @@ def parse_args(argv=None):
     ap.add_argument("--settle-ms", type=float, default=100.0,
                     help="untimed rendering before the warm-up steps, in ms of wall time (default 100): clocks and caches reach the steady "
                          "state the metric is about; 0 = none")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure (see the module docstring); a plain run sets up, settles, warms up, times "
+                         "the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-oracle-check", action="store_true",
-                    help="skip `sum_rows_match_oracle` (after the timed region every block renders one more step in the timed form and compares "
+                    help="skip `sum_rows_match_oracle` (--full: after the timed region every block renders one more step in the timed form and compares "
                          "16 rows of the sum with the CPU oracle)")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="auto workload at N = 1: do not run the rocprofv3 --pmc passes (roofline.traffic / valu_issue then come from the "
+                    help="--full, auto workload at N = 1: do not run the rocprofv3 --pmc passes (roofline.traffic / valu_issue then come from the "
                          "committed profiles/pmc_traffic.json and say so)")
     ap.add_argument("--device-built", default=None, metavar="BUILDER",
                     help="explicit workload: crt_scene_create builds the tree itself on the GPU from the source-order arrays (lbvh, ploc<r>, sah)")
-    ap.add_argument("--no-extra", action="store_true", help="auto workload: only the headline block")
-    ap.add_argument("--no-hbm-resident", action="store_true", help="auto workload: skip the 8 M-triangle (> Infinity Cache) blocks")
+    ap.add_argument("--no-extra", action="store_true", help="--full, auto workload: only the headline block")
+    ap.add_argument("--no-hbm-resident", action="store_true", help="--full, auto workload: skip the 8 M-triangle (> Infinity Cache) blocks")
     ap.add_argument("--one-process", action="store_true",
                     help="N GPUs behind ONE scene handle in this one process (crt_set_devices: replication, tile sharding and the RCCL gather "
                          "inside the C ABI) instead of one process per GPU under torch.distributed; the timed region ends with crt_sum_device")
@@ -358,8 +368,9 @@ def live_pmc(workloads, budget_s=330.0):
                     log(f"[bench] live pmc: time budget used up before {key}/{kind}")
                     break
                 d = os.path.join(top, f"pmc_{kind}_{key}")
+                # --full: the counting launch and the single-sample tail that entry_from_dirs sets apart from the steps' launches
                 cmd = [rocprof, "--pmc", *counters, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__), "--gpus", "1",
-                       "--workload", name, "--depth", str(depth), "--spp", str(spp), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-live-pmc",
+                       "--workload", name, "--depth", str(depth), "--spp", str(spp), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-live-pmc",
                        "--settle-ms", "0", "--streams", "1"] + [str(x) for x in more]     # one stream: a dispatch is a whole segment of the frame
                 try:
                     run = subprocess.run(cmd, cwd=top, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, timeout=150)
@@ -419,6 +430,7 @@ def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials
     takes_part = sharded or ctx.rank == 0
     use_dist = ctx.use_dist and sharded
     K, Wu = args.steps, args.warmup
+    full = args.full
 
     out = None
     if takes_part:
@@ -469,7 +481,8 @@ def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials
 
         # ---- untimed: the visit counters of ONE STEP (all its samples and segments), from counting kernels in the form the timed launches
         # have (count_visits 2: four samples in the lanes of a wave where the timed step runs so; the uniform node steps depend on which
-        # rays share a wave).  A step of k launches is counted launch by launch.
+        # rays share a wave).  A step of k launches is counted launch by launch.  A plain run makes it too: it is the block's first launch,
+        # and the settle below has always started after it (without it the timed steps of the headline ran 0.5 % slower)
         scene.set_option("count_visits", 2)
         cs = None
         first = rvs[1 + Wu * spp:1 + (Wu + 1) * spp]            # the frames of the first timed step
@@ -569,15 +582,16 @@ def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials
         n_timed_launches = st["n_trace_launches"] if streams == 1 else launches_per_step * K
         n_segment_launches = K * launches_per_step if streams == 1 else n_timed_launches      # without the deferred any-hit launches (event kind 2)
         launch_ms_timed = (st["ms_trace_closest"] + st["ms_trace_any"]) / max(1, n_segment_launches)
-        # spread of the timed steps: device time of each step = the sum of its launches' own durations (one stream), else of wall-clock
-        # steps rendered one by one after the clock has stopped (several streams carry no events: they would keep the shards from overlapping)
+        # spread of the timed steps: device time of each step = the sum of its launches' own durations (one stream), else (--full) of
+        # wall-clock steps rendered one by one after the clock has stopped (several streams carry no events: they would keep the shards
+        # from overlapping)
+        step_ms = []
         if streams == 1 and depth == 1:
             lt = scene.launch_times()
             per = max(1, len(lt) // K)
             step_ms = [float(lt[i * per:(i + 1) * per].sum()) for i in range(K)] if len(lt) >= K else []
             spread_src = "device time of each timed step (its launches' events)"
-        else:
-            step_ms = []
+        elif full:
             for k in range(min(K, 20)):
                 t1 = time.perf_counter(); step(Wu + k); scene.sync(); step_ms.append((time.perf_counter() - t1) * 1e3)
             spread_src = f"wall time of {len(step_ms)} steps rendered one by one after the timed region"
@@ -586,13 +600,14 @@ def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials
         # samples per pixel one launch rendered: 1, or the step's spp where crt_render_frames batched them
         samples_per_launch = max(1, round(K * spp * max(1, depth) / max(1, n_segment_launches)))
         scene.set_option("timing_accumulate", 0)
-        scene.set_option("timing", 2)
         any_ms, total_ms = [], []
-        for i in range(min(10, K * spp)):
-            scene.render_frame(*rvs[1 + Wu * spp + i])
-            s = scene.frame_stats()
-            any_ms.append(s["ms_trace_any"] / max(1, depth))
-            total_ms.append(s["ms_total"])
+        if full:
+            scene.set_option("timing", 2)
+            for i in range(min(10, K * spp)):
+                scene.render_frame(*rvs[1 + Wu * spp + i])
+                s = scene.frame_stats()
+                any_ms.append(s["ms_trace_any"] / max(1, depth))
+                total_ms.append(s["ms_total"])
         rays_frame = (st["closest_rays"] + st["any_rays"]) / samples_per_launch      # the stats describe the last launch
         rays_all = ctx.sum_over_ranks(rays_frame) if sharded else float(rays_frame)
         value = rays_all * K * spp / dt / 1e6
@@ -638,7 +653,7 @@ def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials
             "algorithmic_bytes_per_launch": int(alg_bytes),
             "l2_hit_rate": pmc.get("l2_hit_rate"),
             "launch_ms": round(t_launch * 1e3, 4), "launches_timed": int(n_segment_launches), "samples_per_launch": int(samples_per_launch),
-            "path_segments": depth, "frame_device_ms": round(float(np.median(total_ms)), 4),
+            "path_segments": depth, "frame_device_ms": round(float(np.median(total_ms)), 4) if total_ms else None,
             "nodes_per_ray": round(cs["nodes_closest"] / max(1, cs["closest_rays"]), 3), "tris_per_ray": round(cs["tris_closest"] / max(1, cs["closest_rays"]), 3),
             "any_hit_nodes_per_ray": round(cs["nodes_any"] / max(1, cs["any_rays"]), 3), "any_hit_tris_per_ray": round(cs["tris_any"] / max(1, cs["any_rays"]), 3),
             "counters": counters,
@@ -668,11 +683,11 @@ def run_block(ctx, name, W, H, depth, spp, sharded, cpu_base, scaling, materials
         if build_info:
             out["config"]["device_build"] = build_info
         out["config"]["launch"] = launch_info
-        if not args.no_oracle_check and (world == 1 or one_proc):
+        if full and not args.no_oracle_check and (world == 1 or one_proc):
             # after the clock has stopped: ONE more step, exactly as the timed region ran it, on a cleared sum, and 16 rows of the result
             # against the CPU oracle on the same frames (the checker, never the thing measured)
             out["sum_rows_match_oracle"] = rows_match_oracle(scene, step, Wu, spp, rvs, data, name, device_built, materials or args.materials, cam, W, H, depth, accel)
-        if cpu_base and not args.no_cpu_baseline and accel == "cwbvh":
+        if full and cpu_base and not args.no_cpu_baseline and accel == "cwbvh":
             out["cpu_baseline"] = cpu_baseline(data, cam, W, H, depth, rvs[1 + Wu * spp:1 + (Wu + 1) * spp], cs)
     if takes_part and dump_dir:
         # what the last timed step computed: its frames once more, exactly as the timed region ran them, on a cleared sum (the sum at the
@@ -918,7 +933,7 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
 
-    if (args.gpus == 1 and "RANK" not in os.environ and args.workload == "auto" and args.accel == "cwbvh"
+    if (args.full and args.gpus == 1 and "RANK" not in os.environ and args.workload == "auto" and args.accel == "cwbvh"
             and not (args.dry_run or args.no_live_pmc or args.option)):
         # hardware counters of this very run, from child processes, before this process makes its first GPU call
         live_pmc([("mesh1m", args.depth, args.spp or 4)] + ([] if args.no_extra else [("mesh1m", 4, 4), ("cornell", 1, 1)])
@@ -962,7 +977,7 @@ def main():
         head = run_block(ctx, name, W, H, args.depth, spp, True, N == 1 and not args.device_built, scaling, device_built=args.device_built,
                          dump_dir=args.dump_outputs)
         extra = {}
-        if auto and not args.no_extra and args.accel == "cwbvh":
+        if auto and args.full and not args.no_extra and args.accel == "cwbvh":
             if N == 1:
                 extra["cornell"] = run_block(ctx, "cornell", 1920, 1080, 1, 1, True, False, "weak")
                 extra["gpu_tree"] = run_block(ctx, "mesh1m", 1920, 1080, 1, 4, True, False, "weak", device_built="sah")

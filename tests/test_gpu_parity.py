@@ -2006,7 +2006,7 @@ def test_warmup_loads_the_code_objects_and_can_be_repeated(cr, cornell_data):
 
 
 def test_bench_line_contract(tmp_path):
-    """`python bench.py` (N = 1): exactly one JSON line, short enough for the driver's record (< 8 KB), whose top-level fields are
+    """`python bench.py --full` (N = 1): exactly one JSON line, short enough for the driver's record (< 8 KB), whose top-level fields are
     configs[2] — the 1,004,672-triangle workload BASELINE.json's targets are quoted on — with the roofline object against the roof
     that binds (vector-instruction issue; every figure recomputable from the line), the CPU baseline, compact extras for the other
     configs, the reference's own claims (README.md:21-22) measured on this GPU and the drop-in frame loop."""
@@ -2016,8 +2016,8 @@ def test_bench_line_contract(tmp_path):
     import subprocess
     import sys
     from conftest import ROOT
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--no-hbm-resident"], capture_output=True, text=True,
-                         cwd=str(tmp_path))
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--full", "--no-hbm-resident"], capture_output=True,
+                         text=True, cwd=str(tmp_path))
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [l for l in run.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, run.stdout
@@ -2088,6 +2088,39 @@ def test_bench_line_contract(tmp_path):
     for k in ("frame_loop_cornell", "frame_loop_mesh1m"):
         fl = ex[k]
         assert 0 < fl["segment_launch_ms"] < fl["ms_per_frame_image_in_hbm"] <= fl["ms_per_frame_image_in_host_memory"] and fl["rgba_rows_match_oracle"] is True, (k, fl)
+
+
+def test_plain_bench_run_is_the_headline_alone(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: one JSON line with the headline's figures (configs[2], value = rays per
+    step / ms per step, the spread of the timed steps from their own events, the roofline from the step's counters and the committed counter
+    passes) and nothing that takes runs of its own — no rocprofv3 passes, single-sample tail, oracle rows, CPU baseline or extras
+    (test_bench_line_contract checks those under --full)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2"], capture_output=True, text=True,
+                         cwd=str(tmp_path), timeout=600)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = [l for l in run.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, run.stdout
+    d = json.loads(lines[0])
+    assert d["unit"] == "Mray/s" and d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and "1920x1080" in d["metric"]
+    cfg = d["config"]
+    assert "1004672 tris" in cfg["workload"] and cfg["spp_per_step"] == 4 and cfg["path_segments"] == 1 and cfg["stack_overflows"] == 0
+    assert cfg["launch"] == {"form": 2, "wide": True, "one_pass": True, "samples": 4, "shards": 1}
+    assert d["value"] > 1000 and abs(d["value"] - cfg["rays_per_step"] / d["ms_per_step"] / 1e3) / d["value"] < 0.01
+    sp = d["step_ms_spread"]
+    assert sp["n"] == 6 and 0 < sp["min"] <= sp["median"] <= sp["max"] < 2 * d["ms_per_step"]
+    r = d["roofline"]
+    assert r["counters"]["primary_rays"] == 4 * 1920 * 1080 and r["launches_timed"] == 6 and r["launch_ms"] > 0 and r["frame_device_ms"] is None
+    assert r["traffic_source"] in ("committed", None) and 0 < r["frac_executed"] < r["frac"] <= 1.0
+    for k in ("cpu_baseline", "sum_rows_match_oracle", "extras", "reference_claims"):
+        assert k not in d, k
+    # one block rendered, no rocprofv3 passes started
+    assert sum("rank(s); BVH build" in l for l in run.stderr.splitlines()) == 1 and "live pmc" not in run.stderr, run.stderr[-2000:]
 
 
 def test_bench_self_launch_under_rccl_on_one_gpu(tmp_path):

@@ -9,7 +9,7 @@ UNITS = {"TA_": 256, "TCP_": 256, "TD_": 256}
 
 
 def main(d, tail=0):
-    """tail: how many of the LAST segment-kernel dispatches of each pass to leave out (bench.py ends a run with min(10, steps x spp)
+    """tail: how many of the LAST segment-kernel dispatches of each pass to leave out (bench.py --full ends a run with min(10, steps x spp)
     single-sample frames, `depth` segment launches each: a quarter of the work of a 4-sample launch, some by the same kernel)."""
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import pmc_traffic

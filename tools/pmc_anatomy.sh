@@ -3,7 +3,7 @@
 # bench.py workload, summarised per kernel by tools/pmc_anatomy.py.
 #   usage (on the box): bash tools/pmc_anatomy.sh OUTDIR "bench.py arguments" [TAIL]
 # TAIL = segment launches of the run's closing single-sample frames to leave out: min(10, steps x spp) x depth (10 for one segment, 40 for four)
-R=$GRAFT_REPO_ROOT; O=$1; ARGS="--no-cpu-baseline --no-live-pmc --no-oracle-check --settle-ms 0 --steps 5 --warmup 2 --streams 1 $2"
+R=$(cd "$(dirname "$0")/.." && pwd); O=$1; ARGS="--full --no-cpu-baseline --no-live-pmc --no-oracle-check --settle-ms 0 --steps 5 --warmup 2 --streams 1 $2"
 mkdir -p $O; cd /tmp && export TMPDIR=/tmp
 i=0
 while read -r LINE; do

@@ -3,7 +3,7 @@
 
 usage: tools/pmc_counters.py [--kernel SUBSTR] [--skip-last N] DIR [DIR ...]
 --kernel     only kernels whose name contains SUBSTR (default "k_segment")
---skip-last  leave out the last N dispatches of every kernel (bench.py ends a run with up to 10 single-sample frames under full event
+--skip-last  leave out the last N dispatches of every kernel (bench.py --full ends a run with up to 10 single-sample frames under full event
              timing; with --spp 4 they are launches of another kernel or another size)
 Prints one line per (directory, kernel, counter): dispatches, mean, min, max.
 """

@@ -18,7 +18,7 @@ N_SIMD = 256 * 4
 
 def per_kernel(dirname, tail=0):
     """{(kernel, counter): [value per dispatch]} of one pass.  `tail` = how many of the LAST dispatches of the non-counting segment
-    kernels to leave out: bench.py ends every run with min(10, steps x spp) single-sample frames rendered with full event timing, and
+    kernels to leave out: bench.py --full ends every run with min(10, steps x spp) single-sample frames rendered with full event timing, and
     those launches — a quarter of the work of a 4-sample launch, some of them by the same kernel — must not be averaged in."""
     rows = []
     for f in glob.glob(os.path.join(dirname, "**", "*counter_collection.csv"), recursive=True):

@@ -10,17 +10,17 @@ TAG=${1:-r05}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/round_$TAG; [ "$PART" != "2" ] && rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [ "$PART" != "2" ]; then
-HEAD="--no-cpu-baseline --no-live-pmc --no-extra"
+HEAD="--full --no-cpu-baseline --no-live-pmc --no-extra"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_headline -- python3 $R/bench.py $HEAD > $O/stats_headline.json 2> $O/stats_headline.log
 echo "headline stats done"
 for CFG in "mesh1m 4 4" "cornell 1 1"; do
   set -- $CFG; WL=$1; D=$2; S=$3
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_${WL}_d$D -- python3 $R/bench.py --no-cpu-baseline --no-live-pmc --workload $WL --depth $D --spp $S > $O/stats_${WL}_d$D.json 2> $O/stats_${WL}_d$D.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_${WL}_d$D -- python3 $R/bench.py --full --no-cpu-baseline --no-live-pmc --workload $WL --depth $D --spp $S > $O/stats_${WL}_d$D.json 2> $O/stats_${WL}_d$D.log
 done
 echo "kernel stats done"
 for CFG in "mesh1m 1 4" "mesh1m 4 4" "cornell 1 1" "mesh520 1 4 --device-built sah" "mesh520 4 4 --device-built sah"; do
   set -- $CFG; WL=$1; D=$2; S=$3; shift 3
-  ARGS="--no-cpu-baseline --no-live-pmc --settle-ms 0 --steps 5 --warmup 2 --streams 1 --workload $WL --depth $D --spp $S $*"
+  ARGS="--full --no-cpu-baseline --no-live-pmc --settle-ms 0 --steps 5 --warmup 2 --streams 1 --workload $WL --depth $D --spp $S $*"
   rocprofv3 --pmc FETCH_SIZE TCC_HIT_sum GRBM_GUI_ACTIVE GRBM_TA_BUSY --output-format csv -d $O/pmc_fetch_${WL}_d$D -- python3 $R/bench.py $ARGS > /dev/null 2>&1
   rocprofv3 --pmc WRITE_SIZE TCC_MISS_sum --output-format csv -d $O/pmc_write_${WL}_d$D -- python3 $R/bench.py $ARGS > /dev/null 2>&1
   rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d $O/pmc_sq_${WL}_d$D -- python3 $R/bench.py $ARGS > /dev/null 2>&1
@@ -30,10 +30,10 @@ python3 $R/tools/pmc_traffic.py $O $O/pmc_traffic.json > $O/pmc_traffic.log 2>&1
 fi
 [ "$PART" = "1" ] && exit 0
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.log
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.log
 echo "bench default done"
-python bench.py --gpus 1 --one-process --virtual-devices 8 --no-cpu-baseline --no-live-pmc > $O/bench_one_process_virtual8.json 2> $O/bench_one_process_virtual8.log
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus 1 --workload mesh1m --resolution 3840x2160 --no-cpu-baseline > $O/bench_config5_world1.json 2> $O/bench_config5_world1.log
+python bench.py --gpus 1 --one-process --virtual-devices 8 --full --no-cpu-baseline --no-live-pmc > $O/bench_one_process_virtual8.json 2> $O/bench_one_process_virtual8.log
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus 1 --workload mesh1m --resolution 3840x2160 --full --no-cpu-baseline > $O/bench_config5_world1.json 2> $O/bench_config5_world1.log
 for A in "mesh1m 1" "mesh1m 1 lanes" "mesh1m 4" "mesh1m 4 lanes" "mesh1m 4 inplace_shadow=1" "mesh1m 4 lanes_per_ray=1" "cornell 1"; do python tools/lane_util.py $A; done > $O/lane_util.txt 2>&1
 for A in "mesh1m 1" "mesh1m 4"; do python tools/lane_hist.py $A; done > $O/lane_hist.txt 2>&1
 python tools/build_probe.py > $O/build_probe.txt 2>&1
