@@ -117,6 +117,8 @@ SYMBOLS = {
     "crt_instances_debug_read": (_I, [_P, _I, _P, _SZ, C.POINTER(_SZ)]),
     "crt_instances_update_meshes": (_I, [_P, _P, _U32, _P, _P]),
     "crt_instances_update_meshes_device": (_I, [_P, _P, _U32, _P, _P, _I]),
+    "crt_instances_add_meshes": (_I, [_P, _P, _U32, C.POINTER(_U32)]),
+    "crt_instances_replace_meshes": (_I, [_P, _P, _U32, _P]),
     "crt_instances_last_update": (_I, [_P, C.POINTER(_F), C.POINTER(_F), C.POINTER(C.c_uint64)]),
     "crt_instances_destroy": (_I, [_P]),
     "crt_instance_inverse": (_I, [_P, _P]),

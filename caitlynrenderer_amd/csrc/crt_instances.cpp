@@ -3,7 +3,8 @@
 // device (binned SAH over boxes, then the same converter) at create and at every set, or refitted in place by crt_instances_refit
 // (DESIGN.md §13).  All node8s live in ONE array (the TLAS region first,
 // sized for `capacity`, then every BLAS with its child / triangle bases rebased) and all triangle records in ONE array, so the walk
-// (instances.hip k_trace_instances) addresses any node with one 32-bit index off one base.
+// (instances.hip k_trace_instances) addresses any node with one 32-bit index off one base.  crt_instances_add_meshes and
+// crt_instances_replace_meshes change the mesh list of a live handle: new arrays in the same layout, swapped in last.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -67,10 +68,15 @@ struct InstUpdateState {
     }
 };
 
+// what a repack needs to know of a packed BLAS (crt_instances_add_meshes / crt_instances_replace_meshes)
+struct MeshSlot { uint32_t n8 = 0, n_tris = 0, depth8 = 0; };
+
 struct crt_instances {
     int device = 0;
     hipStream_t stream = nullptr;
     uint32_t n_meshes = 0, capacity = 0, n_instances = 0;
+    uint32_t gpu_flags = 0;               // the builder given at create: added and replaced meshes are built with it
+    std::vector<MeshSlot> mesh;           // per mesh, in the order of the packed arrays
     uint32_t tlas_cap_nodes = 0, n_tlas8 = 0, tlas_depth8 = 0, max_blas_depth8 = 0, stack_entries = 2;
     uint64_t blas_nodes8 = 0, blas_tris = 0;
     uint4* d_nodes = nullptr;             // TLAS region (tlas_cap_nodes) + every BLAS
@@ -153,13 +159,14 @@ uint32_t gpu_flags_of(uint32_t build_flags) {
 
 // One mesh: LBVH / PLOC / SAH BVH2 -> CWBVH -> records, as crt_scene_create's build-on-device path.  *d_nodes8 and *d_recs are the
 // caller's to free.
-int build_blas(const crt_blas_desc& m, uint32_t gpu_flags, hipStream_t st, crt_node8** d_nodes8, float4** d_recs, uint32_t* n8, uint32_t* depth8) {
+int build_blas(const crt_blas_desc& m, uint32_t gpu_flags, hipStream_t st, const std::string& who, crt_node8** d_nodes8, float4** d_recs, uint32_t* n8,
+               uint32_t* depth8) {
     const uint32_t n = (uint32_t)m.n_triangles, n2 = 2u * n - 1u;
     crt::DeviceArena arena;
     auto P = crt::DeviceArena::padded;
     const size_t tmp = std::max(crt::lbvh_tmp_bytes(n, gpu_flags), crt::cwbvh_tmp_bytes(n2, n));
     hipError_t he = arena.reserve(P(m.n_vertices * 12) + P((size_t)n * sizeof(crt_triangle)) + P((size_t)n2 * sizeof(crt_flatnode)) + 2 * P((size_t)n * 4) + tmp);
-    if (he != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("crt_instances_create: hipMalloc: ") + hipGetErrorString(he));
+    if (he != hipSuccess) return fail(CRT_ERR_NOMEM, who + "hipMalloc: " + hipGetErrorString(he));
     float* d_verts = arena.take<float>(m.n_vertices * 3);
     crt_triangle* d_in = arena.take<crt_triangle>(n);
     crt_flatnode* d_flat = arena.take<crt_flatnode>(n2);
@@ -171,10 +178,10 @@ int build_blas(const crt_blas_desc& m, uint32_t gpu_flags, hipStream_t st, crt_n
     uint32_t depth2 = 0;
     float ms = 0.f;
     int rc = crt::lbvh_build_on_device(reinterpret_cast<const int32_t*>(d_in), 12, d_verts, n, gpu_flags, arena, d_flat, d_order, &depth2, &ms, st);
-    if (rc) return fail(rc, std::string("crt_instances_create: BLAS build failed: ") + crt_last_error());
+    if (rc) return fail(rc, who + "BLAS build failed: " + crt_last_error());
     arena.used = mark;
     rc = crt::cwbvh_convert_on_device(d_flat, n2, n, arena, d_slots, d_nodes8, nullptr, n8, depth8, &ms, st);
-    if (rc) return fail(rc, std::string("crt_instances_create: BLAS BVH2 -> CWBVH failed: ") + crt_last_error());
+    if (rc) return fail(rc, who + "BLAS BVH2 -> CWBVH failed: " + crt_last_error());
     if ((rc = alloc(d_recs, (size_t)n * 3))) { (void)hipFree(*d_nodes8); *d_nodes8 = nullptr; return rc; }
     crt::launch_gather_records(d_in, d_order, d_slots, d_verts, n, *d_recs, st);
     IHIPCHK(hipStreamSynchronize(st));                // before the arena goes
@@ -192,13 +199,17 @@ struct TlasStage {
     ~TlasStage() { if (s && d_t8 && d_t8 != s->d_t8_stage) (void)hipFree(d_t8); }
 };
 
-// n >= 1 instances (DEVICE memory) through the prep kernel against the mesh boxes d_mesh_box, into the set's staging (d_rec, d_box,
-// d_w2o_stage), and the host's one wait for its verdict.  Shared by sets, updates and refits; the walk reads none of it.
-int prep_instances(crt_instances* s, const void* d_src, uint32_t n, const float* d_mesh_box, const std::string& who) {
+// n >= 1 instances (DEVICE memory) through the prep kernel against the mesh boxes d_mesh_box and BLAS roots d_mesh_root of n_meshes
+// meshes (the live ones, or a call's staged ones), into the set's staging (d_rec, d_box, d_w2o_stage), and the host's one wait for its
+// verdict.  Shared by sets, updates, refits and replaces; the walk reads none of it.
+struct MeshTables { const float* d_box; const uint32_t* d_root; uint32_t n_meshes, max_depth8; };
+MeshTables live_tables(const crt_instances* s) { return MeshTables{s->d_mesh_box, s->d_mesh_root, s->n_meshes, s->max_blas_depth8}; }
+
+int prep_instances(crt_instances* s, const void* d_src, uint32_t n, const MeshTables& mt, const std::string& who) {
     hipStream_t st = s->stream;
     IHIPCHK(hipMemsetAsync(s->d_flag, 0, 4, st));
     crt::InstPrepArgs pa{};
-    pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = s->n_meshes; pa.mesh_box = d_mesh_box; pa.mesh_root = s->d_mesh_root;
+    pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = mt.n_meshes; pa.mesh_box = mt.d_box; pa.mesh_root = mt.d_root;
     pa.rec = s->d_rec; pa.box = s->d_box; pa.w2o = s->d_w2o_stage; pa.flag = s->d_flag;
     crt::launch_instance_prep(pa, st);
     uint32_t flag = 0;
@@ -211,10 +222,10 @@ int prep_instances(crt_instances* s, const void* d_src, uint32_t n, const float*
     return CRT_OK;
 }
 
-int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const float* d_mesh_box, const std::string& who, TlasStage& ts) {
+int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const MeshTables& mt, const std::string& who, TlasStage& ts) {
     hipStream_t st = s->stream;
     ts.s = s;
-    int rc = prep_instances(s, d_src, n, d_mesh_box, who);
+    int rc = prep_instances(s, d_src, n, mt, who);
     if (rc) return rc;
     // the TLAS over the world boxes
     s->arena.used = s->arena_mark;
@@ -231,7 +242,7 @@ int stage_tlas(crt_instances* s, const void* d_src, uint32_t n, const float* d_m
     rc = crt::cwbvh_convert_on_device(s->d_flat, n == 1 ? 1u : 2u * n - 1u, n, s->arena, s->d_tri_slots, &ts.d_t8, nullptr, &ts.n8, &ts.depth8, &ms, st,
                                       s->d_t8_stage, s->tlas_cap_nodes);
     if (rc) return fail(rc, who + "TLAS BVH2 -> CWBVH failed: " + crt_last_error());
-    ts.stack = std::max<uint32_t>(2u, ts.depth8 + s->max_blas_depth8);
+    ts.stack = std::max<uint32_t>(2u, ts.depth8 + mt.max_depth8);
     if (ts.stack > CRT_INST_STACK_ENTRIES)
         return fail(CRT_ERR_LIMIT, who + "TLAS depth + deepest BLAS exceed the walk's stack (" + std::to_string(ts.stack) + " > " +
                                        std::to_string(CRT_INST_STACK_ENTRIES) + " entries)");
@@ -262,7 +273,7 @@ int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
     IHIPCHK(hipEventRecord(s->ev0, st));
     if (n > 0) {
         TlasStage ts;
-        int rc = stage_tlas(s, d_src, n, s->d_mesh_box, "crt_instances_set: ", ts);
+        int rc = stage_tlas(s, d_src, n, live_tables(s), "crt_instances_set: ", ts);
         if (rc) return rc;
         if ((rc = publish_tlas(s, d_src, n, ts))) return rc;
         IHIPCHK(hipStreamSynchronize(st));            // the publication is done when the call returns
@@ -311,7 +322,7 @@ int refit_impl(crt_instances* s, const void* d_src, uint32_t n, const std::strin
     hipStream_t st = s->stream;
     IHIPCHK(hipEventRecord(s->ev0, st));
     if (n > 0) {
-        int rc = prep_instances(s, d_src, n, s->d_mesh_box, who);
+        int rc = prep_instances(s, d_src, n, live_tables(s), who);
         if (rc) return rc;
         if (!s->tlas_levels_ok && (rc = find_tlas_levels(s))) return rc;
         const auto* d_mesh = reinterpret_cast<const crt::RefitMesh*>(s->d_tlas_table);
@@ -484,7 +495,9 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
     const uint32_t ni = s->n_instances;
     TlasStage ts;
     if (ni > 0) {
-        const int rc = stage_tlas(s, u->d_live, ni, u->d_mesh_box_stage, who, ts);
+        MeshTables mt = live_tables(s);
+        mt.d_box = u->d_mesh_box_stage;
+        const int rc = stage_tlas(s, u->d_live, ni, mt, who, ts);
         if (rc) return rc;
     }
     // 4. the BLAS refit in place (records first: the leaf slots read only their id words), then the publication
@@ -510,6 +523,25 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
     return CRT_OK;
 }
 
+// One mesh of a create, add or replace, checked on the host before any device work; box: the exact float box of its referenced vertices.
+int validate_mesh(const crt_blas_desc& m, uint32_t k, const std::string& who, float* box) {
+    if (!m.vertices || !m.triangles || m.n_vertices == 0 || m.n_triangles == 0) return fail(CRT_ERR_INVALID, who + "mesh " + std::to_string(k) + " is empty");
+    if (2ull * m.n_triangles >= (1ull << 29)) return fail(CRT_ERR_LIMIT, who + "a mesh has 2^28 triangles or more");
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t i = 0; i < m.n_triangles; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const int32_t vi = m.triangles[i].v[j];
+            if (vi < 0 || (size_t)vi >= m.n_vertices) return fail(CRT_ERR_INVALID, who + "vertex index out of range");
+            for (int a = 0; a < 3; ++a) {
+                const float x = m.vertices[3 * (size_t)vi + a];
+                if (!(std::fabs(x) <= 1e18f)) return fail(CRT_ERR_INVALID, who + "a vertex coordinate is not finite or exceeds 1e18");
+                lo[a] = std::min(lo[a], x); hi[a] = std::max(hi[a], x);
+            }
+        }
+    for (int a = 0; a < 3; ++a) { box[a] = lo[a]; box[3 + a] = hi[a]; }
+    return CRT_OK;
+}
+
 int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instance* instances, uint32_t n_instances, uint32_t capacity,
                 uint32_t build_flags, crt_instances** out) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -523,23 +555,9 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     std::vector<float> mesh_box(6 * (size_t)n_meshes);
     uint64_t tris_total = 0;
     for (uint32_t k = 0; k < n_meshes; ++k) {
-        const crt_blas_desc& m = meshes[k];
-        if (!m.vertices || !m.triangles || m.n_vertices == 0 || m.n_triangles == 0)
-            return fail(CRT_ERR_INVALID, "crt_instances_create: mesh " + std::to_string(k) + " is empty");
-        if (2ull * m.n_triangles >= (1ull << 29)) return fail(CRT_ERR_LIMIT, "crt_instances_create: a mesh has 2^28 triangles or more");
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (size_t i = 0; i < m.n_triangles; ++i)
-            for (int j = 0; j < 3; ++j) {
-                const int32_t vi = m.triangles[i].v[j];
-                if (vi < 0 || (size_t)vi >= m.n_vertices) return fail(CRT_ERR_INVALID, "crt_instances_create: vertex index out of range");
-                for (int a = 0; a < 3; ++a) {
-                    const float x = m.vertices[3 * (size_t)vi + a];
-                    if (!(std::fabs(x) <= 1e18f)) return fail(CRT_ERR_INVALID, "crt_instances_create: a vertex coordinate is not finite or exceeds 1e18");
-                    lo[a] = std::min(lo[a], x); hi[a] = std::max(hi[a], x);
-                }
-            }
-        for (int a = 0; a < 3; ++a) { mesh_box[6 * (size_t)k + a] = lo[a]; mesh_box[6 * (size_t)k + 3 + a] = hi[a]; }
-        tris_total += m.n_triangles;
+        int rc = validate_mesh(meshes[k], k, "crt_instances_create: ", &mesh_box[6 * (size_t)k]);
+        if (rc) return rc;
+        tris_total += meshes[k].n_triangles;
     }
     int rc = require_gpu();
     if (rc) return rc;
@@ -558,10 +576,12 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     struct Blas { crt_node8* nodes = nullptr; float4* recs = nullptr; uint32_t n8 = 0, depth8 = 0; };
     std::vector<Blas> blas(n_meshes);
     struct FreeAll { std::vector<Blas>& b; ~FreeAll() { for (auto& x : b) { if (x.nodes) (void)hipFree(x.nodes); if (x.recs) (void)hipFree(x.recs); } } } free_all{blas};
-    const uint32_t gflags = gpu_flags_of(build_flags);
+    const uint32_t gflags = s->gpu_flags = gpu_flags_of(build_flags);
+    s->mesh.resize(n_meshes);
     uint64_t nodes_total = s->tlas_cap_nodes;
     for (uint32_t k = 0; k < n_meshes; ++k) {
-        if ((rc = build_blas(meshes[k], gflags, st, &blas[k].nodes, &blas[k].recs, &blas[k].n8, &blas[k].depth8))) return rc;
+        if ((rc = build_blas(meshes[k], gflags, st, "crt_instances_create: ", &blas[k].nodes, &blas[k].recs, &blas[k].n8, &blas[k].depth8))) return rc;
+        s->mesh[k] = MeshSlot{blas[k].n8, (uint32_t)meshes[k].n_triangles, blas[k].depth8};
         nodes_total += blas[k].n8;
         s->max_blas_depth8 = std::max(s->max_blas_depth8, blas[k].depth8);
     }
@@ -616,6 +636,217 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     }
     s->build_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = owner.release();
+    return CRT_OK;
+}
+
+// The staging of an add / replace: everything built for the new mesh list.  The publication swaps the live arrays in, so that what is
+// freed here is either an abandoned attempt or the arrays the handle had before.
+struct Remesh {
+    struct Blas { crt_node8* nodes = nullptr; float4* recs = nullptr; uint32_t n8 = 0, depth8 = 0; };
+    hipStream_t st = nullptr;             // set once work is enqueued: an abandoned attempt waits for it before its arrays go
+    std::vector<float> box_all;           // host sources of enqueued uploads: the mesh boxes, the BLAS roots, the call's index triples
+    std::vector<uint32_t> node_at;
+    std::vector<int32_t> idx;
+    std::vector<Blas> blas;               // the call's meshes as built: zero-based
+    uint4* d_nodes = nullptr;
+    float4* d_tris = nullptr;
+    float* d_mesh_box = nullptr;
+    uint32_t* d_mesh_root = nullptr;
+    uint32_t* d_order_new = nullptr;      // level order of the call's meshes (discover_levels)
+    std::unique_ptr<InstUpdateState> upd;
+    ~Remesh() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (auto& b : blas) { if (b.nodes) (void)hipFree(b.nodes); if (b.recs) (void)hipFree(b.recs); }
+        void* bufs[] = {d_nodes, d_tris, d_mesh_box, d_mesh_root, d_order_new};
+        for (void* p : bufs) if (p) (void)hipFree(p);
+    }
+};
+
+// crt_instances_add_meshes (add: the call's meshes go behind the existing ones) and crt_instances_replace_meshes (ids name the meshes
+// they stand for); DESIGN.md §15.  The new mesh list is laid out in NEW arrays as create lays it out: kept BLASes are copied from the live
+// arrays with their bases moved (k_move_nodes), the call's BLASes from their builds.  A replace then stages the live instances' records,
+// boxes and TLAS against the new roots, boxes and deepest BLAS.  Only when every check has passed do the new arrays become the live ones.
+int remesh_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const crt_blas_desc* meshes, uint32_t* first_id, bool add, const std::string& who) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s) return fail(CRT_ERR_INVALID, who + "null handle");
+    InstUpdateState* u = s->upd.get();
+    if (!add && !u) return fail(CRT_ERR_INVALID, who + "the handle was created without CRT_INSTANCES_UPDATABLE");
+    if (n && (!meshes || (!add && !ids))) return fail(CRT_ERR_INVALID, who + "null argument");
+    const uint32_t M0 = s->n_meshes;
+    if (add ? n > 0xffffffffu - M0 : n > M0) return fail(CRT_ERR_INVALID, who + (add ? "too many meshes" : "more meshes than the handle holds"));
+    const uint32_t M1 = add ? M0 + n : M0;
+    std::vector<int32_t> from(M1, -1);                // per mesh of the new list: its position in the call, or -1 = kept
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t m = add ? M0 + k : ids[k];
+        if (m >= M1) return fail(CRT_ERR_INVALID, who + "mesh index " + std::to_string(m) + " is out of range");
+        if (from[m] >= 0) return fail(CRT_ERR_INVALID, who + "mesh index " + std::to_string(m) + " is repeated");
+        from[m] = (int32_t)k;
+    }
+    Remesh r;
+    std::vector<float>& box_all = r.box_all;
+    box_all.resize(6 * (size_t)M1);
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t m = add ? M0 + k : ids[k];
+        const int rc = validate_mesh(meshes[k], m, who, &box_all[6 * (size_t)m]);
+        if (rc) return rc;
+    }
+    if (n == 0) { if (first_id) *first_id = M0; return CRT_OK; }
+    IHIPCHK(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    IHIPCHK(hipEventRecord(s->ev0, st));
+    int rc;
+    r.st = st;
+    r.blas.resize(n);
+    for (uint32_t k = 0; k < n; ++k)
+        if ((rc = build_blas(meshes[k], s->gpu_flags, st, who, &r.blas[k].nodes, &r.blas[k].recs, &r.blas[k].n8, &r.blas[k].depth8))) return rc;
+
+    // the new layout, and where every kept mesh lies today
+    std::vector<MeshSlot> slot(M1);
+    std::vector<uint32_t>& node_at = r.node_at;
+    node_at.resize(M1);
+    std::vector<uint32_t> tri_at(M1), old_node_at(M0), old_tri_at(M0);
+    uint64_t nodes_total = s->tlas_cap_nodes, tris_total = 0;
+    uint32_t max_depth8 = 0;
+    for (uint32_t m = 0; m < M1; ++m) {
+        slot[m] = from[m] < 0 ? s->mesh[m] : MeshSlot{r.blas[from[m]].n8, (uint32_t)meshes[from[m]].n_triangles, r.blas[from[m]].depth8};
+        nodes_total += slot[m].n8; tris_total += slot[m].n_tris;
+        max_depth8 = std::max(max_depth8, slot[m].depth8);
+    }
+    if (nodes_total * CRT_NODE_ROWS * 16 >= (1ull << 32) || tris_total * CRT_TRI_ROWS * 16 >= (1ull << 32))
+        return fail(CRT_ERR_LIMIT, who + "the packed node or record array would exceed 4 GiB");
+    {
+        uint64_t a = s->tlas_cap_nodes, b = 0;
+        for (uint32_t m = 0; m < M1; ++m) { node_at[m] = (uint32_t)a; tri_at[m] = (uint32_t)b; a += slot[m].n8; b += slot[m].n_tris; }
+        a = s->tlas_cap_nodes; b = 0;
+        for (uint32_t m = 0; m < M0; ++m) { old_node_at[m] = (uint32_t)a; old_tri_at[m] = (uint32_t)b; a += s->mesh[m].n8; b += s->mesh[m].n_tris; }
+    }
+    // an add keeps the TLAS: its stack bound is known now.  A replace rebuilds the TLAS: stage_tlas bounds it
+    uint32_t stack = s->stack_entries;
+    if (add && s->n_instances) {
+        stack = std::max<uint32_t>(2u, s->tlas_depth8 + max_depth8);
+        if (stack > CRT_INST_STACK_ENTRIES)
+            return fail(CRT_ERR_LIMIT, who + "TLAS depth + deepest BLAS exceed the walk's stack (" + std::to_string(stack) + " > " +
+                                           std::to_string(CRT_INST_STACK_ENTRIES) + " entries)");
+    }
+    IHIPCHK(hipStreamSynchronize(st));
+    {
+        std::vector<float> live_box(6 * (size_t)M0);
+        IHIPCHK(hipMemcpy(live_box.data(), s->d_mesh_box, live_box.size() * 4, hipMemcpyDeviceToHost));
+        for (uint32_t m = 0; m < M0; ++m)
+            if (from[m] < 0) std::copy(live_box.begin() + 6 * (size_t)m, live_box.begin() + 6 * (size_t)m + 6, box_all.begin() + 6 * (size_t)m);
+    }
+    if ((rc = alloc(&r.d_nodes, nodes_total * 5)) || (rc = alloc(&r.d_tris, tris_total * 3)) || (rc = alloc(&r.d_mesh_box, box_all.size())) ||
+        (rc = alloc(&r.d_mesh_root, M1)))
+        return rc;
+
+    // the refit state of an updatable handle for the new list: kept meshes re-offset, the call's meshes discovered
+    std::vector<int32_t>& idx = r.idx;
+    if (u) {
+        r.upd.reset(new (std::nothrow) InstUpdateState);
+        InstUpdateState* nu = r.upd.get();
+        if (!nu) return fail(CRT_ERR_NOMEM, who + "out of memory");
+        const uint64_t n8_all = nodes_total - s->tlas_cap_nodes;
+        nu->nv.resize(M1); nu->nt.resize(M1); nu->tri_off.resize(M1); nu->v_off.resize(M1); nu->level.resize(M1);
+        nu->mesh_box = box_all;
+        uint64_t v_total = 0, call_tris = 0;
+        for (uint32_t m = 0; m < M1; ++m) {
+            nu->nv[m] = from[m] < 0 ? u->nv[m] : (uint32_t)meshes[from[m]].n_vertices;
+            nu->nt[m] = slot[m].n_tris; nu->tri_off[m] = tri_at[m]; nu->v_off[m] = v_total;
+            v_total += nu->nv[m];
+            if (from[m] >= 0) call_tris += slot[m].n_tris;
+        }
+        if (v_total >= (1ull << 32) / 12) return fail(CRT_ERR_LIMIT, who + "more vertices than an updatable handle stages");
+        if ((rc = alloc(&nu->d_src_idx, 3 * tris_total)) || (rc = alloc(&nu->d_box8, 6 * n8_all)) || (rc = alloc(&nu->d_order, n8_all)) ||
+            (rc = alloc(&nu->d_mesh_box_stage, 6 * (size_t)M1)) || (rc = alloc(&nu->d_vstage, 3 * v_total)) || (rc = alloc(&nu->d_check, 8 * (size_t)M1)))
+            return rc;
+        IHIPCHK(hipHostMalloc(reinterpret_cast<void**>(&nu->h_check), 8 * (size_t)M1 * sizeof(uint32_t)));
+        IHIPCHK(hipEventCreate(&nu->ev0));
+        IHIPCHK(hipEventCreate(&nu->ev1));
+        std::vector<crt::RefitTree> trees(n);
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t m = add ? M0 + k : ids[k];
+            trees[k] = crt::RefitTree{r.blas[k].nodes, false, 5u, r.blas[k].n8, node_at[m]};
+        }
+        std::vector<std::vector<uint32_t>> lv;
+        if ((rc = crt::discover_levels(trees.data(), n, st, &r.d_order_new, lv))) return rc;
+        idx.resize(3 * call_tris);
+        uint64_t io = 0;
+        for (uint32_t m = 0; m < M1; ++m) {
+            // a tree's nodes fill positions [its node offset in the BLAS region, + n8) of the order, as init_update_state lays them out
+            const uint32_t pos = node_at[m] - s->tlas_cap_nodes;
+            if (from[m] < 0) {
+                const std::vector<uint32_t>& ol = u->level[m];
+                nu->level[m].resize(ol.size());
+                for (size_t l = 0; l < ol.size(); ++l) nu->level[m][l] = ol[l] - ol[0] + pos;
+                crt::launch_move_order(u->d_order + ol[0], nu->d_order + pos, slot[m].n8, node_at[m] - old_node_at[m], st);
+                IHIPCHK(hipMemcpyAsync(nu->d_src_idx + 3 * (size_t)tri_at[m], u->d_src_idx + 3 * (size_t)old_tri_at[m], 12 * (size_t)slot[m].n_tris,
+                                       hipMemcpyDeviceToDevice, st));
+            } else {
+                const uint32_t k = (uint32_t)from[m];
+                const std::vector<uint32_t>& ol = lv[k];
+                nu->level[m].resize(ol.size());
+                for (size_t l = 0; l < ol.size(); ++l) nu->level[m][l] = ol[l] - ol[0] + pos;
+                IHIPCHK(hipMemcpyAsync(nu->d_order + pos, r.d_order_new + ol[0], 4 * (size_t)slot[m].n8, hipMemcpyDeviceToDevice, st));
+                for (size_t i = 0; i < meshes[k].n_triangles; ++i)
+                    for (int j = 0; j < 3; ++j) idx[io + 3 * i + j] = meshes[k].triangles[i].v[j];
+                IHIPCHK(hipMemcpyAsync(nu->d_src_idx + 3 * (size_t)tri_at[m], idx.data() + io, 12 * (size_t)slot[m].n_tris, hipMemcpyHostToDevice, st));
+                io += 3 * (uint64_t)slot[m].n_tris;
+            }
+            nu->max_levels = std::max(nu->max_levels, (uint32_t)nu->level[m].size() - 1u);
+        }
+        IHIPCHK(hipMemsetAsync(nu->d_box8, 0, 24 * n8_all, st));
+        auto A = [](size_t b) { return (b + 15) & ~size_t(15); };
+        nu->table_cap = A(M1 * sizeof(crt::RefitMesh)) + A(M1 * 4) + A(M1 * sizeof(crt::RefitSeg)) + (size_t)M1 * nu->max_levels * sizeof(crt::RefitSeg);
+        if ((rc = alloc(&nu->d_table, nu->table_cap))) return rc;
+        nu->bytes = 4 * n8_all + 24 * n8_all + 12 * tris_total + 64 * (uint64_t)s->capacity + 24 * (uint64_t)M1 + 12 * v_total + 32 * (uint64_t)M1 +
+                    nu->table_cap;
+    }
+
+    // the repack: the TLAS region as it is, then every BLAS at its new offset
+    IHIPCHK(hipMemcpyAsync(r.d_nodes, s->d_nodes, (size_t)s->tlas_cap_nodes * sizeof(crt_node8), hipMemcpyDeviceToDevice, st));
+    for (uint32_t m = 0; m < M1; ++m) {
+        const bool kept = from[m] < 0;
+        const void* src_nodes = kept ? static_cast<const void*>(s->d_nodes + 5 * (size_t)old_node_at[m]) : r.blas[from[m]].nodes;
+        const float4* src_recs = kept ? s->d_tris + 3 * (size_t)old_tri_at[m] : r.blas[from[m]].recs;
+        // the wrapped difference new - old offset; a fresh build's offsets are 0
+        crt::launch_move_nodes(src_nodes, r.d_nodes + 5 * (size_t)node_at[m], slot[m].n8, node_at[m] - (kept ? old_node_at[m] : 0u),
+                               tri_at[m] - (kept ? old_tri_at[m] : 0u), st);
+        IHIPCHK(hipMemcpyAsync(r.d_tris + 3 * (size_t)tri_at[m], src_recs, 48 * (size_t)slot[m].n_tris, hipMemcpyDeviceToDevice, st));
+    }
+    IHIPCHK(hipMemcpyAsync(r.d_mesh_box, box_all.data(), box_all.size() * 4, hipMemcpyHostToDevice, st));
+    IHIPCHK(hipMemcpyAsync(r.d_mesh_root, node_at.data(), (size_t)M1 * 4, hipMemcpyHostToDevice, st));
+    IHIPCHK(hipGetLastError());
+
+    // a replace: the live instances against the NEW boxes, roots and deepest BLAS, into staging (the last refusals)
+    const uint32_t ni = s->n_instances;
+    TlasStage ts;
+    if (!add && ni > 0 && (rc = stage_tlas(s, u->d_live, ni, MeshTables{r.d_mesh_box, r.d_mesh_root, M1, max_depth8}, who, ts))) return rc;
+    IHIPCHK(hipStreamSynchronize(st));                // the new arrays are complete, and nothing in flight reads the old ones
+    IHIPCHK(hipGetLastError());
+
+    // publication: r takes the previous arrays and frees them
+    std::swap(s->d_nodes, r.d_nodes); std::swap(s->d_tris, r.d_tris); std::swap(s->d_mesh_box, r.d_mesh_box); std::swap(s->d_mesh_root, r.d_mesh_root);
+    s->mesh.swap(slot);
+    s->n_meshes = M1; s->blas_nodes8 = nodes_total - s->tlas_cap_nodes; s->blas_tris = tris_total; s->max_blas_depth8 = max_depth8;
+    if (u) {
+        InstUpdateState* nu = r.upd.get();
+        std::swap(nu->d_live, u->d_live);
+        nu->have_times = u->have_times; nu->device_ms = u->device_ms; nu->wall_ms = u->wall_ms;
+        s->upd.swap(r.upd);
+    }
+    if (!add && ni > 0) {
+        if ((rc = publish_tlas(s, s->upd->d_live, ni, ts))) return rc;
+        IHIPCHK(hipStreamSynchronize(st));
+        s->n_tlas8 = ts.n8; s->tlas_depth8 = ts.depth8; s->stack_entries = ts.stack;
+    } else {
+        s->stack_entries = stack;
+    }
+    IHIPCHK(hipEventRecord(s->ev1, st));
+    IHIPCHK(hipEventSynchronize(s->ev1));
+    IHIPCHK(hipGetLastError());
+    IHIPCHK(hipEventElapsedTime(&s->set_device_ms, s->ev0, s->ev1));
+    if (first_id) *first_id = M0;
+    s->set_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
 }
 
@@ -800,6 +1031,22 @@ int crt_instances_update_meshes_device(crt_instances* s, const uint32_t* mesh_id
         return update_impl(s, mesh_ids, n, nullptr, d_vertices, n_vertices, "crt_instances_update_meshes_device: ");
     } catch (const std::exception& e) {
         return fail(CRT_ERR_NOMEM, std::string("crt_instances_update_meshes_device: ") + e.what());
+    }
+}
+
+int crt_instances_add_meshes(crt_instances* s, const crt_blas_desc* meshes, uint32_t n, uint32_t* first_id) {
+    try {
+        return remesh_impl(s, nullptr, n, meshes, first_id, true, "crt_instances_add_meshes: ");
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_instances_add_meshes: ") + e.what());
+    }
+}
+
+int crt_instances_replace_meshes(crt_instances* s, const uint32_t* mesh_ids, uint32_t n, const crt_blas_desc* meshes) {
+    try {
+        return remesh_impl(s, mesh_ids, n, meshes, nullptr, false, "crt_instances_replace_meshes: ");
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_instances_replace_meshes: ") + e.what());
     }
 }
 

@@ -55,6 +55,27 @@ __global__ void __launch_bounds__(256) k_rebase_nodes(uint4* __restrict__ nodes,
     nodes[5 * (size_t)i + 1] = r;
 }
 
+// Repack of a live handle (crt_instances_add_meshes / crt_instances_replace_meshes): node8 i of a BLAS region copied from
+// src to dst, a SEPARATE array (the repack never moves a region inside the array it reads), with its child and triangle bases moved by
+// the signed difference new offset - old offset, passed as its two's complement: unsigned wrap-around gives the right sum, since both the
+// old and the new base are below 2^32.  A freshly built BLAS is the case old offset = 0.  One thread per 16-byte row: consecutive lanes
+// read and write consecutive rows.
+__global__ void __launch_bounds__(256) k_move_nodes(const uint4* __restrict__ src, uint4* __restrict__ dst, uint32_t n8, uint32_t node_delta,
+                                                    uint32_t tri_delta) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= 5u * n8) return;                     // 5 n8 < 2^32: the packed array is below 4 GiB
+    uint4 r = src[j];
+    if (j % 5u == 1u) { r.x += node_delta; r.y += tri_delta; }
+    dst[j] = r;
+}
+
+// the level order of a moved BLAS (global node indices): dst[i] = src[i] + delta, delta again a wrapped difference
+__global__ void __launch_bounds__(256) k_move_order(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t n, uint32_t delta) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    dst[i] = src[i] + delta;
+}
+
 __global__ void k_single_leaf(const float* __restrict__ box, crt_flatnode* __restrict__ flat, uint32_t* __restrict__ tri_order) {
     if (threadIdx.x != 0) return;
     crt_flatnode f;
@@ -315,6 +336,13 @@ void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream) {
 }
 void launch_rebase_nodes(void* d_nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off, hipStream_t stream) {
     if (n8) hipLaunchKernelGGL(k_rebase_nodes, grid_for(n8), dim3(256), 0, stream, static_cast<uint4*>(d_nodes), n8, node_off, tri_off);
+}
+void launch_move_nodes(const void* d_src, void* d_dst, uint32_t n8, uint32_t node_delta, uint32_t tri_delta, hipStream_t stream) {
+    if (n8) hipLaunchKernelGGL(k_move_nodes, grid_for(5ull * n8), dim3(256), 0, stream, static_cast<const uint4*>(d_src), static_cast<uint4*>(d_dst), n8,
+                               node_delta, tri_delta);
+}
+void launch_move_order(const uint32_t* d_src, uint32_t* d_dst, uint32_t n, uint32_t delta, hipStream_t stream) {
+    if (n) hipLaunchKernelGGL(k_move_order, grid_for(n), dim3(256), 0, stream, d_src, d_dst, n, delta);
 }
 void launch_single_leaf(const float* d_box, crt_flatnode* d_flat, uint32_t* d_tri_order, hipStream_t stream) {
     hipLaunchKernelGGL(k_single_leaf, dim3(1), dim3(64), 0, stream, d_box, d_flat, d_tri_order);

@@ -42,6 +42,11 @@ struct InstPrepArgs {
 void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream);
 // node8 i: child_base_index += node_off, triangle_base_index += tri_off
 void launch_rebase_nodes(void* d_nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off, hipStream_t stream);
+// d_dst node8 i = d_src node8 i with child_base_index += node_delta, triangle_base_index += tri_delta (wrapped differences new - old
+// offset).  d_src and d_dst must not overlap
+void launch_move_nodes(const void* d_src, void* d_dst, uint32_t n8, uint32_t node_delta, uint32_t tri_delta, hipStream_t stream);
+// d_dst[i] = d_src[i] + delta, i < n: a BLAS's level order (global node indices) after its move.  No overlap either
+void launch_move_order(const uint32_t* d_src, uint32_t* d_dst, uint32_t n, uint32_t delta, hipStream_t stream);
 // the BVH2 of ONE box: a leaf root holding slot 0
 void launch_single_leaf(const float* d_box, crt_flatnode* d_flat, uint32_t* d_tri_order, hipStream_t stream);
 // out[i] = rec[tri_order[tri_slots[i]]] (4 rows): the instance records in CWBVH leaf order

@@ -1,8 +1,8 @@
 """Instanced scenes: one bottom-level CWBVH per mesh, built once on the device, under a top-level CWBVH over transformed instances that
 is rebuilt on the device at every `set` (include/crt.h crt_instances_*) or refitted in place by `refit`, which moves the
 instances and keeps the TLAS's topology (§13).  An updatable scene also moves the vertices of its meshes: a GPU refit of their BLASes and a
-TLAS rebuild per update.  Instances carry 8-bit visibility masks that a masked trace ANDs with each ray's (§14).  Ray
-queries only: no frames."""
+TLAS rebuild per update.  Instances carry 8-bit visibility masks that a masked trace ANDs with each ray's (§14).  Meshes
+can be appended to a live scene and, in an updatable one, replaced by new geometry (§15).  Ray queries only: no frames."""
 import ctypes as C
 
 import numpy as np
@@ -55,6 +55,23 @@ def instance_world_box(object_to_world, box):
     return out
 
 
+def _blas_descs(meshes):
+    """-> (crt_blas_desc array, the arrays it points into) of Mesh objects or (vertices, triangles) pairs"""
+    descs = (crt_blas_desc * max(len(meshes), 1))()
+    keep = []
+    for k, m in enumerate(meshes):
+        v, t = (m.vertices, m.triangles) if hasattr(m, "vertices") else m
+        v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+        t = np.asarray(t, np.int32)
+        if t.ndim == 2 and t.shape[1] == 3:
+            t = np.concatenate([t, np.zeros((t.shape[0], 9), np.int32)], 1)
+        t = np.ascontiguousarray(t, np.int32).reshape(-1, 12)
+        keep += [v, t]
+        descs[k].vertices, descs[k].n_vertices = _ptr(v), v.shape[0]
+        descs[k].triangles, descs[k].n_triangles = _ptr(t), t.shape[0]
+    return descs, keep
+
+
 class InstancedScene:
     """meshes: Mesh objects (or (vertices, triangles) pairs, triangles (n, 12) int32 or (n, 3)); instances: an INSTANCE_DT array
     (instances_array); capacity: the most instances a later `set` may hold (default: len(instances)); builder: "sah", "ploc", "lbvh";
@@ -62,23 +79,12 @@ class InstancedScene:
 
     def __init__(self, meshes, instances, capacity=None, builder="sah", updatable=False):
         self._h = C.c_void_p()
-        descs = (crt_blas_desc * len(meshes))()
-        self._keep = []
-        for k, m in enumerate(meshes):
-            v, t = (m.vertices, m.triangles) if hasattr(m, "vertices") else m
-            v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
-            t = np.asarray(t, np.int32)
-            if t.ndim == 2 and t.shape[1] == 3:
-                t = np.concatenate([t, np.zeros((t.shape[0], 9), np.int32)], 1)
-            t = np.ascontiguousarray(t, np.int32).reshape(-1, 12)
-            self._keep += [v, t]
-            descs[k].vertices, descs[k].n_vertices = _ptr(v), v.shape[0]
-            descs[k].triangles, descs[k].n_triangles = _ptr(t), t.shape[0]
+        descs, keep = _blas_descs(meshes)
         inst = np.ascontiguousarray(instances, INSTANCE_DT)
         cap = inst.shape[0] if capacity is None else int(capacity)
         flags = _build_flags(builder) | (CRT_INSTANCES_UPDATABLE if updatable else 0)
         check(lib().crt_instances_create(descs, len(meshes), _ptr(inst), inst.shape[0], cap, flags, C.byref(self._h)))
-        self._keep = []
+        del keep
 
     def set(self, instances):
         inst = np.ascontiguousarray(instances, INSTANCE_DT)
@@ -104,6 +110,24 @@ class InstancedScene:
         ptrs = (C.c_void_p * max(len(vs), 1))(*[v.ctypes.data for v in vs])
         counts = np.array([v.shape[0] for v in vs], np.uint64)
         check(lib().crt_instances_update_meshes(self._h, _ptr(ids), len(vs), ptrs, _ptr(counts)))
+
+    def add_meshes(self, meshes):
+        """appends meshes (what the constructor takes) to the live scene -> the index of the first; instances, the TLAS and the existing
+        BLASes stay (crt_instances_add_meshes)"""
+        meshes = list(meshes)
+        descs, keep = _blas_descs(meshes)
+        first = C.c_uint32()
+        check(lib().crt_instances_add_meshes(self._h, descs, len(meshes), C.byref(first)))
+        del keep
+        return first.value
+
+    def replace_meshes(self, meshes_by_index):
+        """{mesh index: mesh}: new geometry (any vertex and triangle count) for existing meshes, each BLAS rebuilt from scratch and the TLAS
+        rebuilt over the live instances (crt_instances_replace_meshes; updatable scenes only)"""
+        ids = np.array(list(meshes_by_index.keys()), np.uint32)
+        descs, keep = _blas_descs(list(meshes_by_index.values()))
+        check(lib().crt_instances_replace_meshes(self._h, _ptr(ids), ids.shape[0], descs))
+        del keep
 
     def update_mesh(self, k, vertices):
         self.update_meshes({k: vertices})

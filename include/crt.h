@@ -526,6 +526,31 @@ int crt_instances_update_meshes_device(crt_instances* s, const uint32_t* mesh_id
 /* device ms and host wall ms of the last update (CRT_ERR_INVALID before the first one) and the device bytes the refit state holds
  * (filled for an updatable handle even then; 0 otherwise).  Any pointer may be NULL. */
 int crt_instances_last_update(crt_instances* s, float* device_ms, float* wall_ms, uint64_t* state_bytes);
+/* Changing which geometry a live handle holds.  Both calls are synchronous, may allocate and free device memory (they
+ * are not per-frame calls), build with the builder given at create, and leave the packed arrays as crt_instances_create lays them out
+ * for the resulting mesh list: the TLAS region, then the BLASes in mesh index order without gaps, child and triangle bases rebased;
+ * records likewise.  Each mesh is checked as create checks it, before any device work: non-null and non-empty, every vertex index in
+ * range, every referenced coordinate finite and within 1e18 (CRT_ERR_INVALID), fewer than 2^28 triangles (CRT_ERR_LIMIT).  A packed
+ * node or record array of 4 GiB or more, or TLAS depth + deepest BLAS beyond the walk's 40 entries, returns CRT_ERR_LIMIT.  All or
+ * nothing: after any refusal (CRT_ERR_NOMEM included) nothing the walk reads, no debug read and no crt_instances_get_info field other
+ * than the times has changed, and the previous geometry traces on bit for bit.  n == 0 is CRT_OK and changes nothing.  Hits after either
+ * call equal those of a fresh crt_instances_create from the resulting mesh list and the live instances (the minimum of (t, instance, id)
+ * does not depend on the tree), the grazing-margin exception above aside.  crt_instances_info's set_device_ms / set_wall_ms then
+ * describe the call.
+ *
+ * crt_instances_add_meshes appends n meshes; *first_id (may be NULL) receives the index of the first, the others follow.  Instances, the
+ * TLAS and every existing BLAS stay as they are and where they are: debug reads 0, 1, 2, 3 and 6 are byte for byte what they were, reads
+ * 4 and 5 keep their old content as a prefix, and every trace returns the same bits and per-ray stats.  The next set / refit may name
+ * the new meshes.  Any handle; an updatable one accepts the new meshes in crt_instances_update_meshes at once. */
+int crt_instances_add_meshes(crt_instances* s, const crt_blas_desc* meshes, uint32_t n, uint32_t* first_id);
+/* crt_instances_replace_meshes gives n DISTINCT existing meshes new geometry (vertex and triangle counts may differ from before): each
+ * listed BLAS is rebuilt from scratch (the remedy for a BLAS that crt_instances_update_meshes has deformed far from the placement its
+ * tree was built for), the meshes behind a resized one shift, the mesh boxes become those of the new geometry, and the live instances
+ * get new records (the new BLAS roots), new world boxes and a rebuilt TLAS as after crt_instances_update_meshes; instances, their masks
+ * and world_to_object stay.  CRT_INSTANCES_UPDATABLE handles only (the world boxes are recomputed from the live instances, which only
+ * such a handle keeps).  Also CRT_ERR_INVALID: a mesh index out of range or repeated, a null pointer, a handle without the flag, a
+ * world box beyond 1e18. */
+int crt_instances_replace_meshes(crt_instances* s, const uint32_t* mesh_ids, uint32_t n, const crt_blas_desc* meshes);
 /* test hook: which 0 = world_to_object (12 floats per instance, instance order), 1 = world boxes (6 floats: lo, hi), 2 = TLAS node8s
  * (80 B), 3 = instance records in TLAS leaf order (64 B: world_to_object rows, then BLAS root node, instance index, identity flag, mask & 0xff),
  * 4 = every BLAS node8 (80 B; the packed region after the TLAS region, bases rebased), 5 = every BLAS record (48 B), 6 = the TLAS child
