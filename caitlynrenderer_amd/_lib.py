@@ -74,6 +74,18 @@ class crt_instance(C.Structure):
     _fields_ = [("object_to_world", C.c_float * 12), ("mesh", C.c_uint32), ("mask", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class crt_mesh_shading(C.Structure):
+    _fields_ = [("triangles", C.c_void_p), ("n_triangles", C.c_size_t), ("normals", C.c_void_p), ("n_normals", C.c_size_t),
+                ("texcoords", C.c_void_p), ("n_texcoords", C.c_size_t)]
+
+
+class crt_instanced_scene_desc(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("instances", C.c_void_p), ("meshes", C.POINTER(crt_mesh_shading)), ("n_meshes", C.c_uint32),
+                ("materials", C.c_void_p), ("n_materials", C.c_size_t), ("lights", C.c_void_p), ("n_lights", C.c_size_t),
+                ("albedo_textures", C.c_void_p), ("tex_width", C.c_uint32), ("tex_height", C.c_uint32), ("n_textures", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("max_depth", C.c_uint32)]
+
+
 class crt_instances_info(C.Structure):
     _fields_ = [("n_meshes", C.c_uint32), ("n_instances", C.c_uint32), ("capacity", C.c_uint32), ("stack_entries", C.c_uint32),
                 ("tlas_nodes8", C.c_uint32), ("tlas_depth8", C.c_uint32), ("max_blas_depth8", C.c_uint32), ("stack_overflows", C.c_uint32),
@@ -121,6 +133,7 @@ SYMBOLS = {
     "crt_instances_replace_meshes": (_I, [_P, _P, _U32, _P]),
     "crt_instances_last_update": (_I, [_P, C.POINTER(_F), C.POINTER(_F), C.POINTER(C.c_uint64)]),
     "crt_instances_destroy": (_I, [_P]),
+    "crt_scene_create_instanced": (_I, [C.POINTER(crt_instanced_scene_desc), C.POINTER(_P)]),
     "crt_instance_inverse": (_I, [_P, _P]),
     "crt_instance_world_box": (_I, [_P, _P, _P]),
     "crt_debug_read_queue": (_I, [_P, _I, _U32, _P, _SZ, C.POINTER(_SZ)]),

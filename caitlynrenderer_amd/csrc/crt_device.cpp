@@ -25,6 +25,8 @@
 #include "host/cwbvh.hpp"
 #include "host/flatnode_link.hpp"
 #include "host/refit_core.hpp"
+#include "instances.hpp"
+#include "instances_bind.hpp"
 #include "rt_kernels.hpp"
 
 using crt::fail;
@@ -126,6 +128,12 @@ struct crt_scene {
     uint32_t bvh2_stack = 0;             // BVH2 depth + 2
     size_t n_vertices = 0, n_normals = 0, n_slots = 0;   // as created (n_slots: the leaf-order triangle array); crt_update_vertices checks against them
     RefitState* refit = nullptr;         // crt_update_vertices' state, from the first update on
+    // A scene whose geometry is a live crt_instances handle (crt_scene_create_instanced): BORROWED, and bound from create to
+    // destroy.  d_nodes / d_tris / d_planes stay null: a frame reads the handle's arrays as they are when it is enqueued.  d_triangles,
+    // d_normals and d_texcoords hold every mesh's arrays one after the other, d_mesh_base where each mesh's start.
+    crt_instances* inst = nullptr;
+    uint4* d_mesh_base = nullptr;        // per mesh: first triangle, first normal, first texcoord, 0
+    int32_t* d_qinst = nullptr;          // the hit instance of every entry of the path-ray queue (beside d_qhits)
 
     // shard + frame buffers
     uint32_t rank = 0, world = 1, tile = 16;   // 16x16: four waves per tile — fine enough for the cost-sorted schedule (1 M triangles: 0.273 ms at 64, 0.257 at 16)
@@ -299,12 +307,13 @@ struct crt_scene {
         drop_peers();
         hipSetDevice(device);
         if (stream) hipStreamSynchronize(stream);
+        if (inst) crt::instances_unbind(inst, stream);
         delete refit;
         if (shares_scene)                    // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
                         d_rays[0], d_rays[1], d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
-                        d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins};
+                        d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins, d_mesh_base, d_qinst};
         for (void* p : ptrs) if (p) hipFree(p);
         if (h_tile_cost) hipHostFree(h_tile_cost);
         if (h_tile_order) hipHostFree(h_tile_order);
@@ -409,7 +418,7 @@ int build_shard(crt_scene* s) {
 void free_frame_buffers(crt_scene* s) {
     void** ptrs[] = {(void**)&s->d_tile_xy, (void**)&s->d_tile_order, (void**)&s->d_tile_cost, (void**)&s->d_sum, (void**)&s->d_linear, (void**)&s->d_rgba, (void**)&s->d_rays[0],
                      (void**)&s->d_rays[1], (void**)&s->d_nee, (void**)&s->d_contrib, (void**)&s->d_nee_perm, (void**)&s->d_qhits, (void**)&s->pb.L, (void**)&s->pb.T, (void**)&s->pb.seed,
-                     (void**)&s->d_lfinal};
+                     (void**)&s->d_lfinal, (void**)&s->d_qinst};
     for (void** p : ptrs) { if (*p) hipFree(*p); *p = nullptr; }
     s->batch_cap = 1;
     s->defer_cap = s->defer_regions = s->defer_sub_capacity = s->lfinal_cap = 0;
@@ -453,7 +462,7 @@ int alloc_frame_buffers(crt_scene* s) {
     const size_t Q = 8 * (size_t)s->sub_capacity;
     // the deferred shadow rays' buffers (inplace_shadow 0 / 2) and the hit buffer of the bounce pools (bounce_refill = 1) are allocated
     // by the first frame that needs them
-    if (s->max_depth > 1) {                      // path state and ray queues exist only for multi-segment paths
+    if (s->max_depth > 1 || s->inst) {           // path state and ray queues exist only for multi-segment paths, and for the queue-fed frames of an instanced scene
         if ((rc = dev_alloc(&s->d_rays[0], 2 * Q))) return rc;
         if ((rc = dev_alloc(&s->d_rays[1], 2 * Q))) return rc;
         s->rays_doubled = false;
@@ -700,6 +709,113 @@ int crt_scene_create(const crt_scene_desc* d, crt_scene** out) {
     } catch (const std::exception& e) {
         if (out) *out = nullptr;
         return fail(CRT_ERR_NOMEM, std::string("crt_scene_create: ") + e.what());
+    }
+}
+
+// A scene whose geometry is a live crt_instances handle: the shading's copies of every mesh's triangles, normals and
+// texcoords, one mesh after the other with a per-mesh table of where each starts, and the binding.  Checks are crt_scene_create's, per mesh.
+static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_scene** out) {
+    const std::string who = "crt_scene_create_instanced: ";
+    if (!out) return fail(CRT_ERR_INVALID, who + "null out");
+    *out = nullptr;
+    if (!d) return fail(CRT_ERR_INVALID, who + "null desc");
+    if (d->abi_version != CRT_ABI_VERSION) return fail(CRT_ERR_INVALID, who + "abi_version mismatch");
+    if (!d->instances) return fail(CRT_ERR_INVALID, who + "null instances handle");
+    if (!d->meshes || d->n_meshes == 0) return fail(CRT_ERR_INVALID, who + "meshes missing");
+    if (!d->materials || d->n_materials == 0) return fail(CRT_ERR_INVALID, who + "materials missing");
+    if (d->n_lights && !d->lights) return fail(CRT_ERR_INVALID, who + "lights missing");
+    if (d->width == 0 || d->height == 0 || d->width > 65535u * 8u || d->height > 65535u * 8u) return fail(CRT_ERR_INVALID, who + "bad resolution");
+    if (d->max_depth == 0 || d->max_depth > 16) return fail(CRT_ERR_INVALID, who + "max_depth must be 1..16");
+    int rc = require_device();
+    if (rc) return rc;
+    crt::InstancesView v{};
+    crt::instances_view(d->instances, &v);
+    if (d->n_meshes != v.n_meshes)
+        return fail(CRT_ERR_INVALID, who + "n_meshes (" + std::to_string(d->n_meshes) + ") differs from the handle's mesh count (" + std::to_string(v.n_meshes) + ")");
+    const bool have_tex = d->albedo_textures && d->n_textures > 0;
+    if (have_tex && (d->tex_width == 0 || d->tex_height == 0 || d->tex_width > 16384 || d->tex_height > 16384)) return fail(CRT_ERR_INVALID, who + "bad texture size");
+    bool any_textured = false;
+    for (size_t m = 0; m < d->n_materials; ++m) {
+        const float tx = d->materials[m].tex_ind[0];
+        if (have_tex && tx != -1.0f) {
+            if (!(tx >= 0.0f && tx < (float)d->n_textures)) return fail(CRT_ERR_INVALID, who + "material texture index out of range");
+            any_textured = true;
+        }
+        const float ew = d->materials[m].emission[3];
+        if (ew != -1.0f && !(ew >= 0.0f && (size_t)ew < d->n_lights)) return fail(CRT_ERR_INVALID, who + "emissive material refers to a light that does not exist");
+    }
+    size_t n_tris = 0, n_normals = 0, n_texcoords = 0;
+    std::vector<uint4> base(d->n_meshes);
+    for (uint32_t k = 0; k < d->n_meshes; ++k) {
+        const crt_mesh_shading& m = d->meshes[k];
+        const std::string mesh = "mesh " + std::to_string(k) + ": ";
+        if (!m.triangles || m.n_triangles != crt::instances_mesh_triangles(d->instances, k))
+            return fail(CRT_ERR_INVALID, who + mesh + "n_triangles differs from the handle's mesh (or triangles is null)");
+        if ((m.n_normals && !m.normals) || (m.n_texcoords && !m.texcoords)) return fail(CRT_ERR_INVALID, who + mesh + "null normals / texcoords");
+        for (size_t i = 0; i < 3 * m.n_normals; ++i)
+            if (!std::isfinite(m.normals[i])) return fail(CRT_ERR_INVALID, who + mesh + "a normal is not finite");
+        for (size_t i = 0; i < m.n_triangles; ++i) {
+            const crt_triangle& t = m.triangles[i];
+            if (t.v[3] < 0 || (size_t)t.v[3] >= d->n_materials) return fail(CRT_ERR_INVALID, who + mesh + "material index out of range");
+            if (t.vn[3] != 0)
+                for (int j = 0; j < 3; ++j)
+                    if (t.vn[j] < 0 || (size_t)t.vn[j] >= m.n_normals) return fail(CRT_ERR_INVALID, who + mesh + "normal index out of range");
+            if (have_tex && d->materials[t.v[3]].tex_ind[0] != -1.0f)
+                for (int j = 0; j < 3; ++j)
+                    if (t.vt[j] < 0 || (size_t)t.vt[j] >= m.n_texcoords) return fail(CRT_ERR_INVALID, who + mesh + "texcoord index out of range");
+        }
+        base[k] = make_uint4((uint32_t)n_tris, (uint32_t)n_normals, (uint32_t)n_texcoords, 0u);
+        n_tris += m.n_triangles; n_normals += m.n_normals; n_texcoords += m.n_texcoords;
+    }
+    if (n_tris >= (1ull << 31) || n_normals >= (1ull << 31) || n_texcoords >= (1ull << 31)) return fail(CRT_ERR_LIMIT, who + "too many elements");
+    (void)any_textured;
+    HIPCHK(hipSetDevice(v.device));
+    std::unique_ptr<crt_scene> owner(new (std::nothrow) crt_scene);
+    crt_scene* s = owner.get();
+    if (!s) return fail(CRT_ERR_NOMEM, who + "out of memory");
+    crt_scene_desc common{};                 // what init_scene_common reads: the frame's scalars and the materials
+    common.width = d->width; common.height = d->height; common.max_depth = d->max_depth; common.n_lights = d->n_lights;
+    common.materials = d->materials; common.n_materials = d->n_materials; common.n_triangles = n_tris; common.n_normals = n_normals;
+    if ((rc = init_scene_common(s, &common))) return rc;
+    std::vector<crt_triangle> tris(n_tris);
+    std::vector<float> normals(3 * n_normals), texcoords(2 * n_texcoords);
+    for (uint32_t k = 0; k < d->n_meshes; ++k) {
+        const crt_mesh_shading& m = d->meshes[k];
+        std::copy(m.triangles, m.triangles + m.n_triangles, tris.begin() + base[k].x);
+        if (m.n_normals) std::copy(m.normals, m.normals + 3 * m.n_normals, normals.begin() + 3 * (size_t)base[k].y);
+        if (m.n_texcoords) std::copy(m.texcoords, m.texcoords + 2 * m.n_texcoords, texcoords.begin() + 2 * (size_t)base[k].z);
+    }
+    auto up = [&](auto** dst, const void* src, size_t count) -> int {
+        int r = dev_alloc(dst, count);
+        if (r) return r;
+        if (count && hipMemcpy(*dst, src, count * sizeof(**dst), hipMemcpyHostToDevice) != hipSuccess) return fail(CRT_ERR_HIP, "hipMemcpy H2D failed");
+        return CRT_OK;
+    };
+    if ((rc = up(&s->d_triangles, tris.data(), n_tris * 3)) || (rc = up(&s->d_normals, normals.data(), normals.size())) ||
+        (rc = up(&s->d_materials, d->materials, d->n_materials * 4)) || (rc = up(&s->d_lights, d->lights, d->n_lights * 18)) ||
+        (rc = up(&s->d_mesh_base, base.data(), base.size())))
+        return rc;
+    if (have_tex) {
+        const size_t n_tex = (size_t)d->tex_width * d->tex_height * d->n_textures * 3;
+        std::vector<float> texf(n_tex);
+        for (size_t i = 0; i < n_tex; ++i) texf[i] = (float)d->albedo_textures[i] / 255.0f;
+        if ((rc = up(&s->d_texcoords, texcoords.data(), n_texcoords)) || (rc = up(&s->d_textures, texf.data(), n_tex))) return rc;
+        s->tex_width = (int32_t)d->tex_width; s->tex_height = (int32_t)d->tex_height; s->n_textures = (int32_t)d->n_textures;
+    }
+    s->rows_padded = true;                   // no tree of its own
+    if ((rc = finish_scene_setup(s))) return rc;
+    if ((rc = crt::instances_bind(d->instances, s->stream))) return rc;
+    s->inst = d->instances;
+    *out = owner.release();
+    return CRT_OK;
+}
+
+int crt_scene_create_instanced(const crt_instanced_scene_desc* d, crt_scene** out) {
+    try {
+        return scene_create_instanced_impl(d, out);
+    } catch (const std::exception& e) {
+        if (out) *out = nullptr;
+        return fail(CRT_ERR_NOMEM, std::string("crt_scene_create_instanced: ") + e.what());
     }
 }
 
@@ -1085,6 +1201,16 @@ int crt_reset(crt_scene* s) {
 
 int crt_set_option(crt_scene* s, const char* name, int value) {
     if (!s || !name) return fail(CRT_ERR_INVALID, "crt_set_option: null argument");
+    if (s->inst) {
+        // an instanced scene: one stream, the two-level walk, no tile clock
+        if (!std::strcmp(name, "streams")) {
+            if (value != 0 && value != 1) return fail(CRT_ERR_INVALID, "crt_set_option: an instanced scene renders on one stream (streams is 0 or 1)");
+            return CRT_OK;
+        }
+        if (!std::strcmp(name, "accel") && value != 0)
+            return fail(CRT_ERR_INVALID, "crt_set_option: an instanced scene has no BVH2: its frames walk the handle's two-level CWBVH (accel is 0)");
+        if (!std::strcmp(name, "adaptive_tiles")) return CRT_OK;      // treated as 0: the per-tile clock lives in the fused first-segment kernel
+    }
     if (!std::strcmp(name, "jitter")) s->jitter = value ? 1u : 0u;
     else if (!std::strcmp(name, "count_visits")) { s->count_visits = value != 0; s->count_batched = value == 2; }
     else if (!std::strcmp(name, "bounce_refill")) s->bounce_refill = value ? 1u : 0u;
@@ -1193,6 +1319,7 @@ static bool uses_ray_bins(const crt_scene* s) {
 }
 // Segments [first, max_depth) defer their NEE shadow rays (option "inplace_shadow"); first = max_depth: none does.  BVH2 frames walk in place.
 static uint32_t first_deferred_segment(const crt_scene* s) {
+    if (s->inst) return 0u;                  // an instanced scene's frames defer every segment's shadow rays (k_shadow_instances_deferred)
     const uint32_t mode = s->inplace_shadow == 3u ? (s->info.n_nodes8 >= 64 ? 2u : 1u) : s->inplace_shadow;
     if (s->accel != 0u || mode == 1u) return s->max_depth;
     return mode == 0u ? 0u : std::min(1u, s->max_depth);
@@ -1246,7 +1373,8 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
     }
     // the hit buffer of the bounce pools (bounce_refill = 1): allocated by the first frame that needs it
     const size_t Q = 8 * (size_t)s->sub_capacity;
-    if (s->bounce_refill && s->max_depth > 1 && !s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
+    if (((s->bounce_refill && s->max_depth > 1) || s->inst) && !s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
+    if (s->inst && !s->d_qinst && (rc = dev_alloc(&s->d_qinst, Q))) return rc;
     if (uses_ray_bins(s)) {
         if (!s->d_bins) {
             if ((rc = dev_alloc(&s->d_bins, crt_scene::bins_words()))) return rc;
@@ -1267,12 +1395,92 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
     return CRT_OK;
 }
 
+// One frame of an instanced scene, buffers prepared: k_raygen, then per segment the two-level closest-hit walk over the
+// segment's queue and the shade-only pass, then ONE two-level any-hit launch for every segment's shadow rays and the fold — the
+// bounce_refill 1 + inplace_shadow 0 sequence below with segment 0 included.  The handle's live arrays are read HERE, at enqueue time.
+static int render_instanced_async(crt_scene* s, float rx, float ry) {
+    crt::InstancesView v{};
+    crt::instances_view(s->inst, &v);
+    const uint32_t P = s->n_local_pixels;
+    const size_t n_paths = P;
+    if (!s->timing_accumulate) s->n_spans = 0;
+    if (s->count_visits) HIPCHK(hipMemsetAsync(s->d_visit_totals, 0, 16 * sizeof(unsigned long long), s->stream));
+    s->bank ^= 1u;
+    if (!s->counts_clean) HIPCHK(hipMemsetAsync(s->d_counts, 0, 2 * kCounters * sizeof(uint32_t), s->stream));
+    s->counts_clean = false;
+    uint32_t* const cnt = s->counts();
+    // the instanced kernels carry no events of their own: a timed launch sits between two recorded events
+    auto timed = [&](int kind, auto&& enqueue) {
+        EventSpan* sp = s->new_span(kind);
+        if (sp) (void)hipEventRecord(sp->a, s->stream);
+        enqueue();
+        if (sp) (void)hipEventRecord(sp->b, s->stream);
+    };
+    crt::RaygenArgs ra{};
+    ra.f = frame_args(s, rx, ry);
+    ra.f.tile_order = nullptr;                      // the adaptive tile order belongs to the fused first-segment kernel
+    ra.rays = s->d_rays[0]; ra.count = cnt + counter_index(0, 0, 0); ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
+    ra.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; ra.n_zero = kCounters;
+    timed(0, [&] { crt::launch_raygen(ra, s->stream); });
+    for (uint32_t b = 0; b < s->max_depth; ++b) {
+        crt::InstQueueArgs qa{};
+        qa.nodes = v.nodes; qa.tris = v.tris; qa.inst = v.inst;
+        qa.rays = s->d_rays[b & 1]; qa.count = cnt + counter_index(b, 0, 0); qa.hits = s->d_qhits; qa.hit_inst = s->d_qinst;
+        qa.sub_capacity = s->sub_capacity; qa.n_instances = v.n_instances; qa.stack_entries = v.stack_entries;
+        qa.refill_min = 8; qa.tri_min = 2;          // crt_instances_trace's
+        qa.visit_totals = s->d_visit_totals; qa.overflow = s->d_overflow;
+        timed(1, [&] { crt::launch_closest_instances_queue(qa, s->count_visits, s->stream); });
+        crt::InstSegmentArgs sa{};
+        sa.triangles = s->d_triangles; sa.normals = s->d_normals; sa.materials = s->d_materials; sa.lights = s->d_lights; sa.n_lights = (int32_t)s->n_lights;
+        sa.stack_entries = 2;                       // the shade-only pass walks nothing
+        sa.texcoords = s->d_texcoords; sa.textures = s->d_textures;
+        sa.tex_width = s->tex_width; sa.tex_height = s->tex_height; sa.n_textures = s->n_textures;
+        sa.f = ra.f;
+        sa.sub_capacity = s->sub_capacity;
+        sa.rays_in = s->d_rays[b & 1]; sa.count_in = cnt + counter_index(b, 0, 0); sa.hits_in = s->d_qhits;
+        sa.rays_next = s->d_rays[(b + 1) & 1]; sa.count_next = cnt + counter_index(b + 1, 0, 0);
+        sa.count_shadow = cnt + counter_index(b, 1, 0);
+        sa.shadow = s->d_nee + 2 * (size_t)b * 8u * s->sub_capacity;      // region = segment: every segment defers
+        sa.contrib = s->d_contrib + (size_t)b * n_paths;
+        sa.slot_first = (uint32_t)((size_t)b * n_paths);
+        sa.slot_bit = 1u << (8u + b);
+        sa.pb = s->pb; sa.sum = s->d_sum;
+        sa.last_segment = (b + 1 == s->max_depth) ? 1u : 0u;
+        sa.visit_totals = s->d_visit_totals; sa.overflow = s->d_overflow;
+        sa.l_final = s->d_lfinal;
+        sa.n_samples = 1u; sa.rv_s[0] = rx * ry;
+        sa.hit_inst = s->d_qinst; sa.inst_w2o = v.w2o; sa.inst_mesh = v.mesh_of; sa.mesh_base = s->d_mesh_base;
+        timed(3, [&] { crt::launch_segment_instanced(sa, s->count_visits, s->trace_grid(P, 5), s->waves_per_workgroup, s->stream); });
+    }
+    crt::InstShadowArgs sh{};
+    sh.nodes = v.nodes; sh.tris = v.tris; sh.inst = v.inst;
+    sh.shadow = s->d_nee; sh.count = cnt + counter_index(0, 1, 0); sh.count_stride = counter_index(1, 1, 0) - counter_index(0, 1, 0);
+    sh.contrib = s->d_contrib; sh.n_slots = (uint32_t)(n_paths * s->max_depth);
+    sh.pools_per_region = (s->sub_capacity + 63u) / 64u; sh.n_regions = s->max_depth;
+    sh.sub_capacity = s->sub_capacity; sh.n_instances = v.n_instances; sh.stack_entries = v.stack_entries;
+    sh.refill_min = 8; sh.tri_min = 2;
+    sh.visit_totals = s->d_visit_totals ? s->d_visit_totals + 2 : nullptr; sh.overflow = s->d_overflow;
+    timed(2, [&] { crt::launch_shadow_instances_deferred(sh, s->count_visits, s->stream); });
+    crt::launch_fold_paths(s->d_sum, s->d_lfinal, s->d_contrib, P, 1u, 0u, s->stream);
+    if (s->count_visits)
+        HIPCHK(hipMemcpyAsync(s->h_visit_totals, s->d_visit_totals, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+    s->stats_counted = s->count_visits;
+    HIPCHK(hipGetLastError());
+    s->counts_clean = true;
+    s->stats_pending = true;
+    s->stats_from_frame = true;
+    s->samples_in_stats = 1;
+    s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0;
+    return CRT_OK;
+}
+
 static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs, const float* rys) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_render_frame: null scene");
     if (!s->have_camera) return fail(CRT_ERR_INVALID, "crt_render_frame: crt_set_camera was never called");
     int rc = prepare_batch(s, n_samples);            // sets the device; a no-op when render_batch_all has prepared every device already
     if (rc) return rc;
     if (s->n_local_pixels == 0) return CRT_OK;
+    if (s->inst) return render_instanced_async(s, rxs[0], rys[0]);      // one sample per launch chain (batch_limit)
     const uint32_t P = s->n_local_pixels;
     const bool batched_paths = n_samples > 1u && s->max_depth > 1u;
     const uint32_t first_deferred = first_deferred_segment(s);         // segments from here on leave their shadow rays to k_shadow_deferred
@@ -1651,6 +1859,12 @@ int crt_get_frame_stats(crt_scene* s, crt_frame_stats* out) {
 
 int crt_get_bvh_info(crt_scene* s, crt_bvh_info* out) {
     if (!s || !out) return fail(CRT_ERR_INVALID, "crt_get_bvh_info: null argument");
+    if (s->inst) {                           // the handle's live totals, as crt_instances_get_info reports them
+        crt::InstancesView v{};
+        crt::instances_view(s->inst, &v);
+        s->info.n_nodes8 = (uint64_t)v.tlas_nodes8 + v.blas_nodes8; s->info.n_tris8 = v.blas_tris;
+        s->info.max_depth8 = (uint64_t)v.tlas_depth8 + v.max_blas_depth8; s->info.built_on_device = 1;
+    }
     *out = s->info;
     return CRT_OK;
 }
@@ -1969,6 +2183,8 @@ static int replicate_scene(const crt_scene* src, int device, crt_scene** out) {
 // the caller's own shard (crt_set_shard) when option "streams" splits it over streams of one GPU: device k takes the tiles
 // base_rank + k * base_world, + n * base_world, ... of the Morton order, i.e. every n-th tile of that shard's list starting at its k-th
 int crt_set_devices(crt_scene* s, const int32_t* devices, uint32_t n_devices, uint32_t tile) {
+    if (s && s->inst && n_devices > 1)
+        return fail(CRT_ERR_INVALID, "crt_set_devices: an instanced scene renders on the one device its crt_instances handle lives on");
     const int rc = set_devices_of_shard(s, devices, n_devices, tile, 0u, 1u);
     if (rc == CRT_OK) { s->shard_rank = 0u; s->shard_world = 1u; }      // the devices divide the whole frame (a refused call changes nothing)
     return rc;
@@ -2159,6 +2375,7 @@ int crt_debug_launch_info(crt_scene* s, int32_t info[4]) {
 int crt_debug_time_graph(crt_scene* s, uint32_t n_frames, const float* rxy, uint32_t reps, float* ms_stream, float* ms_graph) {
     if (!s || !rxy || !ms_stream || !ms_graph || n_frames == 0 || (n_frames & 1u) || reps == 0)
         return fail(CRT_ERR_INVALID, "crt_debug_time_graph: bad argument (n_frames must be even: the counter banks alternate)");
+    if (s->inst) return fail(CRT_ERR_INVALID, "crt_debug_time_graph: not offered for an instanced scene");
     if (!s->peers.empty() || s->primary)
         return fail(CRT_ERR_INVALID, "crt_debug_time_graph: one stream only (option streams 1, no crt_set_devices): the capture records this scene's stream, not its peers'");
     HIPCHK(hipSetDevice(s->device));
@@ -2241,6 +2458,7 @@ int crt_debug_read_queue(crt_scene* s, int which, uint32_t segment, crt_ray* dst
 
 int crt_trace_device(crt_scene* s, const void* d_rays, size_t n, void* d_hits, int mode, void* d_stats, int sync) {
     if (!s || !d_rays || !d_hits) return fail(CRT_ERR_INVALID, "crt_trace_device: null argument");
+    if (s->inst) return fail(CRT_ERR_INVALID, "crt_trace_device: an instanced scene has no tree of its own: use crt_instances_trace_device on its handle");
     if (mode < 0 || mode > (CRT_TRACE_ANY | CRT_TRACE_BVH2 | CRT_TRACE_TIE_LOWEST_ID)) return fail(CRT_ERR_INVALID, "crt_trace_device: bad mode");
     const bool any_hit = (mode & CRT_TRACE_ANY) != 0;
     if (n >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_trace_device: too many rays for one launch");
@@ -2279,6 +2497,7 @@ int crt_trace_device(crt_scene* s, const void* d_rays, size_t n, void* d_hits, i
 
 int crt_trace(crt_scene* s, const crt_ray* rays, size_t n, crt_hit* hits, int mode, crt_ray_stats* stats) {
     if (!s || (n && (!rays || !hits))) return fail(CRT_ERR_INVALID, "crt_trace: null argument");
+    if (s->inst) return fail(CRT_ERR_INVALID, "crt_trace: an instanced scene has no tree of its own: use crt_instances_trace on its handle");
     HIPCHK(hipSetDevice(s->device));
     if (n == 0) return CRT_OK;
     if (n > s->t_cap) {
@@ -2346,6 +2565,7 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
                        const crt_light* lights, size_t n_lights, int sync) {
     const auto t_begin = std::chrono::steady_clock::now();
     if (!s || (!h_verts && !d_user)) return fail(CRT_ERR_INVALID, "crt_update_vertices: null argument");
+    if (s->inst) return fail(CRT_ERR_INVALID, "crt_update_vertices: an instanced scene's geometry belongs to its handle: use crt_instances_update_meshes");
     if (s->primary) return fail(CRT_ERR_INVALID, "crt_update_vertices: not on a replica");
     if (n_vertices != s->n_vertices) return fail(CRT_ERR_INVALID, "crt_update_vertices: n_vertices differs from the count given at create");
     if (normals && n_normals != s->n_normals) return fail(CRT_ERR_INVALID, "crt_update_vertices: n_normals differs from the count given at create");
@@ -2485,6 +2705,7 @@ int crt_last_update_ms(crt_scene* s, float* device_ms, float* wall_ms) {
 
 int crt_debug_read_accel(crt_scene* s, int which, void* dst, size_t cap_bytes, size_t* n_out) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_debug_read_accel: null scene");
+    if (s->inst) return fail(CRT_ERR_INVALID, "crt_debug_read_accel: an instanced scene has no tree of its own: use crt_instances_debug_read on its handle");
     const void* src = nullptr;
     size_t n = 0, item = 0, pitch = 0;
     switch (which) {

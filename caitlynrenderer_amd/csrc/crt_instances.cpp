@@ -22,6 +22,7 @@
 #include "host/instance_math.hpp"
 #include "host/refit_core.hpp"
 #include "instances.hpp"
+#include "instances_bind.hpp"
 #include "rt_kernels.hpp"
 
 using crt::fail;
@@ -84,6 +85,7 @@ struct crt_instances {
     float4* d_inst = nullptr;             // live instance records in TLAS leaf order (capacity x 4 rows)
     float* d_w2o = nullptr;               // live world_to_object, instance order (capacity x 12)
     float* d_wbox = nullptr;              // live world boxes, instance order (capacity x 6)
+    uint32_t* d_mesh_of = nullptr;        // live, instance order: mesh index, bit 31 = identity matrix (what a bound scene's shading reads)
     float* d_mesh_box = nullptr;          // 6 per mesh
     uint32_t* d_mesh_root = nullptr;      // BLAS root node per mesh
     // a set's staging: nothing here is read by the walk, so a refused set leaves the scene as it was
@@ -91,6 +93,7 @@ struct crt_instances {
     float4* d_rec = nullptr;              // records in instance order
     float* d_box = nullptr;
     float* d_w2o_stage = nullptr;
+    uint32_t* d_mesh_of_stage = nullptr;
     crt_node8* d_t8_stage = nullptr;      // the converter's output (tlas_cap_nodes)
     uint32_t* d_flag = nullptr;
     uint32_t* d_overflow = nullptr;
@@ -120,11 +123,14 @@ struct crt_instances {
     void* d_t_rays = nullptr; void* d_t_hits = nullptr; void* d_t_inst = nullptr; void* d_t_stats = nullptr;
     size_t t_cap = 0;
     std::unique_ptr<InstUpdateState> upd;     // CRT_INSTANCES_UPDATABLE only
+    // scenes that render this handle (crt_scene_create_instanced), by their streams: while there is one, every mutator
+    // first waits for them (wait_bound), and destroy / add_meshes / replace_meshes are refused
+    std::vector<hipStream_t> bound;
 
     ~crt_instances() {
         void* bufs[] = {d_nodes, d_tris, d_inst, d_w2o, d_wbox, d_mesh_box, d_mesh_root, d_in, d_rec, d_box, d_w2o_stage, d_flag, d_overflow,
                         d_t8_stage, d_t_rays, d_t_hits, d_t_inst, d_t_stats, d_tlas_order, d_tlas_box8, d_box_idx, d_tlas_table, d_cmask, d_cm_parent,
-                        d_cm_leaf};
+                        d_cm_leaf, d_mesh_of, d_mesh_of_stage};
         if (stream) (void)hipStreamSynchronize(stream);
         upd.reset();
         for (void* p : bufs) if (p) (void)hipFree(p);
@@ -205,12 +211,18 @@ struct TlasStage {
 struct MeshTables { const float* d_box; const uint32_t* d_root; uint32_t n_meshes, max_depth8; };
 MeshTables live_tables(const crt_instances* s) { return MeshTables{s->d_mesh_box, s->d_mesh_root, s->n_meshes, s->max_blas_depth8}; }
 
+// Before a mutator enqueues anything: the frames a bound scene has queued (crt_render_frame*_async) have read the live arrays
+int wait_bound(crt_instances* s) {
+    for (hipStream_t st : s->bound) IHIPCHK(hipStreamSynchronize(st));
+    return CRT_OK;
+}
+
 int prep_instances(crt_instances* s, const void* d_src, uint32_t n, const MeshTables& mt, const std::string& who) {
     hipStream_t st = s->stream;
     IHIPCHK(hipMemsetAsync(s->d_flag, 0, 4, st));
     crt::InstPrepArgs pa{};
     pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = mt.n_meshes; pa.mesh_box = mt.d_box; pa.mesh_root = mt.d_root;
-    pa.rec = s->d_rec; pa.box = s->d_box; pa.w2o = s->d_w2o_stage; pa.flag = s->d_flag;
+    pa.rec = s->d_rec; pa.box = s->d_box; pa.w2o = s->d_w2o_stage; pa.flag = s->d_flag; pa.mesh_of = s->d_mesh_of_stage;
     crt::launch_instance_prep(pa, st);
     uint32_t flag = 0;
     IHIPCHK(hipMemcpyAsync(&flag, s->d_flag, 4, hipMemcpyDeviceToHost, st));
@@ -260,6 +272,7 @@ int publish_tlas(crt_instances* s, const void* d_src, uint32_t n, const TlasStag
     crt::launch_gather_instances(s->d_rec, s->d_tri_order, s->d_tri_slots, n, s->d_inst, st);
     IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
     IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+    IHIPCHK(hipMemcpyAsync(s->d_mesh_of, s->d_mesh_of_stage, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     if (s->upd && d_src != s->upd->d_live)
         IHIPCHK(hipMemcpyAsync(s->upd->d_live, d_src, (size_t)n * sizeof(crt_instance), hipMemcpyDeviceToDevice, st));
     return CRT_OK;
@@ -270,6 +283,7 @@ int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
     const auto t0 = std::chrono::steady_clock::now();
     if (n > s->capacity) return fail(CRT_ERR_INVALID, "crt_instances_set: more instances than the capacity given at create");
     hipStream_t st = s->stream;
+    { const int wrc = wait_bound(s); if (wrc) return wrc; }
     IHIPCHK(hipEventRecord(s->ev0, st));
     if (n > 0) {
         TlasStage ts;
@@ -320,6 +334,7 @@ int refit_impl(crt_instances* s, const void* d_src, uint32_t n, const std::strin
     if (n != s->n_instances)
         return fail(CRT_ERR_INVALID, who + "n_instances (" + std::to_string(n) + ") differs from the live count (" + std::to_string(s->n_instances) + ")");
     hipStream_t st = s->stream;
+    { const int wrc = wait_bound(s); if (wrc) return wrc; }
     IHIPCHK(hipEventRecord(s->ev0, st));
     if (n > 0) {
         int rc = prep_instances(s, d_src, n, live_tables(s), who);
@@ -336,6 +351,7 @@ int refit_impl(crt_instances* s, const void* d_src, uint32_t n, const std::strin
         IHIPCHK(hipGetLastError());
         IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
         IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
+        IHIPCHK(hipMemcpyAsync(s->d_mesh_of, s->d_mesh_of_stage, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
         if (s->upd && d_src != s->upd->d_live)
             IHIPCHK(hipMemcpyAsync(s->upd->d_live, d_src, (size_t)n * sizeof(crt_instance), hipMemcpyDeviceToDevice, st));
     }
@@ -427,6 +443,7 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
     if (n == 0) return CRT_OK;
     IHIPCHK(hipSetDevice(s->device));
     hipStream_t st = s->stream;
+    { const int wrc = wait_bound(s); if (wrc) return wrc; }
     // the call's tables
     auto A = [](size_t b) { return (b + 15) & ~size_t(15); };
     const size_t o_chunk = A(n * sizeof(crt::RefitMesh)), o_rseg = o_chunk + A(n * 4), o_lseg = o_rseg + A(n * sizeof(crt::RefitSeg));
@@ -613,7 +630,8 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
         (rc = alloc(&s->d_rec, C * 4)) || (rc = alloc(&s->d_box, C * 6)) || (rc = alloc(&s->d_w2o_stage, C * 12)) || (rc = alloc(&s->d_flag, 1)) ||
         (rc = alloc(&s->d_overflow, 1)) || (rc = alloc(&s->d_t8_stage, s->tlas_cap_nodes)) || (rc = alloc(&s->d_tlas_box8, 6 * (size_t)s->tlas_cap_nodes)) ||
         (rc = alloc(&s->d_box_idx, C * 3)) || (rc = alloc(&s->d_tlas_table, sizeof(crt::RefitMesh) + 255 * sizeof(crt::RefitSeg))) ||
-        (rc = alloc(&s->d_cmask, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_parent, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_leaf, C)))
+        (rc = alloc(&s->d_cmask, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_parent, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_leaf, C)) ||
+        (rc = alloc(&s->d_mesh_of, C)) || (rc = alloc(&s->d_mesh_of_stage, C)))
         return rc;
     crt::launch_box_triples(s->d_box_idx, capacity, st);
     IHIPCHK(hipMemsetAsync(s->d_overflow, 0, 4, st));
@@ -669,6 +687,8 @@ struct Remesh {
 int remesh_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const crt_blas_desc* meshes, uint32_t* first_id, bool add, const std::string& who) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!s) return fail(CRT_ERR_INVALID, who + "null handle");
+    if (!s->bound.empty())
+        return fail(CRT_ERR_INVALID, who + "a scene renders this handle (crt_scene_create_instanced): its per-mesh shading tables would go stale; destroy the scene first");
     InstUpdateState* u = s->upd.get();
     if (!add && !u) return fail(CRT_ERR_INVALID, who + "the handle was created without CRT_INSTANCES_UPDATABLE");
     if (n && (!meshes || (!add && !ids))) return fail(CRT_ERR_INVALID, who + "null argument");
@@ -851,6 +871,24 @@ int remesh_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const crt_bla
 }
 
 }  // namespace
+
+namespace crt {
+
+void instances_view(const crt_instances* h, InstancesView* out) {
+    *out = InstancesView{h->device, h->d_nodes, h->d_tris, h->d_inst, h->d_w2o, h->d_mesh_of, h->n_instances, h->stack_entries, h->n_meshes,
+                         h->n_tlas8, h->tlas_depth8, h->max_blas_depth8, h->blas_nodes8, h->blas_tris};
+}
+uint32_t instances_mesh_triangles(const crt_instances* h, uint32_t mesh) { return h->mesh[mesh].n_tris; }
+int instances_bind(crt_instances* h, hipStream_t stream) {
+    try { h->bound.push_back(stream); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_scene_create_instanced: out of memory"); }
+    return CRT_OK;
+}
+void instances_unbind(crt_instances* h, hipStream_t stream) {
+    auto it = std::find(h->bound.begin(), h->bound.end(), stream);
+    if (it != h->bound.end()) h->bound.erase(it);
+}
+
+}  // namespace crt
 
 extern "C" {
 
@@ -1062,6 +1100,8 @@ int crt_instances_last_update(crt_instances* s, float* device_ms, float* wall_ms
 
 int crt_instances_destroy(crt_instances* s) {
     if (!s) return CRT_OK;
+    if (!s->bound.empty())
+        return fail(CRT_ERR_INVALID, "crt_instances_destroy: a scene renders this handle (crt_scene_create_instanced): destroy the scene first");
     (void)hipSetDevice(s->device);
     delete s;
     return CRT_OK;

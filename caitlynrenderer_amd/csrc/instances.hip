@@ -1,17 +1,14 @@
 // HIP kernels of instanced scenes (include/crt.h crt_instances_*): per-instance preparation (validation, inverse, world
-// box, record), the packing of the BLASes into one node array, and the two-level walk k_trace_instances.
-//
-// The walk is ONE loop with ONE stack per lane.  TLAS and BLAS nodes are the same node8 format in the same array, so a wave whose lanes
-// are at different levels still runs a single node step together.  A TLAS leaf's "triangles" are instances: the instance step pushes
-// what the lane still has pending at the TLAS level (inner hits, the rest of the leaf), then a return marker, moves the ray into object
-// space and continues at the BLAS root.  Popping the marker restores the world ray, which the lane keeps in registers.
-// The masked walk (MASK) culls TLAS children whose instances are all hidden from the ray and skips hidden instances.
+// box, record), the packing of the BLASes into one node array, and the kernels of the two-level walk (instances_walk.hpp,
+// instances_walk_loop.hpp): k_trace_instances for explicit rays, k_closest_instances_queue and k_shadow_instances_deferred for the frames
+// of an instanced scene.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
 #include "instances.hpp"
+#include "instances_walk.hpp"
 #include "rt_kernels.hpp"
 #include "rt_math.hpp"
 #include "rt_traverse.hpp"
@@ -44,6 +41,7 @@ __global__ void __launch_bounds__(256) k_instance_prep(InstPrepArgs a) {
                        __uint_as_float(src[13] & 0xffu));       // crt_instance.mask: bits 8..31 are ignored
     for (int k = 0; k < 6; ++k) a.box[6 * (size_t)i + k] = box[k];
     for (int k = 0; k < 12; ++k) a.w2o[12 * (size_t)i + k] = w[k];
+    a.mesh_of[i] = mesh | (instance_is_identity(m) ? 0x80000000u : 0u);
 }
 
 __global__ void __launch_bounds__(256) k_rebase_nodes(uint4* __restrict__ nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off) {
@@ -146,28 +144,8 @@ __global__ void __launch_bounds__(256) k_tlas_mask_up(const float4* __restrict__
     }
 }
 
-// the ray's mask against one TLAS node8's child masks: bit i set iff byte i of cm meets rmask (rmask <= 0xff)
-__device__ __forceinline__ uint32_t child_keep(uint2 cm, uint32_t rmask) {
-    const uint32_t r4 = rmask * 0x01010101u;
-    uint32_t lo = cm.x & r4, hi = cm.y & r4;
-    lo = (((lo & 0x7f7f7f7fu) + 0x7f7f7f7fu) | lo) & 0x80808080u;      // 0x80 in each non-zero byte, no carry between bytes
-    hi = (((hi & 0x7f7f7f7fu) + 0x7f7f7f7fu) | hi) & 0x80808080u;
-    // bits 0, 8, 16, 24 times 2^21 + 2^14 + 2^7 + 1 land on bits 21..24 without carries
-    return ((((lo >> 7) * 0x00204081u) >> 21) & 0xfu) | (((((hi >> 7) * 0x00204081u) >> 21) & 0xfu) << 4);
-}
-
-// direction-dependent part of a walk's ray: octant and clamped reciprocal (traverse() / walk_pool's prologue)
-__device__ __forceinline__ void ray_setup(vec3 d, vec3& inv, bool& negx, bool& negy, bool& negz, uint32_t& oct4) {
-    const vec3 dc = V3(clamp_dir(d.x), clamp_dir(d.y), clamp_dir(d.z));
-    negx = dc.x < 0.0f; negy = dc.y < 0.0f; negz = dc.z < 0.0f;
-    oct4 = (negx ? 0u : 0x04040404u) | (negy ? 0u : 0x02020202u) | (negz ? 0u : 0x01010101u);
-    inv = V3(rcp_ieee(dc.x), rcp_ieee(dc.y), rcp_ieee(dc.z));
-}
-
 // One lane per ray, pools of 64 rays per wave with lane refill (k_trace's mapping with crt_trace's default pool of 64: each 256-ray slot
-// of the index space is walked by four single-wave workgroups), one loop and one LDS stack over both levels.  Stack entries: a node group (top byte set), the rest of a TLAS leaf (low 24 bits only) or the return marker (y == 0).
-// MASK: the low 8 bits of the ray's pad word are its mask; a TLAS step culls the children whose child mask does not meet it, and the
-// instance step skips an instance whose mask does not, before it transforms the ray.  Without MASK every such test folds away.
+// of the index space is walked by four single-wave workgroups); the walk itself is instances_walk_loop.hpp.
 template <bool ANY, bool STATS, bool MASK>
 __global__ void __launch_bounds__(64) k_trace_instances(std::conditional_t<MASK, InstMaskTraceArgs, InstTraceArgs> a) {
     extern __shared__ uint2 s_lds[];          // [level][lane] of the workgroup's one wave
@@ -181,152 +159,81 @@ __global__ void __launch_bounds__(64) k_trace_instances(std::conditional_t<MASK,
         uint32_t next = dense_pool_first(v, wid.wave) + wid.sub * 64u;
         if (next >= a.n) continue;
         const uint32_t end = next + 64u < a.n ? next + 64u : a.n;
-        uint32_t idx = 0, nn = 0, nt = 0, inst_cur = 0, rmask = 0;
-        vec3 wo = V3(0.f, 0.f, 0.f), wd = V3(0.f, 0.f, 1.f), o = wo, d = wd, inv = V3(0.f, 0.f, 0.f);
-        bool negx = false, negy = false, negz = false, in_blas = false;
-        uint32_t oct4 = 0;
-        float best_t = 0.f, best_u = 0.f, best_v = 0.f;
-        int best_id = -1, best_inst = -1;
-        int sp = 0;
-        uint2 cur = make_uint2(0u, 0u), tg = make_uint2(0u, 0u);
-        for (;;) {
-            bool busy = tg.y != 0u || (cur.y & 0xff000000u) != 0u;
-            if (next < end) {
-                const unsigned long long idle = __ballot(!busy);
-                const uint32_t n_idle = (uint32_t)__builtin_popcountll(idle);
-                if (n_idle >= a.refill_min || n_idle == 64u) {
-                    const uint32_t got = end - next < n_idle ? end - next : n_idle;
-                    const uint32_t rank = (uint32_t)__builtin_popcountll(idle & ((1ull << lane) - 1ull));
-                    if (!busy && rank < got) {
-                        idx = next + rank;
-                        const float4 r0 = a.rays[2 * (size_t)idx], r1 = a.rays[2 * (size_t)idx + 1];
-                        wo = V3(r0.x, r0.y, r0.z); wd = V3(r1.x, r1.y, r1.z);
-                        if (MASK) rmask = __float_as_uint(r1.w) & 0xffu;
-                        o = wo; d = wd;
-                        best_t = r0.w; best_u = 0.f; best_v = 0.f; best_id = -1; best_inst = -1;
-                        nn = 0; nt = 0; sp = 0; in_blas = false;
-                        busy = true;
-                        // a non-finite origin hits nothing (traverse()); no instance: every ray misses
-                        const bool finite = __builtin_isfinite(o.x) && __builtin_isfinite(o.y) && __builtin_isfinite(o.z);
-                        ray_setup(d, inv, negx, negy, negz, oct4);
-                        cur = (finite && a.n_instances != 0u) ? make_uint2(0u, 0x80000000u) : make_uint2(0u, 0u);
-                        tg = make_uint2(0u, 0u);
-                    }
-                    next += got;
-                }
-            }
-            if (__ballot(busy) == 0ull) break;        // pool drained and every lane finished
-
-            // one step per iteration: a node step (TLAS or BLAS: the same code) or a leaf step (a triangle test, or entering an instance),
-            // with walk_pool's vote between the two
-            const bool has_tri = busy && tg.y != 0u;
-            const bool can_node = busy && !has_tri && (cur.y & 0xff000000u);
-            const uint32_t n_tri = (uint32_t)__builtin_popcountll(__ballot(has_tri));
-            const uint32_t n_node = (uint32_t)__builtin_popcountll(__ballot(can_node));
-            const bool node_phase = n_node != 0u && n_node >= a.tri_min * n_tri;
-            bool finished = false;
-            if (node_phase) {
-                if (can_node) {
-                    const uint32_t hits_imask = cur.y;
-                    const int off = 31 - __builtin_clz(hits_imask);
-                    const uint32_t nbase = cur.x;
-                    cur.y &= ~(1u << off);
-                    if (cur.y & 0xff000000u) { if (sp < stack_entries) { stk[sp * 64] = cur; ++sp; } else atomicAdd(a.overflow, 1u); }
-                    const uint32_t slot = (uint32_t)(off - 24) ^ (oct4 & 0xffu);
-                    const uint32_t nidx = nbase + (uint32_t)__builtin_popcount(hits_imask & ~(0xffffffffu << slot));
-                    const uint4* np = node_rows(a.nodes, nidx);
-                    const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3], n4 = np[4];
-                    if (STATS) ++nn;
-                    uint32_t keep = 0xffu;
-                    if constexpr (MASK) { if (nidx < a.n_tlas8) keep = child_keep(a.child_masks[nidx], rmask); }
-                    const uint32_t hitmask = node8_intersect(n0, n1, n2, n3, n4, o, inv, negx, negy, negz, oct4, best_t, keep);
-                    cur.x = n1.x;
-                    tg.x = n1.y;
-                    cur.y = (hitmask & 0xff000000u) | (n0.w >> 24);
-                    tg.y = hitmask & 0x00ffffffu;
-                }
-            } else if (has_tri) {
-                const int b = 31 - __builtin_clz(tg.y);
-                tg.y &= ~(1u << b);
-                const uint32_t ti = tg.x + (uint32_t)b;
-                if (in_blas) {
-                    const float4* tp = tri_rows(a.tris, ti);
-                    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
-                    if (STATS) ++nt;
-                    float u, vv, t;
-                    if (mt_test(ta, tb, tc, o, d, u, vv, t)) {
-                        if (ANY) {
-                            if (t < best_t) { best_inst = (int)inst_cur; finished = true; tg.y = 0u; }
-                        } else {
-                            // nearest t, then lowest instance, then lowest triangle id: independent of the order the TLAS hands out instances
-                            const int id = __float_as_int(ta.w);
-                            bool take = t < best_t;
-                            if (t == best_t && best_inst >= 0) take = (int)inst_cur < best_inst || ((int)inst_cur == best_inst && id < best_id);
-                            if (take) { best_t = t; best_u = u; best_v = vv; best_id = id; best_inst = (int)inst_cur; }
-                        }
-                    }
-                } else {
-                    // an instance: into its object space (fp32, no fma, direction not renormalised: t is the same parameter in both spaces)
-                    const float4* ip = a.inst + 4 * (size_t)ti;
-                    const float4 w0 = ip[0], w1 = ip[1], w2 = ip[2], w3 = ip[3];
-                    const bool visible = !MASK || (__float_as_uint(w3.w) & rmask) != 0u;      // a hidden instance: skipped untransformed
-                    vec3 oo = wo, od = wd;
-                    if (visible && __float_as_uint(w3.z) == 0u) {
-                        oo = V3(((w0.x * wo.x + w0.y * wo.y) + w0.z * wo.z) + w0.w, ((w1.x * wo.x + w1.y * wo.y) + w1.z * wo.z) + w1.w,
-                                ((w2.x * wo.x + w2.y * wo.y) + w2.z * wo.z) + w2.w);
-                        od = V3((w0.x * wd.x + w0.y * wd.y) + w0.z * wd.z, (w1.x * wd.x + w1.y * wd.y) + w1.z * wd.z, (w2.x * wd.x + w2.y * wd.y) + w2.z * wd.z);
-                    }
-                    // an object origin that is not finite hits nothing in this instance (traverse()): the instance is skipped
-                    if (visible && __builtin_isfinite(oo.x) && __builtin_isfinite(oo.y) && __builtin_isfinite(oo.z)) {
-                        const int need = ((cur.y & 0xff000000u) ? 1 : 0) + (tg.y ? 1 : 0) + 1;
-                        if (sp + need <= stack_entries) {
-                            if (cur.y & 0xff000000u) { stk[sp * 64] = cur; ++sp; }
-                            if (tg.y) { stk[sp * 64] = tg; ++sp; }
-                            stk[sp * 64] = make_uint2(0u, 0u);      // return marker
-                            ++sp;
-                            o = oo; d = od;
-                            ray_setup(d, inv, negx, negy, negz, oct4);
-                            in_blas = true;
-                            inst_cur = __float_as_uint(w3.y);
-                            cur = make_uint2(__float_as_uint(w3.x), 0x80000000u);
-                            tg = make_uint2(0u, 0u);
-                        } else {
-                            atomicAdd(a.overflow, 1u);
-                        }
-                    }
-                }
-            }
-            // a lane with neither a leaf group nor inner hits left pops its stack (through a return marker: back to the world ray), or is done
-            if (busy && !finished && tg.y == 0u && !(cur.y & 0xff000000u)) {
-                for (;;) {
-                    if (sp == 0) { finished = true; break; }
-                    --sp;
-                    const uint2 e = stk[sp * 64];
-                    if (e.y == 0u) {
-                        o = wo; d = wd;
-                        ray_setup(d, inv, negx, negy, negz, oct4);
-                        in_blas = false;
-                        continue;
-                    }
-                    if (e.y & 0xff000000u) cur = e;
-                    else { tg = e; cur = make_uint2(0u, 0u); }
-                    break;
-                }
-            }
-            if (finished) {
-                const bool hit = best_inst >= 0;
-                float4 h;
-                h.x = ANY ? 0.f : (hit ? best_t : 0.f);
-                h.y = ANY ? 0.f : best_u;
-                h.z = ANY ? 0.f : best_v;
-                h.w = __int_as_float(ANY ? (hit ? 0 : -1) : (hit ? best_id : -1));
-                a.hits[idx] = h;
-                if (a.inst_out) a.inst_out[idx] = hit ? best_inst : -1;
-                if (STATS) a.stats[idx] = ((nt > 65535u ? 65535u : nt) << 16) | (nn > 65535u ? 65535u : nn);
-                cur = make_uint2(0u, 0u); tg = make_uint2(0u, 0u); sp = 0; in_blas = false;
-            }
-        }
+#define CRT_WALK_LOAD(idx, r0, r1) const float4 r0 = a.rays[2 * (size_t)idx], r1 = a.rays[2 * (size_t)idx + 1];
+#define CRT_WALK_DONE(idx, h, hit, inst, nn, nt)                \
+            a.hits[idx] = h;                                    \
+            if (a.inst_out) a.inst_out[idx] = hit ? inst : -1;  \
+            if (STATS) a.stats[idx] = ((nt > 65535u ? 65535u : nt) << 16) | (nn > 65535u ? 65535u : nn);
+#include "instances_walk_loop.hpp"
+#undef CRT_WALK_LOAD
+#undef CRT_WALK_DONE
     }
+}
+
+// ---- the frame path of an instanced scene (crt_scene_create_instanced) ----
+
+// a wave's visit counts into the frame's totals: [0] += node steps, [1] += triangle tests
+__device__ __forceinline__ void flush_inst_totals(unsigned long long* totals, uint32_t nn, uint32_t nt) {
+    for (int off = 32; off > 0; off >>= 1) { nn += __shfl_down(nn, off); nt += __shfl_down(nt, off); }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (nn) atomicAdd(totals, (unsigned long long)nn);
+        if (nt) atomicAdd(totals + 1, (unsigned long long)nt);
+    }
+}
+
+// Closest hits of a segment's path-ray queue: workgroup (g, c) = one wave walks entries [64 c, 64 c + 64) of sub-queue g, as far as its
+// device-side count goes; hits and hit instances go to buffers parallel to the queue, and k_segment<PRETRACED, INST> shades them.
+template <bool STATS>
+__global__ void __launch_bounds__(64) k_closest_instances_queue(InstQueueArgs a) {
+    extern __shared__ uint2 s_lds[];          // [level][lane] of the workgroup's one wave
+    constexpr bool ANY = false, MASK = false;
+    const uint32_t lane = threadIdx.x & 63u, g = blockIdx.x & 7u, c = blockIdx.x >> 3;
+    const uint32_t cnt = a.count[g * CRT_COUNTER_STRIDE], n = cnt < a.sub_capacity ? cnt : a.sub_capacity;
+    if (c * 64u >= n) return;
+    uint32_t next = g * a.sub_capacity + c * 64u;
+    const uint32_t end = g * a.sub_capacity + (c * 64u + 64u < n ? c * 64u + 64u : n);
+    uint2* const stk = s_lds + lane;
+    const int stack_entries = (int)a.stack_entries;
+    uint32_t tn = 0, tt = 0;
+#define CRT_WALK_LOAD(idx, r0, r1) const float4 r0 = a.rays[2 * (size_t)idx], r1 = a.rays[2 * (size_t)idx + 1];
+#define CRT_WALK_DONE(idx, h, hit, inst, nn, nt) \
+            a.hits[idx] = h;                     \
+            a.hit_inst[idx] = hit ? inst : -1;   \
+            if (STATS) { tn += nn; tt += nt; }
+#include "instances_walk_loop.hpp"
+#undef CRT_WALK_LOAD
+#undef CRT_WALK_DONE
+    if (STATS) flush_inst_totals(a.visit_totals, tn, tt);
+}
+
+// The frame's deferred NEE shadow rays (k_shadow_deferred's queue layout: region r = segment, 8 sub-queues each, entry = (o, tmax)
+// (d, contribution slot)): workgroup (g, r, c) walks 64 entries; an OCCLUDED ray clears the visibility word of its contribution slot.
+template <bool STATS>
+__global__ void __launch_bounds__(64) k_shadow_instances_deferred(InstShadowArgs a) {
+    extern __shared__ uint2 s_lds[];
+    constexpr bool ANY = true, MASK = false;
+    const uint32_t lane = threadIdx.x & 63u, g = blockIdx.x & 7u, q = blockIdx.x >> 3;
+    const uint32_t r = q / a.pools_per_region, c = q - r * a.pools_per_region;
+    if (r >= a.n_regions) return;
+    const uint32_t cnt = a.count[(size_t)r * a.count_stride + g * CRT_COUNTER_STRIDE], n = cnt < a.sub_capacity ? cnt : a.sub_capacity;
+    if (c * 64u >= n) return;
+    const uint32_t qb = (r * 8u + g) * a.sub_capacity;
+    uint32_t next = qb + c * 64u;
+    const uint32_t end = qb + (c * 64u + 64u < n ? c * 64u + 64u : n);
+    uint2* const stk = s_lds + lane;
+    const int stack_entries = (int)a.stack_entries;
+    uint32_t tn = 0, tt = 0;
+#define CRT_WALK_LOAD(idx, r0, r1) const float4 r0 = a.shadow[2 * (size_t)idx], r1 = a.shadow[2 * (size_t)idx + 1];
+#define CRT_WALK_DONE(idx, h, hit, inst, nn, nt)                                              \
+            if (hit) {                                                                        \
+                const uint32_t slot = __float_as_uint(a.shadow[2 * (size_t)idx + 1].w);       \
+                if (slot < a.n_slots) reinterpret_cast<float*>(a.contrib + slot)[3] = 0.0f;   \
+            }                                                                                 \
+            if (STATS) { tn += nn; tt += nt; }
+#include "instances_walk_loop.hpp"
+#undef CRT_WALK_LOAD
+#undef CRT_WALK_DONE
+    if (STATS) flush_inst_totals(a.visit_totals, tn, tt);
 }
 
 static inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255u) / 256u)); }
@@ -375,6 +282,19 @@ void launch_trace_instances(const InstMaskTraceArgs& a, int any, bool stats, boo
     const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
     if (mask) launch_trace_instances_t<true>(a, any, stats, g, b, lds, stream);
     else      launch_trace_instances_t<false>(static_cast<const InstTraceArgs&>(a), any, stats, g, b, lds, stream);
+}
+
+void launch_closest_instances_queue(const InstQueueArgs& a, bool stats, hipStream_t stream) {
+    const dim3 g(8u * ((a.sub_capacity + 63u) / 64u)), b(64);
+    const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
+    if (stats) hipLaunchKernelGGL(k_closest_instances_queue<true>, g, b, lds, stream, a);
+    else       hipLaunchKernelGGL(k_closest_instances_queue<false>, g, b, lds, stream, a);
+}
+void launch_shadow_instances_deferred(const InstShadowArgs& a, bool stats, hipStream_t stream) {
+    const dim3 g(8u * a.n_regions * a.pools_per_region), b(64);
+    const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
+    if (stats) hipLaunchKernelGGL(k_shadow_instances_deferred<true>, g, b, lds, stream, a);
+    else       hipLaunchKernelGGL(k_shadow_instances_deferred<false>, g, b, lds, stream, a);
 }
 
 // crt_warmup: load this translation unit's code object on the current device (device_build.hpp)

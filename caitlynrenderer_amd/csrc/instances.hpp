@@ -37,6 +37,38 @@ struct InstPrepArgs {
     float* box;                // 6 floats per instance: world box
     float* w2o;                // 12 floats per instance: world_to_object
     uint32_t* flag;            // |= 1 matrix not finite / singular / inverse not finite, 2 mesh index out of range, 4 world box beyond 1e18
+    uint32_t* mesh_of;         // the instance's mesh index, bit 31 = the identity flag (what a frame's shading looks the hit triangle up by)
+};
+
+// The frame path of an instanced scene (crt_scene_create_instanced): the two-level walk fed by a frame's device-written
+// ray queues.  The member names the walk reads (instances_walk.hpp) are InstTraceArgs'.
+struct InstQueueArgs {         // k_closest_instances_queue: closest hits of a segment's path-ray queue
+    const uint4* nodes;
+    const float4* tris;
+    const float4* inst;
+    const uint2* child_masks;  // what a masked walk would read: frames do not mask (out of scope), null / 0
+    uint32_t n_tlas8;
+    const float4* rays;        // 8 sub-queues of crt_ray, sub_capacity entries each
+    const uint32_t* count;     // 8 device-side counts, CRT_COUNTER_STRIDE apart
+    float4* hits;              // parallel to the queue: (t, u, v, triangle id within the hit instance's mesh)
+    int32_t* hit_inst;         // parallel to the queue: the hit's instance, -1 = miss
+    uint32_t sub_capacity, n_instances, stack_entries, refill_min, tri_min;
+    unsigned long long* visit_totals;   // counting frames: [0] += node steps, [1] += triangle tests
+    uint32_t* overflow;
+};
+struct InstShadowArgs {        // k_shadow_instances_deferred: the frame's deferred NEE shadow rays, every segment's in one launch
+    const uint4* nodes;
+    const float4* tris;
+    const float4* inst;
+    const uint2* child_masks;  // as InstQueueArgs: null / 0
+    uint32_t n_tlas8;
+    const float4* shadow;      // [region][8 sub-queues][sub_capacity] x 2 float4: (o, tmax) (d, contribution slot)
+    const uint32_t* count;     // region r, group g: count[r * count_stride + g * CRT_COUNTER_STRIDE]
+    float4* contrib;           // n_slots contribution slots; an occluded ray clears its slot's visibility word
+    uint32_t n_slots, count_stride, pools_per_region, n_regions;
+    uint32_t sub_capacity, n_instances, stack_entries, refill_min, tri_min;
+    unsigned long long* visit_totals;
+    uint32_t* overflow;
 };
 
 void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream);
@@ -60,5 +92,8 @@ void launch_tlas_child_masks(const void* d_nodes, uint32_t n8, const float4* d_i
                              uint2* d_child_masks, hipStream_t stream);
 // `chunks`: 1024-ray chunks of the dense index space (k_trace's mapping), a multiple of 8; mask: CRT_TRACE_INSTANCE_MASK walk
 void launch_trace_instances(const InstMaskTraceArgs& a, int any, bool stats, bool mask, uint32_t chunks, hipStream_t stream);
+// one single-wave workgroup per 64 entries a sub-queue can hold; LDS = stack_entries x 512 B
+void launch_closest_instances_queue(const InstQueueArgs& a, bool stats, hipStream_t stream);
+void launch_shadow_instances_deferred(const InstShadowArgs& a, bool stats, hipStream_t stream);
 
 }  // namespace crt

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+
+#include <type_traits>
 #include <stdlib.h>
 
 #include <algorithm>
@@ -1225,6 +1227,33 @@ __device__ __forceinline__ vec3 disney_sample(const Disney& m, vec3 n, vec3 wo, 
     return (ou * dl.x + ov * dl.y) + n * dl.z;
 }
 
+// The primary ray of pixel (px, py) and the shader's RNG state behind its jitter draws (path_trace.fs:1026-1047) for k_raygen (the frames of
+// an instanced scene): k_segment<FIRST>'s own lines, restated operation for operation.  The first-segment kernels keep their text: calling
+// this function from them changed the registers and the order of nine of them ("assembly"), the headline's launch among them.
+__device__ __forceinline__ void primary_ray(const FrameArgs& f, uint32_t px, uint32_t py, float rv, float& sx, float& sy, vec3& o, vec3& d) {
+    sx = (float)px + 0.5f; sy = (float)py + 0.5f;
+    const float W = (float)here(f.width), H = (float)here(f.height);
+    float jx = 0.f, jy = 0.f;
+    if (f.jitter) {
+        const float r1 = 2.0f * shader_rand(sx, sy, rv);
+        const float r2 = 2.0f * shader_rand(sx, sy, rv);
+        jx = r1 < 1.0f ? sqrt_ieee(r1) - 1.0f : 1.0f - sqrt_ieee(2.0f - r1);
+        jy = r2 < 1.0f ? sqrt_ieee(r2) - 1.0f : 1.0f - sqrt_ieee(2.0f - r2);
+        jx = __fdiv_rn(jx, W * 0.5f);
+        jy = __fdiv_rn(jy, H * 0.5f);
+    }
+    const float tx = __fdiv_rn((float)px + 0.5f, W), ty = __fdiv_rn((float)py + 0.5f, H);
+    float dx = (2.0f * tx - 1.0f) + jx;
+    float dy = (2.0f * ty - 1.0f) + jy;
+    dx = dx * f.aspect_tan;                         // (W / H * tan(fov/2)), formed on the host like the oracle does
+    dy = dy * f.tan_fov;
+    const vec3 right = V3(f.cam_right[0], f.cam_right[1], f.cam_right[2]);
+    const vec3 up = V3(f.cam_up[0], f.cam_up[1], f.cam_up[2]);
+    const vec3 fwd = V3(f.cam_forward[0], f.cam_forward[1], f.cam_forward[2]);
+    d = normalize((right * dx + up * dy) + fwd);
+    o = V3(f.cam_pos[0], f.cam_pos[1], f.cam_pos[2]);
+}
+
 // ------------------------------------------------------------------ path segment -----
 // The kernel's argument block through the kernarg segment pointer, passed through an empty asm statement: a member read through the
 // result is a scalar load placed where it is written (the compiler cannot hoist it above the statement), not one of the loads the
@@ -1291,8 +1320,12 @@ __device__ __forceinline__ KArgs kernarg_here() {
 // BVH2 (in place only): the closest-hit and the shadow walk are the shipped shader's own BVH2 walks (path_trace.fs:511-819, traverse_bvh2)
 // on the FlatNode array — the live path of the reference as a frame renderer.
 // BATCH (FIRST + INPLACE): a.n_samples samples per pixel in one launch (crt_render_frames), see the sample loop.  WIDE / ONE: see below.
-template <bool FIRST, bool STATS, bool TEX, bool PRETRACED, bool INPLACE, bool BVH2 = false, bool MAT = false, bool BATCH = false, bool WIDE = false, bool ONE = false>
-__global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_FIRST : (BATCH || STATS) ? CRT_SEG_OCC_BATCH : (!FIRST && !INPLACE && !PRETRACED) ? CRT_SEG_OCC_DEFERRED : CRT_SEG_OCC)) k_segment(SegmentArgs a) {
+// INST (PRETRACED, !INPLACE, !FIRST): the frames of an instanced scene.  The hit came from k_closest_instances_queue as
+// (instance, triangle id within the instance's mesh): the triangle, its normals and its texcoords are looked up through the instance's
+// mesh, and the object-space normal is taken to world space by the inverse transpose of the instance's matrix, rescaled to its own length.
+template <bool FIRST, bool STATS, bool TEX, bool PRETRACED, bool INPLACE, bool BVH2 = false, bool MAT = false, bool BATCH = false, bool WIDE = false, bool ONE = false,
+          bool INST = false>
+__global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_FIRST : (BATCH || STATS) ? CRT_SEG_OCC_BATCH : (!FIRST && !INPLACE && !PRETRACED) ? CRT_SEG_OCC_DEFERRED : CRT_SEG_OCC)) k_segment(std::conditional_t<INST, InstSegmentArgs, SegmentArgs> a) {
     extern __shared__ uint2 s_lds[];     // traversal stacks [wave][level][lane]
     // Uniform node steps are compiled into every first-segment kernel.  (In the single-sample kernel they lost while the uniform step still
     // converted bytes and the loops carried their flags — 8 x 8-pixel waves agree less than the 4 x 4-pixel waves of a batched launch, and the
@@ -1492,9 +1525,21 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
             if (STATS) ++n_hits;
             const float t = hit.t, bu = hit.u, bv = hit.v;
             const size_t rec_rows = BVH2 ? 3u : (size_t)CRT_TRI_ROWS;            // the BVH2 walk's slot-ordered records stay packed
-            const float4 tb = recs[rec_rows * (size_t)hit.tri + 1], tc = recs[rec_rows * (size_t)hit.tri + 2];
-            const int slot = __float_as_int(tb.w), mtl = __float_as_int(tc.w);
-            const int4 vn = ka->triangles[3 * (size_t)slot + 1];                    // path_trace.fs:440-454
+            int slot, mtl;
+            uint32_t inst_word = 0u, inst_id = 0u, normal0 = 0u, texcoord0 = 0u;   // INST: (identity flag | mesh) of the hit instance, and its mesh's places in the scene's arrays
+            if constexpr (INST) {
+                inst_id = (uint32_t)a.hit_inst[(size_t)g * ka->sub_capacity + e];
+                inst_word = a.inst_mesh[inst_id];
+                const uint4 mb = a.mesh_base[inst_word & 0x7fffffffu];
+                slot = (int)mb.x + hit.tri;                                         // hit.tri: the triangle's id within its mesh = its index in the mesh's source-order triangles
+                mtl = ka->triangles[3 * (size_t)slot].w;
+                normal0 = mb.y; texcoord0 = mb.z;
+            } else {
+                const float4 tb = recs[rec_rows * (size_t)hit.tri + 1], tc = recs[rec_rows * (size_t)hit.tri + 2];
+                slot = __float_as_int(tb.w); mtl = __float_as_int(tc.w);
+            }
+            int4 vn = ka->triangles[3 * (size_t)slot + 1];                          // path_trace.fs:440-454
+            if constexpr (INST) { if (vn.w != 0) { vn.x += (int)normal0; vn.y += (int)normal0; vn.z += (int)normal0; } }
             vec3 n;
             if (vn.w == 0) n = V3((float)vn.x, (float)vn.y, (float)vn.z);
             else {
@@ -1504,6 +1549,17 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                 const vec3 nc = V3(N[3 * (size_t)vn.z], N[3 * (size_t)vn.z + 1], N[3 * (size_t)vn.z + 2]);
                 const float w = 1.0f - bu - bv;
                 n = (na * w + nb * bu) + nc * bv;
+            }
+            if constexpr (INST) {
+                // world normal = (inverse transpose of A) n_obj, i.e. the COLUMNS of world_to_object's rows W_r dotted with n_obj, rescaled to
+                // |n_obj|: a shading normal keeps its file's length whatever the instance's scale, as in a flat scene (include/crt.h, item 4)
+                if ((inst_word & 0x80000000u) == 0u) {
+                    const float* W = a.inst_w2o + 12 * (size_t)inst_id;
+                    vec3 m = V3((W[0] * n.x + W[4] * n.y) + W[8] * n.z, (W[1] * n.x + W[5] * n.y) + W[9] * n.z, (W[2] * n.x + W[6] * n.y) + W[10] * n.z);
+                    const float ln = sqrt_ieee((n.x * n.x + n.y * n.y) + n.z * n.z), lm = sqrt_ieee((m.x * m.x + m.y * m.y) + m.z * m.z);
+                    if (lm != 0.0f && __builtin_isfinite(lm)) m = m * __fdiv_rn(ln, lm);
+                    n = m;
+                }
             }
             const float4 m_albedo = ka->materials[4 * (size_t)mtl], m_emission = ka->materials[4 * (size_t)mtl + 1],
                          m_specular = ka->materials[4 * (size_t)mtl + 2];
@@ -1533,7 +1589,8 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                 if (TEX) {                                                        // path_trace.fs:471-483
                     const float tex = ka->materials[4 * (size_t)mtl + 3].x;
                     if (tex != -1.0f && ka->textures != nullptr) {
-                        const int4 vt = ka->triangles[3 * (size_t)slot + 2];
+                        int4 vt = ka->triangles[3 * (size_t)slot + 2];
+                        if constexpr (INST) { vt.x += (int)texcoord0; vt.y += (int)texcoord0; vt.z += (int)texcoord0; }
                         const float2 ta = ka->texcoords[vt.x], tb2 = ka->texcoords[vt.y], tc2 = ka->texcoords[vt.z];
                         const float w = 1.0f - bu - bv;
                         const float tu = (ta.x * w + tb2.x * bu) + tc2.x * bv;
@@ -1768,6 +1825,31 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
     if (STATS) flush_visit_totals(a.visit_totals + 8, n_hits, 0u);
     if (STATS) flush_visit_totals(a.visit_totals + 10, nu, nu_any);
     (void)stk; (void)stk2;
+}
+
+// Segment 0 of an instanced scene's frame: one lane per local pixel, in the storage order of the packed sum (pixel_of).  The
+// primary ray goes to the segment's sub-queue of the pixel's unit of 4096 (group = unit & 7, as every dense index space is dealt), payload =
+// path = local pixel, and the path state starts as k_segment<FIRST> starts it: L = 0, T = 1, prev_pdf = 1, the specular flag, the RNG state
+// behind the two jitter draws.  The segment itself then runs as a queue-fed one.
+__global__ void __launch_bounds__(256) k_raygen(RaygenArgs a) {
+    if (a.zero_counts && blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < a.n_zero; i += blockDim.x) a.zero_counts[i] = 0u;
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t g = (e >> 12) & 7u;                     // uniform over the workgroup: 256 divides 4096
+    uint32_t px = 0, py = 0;
+    const bool active = e < a.f.n_local_pixels && pixel_of(a.f, e, px, py);
+    float sx = 0.f, sy = 0.f;
+    vec3 o = V3(0.f, 0.f, 0.f), d = V3(0.f, 0.f, 1.f);
+    if (active) primary_ray(a.f, px, py, a.f.rv, sx, sy, o, d);
+    const uint32_t ni = wave_append(active, a.count + g * CRT_COUNTER_STRIDE);
+    if (active && ni < a.sub_capacity) {
+        float4* const q = a.rays + 2 * ((size_t)g * a.sub_capacity + ni);
+        q[0] = make_float4(o.x, o.y, o.z, CRT_INF);
+        q[1] = make_float4(d.x, d.y, d.z, __uint_as_float(e));
+        a.pb.L[e] = make_float4(0.f, 0.f, 0.f, 1.0f);
+        a.pb.T[e] = make_float4(1.f, 1.f, 1.f, __uint_as_float(1u));
+        a.pb.seed[e] = make_float2(sx, sy);
+    }
 }
 
 // Closest hit for a device-written path-ray queue (segments >= 1; option bounce_refill): lane refill (walk_pool: a finished lane takes the
@@ -2063,6 +2145,17 @@ int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplac
     return 0;
 }
 #undef CRT_K
+void launch_raygen(const RaygenArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_raygen, dim3((a.f.n_local_pixels + 255u) / 256u), dim3(256), 0, stream, a);
+}
+// the full feature level, like the other shade-only forms (the branches are decided per material at run time)
+void launch_segment_instanced(const InstSegmentArgs& a, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream) {
+    waves = fit_waves(waves, stack_bytes(a.stack_entries));
+    const dim3 g = grid_dim(grid, waves), b = block_dim(waves);
+    const size_t lds = waves * stack_bytes(a.stack_entries);
+    if (stats) launch(k_segment<false, true, true, true, false, false, true, false, false, false, true>, g, b, lds, stream, a);
+    else       launch(k_segment<false, false, true, true, false, false, true, false, false, false, true>, g, b, lds, stream, a);
+}
 // grid: 8 x (pools a sub-queue can hold) single-wave workgroups, a pool beyond its sub-queue's count returns at once; persistent: `grid_waves`
 // workgroups (a multiple of 8), as many as the chip holds
 void launch_closest_queue(const QueueTraceArgs& a, bool stats, uint32_t grid_waves, hipStream_t stream) {

@@ -157,6 +157,24 @@ struct SegmentArgs {
     const uint32_t* bin_off_in;
     uint32_t ovf_base_in;
 };
+// k_segment<INST>, the frames of an instanced scene.  A type of its own, so that every other k_segment keeps its argument
+// block (the hidden arguments lie behind it), and with it its code, exactly as before.
+struct InstSegmentArgs : SegmentArgs {
+    const int32_t* hit_inst;   // parallel to hits_in: the hit's instance (hits_in's w = the triangle's id within that instance's mesh)
+    const float* inst_w2o;     // world_to_object, 12 floats per instance, instance order (the handle's live array)
+    const uint32_t* inst_mesh; // per instance: its mesh index, bit 31 = its matrix is bitwise the identity
+    const uint4* mesh_base;    // per mesh: its first triangle (triangles), first normal (normals), first texcoord (texcoords), 0
+};
+
+struct RaygenArgs {            // k_raygen: segment 0's path-ray queue and path state of an instanced scene's frame
+    FrameArgs f;
+    float4* rays;              // 8 sub-queues of crt_ray, payload = path = local pixel
+    uint32_t* count;           // their 8 counters, CRT_COUNTER_STRIDE apart, zero at launch
+    uint32_t sub_capacity;
+    PathBuffers pb;
+    uint32_t* zero_counts;     // the other frame's counter bank, cleared here as k_segment<FIRST> does
+    uint32_t n_zero;
+};
 
 struct QueueTraceArgs {        // k_closest_queue: closest hit for a device-written path-ray queue
     const uint4* nodes;
@@ -217,6 +235,9 @@ void launch_trace_bvh2(const Bvh2Args& a, int any, bool stats, uint32_t grid, ui
 // inplace_shadow: the NEE shadow rays are walked inside the kernel; false = deferred to the frame's k_shadow_deferred launch
 // returns bit 0: the launch ran the 6-waves-per-SIMD (WIDE) build of the first-segment kernel, bit 1: a one-pass (ONE) build
 int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplace_shadow, bool bvh2, bool mat, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);
+// the frames of an instanced scene: ray generation, and the shade-only pass behind k_closest_instances_queue (shadow rays deferred)
+void launch_raygen(const RaygenArgs& a, hipStream_t stream);
+void launch_segment_instanced(const InstSegmentArgs& a, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);
 void launch_closest_queue(const QueueTraceArgs& a, bool stats, uint32_t grid_waves, hipStream_t stream);
 void launch_shadow_deferred(const ShadowArgs& a, bool stats, uint32_t grid_waves, hipStream_t stream);
 void launch_nee_sort(const NeeSortArgs& a, uint32_t blocks, hipStream_t stream);

@@ -2,15 +2,16 @@
 is rebuilt on the device at every `set` (include/crt.h crt_instances_*) or refitted in place by `refit`, which moves the
 instances and keeps the TLAS's topology (§13).  An updatable scene also moves the vertices of its meshes: a GPU refit of their BLASes and a
 TLAS rebuild per update.  Instances carry 8-bit visibility masks that a masked trace ANDs with each ray's (§14).  Meshes
-can be appended to a live scene and, in an updatable one, replaced by new geometry (§15).  Ray queries only: no frames."""
+can be appended to a live scene and, in an updatable one, replaced by new geometry (§15).  The handle answers ray queries; `frame_scene`
+returns a Scene that renders frames of it (§16)."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import (CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_INSTANCES_UPDATABLE, CRT_TRACE_CLOSEST, CRT_TRACE_INSTANCE_MASK,
-                   check, crt_blas_desc, crt_instances_info, lib)
-from .host import _ptr
-from .scene import HIT_DT, RAY_DT, STATS_DT
+from ._lib import (CRT_ABI_VERSION, CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_INSTANCES_UPDATABLE, CRT_TRACE_CLOSEST,
+                   CRT_TRACE_INSTANCE_MASK, check, crt_blas_desc, crt_instanced_scene_desc, crt_instances_info, crt_mesh_shading, lib)
+from .host import Rnd, _ptr
+from .scene import HIT_DT, RAY_DT, STATS_DT, Scene
 
 INSTANCE_DT = np.dtype([("object_to_world", "<f4", 12), ("mesh", "<u4"), ("mask", "<u4"), ("reserved", "<u4", 2)])      # crt_instance, 64 B
 
@@ -203,6 +204,47 @@ class InstancedScene:
         stale)"""
         return self._read(6, np.uint8, 8)
 
+    def frame_scene(self, shading, materials, lights, width, height, max_depth=3, textures=None):
+        """A Scene that renders frames of this handle's LIVE instances (crt_scene_create_instanced): every Scene method works
+        on it, and a set / refit / update_meshes between frames changes what the next frame sees (call reset()).  shading: per mesh, in mesh
+        order, (triangles (n, 12) int32 in source order [, normals (k, 3) [, texcoords (k, 2)]]) or an object with those attributes;
+        materials (m, 16) float32, lights (l, 18) float32 in WORLD space, textures (layers, H, W, 3) uint8 or None.  Close the returned scene
+        before this handle: destroy, add_meshes and replace_meshes are refused while it lives."""
+        keep = []
+
+        def arr(a, dtype, shape):
+            a = np.ascontiguousarray(a if a is not None else np.zeros((0,) + shape[1:]), dtype=dtype).reshape(shape)
+            keep.append(a)
+            return a
+
+        descs = (crt_mesh_shading * max(len(shading), 1))()
+        for k, m in enumerate(shading):
+            if hasattr(m, "triangles"):
+                m = (m.triangles, getattr(m, "normals", None), getattr(m, "texcoords", None))
+            m = tuple(m) + (None,) * (3 - len(m))
+            t, n, uv = arr(m[0], np.int32, (-1, 12)), arr(m[1], np.float32, (-1, 3)), arr(m[2], np.float32, (-1, 2))
+            descs[k].triangles, descs[k].n_triangles = _ptr(t), t.shape[0]
+            descs[k].normals, descs[k].n_normals = (_ptr(n) if n.shape[0] else None), n.shape[0]
+            descs[k].texcoords, descs[k].n_texcoords = (_ptr(uv) if uv.shape[0] else None), uv.shape[0]
+        d = crt_instanced_scene_desc()
+        d.abi_version, d.instances, d.meshes, d.n_meshes = CRT_ABI_VERSION, self._h, descs, len(shading)
+        mt, lt = arr(materials, np.float32, (-1, 16)), arr(lights, np.float32, (-1, 18))
+        d.materials, d.n_materials = _ptr(mt), mt.shape[0]
+        d.lights, d.n_lights = (_ptr(lt) if lt.shape[0] else None), lt.shape[0]
+        if textures is not None:
+            tex = np.ascontiguousarray(textures, np.uint8)
+            assert tex.ndim == 4 and tex.shape[3] == 3, "textures must be (layers, H, W, 3) uint8"
+            keep.append(tex)
+            d.albedo_textures, d.n_textures, d.tex_height, d.tex_width = _ptr(tex), tex.shape[0], tex.shape[1], tex.shape[2]
+        d.width, d.height, d.max_depth = int(width), int(height), int(max_depth)
+        sc = Scene.__new__(Scene)
+        sc._h = C.c_void_p()
+        sc.width, sc.height, sc.max_depth, sc.frame_count, sc.rnd, sc.create_ms = int(width), int(height), int(max_depth), 0, Rnd(), 0.0
+        check(lib().crt_scene_create_instanced(C.byref(d), C.byref(sc._h)))
+        sc._instances = self                       # the handle must outlive the scene
+        del keep
+        return sc
+
     def info(self):
         st = crt_instances_info()
         check(lib().crt_instances_get_info(self._h, C.byref(st)))
@@ -210,7 +252,7 @@ class InstancedScene:
 
     def close(self):
         if self._h:
-            lib().crt_instances_destroy(self._h)
+            check(lib().crt_instances_destroy(self._h))       # refused while a frame_scene lives: the handle then stays open
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -411,7 +411,8 @@ int crt_has_experiments(void);
 /* ------------------------------------------- instanced scenes (needs GPU) -- */
 
 /* Many copies of a mesh and rigid objects that move (no reference counterpart; DXR / Vulkan RT / OptiX call the two levels BLAS and
- * TLAS).  A crt_instances handle is separate from crt_scene: it has no framebuffer, camera or frame path, only ray queries.
+ * TLAS).  A crt_instances handle is separate from crt_scene: it answers ray queries; frames of it come from a crt_scene bound to it
+ * (crt_scene_create_instanced, below).
  *
  * A mesh as a bottom-level structure: positions and triangles in SOURCE order (a triangle's id is its index); only crt_triangle.v[0..2]
  * are read. */
@@ -558,6 +559,62 @@ int crt_instances_replace_meshes(crt_instances* s, const uint32_t* mesh_ids, uin
  * dst may be NULL to query the count. */
 int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_bytes, size_t* n_out);
 int crt_instances_destroy(crt_instances* s);
+
+/* ---- frames of an instanced scene ----
+ *
+ * A crt_scene whose geometry is a LIVE crt_instances handle.  Every frame-side entry point (crt_set_camera, crt_render_frame[s][_async],
+ * crt_sync, crt_reset, crt_read_sum, crt_sum_device, crt_resolve[_device], crt_set_shard, the crt_packed_* calls, crt_get_frame_stats,
+ * crt_get_launch_times, crt_debug_read_queue) works on it as on any scene.
+ *
+ * What the shading reads of one mesh, in the handle's mesh order; copied.  triangles: n_triangles == the mesh's triangle count, in SOURCE
+ * order (a hit's id indexes it); v[3] = material, vn / vt as in crt_scene_desc, indexing THIS mesh's normals / texcoords (object space). */
+typedef struct crt_mesh_shading {
+    const crt_triangle* triangles; size_t n_triangles;
+    const float* normals;   size_t n_normals;
+    const float* texcoords; size_t n_texcoords;
+} crt_mesh_shading;
+typedef struct crt_instanced_scene_desc {
+    uint32_t abi_version;                                /* CRT_ABI_VERSION */
+    crt_instances* instances;                            /* BORROWED: must outlive the scene */
+    const crt_mesh_shading* meshes; uint32_t n_meshes;   /* == the handle's mesh count */
+    const crt_material* materials; size_t n_materials;   /* shared by all meshes, as crt_scene_desc */
+    const crt_light* lights; size_t n_lights;            /* WORLD space */
+    const uint8_t* albedo_textures; uint32_t tex_width, tex_height, n_textures;
+    uint32_t width, height, max_depth;
+} crt_instanced_scene_desc;
+/* Checks are crt_scene_create's for the same arrays, each per mesh (CRT_ERR_INVALID): the counts, the vn indices where vn.w != 0, the vt
+ * indices of textured materials, the material indices, finite normals.
+ *
+ * Binding:
+ *   - The scene reads the handle's LIVE arrays when a frame is enqueued: crt_instances_set / _refit / _update_meshes (and their device
+ *     forms) between frames change what the next frame sees.  Call crt_reset as after a camera move: the sum is not cleared for them.
+ *     Each of these mutators, on a handle with a bound scene, first waits for that scene's stream, so a frame queued with *_async never
+ *     reads arrays a mutator is rewriting.
+ *   - While a scene is bound, crt_instances_destroy, crt_instances_add_meshes and crt_instances_replace_meshes return CRT_ERR_INVALID and
+ *     change nothing (the scene's per-mesh tables would go stale).  crt_scene_destroy unbinds.  A handle without a bound scene behaves
+ *     exactly as before.
+ *   - On such a scene these return CRT_ERR_INVALID (crt_last_error says why): crt_trace* (use crt_instances_trace), crt_update_vertices*,
+ *     crt_debug_read_accel, crt_debug_time_graph, crt_set_devices with more than one entry, option "streams" other than 0 / 1, option
+ *     "accel" other than 0.  "jitter", "count_visits" (0 / 1) and "timing" work; the other tuning options are accepted and have no effect
+ *     (results never depend on them); "adaptive_tiles" is treated as 0 (the per-tile clock lives in the fused first-segment kernel, which
+ *     this path does not run).  crt_get_bvh_info reports the TLAS + BLAS totals of the handle's crt_instances_get_info.
+ *
+ * Numerical contract (tests/test_instances_frames.py holds the kernels to it):
+ *   1. Primary rays, RNG, NEE, MIS, materials, textures, the sum and the resolve are the flat frame path's, bit for bit (the shading is
+ *      the same source).
+ *   2. The closest hit of every path ray and the occlusion of every shadow ray are crt_instances_trace's without the mask bit
+ *      (CRT_TRACE_CLOSEST / CRT_TRACE_ANY on the same ray, tmax = the flat path's: 1e9 for path rays, distance to the light sample - 1e-4
+ *      for shadow rays): the minimum of (t, instance, id), with the equal-t and grazing-margin exceptions documented there.
+ *   3. The material is triangles[id].v[3] of the hit instance's mesh; u, v, t are used as returned; hit_point = (o + d*t) + n*0.0002f on
+ *      the WORLD ray.
+ *   4. The normal: n_obj is what the flat path computes from that mesh's vn / normals (interpolated, or the truncated geometric normal;
+ *      not normalised).  An instance whose record carries the identity flag: n = n_obj.  Otherwise, with W_r the rows of world_to_object,
+ *      in fp32 without fma: m_c = (W_0c*n_obj.x + W_1c*n_obj.y) + W_2c*n_obj.z (the inverse transpose of A applied to n_obj), then
+ *      n = m * (|n_obj| / |m|), |x| = sqrt((x.x*x.x + x.y*x.y) + x.z*x.z), IEEE sqrt and division, and n = m when |m| is 0 or not finite.
+ *      A shading normal so keeps its file's length whatever the instance's scale, as in a flat scene, and a matrix that is numerically
+ *      the identity gives n_obj back bit for bit.
+ * Not offered: masks in frames, per-instance material offsets, several devices or streams, several samples per launch. */
+int crt_scene_create_instanced(const crt_instanced_scene_desc* desc, crt_scene** out);
 
 /* --------------------------------------------------- host side ([host]) ----- */
 

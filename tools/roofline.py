@@ -56,12 +56,14 @@ ATTAINABLE_GINSTR = N_SIMD * CLOCK_GHZ / MIX_CYCLES_PER_INSTR
 
 
 def demangle_args(name):
-    """k_segment<...> template arguments of a mangled name: _ZN3crt9k_segmentILb1ELb0E...EEvNS_11SegmentArgsE -> [1,0,...]"""
+    """k_segment<...> template arguments of a mangled name: _ZN3crt9k_segmentILb1ELb0E...EEv... -> [1,0,...]"""
     m = re.search(r"k_segmentI((?:Lb[01]E)+)E", name)
-    return [int(x) for x in re.findall(r"Lb([01])E", m.group(1))] if m else None
+    a = [int(x) for x in re.findall(r"Lb([01])E", m.group(1))] if m else None
+    # the eleventh argument, INST (the frames of an instanced scene, DESIGN.md section 16), defaults to false: such a kernel keeps its ten-argument name here
+    return a[:10] if a and len(a) == 11 and a[10] == 0 else a
 
 
-SEG_PARAMS = ["FIRST", "STATS", "TEX", "PRETRACED", "INPLACE", "BVH2", "MAT", "BATCH", "WIDE", "ONE"]
+SEG_PARAMS = ["FIRST", "STATS", "TEX", "PRETRACED", "INPLACE", "BVH2", "MAT", "BATCH", "WIDE", "ONE", "INST"]
 
 
 def label_of(name):
