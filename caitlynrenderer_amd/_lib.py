@@ -70,8 +70,19 @@ class crt_blas_desc(C.Structure):
     _fields_ = [("vertices", C.c_void_p), ("n_vertices", C.c_size_t), ("triangles", C.c_void_p), ("n_triangles", C.c_size_t)]
 
 
+class _crt_instance_tail_words(C.Structure):
+    _fields_ = [("material_offset", C.c_uint32), ("reserved1", C.c_uint32)]
+
+
+class _crt_instance_tail(C.Union):
+    # the two words at bytes 56..63: `reserved` as they were, `material_offset` the first of them
+    _anonymous_ = ("words",)
+    _fields_ = [("reserved", C.c_uint32 * 2), ("words", _crt_instance_tail_words)]
+
+
 class crt_instance(C.Structure):
-    _fields_ = [("object_to_world", C.c_float * 12), ("mesh", C.c_uint32), ("mask", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+    _anonymous_ = ("tail",)
+    _fields_ = [("object_to_world", C.c_float * 12), ("mesh", C.c_uint32), ("mask", C.c_uint32), ("tail", _crt_instance_tail)]
 
 
 class crt_mesh_shading(C.Structure):

@@ -134,6 +134,11 @@ struct crt_scene {
     crt_instances* inst = nullptr;
     uint4* d_mesh_base = nullptr;        // per mesh: first triangle, first normal, first texcoord, 0
     int32_t* d_qinst = nullptr;          // the hit instance of every entry of the path-ray queue (beside d_qhits)
+    // material offsets and masks in its frames.  The two tables are the rule the handle holds offsets to while bound
+    uint4* d_mesh_mtl = nullptr;         // per mesh: least, greatest v[3], 1 = every vt indexes the mesh's texcoords, 0
+    uint32_t* d_tex_before = nullptr;    // n_materials + 1: the textured materials below each index
+    uint32_t instance_masks = 0, mask_primary = 255, mask_bounce = 255, mask_shadow = 255;   // options of those names
+    uint64_t cmask_seen = 0;             // the handle's child-mask pass this scene's stream last waited for
 
     // shard + frame buffers
     uint32_t rank = 0, world = 1, tile = 16;   // 16x16: four waves per tile — fine enough for the cost-sorted schedule (1 M triangles: 0.273 ms at 64, 0.257 at 16)
@@ -313,7 +318,7 @@ struct crt_scene {
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
                         d_rays[0], d_rays[1], d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
-                        d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins, d_mesh_base, d_qinst};
+                        d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins, d_mesh_base, d_qinst, d_mesh_mtl, d_tex_before};
         for (void* p : ptrs) if (p) hipFree(p);
         if (h_tile_cost) hipHostFree(h_tile_cost);
         if (h_tile_order) hipHostFree(h_tile_order);
@@ -745,7 +750,7 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
         if (ew != -1.0f && !(ew >= 0.0f && (size_t)ew < d->n_lights)) return fail(CRT_ERR_INVALID, who + "emissive material refers to a light that does not exist");
     }
     size_t n_tris = 0, n_normals = 0, n_texcoords = 0;
-    std::vector<uint4> base(d->n_meshes);
+    std::vector<uint4> base(d->n_meshes), mesh_mtl(d->n_meshes);
     for (uint32_t k = 0; k < d->n_meshes; ++k) {
         const crt_mesh_shading& m = d->meshes[k];
         const std::string mesh = "mesh " + std::to_string(k) + ": ";
@@ -754,9 +759,13 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
         if ((m.n_normals && !m.normals) || (m.n_texcoords && !m.texcoords)) return fail(CRT_ERR_INVALID, who + mesh + "null normals / texcoords");
         for (size_t i = 0; i < 3 * m.n_normals; ++i)
             if (!std::isfinite(m.normals[i])) return fail(CRT_ERR_INVALID, who + mesh + "a normal is not finite");
+        uint32_t mtl_lo = 0xffffffffu, mtl_hi = 0u, vt_ok = 1u;
         for (size_t i = 0; i < m.n_triangles; ++i) {
             const crt_triangle& t = m.triangles[i];
             if (t.v[3] < 0 || (size_t)t.v[3] >= d->n_materials) return fail(CRT_ERR_INVALID, who + mesh + "material index out of range");
+            mtl_lo = std::min(mtl_lo, (uint32_t)t.v[3]); mtl_hi = std::max(mtl_hi, (uint32_t)t.v[3]);
+            for (int j = 0; j < 3; ++j)
+                if (t.vt[j] < 0 || (size_t)t.vt[j] >= m.n_texcoords) vt_ok = 0u;
             if (t.vn[3] != 0)
                 for (int j = 0; j < 3; ++j)
                     if (t.vn[j] < 0 || (size_t)t.vn[j] >= m.n_normals) return fail(CRT_ERR_INVALID, who + mesh + "normal index out of range");
@@ -765,10 +774,15 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
                     if (t.vt[j] < 0 || (size_t)t.vt[j] >= m.n_texcoords) return fail(CRT_ERR_INVALID, who + mesh + "texcoord index out of range");
         }
         base[k] = make_uint4((uint32_t)n_tris, (uint32_t)n_normals, (uint32_t)n_texcoords, 0u);
+        mesh_mtl[k] = make_uint4(mtl_lo, mtl_hi, vt_ok, 0u);
         n_tris += m.n_triangles; n_normals += m.n_normals; n_texcoords += m.n_texcoords;
     }
     if (n_tris >= (1ull << 31) || n_normals >= (1ull << 31) || n_texcoords >= (1ull << 31)) return fail(CRT_ERR_LIMIT, who + "too many elements");
     (void)any_textured;
+    // the rule for material offsets (include/crt.h): a material is textured when the shading would read texcoords for it
+    if (d->n_materials >= (1ull << 31)) return fail(CRT_ERR_LIMIT, who + "too many materials");
+    std::vector<uint32_t> tex_before(d->n_materials + 1, 0u);
+    for (size_t m = 0; m < d->n_materials; ++m) tex_before[m + 1] = tex_before[m] + ((have_tex && d->materials[m].tex_ind[0] != -1.0f) ? 1u : 0u);
     HIPCHK(hipSetDevice(v.device));
     std::unique_ptr<crt_scene> owner(new (std::nothrow) crt_scene);
     crt_scene* s = owner.get();
@@ -793,7 +807,8 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
     };
     if ((rc = up(&s->d_triangles, tris.data(), n_tris * 3)) || (rc = up(&s->d_normals, normals.data(), normals.size())) ||
         (rc = up(&s->d_materials, d->materials, d->n_materials * 4)) || (rc = up(&s->d_lights, d->lights, d->n_lights * 18)) ||
-        (rc = up(&s->d_mesh_base, base.data(), base.size())))
+        (rc = up(&s->d_mesh_base, base.data(), base.size())) || (rc = up(&s->d_mesh_mtl, mesh_mtl.data(), mesh_mtl.size())) ||
+        (rc = up(&s->d_tex_before, tex_before.data(), tex_before.size())))
         return rc;
     if (have_tex) {
         const size_t n_tex = (size_t)d->tex_width * d->tex_height * d->n_textures * 3;
@@ -804,7 +819,7 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
     }
     s->rows_padded = true;                   // no tree of its own
     if ((rc = finish_scene_setup(s))) return rc;
-    if ((rc = crt::instances_bind(d->instances, s->stream))) return rc;
+    if ((rc = crt::instances_bind(d->instances, s->stream, crt::InstOffsetRule{s->d_mesh_mtl, s->d_tex_before, (uint32_t)d->n_materials}))) return rc;
     s->inst = d->instances;
     *out = owner.release();
     return CRT_OK;
@@ -1210,6 +1225,17 @@ int crt_set_option(crt_scene* s, const char* name, int value) {
         if (!std::strcmp(name, "accel") && value != 0)
             return fail(CRT_ERR_INVALID, "crt_set_option: an instanced scene has no BVH2: its frames walk the handle's two-level CWBVH (accel is 0)");
         if (!std::strcmp(name, "adaptive_tiles")) return CRT_OK;      // treated as 0: the per-tile clock lives in the fused first-segment kernel
+        // masks in frames: read when the next frame is enqueued
+        if (!std::strcmp(name, "instance_masks")) {
+            if (value != 0 && value != 1) return fail(CRT_ERR_INVALID, "crt_set_option: instance_masks is 0 or 1");
+            s->instance_masks = (uint32_t)value;
+            return CRT_OK;
+        }
+        if (!std::strcmp(name, "mask_primary") || !std::strcmp(name, "mask_bounce") || !std::strcmp(name, "mask_shadow")) {
+            if (value < 0 || value > 255) return fail(CRT_ERR_INVALID, std::string("crt_set_option: ") + name + " is a ray mask, 0..255");
+            (name[5] == 'p' ? s->mask_primary : name[5] == 'b' ? s->mask_bounce : s->mask_shadow) = (uint32_t)value;
+            return CRT_OK;
+        }
     }
     if (!std::strcmp(name, "jitter")) s->jitter = value ? 1u : 0u;
     else if (!std::strcmp(name, "count_visits")) { s->count_visits = value != 0; s->count_batched = value == 2; }
@@ -1403,6 +1429,9 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
     crt::instances_view(s->inst, &v);
     const uint32_t P = s->n_local_pixels;
     const size_t n_paths = P;
+    const bool masked = s->instance_masks != 0u;
+    // a masked frame walks by the handle's TLAS child masks: renewed on the handle's stream if stale, this stream ordered behind that
+    if (masked) { const int rc = crt::instances_child_masks_for(s->inst, s->stream, &s->cmask_seen); if (rc) return rc; }
     if (!s->timing_accumulate) s->n_spans = 0;
     if (s->count_visits) HIPCHK(hipMemsetAsync(s->d_visit_totals, 0, 16 * sizeof(unsigned long long), s->stream));
     s->bank ^= 1u;
@@ -1423,13 +1452,14 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
     ra.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; ra.n_zero = kCounters;
     timed(0, [&] { crt::launch_raygen(ra, s->stream); });
     for (uint32_t b = 0; b < s->max_depth; ++b) {
-        crt::InstQueueArgs qa{};
+        crt::InstMaskQueueArgs qa{};
         qa.nodes = v.nodes; qa.tris = v.tris; qa.inst = v.inst;
+        if (masked) { qa.child_masks = v.child_masks; qa.n_tlas8 = v.tlas_nodes8; qa.ray_mask = b == 0 ? s->mask_primary : s->mask_bounce; }
         qa.rays = s->d_rays[b & 1]; qa.count = cnt + counter_index(b, 0, 0); qa.hits = s->d_qhits; qa.hit_inst = s->d_qinst;
         qa.sub_capacity = s->sub_capacity; qa.n_instances = v.n_instances; qa.stack_entries = v.stack_entries;
         qa.refill_min = 8; qa.tri_min = 2;          // crt_instances_trace's
         qa.visit_totals = s->d_visit_totals; qa.overflow = s->d_overflow;
-        timed(1, [&] { crt::launch_closest_instances_queue(qa, s->count_visits, s->stream); });
+        timed(1, [&] { crt::launch_closest_instances_queue(qa, s->count_visits, masked, s->stream); });
         crt::InstSegmentArgs sa{};
         sa.triangles = s->d_triangles; sa.normals = s->d_normals; sa.materials = s->d_materials; sa.lights = s->d_lights; sa.n_lights = (int32_t)s->n_lights;
         sa.stack_entries = 2;                       // the shade-only pass walks nothing
@@ -1452,15 +1482,16 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
         sa.hit_inst = s->d_qinst; sa.inst_w2o = v.w2o; sa.inst_mesh = v.mesh_of; sa.mesh_base = s->d_mesh_base;
         timed(3, [&] { crt::launch_segment_instanced(sa, s->count_visits, s->trace_grid(P, 5), s->waves_per_workgroup, s->stream); });
     }
-    crt::InstShadowArgs sh{};
+    crt::InstMaskShadowArgs sh{};
     sh.nodes = v.nodes; sh.tris = v.tris; sh.inst = v.inst;
+    if (masked) { sh.child_masks = v.child_masks; sh.n_tlas8 = v.tlas_nodes8; sh.ray_mask = s->mask_shadow; }
     sh.shadow = s->d_nee; sh.count = cnt + counter_index(0, 1, 0); sh.count_stride = counter_index(1, 1, 0) - counter_index(0, 1, 0);
     sh.contrib = s->d_contrib; sh.n_slots = (uint32_t)(n_paths * s->max_depth);
     sh.pools_per_region = (s->sub_capacity + 63u) / 64u; sh.n_regions = s->max_depth;
     sh.sub_capacity = s->sub_capacity; sh.n_instances = v.n_instances; sh.stack_entries = v.stack_entries;
     sh.refill_min = 8; sh.tri_min = 2;
     sh.visit_totals = s->d_visit_totals ? s->d_visit_totals + 2 : nullptr; sh.overflow = s->d_overflow;
-    timed(2, [&] { crt::launch_shadow_instances_deferred(sh, s->count_visits, s->stream); });
+    timed(2, [&] { crt::launch_shadow_instances_deferred(sh, s->count_visits, masked, s->stream); });
     crt::launch_fold_paths(s->d_sum, s->d_lfinal, s->d_contrib, P, 1u, 0u, s->stream);
     if (s->count_visits)
         HIPCHK(hipMemcpyAsync(s->h_visit_totals, s->d_visit_totals, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));

@@ -85,7 +85,7 @@ struct crt_instances {
     float4* d_inst = nullptr;             // live instance records in TLAS leaf order (capacity x 4 rows)
     float* d_w2o = nullptr;               // live world_to_object, instance order (capacity x 12)
     float* d_wbox = nullptr;              // live world boxes, instance order (capacity x 6)
-    uint32_t* d_mesh_of = nullptr;        // live, instance order: mesh index, bit 31 = identity matrix (what a bound scene's shading reads)
+    uint2* d_mesh_of = nullptr;           // live, instance order: (mesh index, bit 31 = identity matrix; material offset): what a bound scene's shading reads
     float* d_mesh_box = nullptr;          // 6 per mesh
     uint32_t* d_mesh_root = nullptr;      // BLAS root node per mesh
     // a set's staging: nothing here is read by the walk, so a refused set leaves the scene as it was
@@ -93,9 +93,9 @@ struct crt_instances {
     float4* d_rec = nullptr;              // records in instance order
     float* d_box = nullptr;
     float* d_w2o_stage = nullptr;
-    uint32_t* d_mesh_of_stage = nullptr;
+    uint2* d_mesh_of_stage = nullptr;
     crt_node8* d_t8_stage = nullptr;      // the converter's output (tlas_cap_nodes)
-    uint32_t* d_flag = nullptr;
+    uint32_t* d_flag = nullptr;           // the verdict of a call's device checks: [0] what failed, [1] the first instance a bound scene refuses
     uint32_t* d_overflow = nullptr;
     crt::DeviceArena arena;               // TLAS build: BVH2, leaf order, CWBVH slots, builder temporaries (sized for capacity)
     crt_flatnode* d_flat = nullptr;
@@ -114,8 +114,11 @@ struct crt_instances {
     uint8_t* d_tlas_table = nullptr;      // the TLAS's RefitMesh, then one RefitSeg per level
     std::vector<uint8_t> tlas_table;
     // masked traces: 8 B per TLAS node8, byte i = OR of the masks under meta slot i.  Stale after every publish and refit;
-    // the next masked trace or debug read recomputes them on the stream (ensure_child_masks).  Reserved at create
+    // the next masked trace, debug read or masked frame of a bound scene recomputes them on the stream (ensure_child_masks), ALWAYS this
+    // handle's: ev_cmask, recorded behind each pass, is what a bound scene's stream waits for.  Reserved at create
     bool cmask_ok = false;
+    uint64_t cmask_gen = 0;               // passes enqueued so far
+    hipEvent_t ev_cmask = nullptr;
     uint2* d_cmask = nullptr;             // tlas_cap_nodes x 8 B
     uint32_t* d_cm_parent = nullptr;      // tlas_cap_nodes: (parent node << 3 | meta slot) of each TLAS node8
     uint32_t* d_cm_leaf = nullptr;        // capacity: (node << 3 | meta slot) of the leaf slot holding each instance record
@@ -125,7 +128,8 @@ struct crt_instances {
     std::unique_ptr<InstUpdateState> upd;     // CRT_INSTANCES_UPDATABLE only
     // scenes that render this handle (crt_scene_create_instanced), by their streams: while there is one, every mutator
     // first waits for them (wait_bound), and destroy / add_meshes / replace_meshes are refused
-    std::vector<hipStream_t> bound;
+    struct Bound { hipStream_t stream; crt::InstOffsetRule rule; };
+    std::vector<Bound> bound;
 
     ~crt_instances() {
         void* bufs[] = {d_nodes, d_tris, d_inst, d_w2o, d_wbox, d_mesh_box, d_mesh_root, d_in, d_rec, d_box, d_w2o_stage, d_flag, d_overflow,
@@ -137,6 +141,7 @@ struct crt_instances {
         arena.release();
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
+        if (ev_cmask) (void)hipEventDestroy(ev_cmask);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -213,24 +218,42 @@ MeshTables live_tables(const crt_instances* s) { return MeshTables{s->d_mesh_box
 
 // Before a mutator enqueues anything: the frames a bound scene has queued (crt_render_frame*_async) have read the live arrays
 int wait_bound(crt_instances* s) {
-    for (hipStream_t st : s->bound) IHIPCHK(hipStreamSynchronize(st));
+    for (const auto& b : s->bound) IHIPCHK(hipStreamSynchronize(b.stream));
     return CRT_OK;
+}
+
+// a bound scene's refusal of a material offset, from the verdict words
+std::string offset_refusal(const uint32_t flag[2]) {
+    return "instance " + std::to_string(flag[1]) +
+           ((flag[0] & 8u) ? ": material_offset is 2^31 or more, or moves its mesh's greatest material index past a bound scene's material table"
+                           : ": material_offset moves a mesh whose vt do not all index its texcoords onto a textured material of a bound scene");
+}
+
+// the rule of one bound scene against n (mesh, offset) words, into d_flag.  Enqueued only
+void check_offsets(crt_instances* s, const crt::InstOffsetRule& rule, const uint2* d_words, uint32_t n, uint32_t n_meshes) {
+    crt::InstOffsetCheckArgs ca{};
+    ca.mesh_of = d_words; ca.n = n; ca.n_meshes = n_meshes; ca.rule = rule; ca.flag = s->d_flag;
+    crt::launch_instance_offsets(ca, s->stream);
 }
 
 int prep_instances(crt_instances* s, const void* d_src, uint32_t n, const MeshTables& mt, const std::string& who) {
     hipStream_t st = s->stream;
     IHIPCHK(hipMemsetAsync(s->d_flag, 0, 4, st));
+    IHIPCHK(hipMemsetAsync(s->d_flag + 1, 0xff, 4, st));
     crt::InstPrepArgs pa{};
     pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = mt.n_meshes; pa.mesh_box = mt.d_box; pa.mesh_root = mt.d_root;
     pa.rec = s->d_rec; pa.box = s->d_box; pa.w2o = s->d_w2o_stage; pa.flag = s->d_flag; pa.mesh_of = s->d_mesh_of_stage;
     crt::launch_instance_prep(pa, st);
-    uint32_t flag = 0;
-    IHIPCHK(hipMemcpyAsync(&flag, s->d_flag, 4, hipMemcpyDeviceToHost, st));
+    // every bound scene's rule for material offsets against the STAGED words, into the same verdict: still one wait
+    for (const auto& b : s->bound) check_offsets(s, b.rule, s->d_mesh_of_stage, n, mt.n_meshes);
+    uint32_t flag[2] = {0u, 0u};
+    IHIPCHK(hipMemcpyAsync(flag, s->d_flag, 8, hipMemcpyDeviceToHost, st));
     IHIPCHK(hipStreamSynchronize(st));
     IHIPCHK(hipGetLastError());
-    if (flag)
-        return fail(CRT_ERR_INVALID, who + ((flag & 1u) ? "a matrix is not finite, or singular, or its inverse is not finite"
-                                            : (flag & 2u) ? "a mesh index is out of range" : "a world box exceeds 1e18"));
+    if (flag[0] & 7u)
+        return fail(CRT_ERR_INVALID, who + ((flag[0] & 1u) ? "a matrix is not finite, or singular, or its inverse is not finite"
+                                            : (flag[0] & 2u) ? "a mesh index is out of range" : "a world box exceeds 1e18"));
+    if (flag[0]) return fail(CRT_ERR_INVALID, who + offset_refusal(flag));
     return CRT_OK;
 }
 
@@ -272,7 +295,7 @@ int publish_tlas(crt_instances* s, const void* d_src, uint32_t n, const TlasStag
     crt::launch_gather_instances(s->d_rec, s->d_tri_order, s->d_tri_slots, n, s->d_inst, st);
     IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
     IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
-    IHIPCHK(hipMemcpyAsync(s->d_mesh_of, s->d_mesh_of_stage, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    IHIPCHK(hipMemcpyAsync(s->d_mesh_of, s->d_mesh_of_stage, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
     if (s->upd && d_src != s->upd->d_live)
         IHIPCHK(hipMemcpyAsync(s->upd->d_live, d_src, (size_t)n * sizeof(crt_instance), hipMemcpyDeviceToDevice, st));
     return CRT_OK;
@@ -351,7 +374,7 @@ int refit_impl(crt_instances* s, const void* d_src, uint32_t n, const std::strin
         IHIPCHK(hipGetLastError());
         IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
         IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
-        IHIPCHK(hipMemcpyAsync(s->d_mesh_of, s->d_mesh_of_stage, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        IHIPCHK(hipMemcpyAsync(s->d_mesh_of, s->d_mesh_of_stage, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
         if (s->upd && d_src != s->upd->d_live)
             IHIPCHK(hipMemcpyAsync(s->upd->d_live, d_src, (size_t)n * sizeof(crt_instance), hipMemcpyDeviceToDevice, st));
     }
@@ -370,6 +393,8 @@ int ensure_child_masks(crt_instances* s) {
     if (s->n_instances)
         crt::launch_tlas_child_masks(s->d_nodes, s->n_tlas8, s->d_inst, s->n_instances, s->d_cm_parent, s->d_cm_leaf, s->d_cmask, s->stream);
     IHIPCHK(hipGetLastError());
+    IHIPCHK(hipEventRecord(s->ev_cmask, s->stream));
+    ++s->cmask_gen;
     s->cmask_ok = true;
     return CRT_OK;
 }
@@ -585,6 +610,7 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     IHIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     IHIPCHK(hipEventCreate(&s->ev0));
     IHIPCHK(hipEventCreate(&s->ev1));
+    IHIPCHK(hipEventCreateWithFlags(&s->ev_cmask, hipEventDisableTiming));
     s->n_meshes = n_meshes; s->capacity = capacity;
     s->tlas_cap_nodes = std::max<uint32_t>(capacity, 1u);          // a CWBVH over c >= 1 leaves has at most max(1, c - 1) node8s
     hipStream_t st = s->stream;
@@ -627,7 +653,7 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     IHIPCHK(hipMemcpyAsync(s->d_mesh_root, roots.data(), n_meshes * 4, hipMemcpyHostToDevice, st));
     const size_t C = capacity;
     if ((rc = alloc(&s->d_inst, C * 4)) || (rc = alloc(&s->d_w2o, C * 12)) || (rc = alloc(&s->d_wbox, C * 6)) || (rc = alloc(&s->d_in, C * 16)) ||
-        (rc = alloc(&s->d_rec, C * 4)) || (rc = alloc(&s->d_box, C * 6)) || (rc = alloc(&s->d_w2o_stage, C * 12)) || (rc = alloc(&s->d_flag, 1)) ||
+        (rc = alloc(&s->d_rec, C * 4)) || (rc = alloc(&s->d_box, C * 6)) || (rc = alloc(&s->d_w2o_stage, C * 12)) || (rc = alloc(&s->d_flag, 2)) ||
         (rc = alloc(&s->d_overflow, 1)) || (rc = alloc(&s->d_t8_stage, s->tlas_cap_nodes)) || (rc = alloc(&s->d_tlas_box8, 6 * (size_t)s->tlas_cap_nodes)) ||
         (rc = alloc(&s->d_box_idx, C * 3)) || (rc = alloc(&s->d_tlas_table, sizeof(crt::RefitMesh) + 255 * sizeof(crt::RefitSeg))) ||
         (rc = alloc(&s->d_cmask, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_parent, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_leaf, C)) ||
@@ -875,17 +901,41 @@ int remesh_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const crt_bla
 namespace crt {
 
 void instances_view(const crt_instances* h, InstancesView* out) {
-    *out = InstancesView{h->device, h->d_nodes, h->d_tris, h->d_inst, h->d_w2o, h->d_mesh_of, h->n_instances, h->stack_entries, h->n_meshes,
+    *out = InstancesView{h->device, h->d_nodes, h->d_tris, h->d_inst, h->d_w2o, h->d_mesh_of, h->d_cmask, h->n_instances, h->stack_entries, h->n_meshes,
                          h->n_tlas8, h->tlas_depth8, h->max_blas_depth8, h->blas_nodes8, h->blas_tris};
 }
 uint32_t instances_mesh_triangles(const crt_instances* h, uint32_t mesh) { return h->mesh[mesh].n_tris; }
-int instances_bind(crt_instances* h, hipStream_t stream) {
-    try { h->bound.push_back(stream); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_scene_create_instanced: out of memory"); }
+int instances_bind(crt_instances* h, hipStream_t stream, const InstOffsetRule& rule) {
+    // the rule against the LIVE instances, on the handle's stream behind whatever it has queued
+    if (h->n_instances) {
+        hipStream_t st = h->stream;
+        IHIPCHK(hipMemsetAsync(h->d_flag, 0, 4, st));
+        IHIPCHK(hipMemsetAsync(h->d_flag + 1, 0xff, 4, st));
+        check_offsets(h, rule, h->d_mesh_of, h->n_instances, h->n_meshes);
+        uint32_t flag[2] = {0u, 0u};
+        IHIPCHK(hipMemcpyAsync(flag, h->d_flag, 8, hipMemcpyDeviceToHost, st));
+        IHIPCHK(hipStreamSynchronize(st));
+        IHIPCHK(hipGetLastError());
+        if (flag[0]) return fail(CRT_ERR_INVALID, "crt_scene_create_instanced: " + offset_refusal(flag));
+    }
+    try { h->bound.push_back(crt_instances::Bound{stream, rule}); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_scene_create_instanced: out of memory"); }
     return CRT_OK;
 }
 void instances_unbind(crt_instances* h, hipStream_t stream) {
-    auto it = std::find(h->bound.begin(), h->bound.end(), stream);
+    auto it = std::find_if(h->bound.begin(), h->bound.end(), [&](const crt_instances::Bound& b) { return b.stream == stream; });
     if (it != h->bound.end()) h->bound.erase(it);
+}
+// The pass itself runs on the handle's stream only, and only when a publish or refit has left the masks stale — calls that have waited
+// for every bound stream first, so no frame in flight reads what the pass rewrites.  `stream` then waits for the event behind the LAST
+// pass, whoever asked for it (a masked trace may have enqueued it and not be done): on the device, and once per pass (*seen).
+int instances_child_masks_for(crt_instances* h, hipStream_t stream, uint64_t* seen) {
+    const int rc = ensure_child_masks(h);
+    if (rc) return rc;
+    if (*seen != h->cmask_gen) {
+        IHIPCHK(hipStreamWaitEvent(stream, h->ev_cmask, 0));
+        *seen = h->cmask_gen;
+    }
+    return CRT_OK;
 }
 
 }  // namespace crt

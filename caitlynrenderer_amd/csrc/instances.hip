@@ -1,7 +1,8 @@
 // HIP kernels of instanced scenes (include/crt.h crt_instances_*): per-instance preparation (validation, inverse, world
 // box, record), the packing of the BLASes into one node array, and the kernels of the two-level walk (instances_walk.hpp,
 // instances_walk_loop.hpp): k_trace_instances for explicit rays, k_closest_instances_queue and k_shadow_instances_deferred for the frames
-// of an instanced scene.
+// of an instanced scene, each also in a masked form that culls by one ray mask per launch (§17), and the check of
+// per-instance material offsets against a bound scene's material table (§17).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -41,7 +42,23 @@ __global__ void __launch_bounds__(256) k_instance_prep(InstPrepArgs a) {
                        __uint_as_float(src[13] & 0xffu));       // crt_instance.mask: bits 8..31 are ignored
     for (int k = 0; k < 6; ++k) a.box[6 * (size_t)i + k] = box[k];
     for (int k = 0; k < 12; ++k) a.w2o[12 * (size_t)i + k] = w[k];
-    a.mesh_of[i] = mesh | (instance_is_identity(m) ? 0x80000000u : 0u);
+    a.mesh_of[i] = make_uint2(mesh | (instance_is_identity(m) ? 0x80000000u : 0u), src[14]);
+}
+
+// A bound scene's rule for material offsets (include/crt.h crt_scene_create_instanced) against (mesh, offset) words: those a
+// set or refit has staged, or the live ones at a scene's create.  Offset 0 is exempt.  A mesh index out of range is k_instance_prep's to
+// refuse (it has then written no word for that instance: what lies there is stale).
+__global__ void __launch_bounds__(256) k_instance_offsets(InstOffsetCheckArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const uint2 w = a.mesh_of[i];
+    const uint32_t mesh = w.x & 0x7fffffffu, off = w.y;
+    if (off == 0u || mesh >= a.n_meshes) return;
+    const uint4 mm = a.rule.mesh_mtl[mesh];          // lo, hi (< n_materials), vt_ok
+    uint32_t bad = 0u;
+    if (off >= 0x80000000u || mm.y + off >= a.rule.n_materials) bad = 8u;      // hi + off < 2^32: no wrap
+    else if (mm.z == 0u && a.rule.tex_before[mm.y + off + 1u] != a.rule.tex_before[mm.x + off]) bad = 16u;
+    if (bad) { atomicOr(a.flag, bad); atomicMin(a.flag + 1, i); }
 }
 
 __global__ void __launch_bounds__(256) k_rebase_nodes(uint4* __restrict__ nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off) {
@@ -164,9 +181,11 @@ __global__ void __launch_bounds__(64) k_trace_instances(std::conditional_t<MASK,
             a.hits[idx] = h;                                    \
             if (a.inst_out) a.inst_out[idx] = hit ? inst : -1;  \
             if (STATS) a.stats[idx] = ((nt > 65535u ? 65535u : nt) << 16) | (nn > 65535u ? 65535u : nn);
+#define CRT_WALK_MASK(lane_mask) (lane_mask)
 #include "instances_walk_loop.hpp"
 #undef CRT_WALK_LOAD
 #undef CRT_WALK_DONE
+#undef CRT_WALK_MASK
     }
 }
 
@@ -181,12 +200,19 @@ __device__ __forceinline__ void flush_inst_totals(unsigned long long* totals, ui
     }
 }
 
+// the ray mask of a masked frame launch: a kernel argument, the same in every lane (the unmasked argument blocks have none: never called)
+__device__ __forceinline__ uint32_t launch_mask(const InstMaskQueueArgs& a) { return a.ray_mask; }
+__device__ __forceinline__ uint32_t launch_mask(const InstMaskShadowArgs& a) { return a.ray_mask; }
+__device__ __forceinline__ uint32_t launch_mask(const InstQueueArgs&) { return 0u; }
+__device__ __forceinline__ uint32_t launch_mask(const InstShadowArgs&) { return 0u; }
+
 // Closest hits of a segment's path-ray queue: workgroup (g, c) = one wave walks entries [64 c, 64 c + 64) of sub-queue g, as far as its
 // device-side count goes; hits and hit instances go to buffers parallel to the queue, and k_segment<PRETRACED, INST> shades them.
-template <bool STATS>
-__global__ void __launch_bounds__(64) k_closest_instances_queue(InstQueueArgs a) {
+// MASK: the walk culls by a.ray_mask, one mask for the launch.
+template <bool STATS, bool MASK>
+__global__ void __launch_bounds__(64) k_closest_instances_queue(std::conditional_t<MASK, InstMaskQueueArgs, InstQueueArgs> a) {
     extern __shared__ uint2 s_lds[];          // [level][lane] of the workgroup's one wave
-    constexpr bool ANY = false, MASK = false;
+    constexpr bool ANY = false;
     const uint32_t lane = threadIdx.x & 63u, g = blockIdx.x & 7u, c = blockIdx.x >> 3;
     const uint32_t cnt = a.count[g * CRT_COUNTER_STRIDE], n = cnt < a.sub_capacity ? cnt : a.sub_capacity;
     if (c * 64u >= n) return;
@@ -200,18 +226,20 @@ __global__ void __launch_bounds__(64) k_closest_instances_queue(InstQueueArgs a)
             a.hits[idx] = h;                     \
             a.hit_inst[idx] = hit ? inst : -1;   \
             if (STATS) { tn += nn; tt += nt; }
+#define CRT_WALK_MASK(lane_mask) ((void)(lane_mask), launch_mask(a))
 #include "instances_walk_loop.hpp"
 #undef CRT_WALK_LOAD
 #undef CRT_WALK_DONE
+#undef CRT_WALK_MASK
     if (STATS) flush_inst_totals(a.visit_totals, tn, tt);
 }
 
 // The frame's deferred NEE shadow rays (k_shadow_deferred's queue layout: region r = segment, 8 sub-queues each, entry = (o, tmax)
 // (d, contribution slot)): workgroup (g, r, c) walks 64 entries; an OCCLUDED ray clears the visibility word of its contribution slot.
-template <bool STATS>
-__global__ void __launch_bounds__(64) k_shadow_instances_deferred(InstShadowArgs a) {
+template <bool STATS, bool MASK>
+__global__ void __launch_bounds__(64) k_shadow_instances_deferred(std::conditional_t<MASK, InstMaskShadowArgs, InstShadowArgs> a) {
     extern __shared__ uint2 s_lds[];
-    constexpr bool ANY = true, MASK = false;
+    constexpr bool ANY = true;
     const uint32_t lane = threadIdx.x & 63u, g = blockIdx.x & 7u, q = blockIdx.x >> 3;
     const uint32_t r = q / a.pools_per_region, c = q - r * a.pools_per_region;
     if (r >= a.n_regions) return;
@@ -230,9 +258,11 @@ __global__ void __launch_bounds__(64) k_shadow_instances_deferred(InstShadowArgs
                 if (slot < a.n_slots) reinterpret_cast<float*>(a.contrib + slot)[3] = 0.0f;   \
             }                                                                                 \
             if (STATS) { tn += nn; tt += nt; }
+#define CRT_WALK_MASK(lane_mask) ((void)(lane_mask), launch_mask(a))
 #include "instances_walk_loop.hpp"
 #undef CRT_WALK_LOAD
 #undef CRT_WALK_DONE
+#undef CRT_WALK_MASK
     if (STATS) flush_inst_totals(a.visit_totals, tn, tt);
 }
 
@@ -240,6 +270,9 @@ static inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255u) / 25
 
 void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream) {
     if (a.n) hipLaunchKernelGGL(k_instance_prep, grid_for(a.n), dim3(256), 0, stream, a);
+}
+void launch_instance_offsets(const InstOffsetCheckArgs& a, hipStream_t stream) {
+    if (a.n) hipLaunchKernelGGL(k_instance_offsets, grid_for(a.n), dim3(256), 0, stream, a);
 }
 void launch_rebase_nodes(void* d_nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off, hipStream_t stream) {
     if (n8) hipLaunchKernelGGL(k_rebase_nodes, grid_for(n8), dim3(256), 0, stream, static_cast<uint4*>(d_nodes), n8, node_off, tri_off);
@@ -284,17 +317,29 @@ void launch_trace_instances(const InstMaskTraceArgs& a, int any, bool stats, boo
     else      launch_trace_instances_t<false>(static_cast<const InstTraceArgs&>(a), any, stats, g, b, lds, stream);
 }
 
-void launch_closest_instances_queue(const InstQueueArgs& a, bool stats, hipStream_t stream) {
+void launch_closest_instances_queue(const InstMaskQueueArgs& a, bool stats, bool mask, hipStream_t stream) {
     const dim3 g(8u * ((a.sub_capacity + 63u) / 64u)), b(64);
     const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
-    if (stats) hipLaunchKernelGGL(k_closest_instances_queue<true>, g, b, lds, stream, a);
-    else       hipLaunchKernelGGL(k_closest_instances_queue<false>, g, b, lds, stream, a);
+    const InstQueueArgs& u = a;
+    if (mask) {
+        if (stats) hipLaunchKernelGGL((k_closest_instances_queue<true, true>), g, b, lds, stream, a);
+        else       hipLaunchKernelGGL((k_closest_instances_queue<false, true>), g, b, lds, stream, a);
+    } else {
+        if (stats) hipLaunchKernelGGL((k_closest_instances_queue<true, false>), g, b, lds, stream, u);
+        else       hipLaunchKernelGGL((k_closest_instances_queue<false, false>), g, b, lds, stream, u);
+    }
 }
-void launch_shadow_instances_deferred(const InstShadowArgs& a, bool stats, hipStream_t stream) {
+void launch_shadow_instances_deferred(const InstMaskShadowArgs& a, bool stats, bool mask, hipStream_t stream) {
     const dim3 g(8u * a.n_regions * a.pools_per_region), b(64);
     const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
-    if (stats) hipLaunchKernelGGL(k_shadow_instances_deferred<true>, g, b, lds, stream, a);
-    else       hipLaunchKernelGGL(k_shadow_instances_deferred<false>, g, b, lds, stream, a);
+    const InstShadowArgs& u = a;
+    if (mask) {
+        if (stats) hipLaunchKernelGGL((k_shadow_instances_deferred<true, true>), g, b, lds, stream, a);
+        else       hipLaunchKernelGGL((k_shadow_instances_deferred<false, true>), g, b, lds, stream, a);
+    } else {
+        if (stats) hipLaunchKernelGGL((k_shadow_instances_deferred<true, false>), g, b, lds, stream, u);
+        else       hipLaunchKernelGGL((k_shadow_instances_deferred<false, false>), g, b, lds, stream, u);
+    }
 }
 
 // crt_warmup: load this translation unit's code object on the current device (device_build.hpp)

@@ -37,7 +37,20 @@ struct InstPrepArgs {
     float* box;                // 6 floats per instance: world box
     float* w2o;                // 12 floats per instance: world_to_object
     uint32_t* flag;            // |= 1 matrix not finite / singular / inverse not finite, 2 mesh index out of range, 4 world box beyond 1e18
-    uint32_t* mesh_of;         // the instance's mesh index, bit 31 = the identity flag (what a frame's shading looks the hit triangle up by)
+    uint2* mesh_of;            // x: the instance's mesh index, bit 31 = the identity flag (what a frame's shading looks the hit triangle up by;
+                               // DESIGN.md §16), y: crt_instance.material_offset (what it adds to the triangle's material; §17)
+};
+// What a scene bound to the handle admits as material offsets (crt_scene_create_instanced's validation rule)
+struct InstOffsetRule {
+    const uint4* mesh_mtl;     // per mesh: least and greatest v[3] of its triangles, 1 = every vt indexes the mesh's texcoords, 0
+    const uint32_t* tex_before;// n_materials + 1 words: the textured materials below each index
+    uint32_t n_materials;
+};
+struct InstOffsetCheckArgs {   // k_instance_offsets: the rule against n instances' (mesh, offset) words
+    const uint2* mesh_of;
+    uint32_t n, n_meshes;
+    InstOffsetRule rule;
+    uint32_t* flag;            // [0] |= 8 offset out of range, 16 offset onto a textured material without texcoords; [1] min= the instance
 };
 
 // The frame path of an instanced scene (crt_scene_create_instanced): the two-level walk fed by a frame's device-written
@@ -46,7 +59,7 @@ struct InstQueueArgs {         // k_closest_instances_queue: closest hits of a s
     const uint4* nodes;
     const float4* tris;
     const float4* inst;
-    const uint2* child_masks;  // what a masked walk would read: frames do not mask (out of scope), null / 0
+    const uint2* child_masks;  // the unmasked kernels read neither: null / 0.  The masked ones (InstMaskQueueArgs): as InstMaskTraceArgs
     uint32_t n_tlas8;
     const float4* rays;        // 8 sub-queues of crt_ray, sub_capacity entries each
     const uint32_t* count;     // 8 device-side counts, CRT_COUNTER_STRIDE apart
@@ -56,6 +69,10 @@ struct InstQueueArgs {         // k_closest_instances_queue: closest hits of a s
     unsigned long long* visit_totals;   // counting frames: [0] += node steps, [1] += triangle tests
     uint32_t* overflow;
 };
+// The masked walks of a frame (option "instance_masks").  Types of their own, as InstMaskTraceArgs, so that the unmasked
+// kernels keep their argument blocks and code.  ray_mask: the launch's ONE ray mask (0..255) — in the queues the rays' w words are the
+// path index and the contribution slot — wave-uniform, a scalar operand of both mask tests.
+struct InstMaskQueueArgs : InstQueueArgs { uint32_t ray_mask; };
 struct InstShadowArgs {        // k_shadow_instances_deferred: the frame's deferred NEE shadow rays, every segment's in one launch
     const uint4* nodes;
     const float4* tris;
@@ -71,7 +88,10 @@ struct InstShadowArgs {        // k_shadow_instances_deferred: the frame's defer
     uint32_t* overflow;
 };
 
+struct InstMaskShadowArgs : InstShadowArgs { uint32_t ray_mask; };
+
 void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream);
+void launch_instance_offsets(const InstOffsetCheckArgs& a, hipStream_t stream);
 // node8 i: child_base_index += node_off, triangle_base_index += tri_off
 void launch_rebase_nodes(void* d_nodes, uint32_t n8, uint32_t node_off, uint32_t tri_off, hipStream_t stream);
 // d_dst node8 i = d_src node8 i with child_base_index += node_delta, triangle_base_index += tri_delta (wrapped differences new - old
@@ -93,7 +113,8 @@ void launch_tlas_child_masks(const void* d_nodes, uint32_t n8, const float4* d_i
 // `chunks`: 1024-ray chunks of the dense index space (k_trace's mapping), a multiple of 8; mask: CRT_TRACE_INSTANCE_MASK walk
 void launch_trace_instances(const InstMaskTraceArgs& a, int any, bool stats, bool mask, uint32_t chunks, hipStream_t stream);
 // one single-wave workgroup per 64 entries a sub-queue can hold; LDS = stack_entries x 512 B
-void launch_closest_instances_queue(const InstQueueArgs& a, bool stats, hipStream_t stream);
-void launch_shadow_instances_deferred(const InstShadowArgs& a, bool stats, hipStream_t stream);
+// mask: the masked walk with a.ray_mask (child_masks, n_tlas8 set); else those three are not read
+void launch_closest_instances_queue(const InstMaskQueueArgs& a, bool stats, bool mask, hipStream_t stream);
+void launch_shadow_instances_deferred(const InstMaskShadowArgs& a, bool stats, bool mask, hipStream_t stream);
 
 }  // namespace crt

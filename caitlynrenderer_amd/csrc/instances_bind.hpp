@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/crt.h"
+#include "instances.hpp"
 
 namespace crt {
 
@@ -15,7 +16,8 @@ struct InstancesView {
     const float4* tris;        // every BLAS's records
     const float4* inst;        // instance records in TLAS leaf order
     const float* w2o;          // world_to_object, 12 floats per instance, instance order
-    const uint32_t* mesh_of;   // per instance: mesh index, bit 31 = the matrix is bitwise the identity
+    const uint2* mesh_of;      // per instance: (mesh index, bit 31 = the matrix is bitwise the identity; material offset)
+    const uint2* child_masks;  // per TLAS node8, for masked walks: fresh once instances_child_masks_for has been called
     uint32_t n_instances, stack_entries, n_meshes;
     uint32_t tlas_nodes8, tlas_depth8, max_blas_depth8;
     uint64_t blas_nodes8, blas_tris;
@@ -23,7 +25,12 @@ struct InstancesView {
 void instances_view(const crt_instances* h, InstancesView* out);
 uint32_t instances_mesh_triangles(const crt_instances* h, uint32_t mesh);     // mesh < n_meshes
 // from now on sets, refits and updates of the handle first wait for `stream`; destroy, add_meshes and replace_meshes are refused
-int instances_bind(crt_instances* h, hipStream_t stream);
+// and of every set / refit the material offsets are held to `rule` (device tables the scene keeps while bound); refused, with nothing
+// bound, when the handle's live instances break it
+int instances_bind(crt_instances* h, hipStream_t stream, const InstOffsetRule& rule);
+// before a masked frame is enqueued on `stream`: the handle's TLAS child masks renewed if stale, and `stream` ordered behind that pass.
+// *seen: the scene's note of the last pass it waited for (0 at first).  No host wait
+int instances_child_masks_for(crt_instances* h, hipStream_t stream, uint64_t* seen);
 void instances_unbind(crt_instances* h, hipStream_t stream);
 
 }  // namespace crt

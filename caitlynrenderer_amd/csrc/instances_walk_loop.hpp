@@ -10,10 +10,13 @@
 //   next, end          the pool [next, end); next is advanced
 //   CRT_WALK_LOAD(idx, r0, r1)                  declares float4 r0, r1 = the two rows of ray idx
 //   CRT_WALK_DONE(idx, h, hit, inst, nn, nt)    ray idx is done: h = crt_hit's row, hit, inst = its instance when hit, visit counts (STATS)
+//   CRT_WALK_MASK(lane_mask)                    MASK: the ray mask the two tests take, given the lane's own (the low byte of its ray's pad word).
+//                                               k_trace_instances: lane_mask itself, a mask per ray.  The frame kernels: their launch's mask, a
+//                                               kernel argument, so that no register carries a mask per lane
 //
 // One lane per ray with lane refill, one loop and one LDS stack over both levels.  Stack entries: a node group (top byte set), the rest of a
 // TLAS leaf (low 24 bits only) or the return marker (y == 0).
-// MASK: the low 8 bits of the ray's pad word are its mask; a TLAS step culls the children whose child mask does not meet it, and the
+// MASK: the ray's mask is CRT_WALK_MASK of the low 8 bits of its pad word; a TLAS step culls the children whose child mask does not meet it, and the
 // instance step skips an instance whose mask does not, before it transforms the ray.  Without MASK every such test folds away.
     uint32_t idx = 0, nn = 0, nt = 0, inst_cur = 0, rmask = 0;
     vec3 wo = V3(0.f, 0.f, 0.f), wd = V3(0.f, 0.f, 1.f), o = wo, d = wd, inv = V3(0.f, 0.f, 0.f);
@@ -72,7 +75,7 @@
                 const uint4 n0 = np[0], n1 = np[1], n2 = np[2], n3 = np[3], n4 = np[4];
                 if (STATS) ++nn;
                 uint32_t keep = 0xffu;
-                if constexpr (MASK) { if (nidx < a.n_tlas8) keep = child_keep(a.child_masks[nidx], rmask); }
+                if constexpr (MASK) { if (nidx < a.n_tlas8) keep = child_keep(a.child_masks[nidx], CRT_WALK_MASK(rmask)); }
                 const uint32_t hitmask = node8_intersect(n0, n1, n2, n3, n4, o, inv, negx, negy, negz, oct4, best_t, keep);
                 cur.x = n1.x;
                 tg.x = n1.y;
@@ -103,7 +106,7 @@
                 // an instance: into its object space (fp32, no fma, direction not renormalised: t is the same parameter in both spaces)
                 const float4* ip = a.inst + 4 * (size_t)ti;
                 const float4 w0 = ip[0], w1 = ip[1], w2 = ip[2], w3 = ip[3];
-                const bool visible = !MASK || (__float_as_uint(w3.w) & rmask) != 0u;      // a hidden instance: skipped untransformed
+                const bool visible = !MASK || (__float_as_uint(w3.w) & CRT_WALK_MASK(rmask)) != 0u;      // a hidden instance: skipped untransformed
                 vec3 oo = wo, od = wd;
                 if (visible && __float_as_uint(w3.z) == 0u) {
                     oo = V3(((w0.x * wo.x + w0.y * wo.y) + w0.z * wo.z) + w0.w, ((w1.x * wo.x + w1.y * wo.y) + w1.z * wo.z) + w1.w,

@@ -1529,10 +1529,11 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
             uint32_t inst_word = 0u, inst_id = 0u, normal0 = 0u, texcoord0 = 0u;   // INST: (identity flag | mesh) of the hit instance, and its mesh's places in the scene's arrays
             if constexpr (INST) {
                 inst_id = (uint32_t)a.hit_inst[(size_t)g * ka->sub_capacity + e];
-                inst_word = a.inst_mesh[inst_id];
+                const uint2 iw = a.inst_mesh[inst_id];
+                inst_word = iw.x;
                 const uint4 mb = a.mesh_base[inst_word & 0x7fffffffu];
                 slot = (int)mb.x + hit.tri;                                         // hit.tri: the triangle's id within its mesh = its index in the mesh's source-order triangles
-                mtl = ka->triangles[3 * (size_t)slot].w;
+                mtl = ka->triangles[3 * (size_t)slot].w + (int)iw.y;                // + the instance's material offset: in range by the bound scene's rule
                 normal0 = mb.y; texcoord0 = mb.z;
             } else {
                 const float4 tb = recs[rec_rows * (size_t)hit.tri + 1], tc = recs[rec_rows * (size_t)hit.tri + 2];

@@ -162,7 +162,7 @@ struct SegmentArgs {
 struct InstSegmentArgs : SegmentArgs {
     const int32_t* hit_inst;   // parallel to hits_in: the hit's instance (hits_in's w = the triangle's id within that instance's mesh)
     const float* inst_w2o;     // world_to_object, 12 floats per instance, instance order (the handle's live array)
-    const uint32_t* inst_mesh; // per instance: its mesh index, bit 31 = its matrix is bitwise the identity
+    const uint2* inst_mesh;    // per instance: (its mesh index, bit 31 = its matrix is bitwise the identity; its material offset)
     const uint4* mesh_base;    // per mesh: its first triangle (triangles), first normal (normals), first texcoord (texcoords), 0
 };
 

@@ -3,7 +3,8 @@ is rebuilt on the device at every `set` (include/crt.h crt_instances_*, DESIGN.m
 instances and keeps the TLAS's topology (§13).  An updatable scene also moves the vertices of its meshes: a GPU refit of their BLASes and a
 TLAS rebuild per update.  Instances carry 8-bit visibility masks that a masked trace ANDs with each ray's (§14).  Meshes
 can be appended to a live scene and, in an updatable one, replaced by new geometry (§15).  The handle answers ray queries; `frame_scene`
-returns a Scene that renders frames of it (§16)."""
+returns a Scene that renders frames of it (§16); those frames add each instance's material offset to its triangles' material indices and,
+with the scene's option "instance_masks", walk masked per ray class (§17)."""
 import ctypes as C
 
 import numpy as np
@@ -13,19 +14,35 @@ from ._lib import (CRT_ABI_VERSION, CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CR
 from .host import Rnd, _ptr
 from .scene import HIT_DT, RAY_DT, STATS_DT, Scene
 
-INSTANCE_DT = np.dtype([("object_to_world", "<f4", 12), ("mesh", "<u4"), ("mask", "<u4"), ("reserved", "<u4", 2)])      # crt_instance, 64 B
+# crt_instance, 64 B.  material_offset is the first of the two reserved words (byte 56): the fields overlap
+INSTANCE_DT = np.dtype({"names": ["object_to_world", "mesh", "mask", "reserved", "material_offset"],
+                        "formats": [("<f4", 12), "<u4", "<u4", ("<u4", 2), "<u4"],
+                        "offsets": [0, 48, 52, 56, 56], "itemsize": 64})
 
 
-def instances_array(matrices, meshes, masks=None):
+def instances_array(matrices, meshes, masks=None, material_offsets=None):
     """crt_instance records from (n, 3, 4) or (n, 12) object_to_world matrices (row-major, world = A p + t), n mesh indices and, optionally,
-    n visibility masks (bits 0..7; read by masked traces only).  Without masks the mask words stay 0."""
+    n visibility masks (bits 0..7; read by masked traces and by the frames of a scene with `instance_masks` 1) and n
+    material offsets (added to the material index of every triangle of the instance's mesh by the frames of a bound scene, §17).  Without
+    them the mask and offset words stay 0."""
     m = np.asarray(matrices, np.float32).reshape(-1, 12)
     out = np.zeros(m.shape[0], INSTANCE_DT)
     out["object_to_world"] = m
     out["mesh"] = np.asarray(meshes, np.uint32).reshape(-1)
     if masks is not None:
         out["mask"] = np.asarray(masks, np.uint32).reshape(-1)
+    if material_offsets is not None:
+        out["material_offset"] = np.asarray(material_offsets, np.uint32).reshape(-1)
     return out
+
+
+def _records(instances):
+    """a contiguous INSTANCE_DT array of crt_instance records given as INSTANCE_DT or as any other 64-byte layout of the struct (e.g. the
+    fields without `material_offset`): the bytes are taken as they are"""
+    a = np.asarray(instances)
+    if a.dtype != INSTANCE_DT and a.dtype.itemsize == INSTANCE_DT.itemsize:
+        return np.ascontiguousarray(a).view(INSTANCE_DT).reshape(-1)
+    return np.ascontiguousarray(a, INSTANCE_DT)
 
 
 def _build_flags(builder):
@@ -81,14 +98,14 @@ class InstancedScene:
     def __init__(self, meshes, instances, capacity=None, builder="sah", updatable=False):
         self._h = C.c_void_p()
         descs, keep = _blas_descs(meshes)
-        inst = np.ascontiguousarray(instances, INSTANCE_DT)
+        inst = _records(instances)
         cap = inst.shape[0] if capacity is None else int(capacity)
         flags = _build_flags(builder) | (CRT_INSTANCES_UPDATABLE if updatable else 0)
         check(lib().crt_instances_create(descs, len(meshes), _ptr(inst), inst.shape[0], cap, flags, C.byref(self._h)))
         del keep
 
     def set(self, instances):
-        inst = np.ascontiguousarray(instances, INSTANCE_DT)
+        inst = _records(instances)
         check(lib().crt_instances_set(self._h, _ptr(inst), inst.shape[0]))
 
     def set_device(self, ptr, n, sync=True):
@@ -97,7 +114,7 @@ class InstancedScene:
 
     def refit(self, instances):
         """same count, new matrices (and meshes): the TLAS refitted in place, its topology kept (crt_instances_refit)"""
-        inst = np.ascontiguousarray(instances, INSTANCE_DT)
+        inst = _records(instances)
         check(lib().crt_instances_refit(self._h, _ptr(inst), inst.shape[0]))
 
     def refit_device(self, ptr, n, sync=True):
@@ -206,7 +223,8 @@ class InstancedScene:
 
     def frame_scene(self, shading, materials, lights, width, height, max_depth=3, textures=None):
         """A Scene that renders frames of this handle's LIVE instances (crt_scene_create_instanced): every Scene method works
-        on it, and a set / refit / update_meshes between frames changes what the next frame sees (call reset()).  shading: per mesh, in mesh
+        on it, and a set / refit / update_meshes between frames changes what the next frame sees (call reset()).  Its options
+        "instance_masks" (0 / 1), "mask_primary", "mask_bounce", "mask_shadow" (0..255) apply the instances' masks to its rays (§17).  shading: per mesh, in mesh
         order, (triangles (n, 12) int32 in source order [, normals (k, 3) [, texcoords (k, 2)]]) or an object with those attributes;
         materials (m, 16) float32, lights (l, 18) float32 in WORLD space, textures (layers, H, W, 3) uint8 or None.  Close the returned scene
         before this handle: destroy, add_meshes and replace_meshes are refused while it lives."""

@@ -418,9 +418,11 @@ int crt_has_experiments(void);
  * are read. */
 typedef struct crt_blas_desc { const float* vertices; size_t n_vertices; const crt_triangle* triangles; size_t n_triangles; } crt_blas_desc;
 /* One instance: world = A * p + t, object_to_world row-major 3x4 (m[r*4 + c], column 3 = t); mesh = index into the create's meshes;
- * mask bits 0..7 = the instance's visibility mask, read by CRT_TRACE_INSTANCE_MASK traces only (bits 8..31 and reserved are ignored).
- * 64 bytes, mask at offset 52. */
-typedef struct crt_instance { float object_to_world[12]; uint32_t mesh; uint32_t mask; uint32_t reserved[2]; } crt_instance;
+ * mask bits 0..7 = the instance's visibility mask, read by CRT_TRACE_INSTANCE_MASK traces and by the frames of a bound scene whose
+ * option "instance_masks" is 1 (bits 8..31 and reserved are ignored); material_offset = what the frames of a bound scene add to the
+ * material index of every triangle of the instance's mesh (crt_scene_create_instanced, contract item 3, and its validation rule; ray
+ * queries never read it).  64 bytes, mask at offset 52, material_offset at 56. */
+typedef struct crt_instance { float object_to_world[12]; uint32_t mesh; uint32_t mask; uint32_t material_offset; uint32_t reserved; } crt_instance;
 typedef struct crt_instances crt_instances;
 typedef struct crt_instances_info {
     uint32_t n_meshes, n_instances, capacity;
@@ -602,18 +604,37 @@ typedef struct crt_instanced_scene_desc {
  * Numerical contract (tests/test_instances_frames.py holds the kernels to it):
  *   1. Primary rays, RNG, NEE, MIS, materials, textures, the sum and the resolve are the flat frame path's, bit for bit (the shading is
  *      the same source).
- *   2. The closest hit of every path ray and the occlusion of every shadow ray are crt_instances_trace's without the mask bit
- *      (CRT_TRACE_CLOSEST / CRT_TRACE_ANY on the same ray, tmax = the flat path's: 1e9 for path rays, distance to the light sample - 1e-4
- *      for shadow rays): the minimum of (t, instance, id), with the equal-t and grazing-margin exceptions documented there.
- *   3. The material is triangles[id].v[3] of the hit instance's mesh; u, v, t are used as returned; hit_point = (o + d*t) + n*0.0002f on
- *      the WORLD ray.
+ *   2. The closest hit of every path ray and the occlusion of every shadow ray are crt_instances_trace's (CRT_TRACE_CLOSEST /
+ *      CRT_TRACE_ANY on the same ray, tmax = the flat path's: 1e9 for path rays, distance to the light sample - 1e-4 for shadow rays):
+ *      the minimum of (t, instance, id), with the equal-t and grazing-margin exceptions documented there.  With option "instance_masks"
+ *      0 (the default) without the mask bit; with 1, | CRT_TRACE_INSTANCE_MASK with the ray mask of the ray's class: "mask_primary" for
+ *      the path rays of segment 0, "mask_bounce" for those of every later segment, "mask_shadow" for every NEE shadow ray.  Visibility
+ *      is (instance.mask & ray mask) != 0, so with the option on an instance of mask 0 is in no picture.
+ *   3. The material is triangles[id].v[3] of the hit instance's mesh + the instance's material_offset, an index into the scene's one
+ *      material table; everything that follows from a material (emission and its light index, type, texture, Disney parameters) follows
+ *      from that sum.  u, v, t are used as returned; hit_point = (o + d*t) + n*0.0002f on the WORLD ray.
  *   4. The normal: n_obj is what the flat path computes from that mesh's vn / normals (interpolated, or the truncated geometric normal;
  *      not normalised).  An instance whose record carries the identity flag: n = n_obj.  Otherwise, with W_r the rows of world_to_object,
  *      in fp32 without fma: m_c = (W_0c*n_obj.x + W_1c*n_obj.y) + W_2c*n_obj.z (the inverse transpose of A applied to n_obj), then
  *      n = m * (|n_obj| / |m|), |x| = sqrt((x.x*x.x + x.y*x.y) + x.z*x.z), IEEE sqrt and division, and n = m when |m| is 0 or not finite.
  *      A shading normal so keeps its file's length whatever the instance's scale, as in a flat scene, and a matrix that is numerically
  *      the identity gives n_obj back bit for bit.
- * Not offered: masks in frames, per-instance material offsets, several devices or streams, several samples per launch. */
+ *
+ * Material offsets, never an out-of-range read.  With lo / hi the least / greatest v[3] of a mesh's triangles, an instance
+ * with a non-zero material_offset is acceptable to a scene iff material_offset < 2^31 and hi + material_offset < n_materials, and either
+ * every triangle's vt of its mesh indexes that mesh's texcoords or no material in [lo + offset, hi + offset] is textured (texture layer
+ * other than -1).  Offset 0 is exempt: the per-triangle checks above cover it.  crt_scene_create_instanced applies the rule to the
+ * handle's live instances; crt_instances_set* / crt_instances_refit* on a handle with bound scenes apply it for every bound scene, on the
+ * device, to the instances they are given, before anything is published: a refused call returns CRT_ERR_INVALID (crt_last_error names
+ * the instance and the rule) and has changed nothing.  A handle without a bound scene stores any offset unchecked.
+ *
+ * Visibility masks, options of an instanced scene (crt_set_option; refused on any other scene like an unknown name, and
+ * for a value out of range, CRT_ERR_INVALID): "instance_masks" 0 (default: frames ignore masks) / 1, "mask_primary", "mask_bounce",
+ * "mask_shadow" 0..255 (default 255).  Call crt_reset after changing one, as after a camera move.  With "count_visits" the node and
+ * triangle totals of a masked frame count the steps taken: a culled TLAS child and a hidden instance cost nothing.
+ *
+ * Not offered: lights that follow an emissive instance, per-ray masks inside a class, several devices or streams,
+ * several samples per launch. */
 int crt_scene_create_instanced(const crt_instanced_scene_desc* desc, crt_scene** out);
 
 /* --------------------------------------------------- host side ([host]) ----- */
