@@ -283,6 +283,8 @@ struct crt_scene {
     uint32_t* bin_start(uint32_t seg) const { return d_bins + (size_t)17 * 5 * CRT_RAY_BINS + (size_t)seg * (CRT_RAY_BINS + 1u); }
     uint32_t* bin_ovf(uint32_t seg) const { return d_bins + (size_t)17 * 5 * CRT_RAY_BINS + (size_t)17 * (CRT_RAY_BINS + 1u) + (size_t)seg * 32u; }
     static size_t bins_words() { return (size_t)17 * 5 * CRT_RAY_BINS + (size_t)17 * (CRT_RAY_BINS + 1u) + 17u * 32u; }
+    uint32_t last_build = 1;                 // option "last_build": a one-pass launch that is the path's last segment runs the build compiled as one (k_segment<LAST>)
+    int last_launch_last = 0;                // crt_debug_launch_info: bit 2 of the build word
     uint32_t debug_fail_batch_alloc = 0;     // test hook (option of the same name): the next growth of the batch buffers fails before it allocates
     uint32_t batch_cap = 1;                  // samples the path state, the ray queues and d_lfinal are sized for (1 until crt_render_frames needs more)
     uint32_t samples_in_stats = 1;           // samples per pixel of the launch the pending stats describe (crt_render_frames batches)
@@ -1309,6 +1311,7 @@ int crt_set_option(crt_scene* s, const char* name, int value) {
         try { if (s->spans.size() < want) s->spans.resize(want); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_set_option: out of host memory (timing spans)"); }
     }
     else if (!std::strcmp(name, "ray_bins")) s->ray_bins = (uint32_t)std::min(5, std::max(0, value));
+    else if (!std::strcmp(name, "last_build")) s->last_build = value ? 1u : 0u;
     else if (!std::strcmp(name, "debug_fail_batch_alloc")) {
         // one injected failure, on ONE device: 1 = this scene's own, k >= 2 = its (k - 1)-th peer (streams / crt_set_devices); 0 disarms all
         if (value >= 2 && (size_t)(value - 2) < s->peers.size()) s->peers[(size_t)(value - 2)]->debug_fail_batch_alloc = 1u;
@@ -1501,7 +1504,7 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
     s->stats_pending = true;
     s->stats_from_frame = true;
     s->samples_in_stats = 1;
-    s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0;
+    s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0; s->last_launch_last = 0;
     return CRT_OK;
 }
 
@@ -1649,6 +1652,7 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         sa.wide_first = (b == 0 && (s->wide_first == 2u ? wide_auto : s->wide_first != 0u)) ? 1u : 0u;
         if (b == 0) { s->last_launch_form = (int)sa.wave_samples; s->last_launch_samples = (int)n_samples; }
         for (uint32_t k = 0; k < 8u; ++k) sa.rv_s[k] = k < n_samples ? rxs[k] * rys[k] : 0.f;
+        sa.last_build = s->last_build;
         EventSpan* sp = s->new_span(1);
         // option bounce_refill: the closest hits of a bounce segment through lane-refill pools (k_closest_queue), then a shade-only pass
         const bool pretraced = b > 0 && s->bounce_refill && !small_tree && !bvh2 && s->tri_min != 0u && !bins;
@@ -1671,7 +1675,7 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         uint32_t grid = s->trace_grid(P, sa.wide_first ? 6 : 5);
         if (b > 0 && batched_paths) grid *= n_samples;
         const int build = crt::launch_segment(sa, b == 0, pretraced, inplace, bvh2, s->special_materials, s->count_visits, grid, s->waves_per_workgroup, s->stream);
-        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; }
+        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; s->last_launch_last = (build >> 2) & 1; }
         if (sa.bins_out.count) {
             // fill counts -> the next launch's index space and ray count, and the next frame's capacities (the other parity)
             crt::BinScanArgs ba{};
@@ -2186,7 +2190,7 @@ static int replicate_scene(const crt_scene* src, int device, crt_scene** out) {
     r->trace_occupancy = src->trace_occupancy; r->oversubscribe = src->oversubscribe; r->waves_per_workgroup = src->waves_per_workgroup;
     r->lanes_per_ray = src->lanes_per_ray; r->bounce_refill = src->bounce_refill; r->refill_pool = src->refill_pool; r->shadow_pool = src->shadow_pool; r->shadow_refill_min = src->shadow_refill_min; r->shadow_waves = src->shadow_waves; r->persistent = src->persistent; r->sort_shadow = src->sort_shadow;
     r->wave_samples = src->wave_samples; r->wide_first = src->wide_first; r->adaptive_tiles = src->adaptive_tiles; r->timing = src->timing;
-    r->ray_bins = src->ray_bins; r->rows_padded = src->rows_padded;
+    r->ray_bins = src->ray_bins; r->rows_padded = src->rows_padded; r->last_build = src->last_build;
     for (int k = 0; k < 3; ++k) { r->bounds_lo[k] = src->bounds_lo[k]; r->bounds_hi[k] = src->bounds_hi[k]; }
     r->scene_bufs = src->scene_bufs;
     r->shares_scene = device == src->device;
@@ -2399,7 +2403,7 @@ int crt_debug_step_hist(crt_scene* s, unsigned long long* hist) {
 
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]) {
     if (!s || !info) return fail(CRT_ERR_INVALID, "crt_debug_launch_info: null argument");
-    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
+    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1) | (s->last_launch_last << 2); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
     return CRT_OK;
 }
 

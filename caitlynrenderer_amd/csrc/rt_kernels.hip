@@ -1323,9 +1323,13 @@ __device__ __forceinline__ KArgs kernarg_here() {
 // INST (PRETRACED, !INPLACE, !FIRST): the frames of an instanced scene.  The hit came from k_closest_instances_queue as
 // (instance, triangle id within the instance's mesh): the triangle, its normals and its texcoords are looked up through the instance's
 // mesh, and the object-space normal is taken to world space by the inverse transpose of the instance's matrix, rescaled to its own length.
+// LAST (the ONE builds only; DESIGN.md section 5, "the last segment at compile time"): the launch is a path's last segment, known when the
+// kernel is compiled — no bounce sampling, no next-ray queue, no path state.  The other builds skip those at run time through last_segment
+// and still carry their code, registers, zero-initialisations and join copies (measured: profiles/r06_experiments.md section 1).
 template <bool FIRST, bool STATS, bool TEX, bool PRETRACED, bool INPLACE, bool BVH2 = false, bool MAT = false, bool BATCH = false, bool WIDE = false, bool ONE = false,
-          bool INST = false>
+          bool INST = false, bool LAST = false>
 __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_FIRST : (BATCH || STATS) ? CRT_SEG_OCC_BATCH : (!FIRST && !INPLACE && !PRETRACED) ? CRT_SEG_OCC_DEFERRED : CRT_SEG_OCC)) k_segment(std::conditional_t<INST, InstSegmentArgs, SegmentArgs> a) {
+    static_assert(!LAST || (FIRST && ONE && INPLACE && !BVH2), "LAST is a form of the one-pass first-segment builds");
     extern __shared__ uint2 s_lds[];     // traversal stacks [wave][level][lane]
     // Uniform node steps are compiled into every first-segment kernel.  (In the single-sample kernel they lost while the uniform step still
     // converted bytes and the loops carried their flags — 8 x 8-pixel waves agree less than the 4 x 4-pixel waves of a batched launch, and the
@@ -1609,7 +1613,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                     const vec3 ns = normalize(n);
                     const float dn = dot(d, ns);
                     T = T * albedo;
-                    if (!ka->last_segment) {
+                    if (!LAST && !ka->last_segment) {
                         const vec3 rdir = d - ns * (2.0f * dn);
                         if (INPLACE || FIRST) ka->pb.L[pix] = make_float4(L.x, L.y, L.z, prev_pdf);      // (a deferred bounce segment leaves (L, pdf) as they are)
                         ka->pb.T[pix] = make_float4(T.x, T.y, T.z, __uint_as_float(1u | slot_mask));
@@ -1680,7 +1684,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                             }
                         }
                     }
-                    if (!ka->last_segment) {
+                    if (!LAST && !ka->last_segment) {
                         vec3 sdir;
                         float bsdf_pdf;
                         bool go_on = true;
@@ -1720,7 +1724,9 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                 }
             }
         }
-        if (ka->bins_out.count) {
+        if (LAST) {
+            // no ray goes on from a path's last segment: nothing to append
+        } else if (ka->bins_out.count) {
             const RayBins bins_out = load_bins(ka);
             CRT_MARK("loop_begin bins");      // the optional bins are not part of the instruction model (tools/roofline.py): bracketed like a loop
             // the wave's own stack region is free between the walks: the LDS table of the ranked append (3 KB) lives there when it fits
@@ -1754,7 +1760,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                     : traverse<true, STATS, UNI_K>(a.nodes, a.tris, so, sd, sh0.w, stk, (int)a.stack_entries, a.overflow, sh, nn_any, nt_any, wn_any, wt_any, &nu_any);
                 if (!occluded) L = L + V3(sh2.x, sh2.y, sh2.z);
             }
-            if (pending && emit_next) a.pb.L[pix] = make_float4(L.x, L.y, L.z, pend_pdf);     // the path goes on: its radiance so far waits in the path state
+            if (!LAST && pending && emit_next) a.pb.L[pix] = make_float4(L.x, L.y, L.z, pend_pdf);     // the path goes on: its radiance so far waits in the path state
             pending = false;                                                                   // a path that ended here adds L below
         } else {
             // ---- deferred: the shadow ray waits in this segment's region of the NEE queue for k_shadow_deferred ----
@@ -2075,7 +2081,14 @@ void launch_trace_bvh2(const Bvh2Args& a, int any, bool stats, uint32_t grid, ui
 // only (the extra branches are decided per material at run time: same arithmetic, same sums) — 33 instantiations of k_segment.
 //               k_segment<FIRST, STATS, TEX, PRETRACED, INPLACE, BVH2, MAT, BATCH, WIDE, ONE>
 #define CRT_K(F, S, T, P, Y, B2, M, BA, WI, ON) k_segment<F, S, T, P, Y, B2, M, BA, WI, ON>
-// returns bit 0: the launch ran the 6-waves-per-SIMD (WIDE) build of the first-segment kernel; bit 1: a one-pass (ONE) build (crt_debug_launch_info)
+// a one-pass first-segment build <FIRST, S, T, INPLACE, M, BATCH, WI, ONE>, in its LAST form when the launch is the path's last segment
+template <bool S, bool T, bool M, bool WI>
+static void launch_one_pass(bool last, dim3 g, dim3 b, size_t lds, hipStream_t stream, const SegmentArgs& a) {
+    if (last) launch(k_segment<true, S, T, false, true, false, M, true, WI, true, false, true>, g, b, lds, stream, a);
+    else      launch(k_segment<true, S, T, false, true, false, M, true, WI, true, false, false>, g, b, lds, stream, a);
+}
+// returns bit 0: the launch ran the 6-waves-per-SIMD (WIDE) build of the first-segment kernel; bit 1: a one-pass (ONE) build; bit 2: that
+// build's LAST form (crt_debug_launch_info)
 int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplace, bool bvh2, bool mat, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream) {
     const bool tex = a.textures != nullptr;
     // one LDS region serves the CWBVH stack (8 B per level and lane) or the BVH2 stack (4 B)
@@ -2098,13 +2111,14 @@ int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplac
         const dim3 gg = side_by_side ? dim3(grid * 4u) : in_lanes ? dim3(grid * 16u) : g, bb = side_by_side ? dim3(ws * 64u) : in_lanes ? dim3(64u) : b;
         const size_t ll = side_by_side ? lds4 : in_lanes ? per_wave : lds;
         const bool one_pass = in_lanes && a.n_samples == 4u && a.tri_min != 0u && a.lanes_log2 != 0u;      // four samples in the lanes of a wave: the builds without a sample loop
+        const bool last = a.last_segment != 0u && a.last_build != 0u;      // (option last_build 0: the builds that find out at run time)
         // counting in the TIMED form (option count_visits 2): what the uniform node steps see depends on which rays share a wave
-        if (stats && one_pass) { launch(CRT_K(true, true, true, false, true, false, true, true, false, true), gg, bb, ll, stream, v); return 2; }
-        if (feat == 2 && one_pass)      { launch(CRT_K(true, false, true, false, true, false, true, true, false, true), gg, bb, ll, stream, v); return 2; }
-        else if (feat == 1 && one_pass) { launch(CRT_K(true, false, false, false, true, false, true, true, false, true), gg, bb, ll, stream, v); return 2; }
+        if (stats && one_pass) { launch_one_pass<true, true, true, false>(last, gg, bb, ll, stream, v); return 2 | (last ? 4 : 0); }
+        if (feat == 2 && one_pass)      { launch_one_pass<false, true, true, false>(last, gg, bb, ll, stream, v); return 2 | (last ? 4 : 0); }
+        else if (feat == 1 && one_pass) { launch_one_pass<false, false, true, false>(last, gg, bb, ll, stream, v); return 2 | (last ? 4 : 0); }
         else if (feat == 2) launch(CRT_K(true, false, true, false, true, false, true, true, false, false), gg, bb, ll, stream, v);
         else if (feat == 1) launch(CRT_K(true, false, false, false, true, false, true, true, false, false), gg, bb, ll, stream, v);
-        else if (v.wide_first && one_pass) { launch(CRT_K(true, false, false, false, true, false, false, true, true, true), gg, bb, ll, stream, v); return 3; }
+        else if (v.wide_first && one_pass) { launch_one_pass<false, false, false, true>(last, gg, bb, ll, stream, v); return 3 | (last ? 4 : 0); }
         else if (v.wide_first && !side_by_side) { launch(CRT_K(true, false, false, false, true, false, false, true, true, false), gg, bb, ll, stream, v); return 1; }
         else                launch(CRT_K(true, false, false, false, true, false, false, true, false, false), gg, bb, ll, stream, v);
         return 0;

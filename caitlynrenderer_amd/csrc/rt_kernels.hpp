@@ -156,6 +156,8 @@ struct SegmentArgs {
     const uint32_t* bin_start; // segments >= 1, rays_in binned: [CRT_RAY_BINS + 1] consumer index -> bin; null = sub-queues
     const uint32_t* bin_off_in;
     uint32_t ovf_base_in;
+    uint32_t last_build;       // 1: a last segment may run the build that knows it at compile time (k_segment<LAST>; option last_build).  Behind
+                               // everything else, so that every other member keeps its place in the argument block.
 };
 // k_segment<INST>, the frames of an instanced scene.  A type of its own, so that every other k_segment keeps its argument
 // block (the hidden arguments lie behind it), and with it its code, exactly as before.
@@ -233,7 +235,7 @@ void launch_trace(const TraceArgs& a, int mode, bool stats, uint32_t grid, uint3
 void launch_trace_bvh2(const Bvh2Args& a, int any, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);
 // mat: the scene has Mirror / Disney materials (CWBVH segments only: not with bvh2)
 // inplace_shadow: the NEE shadow rays are walked inside the kernel; false = deferred to the frame's k_shadow_deferred launch
-// returns bit 0: the launch ran the 6-waves-per-SIMD (WIDE) build of the first-segment kernel, bit 1: a one-pass (ONE) build
+// returns bit 0: the launch ran the 6-waves-per-SIMD (WIDE) build of the first-segment kernel, bit 1: a one-pass (ONE) build, bit 2: its LAST form
 int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplace_shadow, bool bvh2, bool mat, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);
 // the frames of an instanced scene: ray generation, and the shade-only pass behind k_closest_instances_queue (shadow rays deferred)
 void launch_raygen(const RaygenArgs& a, hipStream_t stream);

@@ -208,6 +208,13 @@ class Scene:
         check(lib().crt_debug_launch_info(self._h, info))
         return {"form": info[0], "wide": bool(info[1] & 1), "one_pass": bool(info[1] & 2), "samples": info[2], "shards": info[3]}
 
+    def debug_last_build(self):
+        """True when the last first-segment launch ran a one-pass build compiled as a path's last segment (bit 2 of
+        crt_debug_launch_info's build word; option "last_build")"""
+        info = (C.c_int32 * 4)()
+        check(lib().crt_debug_launch_info(self._h, info))
+        return bool(info[1] & 4)
+
     def debug_step_hist(self, stop=False):
         """crt_debug_step_hist: (closest[65], any[65]) node steps of the counting frames since the previous call by number of enabled lanes"""
         if stop:

@@ -227,6 +227,10 @@ int crt_sync(crt_scene* s);
  *                         1 = for 6 (80 VGPRs), 2 (default) = 6 where the launch is bound by throughput, 5 where its longest
  *                         waves set its length (the same measure as "wave_samples"); the 6-wave build exists for the batched
  *                         launches of crt_render_frames on Lambert scenes
+ *     "last_build"        1 (default) or 0: a one-pass launch of crt_render_frames (four samples in the lanes of a wave) that is the path's
+ *                         last segment runs a build compiled as one — no bounce sampling, next-ray queue or path state in its code
+ *                         (measured in profiles/r06_experiments.md); 0 = the build that finds out at run time.
+ *                         The same operations either way: sums and visit counters keep their bits.
  *     "streams"           1 (default) .. 4, or 0 = pick for me (3 for scenes of a few nodes, 2 for max_depth > 1, else 1): that many tile shards of the frame rendered side by side on streams of their own on this one GPU
  *                         (own queues and path state, the scene buffers shared).  A multi-segment frame is a chain of dependent
  *                         launches; another shard's launches fill their tails: 1 M triangles, 4 segments, 2 streams +6 %, 8 M triangles
@@ -311,7 +315,8 @@ int crt_debug_time_graph(crt_scene* s, uint32_t n_frames, const float* rxy, uint
  * one after the other in each wave; 1 = side by side on the waves of a workgroup (option "wave_samples") */
 int crt_debug_launch_form(crt_scene* s, int32_t* form);
 /* test hook: the same launch in full: info[0] = form as above (2 = four samples of a 4 x 4 pixel quadrant in the lanes of a wave),
- * info[1] = bit 0: the first segment ran its 6-waves-per-SIMD build (option "wide_first"), bit 1: a one-pass build (no sample loop), info[2] = samples per pixel of the launch,
+ * info[1] = bit 0: the first segment ran its 6-waves-per-SIMD build (option "wide_first"), bit 1: a one-pass build (no sample loop), bit 2: that
+ * build compiled as a last segment (option "last_build"), info[2] = samples per pixel of the launch,
  * info[3] = tile shards rendering side by side (option "streams" / crt_set_devices) */
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]);
 /* measurement aid: hist[130] receives, for the counting frames ("count_visits") rendered since the previous call, how many node steps ran

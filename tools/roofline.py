@@ -59,11 +59,14 @@ def demangle_args(name):
     """k_segment<...> template arguments of a mangled name: _ZN3crt9k_segmentILb1ELb0E...EEv... -> [1,0,...]"""
     m = re.search(r"k_segmentI((?:Lb[01]E)+)E", name)
     a = [int(x) for x in re.findall(r"Lb([01])E", m.group(1))] if m else None
-    # the eleventh argument, INST (the frames of an instanced scene, DESIGN.md section 16), defaults to false: such a kernel keeps its ten-argument name here
-    return a[:10] if a and len(a) == 11 and a[10] == 0 else a
+    # the arguments behind the tenth — INST (the frames of an instanced scene, DESIGN.md section 16), LAST (the last segment at compile time,
+    # section 5) — default to false: a kernel keeps its ten-argument name here while none of them is set
+    while a and len(a) > 10 and a[-1] == 0:
+        a.pop()
+    return a
 
 
-SEG_PARAMS = ["FIRST", "STATS", "TEX", "PRETRACED", "INPLACE", "BVH2", "MAT", "BATCH", "WIDE", "ONE", "INST"]
+SEG_PARAMS = ["FIRST", "STATS", "TEX", "PRETRACED", "INPLACE", "BVH2", "MAT", "BATCH", "WIDE", "ONE", "INST", "LAST"]
 
 
 def label_of(name):
@@ -191,6 +194,9 @@ def cmd_isa(asm=None, remarks=None, tag="r03"):
     k = parse_asm(asm)
     # the kernels the bench line is made of
     want = {"first": [1, 0, 0, 0, 1, 0, 0, 1, 1, 1],     # <FIRST, INPLACE, BATCH, WIDE, ONE>: 4 samples per launch in the lanes of a wave, Lambert
+            # the same build as a one-segment frame launches it (option last_build, the default).  The I_* figures below stay those of
+            # "first": the walks are the same code, and the shell of "first" is an upper bound of what the launch executes
+            "first_last": [1, 0, 0, 0, 1, 0, 0, 1, 1, 1, 0, 1],
             "first_single": [1, 0, 0, 0, 1, 0, 0, 0, 0, 0],
             "bounce_plain": [0, 0, 0, 0, 1, 0, 0, 0, 0, 0],   # <INPLACE>: closest hit + in-place shadow walk
             "bounce_deferred": [0, 0, 0, 0, 0, 0, 0, 0, 0, 0]}    # <>: closest hit only, shadow rays left to k_shadow_deferred
