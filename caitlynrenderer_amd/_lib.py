@@ -97,6 +97,11 @@ class crt_instanced_scene_desc(C.Structure):
                 ("width", C.c_uint32), ("height", C.c_uint32), ("max_depth", C.c_uint32)]
 
 
+class crt_mesh_lights(C.Structure):
+    # struct crt_mesh_lights: one mesh's OBJECT-space lights (crt_scene_create_instanced_lit)
+    _fields_ = [("lights", C.c_void_p), ("n_lights", C.c_size_t)]
+
+
 class crt_instances_info(C.Structure):
     _fields_ = [("n_meshes", C.c_uint32), ("n_instances", C.c_uint32), ("capacity", C.c_uint32), ("stack_entries", C.c_uint32),
                 ("tlas_nodes8", C.c_uint32), ("tlas_depth8", C.c_uint32), ("max_blas_depth8", C.c_uint32), ("stack_overflows", C.c_uint32),
@@ -145,6 +150,11 @@ SYMBOLS = {
     "crt_instances_last_update": (_I, [_P, C.POINTER(_F), C.POINTER(_F), C.POINTER(C.c_uint64)]),
     "crt_instances_destroy": (_I, [_P]),
     "crt_scene_create_instanced": (_I, [C.POINTER(crt_instanced_scene_desc), C.POINTER(_P)]),
+    "crt_scene_create_instanced_lit": (_I, [C.POINTER(crt_instanced_scene_desc), C.POINTER(crt_mesh_lights), C.POINTER(_P)]),
+    "crt_scene_set_mesh_lights": (_I, [_P, _U32, _P, _SZ]),
+    "crt_scene_read_lights": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
+    "crt_instance_lights": (_I, [_P, _P, _SZ, _P]),
+    "crt_lights_finish": (_I, [_P, _SZ]),
     "crt_instance_inverse": (_I, [_P, _P]),
     "crt_instance_world_box": (_I, [_P, _P, _P]),
     "crt_debug_read_queue": (_I, [_P, _I, _U32, _P, _SZ, C.POINTER(_SZ)]),

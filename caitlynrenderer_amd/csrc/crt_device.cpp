@@ -105,6 +105,28 @@ struct RefitState {
     }
 };
 
+// The lights of an instanced scene that follow its instances (crt_scene_create_instanced_lit).  The scene's d_lights is
+// then the world table these are rebuilt into, n_lights its current total.
+struct SceneLights {
+    uint32_t n_static = 0;
+    std::vector<uint2> mesh;              // per mesh: (first light in `obj`, count)
+    std::vector<crt_light> obj;           // every mesh's object-space lights, mesh after mesh (the source of set_mesh_lights' upload)
+    float* d_static = nullptr;            // n_static x 18
+    float* d_obj = nullptr;
+    uint2* d_mesh = nullptr;
+    uint32_t* d_first = nullptr;          // per instance (the handle's capacity): the table index of its first light
+    uint32_t* d_block_sums = nullptr;     // one word per 1024 instances
+    uint32_t* d_total = nullptr;
+    float* d_partial = nullptr;           // the tree sum's partials, sized with the table
+    size_t table_cap = 0;                 // lights d_lights holds
+    uint64_t seen = 0;                    // the handle's mutation count the table was built from
+    bool stale = true;
+    ~SceneLights() {
+        void* bufs[] = {d_static, d_obj, d_mesh, d_first, d_block_sums, d_total, d_partial};
+        for (void* p : bufs) if (p) (void)hipFree(p);
+    }
+};
+
 struct crt_scene {
     int device = 0;
     int n_cu = 256;
@@ -132,13 +154,14 @@ struct crt_scene {
     // destroy.  d_nodes / d_tris / d_planes stay null: a frame reads the handle's arrays as they are when it is enqueued.  d_triangles,
     // d_normals and d_texcoords hold every mesh's arrays one after the other, d_mesh_base where each mesh's start.
     crt_instances* inst = nullptr;
-    uint4* d_mesh_base = nullptr;        // per mesh: first triangle, first normal, first texcoord, 0
+    uint4* d_mesh_base = nullptr;        // per mesh: first triangle, first normal, first texcoord, the lights it carries (§18)
     int32_t* d_qinst = nullptr;          // the hit instance of every entry of the path-ray queue (beside d_qhits)
     // material offsets and masks in its frames.  The two tables are the rule the handle holds offsets to while bound
     uint4* d_mesh_mtl = nullptr;         // per mesh: least, greatest v[3], 1 = every vt indexes the mesh's texcoords, 0
     uint32_t* d_tex_before = nullptr;    // n_materials + 1: the textured materials below each index
     uint32_t instance_masks = 0, mask_primary = 255, mask_bounce = 255, mask_shadow = 255;   // options of those names
     uint64_t cmask_seen = 0;             // the handle's child-mask pass this scene's stream last waited for
+    SceneLights* lit = nullptr;          // lights that follow the instances; null = desc->lights alone, as before
 
     // shard + frame buffers
     uint32_t rank = 0, world = 1, tile = 16;   // 16x16: four waves per tile — fine enough for the cost-sorted schedule (1 M triangles: 0.273 ms at 64, 0.257 at 16)
@@ -316,6 +339,7 @@ struct crt_scene {
         if (stream) hipStreamSynchronize(stream);
         if (inst) crt::instances_unbind(inst, stream);
         delete refit;
+        delete lit;
         if (shares_scene)                    // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
@@ -719,10 +743,17 @@ int crt_scene_create(const crt_scene_desc* d, crt_scene** out) {
     }
 }
 
+// every field of a light (p, u, v, n, e, area_pdf: 18 floats) is finite
+static bool light_finite(const crt_light& l) {
+    const float* f = l.p;
+    for (int k = 0; k < 18; ++k) if (!std::isfinite(f[k])) return false;
+    return true;
+}
+
 // A scene whose geometry is a live crt_instances handle: the shading's copies of every mesh's triangles, normals and
 // texcoords, one mesh after the other with a per-mesh table of where each starts, and the binding.  Checks are crt_scene_create's, per mesh.
-static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_scene** out) {
-    const std::string who = "crt_scene_create_instanced: ";
+static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, const struct crt_mesh_lights* mesh_lights, crt_scene** out) {
+    const std::string who = mesh_lights ? "crt_scene_create_instanced_lit: " : "crt_scene_create_instanced: ";
     if (!out) return fail(CRT_ERR_INVALID, who + "null out");
     *out = nullptr;
     if (!d) return fail(CRT_ERR_INVALID, who + "null desc");
@@ -739,6 +770,23 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
     crt::instances_view(d->instances, &v);
     if (d->n_meshes != v.n_meshes)
         return fail(CRT_ERR_INVALID, who + "n_meshes (" + std::to_string(d->n_meshes) + ") differs from the handle's mesh count (" + std::to_string(v.n_meshes) + ")");
+    // lights that follow the instances: a scene has them when some mesh carries one
+    size_t max_nl = 0, n_obj = 0;
+    if (mesh_lights)
+        for (uint32_t k = 0; k < d->n_meshes; ++k) {
+            if (mesh_lights[k].n_lights && !mesh_lights[k].lights) return fail(CRT_ERR_INVALID, who + "mesh " + std::to_string(k) + ": null lights");
+            max_nl = std::max(max_nl, mesh_lights[k].n_lights); n_obj += mesh_lights[k].n_lights;
+        }
+    const bool lit = max_nl > 0;
+    if (lit) {
+        if ((uint64_t)d->n_lights + (uint64_t)std::max(v.capacity, 1u) * max_nl >= (1ull << 31)) return fail(CRT_ERR_LIMIT, who + "the world light table could exceed 2^31 lights");
+        for (size_t i = 0; i < d->n_lights; ++i)
+            if (!light_finite(d->lights[i])) return fail(CRT_ERR_INVALID, who + "a field of light " + std::to_string(i) + " is not finite");
+        for (uint32_t k = 0; k < d->n_meshes; ++k)
+            for (size_t i = 0; i < mesh_lights[k].n_lights; ++i)
+                if (!light_finite(mesh_lights[k].lights[i])) return fail(CRT_ERR_INVALID, who + "mesh " + std::to_string(k) + ": a field of light " + std::to_string(i) + " is not finite");
+    }
+    const size_t ew_bound = lit ? std::max(d->n_lights, max_nl) : d->n_lights;
     const bool have_tex = d->albedo_textures && d->n_textures > 0;
     if (have_tex && (d->tex_width == 0 || d->tex_height == 0 || d->tex_width > 16384 || d->tex_height > 16384)) return fail(CRT_ERR_INVALID, who + "bad texture size");
     bool any_textured = false;
@@ -749,7 +797,7 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
             any_textured = true;
         }
         const float ew = d->materials[m].emission[3];
-        if (ew != -1.0f && !(ew >= 0.0f && (size_t)ew < d->n_lights)) return fail(CRT_ERR_INVALID, who + "emissive material refers to a light that does not exist");
+        if (ew != -1.0f && !(ew >= 0.0f && (size_t)ew < ew_bound)) return fail(CRT_ERR_INVALID, who + "emissive material refers to a light that does not exist");
     }
     size_t n_tris = 0, n_normals = 0, n_texcoords = 0;
     std::vector<uint4> base(d->n_meshes), mesh_mtl(d->n_meshes);
@@ -765,6 +813,13 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
         for (size_t i = 0; i < m.n_triangles; ++i) {
             const crt_triangle& t = m.triangles[i];
             if (t.v[3] < 0 || (size_t)t.v[3] >= d->n_materials) return fail(CRT_ERR_INVALID, who + mesh + "material index out of range");
+            if (lit) {                       // the triangle's own material (offset 0): mesh-local on a light-bearing mesh, else a static light
+                const float ew = d->materials[t.v[3]].emission[3];
+                const size_t nl = mesh_lights[k].n_lights;
+                if (ew != -1.0f && (size_t)ew >= (nl ? nl : d->n_lights))
+                    return fail(CRT_ERR_INVALID, who + mesh + (nl ? "an emissive triangle refers to a light its mesh does not carry"
+                                                                  : "an emissive triangle of a mesh without lights refers to a static light that does not exist"));
+            }
             mtl_lo = std::min(mtl_lo, (uint32_t)t.v[3]); mtl_hi = std::max(mtl_hi, (uint32_t)t.v[3]);
             for (int j = 0; j < 3; ++j)
                 if (t.vt[j] < 0 || (size_t)t.vt[j] >= m.n_texcoords) vt_ok = 0u;
@@ -775,7 +830,7 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
                 for (int j = 0; j < 3; ++j)
                     if (t.vt[j] < 0 || (size_t)t.vt[j] >= m.n_texcoords) return fail(CRT_ERR_INVALID, who + mesh + "texcoord index out of range");
         }
-        base[k] = make_uint4((uint32_t)n_tris, (uint32_t)n_normals, (uint32_t)n_texcoords, 0u);
+        base[k] = make_uint4((uint32_t)n_tris, (uint32_t)n_normals, (uint32_t)n_texcoords, lit ? (uint32_t)mesh_lights[k].n_lights : 0u);
         mesh_mtl[k] = make_uint4(mtl_lo, mtl_hi, vt_ok, 0u);
         n_tris += m.n_triangles; n_normals += m.n_normals; n_texcoords += m.n_texcoords;
     }
@@ -819,6 +874,26 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
         if ((rc = up(&s->d_texcoords, texcoords.data(), n_texcoords)) || (rc = up(&s->d_textures, texf.data(), n_tex))) return rc;
         s->tex_width = (int32_t)d->tex_width; s->tex_height = (int32_t)d->tex_height; s->n_textures = (int32_t)d->n_textures;
     }
+    if (lit) {
+        // the static lights, every mesh's object-space lights and the scan's arrays; the world table itself (d_lights, which holds the
+        // static lights for now) is sized and filled by the first rebuild
+        s->lit = new (std::nothrow) SceneLights;
+        SceneLights* L = s->lit;
+        if (!L) return fail(CRT_ERR_NOMEM, who + "out of memory");
+        L->n_static = (uint32_t)d->n_lights;
+        L->table_cap = d->n_lights;
+        L->mesh.resize(d->n_meshes);
+        L->obj.reserve(n_obj);
+        for (uint32_t k = 0; k < d->n_meshes; ++k) {
+            L->mesh[k] = make_uint2((uint32_t)L->obj.size(), (uint32_t)mesh_lights[k].n_lights);
+            L->obj.insert(L->obj.end(), mesh_lights[k].lights, mesh_lights[k].lights + mesh_lights[k].n_lights);
+        }
+        const size_t cap = std::max(v.capacity, 1u);
+        if ((rc = up(&L->d_static, d->lights, d->n_lights * 18)) || (rc = up(&L->d_obj, reinterpret_cast<const float*>(L->obj.data()), n_obj * 18)) ||
+            (rc = up(&L->d_mesh, L->mesh.data(), L->mesh.size())) || (rc = dev_alloc(&L->d_first, cap)) ||
+            (rc = dev_alloc(&L->d_block_sums, (cap + 1023) / 1024)) || (rc = dev_alloc(&L->d_total, 1)))
+            return rc;
+    }
     s->rows_padded = true;                   // no tree of its own
     if ((rc = finish_scene_setup(s))) return rc;
     if ((rc = crt::instances_bind(d->instances, s->stream, crt::InstOffsetRule{s->d_mesh_mtl, s->d_tex_before, (uint32_t)d->n_materials}))) return rc;
@@ -829,11 +904,99 @@ static int scene_create_instanced_impl(const crt_instanced_scene_desc* d, crt_sc
 
 int crt_scene_create_instanced(const crt_instanced_scene_desc* d, crt_scene** out) {
     try {
-        return scene_create_instanced_impl(d, out);
+        return scene_create_instanced_impl(d, nullptr, out);
     } catch (const std::exception& e) {
         if (out) *out = nullptr;
         return fail(CRT_ERR_NOMEM, std::string("crt_scene_create_instanced: ") + e.what());
     }
+}
+
+int crt_scene_create_instanced_lit(const crt_instanced_scene_desc* d, const struct crt_mesh_lights* mesh_lights, crt_scene** out) {
+    try {
+        return scene_create_instanced_impl(d, mesh_lights, out);
+    } catch (const std::exception& e) {
+        if (out) *out = nullptr;
+        return fail(CRT_ERR_NOMEM, std::string("crt_scene_create_instanced_lit: ") + e.what());
+    }
+}
+
+// The world light table of a scene with mesh lights, if the handle has changed since it was built (or crt_scene_set_mesh_lights marked
+// it): counts and scan, ONE small read for the total (the host's wait: everything queued on the stream before is then done, so a table
+// that has to grow can be freed), then transform, tree sum and pdf column on the scene's stream.  The mutators of the handle return done
+// and wait for this stream first, so the live arrays are complete and nothing in flight reads the table.
+static int ensure_light_table(crt_scene* s) {
+    SceneLights* L = s->lit;
+    if (!L) return CRT_OK;
+    crt::InstancesView v{};
+    crt::instances_view(s->inst, &v);
+    if (!L->stale && L->seen == v.mutations) return CRT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    crt::LightTableArgs a{};
+    a.mesh_of = v.mesh_of; a.o2w = v.o2w; a.w2o = v.w2o; a.mesh_lights = L->d_mesh; a.obj_lights = L->d_obj; a.static_lights = L->d_static;
+    a.n_instances = v.n_instances; a.n_meshes = v.n_meshes; a.n_static = L->n_static;
+    a.first = L->d_first; a.block_sums = L->d_block_sums; a.total = L->d_total;
+    crt::launch_light_scan(a, s->stream);
+    uint32_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, L->d_total, 4, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipGetLastError());
+    const uint64_t n_total = (uint64_t)L->n_static + total;
+    if (n_total >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "the world light table exceeds 2^31 lights");
+    if (n_total > L->table_cap || !L->d_partial) {
+        const size_t cap = std::max<size_t>(n_total + n_total / 2, 64);
+        float* table = nullptr; float* partial = nullptr;
+        int rc;
+        if ((rc = dev_alloc(&table, cap * 18))) return rc;
+        if ((rc = dev_alloc(&partial, 2 * ((cap + 255) / 256)))) { (void)hipFree(table); return rc; }
+        if (s->d_lights) (void)hipFree(s->d_lights);
+        if (L->d_partial) (void)hipFree(L->d_partial);
+        s->d_lights = table; L->d_partial = partial; L->table_cap = cap;
+    }
+    a.table = s->d_lights; a.partial = L->d_partial; a.n_total = (uint32_t)n_total;
+    crt::launch_light_table(a, s->stream);
+    HIPCHK(hipGetLastError());
+    s->n_lights = (uint32_t)n_total;
+    L->seen = v.mutations; L->stale = false;
+    return CRT_OK;
+}
+
+int crt_scene_set_mesh_lights(crt_scene* s, uint32_t mesh, const crt_light* lights, size_t n_lights) {
+    const std::string who = "crt_scene_set_mesh_lights: ";
+    if (!s) return fail(CRT_ERR_INVALID, who + "null scene");
+    if (!s->inst || !s->lit) return fail(CRT_ERR_INVALID, who + "the scene has no mesh lights (crt_scene_create_instanced_lit)");
+    SceneLights* L = s->lit;
+    if (mesh >= L->mesh.size()) return fail(CRT_ERR_INVALID, who + "mesh index out of range");
+    if (n_lights != L->mesh[mesh].y) return fail(CRT_ERR_INVALID, who + "n_lights differs from the count given at create");
+    if (n_lights && !lights) return fail(CRT_ERR_INVALID, who + "null lights");
+    for (size_t i = 0; i < n_lights; ++i)
+        if (!light_finite(lights[i])) return fail(CRT_ERR_INVALID, who + "a field of light " + std::to_string(i) + " is not finite");
+    if (n_lights == 0) return CRT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    std::copy(lights, lights + n_lights, L->obj.begin() + L->mesh[mesh].x);
+    // behind whatever the stream holds (frames that read the table built from the old lights), from the scene's own copy
+    HIPCHK(hipMemcpyAsync(L->d_obj + 18 * (size_t)L->mesh[mesh].x, L->obj.data() + L->mesh[mesh].x, n_lights * sizeof(crt_light), hipMemcpyHostToDevice, s->stream));
+    L->stale = true;
+    return CRT_OK;
+}
+
+int crt_scene_read_lights(crt_scene* s, crt_light* dst, size_t cap, size_t* n_out) {
+    const std::string who = "crt_scene_read_lights: ";
+    if (!s) return fail(CRT_ERR_INVALID, who + "null scene");
+    if (!s->inst) return fail(CRT_ERR_INVALID, who + "not an instanced scene");
+    try {
+        const int rc = ensure_light_table(s);
+        if (rc) return rc;
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, who + e.what());
+    }
+    if (n_out) *n_out = s->n_lights;
+    if (!dst) return CRT_OK;
+    if (cap < s->n_lights) return fail(CRT_ERR_INVALID, who + "destination too small");
+    if (s->n_lights == 0) return CRT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipMemcpy(dst, s->d_lights, (size_t)s->n_lights * sizeof(crt_light), hipMemcpyDeviceToHost));
+    return CRT_OK;
 }
 
 static int scene_create_impl(const crt_scene_desc* d, crt_scene** out) {
@@ -1428,6 +1591,7 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
 // segment's queue and the shade-only pass, then ONE two-level any-hit launch for every segment's shadow rays and the fold — the
 // bounce_refill 1 + inplace_shadow 0 sequence below with segment 0 included.  The handle's live arrays are read HERE, at enqueue time.
 static int render_instanced_async(crt_scene* s, float rx, float ry) {
+    if (s->lit) { const int rc = ensure_light_table(s); if (rc) return rc; }      // lights that follow the instances
     crt::InstancesView v{};
     crt::instances_view(s->inst, &v);
     const uint32_t P = s->n_local_pixels;
@@ -1483,6 +1647,7 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
         sa.l_final = s->d_lfinal;
         sa.n_samples = 1u; sa.rv_s[0] = rx * ry;
         sa.hit_inst = s->d_qinst; sa.inst_w2o = v.w2o; sa.inst_mesh = v.mesh_of; sa.mesh_base = s->d_mesh_base;
+        sa.light_first = s->lit ? s->lit->d_first : nullptr;
         timed(3, [&] { crt::launch_segment_instanced(sa, s->count_visits, s->trace_grid(P, 5), s->waves_per_workgroup, s->stream); });
     }
     crt::InstMaskShadowArgs sh{};

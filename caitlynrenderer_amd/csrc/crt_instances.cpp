@@ -20,6 +20,7 @@
 #include "crt_error.hpp"
 #include "device_build.hpp"
 #include "host/instance_math.hpp"
+#include "host/light_math.hpp"
 #include "host/refit_core.hpp"
 #include "instances.hpp"
 #include "instances_bind.hpp"
@@ -94,6 +95,11 @@ struct crt_instances {
     float* d_box = nullptr;
     float* d_w2o_stage = nullptr;
     uint2* d_mesh_of_stage = nullptr;
+    // object_to_world as the last successful set / refit gave it (debug read 7), staged by the prep like world_to_object: d_in belongs to
+    // the last ATTEMPTED call.  Ray queries never read it; the light tables of bound scenes do
+    float* d_o2w = nullptr;
+    float* d_o2w_stage = nullptr;
+    uint64_t mutations = 0;               // successful publishes, refits and mesh updates so far: what a bound scene's light table is dated by
     crt_node8* d_t8_stage = nullptr;      // the converter's output (tlas_cap_nodes)
     uint32_t* d_flag = nullptr;           // the verdict of a call's device checks: [0] what failed, [1] the first instance a bound scene refuses
     uint32_t* d_overflow = nullptr;
@@ -134,7 +140,7 @@ struct crt_instances {
     ~crt_instances() {
         void* bufs[] = {d_nodes, d_tris, d_inst, d_w2o, d_wbox, d_mesh_box, d_mesh_root, d_in, d_rec, d_box, d_w2o_stage, d_flag, d_overflow,
                         d_t8_stage, d_t_rays, d_t_hits, d_t_inst, d_t_stats, d_tlas_order, d_tlas_box8, d_box_idx, d_tlas_table, d_cmask, d_cm_parent,
-                        d_cm_leaf, d_mesh_of, d_mesh_of_stage};
+                        d_cm_leaf, d_mesh_of, d_mesh_of_stage, d_o2w, d_o2w_stage};
         if (stream) (void)hipStreamSynchronize(stream);
         upd.reset();
         for (void* p : bufs) if (p) (void)hipFree(p);
@@ -243,6 +249,7 @@ int prep_instances(crt_instances* s, const void* d_src, uint32_t n, const MeshTa
     crt::InstPrepArgs pa{};
     pa.in = static_cast<const uint32_t*>(d_src); pa.n = n; pa.n_meshes = mt.n_meshes; pa.mesh_box = mt.d_box; pa.mesh_root = mt.d_root;
     pa.rec = s->d_rec; pa.box = s->d_box; pa.w2o = s->d_w2o_stage; pa.flag = s->d_flag; pa.mesh_of = s->d_mesh_of_stage;
+    pa.o2w = s->d_o2w_stage;
     crt::launch_instance_prep(pa, st);
     // every bound scene's rule for material offsets against the STAGED words, into the same verdict: still one wait
     for (const auto& b : s->bound) check_offsets(s, b.rule, s->d_mesh_of_stage, n, mt.n_meshes);
@@ -296,6 +303,7 @@ int publish_tlas(crt_instances* s, const void* d_src, uint32_t n, const TlasStag
     IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
     IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
     IHIPCHK(hipMemcpyAsync(s->d_mesh_of, s->d_mesh_of_stage, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    IHIPCHK(hipMemcpyAsync(s->d_o2w, s->d_o2w_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
     if (s->upd && d_src != s->upd->d_live)
         IHIPCHK(hipMemcpyAsync(s->upd->d_live, d_src, (size_t)n * sizeof(crt_instance), hipMemcpyDeviceToDevice, st));
     return CRT_OK;
@@ -319,6 +327,7 @@ int set_impl(crt_instances* s, const void* d_src, uint32_t n) {
         s->n_tlas8 = 0; s->tlas_depth8 = 0; s->stack_entries = 2;
     }
     s->n_instances = n;
+    ++s->mutations;
     IHIPCHK(hipEventRecord(s->ev1, st));
     IHIPCHK(hipGetLastError());
     IHIPCHK(hipEventSynchronize(s->ev1));
@@ -375,12 +384,14 @@ int refit_impl(crt_instances* s, const void* d_src, uint32_t n, const std::strin
         IHIPCHK(hipMemcpyAsync(s->d_w2o, s->d_w2o_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
         IHIPCHK(hipMemcpyAsync(s->d_wbox, s->d_box, (size_t)n * 24, hipMemcpyDeviceToDevice, st));
         IHIPCHK(hipMemcpyAsync(s->d_mesh_of, s->d_mesh_of_stage, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+        IHIPCHK(hipMemcpyAsync(s->d_o2w, s->d_o2w_stage, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
         if (s->upd && d_src != s->upd->d_live)
             IHIPCHK(hipMemcpyAsync(s->upd->d_live, d_src, (size_t)n * sizeof(crt_instance), hipMemcpyDeviceToDevice, st));
     }
     IHIPCHK(hipEventRecord(s->ev1, st));
     IHIPCHK(hipEventSynchronize(s->ev1));             // the publication is done when the call returns
     IHIPCHK(hipGetLastError());
+    ++s->mutations;
     IHIPCHK(hipEventElapsedTime(&s->set_device_ms, s->ev0, s->ev1));
     s->set_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
@@ -559,6 +570,7 @@ int update_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const float* 
     IHIPCHK(hipGetLastError());
     if (ni > 0) { s->n_tlas8 = ts.n8; s->tlas_depth8 = ts.depth8; s->stack_entries = ts.stack; }
     u->mesh_box.swap(u->box_stage);
+    ++s->mutations;
     IHIPCHK(hipEventElapsedTime(&u->device_ms, u->ev0, u->ev1));
     u->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     u->have_times = true;
@@ -657,7 +669,8 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
         (rc = alloc(&s->d_overflow, 1)) || (rc = alloc(&s->d_t8_stage, s->tlas_cap_nodes)) || (rc = alloc(&s->d_tlas_box8, 6 * (size_t)s->tlas_cap_nodes)) ||
         (rc = alloc(&s->d_box_idx, C * 3)) || (rc = alloc(&s->d_tlas_table, sizeof(crt::RefitMesh) + 255 * sizeof(crt::RefitSeg))) ||
         (rc = alloc(&s->d_cmask, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_parent, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_leaf, C)) ||
-        (rc = alloc(&s->d_mesh_of, C)) || (rc = alloc(&s->d_mesh_of_stage, C)))
+        (rc = alloc(&s->d_mesh_of, C)) || (rc = alloc(&s->d_mesh_of_stage, C)) ||
+        (rc = alloc(&s->d_o2w, C * 12)) || (rc = alloc(&s->d_o2w_stage, C * 12)))
         return rc;
     crt::launch_box_triples(s->d_box_idx, capacity, st);
     IHIPCHK(hipMemsetAsync(s->d_overflow, 0, 4, st));
@@ -892,6 +905,7 @@ int remesh_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const crt_bla
     IHIPCHK(hipGetLastError());
     IHIPCHK(hipEventElapsedTime(&s->set_device_ms, s->ev0, s->ev1));
     if (first_id) *first_id = M0;
+    ++s->mutations;
     s->set_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
 }
@@ -902,7 +916,7 @@ namespace crt {
 
 void instances_view(const crt_instances* h, InstancesView* out) {
     *out = InstancesView{h->device, h->d_nodes, h->d_tris, h->d_inst, h->d_w2o, h->d_mesh_of, h->d_cmask, h->n_instances, h->stack_entries, h->n_meshes,
-                         h->n_tlas8, h->tlas_depth8, h->max_blas_depth8, h->blas_nodes8, h->blas_tris};
+                         h->n_tlas8, h->tlas_depth8, h->max_blas_depth8, h->blas_nodes8, h->blas_tris, h->d_o2w, h->capacity, h->mutations};
 }
 uint32_t instances_mesh_triangles(const crt_instances* h, uint32_t mesh) { return h->mesh[mesh].n_tris; }
 int instances_bind(crt_instances* h, hipStream_t stream, const InstOffsetRule& rule) {
@@ -952,6 +966,39 @@ int crt_instance_inverse(const float object_to_world[12], float world_to_object[
 int crt_instance_world_box(const float object_to_world[12], const float box[6], float out[6]) {
     if (!object_to_world || !box || !out) return fail(CRT_ERR_INVALID, "crt_instance_world_box: null argument");
     crt::instance_world_box(object_to_world, box, out);
+    return CRT_OK;
+}
+
+int crt_instance_lights(const float object_to_world[12], const crt_light* in, size_t n, crt_light* out) {
+    if (!object_to_world || (n && (!in || !out))) return fail(CRT_ERR_INVALID, "crt_instance_lights: null argument");
+    float w[12];
+    if (!crt::instance_inverse(object_to_world, w))
+        return fail(CRT_ERR_INVALID, "crt_instance_lights: the matrix is not finite, or singular, or its inverse is not finite");
+    const bool identity = crt::instance_is_identity(object_to_world);
+    for (size_t k = 0; k < n; ++k) {
+        float src[18], dst[18];
+        std::memcpy(src, &in[k], sizeof src);
+        crt::light_to_world(object_to_world, w, identity, src, dst);
+        std::memcpy(&out[k], dst, sizeof dst);
+    }
+    return CRT_OK;
+}
+
+int crt_lights_finish(crt_light* lights, size_t n) {
+    if (n && !lights) return fail(CRT_ERR_INVALID, "crt_lights_finish: null argument");
+    if (n == 0) return CRT_OK;
+    try {
+        size_t p2 = 1;
+        while (p2 < n) p2 <<= 1;
+        std::vector<float> a(p2, 0.0f);
+        for (size_t k = 0; k < n; ++k) a[k] = crt::light_area_term(lights[k].area_pdf[0]);
+        for (size_t m = p2; m > 1; m >>= 1)
+            for (size_t j = 0; j < m / 2; ++j) a[j] = a[2 * j] + a[2 * j + 1];
+        const float S = a[0];
+        for (size_t k = 0; k < n; ++k) lights[k].area_pdf[1] = crt::light_pdf(crt::light_area_term(lights[k].area_pdf[0]), S);
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_lights_finish: ") + e.what());
+    }
     return CRT_OK;
 }
 
@@ -1070,7 +1117,7 @@ int crt_instances_get_info(crt_instances* s, crt_instances_info* out) {
     i.blas_nodes8 = s->blas_nodes8; i.blas_tris = s->blas_tris;
     i.blas_bytes = s->blas_nodes8 * sizeof(crt_node8) + s->blas_tris * 48;
     i.tlas_bytes = (uint64_t)s->tlas_cap_nodes * sizeof(crt_node8);
-    i.instance_bytes = (uint64_t)s->capacity * (64 + 48 + 24 + 64 + 64 + 24 + 48)    // live records, matrices, boxes + the set's staging
+    i.instance_bytes = (uint64_t)s->capacity * (64 + 48 + 24 + 64 + 64 + 24 + 48 + 48 + 48)    // live records, matrices (both ways), boxes + the set's staging
                        + (uint64_t)s->tlas_cap_nodes * (8 + 4) + (uint64_t)s->capacity * 4;   // TLAS child masks + their parent / leaf links
     i.tlas_build_bytes = (uint64_t)s->arena.cap + (uint64_t)s->tlas_cap_nodes * sizeof(crt_node8);   // the TLAS builder's arena + node staging
     i.set_device_ms = s->set_device_ms; i.set_wall_ms = s->set_wall_ms; i.create_wall_ms = s->build_wall_ms;
@@ -1090,7 +1137,8 @@ int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_
         case 4: src = s->d_nodes + 5 * (size_t)s->tlas_cap_nodes; n = s->blas_nodes8; item = sizeof(crt_node8); break;
         case 5: src = s->d_tris; n = s->blas_tris; item = 48; break;
         case 6: src = s->d_cmask; n = s->n_instances ? s->n_tlas8 : 0; item = 8; break;
-        default: return fail(CRT_ERR_INVALID, "crt_instances_debug_read: which must be 0..6");
+        case 7: src = s->d_o2w; n = s->n_instances; item = 48; break;
+        default: return fail(CRT_ERR_INVALID, "crt_instances_debug_read: which must be 0..7");
     }
     if (n_out) *n_out = n;
     if (!dst || n == 0) return CRT_OK;

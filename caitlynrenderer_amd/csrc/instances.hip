@@ -14,6 +14,8 @@
 #include "rt_math.hpp"
 #include "rt_traverse.hpp"
 #include "host/instance_math.hpp"
+#define CRT_LIGHT_DEVICE_MATH 1      // light_math.hpp: sqrt_ieee / rcp_ieee of rt_math.hpp in device code
+#include "host/light_math.hpp"
 
 namespace crt {
 
@@ -43,6 +45,7 @@ __global__ void __launch_bounds__(256) k_instance_prep(InstPrepArgs a) {
     for (int k = 0; k < 6; ++k) a.box[6 * (size_t)i + k] = box[k];
     for (int k = 0; k < 12; ++k) a.w2o[12 * (size_t)i + k] = w[k];
     a.mesh_of[i] = make_uint2(mesh | (instance_is_identity(m) ? 0x80000000u : 0u), src[14]);
+    for (int k = 0; k < 12; ++k) a.o2w[12 * (size_t)i + k] = m[k];
 }
 
 // A bound scene's rule for material offsets (include/crt.h crt_scene_create_instanced) against (mesh, offset) words: those a
@@ -161,6 +164,127 @@ __global__ void __launch_bounds__(256) k_tlas_mask_up(const float4* __restrict__
     }
 }
 
+// ---- the world light table of a scene with mesh lights (crt_scene_create_instanced_lit) ----
+
+// Scan, pass 1: 1024 instances per block, four consecutive ones per thread.  first[i] = the lights of the block's instances before i,
+// block_sums[block] = the block's lights.
+__global__ void __launch_bounds__(256) k_light_counts(LightTableArgs a) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t t = threadIdx.x, i0 = blockIdx.x * 1024u + 4u * t;
+    uint32_t c[4], mine = 0u;
+    for (uint32_t k = 0; k < 4u; ++k) {
+        c[k] = 0u;
+        if (i0 + k < a.n_instances) {
+            const uint32_t mesh = a.mesh_of[i0 + k].x & 0x7fffffffu;
+            if (mesh < a.n_meshes) c[k] = a.mesh_lights[mesh].y;
+        }
+        mine += c[k];
+    }
+    uint32_t incl = mine;                                     // inclusive scan over the wave, then over the block's four waves
+    const uint32_t lane = t & 63u, wave = t >> 6;
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t up = __shfl_up(incl, off);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0u, all = 0u;
+    for (uint32_t w = 0; w < 4u; ++w) { if (w < wave) before += s_wave[w]; all += s_wave[w]; }
+    uint32_t run = before + incl - mine;
+    for (uint32_t k = 0; k < 4u; ++k) {
+        if (i0 + k < a.n_instances) a.first[i0 + k] = run;
+        run += c[k];
+    }
+    if (t == 0u) a.block_sums[blockIdx.x] = all;
+}
+
+// Scan, pass 2, ONE block: block_sums[] -> their exclusive prefix sums in place, total[0] = the sum of all
+__global__ void __launch_bounds__(256) k_light_block_scan(uint32_t* __restrict__ block_sums, uint32_t n_blocks, uint32_t* __restrict__ total) {
+    __shared__ uint32_t s_wave[4];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    uint32_t carry = 0u;
+    for (uint32_t base = 0; base < n_blocks; base += 256u) {
+        const uint32_t mine = base + t < n_blocks ? block_sums[base + t] : 0u;
+        uint32_t incl = mine;
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off);
+            if (lane >= off) incl += up;
+        }
+        __syncthreads();                                      // the previous round's s_wave has been read
+        if (lane == 63u) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0u, all = 0u;
+        for (uint32_t w = 0; w < 4u; ++w) { if (w < wave) before += s_wave[w]; all += s_wave[w]; }
+        if (base + t < n_blocks) block_sums[base + t] = carry + before + incl - mine;
+        carry += all;
+    }
+    if (t == 0u) total[0] = carry;
+}
+
+// Scan, pass 3: first[i] += its block's prefix + n_static
+__global__ void __launch_bounds__(256) k_light_first(LightTableArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_instances) return;
+    a.first[i] += a.block_sums[i >> 10] + a.n_static;
+}
+
+// One lane per light of the table.  A static light is copied; any other finds its instance by binary search in first[] (the LAST
+// instance whose first light is at or before it: instances without lights repeat their successor's value and are never the last) and
+// is its mesh's object-space light through that instance's live matrices (light_math.hpp).  Lane-per-light, not wave-per-instance: the
+// work per lane is the same whatever the meshes' light counts, and the 18 steps of a search at 256 k instances read a 1 MB array that
+// stays in L2 — less than the 72 B it then writes.
+__global__ void __launch_bounds__(256) k_light_transform(LightTableArgs a) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n_total) return;
+    float* out = a.table + 18 * (size_t)k;
+    if (k < a.n_static) {
+        for (int j = 0; j < 18; ++j) out[j] = a.static_lights[18 * (size_t)k + j];
+        return;
+    }
+    uint32_t lo = 0u, hi = a.n_instances;                     // first[lo] <= k < first[hi] (first[n] = n_total)
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (a.first[mid] <= k) lo = mid; else hi = mid;
+    }
+    const uint32_t word = a.mesh_of[lo].x, mesh = word & 0x7fffffffu;
+    const uint32_t j = k - a.first[lo];
+    float in[18], res[18];
+    bool ok = mesh < a.n_meshes;
+    uint2 ml = make_uint2(0u, 0u);
+    if (ok) { ml = a.mesh_lights[mesh]; ok = j < ml.y; }
+    if (!ok) {                                                // cannot happen while first[] and the live words agree: leave a dark light
+        for (int q = 0; q < 18; ++q) out[q] = 0.0f;
+        return;
+    }
+    const float* src = a.obj_lights + 18 * ((size_t)ml.x + j);
+    for (int q = 0; q < 18; ++q) in[q] = src[q];
+    float A[12], W[12];
+    for (int q = 0; q < 12; ++q) { A[q] = a.o2w[12 * (size_t)lo + q]; W[q] = a.w2o[12 * (size_t)lo + q]; }
+    light_to_world(A, W, (word & 0x80000000u) != 0u, in, res);
+    for (int q = 0; q < 18; ++q) out[q] = res[q];
+}
+
+// The pairwise tree sum (include/crt.h): each block leaves the tree sum of an aligned chunk of 256 values (missing ones +0) — lane
+// offsets 1, 2, 4 .. 32 inside a wave, then the four waves pairwise — so that a further pass over the partials continues the same tree.
+// AREAS: the values are the area terms of the table's lights; else plain floats.
+template <bool AREAS>
+__global__ void __launch_bounds__(256) k_light_tree_sum(const float* __restrict__ src, uint32_t n, float* __restrict__ dst) {
+    __shared__ float s_wave[4];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    float v = 0.0f;
+    if (i < n) v = AREAS ? light_area_term(src[18 * (size_t)i + 15]) : src[i];
+    for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off);
+    if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0u) dst[blockIdx.x] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+}
+
+__global__ void __launch_bounds__(256) k_light_pdf(float* __restrict__ table, uint32_t n, const float* __restrict__ sum) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    table[18 * (size_t)i + 16] = light_pdf(light_area_term(table[18 * (size_t)i + 15]), sum[0]);
+}
+
 // One lane per ray, pools of 64 rays per wave with lane refill (k_trace's mapping with crt_trace's default pool of 64: each 256-ray slot
 // of the index space is walked by four single-wave workgroups); the walk itself is instances_walk_loop.hpp.
 template <bool ANY, bool STATS, bool MASK>
@@ -270,6 +394,29 @@ static inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255u) / 25
 
 void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream) {
     if (a.n) hipLaunchKernelGGL(k_instance_prep, grid_for(a.n), dim3(256), 0, stream, a);
+}
+void launch_light_scan(const LightTableArgs& a, hipStream_t stream) {
+    const uint32_t blocks = (a.n_instances + 1023u) / 1024u;
+    if (a.n_instances) hipLaunchKernelGGL(k_light_counts, dim3(blocks), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_light_block_scan, dim3(1), dim3(256), 0, stream, a.block_sums, blocks, a.total);
+    if (a.n_instances) hipLaunchKernelGGL(k_light_first, grid_for(a.n_instances), dim3(256), 0, stream, a);
+}
+void launch_light_table(const LightTableArgs& a, hipStream_t stream) {
+    if (!a.n_total) return;
+    hipLaunchKernelGGL(k_light_transform, grid_for(a.n_total), dim3(256), 0, stream, a);
+    // the tree sum: passes of 256 until one value is left, alternating between the two regions of a.partial
+    uint32_t n = a.n_total;
+    const uint32_t region = (a.n_total + 255u) / 256u;
+    float* dst = a.partial;
+    hipLaunchKernelGGL((k_light_tree_sum<true>), grid_for(n), dim3(256), 0, stream, a.table, n, dst);
+    n = (n + 255u) / 256u;
+    while (n > 1u) {
+        float* next = dst == a.partial ? a.partial + region : a.partial;
+        hipLaunchKernelGGL((k_light_tree_sum<false>), grid_for(n), dim3(256), 0, stream, dst, n, next);
+        dst = next;
+        n = (n + 255u) / 256u;
+    }
+    hipLaunchKernelGGL(k_light_pdf, grid_for(a.n_total), dim3(256), 0, stream, a.table, a.n_total, dst);
 }
 void launch_instance_offsets(const InstOffsetCheckArgs& a, hipStream_t stream) {
     if (a.n) hipLaunchKernelGGL(k_instance_offsets, grid_for(a.n), dim3(256), 0, stream, a);

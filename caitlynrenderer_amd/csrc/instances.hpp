@@ -39,6 +39,7 @@ struct InstPrepArgs {
     uint32_t* flag;            // |= 1 matrix not finite / singular / inverse not finite, 2 mesh index out of range, 4 world box beyond 1e18
     uint2* mesh_of;            // x: the instance's mesh index, bit 31 = the identity flag (what a frame's shading looks the hit triangle up by;
                                // DESIGN.md §16), y: crt_instance.material_offset (what it adds to the triangle's material; §17)
+    float* o2w;                // 12 floats per instance: object_to_world as given (what the light tables of §18 transform by)
 };
 // What a scene bound to the handle admits as material offsets (crt_scene_create_instanced's validation rule)
 struct InstOffsetRule {
@@ -89,6 +90,27 @@ struct InstShadowArgs {        // k_shadow_instances_deferred: the frame's defer
 };
 
 struct InstMaskShadowArgs : InstShadowArgs { uint32_t ray_mask; };
+
+// The world light table of a scene with mesh lights (crt_scene_create_instanced_lit), rebuilt from the handle's live arrays.
+struct LightTableArgs {
+    const uint2* mesh_of;      // live, per instance: (mesh | identity bit 31, material offset)
+    const float* o2w;          // live object_to_world, 12 floats per instance
+    const float* w2o;          // live world_to_object
+    const uint2* mesh_lights;  // per mesh: (first light in obj_lights, count)
+    const float* obj_lights;   // every mesh's object-space lights, 18 floats each
+    const float* static_lights;// n_static world lights as given at create
+    uint32_t n_instances, n_meshes, n_static;
+    uint32_t* first;           // per instance: table index of its first light (n_static + exclusive prefix sum of the counts)
+    uint32_t* block_sums;      // one word per 1024 instances
+    uint32_t* total;           // [0] = lights of all instances (without n_static)
+    float* table;              // n_total x 18 floats
+    uint32_t n_total;
+    float* partial;            // the tree sum's partials: two regions of ceil(n_total / 256) floats
+};
+// per-instance counts and their exclusive scan into first[] (+ n_static), the total into total[0].  Enqueued only
+void launch_light_scan(const LightTableArgs& a, hipStream_t stream);
+// with a.n_total known (n_static + total[0]): every table entry, then the tree sum of the areas and the pdf column.  Enqueued only
+void launch_light_table(const LightTableArgs& a, hipStream_t stream);
 
 void launch_instance_prep(const InstPrepArgs& a, hipStream_t stream);
 void launch_instance_offsets(const InstOffsetCheckArgs& a, hipStream_t stream);

@@ -21,6 +21,9 @@ struct InstancesView {
     uint32_t n_instances, stack_entries, n_meshes;
     uint32_t tlas_nodes8, tlas_depth8, max_blas_depth8;
     uint64_t blas_nodes8, blas_tris;
+    const float* o2w;          // object_to_world, 12 floats per instance, instance order: what the light tables of DESIGN.md §18 move by
+    uint32_t capacity;
+    uint64_t mutations;        // successful sets, refits and mesh updates so far
 };
 void instances_view(const crt_instances* h, InstancesView* out);
 uint32_t instances_mesh_triangles(const crt_instances* h, uint32_t mesh);     // mesh < n_meshes

@@ -1531,6 +1531,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
             const size_t rec_rows = BVH2 ? 3u : (size_t)CRT_TRI_ROWS;            // the BVH2 walk's slot-ordered records stay packed
             int slot, mtl;
             uint32_t inst_word = 0u, inst_id = 0u, normal0 = 0u, texcoord0 = 0u;   // INST: (identity flag | mesh) of the hit instance, and its mesh's places in the scene's arrays
+            uint32_t mesh_nl = 0u;                                                   // INST: the lights its mesh carries
             if constexpr (INST) {
                 inst_id = (uint32_t)a.hit_inst[(size_t)g * ka->sub_capacity + e];
                 const uint2 iw = a.inst_mesh[inst_id];
@@ -1538,7 +1539,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                 const uint4 mb = a.mesh_base[inst_word & 0x7fffffffu];
                 slot = (int)mb.x + hit.tri;                                         // hit.tri: the triangle's id within its mesh = its index in the mesh's source-order triangles
                 mtl = ka->triangles[3 * (size_t)slot].w + (int)iw.y;                // + the instance's material offset: in range by the bound scene's rule
-                normal0 = mb.y; texcoord0 = mb.z;
+                normal0 = mb.y; texcoord0 = mb.z; mesh_nl = mb.w;
             } else {
                 const float4 tb = recs[rec_rows * (size_t)hit.tri + 1], tc = recs[rec_rows * (size_t)hit.tri + 2];
                 slot = __float_as_int(tb.w); mtl = __float_as_int(tc.w);
@@ -1580,6 +1581,27 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                     ld = normalize(ld);
                     const float cos_light = -1.0f * dot(ld, n);
                     const float len2 = len * len;
+                    if constexpr (INST) {
+                        // a scene with mesh lights: on a light-bearing mesh emission.w is mesh-local, behind the hit instance's
+                        // first light; elsewhere a table index.  Clamped either way: no material offset can cause an out-of-range read
+                        int li = (int)m_emission.w;                               // a scene without mesh lights reads lights[li] unclamped, as it always has: create holds every emissive material to the table
+                        bool no_light = false;
+                        if (a.light_first != nullptr) {
+                            const int ew = li < 0 ? 0 : li;
+                            if (mesh_nl > 0u) li = (int)(a.light_first[inst_id] + (uint32_t)(ew < (int)mesh_nl - 1 ? ew : (int)mesh_nl - 1));
+                            else if (ka->n_lights > 0) li = ew < ka->n_lights - 1 ? ew : ka->n_lights - 1;
+                            else no_light = true;                                 // an empty table: no light can be sampled, the BSDF-sampled hit takes everything
+                        }
+                        if (no_light) contribute(T * em);
+                        else {
+                            const float* ap = ka->lights + 18 * (size_t)li + 15;
+                            float pdf_light = __fdiv_rn(len2, ap[0] * cos_light) * ap[1];
+                            if (MAT && true_area) pdf_light = 2.0f * pdf_light;
+                            const float tt = prev_pdf * prev_pdf;
+                            const float w = __fdiv_rn(tt, pdf_light * pdf_light + tt);
+                            contribute((T * em) * w);
+                        }
+                    } else {      // every other k_segment: these lines stay byte for byte as they were, indentation included — sharing them with the arm above rescheduled two flat kernels
                     const int li = (int)m_emission.w;
                     const float* ap = ka->lights + 18 * (size_t)li + 15;
                     float pdf_light = __fdiv_rn(len2, ap[0] * cos_light) * ap[1];
@@ -1587,6 +1609,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                     const float tt = prev_pdf * prev_pdf;                         // power_heuristic :214-218
                     const float w = __fdiv_rn(tt, pdf_light * pdf_light + tt);
                     contribute((T * em) * w);
+                    }
                 }
             } else {
                 const vec3 hit_point = (o + d * t) + n * 0.0002f;                 // path_trace.fs:930

@@ -165,7 +165,10 @@ struct InstSegmentArgs : SegmentArgs {
     const int32_t* hit_inst;   // parallel to hits_in: the hit's instance (hits_in's w = the triangle's id within that instance's mesh)
     const float* inst_w2o;     // world_to_object, 12 floats per instance, instance order (the handle's live array)
     const uint2* inst_mesh;    // per instance: (its mesh index, bit 31 = its matrix is bitwise the identity; its material offset)
-    const uint4* mesh_base;    // per mesh: its first triangle (triangles), first normal (normals), first texcoord (texcoords), 0
+    const uint4* mesh_base;    // per mesh: its first triangle (triangles), first normal (normals), first texcoord (texcoords), and the
+                               // number of lights the mesh carries (0 in a scene without mesh lights)
+    const uint32_t* light_first;   // a scene with mesh lights (§18): per instance, the index of its first light in `lights` (the scene's
+                                   // current world table, n_lights = its total); null = a scene without: emission.w indexes `lights` as it is
 };
 
 struct RaygenArgs {            // k_raygen: segment 0's path-ray queue and path state of an instanced scene's frame

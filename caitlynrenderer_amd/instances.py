@@ -4,13 +4,14 @@ instances and keeps the TLAS's topology (§13).  An updatable scene also moves t
 TLAS rebuild per update.  Instances carry 8-bit visibility masks that a masked trace ANDs with each ray's (§14).  Meshes
 can be appended to a live scene and, in an updatable one, replaced by new geometry (§15).  The handle answers ray queries; `frame_scene`
 returns a Scene that renders frames of it (§16); those frames add each instance's material offset to its triangles' material indices and,
-with the scene's option "instance_masks", walk masked per ray class (§17)."""
+with the scene's option "instance_masks", walk masked per ray class (§17).  Meshes may carry lights that follow their instances (§18)."""
 import ctypes as C
 
 import numpy as np
 
 from ._lib import (CRT_ABI_VERSION, CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_INSTANCES_UPDATABLE, CRT_TRACE_CLOSEST,
-                   CRT_TRACE_INSTANCE_MASK, check, crt_blas_desc, crt_instanced_scene_desc, crt_instances_info, crt_mesh_shading, lib)
+                   CRT_TRACE_INSTANCE_MASK, check, crt_blas_desc, crt_instanced_scene_desc, crt_instances_info, crt_mesh_lights, crt_mesh_shading,
+                   lib)
 from .host import Rnd, _ptr
 from .scene import HIT_DT, RAY_DT, STATS_DT, Scene
 
@@ -73,6 +74,23 @@ def instance_world_box(object_to_world, box):
     return out
 
 
+def instance_lights(object_to_world, lights):
+    """crt_instance_lights [host]: (n, 18) object-space lights through a 3x4 object_to_world, bit for bit the device's arithmetic
+    (DESIGN.md §18): area set, the pdf column left 0 for lights_finish."""
+    m = np.ascontiguousarray(object_to_world, np.float32).reshape(12)
+    src = np.ascontiguousarray(lights, np.float32).reshape(-1, 18)
+    out = np.empty_like(src)
+    check(lib().crt_instance_lights(_ptr(m), _ptr(src), src.shape[0], _ptr(out)))
+    return out
+
+
+def lights_finish(lights):
+    """crt_lights_finish [host]: a copy of an (n, 18) light table with its pdf column (index 16) filled by the tree-sum rule."""
+    out = np.array(lights, np.float32).reshape(-1, 18)
+    check(lib().crt_lights_finish(_ptr(out), out.shape[0]))
+    return out
+
+
 def _blas_descs(meshes):
     """-> (crt_blas_desc array, the arrays it points into) of Mesh objects or (vertices, triangles) pairs"""
     descs = (crt_blas_desc * max(len(meshes), 1))()
@@ -88,6 +106,22 @@ def _blas_descs(meshes):
         descs[k].vertices, descs[k].n_vertices = _ptr(v), v.shape[0]
         descs[k].triangles, descs[k].n_triangles = _ptr(t), t.shape[0]
     return descs, keep
+
+
+def set_mesh_lights(scene, mesh, lights):
+    """crt_scene_set_mesh_lights: new OBJECT-space lights (same count) for one mesh of a frame_scene with mesh_lights; call reset()"""
+    la = np.ascontiguousarray(lights, np.float32).reshape(-1, 18)
+    check(lib().crt_scene_set_mesh_lights(scene._h, int(mesh), _ptr(la) if la.shape[0] else None, la.shape[0]))
+
+
+def read_lights(scene):
+    """crt_scene_read_lights: the (n, 18) float32 world light table the next frame of a frame_scene samples (rebuilt first if stale)"""
+    n = C.c_size_t()
+    check(lib().crt_scene_read_lights(scene._h, None, 0, C.byref(n)))
+    out = np.empty((n.value, 18), np.float32)
+    if n.value:
+        check(lib().crt_scene_read_lights(scene._h, _ptr(out), n.value, C.byref(n)))
+    return out
 
 
 class InstancedScene:
@@ -221,13 +255,20 @@ class InstancedScene:
         stale)"""
         return self._read(6, np.uint8, 8)
 
-    def frame_scene(self, shading, materials, lights, width, height, max_depth=3, textures=None):
+    def object_to_world(self):
+        """(n, 12) float32: the live object_to_world of every instance, as the last successful set / refit gave them"""
+        return self._read(7, np.float32, 12)
+
+    def frame_scene(self, shading, materials, lights, width, height, max_depth=3, textures=None, mesh_lights=None):
         """A Scene that renders frames of this handle's LIVE instances (crt_scene_create_instanced): every Scene method works
         on it, and a set / refit / update_meshes between frames changes what the next frame sees (call reset()).  Its options
         "instance_masks" (0 / 1), "mask_primary", "mask_bounce", "mask_shadow" (0..255) apply the instances' masks to its rays (§17).  shading: per mesh, in mesh
         order, (triangles (n, 12) int32 in source order [, normals (k, 3) [, texcoords (k, 2)]]) or an object with those attributes;
         materials (m, 16) float32, lights (l, 18) float32 in WORLD space, textures (layers, H, W, 3) uint8 or None.  Close the returned scene
-        before this handle: destroy, add_meshes and replace_meshes are refused while it lives."""
+        before this handle: destroy, add_meshes and replace_meshes are refused while it lives.
+        mesh_lights: None, or per mesh an (l, 18) float32 array (or None) of OBJECT-space lights that every instance of the mesh carries
+        and that follow it through set / refit / update_meshes (crt_scene_create_instanced_lit); on such a mesh a
+        material's emission.w is the light's index within the mesh.  set_mesh_lights(scene, mesh, lights) and read_lights(scene) act on it."""
         keep = []
 
         def arr(a, dtype, shape):
@@ -258,10 +299,26 @@ class InstancedScene:
         sc = Scene.__new__(Scene)
         sc._h = C.c_void_p()
         sc.width, sc.height, sc.max_depth, sc.frame_count, sc.rnd, sc.create_ms = int(width), int(height), int(max_depth), 0, Rnd(), 0.0
-        check(lib().crt_scene_create_instanced(C.byref(d), C.byref(sc._h)))
+        if mesh_lights is None:
+            check(lib().crt_scene_create_instanced(C.byref(d), C.byref(sc._h)))
+        else:
+            ml = (crt_mesh_lights * max(len(mesh_lights), 1))()
+            assert len(mesh_lights) == len(shading), "mesh_lights: one entry per mesh"
+            for k, l in enumerate(mesh_lights):
+                la = arr(l, np.float32, (-1, 18))
+                ml[k].lights, ml[k].n_lights = (_ptr(la) if la.shape[0] else None), la.shape[0]
+            check(lib().crt_scene_create_instanced_lit(C.byref(d), ml, C.byref(sc._h)))
         sc._instances = self                       # the handle must outlive the scene
         del keep
         return sc
+
+    def set_mesh_lights(self, scene, mesh, lights):
+        """new OBJECT-space lights (the create's count) for one mesh of a frame_scene made with mesh_lights; call scene.reset()"""
+        set_mesh_lights(scene, mesh, lights)
+
+    def read_lights(self, scene):
+        """(n, 18) float32: the world light table the next frame of a frame_scene samples (rebuilt first if stale)"""
+        return read_lights(scene)
 
     def info(self):
         st = crt_instances_info()
@@ -280,4 +337,5 @@ class InstancedScene:
             pass
 
 
-__all__ = ["InstancedScene", "INSTANCE_DT", "instances_array", "instance_inverse", "instance_world_box"]
+__all__ = ["InstancedScene", "INSTANCE_DT", "instances_array", "instance_inverse", "instance_world_box", "instance_lights", "lights_finish",
+           "set_mesh_lights", "read_lights"]

@@ -562,7 +562,9 @@ int crt_instances_replace_meshes(crt_instances* s, const uint32_t* mesh_ids, uin
 /* test hook: which 0 = world_to_object (12 floats per instance, instance order), 1 = world boxes (6 floats: lo, hi), 2 = TLAS node8s
  * (80 B), 3 = instance records in TLAS leaf order (64 B: world_to_object rows, then BLAS root node, instance index, identity flag, mask & 0xff),
  * 4 = every BLAS node8 (80 B; the packed region after the TLAS region, bases rebased), 5 = every BLAS record (48 B), 6 = the TLAS child
- * masks (8 B per TLAS node8, byte i = the OR of the masks & 0xff of every instance under meta slot i; recomputed first if stale).
+ * masks (8 B per TLAS node8, byte i = the OR of the masks & 0xff of every instance under meta slot i; recomputed first if stale), 7 = the
+ * live object_to_world (12 floats per instance, instance order, as the last successful set / refit gave them; read by the light tables of
+ * DESIGN.md §18, never by ray queries).
  * dst may be NULL to query the count. */
 int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_bytes, size_t* n_out);
 int crt_instances_destroy(crt_instances* s);
@@ -638,9 +640,55 @@ typedef struct crt_instanced_scene_desc {
  * "mask_shadow" 0..255 (default 255).  Call crt_reset after changing one, as after a camera move.  With "count_visits" the node and
  * triangle totals of a masked frame count the steps taken: a culled TLAS child and a hidden instance cost nothing.
  *
- * Not offered: lights that follow an emissive instance, per-ray masks inside a class, several devices or streams,
- * several samples per launch. */
+ * Not offered: per-ray masks inside a class, several devices or streams, several samples per launch.  Lights that
+ * follow an emissive instance: crt_scene_create_instanced_lit, below. */
 int crt_scene_create_instanced(const crt_instanced_scene_desc* desc, crt_scene** out);
+
+/* ---- lights that follow emissive instances ----
+ *
+ * desc->lights are world-space constants.  A mesh may carry lights of its own, in OBJECT space (copied): every instance of the mesh then
+ * has them, moved by its object_to_world, and crt_instances_set / _refit / _update_meshes (and their device forms) move them with the
+ * instance.  The scene's WORLD light table holds desc->lights first (n_static, as given), then, instance by instance in instance order,
+ * the lights of that instance's mesh in the mesh's order; first[i] = n_static + the lights of the instances before i.  The table is
+ * rebuilt on the device, on the scene's stream, from the handle's live matrices: lazily, when a frame is enqueued or crt_scene_read_lights
+ * is called after a successful mutator of the handle (or crt_scene_set_mesh_lights), with one small device-to-host read for the total.
+ * Call crt_reset after a mutator, as ever.
+ *
+ * One transformed light, fp32 without fma, A | t the rows of object_to_world, W the handle's world_to_object (crt_instance_inverse):
+ *   p'_r = ((A_r0*p.x + A_r1*p.y) + A_r2*p.z) + t_r;  u'_r = (A_r0*u.x + A_r1*u.y) + A_r2*u.z, v' likewise;
+ *   m_c = (W_0c*n.x + W_1c*n.y) + W_2c*n.z (contract item 4's inverse transpose: the light's side follows the shading normal, mirrors
+ *   included), n' = m * (1 / sqrt((m.x*m.x + m.y*m.y) + m.z*m.z)), IEEE square root and division;  e copied;
+ *   area' = sqrt(dot(c, c)), c = u' x v' (each component a*b - c*d, both products rounded);  area_pdf[2] = 0.
+ *   An instance whose matrix is bitwise the identity copies all 18 floats, area included.
+ * The pdf column is recomputed for the WHOLE table (a static light's given area_pdf[1] is ignored once a scene has mesh lights):
+ *   a_k = the light's area, or +0 when that is not a finite positive float;  S = the pairwise tree sum of a_0 .. a_{n-1} (padded with +0
+ *   to a power of two, a_j <- a_{2j} + a_{2j+1} until one is left);  area_pdf[1] = a_k * (1.0f / S) when S > 0, else 0.
+ * crt_instance_lights and crt_lights_finish are this arithmetic on the host, bit for bit.
+ *
+ * Shading.  NEE samples the table.  An emitter hit looks its light up by ew = (int)material.emission[3] of the hit's material (contract
+ * item 3): when the hit instance's mesh has nl > 0 lights, ew is MESH-LOCAL and the light is first[instance] + min(ew, nl - 1); on any
+ * other mesh it is min(ew, total - 1), a table index (a static light when ew < n_static); with an empty table the hit's MIS weight is 1.
+ * The clamp only keeps a material offset from causing an out-of-range read: the area cancels in the light's pdf, so a clamped index
+ * changes the rounding alone.
+ *
+ * Lights are not geometry: an instance hidden by a visibility mask ("instance_masks") still lights the scene.
+ *
+ * crt_scene_create_instanced_lit: mesh_lights = desc->n_meshes entries (n_lights may be 0, lights then ignored), or NULL, or every entry
+ * empty = crt_scene_create_instanced exactly (nothing new is allocated or launched, the frames keep their bits).  Besides that call's
+ * checks, CRT_ERR_INVALID and nothing created for: a light field (static or mesh) that is not finite; an emissive material with
+ * ew < 0 or ew >= max(n_static, the greatest nl); a triangle of a light-bearing mesh whose own material is emissive with ew >= nl; a
+ * triangle of a light-less mesh whose own material is emissive with ew >= n_static. */
+/* (a struct TAG only, written `struct crt_mesh_lights`: the loader's accessor crt_mesh_lights() below already owns the plain name) */
+struct crt_mesh_lights { const crt_light* lights; size_t n_lights; };   /* OBJECT space, copied */
+int crt_scene_create_instanced_lit(const crt_instanced_scene_desc* desc, const struct crt_mesh_lights* mesh_lights, crt_scene** out);
+/* replaces ONE mesh's object-space lights (n_lights == the count given at create), e.g. after crt_instances_update_meshes deformed the
+ * lamp; the table is rebuilt before the next frame; call crt_reset.  CRT_ERR_INVALID and nothing changed: a scene without mesh lights
+ * (flat scenes included), a mesh out of range, another count, a field that is not finite, a null pointer with n_lights > 0. */
+int crt_scene_set_mesh_lights(crt_scene* s, uint32_t mesh, const crt_light* lights, size_t n_lights);
+/* the scene's CURRENT world light table (rebuilt first if stale): *n_out = its count, up to cap lights copied to dst (dst may be NULL to
+ * query the count; cap below the count with dst given is CRT_ERR_INVALID).  Instanced scenes only; one without mesh lights returns
+ * desc->lights as given.  Synchronous. */
+int crt_scene_read_lights(crt_scene* s, crt_light* dst, size_t cap, size_t* n_out);
 
 /* --------------------------------------------------- host side ([host]) ----- */
 
@@ -650,6 +698,12 @@ int crt_camera_look_at(const float pos[3], const float look_at[3], float fov_deg
  * (CRT_ERR_INVALID for a non-finite or singular matrix or a non-finite inverse), and the world box (lo[3], hi[3]) of an object box. */
 int crt_instance_inverse(const float object_to_world[12], float world_to_object[12]);
 int crt_instance_world_box(const float object_to_world[12], const float box[6], float out[6]);
+/* The light arithmetic of crt_scene_create_instanced_lit on the host, bit for bit what the device computes [host].  crt_instance_lights:
+ * n object-space lights through object_to_world (its inverse as crt_instance_inverse, CRT_ERR_INVALID where that refuses): out's area is
+ * set, area_pdf[1] = area_pdf[2] = 0; a matrix that is bitwise the identity copies the lights.  in and out may be the same array.
+ * crt_lights_finish: fills area_pdf[1] of a whole table by the tree-sum rule. */
+int crt_instance_lights(const float object_to_world[12], const crt_light* in, size_t n, crt_light* out);
+int crt_lights_finish(crt_light* lights, size_t n);
 
 /* Caitlyn/Rnd.h:21-40 PCG_Hash / randf2 (state starts at 1, Rnd.h:7) [host] */
 uint32_t crt_pcg_hash(uint32_t x);
