@@ -66,6 +66,12 @@ class crt_bvh_info(C.Structure):
                 ("build_lbvh_device_ms", C.c_float), ("build_convert_device_ms", C.c_float)]
 
 
+class crt_tree_cost(C.Structure):
+    _fields_ = [("root_area", C.c_double), ("inner_area", C.c_double), ("leaf_area", C.c_double),
+                ("n_nodes8", C.c_uint64), ("n_inner_slots", C.c_uint64), ("n_leaf_slots", C.c_uint64), ("n_leaf_items", C.c_uint64),
+                ("cost", C.c_double)]
+
+
 class crt_blas_desc(C.Structure):
     _fields_ = [("vertices", C.c_void_p), ("n_vertices", C.c_size_t), ("triangles", C.c_void_p), ("n_triangles", C.c_size_t)]
 
@@ -133,6 +139,10 @@ SYMBOLS = {
     "crt_update_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),
     "crt_last_update_ms": (_I, [_P, C.POINTER(_F), C.POINTER(_F)]),
+    "crt_rebuild_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
+    "crt_rebuild_vertices_device": (_I, [_P, _P, _SZ, _I]),
+    "crt_get_tree_cost": (_I, [_P, C.POINTER(crt_tree_cost)]),
+    "crt_instances_tree_cost": (_I, [_P, C.c_int32, C.POINTER(crt_tree_cost)]),
     "crt_debug_read_accel": (_I, [_P, _I, _P, _SZ, C.POINTER(_SZ)]),
     "crt_instances_create": (_I, [C.POINTER(crt_blas_desc), _U32, _P, _U32, _U32, _U32, C.POINTER(_P)]),
     "crt_instances_set": (_I, [_P, _P, _U32]),
@@ -198,6 +208,7 @@ SYMBOLS = {
     "crt_cwbvh_free": (None, [_P]),
     "crt_bvh2_refit": (_I, [_P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_cwbvh_refit": (_I, [_P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ]),
+    "crt_cwbvh_cost": (_I, [_P, _SZ, _SZ, _SZ, C.POINTER(crt_tree_cost)]),
     "crt_load_obj": (_I, [C.c_char_p, C.POINTER(_F), C.POINTER(_P)]),
     "crt_mesh_counts": (_SZ, [_P] + [C.POINTER(_SZ)] * 6),
     "crt_mesh_vertices": (_P, [_P]),

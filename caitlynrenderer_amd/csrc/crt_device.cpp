@@ -105,6 +105,26 @@ struct RefitState {
     }
 };
 
+// What crt_rebuild_vertices keeps between rebuilds, allocated by a scene's first rebuild: a scene that never rebuilds holds
+// none of it, and no walk or frame reads it.
+struct RebuildState {
+    int device = 0;
+    crt_triangle* d_src = nullptr;           // the triangles in SOURCE order (create threw its copy away): scattered back from the leaf order once
+    float* d_verts = nullptr;                // the host form's upload of the positions
+    uint32_t* d_check = nullptr;             // k_check_vertices' verdict and bounds, as RefitState's
+    uint32_t* h_check = nullptr;             // pinned
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    float device_ms = 0.f, wall_ms = 0.f;
+    ~RebuildState() {
+        (void)hipSetDevice(device);
+        void* ptrs[] = {d_src, d_verts, d_check};
+        for (void* p : ptrs) if (p) (void)hipFree(p);
+        if (h_check) (void)hipHostFree(h_check);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+    }
+};
+
 // The lights of an instanced scene that follow its instances (crt_scene_create_instanced_lit).  The scene's d_lights is
 // then the world table these are rebuilt into, n_lights its current total.
 struct SceneLights {
@@ -150,6 +170,9 @@ struct crt_scene {
     uint32_t bvh2_stack = 0;             // BVH2 depth + 2
     size_t n_vertices = 0, n_normals = 0, n_slots = 0;   // as created (n_slots: the leaf-order triangle array); crt_update_vertices checks against them
     RefitState* refit = nullptr;         // crt_update_vertices' state, from the first update on
+    RebuildState* rebuild = nullptr;     // crt_rebuild_vertices' state, from the first rebuild on
+    uint32_t gpu_build_flags = 0;        // build-on-device scenes: the builder (CRT_GPU_BUILD_*) a rebuild runs again
+    bool last_update_was_rebuild = false;   // crt_last_update_ms reports the rebuild's times
     // A scene whose geometry is a live crt_instances handle (crt_scene_create_instanced): BORROWED, and bound from create to
     // destroy.  d_nodes / d_tris / d_planes stay null: a frame reads the handle's arrays as they are when it is enqueued.  d_triangles,
     // d_normals and d_texcoords hold every mesh's arrays one after the other, d_mesh_base where each mesh's start.
@@ -339,6 +362,7 @@ struct crt_scene {
         if (stream) hipStreamSynchronize(stream);
         if (inst) crt::instances_unbind(inst, stream);
         delete refit;
+        delete rebuild;
         delete lit;
         if (shares_scene)                    // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
@@ -1308,6 +1332,7 @@ static int scene_create_device_built(const crt_scene_desc* d, crt_scene** out) {
     s->stack_entries = std::min<uint32_t>(CRT_STACK_ENTRIES, std::max<uint32_t>(2, depth8 - 1u));      // as for host-built trees: depth8 - 1 entries hold any walk
     s->info.n_nodes8 = n8; s->info.n_tris8 = n; s->info.n_bvh2_nodes = n2; s->info.max_depth8 = depth8;
     s->info.built_on_device = 1u; s->info.bvh2_depth = depth2;
+    s->gpu_build_flags = gpu_build_flags;
     s->info.build_upload_ms = upload_ms; s->info.build_lbvh_device_ms = lbvh_ms; s->info.build_convert_device_ms = conv_ms;
     note_buf(s, &s->d_nodes, (size_t)n8 * CRT_NODE_ROWS * 16);
     note_buf(s, &s->d_tris, (size_t)n * CRT_TRI_ROWS * 16);
@@ -2856,6 +2881,7 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
     HIPCHK(hipSetDevice(s->device));
     r->have_times = true;
     r->times_pending = true;
+    s->last_update_was_rebuild = false;
     if (sync) {
         HIPCHK(hipStreamSynchronize(st));
         for (crt_scene* p : s->peers) { HIPCHK(hipSetDevice(p->device)); HIPCHK(hipStreamSynchronize(p->stream)); }
@@ -2867,7 +2893,212 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
     return CRT_OK;
 }
 
+// ---------------------------------------------------------------- crt_rebuild_vertices --
+// New positions and a new tree: scene_create_device_built's chain run again over the source-order triangles into new
+// buffers, published at the end.  Until then nothing a walk, a frame or a debug read sees has changed.
+
+static void set_buf_bytes(crt_scene* s, const void* member, size_t bytes) {
+    const size_t off = (size_t)(reinterpret_cast<const char*>(member) - reinterpret_cast<const char*>(s));
+    for (auto& b : s->scene_bufs) if (b.first == off) { b.second = bytes; return; }
+    s->scene_bufs.emplace_back(off, bytes);
+}
+
+static int ensure_rebuild_state(crt_scene* s) {
+    if (s->rebuild) return CRT_OK;
+    std::unique_ptr<RebuildState> owner(new (std::nothrow) RebuildState);
+    RebuildState* r = owner.get();
+    if (!r) return fail(CRT_ERR_NOMEM, "crt_rebuild_vertices: out of memory");
+    r->device = s->device;
+    int rc;
+    if ((rc = dev_alloc(&r->d_check, 8))) return rc;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_check), 8 * sizeof(uint32_t)));
+    HIPCHK(hipEventCreate(&r->ev_a));
+    HIPCHK(hipEventCreate(&r->ev_b));
+    // one triangle per slot and no duplicates in a device build: the records' (original id, slot) pairs are a permutation
+    const uint32_t n = (uint32_t)s->info.n_tris8;
+    if ((rc = dev_alloc(&r->d_src, n))) return rc;
+    crt::launch_scatter_source(s->d_tris, (uint32_t)CRT_TRI_ROWS, n, reinterpret_cast<const crt_triangle*>(s->d_triangles), r->d_src, s->stream);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess)
+        return fail(CRT_ERR_HIP, "crt_rebuild_vertices: the source-order scatter failed");
+    s->rebuild = owner.release();
+    return CRT_OK;
+}
+
+static int rebuild_impl(crt_scene* s, const float* h_verts, const float* d_user, size_t n_vertices, const float* normals, size_t n_normals,
+                        const crt_light* lights, size_t n_lights) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!s || (!h_verts && !d_user)) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: null argument");
+    if (s->inst) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: an instanced scene's geometry belongs to its handle: use crt_instances_replace_meshes");
+    if (s->primary) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: not on a replica");
+    if (!s->info.built_on_device)
+        return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: only a scene built on the device (CRT_BUILD_LBVH_ON_DEVICE) is rebuilt in place; one created from host arrays is created again");
+    for (const crt_scene* p : s->peers)
+        if (!p->shares_scene)
+            return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: a replica on another GPU (crt_set_devices) cannot follow a rebuild: return to one device, rebuild, and set the devices again");
+    if (n_vertices != s->n_vertices) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: n_vertices differs from the count given at create");
+    if (normals && n_normals != s->n_normals) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: n_normals differs from the count given at create");
+    if (lights && n_lights != s->n_lights) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: n_lights differs from the count given at create");
+    if (normals)
+        for (size_t i = 0; i < 3 * n_normals; ++i)
+            if (!std::isfinite(normals[i])) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: a normal is not finite");
+    HIPCHK(hipSetDevice(s->device));
+    int rc = ensure_rebuild_state(s);
+    if (rc) return rc;
+    RebuildState* r = s->rebuild;
+    hipStream_t st = s->stream;
+    const uint32_t nv = (uint32_t)n_vertices;
+    const float* verts = d_user;
+    if (h_verts) {
+        if (!r->d_verts && (rc = dev_alloc(&r->d_verts, 3 * n_vertices))) return rc;
+        HIPCHK(hipMemcpyAsync(r->d_verts, h_verts, 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice, st));
+        verts = r->d_verts;
+    }
+    HIPCHK(hipMemsetAsync(r->d_check, 0, 8 * sizeof(uint32_t), st));
+    crt::launch_check_vertices(verts, nv, r->d_check, st);
+    HIPCHK(hipMemcpyAsync(r->h_check, r->d_check, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (r->h_check[0]) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: a vertex coordinate is not finite or exceeds 1e18");
+
+    // the new tree, in buffers of its own: whatever is left in `fresh` when this returns is freed
+    struct Fresh {
+        hipStream_t st;
+        float4* bvh2 = nullptr; uint4* nodes = nullptr; float4* tris = nullptr; int4* triangles = nullptr; float4* tris2 = nullptr; float4* planes = nullptr;
+        ~Fresh() {
+            (void)hipStreamSynchronize(st);
+            void* ptrs[] = {bvh2, nodes, tris, triangles, tris2, planes};
+            for (void* p : ptrs) if (p) (void)hipFree(p);
+        }
+    } fresh{st};
+    const uint32_t n = (uint32_t)s->info.n_tris8, n2 = 2u * n - 1u;
+    crt::DeviceArena arena;
+    auto P = crt::DeviceArena::padded;
+    const size_t tmp_bytes = std::max(crt::lbvh_tmp_bytes(n, s->gpu_build_flags), crt::cwbvh_tmp_bytes(n2, n));
+    hipError_t he = arena.reserve(P((size_t)n * 4) + P((size_t)n * 4) + tmp_bytes);
+    if (he != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("crt_rebuild_vertices: hipMalloc: ") + hipGetErrorString(he));
+    uint32_t* d_tri_order = arena.take<uint32_t>(n);
+    int32_t* d_tri_slots = arena.take<int32_t>(n);
+    const size_t persistent_mark = arena.used;
+    if ((rc = dev_alloc(&fresh.bvh2, (size_t)n2 * 2))) return rc;
+    uint32_t depth2 = 0, n8 = 0, depth8 = 0;
+    float lbvh_ms = 0.f, conv_ms = 0.f;
+    HIPCHK(hipEventRecord(r->ev_a, st));
+    rc = crt::lbvh_build_on_device(reinterpret_cast<const int32_t*>(r->d_src), 12, verts, n, s->gpu_build_flags, arena, reinterpret_cast<crt_flatnode*>(fresh.bvh2),
+                                   d_tri_order, &depth2, &lbvh_ms, st);
+    if (rc) return fail(rc, std::string("crt_rebuild_vertices: LBVH build failed: ") + crt_last_error());
+    arena.used = persistent_mark;
+    crt_node8* d_nodes8 = nullptr;
+    rc = crt::cwbvh_convert_on_device(reinterpret_cast<const crt_flatnode*>(fresh.bvh2), n2, n, arena, d_tri_slots, &d_nodes8, nullptr, &n8, &depth8, &conv_ms, st);
+    if (rc) return fail(rc, std::string("crt_rebuild_vertices: BVH2 -> CWBVH failed: ") + crt_last_error());
+    fresh.nodes = reinterpret_cast<uint4*>(d_nodes8);
+    if (depth8 > CRT_STACK_ENTRIES) return fail(CRT_ERR_LIMIT, "crt_rebuild_vertices: CWBVH rejected: CWBVH deeper than the traversal stack");
+    if ((rc = dev_alloc(&fresh.triangles, (size_t)n * 3))) return rc;
+    if ((rc = dev_alloc(&fresh.tris, (size_t)n * 3))) return rc;
+    const bool keep_bvh2 = depth2 + 2u <= 96u;    // create's rule: the BVH2 walk's LDS stack bound
+    if (keep_bvh2 && (rc = dev_alloc(&fresh.tris2, (size_t)n * 3))) return rc;
+    crt::launch_gather_slots(r->d_src, d_tri_order, verts, n, reinterpret_cast<crt_triangle*>(fresh.triangles), keep_bvh2 ? fresh.tris2 : nullptr, st);
+    crt::launch_gather_records(r->d_src, d_tri_order, d_tri_slots, verts, n, fresh.tris, st);
+    if ((uint32_t)CRT_NODE_ROWS != 5u) {           // the traversal's stride, as finish_scene_setup pads a create's arrays
+        uint4* padded = nullptr;
+        if ((rc = dev_alloc(&padded, (size_t)n8 * CRT_NODE_ROWS))) return rc;
+        crt::launch_restride(fresh.nodes, 5u, padded, (uint32_t)CRT_NODE_ROWS, n8, st);
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(fresh.nodes);
+        fresh.nodes = padded;
+    }
+    if ((uint32_t)CRT_TRI_ROWS != 3u) {
+        float4* padded = nullptr;
+        if ((rc = dev_alloc(&padded, (size_t)n * CRT_TRI_ROWS))) return rc;
+        crt::launch_restride(fresh.tris, 3u, padded, (uint32_t)CRT_TRI_ROWS, n, st);
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(fresh.tris);
+        fresh.tris = padded;
+    }
+    if (s->d_planes) {                            // re-expanded as create's first frame does; a scene without them still builds them lazily
+        if ((rc = dev_alloc(&fresh.planes, (size_t)n8 * 12))) return rc;
+        crt::launch_expand_planes(fresh.nodes, (uint32_t)CRT_NODE_ROWS, fresh.planes, n8, st);
+    }
+    HIPCHK(hipEventRecord(r->ev_b, st));
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, "crt_rebuild_vertices: scene assembly kernels failed");
+    if (!keep_bvh2) { (void)hipFree(fresh.bvh2); fresh.bvh2 = nullptr; }
+    // every stream that reads the shared buffers is done with the old tree (replicas live on this device: checked above)
+    for (crt_scene* p : s->peers) HIPCHK(hipStreamSynchronize(p->stream));
+
+    // ---- publish: nothing below can refuse ----
+    if (normals && n_normals) HIPCHK(hipMemcpyAsync(s->d_normals, normals, 3 * n_normals * sizeof(float), hipMemcpyHostToDevice, st));
+    if (lights && n_lights) HIPCHK(hipMemcpyAsync(s->d_lights, lights, n_lights * sizeof(crt_light), hipMemcpyHostToDevice, st));
+    const bool had_planes = s->d_planes != nullptr;
+    std::swap(s->d_bvh2, fresh.bvh2); std::swap(s->d_nodes, fresh.nodes); std::swap(s->d_tris, fresh.tris);
+    std::swap(s->d_triangles, fresh.triangles); std::swap(s->d_tris2, fresh.tris2); std::swap(s->d_planes, fresh.planes);
+    s->bvh2_stack = keep_bvh2 ? depth2 + 2u : 0u;
+    s->stack_entries = std::min<uint32_t>(CRT_STACK_ENTRIES, std::max<uint32_t>(2, depth8 - 1u));
+    s->info.n_nodes8 = n8; s->info.n_tris8 = n; s->info.n_bvh2_nodes = n2; s->info.max_depth8 = depth8; s->info.bvh2_depth = depth2;
+    s->info.build_lbvh_device_ms = lbvh_ms; s->info.build_convert_device_ms = conv_ms;
+    set_buf_bytes(s, &s->d_nodes, (size_t)n8 * CRT_NODE_ROWS * 16);
+    if (had_planes) set_buf_bytes(s, &s->d_planes, (size_t)n8 * 12 * sizeof(float4));
+    if (keep_bvh2) {
+        set_buf_bytes(s, &s->d_bvh2, (size_t)n2 * sizeof(crt_flatnode));
+        set_buf_bytes(s, &s->d_tris2, (size_t)n * 3 * sizeof(float4));
+    }
+    delete s->refit;                              // its level order described the old tree: the next update finds the new tree's
+    s->refit = nullptr;
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) { hi[k] = crt::rf::key_to_float(r->h_check[1 + k]); lo[k] = crt::rf::key_to_float(~r->h_check[4 + k]); }
+    auto refresh = [&](crt_scene* x) -> int {
+        for (int k = 0; k < 3; ++k) { x->bounds_lo[k] = lo[k]; x->bounds_hi[k] = hi[k]; }
+        x->tile_state = crt_scene::TILES_WANT;
+        const int erc = ensure_frame(x);
+        if (erc) return erc;
+        HIPCHK(hipMemsetAsync(x->d_sum, 0, 3 * (size_t)std::max<uint32_t>(x->n_local_pixels, 1) * sizeof(float), x->stream));
+        return CRT_OK;
+    };
+    if ((rc = refresh(s))) return rc;
+    for (crt_scene* p : s->peers) {               // the same buffers, borrowed
+        p->d_bvh2 = s->d_bvh2; p->d_nodes = s->d_nodes; p->d_tris = s->d_tris; p->d_triangles = s->d_triangles; p->d_tris2 = s->d_tris2;
+        p->d_planes = p->d_planes ? s->d_planes : nullptr;
+        const bool peer_planes = p->d_planes != nullptr;
+        p->info = s->info; p->bvh2_stack = s->bvh2_stack; p->stack_entries = s->stack_entries;
+        p->scene_bufs = s->scene_bufs;
+        if (!peer_planes)                         // not borrowed yet: ensure_planes notes it when it is
+            p->scene_bufs.erase(std::remove_if(p->scene_bufs.begin(), p->scene_bufs.end(), [&](const std::pair<size_t, size_t>& b) {
+                return b.first == (size_t)(reinterpret_cast<const char*>(&s->d_planes) - reinterpret_cast<const char*>(s)); }), p->scene_bufs.end());
+        if ((rc = refresh(p))) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (crt_scene* p : s->peers) HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipEventElapsedTime(&r->device_ms, r->ev_a, r->ev_b));
+    s->last_update_was_rebuild = true;
+    r->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return CRT_OK;
+}
+
 extern "C" {
+
+int crt_rebuild_vertices(crt_scene* s, const float* vertices, size_t n_vertices, const float* normals, size_t n_normals, const crt_light* lights,
+                         size_t n_lights) {
+    if (!vertices) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: null vertices");
+    try {
+        return rebuild_impl(s, vertices, nullptr, n_vertices, normals, n_normals, lights, n_lights);
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_rebuild_vertices: ") + e.what());
+    }
+}
+
+int crt_rebuild_vertices_device(crt_scene* s, const void* d_vertices, size_t n_vertices, int sync) {
+    if (!d_vertices) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices_device: null vertices");
+    (void)sync;                                   // the builders wait on the host: a rebuild always returns done
+    try {
+        return rebuild_impl(s, nullptr, static_cast<const float*>(d_vertices), n_vertices, nullptr, 0, nullptr, 0);
+    } catch (const std::exception& e) {
+        return fail(CRT_ERR_NOMEM, std::string("crt_rebuild_vertices_device: ") + e.what());
+    }
+}
+
+int crt_get_tree_cost(crt_scene* s, crt_tree_cost* out) {
+    if (!s || !out) return fail(CRT_ERR_INVALID, "crt_get_tree_cost: null argument");
+    if (s->inst) return fail(CRT_ERR_INVALID, "crt_get_tree_cost: an instanced scene has no tree of its own: use crt_instances_tree_cost on its handle");
+    HIPCHK(hipSetDevice(s->device));
+    return crt::tree_cost_on_device(s->d_nodes, (uint32_t)CRT_NODE_ROWS, 0u, s->info.n_nodes8, 0u, s->stream, out);
+}
 
 int crt_update_vertices(crt_scene* s, const float* vertices, size_t n_vertices, const float* normals, size_t n_normals, const crt_light* lights,
                         size_t n_lights) {
@@ -2890,6 +3121,11 @@ int crt_update_vertices_device(crt_scene* s, const void* d_vertices, size_t n_ve
 
 int crt_last_update_ms(crt_scene* s, float* device_ms, float* wall_ms) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_last_update_ms: null scene");
+    if (s->last_update_was_rebuild && s->rebuild) {
+        if (device_ms) *device_ms = s->rebuild->device_ms;
+        if (wall_ms) *wall_ms = s->rebuild->wall_ms;
+        return CRT_OK;
+    }
     RefitState* r = s->refit;
     if (!r || !r->have_times) return fail(CRT_ERR_INVALID, "crt_last_update_ms: no update yet");
     if (r->times_pending) {

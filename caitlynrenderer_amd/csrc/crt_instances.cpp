@@ -1150,6 +1150,22 @@ int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_
     return CRT_OK;
 }
 
+int crt_instances_tree_cost(crt_instances* s, int32_t mesh, crt_tree_cost* out) {
+    if (!s || !out) return fail(CRT_ERR_INVALID, "crt_instances_tree_cost: null argument");
+    *out = crt_tree_cost{};
+    if (mesh < -1 || (mesh >= 0 && (uint32_t)mesh >= s->n_meshes)) return fail(CRT_ERR_INVALID, "crt_instances_tree_cost: mesh must be -1 (the TLAS) or a mesh index");
+    IHIPCHK(hipSetDevice(s->device));
+    { const int wrc = wait_bound(s); if (wrc) return wrc; }
+    IHIPCHK(hipStreamSynchronize(s->stream));
+    if (mesh < 0) {
+        if (s->n_instances == 0) return CRT_OK;
+        return crt::tree_cost_on_device(s->d_nodes, 5u, 0u, s->n_tlas8, 0u, s->stream, out);
+    }
+    uint64_t first = s->tlas_cap_nodes;           // the packed array: the TLAS region, then the BLASes in mesh order, each root first
+    for (int32_t k = 0; k < mesh; ++k) first += s->mesh[(size_t)k].n8;
+    return crt::tree_cost_on_device(s->d_nodes, 5u, first, s->mesh[(size_t)mesh].n8, first, s->stream, out);
+}
+
 int crt_instances_update_meshes(crt_instances* s, const uint32_t* mesh_ids, uint32_t n, const float* const* vertices, const size_t* n_vertices) {
     if (n && !vertices) return fail(CRT_ERR_INVALID, "crt_instances_update_meshes: null vertices");
     try {

@@ -131,6 +131,15 @@ void launch_refit_node8_level(void* d_nodes, uint32_t node_rows, uint32_t node_b
                               const RefitSeg* d_segs, uint32_t n_segs, uint32_t count, const void* d_recs, uint32_t tri_rows, uint32_t n_recs,
                               const RefitMesh* d_meshes, float* d_box8, hipStream_t stream);
 
+// ---- SAH cost of a tree, rebuild support (refit.hip) ----
+// crt_tree_cost of the node8s [first, first + count) of a device array at node_rows 16-byte rows per node, `root` among them (count == 0:
+// all zeros).  Allocates its partial sums, runs on `stream` and waits for it.
+int tree_cost_on_device(const void* d_nodes, uint32_t node_rows, uint64_t first, uint64_t count, uint64_t root, hipStream_t stream,
+                        crt_tree_cost* out);
+// d_src[id] = d_slot_tris[slot] for the (id, slot) every CWBVH-order record of a device-built scene names (v0.w, e1.w): the source-order
+// triangle array crt_scene_create's build-on-device path read and threw away
+void launch_scatter_source(const void* d_recs, uint32_t tri_rows, uint32_t n, const crt_triangle* d_slot_tris, crt_triangle* d_src, hipStream_t stream);
+
 // ---- code-object warm-up (crt_warmup) ----
 // HIP loads a code object the first time one of its kernels is looked up; each of these asks for the attributes of its
 // translation unit's kernels, which loads that unit's code object on the current device (~ms each) without launching anything.

@@ -1,5 +1,5 @@
 // Refit kernels of crt_update_vertices, crt_instances_update_meshes (§12) and crt_instances_refit (§13): new vertex
-// positions or instance boxes, same topology.  The
+// positions or instance boxes, same topology; and what tells a caller when to stop refitting (§19): the SAH cost of a tree.  The
 // trees and record arrays are rewritten in place, one launch per tree level, deepest first (the kernel boundary orders the levels, as in
 // lbvh.hip k_refit_level).  The records and node8 kernels serve both callers: each refitted tree is a RefitMesh (device_build.hpp), and a
 // per-launch segment table maps an entry to its mesh and item, so one launch covers every mesh of an instanced call and a scene is the
@@ -13,6 +13,7 @@
 
 #include "crt_error.hpp"
 #include "device_build.hpp"
+#include "host/cost_core.hpp"
 #include "host/flatnode_link.hpp"
 #include "host/refit_core.hpp"
 
@@ -261,6 +262,106 @@ __global__ void k_box_triples(int32_t* __restrict__ idx, uint32_t n) {
     idx[3 * (size_t)i + 2] = (int32_t)(2u * i);
 }
 
+// ---- SAH cost of a node8 range (crt_get_tree_cost, crt_instances_tree_cost) ----
+// Eight adjacent lanes per node8, one per slot, as k_refit_node8_level maps them.  A lane decodes its slot's box (host/cost_core.hpp: the
+// host function's arithmetic) and adds its half-area to its own partial; a block walks its share of the range with a fixed stride, so
+// which slots a lane adds, and in which order, depends on the launch shape alone.  The partials are reduced across the wave by lane
+// shuffles and across the block's four waves through LDS in wave order; k_tree_cost_sum adds the blocks' partials in index order.  No
+// floating-point atomics anywhere: two calls on one tree return the same bits.
+struct CostPartial { double inner, leaf; unsigned long long n_inner, n_leaf, n_items, pad; };
+static_assert(sizeof(CostPartial) == 48, "CostPartial is 48 bytes");
+struct CostResult { double root, inner, leaf; unsigned long long n_inner, n_leaf, n_items; };
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __shfl_xor((int)(b & 0xffffffffll), m), hi = __shfl_xor((int)(b >> 32), m);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(uint32_t)lo);
+}
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
+    const int lo = __shfl_xor((int)(v & 0xffffffffull), m), hi = __shfl_xor((int)(v >> 32), m);
+    return ((unsigned long long)(uint32_t)hi << 32) | (unsigned long long)(uint32_t)lo;
+}
+
+constexpr uint32_t kCostBlocks = 256;      // at most: 65,536 lanes = 8,192 node8s per pass over the range
+
+__global__ __launch_bounds__(256) void k_tree_cost(const uint4* __restrict__ nodes, uint32_t node_rows, uint64_t first, uint64_t count, uint64_t root,
+                                                   CostPartial* __restrict__ partial, double* __restrict__ root_area) {
+    __shared__ CostPartial wave_part[4];
+    const uint32_t s = threadIdx.x & 7u;
+    CostPartial acc{0.0, 0.0, 0ull, 0ull, 0ull, 0ull};
+    const uint64_t per_pass = (uint64_t)gridDim.x * kNodesPerBlock;
+    // every lane of a wave runs the same number of passes (the shuffles below need them all)
+    for (uint64_t base = (uint64_t)blockIdx.x * kNodesPerBlock; base < count; base += per_pass) {
+        const uint64_t j = base + (threadIdx.x >> 3);
+        const bool valid = j < count;
+        const uint64_t node = first + (valid ? j : 0ull);
+        const uint8_t* bytes = reinterpret_cast<const uint8_t*>(nodes + node * node_rows);
+        const uint8_t meta = valid ? bytes[24 + s] : (uint8_t)0;
+        const uint32_t imask = valid ? (uint32_t)bytes[15] : 0u;
+        Box b = rf::empty_box();
+        uint32_t used = 0u;
+        if (meta) {
+            b = tc::slot_box(bytes, (int)s);
+            used = 1u;
+            const double a = tc::half_area(b);
+            if ((imask >> s) & 1u) {
+                acc.inner += a;
+                ++acc.n_inner;
+            } else {
+                const int items = rf::leaf_count(meta);
+                acc.leaf += a * (double)items;
+                ++acc.n_leaf;
+                acc.n_items += (unsigned long long)items;
+            }
+        }
+        // the root's box: the union of its used slots across its eight lanes
+        Box u = b;
+        for (int m = 1; m <= 4; m <<= 1) {
+            for (int k = 0; k < 3; ++k) { u.lo[k] = rf::tmin(u.lo[k], __shfl_xor(u.lo[k], m)); u.hi[k] = rf::tmax(u.hi[k], __shfl_xor(u.hi[k], m)); }
+            used |= (uint32_t)__shfl_xor((int)used, m);
+        }
+        if (valid && s == 0u && first + j == root) *root_area = used ? tc::half_area(u) : 0.0;
+    }
+    for (int m = 1; m <= 32; m <<= 1) {
+        acc.inner += shfl_xor_f64(acc.inner, m);
+        acc.leaf += shfl_xor_f64(acc.leaf, m);
+        acc.n_inner += shfl_xor_u64(acc.n_inner, m);
+        acc.n_leaf += shfl_xor_u64(acc.n_leaf, m);
+        acc.n_items += shfl_xor_u64(acc.n_items, m);
+    }
+    if ((threadIdx.x & 63u) == 0u) wave_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        CostPartial t = wave_part[0];
+        for (int w = 1; w < 4; ++w) {
+            t.inner += wave_part[w].inner; t.leaf += wave_part[w].leaf;
+            t.n_inner += wave_part[w].n_inner; t.n_leaf += wave_part[w].n_leaf; t.n_items += wave_part[w].n_items;
+        }
+        partial[blockIdx.x] = t;
+    }
+}
+// the last pass: one lane adds the blocks' partials in index order
+__global__ void k_tree_cost_sum(const CostPartial* __restrict__ partial, uint32_t n, const double* __restrict__ root_area, CostResult* __restrict__ out) {
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    CostResult r{*root_area, 0.0, 0.0, 0ull, 0ull, 0ull};
+    for (uint32_t i = 0; i < n; ++i) {
+        r.inner += partial[i].inner; r.leaf += partial[i].leaf;
+        r.n_inner += partial[i].n_inner; r.n_leaf += partial[i].n_leaf; r.n_items += partial[i].n_items;
+    }
+    *out = r;
+}
+
+// ---- crt_rebuild_vertices: the source-order triangle array back from the leaf-order one ----
+// Record i of a device-built scene names its triangle's original id in v0.w and its leaf slot in e1.w; one triangle per slot and no
+// duplicates, so id <- slot is a permutation.
+__global__ void k_scatter_source(const float4* __restrict__ recs, uint32_t tri_rows, uint32_t n, const crt_triangle* __restrict__ slot_tris,
+                                 crt_triangle* __restrict__ src) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = (uint32_t)__float_as_int(recs[(size_t)i * tri_rows].w), slot = (uint32_t)__float_as_int(recs[(size_t)i * tri_rows + 1].w);
+    if (id < n && slot < n) src[id] = slot_tris[slot];
+}
+
 inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)std::max<uint64_t>(1u, (n + 255u) / 256u)); }
 
 }  // namespace
@@ -310,6 +411,35 @@ int discover_levels(const RefitTree* trees, size_t n_trees, hipStream_t stream, 
         (he = hipStreamSynchronize(stream)) != hipSuccess)               // before the host order goes
         return fail(CRT_ERR_HIP, std::string("refit level discovery: ") + hipGetErrorString(he));
     return CRT_OK;
+}
+
+int tree_cost_on_device(const void* d_nodes, uint32_t node_rows, uint64_t first, uint64_t count, uint64_t root, hipStream_t stream,
+                        crt_tree_cost* out) {
+    *out = crt_tree_cost{};
+    if (count == 0) return CRT_OK;
+    if (!d_nodes || root < first || root - first >= count) return fail(CRT_ERR_INVALID, "tree cost: the root lies outside the node range");
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(kCostBlocks, (count + kNodesPerBlock - 1u) / kNodesPerBlock);
+    DeviceArena tmp;
+    hipError_t he = tmp.reserve(DeviceArena::padded(blocks * sizeof(CostPartial)) + DeviceArena::padded(sizeof(double)) + DeviceArena::padded(sizeof(CostResult)));
+    if (he != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("tree cost: hipMalloc: ") + hipGetErrorString(he));
+    CostPartial* d_partial = tmp.take<CostPartial>(blocks);
+    double* d_root = tmp.take<double>(1);
+    CostResult* d_res = tmp.take<CostResult>(1);
+    CostResult res{};
+    if ((he = hipMemsetAsync(d_root, 0, sizeof(double), stream)) != hipSuccess) return fail(CRT_ERR_HIP, std::string("tree cost: ") + hipGetErrorString(he));
+    hipLaunchKernelGGL(k_tree_cost, dim3(blocks), dim3(256), 0, stream, static_cast<const uint4*>(d_nodes), node_rows, first, count, root, d_partial, d_root);
+    hipLaunchKernelGGL(k_tree_cost_sum, dim3(1), dim3(64), 0, stream, d_partial, blocks, d_root, d_res);
+    if ((he = hipGetLastError()) != hipSuccess || (he = hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (he = hipStreamSynchronize(stream)) != hipSuccess)
+        return fail(CRT_ERR_HIP, std::string("tree cost: ") + hipGetErrorString(he));
+    out->root_area = res.root; out->inner_area = res.inner; out->leaf_area = res.leaf;
+    out->n_nodes8 = count; out->n_inner_slots = res.n_inner; out->n_leaf_slots = res.n_leaf; out->n_leaf_items = res.n_items;
+    out->cost = tc::finish(res.root, res.inner, res.leaf);
+    return CRT_OK;
+}
+
+void launch_scatter_source(const void* d_recs, uint32_t tri_rows, uint32_t n, const crt_triangle* d_slot_tris, crt_triangle* d_src, hipStream_t stream) {
+    if (n) hipLaunchKernelGGL(k_scatter_source, grid_for(n), dim3(256), 0, stream, static_cast<const float4*>(d_recs), tri_rows, n, d_slot_tris, d_src);
 }
 
 void launch_check_vertices(const float* d_verts, uint32_t n_vertices, uint32_t* d_out, hipStream_t stream) {

@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, crt_camera, lib
+from ._lib import check, crt_camera, crt_tree_cost, lib
 
 
 def _copy(ptr, ctype, shape, dtype):
@@ -25,6 +25,11 @@ def _copy(ptr, ctype, shape, dtype):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+
+
+def _cost_dict(c):
+    """a crt_tree_cost as a dict: the areas and `cost` as Python floats (doubles), the counts as ints"""
+    return {k: getattr(c, k) for k, _ in c._fields_}
 
 
 class Rnd:
@@ -240,3 +245,13 @@ class CWBVH:
         check(lib().crt_cwbvh_refit(_ptr(self.nodes), self.nodes.shape[0], _ptr(self.tri_slots), self.tri_slots.shape[0], _ptr(tris),
                                     tris.shape[0], _ptr(verts), verts.shape[0]))
         return self
+
+    def cost(self, first=0, count=None, root=0):
+        """crt_cwbvh_cost [host]: the SAH cost (crt_tree_cost as a dict) of nodes [first, first + count), `root` among them; count=None
+        = to the end of the array.  The definition the device's Scene.tree_cost / InstancedScene.tree_cost share."""
+        nodes = np.ascontiguousarray(self.nodes, dtype=np.uint8).reshape(-1, 80)
+        if count is None:
+            count = nodes.shape[0] - int(first)
+        c = crt_tree_cost()
+        check(lib().crt_cwbvh_cost(_ptr(nodes), int(first), int(count), int(root), C.byref(c)))
+        return _cost_dict(c)

@@ -11,8 +11,8 @@ import numpy as np
 
 from ._lib import (CRT_ABI_VERSION, CRT_BUILD_LBVH_ON_DEVICE, CRT_BUILD_PLOC, CRT_BUILD_SAH, CRT_INSTANCES_UPDATABLE, CRT_TRACE_CLOSEST,
                    CRT_TRACE_INSTANCE_MASK, check, crt_blas_desc, crt_instanced_scene_desc, crt_instances_info, crt_mesh_lights, crt_mesh_shading,
-                   lib)
-from .host import Rnd, _ptr
+                   crt_tree_cost, lib)
+from .host import Rnd, _cost_dict, _ptr
 from .scene import HIT_DT, RAY_DT, STATS_DT, Scene
 
 # crt_instance, 64 B.  material_offset is the first of the two reserved words (byte 56): the fields overlap
@@ -191,6 +191,13 @@ class InstancedScene:
         ptrs = (C.c_void_p * max(len(items), 1))(*[int(p) for p, _ in items])
         counts = np.array([int(nv) for _, nv in items], np.uint64)
         check(lib().crt_instances_update_meshes_device(self._h, _ptr(ids), len(items), ptrs, _ptr(counts), 1 if sync else 0))
+
+    def tree_cost(self, mesh=-1):
+        """crt_instances_tree_cost: the SAH cost (a dict of crt_tree_cost's fields) of the live TLAS (mesh = -1) or of mesh m's BLAS,
+        computed on the device.  A TLAS's cost compares TLASes over the same instances only."""
+        c = crt_tree_cost()
+        check(lib().crt_instances_tree_cost(self._h, int(mesh), C.byref(c)))
+        return _cost_dict(c)
 
     def last_update(self):
         """{device_ms, wall_ms, state_bytes} of the last update (crt_instances_last_update)"""

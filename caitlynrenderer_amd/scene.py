@@ -9,8 +9,8 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (CRT_ABI_VERSION, CRT_BUILD_LBVH_ON_DEVICE, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_frame_stats,
-                   crt_scene_desc, lib)
-from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _ptr
+                   crt_scene_desc, crt_tree_cost, lib)
+from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _cost_dict, _ptr
 
 RAY_DT = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("pad", "<u4")])
 HIT_DT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<i4")])
@@ -244,6 +244,39 @@ class Scene:
         d, w = C.c_float(), C.c_float()
         check(lib().crt_last_update_ms(self._h, C.byref(d), C.byref(w)))
         return d.value, w.value
+
+    def rebuild_vertices(self, vertices, normals=None, lights=None):
+        """crt_rebuild_vertices: new positions (same count), optionally new normals / lights, and the tree built again from them in place
+        with the scene's own builder (scenes from for_device_build only); clears the sum (frame_count restarts).  A torch
+        tensor that lives on the GPU goes through crt_rebuild_vertices_device without leaving it (positions only)."""
+        if getattr(vertices, "is_cuda", False):
+            if normals is not None or lights is not None:
+                raise ValueError("rebuild_vertices: the device form takes positions only")
+            t = vertices.detach().reshape(-1, 3).contiguous()
+            if str(t.dtype) != "torch.float32":
+                raise TypeError("rebuild_vertices: a device tensor must be float32")
+            import torch
+            torch.cuda.current_stream(t.device).synchronize()          # the library reads it on the scene's own stream
+            self.rebuild_vertices_device(t.data_ptr(), t.shape[0])
+            return
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        l = None if lights is None else np.ascontiguousarray(lights, dtype=np.float32).reshape(-1, 18)
+        check(lib().crt_rebuild_vertices(self._h, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0],
+                                         _ptr(l), 0 if l is None else l.shape[0]))
+        self.frame_count = 0
+
+    def rebuild_vertices_device(self, ptr, n, sync=True):
+        """crt_rebuild_vertices_device: positions already on the scene's device (ptr = device address of n x 3 float32)."""
+        check(lib().crt_rebuild_vertices_device(self._h, C.c_void_p(int(ptr)), int(n), int(bool(sync))))
+        self.frame_count = 0
+
+    def tree_cost(self):
+        """crt_get_tree_cost: the SAH cost of the live CWBVH, computed on the device (a dict of crt_tree_cost's fields).  Compare a
+        refitted scene's with a rebuilt one's over the same positions."""
+        c = crt_tree_cost()
+        check(lib().crt_get_tree_cost(self._h, C.byref(c)))
+        return _cost_dict(c)
 
     def debug_read_accel(self, which):
         """crt_debug_read_accel: 0 node8 (n,80) u8, 1 CWBVH-order records (n,12) f32, 2 BVH2 (n,8) f32, 3 slot-order records (n,12) f32."""

@@ -285,7 +285,7 @@ int crt_trace_device(crt_scene* s, const void* d_rays, size_t n, void* d_hits, i
  * and the float planes if they exist, on the scene's device, one launch per tree level; clears the accumulated sum like crt_reset and
  * has the tile order measured again.  Every coordinate is checked first (finite, |x| <= 1e18, as crt_scene_create): a bad one or a
  * wrong count returns CRT_ERR_INVALID and leaves the scene as it was.  The tree keeps its topology, so its quality decays as the
- * geometry moves away from the positions it was built for ("Refit").  crt_triangle.vn with w == 0 (the loader's
+ * geometry moves away from the positions it was built for ("Refit"; crt_rebuild_vertices builds it again, crt_get_tree_cost measures it).  crt_triangle.vn with w == 0 (the loader's
  * truncated geometric normal, Scene.h:849-852) is caller data and stays as given.  Under crt_set_devices every replica follows:
  * replicas on this GPU share the refitted buffers, replicas on other GPUs receive them by peer copy.  The first call allocates
  * the refit's own state (~2.7 MB at 1 M triangles plus the host form's vertex buffer); a scene that never calls it has none. */
@@ -295,8 +295,54 @@ int crt_update_vertices(crt_scene* s, const float* vertices, size_t n_vertices,
  * host for the check of the coordinates, then runs asynchronously on the scene's stream unless sync != 0 (d_vertices must stay valid
  * until then) */
 int crt_update_vertices_device(crt_scene* s, const void* d_vertices, size_t n_vertices, int sync);
-/* device ms of the last update's refit kernels and host wall ms of the call (CRT_ERR_INVALID before the first update) */
+/* device ms of the last update's refit kernels and host wall ms of the call (CRT_ERR_INVALID before the first update); after a
+ * crt_rebuild_vertices* the two describe that call (device ms: stream time from the first builder launch to the last assembly kernel) */
 int crt_last_update_ms(crt_scene* s, float* device_ms, float* wall_ms);
+/* Animated geometry, the other remedy (DXR / OptiX call this a rebuild): new positions AND a new tree, in place.
+ * Arguments, checks and refusals are crt_update_vertices': the counts equal the create's, every coordinate finite and within 1e18
+ * (checked on the device first), normals and lights optional.  The tree is then built again from the new positions with the builder
+ * the scene was created with, by crt_scene_create's own build-on-device chain (BVH2 -> CWBVH -> leaf-order triangles and records), so
+ * every debug read, every crt_get_bvh_info field other than the times, every walk (per-ray counts included) and every frame are those
+ * of a crt_scene_create from the same arrays with the linear and the binned-SAH builder (PLOC merges in an order its atomics decide,
+ * as at create: hits and sums are equal, the tree's bytes need not be).  Only the positions cross PCIe; camera, options, shard,
+ * streams and frame buffers stay.
+ *   - Scenes built on the device only (crt_bvh_info.built_on_device): a scene created from host arrays and an instanced scene
+ *     return CRT_ERR_INVALID, and so does a scene with a replica on ANOTHER GPU (crt_set_devices).  Replicas on the scene's own GPU
+ *     (option "streams", or crt_set_devices naming it again) share the rebuilt buffers and have them before the call returns.
+ *   - All or nothing: the tree is built into new buffers and published last.  A failed check (CRT_ERR_INVALID), a CWBVH deeper than
+ *     the traversal stack (CRT_ERR_LIMIT) or a failed allocation (CRT_ERR_NOMEM) leaves everything a walk or a frame reads, every
+ *     debug read and every crt_get_bvh_info field as it was.
+ *   - A success replaces the node8s, both record arrays, the leaf-order triangles, the BVH2 (kept or dropped by create's depth
+ *     rule), the float planes where they exist, the stack sizes, the node counts, depths and the two device build times of
+ *     crt_bvh_info, and drops the refit state (the next crt_update_vertices finds the new tree's levels); the accumulated sum is
+ *     cleared as by crt_reset and the tile order is measured again.
+ *   - The first rebuild scatters the leaf-order triangle array back to source order (create threw that array away) and keeps it,
+ *     48 B per triangle, beside the host form's vertex staging; a scene that never rebuilds allocates and launches nothing for this.
+ *   - The builders wait on the host, so both forms return when the rebuild is done; sync is accepted for symmetry.
+ * There is no automatic choice between refit and rebuild: crt_get_tree_cost, taken after a refit and after a rebuild of the same
+ * positions, is the number to build a policy on. */
+int crt_rebuild_vertices(crt_scene* s, const float* vertices, size_t n_vertices,
+                         const float* normals, size_t n_normals, const crt_light* lights, size_t n_lights);
+int crt_rebuild_vertices_device(crt_scene* s, const void* d_vertices, size_t n_vertices, int sync);
+
+/* The SAH cost of a CWBVH.  For every node8 of a range and every slot with meta != 0 the slot's corners are decoded as
+ * the walk decodes them, lo = p + q_lo * 2^(e-127) and hi likewise, each rounded once to fp32, then widened to double:
+ * A = (dx*dy + dy*dz) + dz*dx, half the slot's surface area.  inner_area sums A over the inner (imask) slots; leaf_area sums
+ * A * items over the others, items = popcount(meta >> 5); root_area is A of the union of the used slots of the root node;
+ * cost = (233 * (root_area + inner_area) + 71 * leaf_area) / root_area, 0 when root_area is 0: the expected price of a random ray
+ * that hits the root box, in the instruction counts of a general node step and a triangle test (profiles/isa_counts.json).  The
+ * device computes every slot's A to the host's bits; the sums may differ by the order of the additions (no floating-point atomics:
+ * two calls on one tree return the same bits).  The cost of a tree grows when its geometry spreads out, whatever its quality:
+ * compare two trees over the SAME positions (a refit against a rebuild), not a tree with its own past.  For a TLAS the leaf items are
+ * instances, whose price is not a triangle test's: its cost compares two TLASes over the same instances and nothing else. */
+typedef struct crt_tree_cost {
+    double root_area, inner_area, leaf_area;   /* half-areas; leaf_area = sum of A(slot) * items(slot) */
+    uint64_t n_nodes8, n_inner_slots, n_leaf_slots, n_leaf_items;
+    double cost;
+} crt_tree_cost;
+/* the live CWBVH of a scene (nodes [0, n_nodes8), root 0), computed on its device; synchronous.  An instanced scene returns
+ * CRT_ERR_INVALID: its trees belong to its handle (crt_instances_tree_cost) */
+int crt_get_tree_cost(crt_scene* s, crt_tree_cost* out);
 /* test hook: the device-resident tree and records as the walks see them, unpadded: which 0 = node8 (80 B each), 1 = records in
  * CWBVH order (48 B), 2 = BVH2 FlatNodes (32 B; none when the scene has no BVH2), 3 = records in slot order (48 B).
  * dst may be NULL to query the count. */
@@ -567,6 +613,12 @@ int crt_instances_replace_meshes(crt_instances* s, const uint32_t* mesh_ids, uin
  * DESIGN.md §18, never by ray queries).
  * dst may be NULL to query the count. */
 int crt_instances_debug_read(crt_instances* s, int which, void* dst, size_t cap_bytes, size_t* n_out);
+/* crt_tree_cost (above) of the handle's live trees, computed on its device: mesh = -1 the TLAS (nodes [0, tlas_nodes8), root 0; all
+ * zeros for a handle with 0 instances), mesh = m the BLAS of mesh m (its slice of the packed node array, its own root); any other mesh
+ * is CRT_ERR_INVALID.  Any handle.  Waits for the handle's stream and for bound scenes' queued frames; synchronous.  After
+ * crt_instances_refit compare the TLAS's cost with that of a crt_instances_set of the same array, after crt_instances_update_meshes a
+ * BLAS's with that of a crt_instances_replace_meshes: "as the tree ages" in the comments above means this ratio. */
+int crt_instances_tree_cost(crt_instances* s, int32_t mesh, crt_tree_cost* out);
 int crt_instances_destroy(crt_instances* s);
 
 /* ---- frames of an instanced scene ----
@@ -766,6 +818,9 @@ int crt_bvh2_refit(crt_flatnode* nodes, size_t n_nodes, const crt_triangle* leaf
                    const float* vertices, size_t n_vertices);
 int crt_cwbvh_refit(crt_node8* nodes, size_t n_nodes8, const int32_t* tri_slots, size_t n_tris8,
                     const crt_triangle* leaf_tris, size_t n_slots, const float* vertices, size_t n_vertices);
+/* crt_tree_cost (defined with crt_get_tree_cost) of the node8s [first, first + count) of a host array, `root` among them [host]:
+ * the reference of the device kernel.  count == 0 returns all zeros; a null pointer or a root outside the range is CRT_ERR_INVALID. */
+int crt_cwbvh_cost(const crt_node8* nodes, size_t first, size_t count, size_t root, crt_tree_cost* out);
 
 /* OBJ/MTL loader, Caitlyn/Scene.h:742-926 Read_Object (+ ReadMtl :507-596; textures
  * not loaded) [host].  Applies the -vertex_min translation (:915-925) to vertices,

@@ -1,0 +1,502 @@
+"""Rebuilding a live scene's tree on the GPU and asking what a tree costs.
+
+crt_rebuild_vertices gives a device-built scene new positions AND a new tree, in place: every debug read, walk and frame is held here to
+a scene created fresh from the same arrays.  crt_cwbvh_cost / crt_get_tree_cost / crt_instances_tree_cost report the SAH cost of a
+CWBVH: the host function is held to a numpy restatement of its definition, the device kernel to the host function.
+
+The deformation that makes a rebuild worth it is `scatter`: blocks of B consecutive vertices (one tessellated quad each) translated at
+random, so rigid pieces fly apart and a refitted tree keeps boxes that span the gaps."""
+
+import numpy as np
+import pytest
+
+from conftest import numpy_brute_force, seeded_rays
+
+RX1, RY1 = 0.6591631174087524, 0.9108020067214966      # frame-1 randomVector
+W, H = 120, 72
+TIMES = ("build_wall_ms", "build_upload_ms", "build_lbvh_device_ms", "build_convert_device_ms")
+
+
+def _tess(cornell, n, amplitude, disney=False):
+    from caitlynrenderer_amd.meshgen import tessellated_cornell, with_disney_materials
+    base = cornell[0]
+    return tessellated_cornell(with_disney_materials(base) if disney else base, n, amplitude)
+
+
+def scatter(cr, m, B, amp, seed):
+    """amp * (pcg_hash(3 * (i // B) + k + 7919 * seed) / 2^32 - 0.5) added to coordinate k of vertex i, in double, rounded to fp32"""
+    from caitlynrenderer_amd.meshgen import pcg_hash_np
+    V = m.vertices.astype(np.float64)
+    i = np.arange(V.shape[0], dtype=np.uint64)
+    for k in range(3):
+        h = pcg_hash_np((np.uint64(3) * (i // np.uint64(B)) + np.uint64(k + 7919 * seed)) & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        V[:, k] += amp * (h / 4294967296.0 - 0.5)
+    out = cr.Mesh(V.astype(np.float32), m.normals, m.texcoords, m.triangles, m.materials, m.lights, m.vertex_min)
+    out.albedo_textures = getattr(m, "albedo_textures", None)
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+def _host_cost(cr, nodes, first=0, count=None, root=0):
+    cw = cr.CWBVH()
+    cw.nodes = np.ascontiguousarray(nodes, np.uint8)
+    return cw.cost(first, count, root)
+
+
+def _np_cost(nodes, first=0, count=None, root=0):
+    """The definition of crt_tree_cost restated in numpy: corners in float32 (one rounding each), areas and sums in float64."""
+    nodes = np.ascontiguousarray(nodes, np.uint8).reshape(-1, 80)
+    count = nodes.shape[0] - first if count is None else count
+    zero = dict(root_area=0.0, inner_area=0.0, leaf_area=0.0, n_nodes8=0, n_inner_slots=0, n_leaf_slots=0, n_leaf_items=0, cost=0.0)
+    if count == 0:
+        return zero
+    nd = nodes[first:first + count]
+    p = nd[:, 0:12].copy().view(np.float32)                                           # (n, 3)
+    scale = np.ldexp(np.float32(1.0), nd[:, 12:15].astype(np.int32) - 127).astype(np.float32)
+    imask, meta = nd[:, 15].astype(np.uint32), nd[:, 24:32]
+    q = nd[:, 32:80].reshape(-1, 3, 2, 8).astype(np.float32)
+    lo = (p[:, :, None] + (q[:, :, 0, :] * scale[:, :, None]).astype(np.float32)).astype(np.float32)       # (n, 3, 8)
+    hi = (p[:, :, None] + (q[:, :, 1, :] * scale[:, :, None]).astype(np.float32)).astype(np.float32)
+
+    def area(lo3, hi3):
+        d = hi3.astype(np.float64) - lo3.astype(np.float64)
+        return (d[0] * d[1] + d[1] * d[2]) + d[2] * d[0]
+    A = area(np.moveaxis(lo, 1, 0), np.moveaxis(hi, 1, 0))                            # (n, 8)
+    used = meta != 0
+    inner = used & (((imask[:, None] >> np.arange(8, dtype=np.uint32)[None, :]) & 1) != 0)
+    leaf = used & ~inner
+    items = sum(((meta >> (5 + b)) & 1).astype(np.int64) for b in range(3))
+    r = root - first
+    out = dict(zero)
+    if used[r].any():
+        out["root_area"] = float(area(lo[r][:, used[r]].min(1), hi[r][:, used[r]].max(1)))
+    out["inner_area"] = float(A[inner].sum())
+    out["leaf_area"] = float((A[leaf] * items[leaf].astype(np.float64)).sum())
+    out["n_nodes8"], out["n_inner_slots"], out["n_leaf_slots"] = int(count), int(inner.sum()), int(leaf.sum())
+    out["n_leaf_items"] = int(items[leaf].sum())
+    ra = out["root_area"]
+    out["cost"] = 0.0 if ra == 0.0 else (233.0 * (ra + out["inner_area"]) + 71.0 * out["leaf_area"]) / ra
+    return out
+
+
+def _same_cost(a, b, n_nodes8):
+    """equal counts; areas and cost within 2 * 8 * n_nodes8 * 2^-53, relative: two summation orders of at most 8 * n_nodes8 non-negative
+    doubles each stay within (terms) * 2^-53 of the exact sum, relative; twice that apart (the root area is one term: equal bits)"""
+    for k in ("n_nodes8", "n_inner_slots", "n_leaf_slots", "n_leaf_items"):
+        assert a[k] == b[k], (k, a[k], b[k])
+    assert a["root_area"] == b["root_area"]
+    bound = 2.0 * 8.0 * max(n_nodes8, 1) * 2.0 ** -53
+    for k in ("inner_area", "leaf_area", "cost"):
+        assert abs(a[k] - b[k]) <= bound * max(abs(a[k]), abs(b[k])), (k, a[k], b[k], bound)
+
+
+def _refitted(cr, data, V):
+    cw = cr.CWBVH()
+    cw.nodes, cw.tri_slots = data.bvh8.copy(), data.bvh8_tri_slots
+    return cw.refit(data.triangles, V).nodes
+
+
+# ------------------------------------------------------------------------------------------------------------ host (no GPU) --
+
+def test_c1_symbols_and_null_arguments(cr, cornell):
+    import ctypes as C
+    import caitlynrenderer_amd._lib as L
+    for name in ("crt_rebuild_vertices", "crt_rebuild_vertices_device", "crt_get_tree_cost", "crt_instances_tree_cost", "crt_cwbvh_cost"):
+        assert name in L.SYMBOLS
+    assert all(hasattr(cr.Scene, k) for k in ("rebuild_vertices", "rebuild_vertices_device", "tree_cost"))
+    assert hasattr(cr.InstancedScene, "tree_cost") and hasattr(cr.CWBVH, "cost")
+    lib, cost = L.lib(), L.crt_tree_cost()
+    v = np.zeros((3, 3), np.float32)
+    vp = v.ctypes.data_as(C.c_void_p)
+    assert lib.crt_rebuild_vertices(None, vp, 3, None, 0, None, 0) == L.CRT_ERR_INVALID
+    assert lib.crt_rebuild_vertices(None, None, 3, None, 0, None, 0) == L.CRT_ERR_INVALID
+    assert lib.crt_rebuild_vertices_device(None, vp, 3, 1) == L.CRT_ERR_INVALID
+    assert lib.crt_rebuild_vertices_device(None, None, 3, 1) == L.CRT_ERR_INVALID
+    assert lib.crt_get_tree_cost(None, C.byref(cost)) == L.CRT_ERR_INVALID
+    assert lib.crt_instances_tree_cost(None, -1, C.byref(cost)) == L.CRT_ERR_INVALID
+    nodes = np.zeros((2, 80), np.uint8)
+    npt = nodes.ctypes.data_as(C.c_void_p)
+    assert lib.crt_cwbvh_cost(npt, 0, 2, 0, None) == L.CRT_ERR_INVALID
+    assert lib.crt_cwbvh_cost(None, 0, 2, 0, C.byref(cost)) == L.CRT_ERR_INVALID
+    assert lib.crt_cwbvh_cost(npt, 0, 2, 2, C.byref(cost)) == L.CRT_ERR_INVALID         # a root outside the range
+    assert lib.crt_cwbvh_cost(npt, 1, 1, 0, C.byref(cost)) == L.CRT_ERR_INVALID
+    if lib.crt_device_count() == 0:                   # no scene to rebuild or measure without a GPU: the create itself refuses
+        with pytest.raises(L.CrtError) as e:
+            cr.Scene(cr.SceneData.for_device_build(_tess(cornell, 4, 0.02), cornell[1], "sah"), W, H, 1)
+        assert e.value.code == L.CRT_ERR_NO_DEVICE
+
+
+@pytest.mark.parametrize("n", [4, 8])
+def test_c2_host_cost_against_the_numpy_restatement(cr, cornell, n):
+    m0 = _tess(cornell, n, 0.02)
+    m1 = scatter(cr, m0, (n + 1) ** 2, 6.0, 1)
+    data = cr.SceneData.build(m0, cornell[1], sbvh_flags=1)
+    for nodes in (data.bvh8, _refitted(cr, data, m1.vertices)):
+        n8 = nodes.shape[0]
+        got, want = _host_cost(cr, nodes), _np_cost(nodes)
+        _same_cost(got, want, n8)
+        assert got["n_nodes8"] == n8 and got["n_inner_slots"] == n8 - 1 and got["n_leaf_items"] == data.bvh8_tri_slots.shape[0]
+        assert got["root_area"] > 0.0 and got["cost"] > 233.0
+        # a sub-range with its own root: the subtree below the root's first inner slot is not contiguous, so take a plain range
+        first, count = n8 // 3, n8 // 2
+        sub, sub_want = _host_cost(cr, nodes, first, count, first + 2), _np_cost(nodes, first, count, first + 2)
+        _same_cost(sub, sub_want, count)
+        assert sub["n_nodes8"] == count and sub["root_area"] != got["root_area"]
+        empty = _host_cost(cr, nodes, 5, 0, 0)
+        assert all(v == 0 for v in empty.values())
+
+
+def test_c3_a_refit_of_scattered_pieces_costs_more_than_a_fresh_build(cr, cornell):
+    """The premise (measured on these host trees: 3.025 at n = 8, 2.404 at n = 4).  The displacement field 0.02 -> 0.5 is the
+    counter-example: a refit of it costs 0.992 of a fresh build at n = 8, so nothing is asserted of it but that both are finite."""
+    for n in (8, 4):
+        m0 = _tess(cornell, n, 0.02)
+        m1 = scatter(cr, m0, (n + 1) ** 2, 6.0, 1)
+        d0 = cr.SceneData.build(m0, cornell[1], sbvh_flags=1)
+        d1 = cr.SceneData.build(m1, cornell[1], sbvh_flags=1)
+        refit, fresh = _host_cost(cr, _refitted(cr, d0, m1.vertices))["cost"], _host_cost(cr, d1.bvh8)["cost"]
+        print(f"n = {n}: cost(refit) / cost(fresh build) = {refit / fresh:.3f}")
+        assert refit > fresh
+    m0, m1 = _tess(cornell, 8, 0.02), _tess(cornell, 8, 0.5)
+    d0, d1 = cr.SceneData.build(m0, cornell[1], sbvh_flags=1), cr.SceneData.build(m1, cornell[1], sbvh_flags=1)
+    refit, fresh = _host_cost(cr, _refitted(cr, d0, m1.vertices))["cost"], _host_cost(cr, d1.bvh8)["cost"]
+    print(f"displacement 0.02 -> 0.5, n = 8: cost(refit) / cost(fresh build) = {refit / fresh:.3f}")
+    assert np.isfinite(refit) and np.isfinite(fresh) and fresh > 0.0
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU --
+
+def _accel(scene):
+    return [scene.debug_read_accel(k) for k in range(4)]
+
+
+def _same_accel(a, b):
+    for k in range(4):
+        assert a[k].shape == b[k].shape and np.array_equal(_bits(a[k]), _bits(b[k])), k
+
+
+def _info(scene):
+    return {k: v for k, v in scene.bvh_info().items() if k not in TIMES}
+
+
+def _frames(scene, rvs):
+    scene.render_frame(*rvs[0])
+    scene.render_frames(rvs[1:])
+    return scene.read_sum().copy()
+
+
+_meshes = {}
+
+
+def _pair(cr, cornell, disney=False):
+    """(m0, m1): pose 0 and its pieces scattered, shared by the tests"""
+    if disney not in _meshes:
+        m0 = _tess(cornell, 8, 0.02, disney)
+        _meshes[disney] = (m0, scatter(cr, m0, 81, 6.0, 1))
+    return _meshes[disney]
+
+
+@pytest.mark.gpu
+def test_g1_a_rebuild_gives_the_bytes_of_a_create(cr, cornell):
+    m0, m1 = _pair(cr, cornell)
+    sizes = {}
+    for builder in ("sah", "lbvh"):
+        sc = cr.Scene(cr.SceneData.for_device_build(m0, cornell[1], builder), W, H, 1)
+        n8_0 = sc.bvh_info()["n_nodes8"]
+        sc.rebuild_vertices(m1.vertices)
+        fresh = cr.Scene(cr.SceneData.for_device_build(m1, cornell[1], builder), W, H, 1)
+        _same_accel(_accel(sc), _accel(fresh))
+        assert _info(sc) == _info(fresh)
+        sizes[builder] = (n8_0, sc.bvh_info()["n_nodes8"])
+        dev_ms, wall_ms = sc.last_update_ms()
+        assert dev_ms > 0.0 and wall_ms > 0.0
+        sc.close(); fresh.close()
+    print("node8 counts (m0, m1) per builder:", sizes)
+    assert any(a != b for a, b in sizes.values()), sizes          # a changed array size is exercised (host trees: 206 and 178)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("builder", ["sah", "lbvh", "ploc"])
+def test_g2_walks_of_a_rebuilt_scene(cr, cornell, builder):
+    from caitlynrenderer_amd._lib import CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_CLOSEST, CRT_TRACE_TIE_LOWEST_ID
+    m0, m1 = _pair(cr, cornell)
+    sc = cr.Scene(cr.SceneData.for_device_build(m0, cornell[1], builder), W, H, 1)
+    sc.rebuild_vertices(m1.vertices)
+    fresh = cr.Scene(cr.SceneData.for_device_build(m1, cornell[1], builder), W, H, 1)
+    rays = seeded_rays(m1, 20000, 7, cr.RAY_DT)
+    for mode in (CRT_TRACE_CLOSEST, CRT_TRACE_BVH2 | CRT_TRACE_TIE_LOWEST_ID):
+        got, want = sc.trace(rays, mode), fresh.trace(rays, mode)
+        assert np.array_equal(got["tri"], want["tri"]) and (got["tri"] >= 0).any() and (got["tri"] < 0).any()
+        for k in ("t", "u", "v"):
+            assert np.array_equal(got[k].view(np.uint32), want[k].view(np.uint32)), (mode, k)
+    for mode in (CRT_TRACE_ANY, CRT_TRACE_ANY | CRT_TRACE_BVH2):
+        assert np.array_equal(sc.trace(rays, mode)["tri"] >= 0, fresh.trace(rays, mode)["tri"] >= 0), mode
+    st = sc.trace(rays, CRT_TRACE_CLOSEST, stats=True)[1]
+    if builder != "ploc":                                          # the same tree: the same steps, ray by ray
+        st_fresh = fresh.trace(rays, CRT_TRACE_CLOSEST, stats=True)[1]
+        assert np.array_equal(st["nodes"], st_fresh["nodes"]) and np.array_equal(st["tris"], st_fresh["tris"])
+    upd = cr.Scene(cr.SceneData.for_device_build(m0, cornell[1], builder), W, H, 1)
+    upd.update_vertices(m1.vertices)
+    st_upd = upd.trace(rays, CRT_TRACE_CLOSEST, stats=True)[1]
+    assert not np.array_equal(st["nodes"], st_upd["nodes"])       # not the refitted tree
+    sub = rays[:48]
+    tri, t, u, v = numpy_brute_force(m1, sub)
+    got = sc.trace(sub)
+    assert np.array_equal(got["tri"], tri) and np.array_equal(got["t"].view(np.uint32), t.view(np.uint32))
+    sc.close(); fresh.close(); upd.close()
+
+
+_oracle_frames = {}
+
+
+def _reference_frames(cr, ob, cornell, depth, disney, rvs):
+    """the fresh scene's and the oracle's four frames of m1, computed once per (depth, materials)"""
+    key = (depth, disney)
+    if key not in _oracle_frames:
+        m1 = _pair(cr, cornell, disney)[1]
+        fresh = cr.Scene(cr.SceneData.for_device_build(m1, cornell[1], "sah"), W, H, depth)
+        want = _frames(fresh, rvs)
+        fresh.close()
+        orc = ob.Oracle(cr.SceneData.build(m1, cornell[1], builder="sah", convert="device"), W, H, depth, cornell[1])
+        ref = np.zeros((H, W, 3), np.float32)
+        for r in rvs:
+            orc.render_frame(r[0], r[1], ref, threads=8)
+        assert ref.max() > 0.1
+        want.setflags(write=False); ref.setflags(write=False)
+        _oracle_frames[key] = (want, ref)
+    return _oracle_frames[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fan", ["default", "streams0", "streams1", "devices"])
+@pytest.mark.parametrize("depth,disney", [(1, False), (4, False), (4, True)])
+def test_g3_frames_after_a_rebuild_equal_a_fresh_scene_and_the_oracle(cr, ob, cornell, depth, disney, fan):
+    m0, m1 = _pair(cr, cornell, disney)
+    rnd = cr.Rnd()
+    rvs = [(rnd.randf2(), rnd.randf2()) for _ in range(4)]
+    sc = cr.Scene(cr.SceneData.for_device_build(m0, cornell[1], "sah"), W, H, depth)
+    if fan == "streams0":
+        sc.set_option("streams", 0)                                # the library's pick: two streams at depth 4
+    elif fan == "streams1":
+        sc.set_option("streams", 1)
+    elif fan == "devices":
+        sc.set_devices([0, 0])
+    sc.render_frame(RX1, RY1)                                      # the replicas exist and hold the old tree's planes
+    assert sc.read_sum().any()
+    if fan == "streams0" and depth == 4:
+        assert sc.debug_launch_info()["shards"] == 2
+    sc.rebuild_vertices(m1.vertices)
+    assert not sc.read_sum().any()                                 # the rebuild clears the sum
+    got = _frames(sc, rvs)
+    want, ref = _reference_frames(cr, ob, cornell, depth, disney, rvs)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+    assert sc.frame_stats()["stack_overflows"] == 0
+    sc.close()
+
+
+@pytest.mark.gpu
+def test_g4_a_sequence_of_updates_and_rebuilds(cr, cornell):
+    import torch
+    m0, m1 = _pair(cr, cornell)
+    m_a, m2 = _tess(cornell, 8, 0.4), scatter(cr, m0, 81, 3.0, 2)
+    sc = cr.Scene(cr.SceneData.for_device_build(m0, cornell[1], "sah"), W, H, 2)
+    created = _accel(sc)
+    info0 = _info(sc)
+    sc.update_vertices(m_a.vertices)
+    sc.rebuild_vertices(m1.vertices)
+    sc.update_vertices(m2.vertices)                                # the refit state was found again on the new tree
+    twin = cr.Scene(cr.SceneData.for_device_build(m1, cornell[1], "sah"), W, H, 2)
+    twin.update_vertices(m2.vertices)
+    _same_accel(_accel(sc), _accel(twin))
+    assert np.array_equal(_frames(sc, [(RX1, RY1), (0.3, 0.7)]).view(np.uint32), _frames(twin, [(RX1, RY1), (0.3, 0.7)]).view(np.uint32))
+    twin.close()
+    sc.rebuild_vertices(m0.vertices)
+    _same_accel(_accel(sc), created)
+    assert _info(sc) == info0
+    used = []
+    for k in range(10):                                            # m1, m0, m1, ...: nothing accumulates
+        sc.rebuild_vertices((m1 if k % 2 == 0 else m0).vertices)
+        free, total = torch.cuda.mem_get_info()
+        used.append(total - free)
+    print("device bytes in use after each rebuild:", used)
+    assert used[9] == used[1], used
+    _same_accel(_accel(sc), created)
+    sc.close()
+
+
+def _refused(cr, sc, code, *args, **kw):
+    from caitlynrenderer_amd._lib import CrtError
+    with pytest.raises(CrtError) as e:
+        sc.rebuild_vertices(*args, **kw)
+    assert e.value.code == code, e.value
+    return str(e.value)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bad", ["count_less", "count_more", "nan", "+inf", "-inf", "normals", "lights", "host_arrays"])
+def test_g5_a_refused_rebuild_leaves_the_scene_as_it_was(cr, cornell, bad):
+    from caitlynrenderer_amd._lib import CRT_ERR_INVALID
+    m0, m1 = _pair(cr, cornell)
+    data = cr.SceneData.build(m0, cornell[1]) if bad == "host_arrays" else cr.SceneData.for_device_build(m0, cornell[1], "sah")
+    sc, ref = cr.Scene(data, W, H, 2), cr.Scene(data, W, H, 2)
+    sc.render_frame(RX1, RY1); ref.render_frame(RX1, RY1)
+    if bad != "host_arrays":
+        sc.rebuild_vertices(m0.vertices)                           # a scene that HAS rebuild state refuses the same way
+        ref.reset(); ref.render_frame(RX1, RY1)
+        sc.render_frame(RX1, RY1)
+    V = m1.vertices.copy()
+    kw = {}
+    if bad == "count_less":
+        V = V[:-1]
+    elif bad == "count_more":
+        V = np.concatenate([V, V[:1]])
+    elif bad == "normals":
+        kw["normals"] = m0.normals[:-1]
+    elif bad == "lights":
+        kw["lights"] = np.concatenate([m0.lights, m0.lights])
+    elif bad != "host_arrays":
+        V[V.shape[0] - 3, 2] = {"nan": np.nan, "+inf": np.inf, "-inf": -np.inf}[bad]
+    a0, info0 = _accel(sc), _info(sc)
+    _refused(cr, sc, CRT_ERR_INVALID, V, **kw)
+    _same_accel(_accel(sc), a0)
+    assert _info(sc) == info0
+    rvs = [(0.3, 0.7), (0.1, 0.2), (0.5, 0.25), (0.9, 0.4)]
+    assert np.array_equal(_frames(sc, rvs).view(np.uint32), _frames(ref, rvs).view(np.uint32))
+    sc.close(); ref.close()
+
+
+def _two_mesh_handle(cr, cornell, updatable=False, n_instances=6):
+    m_a, m_b = _tess(cornell, 4, 0.02), _tess(cornell, 8, 0.02)
+    rng = np.random.default_rng(11)
+    mats = np.zeros((n_instances, 3, 4), np.float32)
+    mats[:, :, :3] = np.eye(3, dtype=np.float32)
+    mats[:, :, 3] = rng.uniform(-900.0, 900.0, (n_instances, 3)).astype(np.float32)
+    inst = cr.instances_array(mats, np.arange(n_instances) % 2)
+    return (m_a, m_b), inst, cr.InstancedScene([m_a, m_b], inst, builder="sah", updatable=updatable)
+
+
+@pytest.mark.gpu
+def test_g5_an_instanced_scene_is_refused(cr, cornell):
+    from caitlynrenderer_amd._lib import CRT_ERR_INVALID, CrtError
+    (m_a, m_b), inst, h = _two_mesh_handle(cr, cornell)
+    sc = h.frame_scene([m_a, m_b], m_a.materials, m_a.lights, W, H, 2)
+    sc.update(cornell[1])
+    rvs = [(0.3, 0.7), (0.1, 0.2), (0.5, 0.25), (0.9, 0.4)]
+    before = _frames(sc, rvs)
+    nodes = (h.tlas_nodes(), h.blas_nodes(), h.blas_records())
+    msg = _refused(cr, sc, CRT_ERR_INVALID, m_a.vertices)
+    assert "crt_instances_replace_meshes" in msg
+    with pytest.raises(CrtError) as e:
+        sc.tree_cost()
+    assert e.value.code == CRT_ERR_INVALID and "crt_instances_tree_cost" in str(e.value)
+    for a, b in zip(nodes, (h.tlas_nodes(), h.blas_nodes(), h.blas_records())):
+        assert np.array_equal(_bits(a), _bits(b))
+    sc.reset()
+    assert np.array_equal(_frames(sc, rvs).view(np.uint32), before.view(np.uint32))
+    sc.close(); h.close()
+
+
+@pytest.mark.gpu
+def test_g5_a_replica_on_another_gpu_is_refused(cr, cornell):
+    import torch
+    from caitlynrenderer_amd._lib import CRT_ERR_INVALID
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    m0, m1 = _pair(cr, cornell)
+    data = cr.SceneData.for_device_build(m0, cornell[1], "sah")
+    sc, ref = cr.Scene(data, W, H, 2), cr.Scene(data, W, H, 2)
+    sc.set_devices([0, 1])
+    a0 = _accel(sc)
+    assert "another GPU" in _refused(cr, sc, CRT_ERR_INVALID, m1.vertices)
+    _same_accel(_accel(sc), a0)
+    rvs = [(0.3, 0.7), (0.1, 0.2), (0.5, 0.25), (0.9, 0.4)]
+    assert np.array_equal(_frames(sc, rvs).view(np.uint32), _frames(ref, rvs).view(np.uint32))
+    sc.close(); ref.close()
+
+
+@pytest.mark.gpu
+def test_g6_the_device_form_takes_a_torch_tensor(cr, cornell):
+    import torch
+    m0, m1 = _pair(cr, cornell)
+    data = cr.SceneData.for_device_build(m0, cornell[1], "sah")
+    a, b = cr.Scene(data, W, H, 2), cr.Scene(data, W, H, 2)
+    t = torch.from_numpy(m1.vertices).to("cuda")
+    a.rebuild_vertices(t)
+    b.rebuild_vertices(m1.vertices)
+    _same_accel(_accel(a), _accel(b))
+    assert _info(a) == _info(b)
+    a.rebuild_vertices_device(t.data_ptr(), t.shape[0], sync=False)      # the explicit form, on a scene that already rebuilt
+    a.sync()
+    _same_accel(_accel(a), _accel(b))
+    rvs = [(RX1, RY1), (0.3, 0.7)]
+    assert np.array_equal(_frames(a, rvs).view(np.uint32), _frames(b, rvs).view(np.uint32))
+    assert a.last_update_ms()[0] > 0.0
+    a.close(); b.close()
+
+
+@pytest.mark.gpu
+def test_g7_scene_cost_equals_the_host_function(cr, cornell):
+    m0, m1 = _pair(cr, cornell)
+    sc = cr.Scene(cr.SceneData.for_device_build(m0, cornell[1], "sah"), W, H, 1)
+
+    def check():
+        nodes = sc.debug_read_accel(0)
+        got, again = sc.tree_cost(), sc.tree_cost()
+        assert got == again                                        # no floating-point atomics: the same bits
+        _same_cost(got, _host_cost(cr, nodes), nodes.shape[0])
+        assert got["n_nodes8"] == nodes.shape[0] and got["n_leaf_items"] == m0.triangles.shape[0] and got["cost"] > 233.0
+        return got["cost"]
+    check()
+    sc.update_vertices(m1.vertices)
+    refitted = check()
+    sc.rebuild_vertices(m1.vertices)
+    rebuilt = check()
+    print(f"sah, scatter 6.0: cost(update) / cost(rebuild) = {refitted / rebuilt:.3f}")
+    assert refitted > rebuilt
+    sc.close()
+
+
+@pytest.mark.gpu
+def test_g7_instances_cost_equals_the_host_function(cr, cornell):
+    from caitlynrenderer_amd._lib import CRT_ERR_INVALID, CrtError
+    (m_a, m_b), inst, h = _two_mesh_handle(cr, cornell, updatable=True)
+    n8 = []
+    for m in (m_a, m_b):                                           # per-mesh node counts from one-mesh handles
+        one = cr.InstancedScene([m], cr.instances_array(np.eye(3, 4, dtype=np.float32)[None], [0]), builder="sah")
+        n8.append(int(one.info()["blas_nodes8"]))
+        one.close()
+    assert sum(n8) == h.info()["blas_nodes8"]
+
+    def check():
+        tlas, blas = h.tlas_nodes(), h.blas_nodes()
+        got = h.tree_cost(-1)
+        assert got == h.tree_cost() == h.tree_cost(-1)
+        _same_cost(got, _host_cost(cr, tlas), tlas.shape[0])
+        assert got["n_leaf_items"] == inst.shape[0] and got["root_area"] > 0.0
+        _same_cost(h.tree_cost(0), _host_cost(cr, blas, 0, n8[0], 0), n8[0])
+        _same_cost(h.tree_cost(1), _host_cost(cr, blas, n8[0], n8[1], n8[0]), n8[1])
+        assert h.tree_cost(0)["n_leaf_items"] == m_a.triangles.shape[0] and h.tree_cost(1)["n_leaf_items"] == m_b.triangles.shape[0]
+        return got["cost"]
+    c_set = check()
+    moved = inst.copy()
+    moved["object_to_world"][:, [3, 7, 11]] = moved["object_to_world"][::-1, [3, 7, 11]] * np.float32(1.5)
+    h.refit(moved)
+    c_refit = check()
+    assert c_refit != c_set
+    blas_before = h.tree_cost(1)["cost"]
+    h.update_meshes({1: scatter(cr, m_b, 81, 6.0, 1).vertices})
+    check()
+    assert h.tree_cost(1)["cost"] != blas_before
+    for bad in (2, 7, -2):
+        with pytest.raises(CrtError) as e:
+            h.tree_cost(bad)
+        assert e.value.code == CRT_ERR_INVALID
+    h.close()
+    empty = cr.InstancedScene([m_a], cr.instances_array(np.zeros((0, 12), np.float32), []), capacity=4, builder="sah")
+    assert all(v == 0 for v in empty.tree_cost(-1).values())
+    assert empty.tree_cost(0)["n_leaf_items"] == m_a.triangles.shape[0]
+    empty.close()
