@@ -15,6 +15,7 @@ CRT_ABI_VERSION = int(os.environ.get("CRT_LIB_ABI", "6"))      # CRT_LIB_ABI: wi
 CRT_OK, CRT_ERR_INVALID, CRT_ERR_NO_DEVICE, CRT_ERR_HIP, CRT_ERR_IO, CRT_ERR_LIMIT, CRT_ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6
 CRT_TRACE_CLOSEST, CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_TIE_LOWEST_ID = 0, 1, 2, 4
 CRT_TRACE_INSTANCE_MASK = 8              # crt_instances_trace only: the low 8 bits of crt_ray.pad are the ray's instance mask
+CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_AOV_ALBEDO, CRT_AOV_EMISSION, CRT_AOV_ALL = 1, 2, 4, 8, 16, 31    # crt_render_aov's channels
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
 CRT_INSTANCES_UPDATABLE = 1 << 16
@@ -135,6 +136,9 @@ SYMBOLS = {
     "crt_trace": (_I, [_P, _P, _SZ, _P, _I, _P]),
     "crt_trace_device": (_I, [_P, _P, _SZ, _P, _I, _P, _I]),
     "crt_resolve_device": (_I, [_P, C.c_float, C.POINTER(C.c_void_p), _I]),
+    "crt_render_aov": (_I, [_P, _F, _F, _U32, _I]),
+    "crt_read_aov": (_I, [_P, _U32, _P, _SZ]),
+    "crt_aov_device": (_I, [_P, _U32, C.POINTER(_P)]),
     "crt_get_launch_times": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "crt_update_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),

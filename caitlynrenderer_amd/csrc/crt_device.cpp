@@ -76,6 +76,23 @@ uint32_t morton2(uint32_t x, uint32_t y) {
 
 }  // namespace
 
+// What crt_render_aov keeps, allocated by a scene's first call: the five channel buffers, each by the first call that asks
+// for it, and what the dispatch needs beside the frame's own buffers.  The scene's stream has drained when this is destroyed.
+struct AovState {
+    void* d_chan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // HIT, IDS, NORMAL, ALBEDO, EMISSION: width * height * 16 bytes, linear pixel order
+    uint32_t rendered = 0;               // channels some call has written
+    uint32_t last = 0;                   // the channels of the last call
+    // flat scenes: the tiles of the CALLER's shard (crt_set_shard), whatever option "streams" made of them for the frames
+    uint2* d_tile_xy = nullptr;
+    uint32_t n_local_pixels = 0, rank = 0, world = 0, tile = 0;
+    uint32_t* d_count = nullptr;         // instanced scenes: the 8 counters of the primary rays' queue (the frames' banks stay as they are)
+    ~AovState() {
+        for (void* p : d_chan) if (p) (void)hipFree(p);
+        if (d_tile_xy) (void)hipFree(d_tile_xy);
+        if (d_count) (void)hipFree(d_count);
+    }
+};
+
 // What crt_update_vertices keeps between updates, allocated by a scene's first update: a scene that never updates holds none of it.
 struct RefitState {
     int device = 0;
@@ -185,6 +202,7 @@ struct crt_scene {
     uint32_t instance_masks = 0, mask_primary = 255, mask_bounce = 255, mask_shadow = 255;   // options of those names
     uint64_t cmask_seen = 0;             // the handle's child-mask pass this scene's stream last waited for
     SceneLights* lit = nullptr;          // lights that follow the instances; null = desc->lights alone, as before
+    AovState* aov = nullptr;             // crt_render_aov's buffers, from the first call on
 
     // shard + frame buffers
     uint32_t rank = 0, world = 1, tile = 16;   // 16x16: four waves per tile — fine enough for the cost-sorted schedule (1 M triangles: 0.273 ms at 64, 0.257 at 16)
@@ -364,7 +382,8 @@ struct crt_scene {
         delete refit;
         delete rebuild;
         delete lit;
-        if (shares_scene)                    // borrowed from the primary, which frees them
+        delete aov;
+        if (shares_scene)                   // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
                         d_rays[0], d_rays[1], d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
@@ -2678,6 +2697,150 @@ int crt_debug_read_queue(crt_scene* s, int which, uint32_t segment, crt_ray* dst
             done += n;
         }
     }
+    return CRT_OK;
+}
+
+// ---------------------------------------------------------------- crt_render_aov --
+// First-hit feature buffers of the current view: enqueued on the scene's stream behind whatever frames are queued there.
+// Nothing a frame reads or reports is written: not the sum, the counter banks, the spans or the stats.  An instanced scene borrows the
+// frame's segment-0 queue, hit buffers and path state, which every frame writes anew before it reads them.
+
+static int aov_channel_index(uint32_t channel) {
+    switch (channel) {
+        case CRT_AOV_HIT: return 0;
+        case CRT_AOV_IDS: return 1;
+        case CRT_AOV_NORMAL: return 2;
+        case CRT_AOV_ALBEDO: return 3;
+        case CRT_AOV_EMISSION: return 4;
+        default: return -1;
+    }
+}
+
+int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_render_aov: null scene");
+    if (channels == 0u || (channels & ~(uint32_t)CRT_AOV_ALL)) return fail(CRT_ERR_INVALID, "crt_render_aov: channels is a non-empty set of CRT_AOV_* bits");
+    if (!s->have_camera) return fail(CRT_ERR_INVALID, "crt_render_aov: crt_set_camera was never called");
+    if (s->accel != 0u) return fail(CRT_ERR_INVALID, "crt_render_aov: the feature buffers come from the CWBVH walk (option accel is 0): the BVH2 walk has another tie rule");
+    if (s->primary || (!s->peers.empty() && s->streams <= 1u))
+        return fail(CRT_ERR_INVALID, "crt_render_aov: a scene on one device only (crt_set_devices has dealt this one's tiles to several)");
+    HIPCHK(hipSetDevice(s->device));
+    int rc;
+    if (!s->aov) {
+        s->aov = new (std::nothrow) AovState;
+        if (!s->aov) return fail(CRT_ERR_NOMEM, "crt_render_aov: out of host memory");
+    }
+    AovState* const av = s->aov;
+    const size_t n_pixels = (size_t)s->width * s->height;
+    if (n_pixels >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_render_aov: frame too large for 32-bit pixel indices");
+    for (int k = 0; k < 5; ++k)
+        if ((channels >> k & 1u) && !av->d_chan[k]) {
+            float4* p = nullptr;
+            if ((rc = dev_alloc(&p, n_pixels))) return rc;
+            av->d_chan[k] = p;
+        }
+    crt::AovOut out{};
+    out.hit = static_cast<float4*>(av->d_chan[0]); out.ids = static_cast<int4*>(av->d_chan[1]); out.normal = static_cast<float4*>(av->d_chan[2]);
+    out.albedo = static_cast<float4*>(av->d_chan[3]); out.emission = static_cast<float4*>(av->d_chan[4]);
+    if (s->inst) {
+        if ((rc = ensure_frame(s))) return rc;
+        const size_t Q = 8 * (size_t)s->sub_capacity;
+        if (!s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
+        if (!s->d_qinst && (rc = dev_alloc(&s->d_qinst, Q))) return rc;
+        if (!av->d_count && (rc = dev_alloc(&av->d_count, 8 * kCounterStride))) return rc;
+    } else if (!av->d_tile_xy || av->rank != s->shard_rank || av->world != s->shard_world || av->tile != s->tile) {
+        // the caller's shard, dealt as crt_set_shard deals it
+        std::vector<uint2> tiles;
+        try { deal_tiles(s->width, s->height, s->tile, s->shard_rank, s->shard_world, tiles, nullptr); }
+        catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_render_aov: out of host memory (tile list)"); }
+        const uint64_t px = (uint64_t)tiles.size() * s->tile * s->tile;
+        if (px >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_render_aov: shard too large for 32-bit pixel indices");
+        HIPCHK(hipStreamSynchronize(s->stream));                          // an earlier call may still read the old list
+        if (av->d_tile_xy) { (void)hipFree(av->d_tile_xy); av->d_tile_xy = nullptr; }
+        if ((rc = dev_alloc(&av->d_tile_xy, tiles.size()))) return rc;
+        if (!tiles.empty()) HIPCHK(hipMemcpy(av->d_tile_xy, tiles.data(), tiles.size() * sizeof(uint2), hipMemcpyHostToDevice));
+        av->n_local_pixels = (uint32_t)px; av->rank = s->shard_rank; av->world = s->shard_world; av->tile = s->tile;
+    }
+    crt::launch_aov_fill(out, channels, (uint32_t)n_pixels, s->stream);
+    if (s->inst) {
+        if (s->n_local_pixels) {
+            crt::InstancesView v{};
+            crt::instances_view(s->inst, &v);
+            const bool masked = s->instance_masks != 0u;
+            if (masked && (rc = crt::instances_child_masks_for(s->inst, s->stream, &s->cmask_seen))) return rc;
+            HIPCHK(hipMemsetAsync(av->d_count, 0, 8 * kCounterStride * sizeof(uint32_t), s->stream));
+            crt::RaygenArgs ra{};
+            ra.f = frame_args(s, rx, ry);
+            ra.f.tile_order = nullptr;
+            ra.rays = s->d_rays[0]; ra.count = av->d_count; ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
+            ra.zero_counts = nullptr; ra.n_zero = 0;                      // the frames' counter banks stay as the last frame left them
+            crt::launch_raygen(ra, s->stream);
+            crt::InstMaskQueueArgs qa{};
+            qa.nodes = v.nodes; qa.tris = v.tris; qa.inst = v.inst;
+            if (masked) { qa.child_masks = v.child_masks; qa.n_tlas8 = v.tlas_nodes8; qa.ray_mask = s->mask_primary; }
+            qa.rays = s->d_rays[0]; qa.count = av->d_count; qa.hits = s->d_qhits; qa.hit_inst = s->d_qinst;
+            qa.sub_capacity = s->sub_capacity; qa.n_instances = v.n_instances; qa.stack_entries = v.stack_entries;
+            qa.refill_min = 8; qa.tri_min = 2;
+            qa.visit_totals = nullptr; qa.overflow = s->d_overflow;
+            crt::launch_closest_instances_queue(qa, false, masked, s->stream);
+            crt::InstAovArgs a{};
+            a.triangles = s->d_triangles; a.normals = s->d_normals; a.materials = s->d_materials;
+            a.texcoords = s->d_texcoords; a.textures = s->d_textures;
+            a.tex_width = s->tex_width; a.tex_height = s->tex_height; a.n_textures = s->n_textures;
+            a.f = ra.f;
+            a.sub_capacity = s->sub_capacity;
+            a.rays_in = s->d_rays[0]; a.count_in = av->d_count; a.hits_in = s->d_qhits;
+            a.hit_inst = s->d_qinst; a.inst_w2o = v.w2o; a.inst_mesh = v.mesh_of; a.mesh_base = s->d_mesh_base;
+            a.channels = channels; a.out = out;
+            crt::launch_aov_instanced(a, s->stream);
+        }
+    } else if (av->n_local_pixels) {
+        crt::AovArgs a{};
+        a.nodes = s->d_nodes; a.tris = s->d_tris; a.triangles = s->d_triangles; a.normals = s->d_normals; a.materials = s->d_materials;
+        a.stack_entries = s->stack_entries;
+        a.texcoords = s->d_texcoords; a.textures = s->d_textures;
+        a.tex_width = s->tex_width; a.tex_height = s->tex_height; a.n_textures = s->n_textures;
+        a.f = frame_args(s, rx, ry);
+        a.f.tile_xy = av->d_tile_xy; a.f.tile_order = nullptr; a.f.n_local_pixels = av->n_local_pixels;
+        a.overflow = s->d_overflow;
+        a.channels = channels; a.out = out;
+        crt::launch_aov(a, s->stream);
+    }
+    HIPCHK(hipGetLastError());
+    av->rendered |= channels;
+    av->last = channels;
+    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+static int aov_channel_of(crt_scene* s, uint32_t channel, const char* who, void** d_ptr) {
+    const int k = aov_channel_index(channel);
+    if (k < 0) return fail(CRT_ERR_INVALID, std::string(who) + ": channel is ONE of the CRT_AOV_* bits");
+    if (!s->aov || !(s->aov->rendered & channel) || !s->aov->d_chan[k]) return fail(CRT_ERR_INVALID, std::string(who) + ": no crt_render_aov call has rendered this channel");
+    *d_ptr = s->aov->d_chan[k];
+    return CRT_OK;
+}
+
+int crt_read_aov(crt_scene* s, uint32_t channel, void* dst, size_t n_bytes) {
+    if (!s || !dst) return fail(CRT_ERR_INVALID, "crt_read_aov: null argument");
+    void* d = nullptr;
+    const int rc = aov_channel_of(s, channel, "crt_read_aov", &d);
+    if (rc) return rc;
+    if (n_bytes != (size_t)s->width * s->height * 16u) return fail(CRT_ERR_INVALID, "crt_read_aov: n_bytes must be width*height*16");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemcpyAsync(dst, d, n_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr) {
+    if (!s || !d_ptr) return fail(CRT_ERR_INVALID, "crt_aov_device: null argument");
+    *d_ptr = nullptr;
+    void* d = nullptr;
+    const int rc = aov_channel_of(s, channel, "crt_aov_device", &d);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    *d_ptr = d;
     return CRT_OK;
 }
 

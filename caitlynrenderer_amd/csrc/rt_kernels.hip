@@ -2034,6 +2034,127 @@ __global__ void __launch_bounds__(256) k_resolve_packed(FrameArgs f, const float
     }
 }
 
+// ------------------------------------------------------------------ first-hit feature buffers ----
+// What k_segment computes at a frame's first hit, handed out: the hit record, the ids, the shading normal after the face-forward flip, the
+// albedo the Lambert branch multiplies into T, the emission.  The attribute fetch restates k_segment's lines operation for operation (record ->
+// slot / material, vn, the instance's normal transform, vt, sample_albedo, pow), so a value equals the integrator's by bits.  Kernels of
+// their own: every k_segment keeps its text.
+
+// the miss values of the requested channels, every pixel of the frame: what a miss, or a pixel of another shard rank, keeps
+__global__ void __launch_bounds__(256) k_aov_fill(AovOut out, uint32_t channels, uint32_t n_pixels) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (channels & CRT_AOV_BIT_HIT) out.hit[i] = make_float4(CRT_INF, 0.f, 0.f, __int_as_float(-1));
+    if (channels & CRT_AOV_BIT_IDS) out.ids[i] = make_int4(-1, -1, -1, 0);
+    if (channels & CRT_AOV_BIT_NORMAL) out.normal[i] = zero;
+    if (channels & CRT_AOV_BIT_ALBEDO) out.albedo[i] = zero;
+    if (channels & CRT_AOV_BIT_EMISSION) out.emission[i] = zero;
+}
+
+// One hit's channels.  slot: the triangle's place in `triangles`; tri_out: what HIT.tri reports; d: the primary ray's direction.
+// INST: the hit instance's words, as k_segment<INST> reads them.  `channels` is wave-uniform.
+template <bool INST, typename Args>
+__device__ __forceinline__ void aov_store(const Args& a, const AovOut& out, uint32_t channels, size_t at, vec3 d, float t, float bu, float bv, int tri_out,
+                                          int slot, int mtl, uint32_t inst_id, uint32_t inst_word, uint32_t normal0, uint32_t texcoord0) {
+    int4 vn = a.triangles[3 * (size_t)slot + 1];
+    if constexpr (INST) { if (vn.w != 0) { vn.x += (int)normal0; vn.y += (int)normal0; vn.z += (int)normal0; } }
+    vec3 n;
+    if (vn.w == 0) n = V3((float)vn.x, (float)vn.y, (float)vn.z);
+    else {
+        const float* N = a.normals;
+        const vec3 na = V3(N[3 * (size_t)vn.x], N[3 * (size_t)vn.x + 1], N[3 * (size_t)vn.x + 2]);
+        const vec3 nb = V3(N[3 * (size_t)vn.y], N[3 * (size_t)vn.y + 1], N[3 * (size_t)vn.y + 2]);
+        const vec3 nc = V3(N[3 * (size_t)vn.z], N[3 * (size_t)vn.z + 1], N[3 * (size_t)vn.z + 2]);
+        const float w = 1.0f - bu - bv;
+        n = (na * w + nb * bu) + nc * bv;
+    }
+    if constexpr (INST) {
+        if ((inst_word & 0x80000000u) == 0u) {
+            const float* W = a.inst_w2o + 12 * (size_t)inst_id;
+            vec3 m = V3((W[0] * n.x + W[4] * n.y) + W[8] * n.z, (W[1] * n.x + W[5] * n.y) + W[9] * n.z, (W[2] * n.x + W[6] * n.y) + W[10] * n.z);
+            const float ln = sqrt_ieee((n.x * n.x + n.y * n.y) + n.z * n.z), lm = sqrt_ieee((m.x * m.x + m.y * m.y) + m.z * m.z);
+            if (lm != 0.0f && __builtin_isfinite(lm)) m = m * __fdiv_rn(ln, lm);
+            n = m;
+        }
+    }
+    const float4 m_albedo = a.materials[4 * (size_t)mtl], m_emission = a.materials[4 * (size_t)mtl + 1];
+    const float cos_incident = dot(d, n);
+    if (cos_incident > 0) n = -n;
+    const bool emissive = m_emission.w != -1.0f;
+    bool textured = false;
+    if (channels & (CRT_AOV_BIT_ALBEDO | CRT_AOV_BIT_IDS)) {
+        const float tex = a.materials[4 * (size_t)mtl + 3].x;
+        textured = tex != -1.0f && a.textures != nullptr;
+        if (channels & CRT_AOV_BIT_ALBEDO) {
+            vec3 albedo = V3(m_albedo.x, m_albedo.y, m_albedo.z);
+            if (textured) {
+                int4 vt = a.triangles[3 * (size_t)slot + 2];
+                if constexpr (INST) { vt.x += (int)texcoord0; vt.y += (int)texcoord0; vt.z += (int)texcoord0; }
+                const float2 ta = a.texcoords[vt.x], tb2 = a.texcoords[vt.y], tc2 = a.texcoords[vt.z];
+                const float w = 1.0f - bu - bv;
+                const float tu = (ta.x * w + tb2.x * bu) + tc2.x * bv;
+                const float tv = (ta.y * w + tb2.y * bu) + tc2.y * bv;
+                const vec3 c = sample_albedo(a, tu, tv, (int)tex);
+                albedo = V3((float)pow((double)c.x, (double)2.2f), (float)pow((double)c.y, (double)2.2f),
+                            (float)pow((double)c.z, (double)2.2f));
+            }
+            out.albedo[at] = make_float4(albedo.x, albedo.y, albedo.z, 0.f);
+        }
+    }
+    if (channels & CRT_AOV_BIT_HIT) out.hit[at] = make_float4(t, bu, bv, __int_as_float(tri_out));
+    if (channels & CRT_AOV_BIT_IDS)
+        out.ids[at] = make_int4(INST ? (int)inst_id : 0, INST ? (int)(inst_word & 0x7fffffffu) : 0, mtl,
+                                (cos_incident > 0 ? 1 : 0) | (emissive ? 2 : 0) | (textured ? 4 : 0));
+    if (channels & CRT_AOV_BIT_NORMAL) out.normal[at] = make_float4(n.x, n.y, n.z, 0.f);
+    if (channels & CRT_AOV_BIT_EMISSION)
+        out.emission[at] = emissive ? make_float4(m_emission.x, m_emission.y, m_emission.z, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// A flat scene's feature buffers: one lane per local pixel in the packed storage order (a wave = an 8 x 8 pixel block), the frame's primary
+// ray (primary_ray), k_trace's plain per-lane closest-hit walk, the attribute fetch, one 16-byte store per requested channel at the linear
+// pixel index.  A miss writes nothing: k_aov_fill ran before.
+__global__ void __launch_bounds__(64) k_aov(AovArgs a) {
+    extern __shared__ uint2 s_lds[];     // this wave's traversal stack [level][lane]
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t e = blockIdx.x * 64u + lane;
+    uint32_t px = 0, py = 0;
+    if (!(e < a.f.n_local_pixels && pixel_of(a.f, e, px, py))) return;
+    float sx, sy;
+    vec3 o, d;
+    primary_ray(a.f, px, py, a.f.rv, sx, sy, o, d);
+    HitState hit;
+    uint32_t nn = 0, nt = 0, wn = 0, wt = 0;
+    traverse<false, false>(a.nodes, a.tris, o, d, CRT_INF, s_lds + lane, (int)a.stack_entries, a.overflow, hit, nn, nt, wn, wt);
+    if (hit.tri < 0) return;
+    const float4 tb = a.tris[(size_t)CRT_TRI_ROWS * (size_t)hit.tri + 1], tc = a.tris[(size_t)CRT_TRI_ROWS * (size_t)hit.tri + 2];
+    aov_store<false>(a, a.out, a.channels, (size_t)py * a.f.width + px, d, hit.t, hit.u, hit.v, hit.id, __float_as_int(tb.w), __float_as_int(tc.w), 0u, 0u, 0u, 0u);
+}
+
+// An instanced scene's feature buffers, behind k_raygen and k_closest_instances_queue: one lane per entry of the primary rays' queue (payload =
+// local pixel), hits and hit instances parallel to it; the triangle, its normals and texcoords through the hit instance's mesh, the material
+// plus the instance's offset, the normal through the instance's world_to_object, as k_segment<INST> has them.
+__global__ void __launch_bounds__(256) k_aov_instanced(InstAovArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t g = i / a.sub_capacity, e = i - g * a.sub_capacity;        // uniform over the workgroup: 256 divides sub_capacity
+    if (g >= 8u) return;
+    const uint32_t cnt = a.count_in[g * CRT_COUNTER_STRIDE], n = cnt < a.sub_capacity ? cnt : a.sub_capacity;
+    if (e >= n) return;
+    const size_t q = (size_t)g * a.sub_capacity + e;
+    const float4 h = a.hits_in[q];
+    const int tri = __float_as_int(h.w);
+    if (tri < 0) return;
+    const float4 r1 = a.rays_in[2 * q + 1];
+    uint32_t px = 0, py = 0;
+    if (!pixel_of(a.f, __float_as_uint(r1.w), px, py)) return;
+    const uint32_t inst_id = (uint32_t)a.hit_inst[q];
+    const uint2 iw = a.inst_mesh[inst_id];
+    const uint4 mb = a.mesh_base[iw.x & 0x7fffffffu];
+    const int slot = (int)mb.x + tri;
+    const int mtl = a.triangles[3 * (size_t)slot].w + (int)iw.y;
+    aov_store<true>(a, a.out, a.channels, (size_t)py * a.f.width + px, V3(r1.x, r1.y, r1.z), h.x, h.y, h.z, tri, slot, mtl, inst_id, iw.x, mb.y, mb.z);
+}
+
 // ------------------------------------------------------------------ launchers --------
 
 // Timing events ride on the dispatch itself (hipExtLaunchKernelGGL): the events take the kernel's own start/stop
@@ -2216,6 +2337,15 @@ void launch_bin_scan(const BinScanArgs& a, hipStream_t stream) {
 }
 void launch_fold_paths(float* sum, const float4* l_final, const float4* contrib, uint32_t n_pixels, uint32_t n_samples, uint32_t first_slot_segment, hipStream_t stream) {
     hipLaunchKernelGGL(k_fold_paths, dim3((n_pixels + 255u) / 256u), dim3(256), 0, stream, sum, l_final, contrib, n_pixels, n_samples, first_slot_segment);
+}
+void launch_aov_fill(const AovOut& out, uint32_t channels, uint32_t n_pixels, hipStream_t stream) {
+    hipLaunchKernelGGL(k_aov_fill, dim3((n_pixels + 255u) / 256u), dim3(256), 0, stream, out, channels, n_pixels);
+}
+void launch_aov(const AovArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_aov, dim3((a.f.n_local_pixels + 63u) / 64u), dim3(64), (size_t)a.stack_entries * 64 * sizeof(uint2), stream, a);
+}
+void launch_aov_instanced(const InstAovArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_aov_instanced, dim3(8u * (a.sub_capacity / 256u)), dim3(256), 0, stream, a);
 }
 void launch_untile(const FrameArgs& f, const float* packed, float* linear, uint32_t grid, hipStream_t stream) {
     hipLaunchKernelGGL(k_untile, dim3(grid), dim3(256), 0, stream, f, packed, linear);

@@ -171,6 +171,30 @@ struct InstSegmentArgs : SegmentArgs {
                                    // current world table, n_lights = its total); null = a scene without: emission.w indexes `lights` as it is
 };
 
+// First-hit feature buffers (crt_render_aov): 16 bytes per pixel and channel, linear pixel order (py * width + px); a
+// channel that was not asked for is not touched and may be null.  The bits are include/crt.h's CRT_AOV_*.
+#define CRT_AOV_BIT_HIT 1u
+#define CRT_AOV_BIT_IDS 2u
+#define CRT_AOV_BIT_NORMAL 4u
+#define CRT_AOV_BIT_ALBEDO 8u
+#define CRT_AOV_BIT_EMISSION 16u
+struct AovOut {
+    float4* hit;               // crt_hit: (t, u, v, tri)
+    int4* ids;                 // (instance, mesh, material, flags)
+    float4* normal;
+    float4* albedo;
+    float4* emission;
+};
+// Argument blocks of their own behind the segment kernels' (the attribute fetch reads the same members by the same names; no existing kernel's block moves)
+struct AovArgs : SegmentArgs {          // k_aov: nodes, tris, triangles, normals, materials, texcoords, textures, f, stack_entries, overflow
+    uint32_t channels;
+    AovOut out;
+};
+struct InstAovArgs : InstSegmentArgs {  // k_aov_instanced: rays_in / count_in / hits_in / hit_inst = the primary rays' queue and its hits
+    uint32_t channels;
+    AovOut out;
+};
+
 struct RaygenArgs {            // k_raygen: segment 0's path-ray queue and path state of an instanced scene's frame
     FrameArgs f;
     float4* rays;              // 8 sub-queues of crt_ray, payload = path = local pixel
@@ -251,6 +275,11 @@ void set_launch_events(hipEvent_t start, hipEvent_t stop);
 void launch_bin_scan(const BinScanArgs& a, hipStream_t stream);
 // contrib may be null (no deferred segment); first_slot_segment = the segment slot 0 of the slot array belongs to
 void launch_fold_paths(float* sum, const float4* l_final, const float4* contrib, uint32_t n_pixels, uint32_t n_samples, uint32_t first_slot_segment, hipStream_t stream);
+// first-hit feature buffers: the miss values into every pixel of the requested channels, then the hits' values (flat: one lane per local
+// pixel, walks by itself; instanced: one lane per entry of the queue k_raygen and k_closest_instances_queue left)
+void launch_aov_fill(const AovOut& out, uint32_t channels, uint32_t n_pixels, hipStream_t stream);
+void launch_aov(const AovArgs& a, hipStream_t stream);
+void launch_aov_instanced(const InstAovArgs& a, hipStream_t stream);
 void launch_untile(const FrameArgs& f, const float* packed, float* linear, uint32_t grid, hipStream_t stream);
 // thr: the 256 thresholds of the pinned gamma (thr[j] = smallest x whose byte is >= j; thr[0] unused), in device memory
 void launch_resolve(const float* linear, uint32_t n_pixels, float inv_count, const float* thr, uint8_t* rgba, uint32_t grid, hipStream_t stream);

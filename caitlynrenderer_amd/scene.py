@@ -8,13 +8,19 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CRT_ABI_VERSION, CRT_BUILD_LBVH_ON_DEVICE, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_frame_stats,
+from ._lib import (CRT_ABI_VERSION, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_frame_stats,
                    crt_scene_desc, crt_tree_cost, lib)
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _cost_dict, _ptr
 
 RAY_DT = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("pad", "<u4")])
 HIT_DT = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("tri", "<i4")])
 STATS_DT = np.dtype([("nodes", "<u2"), ("tris", "<u2")])
+# crt_render_aov's channels (include/crt.h): 16 bytes per pixel each
+AOV_HIT, AOV_IDS, AOV_NORMAL, AOV_ALBEDO, AOV_EMISSION, AOV_ALL = CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_AOV_ALBEDO, CRT_AOV_EMISSION, CRT_AOV_ALL
+AOV_IDS_DT = np.dtype([("instance", "<i4"), ("mesh", "<i4"), ("material", "<i4"), ("flags", "<i4")])
+# what Scene.read_aov returns per channel: (dtype, trailing shape behind (height, width))
+AOV_DTYPES = {AOV_HIT: (HIT_DT, ()), AOV_IDS: (AOV_IDS_DT, ()), AOV_NORMAL: (np.dtype("<f4"), (4,)), AOV_ALBEDO: (np.dtype("<f4"), (4,)),
+              AOV_EMISSION: (np.dtype("<f4"), (4,))}
 
 
 class SceneData:
@@ -164,6 +170,27 @@ class Scene:
         p = C.c_void_p()
         check(lib().crt_resolve_device(self._h, float(np.float32(inv_count)), C.byref(p), 1 if sync else 0))
         return p.value
+
+    def render_aov(self, rx=0.0, ry=0.0, channels=AOV_ALL, sync=True):
+        """crt_render_aov: the first-hit feature buffers of the current view, through the primary rays of render_frame(rx, ry): `channels` is
+        a set of AOV_* bits.  Touches nothing a frame reads or reports."""
+        check(lib().crt_render_aov(self._h, float(np.float32(rx)), float(np.float32(ry)), int(channels), 1 if sync else 0))
+
+    def read_aov(self, channel):
+        """crt_read_aov: one channel as an (height, width) array, rows as read_sum has them: AOV_HIT as HIT_DT, AOV_IDS as AOV_IDS_DT
+        (instance, mesh, material, flags), the others float32 (height, width, 4)."""
+        if channel not in AOV_DTYPES:
+            raise ValueError("read_aov: channel is ONE of the AOV_* bits")
+        dt, tail = AOV_DTYPES[channel]
+        out = np.empty((self.height, self.width) + tail, dt)
+        check(lib().crt_read_aov(self._h, int(channel), _ptr(out), out.nbytes))
+        return out
+
+    def aov_device(self, channel):
+        """crt_aov_device: device pointer (int) of one channel's array, width * height * 16 bytes, valid until the scene is closed"""
+        ptr = C.c_void_p()
+        check(lib().crt_aov_device(self._h, int(channel), C.byref(ptr)))
+        return ptr.value
 
     def launch_times(self):
         """crt_get_launch_times: ms of every event-carrying launch since the spans were restarted (options timing / timing_accumulate)"""
@@ -344,5 +371,6 @@ class Scene:
             pass
 
 
-__all__ = ["Scene", "SceneData", "Camera", "Mesh", "SBVH", "CWBVH", "RAY_DT", "HIT_DT", "STATS_DT",
+__all__ = ["Scene", "SceneData", "Camera", "Mesh", "SBVH", "CWBVH", "RAY_DT", "HIT_DT", "STATS_DT", "AOV_IDS_DT", "AOV_DTYPES",
+           "AOV_HIT", "AOV_IDS", "AOV_NORMAL", "AOV_ALBEDO", "AOV_EMISSION", "AOV_ALL",
            "CRT_TRACE_CLOSEST", "CRT_TRACE_ANY", "CRT_BUILD_LBVH_ON_DEVICE"]

@@ -278,6 +278,35 @@ int crt_trace(crt_scene* s, const crt_ray* rays, size_t n, crt_hit* hits, int mo
  * on the scene's stream unless sync != 0. */
 int crt_trace_device(crt_scene* s, const void* d_rays, size_t n, void* d_hits, int mode, void* d_stats, int sync);
 
+/* First-hit feature buffers (AOVs) of the scene's current view, flat and instanced scenes (no reference counterpart): what
+ * a denoiser, a picker or an id mask needs of the pixel's FIRST hit, bit for bit what the integrator computes there.  The rays are the
+ * primary rays of crt_render_frame(s, rx, ry): the scene's camera, its "jitter" option, tmax 1e9f.  Every channel is 16 bytes per pixel
+ * in linear pixel order (py * width + px, rows as crt_read_sum has them), allocated by the first call that asks for it, freed with the scene:
+ *   HIT       crt_hit: (t, u, v, tri) of the closest hit (a flat scene: crt_trace's closest hit, lowest-id ties; an instanced scene: what
+ *             crt_instances_trace gives, tri = the id within the mesh; with option "instance_masks" 1 the masked walk with
+ *             "mask_primary", as segment 0 of a frame); a miss, or a pixel another shard rank owns: (1e9f, 0, 0, -1)
+ *   IDS       int32[4]: (instance, mesh, material, flags); (-1, -1, -1, 0).  A flat scene reports instance = mesh = 0.  material: the index
+ *             the integrator reads, triangles[..].v[3] plus the instance's material_offset.  flags: bit 0 the normal was flipped (dot(d, n)
+ *             > 0 before the flip), bit 1 the material is emissive (emission.w != -1), bit 2 the albedo came from a texture
+ *   NORMAL    float[4]: (n, 0), the shading normal as the integrator holds it after the face-forward flip: the flat triangle normal when
+ *             vn.w == 0, else the interpolated one; through a non-identity instance by item 4 of crt_scene_create_instanced; NOT
+ *             normalised (it keeps the file's length); zeros
+ *   ALBEDO    float[4]: (rgb, 0), what the Lambert branch multiplies into the throughput: materials[4 m].xyz, or the filtered texture at
+ *             the interpolated texcoord through pow(c, 2.2f) where the frame would use the texture; also for emissive materials; zeros
+ *   EMISSION  float[4]: (materials[4 m + 1].xyz, 0) of an emissive material, else zeros
+ * crt_render_aov is enqueued on the scene's stream behind any *_async frames (sync = 0 returns at once; crt_sync, crt_read_aov and later
+ * frames are ordered behind it) and renders the channels named; a channel not named keeps its contents.  It leaves the sum, the frame
+ * count, crt_get_frame_stats, the launch times and every frame's path and RNG state as they are.  An instanced scene reads its handle's
+ * live arrays at enqueue, as a frame does: a set / refit / update_meshes before the call is seen, without crt_reset.  crt_set_shard works
+ * (a rank fills its own pixels); option "streams" is ignored.  CRT_ERR_INVALID, nothing written: channels 0 or with other bits; option
+ * "accel" not 0; a scene on several devices (crt_set_devices); crt_read_aov / crt_aov_device with a channel never rendered, more than
+ * one bit, or n_bytes other than width*height*16.  crt_aov_device waits for the stream and leaves the array on the device; the pointer
+ * stays valid until the scene is destroyed. */
+enum { CRT_AOV_HIT = 1, CRT_AOV_IDS = 2, CRT_AOV_NORMAL = 4, CRT_AOV_ALBEDO = 8, CRT_AOV_EMISSION = 16, CRT_AOV_ALL = 31 };
+int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync);
+int crt_read_aov(crt_scene* s, uint32_t channel, void* dst, size_t n_bytes);
+int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr);
+
 /* Animated geometry (no reference counterpart: the reference uploads its scene once, Scene.h:1000-1062; DXR / OptiX call this an
  * update build).  New positions for the scene's vertices; triangles, materials, textures and the tree topology are unchanged.
  * n_vertices must equal the count given at create; normals (n_normals == create's) and lights (n_lights == create's) may be NULL =
