@@ -349,6 +349,10 @@ struct crt_scene {
     static size_t bins_words() { return (size_t)17 * 5 * CRT_RAY_BINS + (size_t)17 * (CRT_RAY_BINS + 1u) + 17u * 32u; }
     uint32_t last_build = 1;                 // option "last_build": a one-pass launch that is the path's last segment runs the build compiled as one (k_segment<LAST>)
     int last_launch_last = 0;                // crt_debug_launch_info: bit 2 of the build word
+    uint32_t lean_build = 1;                 // option "lean_build": such a launch runs that build's LEAN form (k_segment<LAST,LEAN>) where launch_segment finds what the form has compiled in
+    bool tree_validated = false;             // the CWBVH passed crt_scene_create's host validator (validate_cwbvh), whose depth sized the stack: the LEAN form's bare pushes rest on it.
+                                             // A tree built or rebuilt on the device never went through it and keeps the checked pushes
+    int last_launch_lean = 0;                // crt_debug_launch_info: bit 3 of the build word
     uint32_t debug_fail_batch_alloc = 0;     // test hook (option of the same name): the next growth of the batch buffers fails before it allocates
     uint32_t batch_cap = 1;                  // samples the path state, the ray queues and d_lfinal are sized for (1 until crt_render_frames needs more)
     uint32_t samples_in_stats = 1;           // samples per pixel of the launch the pending stats describe (crt_render_frames batches)
@@ -1153,6 +1157,7 @@ static int scene_create_impl(const crt_scene_desc* d, crt_scene** out) {
     // root = 1) has no inner children to descend to: depth8 - 1 entries hold any walk.  One row of the wave's LDS region is 512 bytes and LDS is
     // handed out in 1,280-byte units: at depth 11 (8 M triangles) the row saved is the difference between 21 and 24 waves per CU.
     s->stack_entries = std::min<uint32_t>(CRT_STACK_ENTRIES, std::max<uint32_t>(2, depth8 - 1u));
+    s->tree_validated = true;                     // validate_cwbvh above walked every node and reported this depth
     s->info.n_nodes8 = n_nodes8; s->info.n_tris8 = n_tris8; s->info.n_bvh2_nodes = d->n_bvh; s->info.max_depth8 = depth8;
 
     // pre-gathered intersection records in CWBVH triangle order: (v0|orig id) (e1|slot) (e2|material).
@@ -1519,6 +1524,7 @@ int crt_set_option(crt_scene* s, const char* name, int value) {
     }
     else if (!std::strcmp(name, "ray_bins")) s->ray_bins = (uint32_t)std::min(5, std::max(0, value));
     else if (!std::strcmp(name, "last_build")) s->last_build = value ? 1u : 0u;
+    else if (!std::strcmp(name, "lean_build")) s->lean_build = value ? 1u : 0u;
     else if (!std::strcmp(name, "debug_fail_batch_alloc")) {
         // one injected failure, on ONE device: 1 = this scene's own, k >= 2 = its (k - 1)-th peer (streams / crt_set_devices); 0 disarms all
         if (value >= 2 && (size_t)(value - 2) < s->peers.size()) s->peers[(size_t)(value - 2)]->debug_fail_batch_alloc = 1u;
@@ -1713,7 +1719,7 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
     s->stats_pending = true;
     s->stats_from_frame = true;
     s->samples_in_stats = 1;
-    s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0; s->last_launch_last = 0;
+    s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0; s->last_launch_last = 0; s->last_launch_lean = 0;
     return CRT_OK;
 }
 
@@ -1883,8 +1889,8 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         // (P * n_samples spread evenly over the 8 groups is fewer chunks than that when the units do not divide by 8.)
         uint32_t grid = s->trace_grid(P, sa.wide_first ? 6 : 5);
         if (b > 0 && batched_paths) grid *= n_samples;
-        const int build = crt::launch_segment(sa, b == 0, pretraced, inplace, bvh2, s->special_materials, s->count_visits, grid, s->waves_per_workgroup, s->stream);
-        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; s->last_launch_last = (build >> 2) & 1; }
+        const int build = crt::launch_segment(sa, b == 0, pretraced, inplace, bvh2, s->special_materials, s->count_visits, s->lean_build != 0u && s->tree_validated, grid, s->waves_per_workgroup, s->stream);
+        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; s->last_launch_last = (build >> 2) & 1; s->last_launch_lean = (build >> 3) & 1; }
         if (sa.bins_out.count) {
             // fill counts -> the next launch's index space and ray count, and the next frame's capacities (the other parity)
             crt::BinScanArgs ba{};
@@ -2399,7 +2405,7 @@ static int replicate_scene(const crt_scene* src, int device, crt_scene** out) {
     r->trace_occupancy = src->trace_occupancy; r->oversubscribe = src->oversubscribe; r->waves_per_workgroup = src->waves_per_workgroup;
     r->lanes_per_ray = src->lanes_per_ray; r->bounce_refill = src->bounce_refill; r->refill_pool = src->refill_pool; r->shadow_pool = src->shadow_pool; r->shadow_refill_min = src->shadow_refill_min; r->shadow_waves = src->shadow_waves; r->persistent = src->persistent; r->sort_shadow = src->sort_shadow;
     r->wave_samples = src->wave_samples; r->wide_first = src->wide_first; r->adaptive_tiles = src->adaptive_tiles; r->timing = src->timing;
-    r->ray_bins = src->ray_bins; r->rows_padded = src->rows_padded; r->last_build = src->last_build;
+    r->ray_bins = src->ray_bins; r->rows_padded = src->rows_padded; r->last_build = src->last_build; r->lean_build = src->lean_build; r->tree_validated = src->tree_validated;
     for (int k = 0; k < 3; ++k) { r->bounds_lo[k] = src->bounds_lo[k]; r->bounds_hi[k] = src->bounds_hi[k]; }
     r->scene_bufs = src->scene_bufs;
     r->shares_scene = device == src->device;
@@ -2612,7 +2618,7 @@ int crt_debug_step_hist(crt_scene* s, unsigned long long* hist) {
 
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]) {
     if (!s || !info) return fail(CRT_ERR_INVALID, "crt_debug_launch_info: null argument");
-    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1) | (s->last_launch_last << 2); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
+    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1) | (s->last_launch_last << 2) | (s->last_launch_lean << 3); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
     return CRT_OK;
 }
 
@@ -3194,6 +3200,7 @@ static int rebuild_impl(crt_scene* s, const float* h_verts, const float* d_user,
     std::swap(s->d_triangles, fresh.triangles); std::swap(s->d_tris2, fresh.tris2); std::swap(s->d_planes, fresh.planes);
     s->bvh2_stack = keep_bvh2 ? depth2 + 2u : 0u;
     s->stack_entries = std::min<uint32_t>(CRT_STACK_ENTRIES, std::max<uint32_t>(2, depth8 - 1u));
+    s->tree_validated = false;                    // the fresh tree is the device builders' own: the checked pushes from here on
     s->info.n_nodes8 = n8; s->info.n_tris8 = n; s->info.n_bvh2_nodes = n2; s->info.max_depth8 = depth8; s->info.bvh2_depth = depth2;
     s->info.build_lbvh_device_ms = lbvh_ms; s->info.build_convert_device_ms = conv_ms;
     set_buf_bytes(s, &s->d_nodes, (size_t)n8 * CRT_NODE_ROWS * 16);
@@ -3219,7 +3226,7 @@ static int rebuild_impl(crt_scene* s, const float* h_verts, const float* d_user,
         p->d_bvh2 = s->d_bvh2; p->d_nodes = s->d_nodes; p->d_tris = s->d_tris; p->d_triangles = s->d_triangles; p->d_tris2 = s->d_tris2;
         p->d_planes = p->d_planes ? s->d_planes : nullptr;
         const bool peer_planes = p->d_planes != nullptr;
-        p->info = s->info; p->bvh2_stack = s->bvh2_stack; p->stack_entries = s->stack_entries;
+        p->info = s->info; p->bvh2_stack = s->bvh2_stack; p->stack_entries = s->stack_entries; p->tree_validated = s->tree_validated;
         p->scene_bufs = s->scene_bufs;
         if (!peer_planes)                         // not borrowed yet: ensure_planes notes it when it is
             p->scene_bufs.erase(std::remove_if(p->scene_bufs.begin(), p->scene_bufs.end(), [&](const std::pair<size_t, size_t>& b) {

@@ -398,7 +398,8 @@ __device__ __forceinline__ bool group_tri_step(const float4* __restrict__ tris, 
 // The group phase of walk_batch (and of the first segment's shadow walk): `busy` lanes hand their rays — at most 64 >> GROUP_KL of them —
 // to groups of K adjacent lanes, which finish them; on return out.t / out.tri of a lane whose ray moved hold its result (closest hits: the
 // (u, v, id) record is in the lane's own column slots as always).  Every lane of the wave calls this together.
-template <bool ANY, bool STATS, bool UNIFORM_O>
+// LEAN: see walk_batch.
+template <bool ANY, bool STATS, bool UNIFORM_O, bool LEAN = false>
 __device__ __forceinline__ void group_phase(const uint4* __restrict__ nodes, const float4* __restrict__ tris, uint2* base, int stack_entries, uint32_t* overflow,
                                             bool busy, vec3 o_lane, vec3 d, float best_t, int best_tri, uint2 cur, uint2 tg, int sp, uint32_t tri_min,
                                             HitState& out, uint32_t& n_nodes, uint32_t& n_tris, uint32_t& w_nodes, uint32_t& w_tris, vec3 o_uniform) {
@@ -454,7 +455,8 @@ __device__ __forceinline__ void group_phase(const uint4* __restrict__ nodes, con
                     const uint32_t nbase = cur.x;
                     cur.y &= ~(1u << off);
                     if (cur.y & 0xff000000u) {
-                        if (sp < stack_entries) { if (sub == 0u) stk[sp * 64] = cur; ++sp; } else if (sub == 0u) atomicAdd(overflow, 1u);
+                        if (LEAN) { if (sub == 0u) stk[sp * 64] = cur; ++sp; }
+                        else if (sp < stack_entries) { if (sub == 0u) stk[sp * 64] = cur; ++sp; } else if (sub == 0u) atomicAdd(overflow, 1u);
                     }
                     const uint32_t slot = (uint32_t)(off - 24) ^ (oct4 & 0xffu);
                     const uint32_t nidx = nbase + (uint32_t)__builtin_popcount(hits_imask & ~(0xffffffffu << slot));
@@ -497,7 +499,9 @@ __device__ __forceinline__ void group_phase(const uint4* __restrict__ nodes, con
 // Two loops: phase 1 is the lock-step voting loop (walk_pool's, without the refill), one ray per lane, and ends when at most 64 >> GROUP_KL rays are
 // left; those are regrouped and finished by phase 2, which knows nothing but groups.  (One loop that carried the group size as a variable
 // cost the one-lane phase 5 %: a guard on every stack write, a switch in every step.)
-template <bool ANY, bool STATS, bool UNIFORM_O, bool UNI = false>
+// LEAN (k_segment<LEAN> only): a push is the bare write — the caller vouches that the tree passed the create-time validator, whose depth
+// the stack was sized from, so no push can overflow — and tri_min / max_kl arrive as compile-time constants.
+template <bool ANY, bool STATS, bool UNIFORM_O, bool UNI = false, bool LEAN = false>
 __device__ __forceinline__ void walk_batch(const uint4* __restrict__ nodes, const float4* __restrict__ tris, uint2* base, int stack_entries, uint32_t* overflow,
                                            bool has_ray, vec3 o_in, vec3 d, float tmax_in, uint32_t tri_min, uint32_t max_kl, HitState& out,
                                            uint32_t& n_nodes, uint32_t& n_tris, uint32_t& w_nodes, uint32_t& w_tris, vec3 o_uniform = V3(0.f, 0.f, 0.f),
@@ -543,7 +547,10 @@ __device__ __forceinline__ void walk_batch(const uint4* __restrict__ nodes, cons
                     const int off = 31 - __builtin_clz(hits_imask);
                     const uint32_t nbase = cur.x;
                     cur.y &= ~(1u << off);
-                    if (cur.y & 0xff000000u) { if (sp < stack_entries) { stk[sp * 64] = cur; ++sp; } else atomicAdd(overflow, 1u); }
+                    if (cur.y & 0xff000000u) {
+                        if (LEAN) { stk[sp * 64] = cur; ++sp; }
+                        else if (sp < stack_entries) { stk[sp * 64] = cur; ++sp; } else atomicAdd(overflow, 1u);
+                    }
                     const uint32_t slot = (uint32_t)(off - 24) ^ (oct4 & 0xffu);
                     const uint32_t nidx = nbase + (uint32_t)__builtin_popcount(hits_imask & ~(0xffffffffu << slot));
                     if (STATS) { ++n_nodes; count_wave_step(w_nodes); hist_node_step(ANY, nidx, oct4); }
@@ -602,7 +609,7 @@ __device__ __forceinline__ void walk_batch(const uint4* __restrict__ nodes, cons
     }
     out.t = best_t; out.tri = best_tri;
     if (regroup)
-        group_phase<ANY, STATS, UNIFORM_O>(nodes, tris, base, stack_entries, overflow, busy, o_lane, d, best_t, best_tri, cur, tg, sp, tri_min, out,
+        group_phase<ANY, STATS, UNIFORM_O, LEAN>(nodes, tris, base, stack_entries, overflow, busy, o_lane, d, best_t, best_tri, cur, tg, sp, tri_min, out,
                                            n_nodes, n_tris, w_nodes, w_tris, o_uniform);
     out.u = 0.f; out.v = 0.f; out.id = -1;
     if (!ANY && out.tri >= 0) {
@@ -806,7 +813,8 @@ __device__ __forceinline__ void walk_pool(const uint4* __restrict__ nodes, const
 // Any-hit walk of one batch: the plain per-lane loop of traverse<true> (each lane tests its leaf's triangles right after the node that found
 // them — the fastest form for the coherent shadow rays of primary hits) until at most 64 >> GROUP_KL rays are left, then the group phase.
 // Every lane of the wave calls this together; returns whether this lane's ray is occluded.
-template <bool STATS, bool UNI = false>
+// LEAN: see walk_batch.
+template <bool STATS, bool UNI = false, bool LEAN = false>
 __device__ __forceinline__ bool traverse_any_then_groups(const uint4* __restrict__ nodes, const float4* __restrict__ tris, uint2* base, int stack_entries,
                                                          uint32_t* overflow, bool has_ray, vec3 o, vec3 d, float tmax, uint32_t tri_min, uint32_t max_kl,
                                                          uint32_t& n_nodes, uint32_t& n_tris, uint32_t& w_nodes, uint32_t& w_tris, uint32_t* n_uni = nullptr,
@@ -837,7 +845,10 @@ __device__ __forceinline__ bool traverse_any_then_groups(const uint4* __restrict
                 const int off = 31 - __builtin_clz(hits_imask);
                 const uint32_t nbase = cur.x;
                 cur.y &= ~(1u << off);
-                if (cur.y & 0xff000000u) { if (sp < stack_entries) { stk[sp * 64] = cur; ++sp; } else atomicAdd(overflow, 1u); }
+                if (cur.y & 0xff000000u) {
+                    if (LEAN) { stk[sp * 64] = cur; ++sp; }
+                    else if (sp < stack_entries) { stk[sp * 64] = cur; ++sp; } else atomicAdd(overflow, 1u);
+                }
                 const uint32_t slot = (uint32_t)(off - 24) ^ (oct4 & 0xffu);
                 const uint32_t rel = __builtin_popcount(hits_imask & ~(0xffffffffu << slot));
                 if (STATS) { ++n_nodes; count_wave_step(w_nodes); hist_node_step(true, nbase + rel, oct4); }
@@ -884,8 +895,8 @@ __device__ __forceinline__ bool traverse_any_then_groups(const uint4* __restrict
     HitState out;
     out.t = tmax; out.tri = hit_tri;
     if (regroup)
-        group_phase<true, STATS, false>(nodes, tris, base, stack_entries, overflow, busy, o, d, tmax, -1, cur, tg, sp, tri_min, out, n_nodes, n_tris, w_nodes, w_tris,
-                                        V3(0.f, 0.f, 0.f));
+        group_phase<true, STATS, false, LEAN>(nodes, tris, base, stack_entries, overflow, busy, o, d, tmax, -1, cur, tg, sp, tri_min, out, n_nodes, n_tris, w_nodes, w_tris,
+                                              V3(0.f, 0.f, 0.f));
     return out.tri >= 0;
 }
 
@@ -1326,10 +1337,17 @@ __device__ __forceinline__ KArgs kernarg_here() {
 // LAST (the ONE builds only; DESIGN.md section 5, "the last segment at compile time"): the launch is a path's last segment, known when the
 // kernel is compiled — no bounce sampling, no next-ray queue, no path state.  The other builds skip those at run time through last_segment
 // and still carry their code, registers, zero-initialisations and join copies (measured: profiles/r06_experiments.md section 1).
+// LEAN (the timed LAST builds only; DESIGN.md section 5, "the lean build"; option lean_build): what launch_segment knows about the launch
+// is compiled in — the tree passed the create-time validator (bare stack pushes), the walks' vote ratio and group size are the defaults
+// (CRT_LEAN_TRI_MIN, CRT_LEAN_LANES_LOG2), the launch has no tile_cost — and the RNG's sine is the form of rt_math.hpp with the same bits
+// from fewer double-precision-rate instructions.  Any other launch runs the build without it.  (The two l_final tests stay run-time
+// ones: compiled out together with the bare pushes they cost the build its seventh wave, 79 VGPRs; and the sample select stays as it
+// is: the compiler drops its upper four compares by itself, lane >> 4 being below 4 — profiles/r07_experiments.md.)
 template <bool FIRST, bool STATS, bool TEX, bool PRETRACED, bool INPLACE, bool BVH2 = false, bool MAT = false, bool BATCH = false, bool WIDE = false, bool ONE = false,
-          bool INST = false, bool LAST = false>
+          bool INST = false, bool LAST = false, bool LEAN = false>
 __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_FIRST : (BATCH || STATS) ? CRT_SEG_OCC_BATCH : (!FIRST && !INPLACE && !PRETRACED) ? CRT_SEG_OCC_DEFERRED : CRT_SEG_OCC)) k_segment(std::conditional_t<INST, InstSegmentArgs, SegmentArgs> a) {
     static_assert(!LAST || (FIRST && ONE && INPLACE && !BVH2), "LAST is a form of the one-pass first-segment builds");
+    static_assert(!LEAN || (LAST && !STATS), "LEAN is a form of the timed LAST builds");
     extern __shared__ uint2 s_lds[];     // traversal stacks [wave][level][lane]
     // Uniform node steps are compiled into every first-segment kernel.  (In the single-sample kernel they lost while the uniform step still
     // converted bytes and the loops carried their flags — 8 x 8-pixel waves agree less than the 4 x 4-pixel waves of a batched launch, and the
@@ -1398,7 +1416,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                 cost_tile = f.tile_order[slot];
                 e = cost_tile * tile_px + (e - slot * tile_px);
             }
-            if (a.tile_cost) cost_t0 = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_readcyclecounter());
+            if (!LEAN && a.tile_cost) cost_t0 = __builtin_amdgcn_readfirstlane((uint32_t)__builtin_readcyclecounter());
             // lane 0 reports the batch's cost for its tile (a batch never straddles two tiles): its tile and whether it has a pixel
             // at all, as wave-uniform scalars — a per-lane copy would sit in VGPRs across every loop of the kernel
             cost_tile = __builtin_amdgcn_readlane(cost_tile, 0);
@@ -1440,8 +1458,8 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
             const float W = (float)here(f.width), H = (float)here(f.height);
             float jx = 0.f, jy = 0.f;
             if (f.jitter) {
-                const float r1 = 2.0f * shader_rand(sx, sy, rv);
-                const float r2 = 2.0f * shader_rand(sx, sy, rv);
+                const float r1 = 2.0f * shader_rand<LEAN>(sx, sy, rv);
+                const float r2 = 2.0f * shader_rand<LEAN>(sx, sy, rv);
                 jx = r1 < 1.0f ? sqrt_ieee(r1) - 1.0f : 1.0f - sqrt_ieee(2.0f - r1);
                 jy = r2 < 1.0f ? sqrt_ieee(r2) - 1.0f : 1.0f - sqrt_ieee(2.0f - r2);
                 jx = __fdiv_rn(jx, W * 0.5f);
@@ -1487,7 +1505,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
             // ray say so and finish immediately with no visits (1 M triangles: 0.397 -> 0.310 ms)
             // (primary rays all start at the camera: the origin of the first segment's walk stays in scalar registers, UNIFORM_O)
             // the last rays of the batch get eight lanes each (a.lanes_log2 = 0: never — then this is the lock-step voting loop alone)
-            walk_batch<false, STATS, FIRST, UNI_K>(a.nodes, a.tris, stk - lane, (int)a.stack_entries, a.overflow, active, o, d, CRT_INF, a.tri_min, a.lanes_log2, hit,
+            walk_batch<false, STATS, FIRST, UNI_K, LEAN>(a.nodes, a.tris, stk - lane, (int)a.stack_entries, a.overflow, active, o, d, CRT_INF, LEAN ? CRT_LEAN_TRI_MIN : a.tri_min, LEAN ? CRT_LEAN_LANES_LOG2 : a.lanes_log2, hit,
                                                    nn, nt, wn, wt, V3(f.cam_pos[0], f.cam_pos[1], f.cam_pos[2]), &nu, a.planes);
         }
 
@@ -1654,14 +1672,14 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
                     if (disney) { ns = normalize(n); dm = disney_params(albedo, m_specular.x, m_specular.y); }
                     if (m_specular.w == 0.0f) {
                         if (ka->n_lights <= 0) {
-                            shader_rand(sx, sy, rv); shader_rand(sx, sy, rv); shader_rand(sx, sy, rv);
+                            shader_rand<LEAN>(sx, sy, rv); shader_rand<LEAN>(sx, sy, rv); shader_rand<LEAN>(sx, sy, rv);
                         } else {
-                            int li = (int)(shader_rand(sx, sy, rv) * (float)(int)here((uint32_t)ka->n_lights));
+                            int li = (int)(shader_rand<LEAN>(sx, sy, rv) * (float)(int)here((uint32_t)ka->n_lights));
                             if (li > ka->n_lights - 1) li = ka->n_lights - 1;
                             const float* Lt = ka->lights + 18 * (size_t)li;
-                            const float sq = sqrt_ieee(shader_rand(sx, sy, rv));    // :843-855
+                            const float sq = sqrt_ieee(shader_rand<LEAN>(sx, sy, rv));    // :843-855
                             const float b0 = 1.0f - sq;
-                            const float b1 = shader_rand(sx, sy, rv) * sq;
+                            const float b1 = shader_rand<LEAN>(sx, sy, rv) * sq;
                             const vec3 lp = (V3(Lt[0], Lt[1], Lt[2]) + V3(Lt[3], Lt[4], Lt[5]) * b0) + V3(Lt[6], Lt[7], Lt[8]) * b1;
                             vec3 ldir = lp - hit_point;
                             const float len = length(ldir);
@@ -1766,8 +1784,8 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
             const bool lanes_walks = !BVH2 && (ONE || (a.lanes_log2 != 0u && a.tri_min != 0u));
             if (FIRST && lanes_walks) {
                 // the first segment's shadow rays: the plain loop, then groups for the last rays of the wave
-                const bool occluded = traverse_any_then_groups<STATS, UNI_K>(a.nodes, a.tris, stk - lane, (int)a.stack_entries, a.overflow, pending, V3(sh0.x, sh0.y, sh0.z),
-                                                                      V3(sh1.x, sh1.y, sh1.z), sh0.w, a.tri_min, a.lanes_log2, nn_any, nt_any, wn_any, wt_any, &nu_any, a.planes);
+                const bool occluded = traverse_any_then_groups<STATS, UNI_K, LEAN>(a.nodes, a.tris, stk - lane, (int)a.stack_entries, a.overflow, pending, V3(sh0.x, sh0.y, sh0.z),
+                                                                      V3(sh1.x, sh1.y, sh1.z), sh0.w, LEAN ? CRT_LEAN_TRI_MIN : a.tri_min, LEAN ? CRT_LEAN_LANES_LOG2 : a.lanes_log2, nn_any, nt_any, wn_any, wt_any, &nu_any, a.planes);
                 if (pending && !occluded) L = L + V3(sh2.x, sh2.y, sh2.z);
             } else if (lanes_walks) {
                 // lanes per ray grow as the wave's shadow rays drain (walk_batch)
@@ -1847,7 +1865,7 @@ __global__ void __launch_bounds__(CRT_TRACE_BLOCK, ((WIDE || ONE) ? CRT_SEG_OCC_
             __syncthreads();                                       // persistent grids: the next pass reuses the strip
         }
         }   // samples
-        if (FIRST && a.tile_cost && lane == 0u && cost_valid)
+        if (FIRST && !LEAN && a.tile_cost && lane == 0u && cost_valid)
             atomicAdd(a.tile_cost + cost_tile, (uint32_t)__builtin_readcyclecounter() - cost_t0);     // a wave lives far less than 2^32 cycles
     }
     if (STATS && !PRETRACED) flush_visit_totals(a.visit_totals, nn, nt, wn, wt);
@@ -2226,14 +2244,19 @@ void launch_trace_bvh2(const Bvh2Args& a, int any, bool stats, uint32_t grid, ui
 //               k_segment<FIRST, STATS, TEX, PRETRACED, INPLACE, BVH2, MAT, BATCH, WIDE, ONE>
 #define CRT_K(F, S, T, P, Y, B2, M, BA, WI, ON) k_segment<F, S, T, P, Y, B2, M, BA, WI, ON>
 // a one-pass first-segment build <FIRST, S, T, INPLACE, M, BATCH, WI, ONE>, in its LAST form when the launch is the path's last segment
+// and that in its LEAN form when the launch is what the form has compiled in (never a counting build); returns bits 2 (LAST) and 3 (LEAN)
 template <bool S, bool T, bool M, bool WI>
-static void launch_one_pass(bool last, dim3 g, dim3 b, size_t lds, hipStream_t stream, const SegmentArgs& a) {
+static int launch_one_pass(bool last, bool lean, dim3 g, dim3 b, size_t lds, hipStream_t stream, const SegmentArgs& a) {
+    if constexpr (!S) {
+        if (last && lean) { launch(k_segment<true, S, T, false, true, false, M, true, WI, true, false, true, true>, g, b, lds, stream, a); return 4 | 8; }
+    }
     if (last) launch(k_segment<true, S, T, false, true, false, M, true, WI, true, false, true>, g, b, lds, stream, a);
     else      launch(k_segment<true, S, T, false, true, false, M, true, WI, true, false, false>, g, b, lds, stream, a);
+    return last ? 4 : 0;
 }
 // returns bit 0: the launch ran the 6-waves-per-SIMD (WIDE) build of the first-segment kernel; bit 1: a one-pass (ONE) build; bit 2: that
-// build's LAST form (crt_debug_launch_info)
-int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplace, bool bvh2, bool mat, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream) {
+// build's LAST form; bit 3: that form's LEAN form (crt_debug_launch_info)
+int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplace, bool bvh2, bool mat, bool stats, bool lean_ok, uint32_t grid, uint32_t waves, hipStream_t stream) {
     const bool tex = a.textures != nullptr;
     // one LDS region serves the CWBVH stack (8 B per level and lane) or the BVH2 stack (4 B)
     const size_t per_wave = std::max(stack_bytes(a.stack_entries), bvh2 ? (size_t)a.stack_entries2 * 64 * sizeof(int) : (size_t)0);
@@ -2256,13 +2279,15 @@ int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplac
         const size_t ll = side_by_side ? lds4 : in_lanes ? per_wave : lds;
         const bool one_pass = in_lanes && a.n_samples == 4u && a.tri_min != 0u && a.lanes_log2 != 0u;      // four samples in the lanes of a wave: the builds without a sample loop
         const bool last = a.last_segment != 0u && a.last_build != 0u;      // (option last_build 0: the builds that find out at run time)
+        // the LEAN form has these compiled in (lean_ok: option lean_build, and the tree passed crt_scene_create's validator)
+        const bool lean = lean_ok && a.tri_min == CRT_LEAN_TRI_MIN && a.lanes_log2 == CRT_LEAN_LANES_LOG2 && a.tile_cost == nullptr;
         // counting in the TIMED form (option count_visits 2): what the uniform node steps see depends on which rays share a wave
-        if (stats && one_pass) { launch_one_pass<true, true, true, false>(last, gg, bb, ll, stream, v); return 2 | (last ? 4 : 0); }
-        if (feat == 2 && one_pass)      { launch_one_pass<false, true, true, false>(last, gg, bb, ll, stream, v); return 2 | (last ? 4 : 0); }
-        else if (feat == 1 && one_pass) { launch_one_pass<false, false, true, false>(last, gg, bb, ll, stream, v); return 2 | (last ? 4 : 0); }
+        if (stats && one_pass) return 2 | launch_one_pass<true, true, true, false>(last, false, gg, bb, ll, stream, v);
+        if (feat == 2 && one_pass)      return 2 | launch_one_pass<false, true, true, false>(last, lean, gg, bb, ll, stream, v);
+        else if (feat == 1 && one_pass) return 2 | launch_one_pass<false, false, true, false>(last, lean, gg, bb, ll, stream, v);
         else if (feat == 2) launch(CRT_K(true, false, true, false, true, false, true, true, false, false), gg, bb, ll, stream, v);
         else if (feat == 1) launch(CRT_K(true, false, false, false, true, false, true, true, false, false), gg, bb, ll, stream, v);
-        else if (v.wide_first && one_pass) { launch_one_pass<false, false, false, true>(last, gg, bb, ll, stream, v); return 3 | (last ? 4 : 0); }
+        else if (v.wide_first && one_pass) return 3 | launch_one_pass<false, false, false, true>(last, lean, gg, bb, ll, stream, v);
         else if (v.wide_first && !side_by_side) { launch(CRT_K(true, false, false, false, true, false, false, true, true, false), gg, bb, ll, stream, v); return 1; }
         else                launch(CRT_K(true, false, false, false, true, false, false, true, false, false), gg, bb, ll, stream, v);
         return 0;

@@ -8,6 +8,10 @@ namespace crt {
 // Upper bound of traversal-stack entries per ray, kept in LDS (reference LOCAL_STACK_SIZE, cwbvh.fs:374).
 // crt_scene_create refuses a CWBVH deeper than this; the launch uses min(this, depth of the tree).
 #define CRT_STACK_ENTRIES 16
+// What the LEAN form of the one-pass last-segment builds (k_segment<LAST, LEAN>) has compiled in of the walks' parameters: the vote ratio
+// (option tri_min) and the group size (option lanes_per_ray 8) at their defaults; a launch with other values runs the build without them.
+#define CRT_LEAN_TRI_MIN 2u
+#define CRT_LEAN_LANES_LOG2 3u
 // Two more entries behind every lane's stack column: (u, v) and the original id of a closest-hit walk's best hit so far — written a few
 // times per ray, read once: LDS instead of three VGPRs across the traversal loop (rt_kernels.hip walk_pool, walk_batch; the id's
 // neighbour word is walk_batch's regroup scratch).
@@ -262,8 +266,10 @@ void launch_trace(const TraceArgs& a, int mode, bool stats, uint32_t grid, uint3
 void launch_trace_bvh2(const Bvh2Args& a, int any, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);
 // mat: the scene has Mirror / Disney materials (CWBVH segments only: not with bvh2)
 // inplace_shadow: the NEE shadow rays are walked inside the kernel; false = deferred to the frame's k_shadow_deferred launch
-// returns bit 0: the launch ran the 6-waves-per-SIMD (WIDE) build of the first-segment kernel, bit 1: a one-pass (ONE) build, bit 2: its LAST form
-int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplace_shadow, bool bvh2, bool mat, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);
+// returns bit 0: the launch ran the 6-waves-per-SIMD (WIDE) build of the first-segment kernel, bit 1: a one-pass (ONE) build, bit 2: its LAST form,
+// bit 3: that form's LEAN form (what it has compiled in: CRT_LEAN_TRI_MIN, CRT_LEAN_LANES_LOG2, no tile_cost).  lean_ok: the caller allows
+// that form (option lean_build) and vouches that the tree passed crt_scene_create's validator
+int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplace_shadow, bool bvh2, bool mat, bool stats, bool lean_ok, uint32_t grid, uint32_t waves, hipStream_t stream);
 // the frames of an instanced scene: ray generation, and the shade-only pass behind k_closest_instances_queue (shadow rays deferred)
 void launch_raygen(const RaygenArgs& a, hipStream_t stream);
 void launch_segment_instanced(const InstSegmentArgs& a, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);

@@ -118,29 +118,52 @@ __device__ __forceinline__ double cos_poly(double r) {
 }
 // (Round 3 timed a FREE sine in its place — bare v_sin_f32, parity broken on purpose — to see what a cheaper definition could buy at
 // most: 1 M triangles +2.7 %, 4 segments +0.8 %, Cornell +6.4 %.  Not worth redefining the oracle's RNG for.)
+// LEAN (the <LEAN> forms of k_segment only; DESIGN.md section 5, "the lean build"): the same value from fewer double-precision-rate
+// instructions around the unchanged reduction and polynomial.  The range test on the float: 1e9 is a float and widening is exact, so
+// fabsf(xf) < 1e9f is the same predicate.  The parity of k from (int)k: |k| = |rint(x / pi)| < 3.2e8 < 2^31, one v_cvt_i32_f64 instead of
+// the four-instruction expansion of (long long)k.  The sign after the rounding to float: round-to-nearest-even is symmetric, and flipping
+// the sign bit of the float is what -s is for every s the polynomial can give (zero included).  Every other kernel keeps the bodies below
+// instruction for instruction (tools/ubench/pinned_exhaustive.hip holds the two forms against each other).
+template <bool LEAN = false>
 __device__ __forceinline__ float pinned_sin(float xf) {
-    double x = (double)xf;
-    if (!(__builtin_fabs(x) < 1e9)) return 0.0f;
-    double k, r = reduce_pi(x, k);
-    double s = sin_poly(r);
-    if (((long long)k) & 1) s = -s;
-    return (float)s;
+    if constexpr (LEAN) {
+        if (!(__builtin_fabsf(xf) < 1e9f)) return 0.0f;
+        double k, r = reduce_pi((double)xf, k);
+        const float s = (float)sin_poly(r);
+        return __uint_as_float(__float_as_uint(s) ^ ((uint32_t)(int)k << 31));
+    } else {
+        double x = (double)xf;
+        if (!(__builtin_fabs(x) < 1e9)) return 0.0f;
+        double k, r = reduce_pi(x, k);
+        double s = sin_poly(r);
+        if (((long long)k) & 1) s = -s;
+        return (float)s;
+    }
 }
+template <bool LEAN = false>
 __device__ __forceinline__ float pinned_cos(float xf) {
-    double x = (double)xf;
-    if (!(__builtin_fabs(x) < 1e9)) return 1.0f;
-    double k, r = reduce_pi(x, k);
-    double c = cos_poly(r);
-    if (((long long)k) & 1) c = -c;
-    return (float)c;
+    if constexpr (LEAN) {
+        if (!(__builtin_fabsf(xf) < 1e9f)) return 1.0f;
+        double k, r = reduce_pi((double)xf, k);
+        const float c = (float)cos_poly(r);
+        return __uint_as_float(__float_as_uint(c) ^ ((uint32_t)(int)k << 31));
+    } else {
+        double x = (double)xf;
+        if (!(__builtin_fabs(x) < 1e9)) return 1.0f;
+        double k, r = reduce_pi(x, k);
+        double c = cos_poly(r);
+        if (((long long)k) & 1) c = -c;
+        return (float)c;
+    }
 }
 
 // Shader/path_trace.fs:38-42
+template <bool LEAN = false>
 __device__ __forceinline__ float shader_rand(float& sx, float& sy, float rv) {
     sx -= rv;
     sy -= rv;
     float d = sx * 12.9898f + sy * 78.233f;
-    float v = pinned_sin(d) * 43758.5453f;
+    float v = pinned_sin<LEAN>(d) * 43758.5453f;
     return v - __builtin_floorf(v);
 }
 

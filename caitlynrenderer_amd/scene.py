@@ -242,6 +242,12 @@ class Scene:
         check(lib().crt_debug_launch_info(self._h, info))
         return bool(info[1] & 4)
 
+    def debug_lean_build(self):
+        """True when that build ran in its LEAN form (bit 3 of crt_debug_launch_info's build word; option "lean_build")"""
+        info = (C.c_int32 * 4)()
+        check(lib().crt_debug_launch_info(self._h, info))
+        return bool(info[1] & 8)
+
     def debug_step_hist(self, stop=False):
         """crt_debug_step_hist: (closest[65], any[65]) node steps of the counting frames since the previous call by number of enabled lanes"""
         if stop:

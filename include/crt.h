@@ -231,6 +231,11 @@ int crt_sync(crt_scene* s);
  *                         last segment runs a build compiled as one — no bounce sampling, next-ray queue or path state in its code
  *                         (measured in profiles/r06_experiments.md); 0 = the build that finds out at run time.
  *                         The same operations either way: sums and visit counters keep their bits.
+ *     "lean_build"        1 (default) or 0: such a last-segment launch (never a counting one) runs the LEAN form of its build where the
+ *                         launch is what the form has compiled in — a tree that passed crt_scene_create's validator (stack pushes without
+ *                         the overflow check), "tri_min" 2 and "lanes_per_ray" 8, no frame of tile-cost measurement —
+ *                         with the RNG's sine in a form of fewer double-precision-rate instructions and the same bits (DESIGN.md
+ *                         section 5; profiles/r07_experiments.md); 0 = the build without it.  The same sums either way.
  *     "streams"           1 (default) .. 4, or 0 = pick for me (3 for scenes of a few nodes, 2 for max_depth > 1, else 1): that many tile shards of the frame rendered side by side on streams of their own on this one GPU
  *                         (own queues and path state, the scene buffers shared).  A multi-segment frame is a chain of dependent
  *                         launches; another shard's launches fill their tails: 1 M triangles, 4 segments, 2 streams +6 %, 8 M triangles
@@ -391,7 +396,7 @@ int crt_debug_time_graph(crt_scene* s, uint32_t n_frames, const float* rxy, uint
 int crt_debug_launch_form(crt_scene* s, int32_t* form);
 /* test hook: the same launch in full: info[0] = form as above (2 = four samples of a 4 x 4 pixel quadrant in the lanes of a wave),
  * info[1] = bit 0: the first segment ran its 6-waves-per-SIMD build (option "wide_first"), bit 1: a one-pass build (no sample loop), bit 2: that
- * build compiled as a last segment (option "last_build"), info[2] = samples per pixel of the launch,
+ * build compiled as a last segment (option "last_build"), bit 3: that build's LEAN form (option "lean_build"), info[2] = samples per pixel of the launch,
  * info[3] = tile shards rendering side by side (option "streams" / crt_set_devices) */
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]);
 /* measurement aid: hist[130] receives, for the counting frames ("count_visits") rendered since the previous call, how many node steps ran

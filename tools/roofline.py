@@ -60,13 +60,13 @@ def demangle_args(name):
     m = re.search(r"k_segmentI((?:Lb[01]E)+)E", name)
     a = [int(x) for x in re.findall(r"Lb([01])E", m.group(1))] if m else None
     # the arguments behind the tenth — INST (the frames of an instanced scene), LAST (the last segment at compile time,
-    # section 5) — default to false: a kernel keeps its ten-argument name here while none of them is set
+    # section 5), LEAN (that build's lean form, section 5) — default to false: a kernel keeps its ten-argument name here while none of them is set
     while a and len(a) > 10 and a[-1] == 0:
         a.pop()
     return a
 
 
-SEG_PARAMS = ["FIRST", "STATS", "TEX", "PRETRACED", "INPLACE", "BVH2", "MAT", "BATCH", "WIDE", "ONE", "INST", "LAST"]
+SEG_PARAMS = ["FIRST", "STATS", "TEX", "PRETRACED", "INPLACE", "BVH2", "MAT", "BATCH", "WIDE", "ONE", "INST", "LAST", "LEAN"]
 
 
 def label_of(name):
@@ -197,6 +197,8 @@ def cmd_isa(asm=None, remarks=None, tag="r03"):
             # the same build as a one-segment frame launches it (option last_build, the default).  The I_* figures below stay those of
             # "first": the walks are the same code, and the shell of "first" is an upper bound of what the launch executes
             "first_last": [1, 0, 0, 0, 1, 0, 0, 1, 1, 1, 0, 1],
+            # and its LEAN form (option lean_build, the default): what the headline's timed launches run
+            "first_lean": [1, 0, 0, 0, 1, 0, 0, 1, 1, 1, 0, 1, 1],
             "first_single": [1, 0, 0, 0, 1, 0, 0, 0, 0, 0],
             "bounce_plain": [0, 0, 0, 0, 1, 0, 0, 0, 0, 0],   # <INPLACE>: closest hit + in-place shadow walk
             "bounce_deferred": [0, 0, 0, 0, 0, 0, 0, 0, 0, 0]}    # <>: closest hit only, shadow rays left to k_shadow_deferred
