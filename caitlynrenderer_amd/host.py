@@ -153,7 +153,9 @@ class SBVH:
 
     def __init__(self, triangles, vertices, flags=0, builder="sbvh"):
         """builder="sbvh": the reference's split-BVH on the host; "lbvh": GPU linear BVH (crt_lbvh_build); "ploc" / "ploc<radius>":
-        GPU parallel locally-ordered clustering (crt_lbvh_build with CRT_GPU_BUILD_PLOC)."""
+        GPU parallel locally-ordered clustering (crt_lbvh_build with CRT_GPU_BUILD_PLOC; radius 0 or none = 16, at most 64); "sah" /
+        "sah<threshold>": GPU binned-SAH build (CRT_GPU_BUILD_SAH) whose nodes of at most <threshold> triangles are finished by the exact
+        sweep (0 or none = 8, clamped to [8, 32]).  DESIGN.md §21 defines the three GPU builders."""
         L = lib()
         tris = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 12)
         verts = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
