@@ -29,7 +29,9 @@
 #include "instances_bind.hpp"
 #include "rt_kernels.hpp"
 
+using crt::dev_alloc;
 using crt::fail;
+using crt::require_device;
 
 #define HIPCHK(expr)                                                                             \
     do {                                                                                         \
@@ -52,15 +54,6 @@ constexpr uint32_t kCursorShadow = kQueueCounters + 17 * 8 * kCounterStride;
 constexpr uint32_t kCounters = kCursorShadow + 17 * 8 * kCounterStride;
 
 struct EventSpan { hipEvent_t a = nullptr, b = nullptr; int kind = 0; };   // kind: 0 raygen 1 closest 2 any 3 shade/other
-
-template <typename T>
-int dev_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-    if (e != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return CRT_OK;
-}
 
 uint32_t morton2(uint32_t x, uint32_t y) {
     auto spread = [](uint32_t v) {
@@ -93,30 +86,39 @@ struct AovState {
     }
 };
 
+// What crt_update_vertices and crt_rebuild_vertices take new positions through, allocated by a scene's first call of either: a scene that
+// never moves holds none of it.  The times are those of the most recent call that succeeded (crt_last_update_ms).
+struct VertexIntake {
+    float* d_verts = nullptr;                // the host forms' upload of the positions
+    uint32_t* d_check = nullptr;             // k_check_vertices: non-finite flag, max keys, complemented min keys
+    uint32_t* h_check = nullptr;             // pinned
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    bool have_times = false, times_pending = false;
+    float device_ms = 0.f, wall_ms = 0.f;
+    ~VertexIntake() {                        // on the scene's device
+        if (d_verts) (void)hipFree(d_verts);
+        if (d_check) (void)hipFree(d_check);
+        if (h_check) (void)hipHostFree(h_check);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+    }
+};
+
 // What crt_update_vertices keeps between updates, allocated by a scene's first update: a scene that never updates holds none of it.
 struct RefitState {
     int device = 0;
-    float* d_verts = nullptr;                // the host form's upload of the positions
-    uint32_t* d_check = nullptr;             // k_check_vertices: non-finite flag, max keys, complemented min keys
-    uint32_t* h_check = nullptr;             // pinned
     uint32_t* d_order = nullptr;             // node8 indices level by level, root level first, then the BVH2's the same way
     std::vector<uint32_t> level8, level2;    // level8[l] = position in d_order of node8 level l (+ end); level2 the same for the BVH2
     crt::RefitMesh* d_mesh = nullptr;        // the scene as one refit mesh (its vertex pointer changes between calls) ...
     crt::RefitMesh* h_mesh = nullptr;        // ... sent from here, pinned
     crt::RefitSeg* d_seg = nullptr;          // the one segment of every launch: entries from 0, items from 0, mesh 0
     float* d_box8 = nullptr;                 // the float box of every node8 (6 floats), which its parent's slot reads
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
     std::vector<hipEvent_t> ev_peer;         // per peer, on its device: "the peer's stream is done with the old scene"
-    bool have_times = false, times_pending = false;
-    float device_ms = 0.f, wall_ms = 0.f;
     ~RefitState() {
         (void)hipSetDevice(device);
-        void* ptrs[] = {d_verts, d_check, d_order, d_box8, d_mesh, d_seg};
+        void* ptrs[] = {d_order, d_box8, d_mesh, d_seg};
         for (void* p : ptrs) if (p) (void)hipFree(p);
-        if (h_check) (void)hipHostFree(h_check);
         if (h_mesh) (void)hipHostFree(h_mesh);
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
         for (hipEvent_t e : ev_peer) if (e) (void)hipEventDestroy(e);
         (void)hipSetDevice(device);
     }
@@ -125,21 +127,8 @@ struct RefitState {
 // What crt_rebuild_vertices keeps between rebuilds, allocated by a scene's first rebuild: a scene that never rebuilds holds
 // none of it, and no walk or frame reads it.
 struct RebuildState {
-    int device = 0;
     crt_triangle* d_src = nullptr;           // the triangles in SOURCE order (create threw its copy away): scattered back from the leaf order once
-    float* d_verts = nullptr;                // the host form's upload of the positions
-    uint32_t* d_check = nullptr;             // k_check_vertices' verdict and bounds, as RefitState's
-    uint32_t* h_check = nullptr;             // pinned
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    float device_ms = 0.f, wall_ms = 0.f;
-    ~RebuildState() {
-        (void)hipSetDevice(device);
-        void* ptrs[] = {d_src, d_verts, d_check};
-        for (void* p : ptrs) if (p) (void)hipFree(p);
-        if (h_check) (void)hipHostFree(h_check);
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-    }
+    ~RebuildState() { if (d_src) (void)hipFree(d_src); }     // on the scene's device
 };
 
 // The lights of an instanced scene that follow its instances (crt_scene_create_instanced_lit).  The scene's d_lights is
@@ -186,10 +175,10 @@ struct crt_scene {
     float4* d_tris2 = nullptr;           // intersection records in BVH2 leaf-slot order
     uint32_t bvh2_stack = 0;             // BVH2 depth + 2
     size_t n_vertices = 0, n_normals = 0, n_slots = 0;   // as created (n_slots: the leaf-order triangle array); crt_update_vertices checks against them
+    VertexIntake* intake = nullptr;      // what both take new positions through, from the first update or rebuild on
     RefitState* refit = nullptr;         // crt_update_vertices' state, from the first update on
     RebuildState* rebuild = nullptr;     // crt_rebuild_vertices' state, from the first rebuild on
     uint32_t gpu_build_flags = 0;        // build-on-device scenes: the builder (CRT_GPU_BUILD_*) a rebuild runs again
-    bool last_update_was_rebuild = false;   // crt_last_update_ms reports the rebuild's times
     // A scene whose geometry is a live crt_instances handle (crt_scene_create_instanced): BORROWED, and bound from create to
     // destroy.  d_nodes / d_tris / d_planes stay null: a frame reads the handle's arrays as they are when it is enqueued.  d_triangles,
     // d_normals and d_texcoords hold every mesh's arrays one after the other, d_mesh_base where each mesh's start.
@@ -385,6 +374,7 @@ struct crt_scene {
         if (inst) crt::instances_unbind(inst, stream);
         delete refit;
         delete rebuild;
+        delete intake;
         delete lit;
         delete aov;
         if (shares_scene)                   // borrowed from the primary, which frees them
@@ -448,14 +438,6 @@ struct crt_scene {
 };
 
 namespace {
-
-int require_device() {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(CRT_ERR_NO_DEVICE, "no HIP device visible: the traversal path has no CPU fallback");
-    return CRT_OK;
-}
 
 // The tiles of shard `rank` of `world`: the frame's tile x tile squares in Morton order, every world-th one starting at the rank-th
 // (SURVEY 8e).  Pure host arithmetic: crt_set_shard, crt_set_devices, option "streams" and the [host] entry crt_shard_tiles share it.
@@ -629,20 +611,26 @@ static int init_scene_common(crt_scene* s, const crt_scene_desc* d) {
     return CRT_OK;
 }
 
-// What a replica on another GPU needs copied (crt_set_devices): the scene-level device buffers and their sizes.
-static void note_buf(crt_scene* s, const void* member, size_t bytes) {
-    s->scene_bufs.emplace_back((size_t)(reinterpret_cast<const char*>(member) - reinterpret_cast<const char*>(s)), bytes);
+// What a replica on another GPU needs copied (crt_set_devices): the scene-level device buffers (by the offset of their pointer member in
+// the scene, which is the same in the replica) and their sizes.
+static size_t buf_offset(const crt_scene* s, const void* member) {
+    return (size_t)(reinterpret_cast<const char*>(member) - reinterpret_cast<const char*>(s));
+}
+static void set_buf_bytes(crt_scene* s, const void* member, size_t bytes) {
+    const size_t off = buf_offset(s, member);
+    for (auto& b : s->scene_bufs) if (b.first == off) { b.second = bytes; return; }
+    s->scene_bufs.emplace_back(off, bytes);
 }
 
 // The traversal's copies of nodes and records at the build's stride (CRT_NODE_ROWS / CRT_TRI_ROWS): packed input -> padded copy.
 template <typename T>
-static int pad_rows(crt_scene* s, T** buf, uint32_t rows_in, uint32_t rows_out, size_t n_items) {
+static int pad_rows(hipStream_t st, const char* who, T** buf, uint32_t rows_in, uint32_t rows_out, size_t n_items) {
     if (rows_in == rows_out || !*buf) return CRT_OK;
     T* padded = nullptr;
     int rc = dev_alloc(&padded, n_items * rows_out);
     if (rc) return rc;
-    crt::launch_restride(*buf, rows_in, padded, rows_out, n_items, s->stream);
-    if (hipStreamSynchronize(s->stream) != hipSuccess || hipGetLastError() != hipSuccess) { (void)hipFree(padded); return fail(CRT_ERR_HIP, "crt_scene_create: re-striding failed"); }
+    crt::launch_restride(*buf, rows_in, padded, rows_out, n_items, st);
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { (void)hipFree(padded); return fail(CRT_ERR_HIP, std::string(who) + "re-striding failed"); }
     (void)hipFree(*buf);
     *buf = padded;
     return CRT_OK;
@@ -661,11 +649,11 @@ static int ensure_planes(crt_scene* s) {
         if ((rc = ensure_planes(p))) return rc;
         HIPCHK(hipStreamSynchronize(p->stream));
         s->d_planes = p->d_planes;
-        note_buf(s, &s->d_planes, (size_t)s->info.n_nodes8 * 12 * sizeof(float4));      // borrowed: the destructor lets go of it
+        set_buf_bytes(s, &s->d_planes, (size_t)s->info.n_nodes8 * 12 * sizeof(float4));      // borrowed: the destructor lets go of it
         return CRT_OK;
     }
     if ((rc = dev_alloc(&s->d_planes, (size_t)s->info.n_nodes8 * 12))) return rc;
-    note_buf(s, &s->d_planes, (size_t)s->info.n_nodes8 * 12 * sizeof(float4));
+    set_buf_bytes(s, &s->d_planes, (size_t)s->info.n_nodes8 * 12 * sizeof(float4));
     crt::launch_expand_planes(s->d_nodes, (uint32_t)CRT_NODE_ROWS, s->d_planes, s->info.n_nodes8, s->stream);
     if (hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, "plane expansion failed");
     return CRT_OK;
@@ -674,8 +662,8 @@ static int ensure_planes(crt_scene* s) {
 static int finish_scene_setup(crt_scene* s) {
     int rc;
     if (!s->rows_padded) {           // a replica's buffers arrive padded (crt_set_devices copies them as they are)
-        if ((rc = pad_rows(s, &s->d_nodes, 5u, (uint32_t)CRT_NODE_ROWS, (size_t)s->info.n_nodes8))) return rc;
-        if ((rc = pad_rows(s, &s->d_tris, 3u, (uint32_t)CRT_TRI_ROWS, (size_t)s->info.n_tris8))) return rc;
+        if ((rc = pad_rows(s->stream, "crt_scene_create: ", &s->d_nodes, 5u, (uint32_t)CRT_NODE_ROWS, (size_t)s->info.n_nodes8))) return rc;
+        if ((rc = pad_rows(s->stream, "crt_scene_create: ", &s->d_tris, 3u, (uint32_t)CRT_TRI_ROWS, (size_t)s->info.n_tris8))) return rc;
         s->rows_padded = true;
     }
     // (the float planes of the uniform node steps: ensure_planes, at the first frame that walks the CWBVH)
@@ -684,6 +672,32 @@ static int finish_scene_setup(crt_scene* s) {
     if ((rc = dev_alloc(&s->d_counts, 2 * kCounters))) return rc;
     s->spans.resize(kMaxEvents);                 // events themselves: created by new_span when a timing option first needs them
     return CRT_OK;
+}
+
+// Publishes a built tree into the scene: its arrays, counts, depths, stack bounds, build times, and the buffer sizes at the traversal's
+// strides (a create pads its arrays right after, finish_scene_setup; a rebuild has padded them).  The scene's previous arrays, if any, are
+// left in `t`, which frees them.  The stream has drained: a BVH2 too deep to walk is freed here.  Cannot fail.
+static void adopt_tree(crt_scene* s, crt::DeviceTree& t) {
+    if (!t.keep_bvh2() && t.bvh2) { (void)hipFree(t.bvh2); t.bvh2 = nullptr; }
+    std::swap(s->d_bvh2, t.bvh2); std::swap(s->d_nodes, t.nodes); std::swap(s->d_tris, t.tris);
+    std::swap(s->d_triangles, t.triangles); std::swap(s->d_tris2, t.tris2);
+    const size_t n2 = 2 * (size_t)t.n - 1;
+    s->bvh2_stack = crt::bvh2_stack_entries(t.depth2);
+    s->stack_entries = t.stack_entries();
+    s->tree_validated = false;                    // the device builders' own tree never went through validate_cwbvh: the checked pushes
+    s->info.n_nodes8 = t.n8; s->info.n_tris8 = t.n; s->info.n_bvh2_nodes = n2; s->info.max_depth8 = t.depth8; s->info.bvh2_depth = t.depth2;
+    s->info.build_lbvh_device_ms = t.lbvh_ms; s->info.build_convert_device_ms = t.conv_ms;
+    set_buf_bytes(s, &s->d_nodes, (size_t)t.n8 * CRT_NODE_ROWS * 16);
+    set_buf_bytes(s, &s->d_tris, (size_t)t.n * CRT_TRI_ROWS * 16);
+    set_buf_bytes(s, &s->d_triangles, (size_t)t.n * sizeof(crt_triangle));
+    if (t.planes) {                               // a scene without planes still builds them at its first CWBVH frame (ensure_planes)
+        std::swap(s->d_planes, t.planes);
+        set_buf_bytes(s, &s->d_planes, (size_t)t.n8 * 12 * sizeof(float4));
+    }
+    if (s->d_bvh2) {
+        set_buf_bytes(s, &s->d_bvh2, n2 * sizeof(crt_flatnode));
+        set_buf_bytes(s, &s->d_tris2, (size_t)t.n * 3 * sizeof(float4));
+    }
 }
 
 extern "C" {
@@ -1153,10 +1167,7 @@ static int scene_create_impl(const crt_scene_desc* d, crt_scene** out) {
     if (!s) return fail(CRT_ERR_NOMEM, "crt_scene_create: out of memory");
     auto bail = [&](int code) { return code; };
     if ((rc = init_scene_common(s, d))) return bail(rc);
-    // A walk pushes at most one entry per level it has descended FROM — what is left of that node's hit list — and the deepest level (depth8,
-    // root = 1) has no inner children to descend to: depth8 - 1 entries hold any walk.  One row of the wave's LDS region is 512 bytes and LDS is
-    // handed out in 1,280-byte units: at depth 11 (8 M triangles) the row saved is the difference between 21 and 24 waves per CU.
-    s->stack_entries = std::min<uint32_t>(CRT_STACK_ENTRIES, std::max<uint32_t>(2, depth8 - 1u));
+    s->stack_entries = crt::cwbvh_stack_entries(depth8);
     s->tree_validated = true;                     // validate_cwbvh above walked every node and reported this depth
     s->info.n_nodes8 = n_nodes8; s->info.n_tris8 = n_tris8; s->info.n_bvh2_nodes = d->n_bvh; s->info.max_depth8 = depth8;
 
@@ -1221,8 +1232,8 @@ static int scene_create_impl(const crt_scene_desc* d, crt_scene** out) {
             if (l <= i || l + 1 >= d->n_bvh) return bail(fail(CRT_ERR_INVALID, "crt_scene_create: BVH2 child link out of order"));
             level[l] = level[l + 1] = level[i] + 1;
         }
-        if (depth2 + 2 > 96) return bail(fail(CRT_ERR_LIMIT, "crt_scene_create: BVH2 deeper than 94 levels"));
-        s->bvh2_stack = depth2 + 2;
+        s->bvh2_stack = crt::bvh2_stack_entries(depth2);
+        if (!s->bvh2_stack) return bail(fail(CRT_ERR_LIMIT, "crt_scene_create: BVH2 deeper than 94 levels"));
         std::vector<float4> rec2(3 * d->n_triangles);
         for (size_t slot = 0; slot < d->n_triangles; ++slot) {
             const crt_triangle& t = d->triangles[slot];
@@ -1243,19 +1254,19 @@ static int scene_create_impl(const crt_scene_desc* d, crt_scene** out) {
         if (hipMemcpy(s->d_tris2, rec2.data(), rec2.size() * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess)
             return bail(fail(CRT_ERR_HIP, "hipMemcpy H2D failed"));
     }
-    note_buf(s, &s->d_nodes, n_nodes8 * (size_t)CRT_NODE_ROWS * 16);
-    note_buf(s, &s->d_tris, n_tris8 * (size_t)CRT_TRI_ROWS * 16);
-    note_buf(s, &s->d_triangles, d->n_triangles * sizeof(crt_triangle));
-    note_buf(s, &s->d_normals, d->n_normals * 3 * sizeof(float));
-    note_buf(s, &s->d_materials, d->n_materials * sizeof(crt_material));
-    note_buf(s, &s->d_lights, d->n_lights * sizeof(crt_light));
+    set_buf_bytes(s, &s->d_nodes, n_nodes8 * (size_t)CRT_NODE_ROWS * 16);
+    set_buf_bytes(s, &s->d_tris, n_tris8 * (size_t)CRT_TRI_ROWS * 16);
+    set_buf_bytes(s, &s->d_triangles, d->n_triangles * sizeof(crt_triangle));
+    set_buf_bytes(s, &s->d_normals, d->n_normals * 3 * sizeof(float));
+    set_buf_bytes(s, &s->d_materials, d->n_materials * sizeof(crt_material));
+    set_buf_bytes(s, &s->d_lights, d->n_lights * sizeof(crt_light));
     if (have_tex) {
-        note_buf(s, &s->d_texcoords, d->n_texcoords * sizeof(float2));
-        note_buf(s, &s->d_textures, (size_t)d->tex_width * d->tex_height * d->n_textures * 3 * sizeof(float));
+        set_buf_bytes(s, &s->d_texcoords, d->n_texcoords * sizeof(float2));
+        set_buf_bytes(s, &s->d_textures, (size_t)d->tex_width * d->tex_height * d->n_textures * 3 * sizeof(float));
     }
     if (d->bvh) {
-        note_buf(s, &s->d_bvh2, d->n_bvh * sizeof(crt_flatnode));
-        note_buf(s, &s->d_tris2, d->n_triangles * 3 * sizeof(float4));
+        set_buf_bytes(s, &s->d_bvh2, d->n_bvh * sizeof(crt_flatnode));
+        set_buf_bytes(s, &s->d_tris2, d->n_triangles * 3 * sizeof(float4));
     }
     if ((rc = finish_scene_setup(s))) return bail(rc);
     *out = owner.release();
@@ -1275,21 +1286,16 @@ static int scene_create_device_built(const crt_scene_desc* d, crt_scene** out) {
     if (!s) return fail(CRT_ERR_NOMEM, "crt_scene_create: out of memory");
     int rc = init_scene_common(s, d);
     if (rc) return rc;
-    const uint32_t n = (uint32_t)d->n_triangles, n2 = 2u * n - 1u;
+    const uint32_t n = (uint32_t)d->n_triangles;
     hipStream_t st = s->stream;
 
     crt::DeviceArena arena;                       // input-order triangles + both builders' temporaries; gone when this returns
     auto P = crt::DeviceArena::padded;
-    const uint32_t gpu_build_flags = (d->build_flags & CRT_BUILD_SAH) ? (CRT_GPU_BUILD_SAH | (d->build_flags & 0xff00u))
-                                     : (d->build_flags & CRT_BUILD_PLOC) ? (CRT_GPU_BUILD_PLOC | (d->build_flags & 0xff00u)) : 0u;
-    const size_t tmp_bytes = std::max(crt::lbvh_tmp_bytes(n, gpu_build_flags), crt::cwbvh_tmp_bytes(n2, n));
-    hipError_t he = arena.reserve(P((size_t)n * sizeof(crt_triangle)) + P(4) + P((size_t)n * 4) + P((size_t)n * 4) + tmp_bytes);
+    s->gpu_build_flags = crt::gpu_flags_of(d->build_flags);
+    hipError_t he = arena.reserve(P((size_t)n * sizeof(crt_triangle)) + P(4) + crt::device_tree_tmp_bytes(n, s->gpu_build_flags));
     if (he != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("crt_scene_create: hipMalloc: ") + hipGetErrorString(he));
     crt_triangle* d_in = arena.take<crt_triangle>(n);
     uint32_t* d_flag = arena.take<uint32_t>(1);
-    uint32_t* d_tri_order = arena.take<uint32_t>(n);
-    int32_t* d_tri_slots = arena.take<int32_t>(n);
-    const size_t persistent_mark = arena.used;
 
 #define UPA(dst, src, count, T)                                                                                      \
     do {                                                                                                             \
@@ -1298,7 +1304,7 @@ static int scene_create_device_built(const crt_scene_desc* d, crt_scene** out) {
             return fail(CRT_ERR_HIP, "hipMemcpy H2D failed");                                                        \
     } while (0)
     float* d_verts = nullptr;
-    struct Guard { void* p = nullptr; ~Guard() { if (p) (void)hipFree(p); } } verts_guard, nodes_guard;
+    struct Guard { void* p = nullptr; ~Guard() { if (p) (void)hipFree(p); } } verts_guard;
     UPA(d_verts, d->vertices, d->n_vertices * 3, float);
     verts_guard.p = d_verts;                      // only the builders and the gather kernels read the vertices
     if (hipMemcpyAsync(d_in, d->triangles, (size_t)n * sizeof(crt_triangle), hipMemcpyHostToDevice, st) != hipSuccess)
@@ -1329,48 +1335,20 @@ static int scene_create_device_built(const crt_scene_desc* d, crt_scene** out) {
 
     // BVH2 (kept: it is the FlatNode array the BVH2 frame mode and CRT_TRACE_BVH2 walk) -> CWBVH
     g_warmer.wait();                              // the builders' code objects: loaded by now, or being loaded by that thread
-    if ((rc = dev_alloc(&s->d_bvh2, (size_t)n2 * 2))) return rc;
-    uint32_t depth2 = 0, n8 = 0, depth8 = 0;
-    float lbvh_ms = 0.f, conv_ms = 0.f;
-    rc = crt::lbvh_build_on_device(reinterpret_cast<const int32_t*>(d_in), 12, d_verts, n, gpu_build_flags, arena, reinterpret_cast<crt_flatnode*>(s->d_bvh2), d_tri_order,
-                                   &depth2, &lbvh_ms, st);
-    if (rc) return fail(rc, std::string("crt_scene_create: LBVH build failed: ") + crt_last_error());
-    arena.used = persistent_mark;                 // the LBVH temporaries are dead: the converter reuses the space
-    crt_node8* d_nodes8 = nullptr;
-    rc = crt::cwbvh_convert_on_device(reinterpret_cast<const crt_flatnode*>(s->d_bvh2), n2, n, arena, d_tri_slots, &d_nodes8, nullptr, &n8, &depth8,
-                                      &conv_ms, st);
-    if (rc) return fail(rc, std::string("crt_scene_create: BVH2 -> CWBVH failed: ") + crt_last_error());
-    s->d_nodes = reinterpret_cast<uint4*>(d_nodes8);
-    if (depth8 > CRT_STACK_ENTRIES) return fail(CRT_ERR_LIMIT, "crt_scene_create: CWBVH rejected: CWBVH deeper than the traversal stack");
-
-    // leaf-order triangle array (what sbvh.h:130-139 leaves behind), records for both walks
-    if ((rc = dev_alloc(&s->d_triangles, (size_t)n * 3))) return rc;
-    if ((rc = dev_alloc(&s->d_tris, (size_t)n * 3))) return rc;
-    const bool keep_bvh2 = depth2 + 2u <= 96u;    // the BVH2 walk's LDS stack bound (crt_scene_create: "BVH2 deeper than 94 levels")
-    if (keep_bvh2 && (rc = dev_alloc(&s->d_tris2, (size_t)n * 3))) return rc;
-    crt::launch_gather_slots(d_in, d_tri_order, d_verts, n, reinterpret_cast<crt_triangle*>(s->d_triangles), keep_bvh2 ? s->d_tris2 : nullptr, st);
-    crt::launch_gather_records(d_in, d_tri_order, d_tri_slots, d_verts, n, s->d_tris, st);
+    crt::DeviceTree tree;
+    if ((rc = dev_alloc(&tree.bvh2, (2 * (size_t)n - 1) * 2))) return rc;
+    if ((rc = crt::build_device_tree(d_in, d_verts, n, s->gpu_build_flags, arena, reinterpret_cast<crt_flatnode*>(tree.bvh2), crt::kSceneTree, st,
+                                     "crt_scene_create: ", &tree))) return rc;
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, "crt_scene_create: scene assembly kernels failed");
-    if (!keep_bvh2) { (void)hipFree(s->d_bvh2); s->d_bvh2 = nullptr; }
-    s->bvh2_stack = keep_bvh2 ? depth2 + 2u : 0u;
-    s->stack_entries = std::min<uint32_t>(CRT_STACK_ENTRIES, std::max<uint32_t>(2, depth8 - 1u));      // as for host-built trees: depth8 - 1 entries hold any walk
-    s->info.n_nodes8 = n8; s->info.n_tris8 = n; s->info.n_bvh2_nodes = n2; s->info.max_depth8 = depth8;
-    s->info.built_on_device = 1u; s->info.bvh2_depth = depth2;
-    s->gpu_build_flags = gpu_build_flags;
-    s->info.build_upload_ms = upload_ms; s->info.build_lbvh_device_ms = lbvh_ms; s->info.build_convert_device_ms = conv_ms;
-    note_buf(s, &s->d_nodes, (size_t)n8 * CRT_NODE_ROWS * 16);
-    note_buf(s, &s->d_tris, (size_t)n * CRT_TRI_ROWS * 16);
-    note_buf(s, &s->d_triangles, (size_t)n * sizeof(crt_triangle));
-    note_buf(s, &s->d_normals, d->n_normals * 3 * sizeof(float));
-    note_buf(s, &s->d_materials, d->n_materials * sizeof(crt_material));
-    note_buf(s, &s->d_lights, d->n_lights * sizeof(crt_light));
+    adopt_tree(s, tree);                          // packed: finish_scene_setup pads to the traversal's strides
+    s->info.built_on_device = 1u;
+    s->info.build_upload_ms = upload_ms;
+    set_buf_bytes(s, &s->d_normals, d->n_normals * 3 * sizeof(float));
+    set_buf_bytes(s, &s->d_materials, d->n_materials * sizeof(crt_material));
+    set_buf_bytes(s, &s->d_lights, d->n_lights * sizeof(crt_light));
     if (have_tex) {
-        note_buf(s, &s->d_texcoords, d->n_texcoords * sizeof(float2));
-        note_buf(s, &s->d_textures, (size_t)d->tex_width * d->tex_height * d->n_textures * 3 * sizeof(float));
-    }
-    if (keep_bvh2) {
-        note_buf(s, &s->d_bvh2, (size_t)n2 * sizeof(crt_flatnode));
-        note_buf(s, &s->d_tris2, (size_t)n * 3 * sizeof(float4));
+        set_buf_bytes(s, &s->d_texcoords, d->n_texcoords * sizeof(float2));
+        set_buf_bytes(s, &s->d_textures, (size_t)d->tex_width * d->tex_height * d->n_textures * 3 * sizeof(float));
     }
     if ((rc = finish_scene_setup(s))) return rc;
     s->info.build_wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
@@ -2929,10 +2907,6 @@ static int ensure_refit_state(crt_scene* s) {
     if (!r) return fail(CRT_ERR_NOMEM, "crt_update_vertices: out of memory");
     r->device = s->device;
     int rc;
-    if ((rc = dev_alloc(&r->d_check, 8))) return rc;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_check), 8 * sizeof(uint32_t)));
-    HIPCHK(hipEventCreate(&r->ev_a));
-    HIPCHK(hipEventCreate(&r->ev_b));
     if ((rc = dev_alloc(&r->d_box8, 6 * (size_t)s->info.n_nodes8))) return rc;
     if ((rc = dev_alloc(&r->d_mesh, 1)) || (rc = dev_alloc(&r->d_seg, 1))) return rc;
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_mesh), sizeof(crt::RefitMesh)));
@@ -2948,43 +2922,86 @@ static int ensure_refit_state(crt_scene* s) {
     return CRT_OK;
 }
 
-static size_t scene_buf_bytes(const crt_scene* s, const void* member) {
-    const size_t off = (size_t)(reinterpret_cast<const char*>(member) - reinterpret_cast<const char*>(s));
-    for (const auto& b : s->scene_bufs) if (b.first == off) return b.second;
-    return 0;
+// The front half of crt_update_vertices and crt_rebuild_vertices (`rebuild`): the argument checks under the call's name, the host form's
+// positions staged on the device, and the check kernel with the call's one host wait for its verdict.  *verts: the positions on the device
+// (the scene's own upload, or the caller's d_user); lo / hi: their bounds.  Nothing the scene shows has been written when this refuses.
+static int take_vertices(crt_scene* s, bool rebuild, const float* h_verts, const float* d_user, size_t n_vertices, const float* normals, size_t n_normals,
+                         const crt_light* lights, size_t n_lights, const float** verts, float lo[3], float hi[3]) {
+    const std::string who = rebuild ? "crt_rebuild_vertices: " : "crt_update_vertices: ";
+    if (!s || (!h_verts && !d_user)) return fail(CRT_ERR_INVALID, who + "null argument");
+    if (s->inst)
+        return fail(CRT_ERR_INVALID, who + "an instanced scene's geometry belongs to its handle: use " +
+                                         (rebuild ? "crt_instances_replace_meshes" : "crt_instances_update_meshes"));
+    if (s->primary) return fail(CRT_ERR_INVALID, who + "not on a replica");
+    if (rebuild) {
+        if (!s->info.built_on_device)
+            return fail(CRT_ERR_INVALID, who + "only a scene built on the device (CRT_BUILD_LBVH_ON_DEVICE) is rebuilt in place; one created from host arrays is created again");
+        for (const crt_scene* p : s->peers)
+            if (!p->shares_scene)
+                return fail(CRT_ERR_INVALID, who + "a replica on another GPU (crt_set_devices) cannot follow a rebuild: return to one device, rebuild, and set the devices again");
+    }
+    if (n_vertices != s->n_vertices) return fail(CRT_ERR_INVALID, who + "n_vertices differs from the count given at create");
+    if (normals && n_normals != s->n_normals) return fail(CRT_ERR_INVALID, who + "n_normals differs from the count given at create");
+    if (lights && n_lights != s->n_lights) return fail(CRT_ERR_INVALID, who + "n_lights differs from the count given at create");
+    if (normals)
+        for (size_t i = 0; i < 3 * n_normals; ++i)
+            if (!std::isfinite(normals[i])) return fail(CRT_ERR_INVALID, who + "a normal is not finite");
+    HIPCHK(hipSetDevice(s->device));
+    int rc;
+    if (!s->intake) {
+        std::unique_ptr<VertexIntake> owner(new (std::nothrow) VertexIntake);
+        if (!owner) return fail(CRT_ERR_NOMEM, who + "out of memory");
+        if ((rc = dev_alloc(&owner->d_check, 8))) return rc;
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&owner->h_check), 8 * sizeof(uint32_t)));
+        HIPCHK(hipEventCreate(&owner->ev_a));
+        HIPCHK(hipEventCreate(&owner->ev_b));
+        s->intake = owner.release();
+    }
+    VertexIntake* in = s->intake;
+    hipStream_t st = s->stream;
+    *verts = d_user;
+    if (h_verts) {
+        if (!in->d_verts && (rc = dev_alloc(&in->d_verts, 3 * n_vertices))) return rc;
+        HIPCHK(hipMemcpyAsync(in->d_verts, h_verts, 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice, st));
+        *verts = in->d_verts;
+    }
+    HIPCHK(hipMemsetAsync(in->d_check, 0, 8 * sizeof(uint32_t), st));
+    crt::launch_check_vertices(*verts, (uint32_t)n_vertices, in->d_check, st);
+    HIPCHK(hipMemcpyAsync(in->h_check, in->d_check, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (in->times_pending) {                      // an unsynchronised update's events have passed by now: read them before this call records its own
+        HIPCHK(hipEventElapsedTime(&in->device_ms, in->ev_a, in->ev_b));
+        in->times_pending = false;
+    }
+    if (in->h_check[0]) return fail(CRT_ERR_INVALID, who + "a vertex coordinate is not finite or exceeds 1e18");
+    for (int k = 0; k < 3; ++k) { hi[k] = crt::rf::key_to_float(in->h_check[1 + k]); lo[k] = crt::rf::key_to_float(~in->h_check[4 + k]); }
+    return CRT_OK;
 }
 
-// d_verts: device positions (the scene's own upload or the caller's); normals / lights: host arrays or null
+// After the geometry of scene x (a primary or a replica) changed: the new bounds (ray_bins / sort_shadow cell grid), a new tile-cost
+// measurement, and the sum cleared as crt_reset does
+static int refresh_after_geometry(crt_scene* x, const float lo[3], const float hi[3]) {
+    for (int k = 0; k < 3; ++k) { x->bounds_lo[k] = lo[k]; x->bounds_hi[k] = hi[k]; }
+    x->tile_state = crt_scene::TILES_WANT;
+    const int rc = ensure_frame(x);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(x->d_sum, 0, 3 * (size_t)std::max<uint32_t>(x->n_local_pixels, 1) * sizeof(float), x->stream));
+    return CRT_OK;
+}
+
+// normals / lights: host arrays or null
 static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, size_t n_vertices, const float* normals, size_t n_normals,
                        const crt_light* lights, size_t n_lights, int sync) {
     const auto t_begin = std::chrono::steady_clock::now();
-    if (!s || (!h_verts && !d_user)) return fail(CRT_ERR_INVALID, "crt_update_vertices: null argument");
-    if (s->inst) return fail(CRT_ERR_INVALID, "crt_update_vertices: an instanced scene's geometry belongs to its handle: use crt_instances_update_meshes");
-    if (s->primary) return fail(CRT_ERR_INVALID, "crt_update_vertices: not on a replica");
-    if (n_vertices != s->n_vertices) return fail(CRT_ERR_INVALID, "crt_update_vertices: n_vertices differs from the count given at create");
-    if (normals && n_normals != s->n_normals) return fail(CRT_ERR_INVALID, "crt_update_vertices: n_normals differs from the count given at create");
-    if (lights && n_lights != s->n_lights) return fail(CRT_ERR_INVALID, "crt_update_vertices: n_lights differs from the count given at create");
-    if (normals)
-        for (size_t i = 0; i < 3 * n_normals; ++i)
-            if (!std::isfinite(normals[i])) return fail(CRT_ERR_INVALID, "crt_update_vertices: a normal is not finite");
-    HIPCHK(hipSetDevice(s->device));
-    int rc = ensure_refit_state(s);
+    const float* verts = nullptr;
+    float lo[3], hi[3];
+    int rc = take_vertices(s, false, h_verts, d_user, n_vertices, normals, n_normals, lights, n_lights, &verts, lo, hi);
     if (rc) return rc;
+    if ((rc = ensure_refit_state(s))) return rc;
+    VertexIntake* in = s->intake;
     RefitState* r = s->refit;
     hipStream_t st = s->stream;
     const uint32_t nv = (uint32_t)n_vertices;
-    const float* verts = d_user;
-    if (h_verts) {
-        if (!r->d_verts && (rc = dev_alloc(&r->d_verts, 3 * n_vertices))) return rc;
-        HIPCHK(hipMemcpyAsync(r->d_verts, h_verts, 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice, st));
-        verts = r->d_verts;
-    }
-    // validation before anything is written: the one host wait of the call
-    HIPCHK(hipMemsetAsync(r->d_check, 0, 8 * sizeof(uint32_t), st));
-    crt::launch_check_vertices(verts, nv, r->d_check, st);
-    HIPCHK(hipMemcpyAsync(r->h_check, r->d_check, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (r->h_check[0]) return fail(CRT_ERR_INVALID, "crt_update_vertices: a vertex coordinate is not finite or exceeds 1e18");
     // the scene as one refit mesh: d_triangles in leaf-slot order, keyed by the slot in e1.w.  The stream is idle here, so the previous
     // call's copy of h_mesh is done; the refit launches read it after this copy, in stream order.
     *r->h_mesh = crt::RefitMesh{verts, reinterpret_cast<const int32_t*>(s->d_triangles), 12u, (uint32_t)s->n_slots, 7u, nv};
@@ -3003,7 +3020,7 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
     if (normals && n_normals) HIPCHK(hipMemcpyAsync(s->d_normals, normals, 3 * n_normals * sizeof(float), hipMemcpyHostToDevice, st));
     if (lights && n_lights) HIPCHK(hipMemcpyAsync(s->d_lights, lights, n_lights * sizeof(crt_light), hipMemcpyHostToDevice, st));
 
-    HIPCHK(hipEventRecord(r->ev_a, st));
+    HIPCHK(hipEventRecord(in->ev_a, st));
     const uint32_t n8 = (uint32_t)s->info.n_nodes8, n_tris8 = (uint32_t)s->info.n_tris8, n_slots = (uint32_t)s->n_slots;
     crt::launch_refit_records(s->d_tris, (uint32_t)CRT_TRI_ROWS, n_tris8, r->d_seg, 1u, n_tris8, r->d_mesh, st);
     if (s->d_tris2) crt::launch_refit_records(s->d_tris2, 3u, n_slots, r->d_seg, 1u, n_slots, r->d_mesh, st);
@@ -3016,75 +3033,52 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
                                       s->d_tris, (uint32_t)CRT_TRI_ROWS, n_tris8, r->d_mesh, r->d_box8, st);
     if (s->d_planes) crt::launch_expand_planes(s->d_nodes, (uint32_t)CRT_NODE_ROWS, s->d_planes, n8, st);
     if (hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, "crt_update_vertices: refit launch failed");
-    HIPCHK(hipEventRecord(r->ev_b, st));
+    HIPCHK(hipEventRecord(in->ev_b, st));
 
-    // the new bounds (ray_bins / sort_shadow cell grid), a new tile-cost measurement, and the sum cleared as crt_reset does
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { hi[k] = crt::rf::key_to_float(r->h_check[1 + k]); lo[k] = crt::rf::key_to_float(~r->h_check[4 + k]); }
-    auto refresh = [&](crt_scene* x) -> int {
-        for (int k = 0; k < 3; ++k) { x->bounds_lo[k] = lo[k]; x->bounds_hi[k] = hi[k]; }
-        x->tile_state = crt_scene::TILES_WANT;
-        const int erc = ensure_frame(x);
-        if (erc) return erc;
-        HIPCHK(hipMemsetAsync(x->d_sum, 0, 3 * (size_t)std::max<uint32_t>(x->n_local_pixels, 1) * sizeof(float), x->stream));
-        return CRT_OK;
-    };
-    if ((rc = refresh(s))) return rc;
+    if ((rc = refresh_after_geometry(s, lo, hi))) return rc;
     // replicas: on this GPU they share the refitted buffers and only wait for them; on another GPU they receive them by peer copy
     for (crt_scene* p : s->peers) {
         HIPCHK(hipSetDevice(p->device));
-        HIPCHK(hipStreamWaitEvent(p->stream, r->ev_b, 0));
+        HIPCHK(hipStreamWaitEvent(p->stream, in->ev_b, 0));
         if (!p->shares_scene) {
-            void* const* bufs[] = {(void* const*)&s->d_nodes, (void* const*)&s->d_tris, (void* const*)&s->d_tris2, (void* const*)&s->d_bvh2,
-                                   (void* const*)&s->d_normals, (void* const*)&s->d_lights};
-            for (void* const* b : bufs) {
-                const size_t off = (size_t)(reinterpret_cast<const char*>(b) - reinterpret_cast<const char*>(s));
-                void* dst = *reinterpret_cast<void**>(reinterpret_cast<char*>(p) + off);
-                const size_t bytes = scene_buf_bytes(s, b);
-                if (*b && dst && bytes) HIPCHK(hipMemcpyPeerAsync(dst, p->device, *b, s->device, bytes, p->stream));
+            const size_t refitted[] = {buf_offset(s, &s->d_nodes), buf_offset(s, &s->d_tris), buf_offset(s, &s->d_tris2), buf_offset(s, &s->d_bvh2),
+                                       buf_offset(s, &s->d_normals), buf_offset(s, &s->d_lights)};
+            for (const auto& b : s->scene_bufs) {
+                if (std::find(std::begin(refitted), std::end(refitted), b.first) == std::end(refitted)) continue;
+                void* src = *reinterpret_cast<void**>(reinterpret_cast<char*>(s) + b.first);
+                void* dst = *reinterpret_cast<void**>(reinterpret_cast<char*>(p) + b.first);
+                if (src && dst && b.second) HIPCHK(hipMemcpyPeerAsync(dst, p->device, src, s->device, b.second, p->stream));
             }
             if (p->d_planes) crt::launch_expand_planes(p->d_nodes, (uint32_t)CRT_NODE_ROWS, p->d_planes, n8, p->stream);
         }
-        if ((rc = refresh(p))) { (void)hipSetDevice(s->device); return rc; }
+        if ((rc = refresh_after_geometry(p, lo, hi))) { (void)hipSetDevice(s->device); return rc; }
     }
     HIPCHK(hipSetDevice(s->device));
-    r->have_times = true;
-    r->times_pending = true;
-    s->last_update_was_rebuild = false;
+    in->have_times = true;
+    in->times_pending = true;
     if (sync) {
         HIPCHK(hipStreamSynchronize(st));
         for (crt_scene* p : s->peers) { HIPCHK(hipSetDevice(p->device)); HIPCHK(hipStreamSynchronize(p->stream)); }
         HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipEventElapsedTime(&r->device_ms, r->ev_a, r->ev_b));
-        r->times_pending = false;
+        HIPCHK(hipEventElapsedTime(&in->device_ms, in->ev_a, in->ev_b));
+        in->times_pending = false;
     }
-    r->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    in->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return CRT_OK;
 }
 
 // ---------------------------------------------------------------- crt_rebuild_vertices --
-// New positions and a new tree: scene_create_device_built's chain run again over the source-order triangles into new
-// buffers, published at the end.  Until then nothing a walk, a frame or a debug read sees has changed.
-
-static void set_buf_bytes(crt_scene* s, const void* member, size_t bytes) {
-    const size_t off = (size_t)(reinterpret_cast<const char*>(member) - reinterpret_cast<const char*>(s));
-    for (auto& b : s->scene_bufs) if (b.first == off) { b.second = bytes; return; }
-    s->scene_bufs.emplace_back(off, bytes);
-}
+// New positions and a new tree: scene_create_device_built's chain (build_device_tree) run again over the source-order
+// triangles into new buffers, published at the end.  Until then nothing a walk, a frame or a debug read sees has changed.
 
 static int ensure_rebuild_state(crt_scene* s) {
     if (s->rebuild) return CRT_OK;
     std::unique_ptr<RebuildState> owner(new (std::nothrow) RebuildState);
     RebuildState* r = owner.get();
     if (!r) return fail(CRT_ERR_NOMEM, "crt_rebuild_vertices: out of memory");
-    r->device = s->device;
-    int rc;
-    if ((rc = dev_alloc(&r->d_check, 8))) return rc;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&r->h_check), 8 * sizeof(uint32_t)));
-    HIPCHK(hipEventCreate(&r->ev_a));
-    HIPCHK(hipEventCreate(&r->ev_b));
     // one triangle per slot and no duplicates in a device build: the records' (original id, slot) pairs are a permutation
     const uint32_t n = (uint32_t)s->info.n_tris8;
+    int rc;
     if ((rc = dev_alloc(&r->d_src, n))) return rc;
     crt::launch_scatter_source(s->d_tris, (uint32_t)CRT_TRI_ROWS, n, reinterpret_cast<const crt_triangle*>(s->d_triangles), r->d_src, s->stream);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess)
@@ -3096,148 +3090,58 @@ static int ensure_rebuild_state(crt_scene* s) {
 static int rebuild_impl(crt_scene* s, const float* h_verts, const float* d_user, size_t n_vertices, const float* normals, size_t n_normals,
                         const crt_light* lights, size_t n_lights) {
     const auto t_begin = std::chrono::steady_clock::now();
-    if (!s || (!h_verts && !d_user)) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: null argument");
-    if (s->inst) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: an instanced scene's geometry belongs to its handle: use crt_instances_replace_meshes");
-    if (s->primary) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: not on a replica");
-    if (!s->info.built_on_device)
-        return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: only a scene built on the device (CRT_BUILD_LBVH_ON_DEVICE) is rebuilt in place; one created from host arrays is created again");
-    for (const crt_scene* p : s->peers)
-        if (!p->shares_scene)
-            return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: a replica on another GPU (crt_set_devices) cannot follow a rebuild: return to one device, rebuild, and set the devices again");
-    if (n_vertices != s->n_vertices) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: n_vertices differs from the count given at create");
-    if (normals && n_normals != s->n_normals) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: n_normals differs from the count given at create");
-    if (lights && n_lights != s->n_lights) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: n_lights differs from the count given at create");
-    if (normals)
-        for (size_t i = 0; i < 3 * n_normals; ++i)
-            if (!std::isfinite(normals[i])) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: a normal is not finite");
-    HIPCHK(hipSetDevice(s->device));
-    int rc = ensure_rebuild_state(s);
+    const float* verts = nullptr;
+    float lo[3], hi[3];
+    int rc = take_vertices(s, true, h_verts, d_user, n_vertices, normals, n_normals, lights, n_lights, &verts, lo, hi);
     if (rc) return rc;
-    RebuildState* r = s->rebuild;
+    if ((rc = ensure_rebuild_state(s))) return rc;
+    VertexIntake* in = s->intake;
     hipStream_t st = s->stream;
-    const uint32_t nv = (uint32_t)n_vertices;
-    const float* verts = d_user;
-    if (h_verts) {
-        if (!r->d_verts && (rc = dev_alloc(&r->d_verts, 3 * n_vertices))) return rc;
-        HIPCHK(hipMemcpyAsync(r->d_verts, h_verts, 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice, st));
-        verts = r->d_verts;
-    }
-    HIPCHK(hipMemsetAsync(r->d_check, 0, 8 * sizeof(uint32_t), st));
-    crt::launch_check_vertices(verts, nv, r->d_check, st);
-    HIPCHK(hipMemcpyAsync(r->h_check, r->d_check, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (r->h_check[0]) return fail(CRT_ERR_INVALID, "crt_rebuild_vertices: a vertex coordinate is not finite or exceeds 1e18");
 
     // the new tree, in buffers of its own: whatever is left in `fresh` when this returns is freed
-    struct Fresh {
-        hipStream_t st;
-        float4* bvh2 = nullptr; uint4* nodes = nullptr; float4* tris = nullptr; int4* triangles = nullptr; float4* tris2 = nullptr; float4* planes = nullptr;
-        ~Fresh() {
-            (void)hipStreamSynchronize(st);
-            void* ptrs[] = {bvh2, nodes, tris, triangles, tris2, planes};
-            for (void* p : ptrs) if (p) (void)hipFree(p);
-        }
-    } fresh{st};
-    const uint32_t n = (uint32_t)s->info.n_tris8, n2 = 2u * n - 1u;
+    const uint32_t n = (uint32_t)s->info.n_tris8;
     crt::DeviceArena arena;
-    auto P = crt::DeviceArena::padded;
-    const size_t tmp_bytes = std::max(crt::lbvh_tmp_bytes(n, s->gpu_build_flags), crt::cwbvh_tmp_bytes(n2, n));
-    hipError_t he = arena.reserve(P((size_t)n * 4) + P((size_t)n * 4) + tmp_bytes);
+    hipError_t he = arena.reserve(crt::device_tree_tmp_bytes(n, s->gpu_build_flags));
     if (he != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("crt_rebuild_vertices: hipMalloc: ") + hipGetErrorString(he));
-    uint32_t* d_tri_order = arena.take<uint32_t>(n);
-    int32_t* d_tri_slots = arena.take<int32_t>(n);
-    const size_t persistent_mark = arena.used;
-    if ((rc = dev_alloc(&fresh.bvh2, (size_t)n2 * 2))) return rc;
-    uint32_t depth2 = 0, n8 = 0, depth8 = 0;
-    float lbvh_ms = 0.f, conv_ms = 0.f;
-    HIPCHK(hipEventRecord(r->ev_a, st));
-    rc = crt::lbvh_build_on_device(reinterpret_cast<const int32_t*>(r->d_src), 12, verts, n, s->gpu_build_flags, arena, reinterpret_cast<crt_flatnode*>(fresh.bvh2),
-                                   d_tri_order, &depth2, &lbvh_ms, st);
-    if (rc) return fail(rc, std::string("crt_rebuild_vertices: LBVH build failed: ") + crt_last_error());
-    arena.used = persistent_mark;
-    crt_node8* d_nodes8 = nullptr;
-    rc = crt::cwbvh_convert_on_device(reinterpret_cast<const crt_flatnode*>(fresh.bvh2), n2, n, arena, d_tri_slots, &d_nodes8, nullptr, &n8, &depth8, &conv_ms, st);
-    if (rc) return fail(rc, std::string("crt_rebuild_vertices: BVH2 -> CWBVH failed: ") + crt_last_error());
-    fresh.nodes = reinterpret_cast<uint4*>(d_nodes8);
-    if (depth8 > CRT_STACK_ENTRIES) return fail(CRT_ERR_LIMIT, "crt_rebuild_vertices: CWBVH rejected: CWBVH deeper than the traversal stack");
-    if ((rc = dev_alloc(&fresh.triangles, (size_t)n * 3))) return rc;
-    if ((rc = dev_alloc(&fresh.tris, (size_t)n * 3))) return rc;
-    const bool keep_bvh2 = depth2 + 2u <= 96u;    // create's rule: the BVH2 walk's LDS stack bound
-    if (keep_bvh2 && (rc = dev_alloc(&fresh.tris2, (size_t)n * 3))) return rc;
-    crt::launch_gather_slots(r->d_src, d_tri_order, verts, n, reinterpret_cast<crt_triangle*>(fresh.triangles), keep_bvh2 ? fresh.tris2 : nullptr, st);
-    crt::launch_gather_records(r->d_src, d_tri_order, d_tri_slots, verts, n, fresh.tris, st);
-    if ((uint32_t)CRT_NODE_ROWS != 5u) {           // the traversal's stride, as finish_scene_setup pads a create's arrays
-        uint4* padded = nullptr;
-        if ((rc = dev_alloc(&padded, (size_t)n8 * CRT_NODE_ROWS))) return rc;
-        crt::launch_restride(fresh.nodes, 5u, padded, (uint32_t)CRT_NODE_ROWS, n8, st);
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(fresh.nodes);
-        fresh.nodes = padded;
-    }
-    if ((uint32_t)CRT_TRI_ROWS != 3u) {
-        float4* padded = nullptr;
-        if ((rc = dev_alloc(&padded, (size_t)n * CRT_TRI_ROWS))) return rc;
-        crt::launch_restride(fresh.tris, 3u, padded, (uint32_t)CRT_TRI_ROWS, n, st);
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(fresh.tris);
-        fresh.tris = padded;
-    }
+    crt::DeviceTree fresh;
+    if ((rc = dev_alloc(&fresh.bvh2, (2 * (size_t)n - 1) * 2))) return rc;
+    HIPCHK(hipEventRecord(in->ev_a, st));
+    if ((rc = crt::build_device_tree(s->rebuild->d_src, verts, n, s->gpu_build_flags, arena, reinterpret_cast<crt_flatnode*>(fresh.bvh2), crt::kSceneTree, st,
+                                     "crt_rebuild_vertices: ", &fresh))) return rc;
+    // the traversal's strides, as finish_scene_setup pads a create's arrays
+    if ((rc = pad_rows(st, "crt_rebuild_vertices: ", &fresh.nodes, 5u, (uint32_t)CRT_NODE_ROWS, (size_t)fresh.n8))) return rc;
+    if ((rc = pad_rows(st, "crt_rebuild_vertices: ", &fresh.tris, 3u, (uint32_t)CRT_TRI_ROWS, (size_t)n))) return rc;
     if (s->d_planes) {                            // re-expanded as create's first frame does; a scene without them still builds them lazily
-        if ((rc = dev_alloc(&fresh.planes, (size_t)n8 * 12))) return rc;
-        crt::launch_expand_planes(fresh.nodes, (uint32_t)CRT_NODE_ROWS, fresh.planes, n8, st);
+        if ((rc = dev_alloc(&fresh.planes, (size_t)fresh.n8 * 12))) return rc;
+        crt::launch_expand_planes(fresh.nodes, (uint32_t)CRT_NODE_ROWS, fresh.planes, fresh.n8, st);
     }
-    HIPCHK(hipEventRecord(r->ev_b, st));
+    HIPCHK(hipEventRecord(in->ev_b, st));
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return fail(CRT_ERR_HIP, "crt_rebuild_vertices: scene assembly kernels failed");
-    if (!keep_bvh2) { (void)hipFree(fresh.bvh2); fresh.bvh2 = nullptr; }
-    // every stream that reads the shared buffers is done with the old tree (replicas live on this device: checked above)
+    // every stream that reads the shared buffers is done with the old tree (replicas live on this device: take_vertices checked)
     for (crt_scene* p : s->peers) HIPCHK(hipStreamSynchronize(p->stream));
 
     // ---- publish: nothing below can refuse ----
     if (normals && n_normals) HIPCHK(hipMemcpyAsync(s->d_normals, normals, 3 * n_normals * sizeof(float), hipMemcpyHostToDevice, st));
     if (lights && n_lights) HIPCHK(hipMemcpyAsync(s->d_lights, lights, n_lights * sizeof(crt_light), hipMemcpyHostToDevice, st));
-    const bool had_planes = s->d_planes != nullptr;
-    std::swap(s->d_bvh2, fresh.bvh2); std::swap(s->d_nodes, fresh.nodes); std::swap(s->d_tris, fresh.tris);
-    std::swap(s->d_triangles, fresh.triangles); std::swap(s->d_tris2, fresh.tris2); std::swap(s->d_planes, fresh.planes);
-    s->bvh2_stack = keep_bvh2 ? depth2 + 2u : 0u;
-    s->stack_entries = std::min<uint32_t>(CRT_STACK_ENTRIES, std::max<uint32_t>(2, depth8 - 1u));
-    s->tree_validated = false;                    // the fresh tree is the device builders' own: the checked pushes from here on
-    s->info.n_nodes8 = n8; s->info.n_tris8 = n; s->info.n_bvh2_nodes = n2; s->info.max_depth8 = depth8; s->info.bvh2_depth = depth2;
-    s->info.build_lbvh_device_ms = lbvh_ms; s->info.build_convert_device_ms = conv_ms;
-    set_buf_bytes(s, &s->d_nodes, (size_t)n8 * CRT_NODE_ROWS * 16);
-    if (had_planes) set_buf_bytes(s, &s->d_planes, (size_t)n8 * 12 * sizeof(float4));
-    if (keep_bvh2) {
-        set_buf_bytes(s, &s->d_bvh2, (size_t)n2 * sizeof(crt_flatnode));
-        set_buf_bytes(s, &s->d_tris2, (size_t)n * 3 * sizeof(float4));
-    }
+    adopt_tree(s, fresh);
     delete s->refit;                              // its level order described the old tree: the next update finds the new tree's
     s->refit = nullptr;
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { hi[k] = crt::rf::key_to_float(r->h_check[1 + k]); lo[k] = crt::rf::key_to_float(~r->h_check[4 + k]); }
-    auto refresh = [&](crt_scene* x) -> int {
-        for (int k = 0; k < 3; ++k) { x->bounds_lo[k] = lo[k]; x->bounds_hi[k] = hi[k]; }
-        x->tile_state = crt_scene::TILES_WANT;
-        const int erc = ensure_frame(x);
-        if (erc) return erc;
-        HIPCHK(hipMemsetAsync(x->d_sum, 0, 3 * (size_t)std::max<uint32_t>(x->n_local_pixels, 1) * sizeof(float), x->stream));
-        return CRT_OK;
-    };
-    if ((rc = refresh(s))) return rc;
+    if ((rc = refresh_after_geometry(s, lo, hi))) return rc;
     for (crt_scene* p : s->peers) {               // the same buffers, borrowed
         p->d_bvh2 = s->d_bvh2; p->d_nodes = s->d_nodes; p->d_tris = s->d_tris; p->d_triangles = s->d_triangles; p->d_tris2 = s->d_tris2;
         p->d_planes = p->d_planes ? s->d_planes : nullptr;
-        const bool peer_planes = p->d_planes != nullptr;
         p->info = s->info; p->bvh2_stack = s->bvh2_stack; p->stack_entries = s->stack_entries; p->tree_validated = s->tree_validated;
         p->scene_bufs = s->scene_bufs;
-        if (!peer_planes)                         // not borrowed yet: ensure_planes notes it when it is
+        if (!p->d_planes)                         // not borrowed yet: ensure_planes notes it when it is
             p->scene_bufs.erase(std::remove_if(p->scene_bufs.begin(), p->scene_bufs.end(), [&](const std::pair<size_t, size_t>& b) {
-                return b.first == (size_t)(reinterpret_cast<const char*>(&s->d_planes) - reinterpret_cast<const char*>(s)); }), p->scene_bufs.end());
-        if ((rc = refresh(p))) return rc;
+                return b.first == buf_offset(s, &s->d_planes); }), p->scene_bufs.end());
+        if ((rc = refresh_after_geometry(p, lo, hi))) return rc;
     }
     HIPCHK(hipStreamSynchronize(st));
     for (crt_scene* p : s->peers) HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipEventElapsedTime(&r->device_ms, r->ev_a, r->ev_b));
-    s->last_update_was_rebuild = true;
-    r->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    HIPCHK(hipEventElapsedTime(&in->device_ms, in->ev_a, in->ev_b));
+    in->have_times = true;
+    in->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return CRT_OK;
 }
 
@@ -3291,12 +3195,7 @@ int crt_update_vertices_device(crt_scene* s, const void* d_vertices, size_t n_ve
 
 int crt_last_update_ms(crt_scene* s, float* device_ms, float* wall_ms) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_last_update_ms: null scene");
-    if (s->last_update_was_rebuild && s->rebuild) {
-        if (device_ms) *device_ms = s->rebuild->device_ms;
-        if (wall_ms) *wall_ms = s->rebuild->wall_ms;
-        return CRT_OK;
-    }
-    RefitState* r = s->refit;
+    VertexIntake* r = s->intake;
     if (!r || !r->have_times) return fail(CRT_ERR_INVALID, "crt_last_update_ms: no update yet");
     if (r->times_pending) {
         HIPCHK(hipSetDevice(s->device));

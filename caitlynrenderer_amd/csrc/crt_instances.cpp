@@ -26,7 +26,10 @@
 #include "instances_bind.hpp"
 #include "rt_kernels.hpp"
 
+using crt::dev_alloc;
 using crt::fail;
+using crt::gpu_flags_of;
+using crt::require_device;
 
 #define IHIPCHK(expr)                                                                            \
     do {                                                                                         \
@@ -154,55 +157,28 @@ struct crt_instances {
 
 namespace {
 
-int require_gpu() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(CRT_ERR_NO_DEVICE, "no HIP device visible: the traversal path has no CPU fallback");
-    return CRT_OK;
-}
-
-template <typename T>
-int alloc(T** p, size_t count) {
-    *p = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return CRT_OK;
-}
-
-uint32_t gpu_flags_of(uint32_t build_flags) {
-    return (build_flags & CRT_BUILD_SAH) ? (CRT_GPU_BUILD_SAH | (build_flags & 0xff00u))
-           : (build_flags & CRT_BUILD_PLOC) ? (CRT_GPU_BUILD_PLOC | (build_flags & 0xff00u)) : 0u;
-}
-
 // One mesh: LBVH / PLOC / SAH BVH2 -> CWBVH -> records, as crt_scene_create's build-on-device path.  *d_nodes8 and *d_recs are the
 // caller's to free.
 int build_blas(const crt_blas_desc& m, uint32_t gpu_flags, hipStream_t st, const std::string& who, crt_node8** d_nodes8, float4** d_recs, uint32_t* n8,
                uint32_t* depth8) {
     const uint32_t n = (uint32_t)m.n_triangles, n2 = 2u * n - 1u;
-    crt::DeviceArena arena;
+    crt::DeviceArena arena;                       // the mesh's vertices, triangles and BVH2 too: one allocation per BLAS
     auto P = crt::DeviceArena::padded;
-    const size_t tmp = std::max(crt::lbvh_tmp_bytes(n, gpu_flags), crt::cwbvh_tmp_bytes(n2, n));
-    hipError_t he = arena.reserve(P(m.n_vertices * 12) + P((size_t)n * sizeof(crt_triangle)) + P((size_t)n2 * sizeof(crt_flatnode)) + 2 * P((size_t)n * 4) + tmp);
+    hipError_t he = arena.reserve(P(m.n_vertices * 12) + P((size_t)n * sizeof(crt_triangle)) + P((size_t)n2 * sizeof(crt_flatnode)) +
+                                  crt::device_tree_tmp_bytes(n, gpu_flags));
     if (he != hipSuccess) return fail(CRT_ERR_NOMEM, who + "hipMalloc: " + hipGetErrorString(he));
     float* d_verts = arena.take<float>(m.n_vertices * 3);
     crt_triangle* d_in = arena.take<crt_triangle>(n);
     crt_flatnode* d_flat = arena.take<crt_flatnode>(n2);
-    uint32_t* d_order = arena.take<uint32_t>(n);
-    int32_t* d_slots = arena.take<int32_t>(n);
-    const size_t mark = arena.used;
     IHIPCHK(hipMemcpyAsync(d_verts, m.vertices, m.n_vertices * 12, hipMemcpyHostToDevice, st));
     IHIPCHK(hipMemcpyAsync(d_in, m.triangles, (size_t)n * sizeof(crt_triangle), hipMemcpyHostToDevice, st));
-    uint32_t depth2 = 0;
-    float ms = 0.f;
-    int rc = crt::lbvh_build_on_device(reinterpret_cast<const int32_t*>(d_in), 12, d_verts, n, gpu_flags, arena, d_flat, d_order, &depth2, &ms, st);
-    if (rc) return fail(rc, who + "BLAS build failed: " + crt_last_error());
-    arena.used = mark;
-    rc = crt::cwbvh_convert_on_device(d_flat, n2, n, arena, d_slots, d_nodes8, nullptr, n8, depth8, &ms, st);
-    if (rc) return fail(rc, who + "BLAS BVH2 -> CWBVH failed: " + crt_last_error());
-    if ((rc = alloc(d_recs, (size_t)n * 3))) { (void)hipFree(*d_nodes8); *d_nodes8 = nullptr; return rc; }
-    crt::launch_gather_records(d_in, d_order, d_slots, d_verts, n, *d_recs, st);
+    crt::DeviceTree tree;
+    const int rc = crt::build_device_tree(d_in, d_verts, n, gpu_flags, arena, d_flat, crt::kBlasTree, st, who, &tree);
+    if (rc) return rc;
     IHIPCHK(hipStreamSynchronize(st));                // before the arena goes
     IHIPCHK(hipGetLastError());
+    *d_nodes8 = reinterpret_cast<crt_node8*>(tree.nodes); *d_recs = tree.tris; *n8 = tree.n8; *depth8 = tree.depth8;
+    tree.nodes = nullptr; tree.tris = nullptr;
     return CRT_OK;
 }
 
@@ -432,9 +408,9 @@ int init_update_state(crt_instances* s, const crt_blas_desc* meshes, const std::
     }
     if (v_total >= (1ull << 32) / 12) return fail(CRT_ERR_LIMIT, "crt_instances_create: more vertices than an updatable handle stages");
     int rc;
-    if ((rc = alloc(&u->d_src_idx, idx.size())) || (rc = alloc(&u->d_box8, 6 * n8_all)) ||
-        (rc = alloc(&u->d_live, 16 * (size_t)s->capacity)) || (rc = alloc(&u->d_mesh_box_stage, 6 * (size_t)M)) ||
-        (rc = alloc(&u->d_vstage, 3 * v_total)) || (rc = alloc(&u->d_check, 8 * (size_t)M)))
+    if ((rc = dev_alloc(&u->d_src_idx, idx.size())) || (rc = dev_alloc(&u->d_box8, 6 * n8_all)) ||
+        (rc = dev_alloc(&u->d_live, 16 * (size_t)s->capacity)) || (rc = dev_alloc(&u->d_mesh_box_stage, 6 * (size_t)M)) ||
+        (rc = dev_alloc(&u->d_vstage, 3 * v_total)) || (rc = dev_alloc(&u->d_check, 8 * (size_t)M)))
         return rc;
     IHIPCHK(hipHostMalloc(reinterpret_cast<void**>(&u->h_check), 8 * (size_t)M * sizeof(uint32_t)));
     IHIPCHK(hipEventCreate(&u->ev0));
@@ -448,7 +424,7 @@ int init_update_state(crt_instances* s, const crt_blas_desc* meshes, const std::
     // the call's tables: RefitMesh, chunk starts and record segments per mesh, level segments per mesh and level
     auto A = [](size_t b) { return (b + 15) & ~size_t(15); };
     u->table_cap = A(M * sizeof(crt::RefitMesh)) + A(M * 4) + A(M * sizeof(crt::RefitSeg)) + (size_t)M * u->max_levels * sizeof(crt::RefitSeg);
-    if ((rc = alloc(&u->d_table, u->table_cap))) return rc;
+    if ((rc = dev_alloc(&u->d_table, u->table_cap))) return rc;
     IHIPCHK(hipStreamSynchronize(st));            // before the host arrays go
     u->bytes = 4 * n8_all + 24 * n8_all + 12 * tris_all + 64 * (uint64_t)s->capacity + 24 * (uint64_t)M + 12 * v_total + 32 * (uint64_t)M +
                u->table_cap;
@@ -613,7 +589,7 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
         if (rc) return rc;
         tris_total += meshes[k].n_triangles;
     }
-    int rc = require_gpu();
+    int rc = require_device();
     if (rc) return rc;
     std::unique_ptr<crt_instances> owner(new (std::nothrow) crt_instances);
     crt_instances* s = owner.get();
@@ -644,8 +620,8 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
     if (nodes_total * CRT_NODE_ROWS * 16 >= (1ull << 32) || tris_total * CRT_TRI_ROWS * 16 >= (1ull << 32))
         return fail(CRT_ERR_LIMIT, "crt_instances_create: the packed node or record array exceeds 4 GiB");
     if (CRT_NODE_ROWS != 5 || CRT_TRI_ROWS != 3) return fail(CRT_ERR_LIMIT, "crt_instances_create: needs the packed row strides (5 / 3)");
-    if ((rc = alloc(&s->d_nodes, nodes_total * 5))) return rc;
-    if ((rc = alloc(&s->d_tris, tris_total * 3))) return rc;
+    if ((rc = dev_alloc(&s->d_nodes, nodes_total * 5))) return rc;
+    if ((rc = dev_alloc(&s->d_tris, tris_total * 3))) return rc;
     std::vector<uint32_t> roots(n_meshes);
     std::vector<crt_node8*> blas_nodes(n_meshes);
     std::vector<uint32_t> blas_n8(n_meshes);
@@ -659,18 +635,18 @@ int create_impl(const crt_blas_desc* meshes, uint32_t n_meshes, const crt_instan
         node_off += blas[k].n8; tri_off += meshes[k].n_triangles;
     }
     s->blas_nodes8 = nodes_total - s->tlas_cap_nodes; s->blas_tris = tris_total;
-    if ((rc = alloc(&s->d_mesh_box, mesh_box.size()))) return rc;
-    if ((rc = alloc(&s->d_mesh_root, n_meshes))) return rc;
+    if ((rc = dev_alloc(&s->d_mesh_box, mesh_box.size()))) return rc;
+    if ((rc = dev_alloc(&s->d_mesh_root, n_meshes))) return rc;
     IHIPCHK(hipMemcpyAsync(s->d_mesh_box, mesh_box.data(), mesh_box.size() * 4, hipMemcpyHostToDevice, st));
     IHIPCHK(hipMemcpyAsync(s->d_mesh_root, roots.data(), n_meshes * 4, hipMemcpyHostToDevice, st));
     const size_t C = capacity;
-    if ((rc = alloc(&s->d_inst, C * 4)) || (rc = alloc(&s->d_w2o, C * 12)) || (rc = alloc(&s->d_wbox, C * 6)) || (rc = alloc(&s->d_in, C * 16)) ||
-        (rc = alloc(&s->d_rec, C * 4)) || (rc = alloc(&s->d_box, C * 6)) || (rc = alloc(&s->d_w2o_stage, C * 12)) || (rc = alloc(&s->d_flag, 2)) ||
-        (rc = alloc(&s->d_overflow, 1)) || (rc = alloc(&s->d_t8_stage, s->tlas_cap_nodes)) || (rc = alloc(&s->d_tlas_box8, 6 * (size_t)s->tlas_cap_nodes)) ||
-        (rc = alloc(&s->d_box_idx, C * 3)) || (rc = alloc(&s->d_tlas_table, sizeof(crt::RefitMesh) + 255 * sizeof(crt::RefitSeg))) ||
-        (rc = alloc(&s->d_cmask, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_parent, s->tlas_cap_nodes)) || (rc = alloc(&s->d_cm_leaf, C)) ||
-        (rc = alloc(&s->d_mesh_of, C)) || (rc = alloc(&s->d_mesh_of_stage, C)) ||
-        (rc = alloc(&s->d_o2w, C * 12)) || (rc = alloc(&s->d_o2w_stage, C * 12)))
+    if ((rc = dev_alloc(&s->d_inst, C * 4)) || (rc = dev_alloc(&s->d_w2o, C * 12)) || (rc = dev_alloc(&s->d_wbox, C * 6)) || (rc = dev_alloc(&s->d_in, C * 16)) ||
+        (rc = dev_alloc(&s->d_rec, C * 4)) || (rc = dev_alloc(&s->d_box, C * 6)) || (rc = dev_alloc(&s->d_w2o_stage, C * 12)) || (rc = dev_alloc(&s->d_flag, 2)) ||
+        (rc = dev_alloc(&s->d_overflow, 1)) || (rc = dev_alloc(&s->d_t8_stage, s->tlas_cap_nodes)) || (rc = dev_alloc(&s->d_tlas_box8, 6 * (size_t)s->tlas_cap_nodes)) ||
+        (rc = dev_alloc(&s->d_box_idx, C * 3)) || (rc = dev_alloc(&s->d_tlas_table, sizeof(crt::RefitMesh) + 255 * sizeof(crt::RefitSeg))) ||
+        (rc = dev_alloc(&s->d_cmask, s->tlas_cap_nodes)) || (rc = dev_alloc(&s->d_cm_parent, s->tlas_cap_nodes)) || (rc = dev_alloc(&s->d_cm_leaf, C)) ||
+        (rc = dev_alloc(&s->d_mesh_of, C)) || (rc = dev_alloc(&s->d_mesh_of_stage, C)) ||
+        (rc = dev_alloc(&s->d_o2w, C * 12)) || (rc = dev_alloc(&s->d_o2w_stage, C * 12)))
         return rc;
     crt::launch_box_triples(s->d_box_idx, capacity, st);
     IHIPCHK(hipMemsetAsync(s->d_overflow, 0, 4, st));
@@ -794,8 +770,8 @@ int remesh_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const crt_bla
         for (uint32_t m = 0; m < M0; ++m)
             if (from[m] < 0) std::copy(live_box.begin() + 6 * (size_t)m, live_box.begin() + 6 * (size_t)m + 6, box_all.begin() + 6 * (size_t)m);
     }
-    if ((rc = alloc(&r.d_nodes, nodes_total * 5)) || (rc = alloc(&r.d_tris, tris_total * 3)) || (rc = alloc(&r.d_mesh_box, box_all.size())) ||
-        (rc = alloc(&r.d_mesh_root, M1)))
+    if ((rc = dev_alloc(&r.d_nodes, nodes_total * 5)) || (rc = dev_alloc(&r.d_tris, tris_total * 3)) || (rc = dev_alloc(&r.d_mesh_box, box_all.size())) ||
+        (rc = dev_alloc(&r.d_mesh_root, M1)))
         return rc;
 
     // the refit state of an updatable handle for the new list: kept meshes re-offset, the call's meshes discovered
@@ -815,8 +791,8 @@ int remesh_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const crt_bla
             if (from[m] >= 0) call_tris += slot[m].n_tris;
         }
         if (v_total >= (1ull << 32) / 12) return fail(CRT_ERR_LIMIT, who + "more vertices than an updatable handle stages");
-        if ((rc = alloc(&nu->d_src_idx, 3 * tris_total)) || (rc = alloc(&nu->d_box8, 6 * n8_all)) || (rc = alloc(&nu->d_order, n8_all)) ||
-            (rc = alloc(&nu->d_mesh_box_stage, 6 * (size_t)M1)) || (rc = alloc(&nu->d_vstage, 3 * v_total)) || (rc = alloc(&nu->d_check, 8 * (size_t)M1)))
+        if ((rc = dev_alloc(&nu->d_src_idx, 3 * tris_total)) || (rc = dev_alloc(&nu->d_box8, 6 * n8_all)) || (rc = dev_alloc(&nu->d_order, n8_all)) ||
+            (rc = dev_alloc(&nu->d_mesh_box_stage, 6 * (size_t)M1)) || (rc = dev_alloc(&nu->d_vstage, 3 * v_total)) || (rc = dev_alloc(&nu->d_check, 8 * (size_t)M1)))
             return rc;
         IHIPCHK(hipHostMalloc(reinterpret_cast<void**>(&nu->h_check), 8 * (size_t)M1 * sizeof(uint32_t)));
         IHIPCHK(hipEventCreate(&nu->ev0));
@@ -856,7 +832,7 @@ int remesh_impl(crt_instances* s, const uint32_t* ids, uint32_t n, const crt_bla
         IHIPCHK(hipMemsetAsync(nu->d_box8, 0, 24 * n8_all, st));
         auto A = [](size_t b) { return (b + 15) & ~size_t(15); };
         nu->table_cap = A(M1 * sizeof(crt::RefitMesh)) + A(M1 * 4) + A(M1 * sizeof(crt::RefitSeg)) + (size_t)M1 * nu->max_levels * sizeof(crt::RefitSeg);
-        if ((rc = alloc(&nu->d_table, nu->table_cap))) return rc;
+        if ((rc = dev_alloc(&nu->d_table, nu->table_cap))) return rc;
         nu->bytes = 4 * n8_all + 24 * n8_all + 12 * tris_total + 64 * (uint64_t)s->capacity + 24 * (uint64_t)M1 + 12 * v_total + 32 * (uint64_t)M1 +
                     nu->table_cap;
     }

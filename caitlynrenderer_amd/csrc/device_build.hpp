@@ -6,11 +6,46 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <string>
 #include <vector>
 
 #include "../../include/crt.h"
+#include "crt_error.hpp"
+#include "rt_kernels.hpp"
 
 namespace crt {
+
+// ---- what the host files share ----
+inline int require_device() {
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0)
+        return fail(CRT_ERR_NO_DEVICE, "no HIP device visible: the traversal path has no CPU fallback");
+    return CRT_OK;
+}
+
+template <typename T>
+int dev_alloc(T** p, size_t count) {
+    *p = nullptr;
+    if (count == 0) count = 1;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
+    if (e != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return CRT_OK;
+}
+
+// the builder a create's CRT_BUILD_* flags ask of the device (CRT_GPU_BUILD_*; bits 8-15: the PLOC radius)
+inline uint32_t gpu_flags_of(uint32_t build_flags) {
+    return (build_flags & CRT_BUILD_SAH) ? (CRT_GPU_BUILD_SAH | (build_flags & 0xff00u))
+           : (build_flags & CRT_BUILD_PLOC) ? (CRT_GPU_BUILD_PLOC | (build_flags & 0xff00u)) : 0u;
+}
+
+// A walk pushes at most one entry per level it has descended FROM — what is left of that node's hit list — and the deepest level (depth8,
+// root = 1) has no inner children to descend to: depth8 - 1 entries hold any walk.  One row of the wave's LDS region is 512 bytes and LDS is
+// handed out in 1,280-byte units: at depth 11 (8 M triangles) the row saved is the difference between 21 and 24 waves per CU.
+inline uint32_t cwbvh_stack_entries(uint32_t depth8) { return std::min<uint32_t>(CRT_STACK_ENTRIES, std::max<uint32_t>(2u, depth8 - 1u)); }
+// The BVH2 walk's LDS stack: depth + 2 entries, 96 at the most.  0 = deeper than that: such a BVH2 is not walked (nor kept)
+inline uint32_t bvh2_stack_entries(uint32_t depth2) { return depth2 + 2u <= 96u ? depth2 + 2u : 0u; }
 
 // One hipMalloc carved into 256-byte aligned pieces and freed as a whole: the builders need ~25 temporaries, and a
 // hipMalloc / hipFree pair per temporary was most of the wall time of a call.
@@ -77,6 +112,48 @@ void launch_gather_slots(const crt_triangle* d_in, const uint32_t* d_tri_order, 
 // CWBVH-ordered intersection records: record i describes slot d_tri_slots[i].
 void launch_gather_records(const crt_triangle* d_in, const uint32_t* d_tri_order, const int32_t* d_tri_slots, const float* d_verts, uint32_t n_tris8,
                            float4* d_recs, hipStream_t stream);
+
+// ---- source-order triangles -> a walkable tree (scene_build.hip): crt_scene_create's build-on-device path, crt_rebuild_vertices, every BLAS ----
+// What differs between a scene's tree and a mesh's.
+struct TreeKind {
+    const char* build;         // the two builder stages, as the messages name them
+    const char* convert;
+    uint32_t max_depth8;       // a deeper CWBVH is refused; 0 = no bound here
+    bool slot_arrays;          // also the leaf-order triangle array and, while the BVH2 is walkable, its records
+};
+constexpr TreeKind kSceneTree{"LBVH build", "BVH2 -> CWBVH", CRT_STACK_ENTRIES, true};
+constexpr TreeKind kBlasTree{"BLAS build", "BLAS BVH2 -> CWBVH", 0u /* bounded with the TLAS's depth, at every set */, false};
+
+// A built tree.  Owns what it holds until the caller takes it (and nulls the pointer): the destructor waits for the stream and frees the rest.
+struct DeviceTree {
+    hipStream_t st = nullptr;
+    float4* bvh2 = nullptr;    // the caller's own allocation, when it wants the tree to own it (a scene's; a BLAS's BVH2 is a piece of its arena)
+    uint4* nodes = nullptr;    // packed: 5 rows per node8 ...
+    float4* tris = nullptr;    // ... and 3 per record, CWBVH order
+    int4* triangles = nullptr; // slot arrays: the triangles in BVH2 leaf order (what sbvh.h:130-139 leaves behind)
+    float4* tris2 = nullptr;   // slot arrays: the records in that order
+    float4* planes = nullptr;  // the caller's, when it expands them (crt_rebuild_vertices)
+    uint32_t n = 0, n8 = 0, depth8 = 0, depth2 = 0;
+    float lbvh_ms = 0.f, conv_ms = 0.f;
+    bool keep_bvh2() const { return bvh2_stack_entries(depth2) != 0u; }
+    uint32_t stack_entries() const { return cwbvh_stack_entries(depth8); }
+    DeviceTree() = default;
+    DeviceTree(const DeviceTree&) = delete;
+    DeviceTree& operator=(const DeviceTree&) = delete;
+    ~DeviceTree() {
+        void* ptrs[] = {bvh2, nodes, tris, triangles, tris2, planes};
+        if (std::all_of(std::begin(ptrs), std::end(ptrs), [](void* p) { return !p; })) return;
+        (void)hipStreamSynchronize(st);
+        for (void* p : ptrs) if (p) (void)hipFree(p);
+    }
+};
+// what build_device_tree takes from the arena: leaf order, CWBVH slots, and the larger of the two builders' temporaries
+size_t device_tree_tmp_bytes(uint32_t n, uint32_t gpu_flags);
+// LBVH / PLOC / SAH BVH2 of the n triangles d_src (source order) into d_flat (2n - 1 nodes, the caller's), then the CWBVH, the records and the
+// slot arrays, each in a hipMalloc of its own that *out owns.  The builders wait for the stream; the gather kernels are only enqueued, and read
+// the arena: the caller waits for the stream before the arena goes.  `who` prefixes the messages.
+int build_device_tree(const crt_triangle* d_src, const float* d_verts, uint32_t n, uint32_t gpu_flags, DeviceArena& arena, crt_flatnode* d_flat,
+                      const TreeKind& kind, hipStream_t st, const std::string& who, DeviceTree* out);
 
 // ---- refit to new positions, same topology (refit.hip): crt_update_vertices, crt_instances_update_meshes, crt_instances_refit ----
 // One refitted tree's geometry.  Index entry e holds a triangle's three vertex indices at idx[stride * e + 0..2]; a record names its entry

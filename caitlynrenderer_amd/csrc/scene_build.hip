@@ -108,6 +108,34 @@ void launch_gather_records(const crt_triangle* d_in, const uint32_t* d_tri_order
     hipLaunchKernelGGL(k_gather_records, grid_for(n_tris8), dim3(256), 0, stream, d_in, d_tri_order, d_tri_slots, d_verts, n_tris8, d_recs);
 }
 
+size_t device_tree_tmp_bytes(uint32_t n, uint32_t gpu_flags) {
+    return 2 * DeviceArena::padded((size_t)n * 4) + std::max(lbvh_tmp_bytes(n, gpu_flags), cwbvh_tmp_bytes(2u * (size_t)n - 1u, n));
+}
+
+int build_device_tree(const crt_triangle* d_src, const float* d_verts, uint32_t n, uint32_t gpu_flags, DeviceArena& arena, crt_flatnode* d_flat,
+                      const TreeKind& kind, hipStream_t st, const std::string& who, DeviceTree* out) {
+    uint32_t* d_tri_order = arena.take<uint32_t>(n);
+    int32_t* d_tri_slots = arena.take<int32_t>(n);
+    if (!d_tri_order || !d_tri_slots) return fail(CRT_ERR_NOMEM, who + "the build arena is smaller than device_tree_tmp_bytes");
+    const size_t persistent_mark = arena.used;
+    out->st = st;
+    out->n = n;
+    int rc = lbvh_build_on_device(reinterpret_cast<const int32_t*>(d_src), 12, d_verts, n, gpu_flags, arena, d_flat, d_tri_order, &out->depth2, &out->lbvh_ms, st);
+    if (rc) return fail(rc, who + kind.build + " failed: " + crt_last_error());
+    arena.used = persistent_mark;                 // the LBVH temporaries are dead: the converter reuses the space
+    crt_node8* d_nodes8 = nullptr;
+    rc = cwbvh_convert_on_device(d_flat, 2u * n - 1u, n, arena, d_tri_slots, &d_nodes8, nullptr, &out->n8, &out->depth8, &out->conv_ms, st);
+    if (rc) return fail(rc, who + kind.convert + " failed: " + crt_last_error());
+    out->nodes = reinterpret_cast<uint4*>(d_nodes8);
+    if (kind.max_depth8 && out->depth8 > kind.max_depth8) return fail(CRT_ERR_LIMIT, who + "CWBVH rejected: CWBVH deeper than the traversal stack");
+    if (kind.slot_arrays && (rc = dev_alloc(&out->triangles, (size_t)n * 3))) return rc;
+    if ((rc = dev_alloc(&out->tris, (size_t)n * 3))) return rc;
+    if (kind.slot_arrays && out->keep_bvh2() && (rc = dev_alloc(&out->tris2, (size_t)n * 3))) return rc;
+    if (kind.slot_arrays) launch_gather_slots(d_src, d_tri_order, d_verts, n, reinterpret_cast<crt_triangle*>(out->triangles), out->tris2, st);
+    launch_gather_records(d_src, d_tri_order, d_tri_slots, d_verts, n, out->tris, st);
+    return CRT_OK;
+}
+
 // crt_warmup: load this translation unit's code object on the current device (device_build.hpp)
 int warm_scene_build_kernels() {
     hipFuncAttributes a;

@@ -438,6 +438,88 @@ def test_g6_the_device_form_takes_a_torch_tensor(cr, cornell):
     a.close(); b.close()
 
 
+# What crt_update_vertices and crt_rebuild_vertices say when they refuse, word for word as the entry points were written before the two
+# shared one intake (each `_device` form speaks under the name of its host form): the text behind "crt error <code>: ".
+_COUNT = "n_vertices differs from the count given at create"
+_NOT_FINITE = "a vertex coordinate is not finite or exceeds 1e18"
+_NORMALS = "n_normals differs from the count given at create"
+_LIGHTS = "n_lights differs from the count given at create"
+_HOST_BUILT = ("only a scene built on the device (CRT_BUILD_LBVH_ON_DEVICE) is rebuilt in place; one created from host arrays is "
+               "created again")
+_UPDATE, _REBUILD = "crt_update_vertices: ", "crt_rebuild_vertices: "
+
+
+@pytest.mark.gpu
+def test_g8_what_a_refused_update_or_rebuild_says(cr, cornell):
+    import torch
+    from caitlynrenderer_amd._lib import CRT_ERR_INVALID, CrtError
+    m0, m1 = _pair(cr, cornell)
+    built = cr.Scene(cr.SceneData.for_device_build(m0, cornell[1], "sah"), W, H, 1)
+    hosted = cr.Scene(cr.SceneData.build(m0, cornell[1]), W, H, 1)
+    nv = m1.vertices.shape[0]
+    bad = m1.vertices.copy()
+    bad[nv - 3, 2] = np.nan
+    t_good, t_bad = torch.from_numpy(m1.vertices).to("cuda"), torch.from_numpy(bad).to("cuda")
+    torch.cuda.synchronize()
+    few_normals, many_lights = m0.normals[:-1], np.concatenate([m0.lights, m0.lights])
+    cases = []
+    for who, host, device in ((_UPDATE, "update_vertices", "update_vertices_device"), (_REBUILD, "rebuild_vertices", "rebuild_vertices_device")):
+        cases += [(who + _COUNT, built, host, (m1.vertices[:-1],), {}),
+                  (who + _COUNT, built, device, (t_good.data_ptr(), nv - 1), {}),
+                  (who + _NOT_FINITE, built, host, (bad,), {}),
+                  (who + _NOT_FINITE, built, device, (t_bad.data_ptr(), nv), {}),
+                  (who + _NORMALS, built, host, (m1.vertices,), {"normals": few_normals}),
+                  (who + _LIGHTS, built, host, (m1.vertices,), {"lights": many_lights})]
+    cases += [(_REBUILD + _HOST_BUILT, hosted, "rebuild_vertices", (m1.vertices,), {}),
+              (_REBUILD + _HOST_BUILT, hosted, "rebuild_vertices_device", (t_good.data_ptr(), nv), {})]
+    for want, scene, entry, args, kw in cases:
+        with pytest.raises(CrtError) as e:
+            getattr(scene, entry)(*args, **kw)
+        assert e.value.code == CRT_ERR_INVALID and str(e.value) == f"crt error {CRT_ERR_INVALID}: {want}", (entry, str(e.value))
+    for scene in (built, hosted):                                  # a refused call is no update: there is still nothing to report
+        with pytest.raises(CrtError) as e:
+            scene.last_update_ms()
+        assert str(e.value) == f"crt error {CRT_ERR_INVALID}: crt_last_update_ms: no update yet"
+    built.close(); hosted.close()
+
+
+@pytest.mark.gpu
+def test_g8_last_update_ms_reports_the_most_recent_call_of_either_kind(cr, cornell):
+    """One timing record serves updates and rebuilds: nothing before the first call of either, then the times of the latest call, whatever
+    its kind.  A call that returns done (every form but an update with sync=False) contains its device span, and the caller's own clock
+    around the call contains the library's wall time: 0 < device <= wall <= the caller's.  A stale answer would repeat the last one."""
+    import time
+    import torch
+    from caitlynrenderer_amd._lib import CRT_ERR_INVALID, CrtError
+    m0, m1 = _pair(cr, cornell)
+    sc = cr.Scene(cr.SceneData.for_device_build(m0, cornell[1], "sah"), W, H, 1)
+    sc.render_frame(RX1, RY1)
+    assert sc.read_sum().any()
+    with pytest.raises(CrtError) as e:
+        sc.last_update_ms()
+    assert e.value.code == CRT_ERR_INVALID and "no update yet" in str(e.value)
+    t = torch.from_numpy(m0.vertices).to("cuda")
+    torch.cuda.synchronize()
+    calls = [("update", lambda: sc.update_vertices(m1.vertices)), ("rebuild", lambda: sc.rebuild_vertices(m0.vertices)),
+             ("update", lambda: sc.update_vertices(m1.vertices)), ("rebuild on the device", lambda: sc.rebuild_vertices(t)),
+             ("update, not waited for", lambda: sc.update_vertices_device(t.data_ptr(), t.shape[0], sync=False)),
+             ("rebuild", lambda: sc.rebuild_vertices(m1.vertices))]
+    seen = []
+    for kind, call in calls:
+        t0 = time.perf_counter()
+        call()
+        outer_ms = (time.perf_counter() - t0) * 1e3
+        dev_ms, wall_ms = sc.last_update_ms()
+        print(f"{kind}: device {dev_ms:.4f} ms, wall {wall_ms:.4f} ms, caller {outer_ms:.4f} ms")
+        assert dev_ms > 0.0 and 0.0 < wall_ms <= outer_ms, kind
+        if kind != "update, not waited for":
+            assert dev_ms <= wall_ms, kind
+        assert (dev_ms, wall_ms) not in seen, kind
+        assert sc.last_update_ms() == (dev_ms, wall_ms)           # asking changes nothing
+        seen.append((dev_ms, wall_ms))
+    sc.close()
+
+
 @pytest.mark.gpu
 def test_g7_scene_cost_equals_the_host_function(cr, cornell):
     m0, m1 = _pair(cr, cornell)
