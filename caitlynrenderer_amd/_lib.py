@@ -16,6 +16,8 @@ CRT_OK, CRT_ERR_INVALID, CRT_ERR_NO_DEVICE, CRT_ERR_HIP, CRT_ERR_IO, CRT_ERR_LIM
 CRT_TRACE_CLOSEST, CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_TIE_LOWEST_ID = 0, 1, 2, 4
 CRT_TRACE_INSTANCE_MASK = 8              # crt_instances_trace only: the low 8 bits of crt_ray.pad are the ray's instance mask
 CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_AOV_ALBEDO, CRT_AOV_EMISSION, CRT_AOV_ALL = 1, 2, 4, 8, 16, 31    # crt_render_aov's channels
+CRT_DENOISE_DEMODULATE = 1               # crt_denoise_params.flags
+DENOISE_DEMODULATE = CRT_DENOISE_DEMODULATE
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
 CRT_INSTANCES_UPDATABLE = 1 << 16
@@ -117,6 +119,12 @@ class crt_instances_info(C.Structure):
                 ("reserved_f", C.c_float)]
 
 
+class crt_denoise_params(C.Structure):
+    # struct crt_denoise_params (32 bytes): crt_denoise's filter settings
+    _fields_ = [("passes", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float),
+                ("normal_power_log2", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 # every symbol include/crt.h declares: name -> (restype, argtypes)
 _P, _SZ, _I, _U32, _F = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_float
 SYMBOLS = {
@@ -139,6 +147,11 @@ SYMBOLS = {
     "crt_render_aov": (_I, [_P, _F, _F, _U32, _I]),
     "crt_read_aov": (_I, [_P, _U32, _P, _SZ]),
     "crt_aov_device": (_I, [_P, _U32, C.POINTER(_P)]),
+    "crt_denoise": (_I, [_P, _F, C.POINTER(crt_denoise_params), _I]),
+    "crt_read_denoised": (_I, [_P, _P, _SZ]),
+    "crt_denoised_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_resolve_denoised": (_I, [_P, _P, _SZ]),
+    "crt_resolve_denoised_device": (_I, [_P, C.POINTER(_P), _I]),
     "crt_get_launch_times": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "crt_update_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),

@@ -21,6 +21,7 @@
 
 #include "../../include/crt.h"
 #include "crt_error.hpp"
+#include "denoise.hpp"
 #include "device_build.hpp"
 #include "host/cwbvh.hpp"
 #include "host/flatnode_link.hpp"
@@ -83,6 +84,20 @@ struct AovState {
         for (void* p : d_chan) if (p) (void)hipFree(p);
         if (d_tile_xy) (void)hipFree(d_tile_xy);
         if (d_count) (void)hipFree(d_count);
+    }
+};
+
+// What crt_denoise keeps, allocated by a scene's first call: the guide records, the two images the passes alternate
+// between, the denoised linear image and its RGBA8.  A scene that never denoises holds none of it.
+struct DenoiseState {
+    float4* d_g = nullptr;               // (unit normal, t) per pixel, constant over the passes
+    float4* d_x[2] = {nullptr, nullptr}; // (x, key) per pixel: pass i reads [i & 1] and writes the other
+    float* d_out = nullptr;              // the denoised MEAN radiance, 3 floats per pixel, linear pixel order
+    uint8_t* d_rgba = nullptr;           // crt_resolve_denoised*'s buffer, from their first call on
+    bool valid = false;                  // some crt_denoise has been enqueued
+    ~DenoiseState() {
+        void* bufs[] = {d_g, d_x[0], d_x[1], d_out, d_rgba};
+        for (void* p : bufs) if (p) (void)hipFree(p);
     }
 };
 
@@ -192,6 +207,8 @@ struct crt_scene {
     uint64_t cmask_seen = 0;             // the handle's child-mask pass this scene's stream last waited for
     SceneLights* lit = nullptr;          // lights that follow the instances; null = desc->lights alone, as before
     AovState* aov = nullptr;             // crt_render_aov's buffers, from the first call on
+    DenoiseState* denoise = nullptr;     // crt_denoise's buffers, from the first call on
+    uint32_t denoise_form = 0;           // option "denoise_form": 0 = each pass in the form measured faster at its tap spacing, 1 = staged, 2 = direct
 
     // shard + frame buffers
     uint32_t rank = 0, world = 1, tile = 16;   // 16x16: four waves per tile — fine enough for the cost-sorted schedule (1 M triangles: 0.273 ms at 64, 0.257 at 16)
@@ -377,6 +394,7 @@ struct crt_scene {
         delete intake;
         delete lit;
         delete aov;
+        delete denoise;
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
@@ -723,7 +741,7 @@ struct Warmer {
     static int load_all() {
         int e;
         if ((e = crt::warm_rt_kernels()) || (e = crt::warm_lbvh_kernels()) || (e = crt::warm_cwbvh_kernels()) || (e = crt::warm_scene_build_kernels()) ||
-            (e = crt::warm_instance_kernels())) return e;
+            (e = crt::warm_instance_kernels()) || (e = crt::warm_denoise_kernels())) return e;
         return 0;
     }
     void start(int device) {                       // returns at once
@@ -1503,6 +1521,10 @@ int crt_set_option(crt_scene* s, const char* name, int value) {
     else if (!std::strcmp(name, "ray_bins")) s->ray_bins = (uint32_t)std::min(5, std::max(0, value));
     else if (!std::strcmp(name, "last_build")) s->last_build = value ? 1u : 0u;
     else if (!std::strcmp(name, "lean_build")) s->lean_build = value ? 1u : 0u;
+    else if (!std::strcmp(name, "denoise_form")) {
+        if (value < 0 || value > 2) return fail(CRT_ERR_INVALID, "crt_set_option: denoise_form is 0 (per tap spacing), 1 (staged) or 2 (direct)");
+        s->denoise_form = (uint32_t)value;
+    }
     else if (!std::strcmp(name, "debug_fail_batch_alloc")) {
         // one injected failure, on ONE device: 1 = this scene's own, k >= 2 = its (k - 1)-th peer (streams / crt_set_devices); 0 disarms all
         if (value >= 2 && (size_t)(value - 2) < s->peers.size()) s->peers[(size_t)(value - 2)]->debug_fail_batch_alloc = 1u;
@@ -2825,6 +2847,147 @@ int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr) {
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipStreamSynchronize(s->stream));
     *d_ptr = d;
+    return CRT_OK;
+}
+
+// ---------------------------------------------------------------- crt_denoise --
+// An edge-avoiding a-trous filter over the un-tiled sum, guided by the feature buffers (kernels in denoise.hip): enqueued
+// on the scene's stream behind whatever frames and crt_render_aov calls are queued there.  It reads the sum and four AOV channels and
+// writes only DenoiseState's buffers (and d_linear, which every crt_read_sum / crt_sum_device writes anew).
+
+int crt_denoise(crt_scene* s, float inv_count, const crt_denoise_params* params, int sync) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_denoise: null scene");
+    crt_denoise_params p{};
+    if (params) p = *params;
+    else { p.passes = 5; p.flags = CRT_DENOISE_DEMODULATE; p.sigma_color = 4.0f; p.sigma_depth = 0.05f; p.normal_power_log2 = 7; }
+    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return fail(CRT_ERR_INVALID, "crt_denoise: inv_count must be finite and > 0");
+    if (p.passes < 1u || p.passes > 6u) return fail(CRT_ERR_INVALID, "crt_denoise: passes must be 1..6");
+    if (p.flags & ~(uint32_t)CRT_DENOISE_DEMODULATE) return fail(CRT_ERR_INVALID, "crt_denoise: unknown flag bits");
+    if (p.reserved[0] | p.reserved[1] | p.reserved[2]) return fail(CRT_ERR_INVALID, "crt_denoise: reserved words must be 0");
+    if (p.sigma_color != 0.f && !(std::isfinite(p.sigma_color) && p.sigma_color >= 1e-6f && p.sigma_color <= 1e6f))
+        return fail(CRT_ERR_INVALID, "crt_denoise: sigma_color must be 0 (no colour term) or finite and in [1e-6, 1e6]");
+    if (!(std::isfinite(p.sigma_depth) && p.sigma_depth >= 1e-6f && p.sigma_depth <= 1e6f))
+        return fail(CRT_ERR_INVALID, "crt_denoise: sigma_depth must be finite and in [1e-6, 1e6]");
+    if (p.normal_power_log2 > 10u) return fail(CRT_ERR_INVALID, "crt_denoise: normal_power_log2 must be 0..10");
+    const uint32_t need = CRT_AOV_HIT | CRT_AOV_IDS | CRT_AOV_NORMAL | CRT_AOV_ALBEDO;
+    if (!s->aov || (s->aov->rendered & need) != need)
+        return fail(CRT_ERR_INVALID, "crt_denoise: crt_render_aov must have rendered the HIT, IDS, NORMAL and ALBEDO channels");
+    if (s->shard_world > 1u) return fail(CRT_ERR_INVALID, "crt_denoise: a shard of a frame (crt_set_shard with world > 1) lacks its neighbours' pixels");
+    if (s->primary || (!s->peers.empty() && s->streams <= 1u))
+        return fail(CRT_ERR_INVALID, "crt_denoise: a scene on one device only (crt_set_devices has dealt this one's tiles to several)");
+    int rc = require_device();
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t n_pixels = (size_t)s->width * s->height;
+    if (n_pixels >= (1ull << 31) / 3u) return fail(CRT_ERR_LIMIT, "crt_denoise: frame too large for 32-bit indices");
+    if ((rc = ensure_frame(s))) return rc;
+    if (!s->denoise) {
+        s->denoise = new (std::nothrow) DenoiseState;
+        if (!s->denoise) return fail(CRT_ERR_NOMEM, "crt_denoise: out of host memory");
+    }
+    DenoiseState* const dn = s->denoise;
+    if (!dn->d_g && (rc = dev_alloc(&dn->d_g, n_pixels))) return rc;
+    if (!dn->d_x[0] && (rc = dev_alloc(&dn->d_x[0], n_pixels))) return rc;
+    if (!dn->d_x[1] && (rc = dev_alloc(&dn->d_x[1], n_pixels))) return rc;
+    if (!dn->d_out && (rc = dev_alloc(&dn->d_out, 3 * n_pixels))) return rc;
+    if ((rc = untile_to_linear(s))) return rc;
+    const uint32_t demodulate = (p.flags & CRT_DENOISE_DEMODULATE) ? 1u : 0u;
+    crt::DenoisePrepareArgs pa{};
+    pa.sum = s->d_linear;
+    pa.hit = static_cast<const float4*>(s->aov->d_chan[0]); pa.ids = static_cast<const int4*>(s->aov->d_chan[1]);
+    pa.normal = static_cast<const float4*>(s->aov->d_chan[2]); pa.albedo = static_cast<const float4*>(s->aov->d_chan[3]);
+    pa.g = dn->d_g; pa.x = dn->d_x[0];
+    pa.n_pixels = (uint32_t)n_pixels; pa.inv_count = inv_count; pa.demodulate = demodulate;
+    crt::launch_denoise_prepare(pa, s->stream);
+    float sigma = p.sigma_color;
+    for (uint32_t i = 0; i < p.passes; ++i) {
+        crt::DenoisePassArgs a{};
+        a.g = dn->d_g; a.x_in = dn->d_x[i & 1u]; a.x_out = dn->d_x[(i & 1u) ^ 1u]; a.out = dn->d_out; a.albedo = pa.albedo;
+        a.width = s->width; a.height = s->height; a.step_log2 = i;
+        a.use_color = p.sigma_color != 0.f ? 1u : 0u;
+        a.inv_c = a.use_color ? 1.0f / (sigma * sigma) : 0.f;
+        a.sigma_depth = p.sigma_depth;
+        a.normal_squarings = p.normal_power_log2;
+        a.demodulate = demodulate;
+        crt::launch_denoise_pass(a, i + 1u == p.passes, s->denoise_form, s->stream);
+        sigma = sigma * 0.5f;
+    }
+    HIPCHK(hipGetLastError());
+    dn->valid = true;
+    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+static int denoised_of(crt_scene* s, const char* who) {
+    if (!s->denoise || !s->denoise->valid) return fail(CRT_ERR_INVALID, std::string(who) + ": no crt_denoise call has succeeded on this scene");
+    return CRT_OK;
+}
+
+int crt_read_denoised(crt_scene* s, float* rgb, size_t n_floats) {
+    if (!s || !rgb) return fail(CRT_ERR_INVALID, "crt_read_denoised: null argument");
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = denoised_of(s, "crt_read_denoised"))) return rc;
+    if (n_floats != 3 * (size_t)s->width * s->height) return fail(CRT_ERR_INVALID, "crt_read_denoised: n_floats must be width*height*3");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemcpyAsync(rgb, s->denoise->d_out, n_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_denoised_device(crt_scene* s, const float** d_rgb) {
+    if (!s || !d_rgb) return fail(CRT_ERR_INVALID, "crt_denoised_device: null argument");
+    *d_rgb = nullptr;
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = denoised_of(s, "crt_denoised_device"))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    *d_rgb = s->denoise->d_out;
+    return CRT_OK;
+}
+
+// the denoised image through crt_resolve's tone map and pinned gamma, into DenoiseState's own RGBA8: crt_resolve_device's stays as it is
+static int resolve_denoised_to_device(crt_scene* s) {
+    DenoiseState* const dn = s->denoise;
+    const size_t npx = (size_t)s->width * s->height;
+    int rc;
+    if (!dn->d_rgba && (rc = dev_alloc(&dn->d_rgba, 4 * npx))) return rc;
+    if (!s->d_gamma) {
+        if ((rc = dev_alloc(&s->d_gamma, 256))) return rc;
+        HIPCHK(hipMemcpy(s->d_gamma, gamma_thresholds(), 256 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    crt::launch_resolve(dn->d_out, (uint32_t)npx, 1.0f, s->d_gamma, dn->d_rgba, s->flat_grid((uint32_t)npx), s->stream);
+    HIPCHK(hipGetLastError());
+    return CRT_OK;
+}
+
+int crt_resolve_denoised(crt_scene* s, uint8_t* rgba, size_t n_bytes) {
+    if (!s || !rgba) return fail(CRT_ERR_INVALID, "crt_resolve_denoised: null argument");
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = denoised_of(s, "crt_resolve_denoised"))) return rc;
+    const size_t npx = (size_t)s->width * s->height;
+    if (n_bytes != 4 * npx) return fail(CRT_ERR_INVALID, "crt_resolve_denoised: n_bytes must be width*height*4");
+    HIPCHK(hipSetDevice(s->device));
+    if ((rc = resolve_denoised_to_device(s))) return rc;
+    if (!s->h_rgba) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_rgba), 4 * npx));
+    HIPCHK(hipMemcpyAsync(s->h_rgba, s->denoise->d_rgba, n_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    std::memcpy(rgba, s->h_rgba, n_bytes);
+    return CRT_OK;
+}
+
+int crt_resolve_denoised_device(crt_scene* s, const uint8_t** d_rgba, int sync) {
+    if (!s || !d_rgba) return fail(CRT_ERR_INVALID, "crt_resolve_denoised_device: null argument");
+    *d_rgba = nullptr;
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = denoised_of(s, "crt_resolve_denoised_device"))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    if ((rc = resolve_denoised_to_device(s))) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
+    *d_rgba = s->denoise->d_rgba;
     return CRT_OK;
 }
 

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CRT_ABI_VERSION, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_frame_stats,
+from ._lib import (CRT_ABI_VERSION, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats,
                    crt_scene_desc, crt_tree_cost, lib)
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _cost_dict, _ptr
 
@@ -191,6 +191,41 @@ class Scene:
         ptr = C.c_void_p()
         check(lib().crt_aov_device(self._h, int(channel), C.byref(ptr)))
         return ptr.value
+
+    def denoise(self, inv_count=None, passes=5, demodulate=True, sigma_color=4.0, sigma_depth=0.05, normal_power_log2=7, sync=True):
+        """crt_denoise: an edge-avoiding a-trous filter over the running sum, guided by the HIT, IDS, NORMAL and ALBEDO channels of the most
+        recent render_aov (the caller keeps them in step with the view and the geometry).  inv_count None = 1 / max(frame_count, 1), as in
+        resolve.  Touches nothing a frame reads or reports, no AOV channel and not resolve_device's buffer."""
+        if inv_count is None:
+            inv_count = 1.0 / max(self.frame_count, 1)
+        p = crt_denoise_params()
+        p.passes, p.flags = int(passes), (CRT_DENOISE_DEMODULATE if demodulate else 0)
+        p.sigma_color, p.sigma_depth, p.normal_power_log2 = float(np.float32(sigma_color)), float(np.float32(sigma_depth)), int(normal_power_log2)
+        check(lib().crt_denoise(self._h, float(np.float32(inv_count)), C.byref(p), 1 if sync else 0))
+
+    def read_denoised(self):
+        """crt_read_denoised: the denoised MEAN radiance, (height, width, 3) float32, rows as read_sum has them"""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(lib().crt_read_denoised(self._h, _ptr(out), out.size))
+        return out
+
+    def denoised_device(self):
+        """crt_denoised_device: device pointer (int) of the denoised image, width * height * 3 floats, valid until the scene is closed"""
+        ptr = C.c_void_p()
+        check(lib().crt_denoised_device(self._h, C.byref(ptr)))
+        return ptr.value
+
+    def resolve_denoised(self):
+        """crt_resolve_denoised: resolve's tone map and pinned gamma on the denoised image, (height, width, 4) uint8"""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        check(lib().crt_resolve_denoised(self._h, _ptr(out), out.size))
+        return out
+
+    def resolve_denoised_device(self, sync=True):
+        """crt_resolve_denoised_device: the same RGBA8 left in device memory, in a buffer of its own; returns the device pointer"""
+        p = C.c_void_p()
+        check(lib().crt_resolve_denoised_device(self._h, C.byref(p), 1 if sync else 0))
+        return p.value
 
     def launch_times(self):
         """crt_get_launch_times: ms of every event-carrying launch since the spans were restarted (options timing / timing_accumulate)"""

@@ -236,6 +236,9 @@ int crt_sync(crt_scene* s);
  *                         the overflow check), "tri_min" 2 and "lanes_per_ray" 8, no frame of tile-cost measurement —
  *                         with the RNG's sine in a form of fewer double-precision-rate instructions and the same bits (DESIGN.md
  *                         section 5; profiles/r07_experiments.md); 0 = the build without it.  The same sums either way.
+ *     "denoise_form"      0 (default), 1 or 2: which form of its pass kernel crt_denoise runs: 0 = at each tap spacing the one measured
+ *                         faster there, 1 = the taps staged in LDS, 2 = the taps read from global memory, at every
+ *                         spacing.  The same bytes either way.
  *     "streams"           1 (default) .. 4, or 0 = pick for me (3 for scenes of a few nodes, 2 for max_depth > 1, else 1): that many tile shards of the frame rendered side by side on streams of their own on this one GPU
  *                         (own queues and path state, the scene buffers shared).  A multi-segment frame is a chain of dependent
  *                         launches; another shard's launches fill their tails: 1 M triangles, 4 segments, 2 streams +6 %, 8 M triangles
@@ -311,6 +314,45 @@ enum { CRT_AOV_HIT = 1, CRT_AOV_IDS = 2, CRT_AOV_NORMAL = 4, CRT_AOV_ALBEDO = 8,
 int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync);
 int crt_read_aov(crt_scene* s, uint32_t channel, void* dst, size_t n_bytes);
 int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr);
+
+/* Denoise a low-sample frame on the device, guided by the feature buffers (no reference counterpart): an edge-avoiding
+ * a-trous wavelet filter over the scene's running sum, flat and instanced scenes.  Inputs: the sum, un-tiled as crt_sum_device has it and
+ * scaled by inv_count, and the channels HIT, IDS, NORMAL and ALBEDO as the most recent crt_render_aov left them.  Keeping those channels in
+ * step with the view and the geometry is the CALLER's duty, as inv_count already is: after a camera change, a refit or an instance move,
+ * call crt_render_aov again before crt_denoise.  `passes` passes of a 5 x 5 B3-spline kernel, tap spacing 2^i in pass i; a tap counts by
+ * the normals' cosine raised to 2^normal_power_log2, by its depth difference against sigma_depth * t * (tap distance), by its colour
+ * difference against sigma_color / 2^i (0 = no colour term), and not at all across instances, misses, emitters seen directly or
+ * degenerate normals: such pixels keep their own mean.  CRT_DENOISE_DEMODULATE filters radiance / max(albedo, 1e-3) and multiplies the
+ * albedo back, so texture detail passes through.  Every step is one IEEE float32 operation in a fixed order: DESIGN.md §22 is the
+ * definition, and the result is the same bytes on every build.  Non-finite radiance in the sum gives unspecified values in the pixels
+ * whose taps reach it.
+ * crt_denoise is enqueued on the scene's stream behind any *_async frames and crt_render_aov calls (sync = 0 returns at once; crt_sync, the
+ * read calls below and later frames are ordered behind it).  It leaves the sum, the frame count, crt_get_frame_stats, the launch times,
+ * every AOV channel, every frame's path and RNG state and crt_resolve_device's buffer as they are.  It does rewrite the un-tiled sum that
+ * crt_sum_device's pointer names, as every crt_read_sum / crt_sum_device does: that array then holds the sum as of this call.  Its own
+ * buffers are allocated by a scene's first crt_denoise and freed with the scene.  params NULL = {5, CRT_DENOISE_DEMODULATE, 4.0f, 0.05f, 7}.
+ * crt_read_denoised: width*height*3 floats, rows as crt_read_sum has them, MEAN radiance (not a sum).  crt_denoised_device waits for the
+ * stream and leaves that image on the device; the pointer stays valid until the scene is destroyed.  crt_resolve_denoised /
+ * crt_resolve_denoised_device: crt_resolve's tone map and pinned gamma on that image (inv_count 1), the latter into a buffer of its own:
+ * crt_resolve_device's pointer and bytes stay valid.
+ * CRT_ERR_INVALID, nothing written: null scene; inv_count not finite or <= 0; passes outside 1..6; unknown flag bits; non-zero reserved;
+ * a sigma outside its range or not finite; normal_power_log2 > 10; one of the four channels never rendered; a shard of a frame
+ * (crt_set_shard with world > 1) or a scene on several devices (a filter needs its neighbours); a read, device or resolve call before any
+ * successful crt_denoise, or with a wrong size. */
+enum { CRT_DENOISE_DEMODULATE = 1 };
+typedef struct crt_denoise_params {      /* 32 bytes */
+    uint32_t passes;             /* 1..6; pass i (from 0) has tap spacing s = 2^i */
+    uint32_t flags;              /* CRT_DENOISE_DEMODULATE or 0; other bits refused */
+    float    sigma_color;        /* 0 = no colour term; else finite, in [1e-6, 1e6]; halves every pass */
+    float    sigma_depth;        /* finite, in [1e-6, 1e6] */
+    uint32_t normal_power_log2;  /* 0..10: normal weight = max(0, dot of the unit normals)^(2^k) by k squarings */
+    uint32_t reserved[3];        /* must be 0 */
+} crt_denoise_params;
+int crt_denoise(crt_scene* s, float inv_count, const crt_denoise_params* p, int sync);
+int crt_read_denoised(crt_scene* s, float* rgb, size_t n_floats);
+int crt_denoised_device(crt_scene* s, const float** d_rgb);
+int crt_resolve_denoised(crt_scene* s, uint8_t* rgba, size_t n_bytes);
+int crt_resolve_denoised_device(crt_scene* s, const uint8_t** d_rgba, int sync);
 
 /* Animated geometry (no reference counterpart: the reference uploads its scene once, Scene.h:1000-1062; DXR / OptiX call this an
  * update build).  New positions for the scene's vertices; triangles, materials, textures and the tree topology are unchanged.
