@@ -18,6 +18,8 @@ CRT_TRACE_INSTANCE_MASK = 8              # crt_instances_trace only: the low 8 b
 CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_AOV_ALBEDO, CRT_AOV_EMISSION, CRT_AOV_ALL = 1, 2, 4, 8, 16, 31    # crt_render_aov's channels
 CRT_DENOISE_DEMODULATE = 1               # crt_denoise_params.flags
 DENOISE_DEMODULATE = CRT_DENOISE_DEMODULATE
+CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_CLAMP = 1, 2                       # crt_temporal_params.flags
+CRT_TEMPORAL_SOURCE_SUM, CRT_TEMPORAL_SOURCE_DENOISED = 0, 1             # crt_temporal_params.source
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
 CRT_INSTANCES_UPDATABLE = 1 << 16
@@ -125,6 +127,12 @@ class crt_denoise_params(C.Structure):
                 ("normal_power_log2", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class crt_temporal_params(C.Structure):
+    # struct crt_temporal_params (32 bytes): crt_temporal's settings
+    _fields_ = [("flags", C.c_uint32), ("source", C.c_uint32), ("max_history", C.c_uint32), ("sigma_depth", C.c_float),
+                ("normal_min", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
 # every symbol include/crt.h declares: name -> (restype, argtypes)
 _P, _SZ, _I, _U32, _F = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_float
 SYMBOLS = {
@@ -152,6 +160,13 @@ SYMBOLS = {
     "crt_denoised_device": (_I, [_P, C.POINTER(_P)]),
     "crt_resolve_denoised": (_I, [_P, _P, _SZ]),
     "crt_resolve_denoised_device": (_I, [_P, C.POINTER(_P), _I]),
+    "crt_temporal": (_I, [_P, _F, C.POINTER(crt_temporal_params), _I]),
+    "crt_temporal_reset": (_I, [_P]),
+    "crt_read_temporal": (_I, [_P, _P, _SZ]),
+    "crt_read_temporal_history": (_I, [_P, _P, _SZ]),
+    "crt_temporal_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_resolve_temporal": (_I, [_P, _P, _SZ]),
+    "crt_resolve_temporal_device": (_I, [_P, C.POINTER(_P), _I]),
     "crt_get_launch_times": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "crt_update_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),

@@ -29,6 +29,7 @@
 #include "instances.hpp"
 #include "instances_bind.hpp"
 #include "rt_kernels.hpp"
+#include "temporal.hpp"
 
 using crt::dev_alloc;
 using crt::fail;
@@ -97,6 +98,27 @@ struct DenoiseState {
     bool valid = false;                  // some crt_denoise has been enqueued
     ~DenoiseState() {
         void* bufs[] = {d_g, d_x[0], d_x[1], d_out, d_rgba};
+        for (void* p : bufs) if (p) (void)hipFree(p);
+    }
+};
+
+// What crt_temporal keeps, allocated by a scene's first call: two sets of (history, guide, key) that the calls alternate
+// between, the accumulated linear image and its RGBA8, the previous call's view and, for an instanced scene, its object_to_world.
+struct TemporalState {
+    float4* d_hist[2] = {nullptr, nullptr};      // (y, N) per pixel: a call reads [cur] and writes the other
+    float4* d_guide[2] = {nullptr, nullptr};     // (unit normal, t) per pixel
+    uint32_t* d_key[2] = {nullptr, nullptr};     // instance + 1, 0 for a pixel that is not filterable
+    float* d_out = nullptr;                      // the accumulated MEAN radiance, 3 floats per pixel, linear pixel order
+    uint8_t* d_rgba = nullptr;                   // crt_resolve_temporal*'s buffer
+    float* d_o2w_prev = nullptr;                 // an instanced scene: object_to_world as of the previous call (capacity x 12)
+    uint32_t n_prev_instances = 0;
+    uint32_t cur = 0;                            // the set the most recent call wrote
+    crt::TemporalView prev_view{};               // the view of the most recent call
+    uint32_t demodulate = 0;                     // the DEMODULATE bit of the most recent call: what the history holds
+    bool have_history = false;                   // false until a call succeeds, and after crt_temporal_reset
+    bool valid = false;                          // some crt_temporal has been enqueued
+    ~TemporalState() {
+        void* bufs[] = {d_hist[0], d_hist[1], d_guide[0], d_guide[1], d_key[0], d_key[1], d_out, d_rgba, d_o2w_prev};
         for (void* p : bufs) if (p) (void)hipFree(p);
     }
 };
@@ -208,6 +230,10 @@ struct crt_scene {
     SceneLights* lit = nullptr;          // lights that follow the instances; null = desc->lights alone, as before
     AovState* aov = nullptr;             // crt_render_aov's buffers, from the first call on
     DenoiseState* denoise = nullptr;     // crt_denoise's buffers, from the first call on
+    TemporalState* temporal = nullptr;   // crt_temporal's buffers, from the first call on
+    uint32_t temporal_form = 0;          // option "temporal_form": how a CLAMP call reads its neighbourhood: 0 = the form measured faster, 1 = staged, 2 = direct
+    crt::TemporalView aov_view{};        // the view of the most recent crt_render_aov that rendered HIT, recorded at enqueue: crt_temporal's current view
+    bool have_aov_view = false;
     uint32_t denoise_form = 0;           // option "denoise_form": 0 = each pass in the form measured faster at its tap spacing, 1 = staged, 2 = direct
 
     // shard + frame buffers
@@ -395,6 +421,7 @@ struct crt_scene {
         delete lit;
         delete aov;
         delete denoise;
+        delete temporal;
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
@@ -741,7 +768,7 @@ struct Warmer {
     static int load_all() {
         int e;
         if ((e = crt::warm_rt_kernels()) || (e = crt::warm_lbvh_kernels()) || (e = crt::warm_cwbvh_kernels()) || (e = crt::warm_scene_build_kernels()) ||
-            (e = crt::warm_instance_kernels()) || (e = crt::warm_denoise_kernels())) return e;
+            (e = crt::warm_instance_kernels()) || (e = crt::warm_denoise_kernels()) || (e = crt::warm_temporal_kernels())) return e;
         return 0;
     }
     void start(int device) {                       // returns at once
@@ -1524,6 +1551,10 @@ int crt_set_option(crt_scene* s, const char* name, int value) {
     else if (!std::strcmp(name, "denoise_form")) {
         if (value < 0 || value > 2) return fail(CRT_ERR_INVALID, "crt_set_option: denoise_form is 0 (per tap spacing), 1 (staged) or 2 (direct)");
         s->denoise_form = (uint32_t)value;
+    }
+    else if (!std::strcmp(name, "temporal_form")) {
+        if (value < 0 || value > 2) return fail(CRT_ERR_INVALID, "crt_set_option: temporal_form is 0 (as measured), 1 (staged) or 2 (direct)");
+        s->temporal_form = (uint32_t)value;
     }
     else if (!std::strcmp(name, "debug_fail_batch_alloc")) {
         // one injected failure, on ONE device: 1 = this scene's own, k >= 2 = its (k - 1)-th peer (streams / crt_set_devices); 0 disarms all
@@ -2814,6 +2845,15 @@ int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync
     HIPCHK(hipGetLastError());
     av->rendered |= channels;
     av->last = channels;
+    if (channels & CRT_AOV_HIT) {                                         // the view crt_temporal reprojects from
+        const crt::FrameArgs f = frame_args(s, rx, ry);
+        for (int k = 0; k < 3; ++k) {
+            s->aov_view.pos[k] = f.cam_pos[k]; s->aov_view.right[k] = f.cam_right[k];
+            s->aov_view.up[k] = f.cam_up[k]; s->aov_view.fwd[k] = f.cam_forward[k];
+        }
+        s->aov_view.aspect_tan = f.aspect_tan; s->aov_view.tan_fov = f.tan_fov; s->aov_view.rv = f.rv; s->aov_view.jitter = f.jitter;
+        s->have_aov_view = true;
+    }
     if (sync) HIPCHK(hipStreamSynchronize(s->stream));
     return CRT_OK;
 }
@@ -2988,6 +3028,188 @@ int crt_resolve_denoised_device(crt_scene* s, const uint8_t** d_rgba, int sync) 
     if ((rc = resolve_denoised_to_device(s))) return rc;
     if (sync) HIPCHK(hipStreamSynchronize(s->stream));
     *d_rgba = s->denoise->d_rgba;
+    return CRT_OK;
+}
+
+// ---------------------------------------------------------------- crt_temporal --
+// Temporal accumulation by reprojection (kernel in temporal.hip): enqueued on the scene's stream behind whatever frames,
+// crt_render_aov and crt_denoise calls are queued there.  It reads the source image, four AOV channels, its own previous set and an
+// instanced scene's live transforms, and writes only TemporalState's buffers (and d_linear, which every crt_read_sum / crt_sum_device
+// writes anew).  crt_reset never comes here: the history outlives the sum.
+
+int crt_temporal(crt_scene* s, float inv_count, const crt_temporal_params* params, int sync) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_temporal: null scene");
+    crt_temporal_params p{};
+    if (params) p = *params;
+    else { p.flags = CRT_TEMPORAL_DEMODULATE; p.source = CRT_TEMPORAL_SOURCE_SUM; p.max_history = 32; p.sigma_depth = 0.1f; p.normal_min = 0.9f; }
+    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return fail(CRT_ERR_INVALID, "crt_temporal: inv_count must be finite and > 0");
+    if (p.flags & ~(uint32_t)(CRT_TEMPORAL_DEMODULATE | CRT_TEMPORAL_CLAMP)) return fail(CRT_ERR_INVALID, "crt_temporal: unknown flag bits");
+    if (p.source > (uint32_t)CRT_TEMPORAL_SOURCE_DENOISED) return fail(CRT_ERR_INVALID, "crt_temporal: source is CRT_TEMPORAL_SOURCE_SUM or CRT_TEMPORAL_SOURCE_DENOISED");
+    if (p.max_history < 1u || p.max_history > 4096u) return fail(CRT_ERR_INVALID, "crt_temporal: max_history must be 1..4096");
+    if (!(std::isfinite(p.sigma_depth) && p.sigma_depth >= 1e-6f && p.sigma_depth <= 1e6f))
+        return fail(CRT_ERR_INVALID, "crt_temporal: sigma_depth must be finite and in [1e-6, 1e6]");
+    if (!(std::isfinite(p.normal_min) && p.normal_min >= -1.0f && p.normal_min <= 1.0f))
+        return fail(CRT_ERR_INVALID, "crt_temporal: normal_min must be finite and in [-1, 1]");
+    if (p.reserved[0] | p.reserved[1] | p.reserved[2]) return fail(CRT_ERR_INVALID, "crt_temporal: reserved words must be 0");
+    const uint32_t demodulate = (p.flags & CRT_TEMPORAL_DEMODULATE) ? 1u : 0u;
+    const uint32_t need = CRT_AOV_HIT | CRT_AOV_IDS | CRT_AOV_NORMAL | (demodulate ? (uint32_t)CRT_AOV_ALBEDO : 0u);
+    if (!s->aov || (s->aov->rendered & need) != need || !s->have_aov_view)
+        return fail(CRT_ERR_INVALID, "crt_temporal: crt_render_aov must have rendered the HIT, IDS and NORMAL channels, and ALBEDO for CRT_TEMPORAL_DEMODULATE");
+    if (p.source == CRT_TEMPORAL_SOURCE_DENOISED && (!s->denoise || !s->denoise->valid))
+        return fail(CRT_ERR_INVALID, "crt_temporal: source CRT_TEMPORAL_SOURCE_DENOISED needs a successful crt_denoise");
+    if (s->shard_world > 1u) return fail(CRT_ERR_INVALID, "crt_temporal: a shard of a frame (crt_set_shard with world > 1) lacks the rest of the previous frame");
+    if (s->primary || (!s->peers.empty() && s->streams <= 1u))
+        return fail(CRT_ERR_INVALID, "crt_temporal: a scene on one device only (crt_set_devices has dealt this one's tiles to several)");
+    int rc = require_device();
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    const size_t n_pixels = (size_t)s->width * s->height;
+    if (n_pixels >= (1ull << 31) / 3u) return fail(CRT_ERR_LIMIT, "crt_temporal: frame too large for 32-bit indices");
+    if ((rc = ensure_frame(s))) return rc;
+    if (!s->temporal) {
+        s->temporal = new (std::nothrow) TemporalState;
+        if (!s->temporal) return fail(CRT_ERR_NOMEM, "crt_temporal: out of host memory");
+    }
+    TemporalState* const ts = s->temporal;
+    for (int k = 0; k < 2; ++k) {
+        if (!ts->d_hist[k] && (rc = dev_alloc(&ts->d_hist[k], n_pixels))) return rc;
+        if (!ts->d_guide[k] && (rc = dev_alloc(&ts->d_guide[k], n_pixels))) return rc;
+        if (!ts->d_key[k] && (rc = dev_alloc(&ts->d_key[k], n_pixels))) return rc;
+    }
+    if (!ts->d_out && (rc = dev_alloc(&ts->d_out, 3 * n_pixels))) return rc;
+    if (!ts->d_rgba && (rc = dev_alloc(&ts->d_rgba, 4 * n_pixels))) return rc;
+    if (!s->d_gamma) {
+        if ((rc = dev_alloc(&s->d_gamma, 256))) return rc;
+        HIPCHK(hipMemcpy(s->d_gamma, gamma_thresholds(), 256 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    crt::InstancesView v{};
+    if (s->inst) {
+        crt::instances_view(s->inst, &v);                                 // the live arrays, read at enqueue as a frame reads them
+        if (!ts->d_o2w_prev && (rc = dev_alloc(&ts->d_o2w_prev, 12 * (size_t)std::max(v.capacity, 1u)))) return rc;
+    }
+    crt::TemporalArgs a{};
+    if (p.source == CRT_TEMPORAL_SOURCE_SUM) {
+        if ((rc = untile_to_linear(s))) return rc;
+        a.src = s->d_linear; a.scale_source = 1u;
+    } else {
+        a.src = s->denoise->d_out; a.scale_source = 0u;
+    }
+    const uint32_t from = ts->cur, to = ts->cur ^ 1u;
+    a.hit = static_cast<const float4*>(s->aov->d_chan[0]); a.ids = static_cast<const int4*>(s->aov->d_chan[1]);
+    a.normal = static_cast<const float4*>(s->aov->d_chan[2]); a.albedo = static_cast<const float4*>(s->aov->d_chan[3]);
+    a.hist_in = ts->d_hist[from]; a.guide_in = ts->d_guide[from]; a.key_in = ts->d_key[from];
+    a.hist_out = ts->d_hist[to]; a.guide_out = ts->d_guide[to]; a.key_out = ts->d_key[to];
+    a.out = ts->d_out;
+    if (s->inst) {
+        a.o2w = v.o2w; a.w2o = v.w2o; a.o2w_prev = ts->d_o2w_prev;
+        a.n_instances = v.n_instances; a.n_prev_instances = ts->n_prev_instances;
+    }
+    a.width = s->width; a.height = s->height;
+    a.inv_count = inv_count;
+    a.demodulate = demodulate; a.clamp = (p.flags & CRT_TEMPORAL_CLAMP) ? 1u : 0u;
+    // history-less: the first call, after crt_temporal_reset, after a change of the DEMODULATE bit (the history holds the other quantity),
+    // and at max_history 1, where the definition takes y = x
+    a.has_history = (ts->have_history && ts->demodulate == demodulate && p.max_history > 1u) ? 1u : 0u;
+    a.max_history = (float)p.max_history; a.sigma_depth = p.sigma_depth; a.normal_min = p.normal_min;
+    a.cur = s->aov_view; a.prev = ts->prev_view;
+    crt::launch_temporal(a, s->temporal_form, s->stream);
+    HIPCHK(hipGetLastError());
+    if (s->inst && v.n_instances) HIPCHK(hipMemcpyAsync(ts->d_o2w_prev, v.o2w, (size_t)v.n_instances * 48, hipMemcpyDeviceToDevice, s->stream));
+    ts->n_prev_instances = s->inst ? v.n_instances : 0u;
+    ts->cur = to;
+    ts->prev_view = s->aov_view;
+    ts->demodulate = demodulate;
+    ts->have_history = true;
+    ts->valid = true;
+    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_temporal_reset(crt_scene* s) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_temporal_reset: null scene");
+    if (s->temporal) s->temporal->have_history = false;
+    return CRT_OK;
+}
+
+static int temporal_of(crt_scene* s, const char* who) {
+    if (!s->temporal || !s->temporal->valid) return fail(CRT_ERR_INVALID, std::string(who) + ": no crt_temporal call has succeeded on this scene");
+    return CRT_OK;
+}
+
+int crt_read_temporal(crt_scene* s, float* rgb, size_t n_floats) {
+    if (!s || !rgb) return fail(CRT_ERR_INVALID, "crt_read_temporal: null argument");
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = temporal_of(s, "crt_read_temporal"))) return rc;
+    if (n_floats != 3 * (size_t)s->width * s->height) return fail(CRT_ERR_INVALID, "crt_read_temporal: n_floats must be width*height*3");
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemcpyAsync(rgb, s->temporal->d_out, n_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_read_temporal_history(crt_scene* s, float* n, size_t n_floats) {
+    if (!s || !n) return fail(CRT_ERR_INVALID, "crt_read_temporal_history: null argument");
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = temporal_of(s, "crt_read_temporal_history"))) return rc;
+    const size_t npx = (size_t)s->width * s->height;
+    if (n_floats != npx) return fail(CRT_ERR_INVALID, "crt_read_temporal_history: n_floats must be width*height");
+    HIPCHK(hipSetDevice(s->device));
+    std::vector<float4> hist;
+    try { hist.resize(npx); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_read_temporal_history: out of host memory"); }
+    HIPCHK(hipMemcpyAsync(hist.data(), s->temporal->d_hist[s->temporal->cur], npx * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    for (size_t i = 0; i < npx; ++i) n[i] = hist[i].w;
+    return CRT_OK;
+}
+
+int crt_temporal_device(crt_scene* s, const float** d_rgb) {
+    if (!s || !d_rgb) return fail(CRT_ERR_INVALID, "crt_temporal_device: null argument");
+    *d_rgb = nullptr;
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = temporal_of(s, "crt_temporal_device"))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    *d_rgb = s->temporal->d_out;
+    return CRT_OK;
+}
+
+// the accumulated image through crt_resolve's tone map and pinned gamma, into TemporalState's own RGBA8
+static int resolve_temporal_to_device(crt_scene* s) {
+    const size_t npx = (size_t)s->width * s->height;
+    crt::launch_resolve(s->temporal->d_out, (uint32_t)npx, 1.0f, s->d_gamma, s->temporal->d_rgba, s->flat_grid((uint32_t)npx), s->stream);
+    HIPCHK(hipGetLastError());
+    return CRT_OK;
+}
+
+int crt_resolve_temporal(crt_scene* s, uint8_t* rgba, size_t n_bytes) {
+    if (!s || !rgba) return fail(CRT_ERR_INVALID, "crt_resolve_temporal: null argument");
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = temporal_of(s, "crt_resolve_temporal"))) return rc;
+    const size_t npx = (size_t)s->width * s->height;
+    if (n_bytes != 4 * npx) return fail(CRT_ERR_INVALID, "crt_resolve_temporal: n_bytes must be width*height*4");
+    HIPCHK(hipSetDevice(s->device));
+    if ((rc = resolve_temporal_to_device(s))) return rc;
+    if (!s->h_rgba) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_rgba), 4 * npx));
+    HIPCHK(hipMemcpyAsync(s->h_rgba, s->temporal->d_rgba, n_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    std::memcpy(rgba, s->h_rgba, n_bytes);
+    return CRT_OK;
+}
+
+int crt_resolve_temporal_device(crt_scene* s, const uint8_t** d_rgba, int sync) {
+    if (!s || !d_rgba) return fail(CRT_ERR_INVALID, "crt_resolve_temporal_device: null argument");
+    *d_rgba = nullptr;
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = temporal_of(s, "crt_resolve_temporal_device"))) return rc;
+    HIPCHK(hipSetDevice(s->device));
+    if ((rc = resolve_temporal_to_device(s))) return rc;
+    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
+    *d_rgba = s->temporal->d_rgba;
     return CRT_OK;
 }
 

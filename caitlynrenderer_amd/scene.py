@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CRT_ABI_VERSION, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats,
+from ._lib import (CRT_ABI_VERSION, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params,
                    crt_scene_desc, crt_tree_cost, lib)
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _cost_dict, _ptr
 
@@ -225,6 +225,55 @@ class Scene:
         """crt_resolve_denoised_device: the same RGBA8 left in device memory, in a buffer of its own; returns the device pointer"""
         p = C.c_void_p()
         check(lib().crt_resolve_denoised_device(self._h, C.byref(p), 1 if sync else 0))
+        return p.value
+
+    def temporal(self, inv_count=None, source="sum", demodulate=True, clamp=False, max_history=32, sigma_depth=0.1, normal_min=0.9, sync=True):
+        """crt_temporal: blend the source ("sum": the running sum times inv_count, "denoised": crt_denoise's image) into the previous call's
+        result, reprojected through the camera's and the instances' motion and guided by the HIT, IDS, NORMAL and ALBEDO channels of the most
+        recent render_aov.  inv_count None = 1 / max(frame_count, 1).  reset() does not touch the history."""
+        if inv_count is None:
+            inv_count = 1.0 / max(self.frame_count, 1)
+        sources = {"sum": CRT_TEMPORAL_SOURCE_SUM, "denoised": CRT_TEMPORAL_SOURCE_DENOISED}
+        if source not in sources:
+            raise ValueError('source is "sum" or "denoised"')
+        p = crt_temporal_params()
+        p.flags = (CRT_TEMPORAL_DEMODULATE if demodulate else 0) | (CRT_TEMPORAL_CLAMP if clamp else 0)
+        p.source, p.max_history = sources[source], int(max_history)
+        p.sigma_depth, p.normal_min = float(np.float32(sigma_depth)), float(np.float32(normal_min))
+        check(lib().crt_temporal(self._h, float(np.float32(inv_count)), C.byref(p), 1 if sync else 0))
+
+    def temporal_reset(self):
+        """crt_temporal_reset: the next temporal() starts every pixel at N = 1; the buffers stay"""
+        check(lib().crt_temporal_reset(self._h))
+
+    def read_temporal(self):
+        """crt_read_temporal: the accumulated MEAN radiance, (height, width, 3) float32, rows as read_sum has them"""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(lib().crt_read_temporal(self._h, _ptr(out), out.size))
+        return out
+
+    def read_temporal_history(self):
+        """crt_read_temporal_history: N per pixel, (height, width) float32"""
+        out = np.empty((self.height, self.width), np.float32)
+        check(lib().crt_read_temporal_history(self._h, _ptr(out), out.size))
+        return out
+
+    def temporal_device(self):
+        """crt_temporal_device: device pointer (int) of the accumulated image, width * height * 3 floats, valid until the scene is closed"""
+        ptr = C.c_void_p()
+        check(lib().crt_temporal_device(self._h, C.byref(ptr)))
+        return ptr.value
+
+    def resolve_temporal(self):
+        """crt_resolve_temporal: resolve's tone map and pinned gamma on the accumulated image, (height, width, 4) uint8"""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        check(lib().crt_resolve_temporal(self._h, _ptr(out), out.size))
+        return out
+
+    def resolve_temporal_device(self, sync=True):
+        """crt_resolve_temporal_device: the same RGBA8 left in device memory, in a buffer of its own; returns the device pointer"""
+        p = C.c_void_p()
+        check(lib().crt_resolve_temporal_device(self._h, C.byref(p), 1 if sync else 0))
         return p.value
 
     def launch_times(self):

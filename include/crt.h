@@ -239,6 +239,9 @@ int crt_sync(crt_scene* s);
  *     "denoise_form"      0 (default), 1 or 2: which form of its pass kernel crt_denoise runs: 0 = at each tap spacing the one measured
  *                         faster there, 1 = the taps staged in LDS, 2 = the taps read from global memory, at every
  *                         spacing.  The same bytes either way.
+ *     "temporal_form"     0 (default), 1 or 2: how a crt_temporal call with CRT_TEMPORAL_CLAMP reads the 3 x 3 neighbourhood: 0 = the form
+ *                         measured faster, 1 = staged in LDS once per 16 x 16 block, 2 = read from global memory by
+ *                         every lane.  The same bytes either way.
  *     "streams"           1 (default) .. 4, or 0 = pick for me (3 for scenes of a few nodes, 2 for max_depth > 1, else 1): that many tile shards of the frame rendered side by side on streams of their own on this one GPU
  *                         (own queues and path state, the scene buffers shared).  A multi-segment frame is a chain of dependent
  *                         launches; another shard's launches fill their tails: 1 M triangles, 4 segments, 2 streams +6 %, 8 M triangles
@@ -353,6 +356,66 @@ int crt_read_denoised(crt_scene* s, float* rgb, size_t n_floats);
 int crt_denoised_device(crt_scene* s, const float** d_rgb);
 int crt_resolve_denoised(crt_scene* s, uint8_t* rgba, size_t n_bytes);
 int crt_resolve_denoised_device(crt_scene* s, const uint8_t** d_rgba, int sync);
+
+/* Accumulate displayed frames across camera and instance motion (no reference counterpart: the reference restarts its sum while
+ * camera.isMoving): temporal accumulation by reprojection, flat and instanced scenes.  Per displayed frame: move things,
+ * crt_reset, crt_render_frames (k samples), crt_render_aov, optionally crt_denoise, crt_temporal, crt_resolve_temporal_device.  crt_reset
+ * does not touch the history: that is the point.
+ * Per pixel: the first-hit point (the recorded view's primary ray at the pixel times HIT's t) is carried into the previous call's view,
+ * through the instance's previous object_to_world where that changed; the previous result is gathered bilinearly from the up to four
+ * pixels around it that show the same surface (the same instance, unit normals with a cosine of at least normal_min, a stored depth within
+ * sigma_depth * t' of the reprojected one); with N' the gathered history length, N = min(N' + 1, max_history) and the result is
+ * previous + (source - previous) / N.  A pixel without such a tap, one whose point lies behind or outside the previous view, one of an
+ * instance index the previous call did not have, a miss, an emitter seen directly or a degenerate normal starts again at N = 1 with the
+ * source.  CRT_TEMPORAL_DEMODULATE accumulates source / max(albedo, 1e-3) and multiplies the albedo back, so texture detail is not
+ * smeared by the resampling; CRT_TEMPORAL_CLAMP clamps the gathered value to the source's range over the pixel and its eight neighbours of
+ * the same instance (against ghosting when lighting changes).  max_history 1 gives the source itself.  Every step is one IEEE float32
+ * operation in a fixed order: DESIGN.md §23 is the definition, and the result is the same bytes on every build.  Non-finite radiance in
+ * the source gives unspecified values where it is blended in.
+ * The source is crt_sum_device's image times inv_count (CRT_TEMPORAL_SOURCE_SUM), or crt_denoise's image as it is
+ * (CRT_TEMPORAL_SOURCE_DENOISED; inv_count is then ignored but still checked).
+ * The current view is the one the most recent crt_render_aov that rendered HIT was given, recorded on the host when that call was
+ * enqueued: the camera, the aspect and field-of-view factors, rx * ry and the "jitter" option.  As for crt_denoise, keeping HIT, IDS,
+ * NORMAL and ALBEDO in step with the view and the geometry is the CALLER's duty, and so is not moving instances between crt_render_aov
+ * and crt_temporal: an instanced scene reads the handle's live object_to_world / world_to_object when crt_temporal is enqueued, as a
+ * frame does, and keeps a copy of object_to_world (and the instance count) as "previous" for the next call.  The camera basis is assumed
+ * orthonormal, as crt_camera_look_at makes it.  The previous normal is in the previous frame's world space and is not rotated: a spinning
+ * instance loses its history once one call's rotation exceeds the normal_min cosine.
+ * Out of scope: deforming geometry.  After crt_update_vertices, crt_rebuild_vertices, crt_instances_update_meshes or a mesh replace the
+ * surface point is assumed not to have moved in object space; the depth and normal tests catch large moves, and a caller that deforms a
+ * lot calls crt_temporal_reset.  No previous-vertex copy is kept.
+ * crt_temporal is enqueued on the scene's stream behind any *_async frames, crt_render_aov and crt_denoise calls (sync = 0 returns at
+ * once; crt_sync, the read calls below and later frames are ordered behind it).  It leaves the sum, the frame count, crt_get_frame_stats,
+ * the launch times, every AOV channel, crt_denoise's buffers, crt_resolve_device's buffer and every frame's path and RNG state as they
+ * are (source SUM rewrites the un-tiled sum that crt_sum_device's pointer names, as every crt_read_sum does).  Its own buffers are
+ * allocated by a scene's first crt_temporal and freed with the scene; later calls allocate nothing.
+ * The next call is history-less (every pixel N = 1) when it is the first, after crt_temporal_reset, and after a change of the DEMODULATE
+ * bit between two calls.  params NULL = {CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_SUM, 32, 0.1f, 0.9f}.
+ * crt_read_temporal: width*height*3 floats, rows as crt_read_sum has them, MEAN radiance.  crt_read_temporal_history: width*height
+ * floats, N per pixel.  crt_temporal_device waits for the stream and leaves the image on the device; the pointer stays valid until the
+ * scene is destroyed.  crt_resolve_temporal / crt_resolve_temporal_device: crt_resolve's tone map and pinned gamma on that image
+ * (inv_count 1), into a buffer of their own.
+ * CRT_ERR_INVALID, nothing written and the history unchanged: null scene; inv_count not finite or <= 0; unknown flag bits; source > 1;
+ * max_history outside 1..4096; sigma_depth or normal_min out of range or not finite; non-zero reserved; HIT, IDS or NORMAL never rendered,
+ * or ALBEDO with CRT_TEMPORAL_DEMODULATE; source DENOISED before any successful crt_denoise; a shard of a frame (crt_set_shard with
+ * world > 1) or a scene on several devices; a read, device or resolve call before any successful crt_temporal, or with a wrong size. */
+enum { CRT_TEMPORAL_DEMODULATE = 1, CRT_TEMPORAL_CLAMP = 2 };
+enum { CRT_TEMPORAL_SOURCE_SUM = 0, CRT_TEMPORAL_SOURCE_DENOISED = 1 };
+typedef struct crt_temporal_params {   /* 32 bytes */
+    uint32_t flags;        /* the two bits above; others refused */
+    uint32_t source;       /* SUM: crt_sum_device's image * inv_count; DENOISED: crt_denoise's image (inv_count ignored but still checked) */
+    uint32_t max_history;  /* 1..4096; 1 = output equals the source */
+    float    sigma_depth;  /* relative depth tolerance, finite, in [1e-6, 1e6] */
+    float    normal_min;   /* finite, in [-1, 1]: smallest cosine between the two unit normals */
+    uint32_t reserved[3];  /* must be 0 */
+} crt_temporal_params;    /* NULL = {DEMODULATE, SUM, 32, 0.1f, 0.9f} */
+int crt_temporal(crt_scene* s, float inv_count, const crt_temporal_params* p, int sync);
+int crt_temporal_reset(crt_scene* s);                               /* drop the history; the buffers stay */
+int crt_read_temporal(crt_scene* s, float* rgb, size_t n_floats);   /* w*h*3, mean radiance */
+int crt_read_temporal_history(crt_scene* s, float* n, size_t n_floats); /* w*h: N per pixel */
+int crt_temporal_device(crt_scene* s, const float** d_rgb);
+int crt_resolve_temporal(crt_scene* s, uint8_t* rgba, size_t n_bytes);
+int crt_resolve_temporal_device(crt_scene* s, const uint8_t** d_rgba, int sync);
 
 /* Animated geometry (no reference counterpart: the reference uploads its scene once, Scene.h:1000-1062; DXR / OptiX call this an
  * update build).  New positions for the scene's vertices; triangles, materials, textures and the tree topology are unchanged.
