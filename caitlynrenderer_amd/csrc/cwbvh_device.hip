@@ -36,7 +36,7 @@ namespace {
 using namespace crt::cw;
 using crt::fail;
 
-enum : uint32_t { ERR_LEAF_SIZE = 1u, ERR_LEAF_RANGE = 2u, ERR_LINK = 4u, ERR_COVER = 8u };
+enum : uint32_t { ERR_LEAF_SIZE = 1u, ERR_LEAF_RANGE = 2u, ERR_LINK = 4u, ERR_COVER = 8u, ERR_COST = 16u };
 
 static_assert(sizeof(Decision) == 8, "7 decisions per node are stored as 7 x 8 bytes");
 
@@ -69,7 +69,7 @@ __global__ void k_level_starts(const uint32_t* __restrict__ depth, uint32_t n2, 
 // The 7-entry cost/decision table of every node of one level (cwbvh.h:75-173); the children's tables are in the next
 // level, computed by the previous launch.  (First version: one thread per leaf climbing with an agent-scope acq_rel
 // arrival counter per node — 3.6 ms of the 4.6 ms conversion at 1 M triangles.)
-__global__ void k_costs_level(const crt_flatnode* __restrict__ bvh2, uint32_t begin, uint32_t end, uint32_t n2, uint32_t n_slots,
+__global__ void k_costs_level(const crt_flatnode* __restrict__ bvh2, uint32_t begin, uint32_t end, uint32_t n2, uint32_t n_slots, float scale,
                               Decision* __restrict__ dec, int32_t* __restrict__ nprims, uint32_t* flags) {
     const uint32_t i = begin + blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= end) return;
@@ -81,14 +81,15 @@ __global__ void k_costs_level(const crt_flatnode* __restrict__ bvh2, uint32_t be
         const int start = crt::link_of(fn.bmin[3]);
         if (np < 1 || np > 3) { atomicOr(flags, ERR_LEAF_SIZE); return; }
         if (start < 0 || (uint32_t)(start + np) > n_slots) { atomicOr(flags, ERR_LEAF_RANGE); return; }
-        leaf_decisions(half_area(fn), np, d);
+        leaf_decisions(half_area(fn, scale), np, d);
     } else {
         const int left = crt::link_of(fn.bmin[3]);
         // the host bails out on ERR_LINK before the first cost pass; this check keeps the kernel in bounds on its own
         if (left <= (int)i || (uint32_t)left + 1u >= n2) { atomicOr(flags, ERR_LINK); return; }
         np = nprims[left] + nprims[left + 1];
-        inner_decisions(half_area(fn), np, dec + (size_t)left * 7, dec + (size_t)(left + 1) * 7, d);
+        inner_decisions(half_area(fn, scale), np, dec + (size_t)left * 7, dec + (size_t)(left + 1) * 7, d);
     }
+    if (!cost_in_range(d)) atomicOr(flags, ERR_COST);      // the table is still written: its dl / dr always name a row
     for (int k = 0; k < 7; ++k) dec[(size_t)i * 7 + k] = d[k];
     nprims[i] = np;
 }
@@ -274,6 +275,8 @@ int cwbvh_convert_on_device(const crt_flatnode* d_bvh2, uint32_t n2, uint32_t ns
     hipLaunchKernelGGL(k_level_starts, grid_for(n2), dim3(256), 0, st, d_depth, n2, d_levels, (uint32_t)kMaxLevels, d_flags);
     uint32_t deepest = 0;
     uint32_t flags = 0;
+    crt_flatnode root{};
+    CW_HIPCHK(hipMemcpyAsync(&root, d_bvh2, sizeof root, hipMemcpyDeviceToHost, st));
     CW_HIPCHK(hipMemcpyAsync(&deepest, d_depth + (n2 - 1), 4, hipMemcpyDeviceToHost, st));
     // a link that is out of order, out of range, negative or NaN was flagged by k_parents / k_level_starts: stop before
     // any pass follows the links (host/cwbvh.cpp returns CRT_ERR_INVALID at the same point)
@@ -288,8 +291,9 @@ int cwbvh_convert_on_device(const crt_flatnode* d_bvh2, uint32_t n2, uint32_t ns
     CW_HIPCHK(hipMemcpyAsync(lv.data(), d_levels, (deepest + 1u) * 4, hipMemcpyDeviceToHost, st));
     CW_HIPCHK(hipStreamSynchronize(st));
     lv[deepest + 1u] = n2;
+    const float scale = area_scale(root);
     for (uint32_t l = deepest + 1u; l-- > 0;)
-        hipLaunchKernelGGL(k_costs_level, grid_for(lv[l + 1] - lv[l]), dim3(256), 0, st, d_bvh2, lv[l], lv[l + 1], n2, ns,
+        hipLaunchKernelGGL(k_costs_level, grid_for(lv[l + 1] - lv[l]), dim3(256), 0, st, d_bvh2, lv[l], lv[l + 1], n2, ns, scale,
                            reinterpret_cast<Decision*>(d_dec), d_nprims, d_flags);
 
     Decision root0;
@@ -301,6 +305,7 @@ int cwbvh_convert_on_device(const crt_flatnode* d_bvh2, uint32_t n2, uint32_t ns
         const char* msg = (f & ERR_LINK) ? "BVH2 child link out of order"
                         : (f & ERR_LEAF_SIZE) ? "BVH2 leaf with more than 3 triangles cannot be encoded"
                         : (f & ERR_LEAF_RANGE) ? "BVH2 leaf range outside the triangle array"
+                        : (f & ERR_COST) ? "BVH2 boxes out of the cost range: a summed cost is not below 1e20 times the root's scale"
                         : "BVH2 leaves do not cover the triangle array exactly once";
         return fail(CRT_ERR_INVALID, std::string("crt_cwbvh_convert_device: ") + msg);
     };

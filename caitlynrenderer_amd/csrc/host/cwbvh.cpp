@@ -14,6 +14,8 @@ namespace {
 using cw::Decision;
 using cw::is_leaf;
 
+const char* const kCostRange = "BVH2 boxes out of the cost range: a summed cost is not below 1e20 times the root's scale";
+
 struct Converter {
     const crt_flatnode* bvh2;
     size_t n2, n_slots;
@@ -32,9 +34,10 @@ struct Converter {
     bool calculate_cost() {
         nprims.assign(n2, 0);
         dec.resize(n2 * 7);
+        const float scale = cw::area_scale(bvh2[0]);
         for (int64_t node = (int64_t)n2 - 1; node >= 0; --node) {
             const crt_flatnode& fn = bvh2[node];
-            const float area = cw::half_area(fn);
+            const float area = cw::half_area(fn, scale);
             if (is_leaf(fn)) {
                 const int np = (int)fn.bmax[3];
                 const int start = link_of(fn.bmin[3]);
@@ -42,6 +45,7 @@ struct Converter {
                 if (start < 0 || (size_t)(start + np) > n_slots) { out->error = "BVH2 leaf range outside the triangle array"; return false; }
                 nprims[node] = np;
                 cw::leaf_decisions(area, np, &D((int)node, 0));
+                if (!cw::cost_in_range(&D((int)node, 0))) { out->error = kCostRange; return false; }
                 continue;
             }
             const int left = link_of(fn.bmin[3]), right = left + 1;
@@ -49,6 +53,7 @@ struct Converter {
             const int np = nprims[left] + nprims[right];
             nprims[node] = np;
             cw::inner_decisions(area, np, &D(left, 0), &D(right, 0), &D((int)node, 0));
+            if (!cw::cost_in_range(&D((int)node, 0))) { out->error = kCostRange; return false; }
         }
         return true;
     }

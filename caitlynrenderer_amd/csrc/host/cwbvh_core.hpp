@@ -18,7 +18,10 @@
 namespace crt {
 namespace cw {
 
-constexpr float kInf = 1e20f;   // sbvh.h:13, the `inf` cwbvh.h:101,103 compares against
+// A summed cost at or above this is refused (DESIGN.md §24 "cost domain"): with the areas scaled by area_scale the sums of a
+// tree whose boxes lie inside its root's stay below 12 * 3 * 2^24, so only boxes some 10^5 times wider than the root's get here.
+// (sbvh.h:13's `inf`, which cwbvh.h:101,103 also used as the "no decision yet" value of a minimum search.)
+constexpr float kInf = 1e20f;
 enum : int8_t { LEAF = 0, INTERNAL = 1, DISTRIBUTE = 2 };   // cwbvh.h:39
 
 struct Decision {   // cwbvh.h:41-49
@@ -30,10 +33,25 @@ CRT_HD uint32_t f2u(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u
 CRT_HD float u2f(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
 
 CRT_HD bool is_leaf(const crt_flatnode& n) { return n.bmax[3] != 0.0f; }   // FlatNode.h:60-63
-CRT_HD float half_area(const crt_flatnode& n) {                            // FlatNode.h:41-47
-    const float dx = n.bmax[0] - n.bmin[0], dy = n.bmax[1] - n.bmin[1], dz = n.bmax[2] - n.bmin[2];
+// The power of two the extents are multiplied by before an area is formed: 2^-floor(log2(largest extent of the root box)), exponent
+// kept in the normal range.  The root's half-area is then in [1, 12) at any scale of the scene; the products and sums of the cost
+// tables are those of the unscaled extents times a power of two, so every comparison (and every byte) is the one the unscaled
+// areas gave wherever those neither overflowed, reached kInf nor underflowed.
+CRT_HD float area_scale(const crt_flatnode& root) {
+    const float dx = root.bmax[0] - root.bmin[0], dy = root.bmax[1] - root.bmin[1], dz = root.bmax[2] - root.bmin[2];
+    float m = dx;
+    if (dy > m) m = dy;
+    if (dz > m) m = dz;
+    uint32_t e = (f2u(m) >> 23) & 0xffu;
+    if (e < 1u) e = 1u;
+    if (e > 253u) e = 253u;
+    return u2f((254u - e) << 23);
+}
+CRT_HD float half_area(const crt_flatnode& n, float a) {                   // FlatNode.h:41-47 of the extents times a
+    const float dx = (n.bmax[0] - n.bmin[0]) * a, dy = (n.bmax[1] - n.bmin[1]) * a, dz = (n.bmax[2] - n.bmin[2]) * a;
     return dx * (dy + dz) + dy * dz;
 }
+CRT_HD bool cost_in_range(const Decision out[7]) { return out[0].cost < kInf; }   // false for a NaN too
 
 // cwbvh.h:84-110: a BVH2 leaf costs area * nprims whatever the root budget
 CRT_HD void leaf_decisions(float area, int np, Decision out[7]) {
@@ -43,16 +61,17 @@ CRT_HD void leaf_decisions(float area, int np, Decision out[7]) {
 
 // cwbvh.h:111-173: out[i] = cheapest way to represent the subtree with at most i+1 roots
 CRT_HD void inner_decisions(float area, int np, const Decision* L, const Decision* R, Decision out[7]) {
-    const float cost_leaf = np <= 3 ? float(np) * area : kInf;
-    float cost_distribute = kInf;
-    int8_t dl = -1, dr = -1;
-    for (int k = 0; k < 7; ++k) {
+    // the first minimum of L[k] + R[6 - k]; dl / dr always name a row, whatever the costs are
+    float cost_distribute = L[0].cost + R[6].cost;
+    int8_t dl = 0, dr = 6;
+    for (int k = 1; k < 7; ++k) {
         const float c = L[k].cost + R[6 - k].cost;
         if (c < cost_distribute) { cost_distribute = c; dl = (int8_t)k; dr = (int8_t)(6 - k); }
     }
     const float cost_internal = cost_distribute + area;
-    if (cost_leaf < cost_internal) out[0] = Decision{cost_leaf, LEAF, dl, dr};
-    else                           out[0] = Decision{cost_internal, INTERNAL, dl, dr};
+    const float cost_leaf = float(np) * area;
+    if (np <= 3 && cost_leaf < cost_internal) out[0] = Decision{cost_leaf, LEAF, dl, dr};
+    else                                      out[0] = Decision{cost_internal, INTERNAL, dl, dr};
     for (int i = 1; i < 7; ++i) {
         float best = out[i - 1].cost;
         int8_t bl = -1, br = -1;
@@ -109,12 +128,12 @@ CRT_HD void order_children(const crt_flatnode* bvh2, int node, int children[8], 
     int assignment[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     bool filled[8] = {false, false, false, false, false, false, false, false};
     for (;;) {
-        float min_cost = kInf;
+        float min_cost = 0.0f;
         int min_slot = -1, min_index = -1;
         for (int c = 0; c < count; ++c) {
             if (assignment[c] != -1) continue;
-            for (int s = 0; s < 8; ++s)
-                if (!filled[s] && cost[c][s] < min_cost) { min_cost = cost[c][s]; min_slot = s; min_index = c; }
+            for (int s = 0; s < 8; ++s)      // the first candidate stands until a strictly cheaper one comes: every child gets a slot
+                if (!filled[s] && (min_slot == -1 || cost[c][s] < min_cost)) { min_cost = cost[c][s]; min_slot = s; min_index = c; }
         }
         if (min_slot == -1) break;
         filled[min_slot] = true;

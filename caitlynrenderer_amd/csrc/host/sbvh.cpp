@@ -68,6 +68,16 @@ struct Builder {
         });
     }
 
+    // true when the boxes of the last n references are equal, coordinate for coordinate
+    bool same_boxes(int n) const {
+        const Aabb& a = refs[refs.size() - n].box;
+        for (size_t r = refs.size() - n + 1; r < refs.size(); ++r) {
+            const Aabb& b = refs[r].box;
+            if (!(a.lo.x == b.lo.x && a.lo.y == b.lo.y && a.lo.z == b.lo.z && a.hi.x == b.hi.x && a.hi.y == b.hi.y && a.hi.z == b.hi.z)) return false;
+        }
+        return true;
+    }
+
     // sbvh.h:338-378: exact SAH sweep over all three axes.
     ObjectSplit find_object_split(const Spec& spec, float node_sah) {
         ObjectSplit best;
@@ -264,13 +274,29 @@ struct Builder {
         const float node_sah = 2.0f * node_area;
         ObjectSplit object = find_object_split(spec, node_sah);
         SpatialSplit spatial;
-        if (spatial_enabled) {
+        // References whose boxes are all the same (coincident triangles, or their clipped halves) cannot be told apart by any plane:
+        // a spatial split clips every one of them into both children, which are again such nodes, and the references double at each
+        // level until the boxes fall below min_overlap (3 coincident triangles: 220,989 references; 300: more than the 2^24 nodes a
+        // float link can number).  Such a node takes the object split, which tells them apart by id.
+        if (spatial_enabled && !same_boxes(spec.n)) {
             Aabb overlap = object.lb;
             overlap.clip(object.rb);
             if (overlap.half_area() >= min_overlap) spatial = find_spatial_split(spec, node_sah);
         }
         const float min_sah = fmin_(object.sah, spatial.sah);
-        if (spatial_enabled && min_sah == spatial.sah) {
+        if (object.n_left == 0 && !(spatial.sah < kHuge)) {
+            // No candidate was priced below the 1e20 sentinel (areas of a scene some 10^9 units wide times their counts reach it, and
+            // so does a non-finite price).  The reference would go on with an empty left child and the whole node as the right one,
+            // for ever; split at the median of the widest axis instead, so that the build ends with a valid, if poor, tree.
+            const float3 ext = spec.box.hi - spec.box.lo;
+            const int dim = ext.y > ext.x ? (ext.z > ext.y ? 2 : 1) : (ext.z > ext.x ? 2 : 0);
+            sort_tail(spec.n, dim);
+            const size_t first = refs.size() - spec.n;
+            left.n = spec.n / 2;
+            right.n = spec.n - left.n;
+            left.box = right.box = Aabb();
+            for (int i = 0; i < spec.n; ++i) (i < left.n ? left.box : right.box).grow(refs[first + i].box);
+        } else if (spatial_enabled && min_sah == spatial.sah) {
             do_spatial_split(left, right, spec, spatial);
         } else {                                   // sbvh.h:379-389
             sort_tail(spec.n, object.dim);

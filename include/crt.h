@@ -902,7 +902,12 @@ float    crt_randf2(uint32_t* state);
 
 /* SBVH builder, Caitlyn/sbvh.h:99-153 SBVH(trs, vertices) [host].
  * Reorders into leaf order with spatial-split duplicates.  flags bit0: disable spatial
- * splits (pure SAH sweep, "SAH BVH" of config 1). */
+ * splits (pure SAH sweep, "SAH BVH" of config 1).  A node for which no split is priced below the builder's 1e20 "no split yet" value
+ * (a scene some 10^9 units wide: area times count reaches it) is split at the median of its widest axis; the reference's rule gave such
+ * a node an empty left child and itself as the right one, without end.  A node whose references all have the same box
+ * (coincident triangles) takes the object split even with spatial splits on: no plane separates them, and clipping every one into both
+ * children doubled the references level by level (300 coincident triangles: more than 2^24 nodes).  References that only nearly
+ * coincide are still duplicated down to the reference's overlap threshold (1e-5 of the root's area): on the order of a thousand references each. */
 typedef struct crt_sbvh crt_sbvh;
 int crt_sbvh_build(const crt_triangle* tris, size_t n_tris, const float* vertices, size_t n_vertices,
                    uint32_t flags, crt_sbvh** out);
@@ -931,7 +936,13 @@ int  crt_lbvh_build(const crt_triangle* tris, size_t n_tris, const float* vertic
 void crt_lbvh_last_build_ms(float* device_ms, float* total_ms);
 
 /* CWBVH converter, Caitlyn/cwbvh.h:58-73 CWBVH::convert(SBVH&) with the defects of
- * SURVEY 8a corrected (appendix C) [host]. */
+ * SURVEY 8a corrected (appendix C) [host].  Defined rule by rule in DESIGN.md §24.  The cost tables are formed from extents scaled by a
+ * power of two taken from the root box, so the result does not depend on the scale of the scene: coordinates times 2^k give the same
+ * tree with p times 2^k and e + k.  Cost domain: with every box inside the root's, no summed cost exceeds 12 * 3 * 2^24; an array in
+ * which one reaches 1e20 (a box some 10^5 root extents wide) is refused, CRT_ERR_INVALID "boxes out of the cost range".  Also
+ * CRT_ERR_INVALID: a leaf of more than 3 triangles, a leaf range outside n_slots, a child link that is not beyond its node and inside the
+ * array, slots not covered exactly once.  Children must follow their parents; the device form below also requires breadth-first order
+ * and returns CRT_ERR_LIMIT beyond 64 node8 levels or 4096 BVH2 levels, which this one accepts. */
 typedef struct crt_cwbvh crt_cwbvh;
 int crt_cwbvh_convert(const crt_flatnode* bvh2, size_t n_nodes, size_t n_slots, crt_cwbvh** out);
 /* The same conversion on the GPU (needs a GPU): byte-identical node, triangle-slot and child arrays
