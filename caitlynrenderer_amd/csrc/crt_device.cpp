@@ -1,4 +1,5 @@
-// Device half of include/crt.h: scene upload, per-frame wavefront dispatch, read-back.
+// Device half of include/crt.h: scene upload, per-frame wavefront dispatch, several GPUs, refit / rebuild, packed read-back.  (The
+// images that leave the library — sum, AOVs, denoised, accumulated, their RGBA8 — are crt_outputs.cpp; the scene itself crt_scene.hpp.)
 // Replaces Scene::gpu_data / Render / update (Caitlyn/Scene.h:1000-1246).  Owns its own HIP
 // stream; every kernel of a frame is enqueued there, queue lengths stay on the device, and the
 // host synchronises once per call (never inside the frame).
@@ -21,6 +22,7 @@
 
 #include "../../include/crt.h"
 #include "crt_error.hpp"
+#include "crt_scene.hpp"
 #include "denoise.hpp"
 #include "device_build.hpp"
 #include "host/cwbvh.hpp"
@@ -29,33 +31,17 @@
 #include "instances.hpp"
 #include "instances_bind.hpp"
 #include "rt_kernels.hpp"
-#include "temporal.hpp"
 
+using crt::deal_tiles;
 using crt::dev_alloc;
+using crt::ensure_frame;
 using crt::fail;
+using crt::frame_args;
 using crt::require_device;
-
-#define HIPCHK(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(CRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
-    } while (0)
 
 namespace {
 
 constexpr int kMaxEvents = 8 + 8 * 16;
-constexpr uint32_t kCounterStride = 32;                        // == CRT_COUNTER_STRIDE in rt_kernels.hip (128 B)
-// kind 0 = rays into the segment, 1 = its shadow rays
-constexpr uint32_t kQueueCounters = 2 * 17 * 8 * kCounterStride;    // (segment, kind, group) x stride
-inline uint32_t counter_index(uint32_t seg, uint32_t kind, uint32_t group) { return ((seg * 2 + kind) * 8 + group) * kCounterStride; }
-// behind them, in the same banks (cleared with them): the cursors of the persistent grids (rt_kernels.hip PoolStream) — one per sub-queue of
-// a segment's path-ray queue (k_closest_queue), one per (region, sub-queue) of the frame's NEE queue (k_shadow_deferred)
-inline uint32_t cursor_index_closest(uint32_t seg) { return kQueueCounters + seg * 8 * kCounterStride; }
-constexpr uint32_t kCursorShadow = kQueueCounters + 17 * 8 * kCounterStride;
-constexpr uint32_t kCounters = kCursorShadow + 17 * 8 * kCounterStride;
-
-struct EventSpan { hipEvent_t a = nullptr, b = nullptr; int kind = 0; };   // kind: 0 raygen 1 closest 2 any 3 shade/other
 
 uint32_t morton2(uint32_t x, uint32_t y) {
     auto spread = [](uint32_t v) {
@@ -71,422 +57,9 @@ uint32_t morton2(uint32_t x, uint32_t y) {
 
 }  // namespace
 
-// What crt_render_aov keeps, allocated by a scene's first call: the five channel buffers, each by the first call that asks
-// for it, and what the dispatch needs beside the frame's own buffers.  The scene's stream has drained when this is destroyed.
-struct AovState {
-    void* d_chan[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // HIT, IDS, NORMAL, ALBEDO, EMISSION: width * height * 16 bytes, linear pixel order
-    uint32_t rendered = 0;               // channels some call has written
-    uint32_t last = 0;                   // the channels of the last call
-    // flat scenes: the tiles of the CALLER's shard (crt_set_shard), whatever option "streams" made of them for the frames
-    uint2* d_tile_xy = nullptr;
-    uint32_t n_local_pixels = 0, rank = 0, world = 0, tile = 0;
-    uint32_t* d_count = nullptr;         // instanced scenes: the 8 counters of the primary rays' queue (the frames' banks stay as they are)
-    ~AovState() {
-        for (void* p : d_chan) if (p) (void)hipFree(p);
-        if (d_tile_xy) (void)hipFree(d_tile_xy);
-        if (d_count) (void)hipFree(d_count);
-    }
-};
-
-// What crt_denoise keeps, allocated by a scene's first call: the guide records, the two images the passes alternate
-// between, the denoised linear image and its RGBA8.  A scene that never denoises holds none of it.
-struct DenoiseState {
-    float4* d_g = nullptr;               // (unit normal, t) per pixel, constant over the passes
-    float4* d_x[2] = {nullptr, nullptr}; // (x, key) per pixel: pass i reads [i & 1] and writes the other
-    float* d_out = nullptr;              // the denoised MEAN radiance, 3 floats per pixel, linear pixel order
-    uint8_t* d_rgba = nullptr;           // crt_resolve_denoised*'s buffer, from their first call on
-    bool valid = false;                  // some crt_denoise has been enqueued
-    ~DenoiseState() {
-        void* bufs[] = {d_g, d_x[0], d_x[1], d_out, d_rgba};
-        for (void* p : bufs) if (p) (void)hipFree(p);
-    }
-};
-
-// What crt_temporal keeps, allocated by a scene's first call: two sets of (history, guide, key) that the calls alternate
-// between, the accumulated linear image and its RGBA8, the previous call's view and, for an instanced scene, its object_to_world.
-struct TemporalState {
-    float4* d_hist[2] = {nullptr, nullptr};      // (y, N) per pixel: a call reads [cur] and writes the other
-    float4* d_guide[2] = {nullptr, nullptr};     // (unit normal, t) per pixel
-    uint32_t* d_key[2] = {nullptr, nullptr};     // instance + 1, 0 for a pixel that is not filterable
-    float* d_out = nullptr;                      // the accumulated MEAN radiance, 3 floats per pixel, linear pixel order
-    uint8_t* d_rgba = nullptr;                   // crt_resolve_temporal*'s buffer
-    float* d_o2w_prev = nullptr;                 // an instanced scene: object_to_world as of the previous call (capacity x 12)
-    uint32_t n_prev_instances = 0;
-    uint32_t cur = 0;                            // the set the most recent call wrote
-    crt::TemporalView prev_view{};               // the view of the most recent call
-    uint32_t demodulate = 0;                     // the DEMODULATE bit of the most recent call: what the history holds
-    bool have_history = false;                   // false until a call succeeds, and after crt_temporal_reset
-    bool valid = false;                          // some crt_temporal has been enqueued
-    ~TemporalState() {
-        void* bufs[] = {d_hist[0], d_hist[1], d_guide[0], d_guide[1], d_key[0], d_key[1], d_out, d_rgba, d_o2w_prev};
-        for (void* p : bufs) if (p) (void)hipFree(p);
-    }
-};
-
-// What crt_update_vertices and crt_rebuild_vertices take new positions through, allocated by a scene's first call of either: a scene that
-// never moves holds none of it.  The times are those of the most recent call that succeeded (crt_last_update_ms).
-struct VertexIntake {
-    float* d_verts = nullptr;                // the host forms' upload of the positions
-    uint32_t* d_check = nullptr;             // k_check_vertices: non-finite flag, max keys, complemented min keys
-    uint32_t* h_check = nullptr;             // pinned
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    bool have_times = false, times_pending = false;
-    float device_ms = 0.f, wall_ms = 0.f;
-    ~VertexIntake() {                        // on the scene's device
-        if (d_verts) (void)hipFree(d_verts);
-        if (d_check) (void)hipFree(d_check);
-        if (h_check) (void)hipHostFree(h_check);
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-    }
-};
-
-// What crt_update_vertices keeps between updates, allocated by a scene's first update: a scene that never updates holds none of it.
-struct RefitState {
-    int device = 0;
-    uint32_t* d_order = nullptr;             // node8 indices level by level, root level first, then the BVH2's the same way
-    std::vector<uint32_t> level8, level2;    // level8[l] = position in d_order of node8 level l (+ end); level2 the same for the BVH2
-    crt::RefitMesh* d_mesh = nullptr;        // the scene as one refit mesh (its vertex pointer changes between calls) ...
-    crt::RefitMesh* h_mesh = nullptr;        // ... sent from here, pinned
-    crt::RefitSeg* d_seg = nullptr;          // the one segment of every launch: entries from 0, items from 0, mesh 0
-    float* d_box8 = nullptr;                 // the float box of every node8 (6 floats), which its parent's slot reads
-    std::vector<hipEvent_t> ev_peer;         // per peer, on its device: "the peer's stream is done with the old scene"
-    ~RefitState() {
-        (void)hipSetDevice(device);
-        void* ptrs[] = {d_order, d_box8, d_mesh, d_seg};
-        for (void* p : ptrs) if (p) (void)hipFree(p);
-        if (h_mesh) (void)hipHostFree(h_mesh);
-        for (hipEvent_t e : ev_peer) if (e) (void)hipEventDestroy(e);
-        (void)hipSetDevice(device);
-    }
-};
-
-// What crt_rebuild_vertices keeps between rebuilds, allocated by a scene's first rebuild: a scene that never rebuilds holds
-// none of it, and no walk or frame reads it.
-struct RebuildState {
-    crt_triangle* d_src = nullptr;           // the triangles in SOURCE order (create threw its copy away): scattered back from the leaf order once
-    ~RebuildState() { if (d_src) (void)hipFree(d_src); }     // on the scene's device
-};
-
-// The lights of an instanced scene that follow its instances (crt_scene_create_instanced_lit).  The scene's d_lights is
-// then the world table these are rebuilt into, n_lights its current total.
-struct SceneLights {
-    uint32_t n_static = 0;
-    std::vector<uint2> mesh;              // per mesh: (first light in `obj`, count)
-    std::vector<crt_light> obj;           // every mesh's object-space lights, mesh after mesh (the source of set_mesh_lights' upload)
-    float* d_static = nullptr;            // n_static x 18
-    float* d_obj = nullptr;
-    uint2* d_mesh = nullptr;
-    uint32_t* d_first = nullptr;          // per instance (the handle's capacity): the table index of its first light
-    uint32_t* d_block_sums = nullptr;     // one word per 1024 instances
-    uint32_t* d_total = nullptr;
-    float* d_partial = nullptr;           // the tree sum's partials, sized with the table
-    size_t table_cap = 0;                 // lights d_lights holds
-    uint64_t seen = 0;                    // the handle's mutation count the table was built from
-    bool stale = true;
-    ~SceneLights() {
-        void* bufs[] = {d_static, d_obj, d_mesh, d_first, d_block_sums, d_total, d_partial};
-        for (void* p : bufs) if (p) (void)hipFree(p);
-    }
-};
-
-struct crt_scene {
-    int device = 0;
-    int n_cu = 256;
-    hipStream_t stream = nullptr;
-    uint32_t width = 0, height = 0, max_depth = 1, n_lights = 0;
-
-    // scene (replicated on every rank)
-    uint4* d_nodes = nullptr;
-    float4* d_planes = nullptr;          // the nodes' child planes as floats, 12 rows per node (uniform node steps; built by ensure_planes at the first CWBVH frame)
-    float4* d_tris = nullptr;
-    int4* d_triangles = nullptr;
-    float* d_normals = nullptr;
-    float4* d_materials = nullptr;
-    float* d_lights = nullptr;
-    float2* d_texcoords = nullptr;
-    float* d_textures = nullptr;         // albedo array as RGB32F (c / 255.0f)
-    int32_t tex_width = 0, tex_height = 0, n_textures = 0;
-    crt_bvh_info info{};
-    float4* d_bvh2 = nullptr;            // FlatNode array as uploaded by the reference (only when desc.bvh was given)
-    float4* d_tris2 = nullptr;           // intersection records in BVH2 leaf-slot order
-    uint32_t bvh2_stack = 0;             // BVH2 depth + 2
-    size_t n_vertices = 0, n_normals = 0, n_slots = 0;   // as created (n_slots: the leaf-order triangle array); crt_update_vertices checks against them
-    VertexIntake* intake = nullptr;      // what both take new positions through, from the first update or rebuild on
-    RefitState* refit = nullptr;         // crt_update_vertices' state, from the first update on
-    RebuildState* rebuild = nullptr;     // crt_rebuild_vertices' state, from the first rebuild on
-    uint32_t gpu_build_flags = 0;        // build-on-device scenes: the builder (CRT_GPU_BUILD_*) a rebuild runs again
-    // A scene whose geometry is a live crt_instances handle (crt_scene_create_instanced): BORROWED, and bound from create to
-    // destroy.  d_nodes / d_tris / d_planes stay null: a frame reads the handle's arrays as they are when it is enqueued.  d_triangles,
-    // d_normals and d_texcoords hold every mesh's arrays one after the other, d_mesh_base where each mesh's start.
-    crt_instances* inst = nullptr;
-    uint4* d_mesh_base = nullptr;        // per mesh: first triangle, first normal, first texcoord, the lights it carries (§18)
-    int32_t* d_qinst = nullptr;          // the hit instance of every entry of the path-ray queue (beside d_qhits)
-    // material offsets and masks in its frames.  The two tables are the rule the handle holds offsets to while bound
-    uint4* d_mesh_mtl = nullptr;         // per mesh: least, greatest v[3], 1 = every vt indexes the mesh's texcoords, 0
-    uint32_t* d_tex_before = nullptr;    // n_materials + 1: the textured materials below each index
-    uint32_t instance_masks = 0, mask_primary = 255, mask_bounce = 255, mask_shadow = 255;   // options of those names
-    uint64_t cmask_seen = 0;             // the handle's child-mask pass this scene's stream last waited for
-    SceneLights* lit = nullptr;          // lights that follow the instances; null = desc->lights alone, as before
-    AovState* aov = nullptr;             // crt_render_aov's buffers, from the first call on
-    DenoiseState* denoise = nullptr;     // crt_denoise's buffers, from the first call on
-    TemporalState* temporal = nullptr;   // crt_temporal's buffers, from the first call on
-    uint32_t temporal_form = 0;          // option "temporal_form": how a CLAMP call reads its neighbourhood: 0 = the form measured faster, 1 = staged, 2 = direct
-    crt::TemporalView aov_view{};        // the view of the most recent crt_render_aov that rendered HIT, recorded at enqueue: crt_temporal's current view
-    bool have_aov_view = false;
-    uint32_t denoise_form = 0;           // option "denoise_form": 0 = each pass in the form measured faster at its tap spacing, 1 = staged, 2 = direct
-
-    // shard + frame buffers
-    uint32_t rank = 0, world = 1, tile = 16;   // 16x16: four waves per tile — fine enough for the cost-sorted schedule (1 M triangles: 0.273 ms at 64, 0.257 at 16)
-    std::vector<uint2> tiles;            // local tiles
-    // Processing order of the local tiles (FrameArgs::tile_order): centre-out to begin with, then by measured cost, most
-    // expensive first (longest-processing-time-first scheduling of the launch).  One frame after every change of camera,
-    // shard or frame size has each wave add the clock ticks it spent to its tile's counter; the counters come back
-    // through a pinned buffer without a stream synchronise, and the re-sorted order is uploaded in stream order.
-    uint32_t* d_tile_order = nullptr; uint32_t* d_tile_cost = nullptr;
-    uint32_t* h_tile_cost = nullptr; uint32_t* h_tile_order = nullptr;      // pinned
-    hipEvent_t ev_tile_cost = nullptr, ev_tile_order = nullptr;
-    enum { TILES_WANT = 0, TILES_PENDING = 1, TILES_DONE = 2 };
-    int tile_state = TILES_WANT;
-    uint32_t adaptive_tiles = 1;             // option: 0 keeps the centre-out order
-    bool tile_order_uploading = false;
-    bool tiles_measured_once = false;
-    uint32_t frames_since_tile_measure = 0;
-    bool capturing = false;                  // crt_debug_time_graph: no host-side decisions inside a stream capture
-    uint2* d_tile_xy = nullptr;
-    uint32_t n_local_tiles = 0, n_local_pixels = 0;
-    uint64_t n_local_in_frame = 0;
-    float* d_sum = nullptr;
-    float* d_linear = nullptr;
-    uint8_t* d_rgba = nullptr;
-    uint8_t* h_rgba = nullptr;           // pinned staging buffer of crt_resolve
-    float* d_gamma = nullptr;            // the 256 thresholds of the pinned gamma (resolve kernels)
-    float4* d_rays[2] = {nullptr, nullptr};   // path-ray queues, only for max_depth > 1
-    // DEFERRED NEE shadow rays (option "inplace_shadow" 0 / 2, rt_kernels.hip k_segment<!INPLACE>): the frame's NEE queue — one region per
-    // deferring segment, 8 sub-queues each, 2 x float4 per ray: (o, tmax) (d, contribution slot) — and the contribution slots, one per
-    // (deferring segment, path): (C | T e, visibility word)
-    float4* d_nee = nullptr;
-    float4* d_contrib = nullptr;
-    // option "sort_shadow": the frame's deferred shadow rays walked in the order of the cell they start in (rt_kernels.hip k_nee_*):
-    // perm[place] = queue entry, 4096-bin histogram + cursors + the eight parts' lengths
-    uint32_t* d_nee_perm = nullptr;
-    uint32_t* d_nee_bins = nullptr;           // hist [4096] | cursor [4096] | meta [9 x stride]
-    uint32_t sort_shadow = 0;                 // (1 M triangles, four segments: 7.18 against 7.59 Gray/s unsorted — the sort costs more than the 4 % fewer any-hit node steps return)
-    uint32_t defer_cap = 0, defer_regions = 0, defer_sub_capacity = 0;   // what the two were sized for
-    uint32_t lfinal_cap = 0;                  // samples d_lfinal is sized for
-    float4* d_qhits = nullptr;                // closest hits of the path-ray queue (max_depth > 1, option bounce_refill)
-    // segments >= 1: 0 = fused lock-step k_segment (default); 1 = closest hits through lane-refill pools (k_closest_queue) + shade-only pass
-    uint32_t bounce_refill = 0;
-    uint32_t refill_pool = 256;               // rays per wave of k_closest_queue (64 with refill_min 65: lock-step batches)
-    // k_shadow_deferred: rays per pool / per chunk a wave reserves, and the idle lanes that trigger a refill (65: never — one lock-step
-    // batch per 64 rays of the pool).  1 M triangles, four segments: lock-step 64 7.34, static pools 128 / 16 7.42 (7.61 - 7.67 after the
-    // kernarg change), persistent 256 / 16 7.72 Gray/s
-    uint32_t shadow_pool = 256;
-    uint32_t shadow_refill_min = 16;
-    uint32_t step_hist_mode = 0;             // crt_debug_step_hist: 0 = node steps by enabled lanes, 1 = by distinct (node, octant) keys in the wave
-    uint32_t shadow_waves = 6;               // waves per SIMD the persistent any-hit grid of the deferred shadow rays is sized for (the kernel fits 8; two shards'
-                                             // grids share the chip: 4 / 5 / 6 / 7 / 8 = 7,723 / 7,767 / 7,776 / 7,750 / 7,721 on four segments, 10,540 / 10,450 / 10,338 at 5 / 6 / 8 on two)
-    // the pool launches (k_shadow_deferred, k_closest_queue) as PERSISTENT grids: as many waves as the chip holds, each reserving chunks of
-    // `pool` rays through per-queue cursors until every queue is dry; 0 = one workgroup per pool
-    uint32_t persistent = 1;
-    // crt_render_frames, how the samples of a launch sit on the hardware (include/crt.h, option "wave_samples"): 0 = one after the other in
-    // each wave; 1 = side by side on the waves of a workgroup; 2 (default) = four samples of a 4 x 4 pixel quadrant in the lanes of a wave
-    // where the launch allows it (a multiple of 4 samples, a tree of >= 64 nodes, CWBVH), otherwise 1 when the launch is bound by its longest
-    // waves rather than by throughput (use_wave_samples) and 0 when not; 3 = lanes where allowed, else 0
-    uint32_t wave_samples = 2;
-    uint32_t wide_first = 2;            // first-segment kernels built for 6 waves per SIMD: 0 never, 1 always, 2 by the same measure
-    float tile_cost_spread = 0.f;       // 99th percentile of the measured tile costs over their mean; 0 = nothing measured yet
-    int last_launch_form = 0;           // crt_debug_launch_form
-    int last_launch_wide = 0, last_launch_samples = 1, last_launch_one_pass = 0;      // crt_debug_launch_info
-    bool use_wave_samples() const { return wave_samples == 2u ? bound_by_longest_waves() : wave_samples == 1u; }
-    bool bound_by_longest_waves() const {
-        // One wave renders the n samples of its 64 pixels one after the other: the launch cannot end before the most expensive
-        // waves have done n samples, c99 * n, while the chip needs about mean * n * waves / slots for all of them.  When the first
-        // is the larger, the samples go on 4 waves side by side (1 M triangles at 1080p, 8 frames per launch: 1/4 of the frame
-        // 0.133 -> 0.062 ms per frame, 1/8 0.114 -> 0.039; the whole frame is throughput-bound and stays as it is, and so does a
-        // Cornell box down to 1/4 of the frame — its waves are short and four times as many of them cost more than they save).
-        const double waves = (double)(n_local_pixels + 63u) / 64.0, slots = (double)n_cu * 4.0 * 5.0;
-        if (tile_cost_spread == 0.f) return waves <= 2.0 * slots;
-        return (double)tile_cost_spread * slots >= 0.9 * waves;
-    }
-    crt::PathBuffers pb{};
-    uint32_t stack_entries = CRT_STACK_ENTRIES;
-    uint32_t sub_capacity = 0;                // entries per sub-queue (8 per queue)
-    uint32_t* d_counts = nullptr;        // 2 banks (frame parity) of counter(seg, kind, group): kind 0 = rays into segment, 1 = its shadow rays
-    uint32_t bank = 0;                   // bank of the most recent frame
-    bool counts_clean = false;           // both banks known to be zero where the next frame needs them
-    uint32_t* counts() const { return d_counts + (size_t)bank * kCounters; }
-    uint32_t* h_counts = nullptr;        // pinned
-    bool frame_buffers_ready = false;
-
-    crt_camera cam{};
-    bool have_camera = false;
-    uint32_t jitter = 1;
-    bool count_visits = false;
-    bool count_batched = false;               // option count_visits 2: counting frames may share a launch in the timed form (four samples in the lanes of a wave)
-    unsigned long long* d_visit_totals = nullptr;   // [0..3] lane visits: closest nodes/tris, any nodes/tris; [4..7] wave-level steps of the same blocks; [8] closest-hit rays that hit; [10], [11] closest / any-hit node visits of uniform node steps
-    unsigned long long* h_visit_totals = nullptr;   // pinned
-
-    // scratch for crt_trace (host rays)
-    float4* d_t_rays = nullptr; float4* d_t_hits = nullptr; uint32_t* d_t_stats = nullptr; size_t t_cap = 0;
-
-    // telemetry
-    std::vector<EventSpan> spans;
-    int n_spans = 0;
-    crt_frame_stats stats{};
-    bool stats_pending = false;
-    bool stats_from_frame = false;
-    bool stats_counted = false;
-    uint32_t tri_min = 2;                    // traverse_pool vote: node step while node-ready lanes >= tri_min x triangle-waiting lanes
-    // NEE shadow rays: 1 = walked inside k_segment, every segment; 0 = every segment's deferred to ONE any-hit launch behind the last
-    // segment (k_shadow_deferred) with the contributions folded per path in segment order (k_fold_paths); 2 = first segment in place,
-    // bounce segments deferred; 3 (default) = 2 for trees of 64+ nodes (1 M triangles, four segments: 7.23 -> 7.72 Gray/s), else 1
-    uint32_t inplace_shadow = 3;
-    uint32_t accel = 0;                      // frames: 0 CWBVH; 1 BVH2 walked as the shipped shader does (first visited wins); 2 BVH2, lowest id wins
-    uint32_t refill_min = 8;                // walk_pool (crt_trace, k_closest_queue): idle lanes that trigger a refill
-    // crt_trace: rays per wave (its refill pool): 64, 128 or 256.  64 = one lock-step batch per single-wave workgroup: four times the
-    // workgroups for the dispatcher to balance, which is what a launch of a few million rays needs (tools/refill_probe.py, 1 M
-    // triangles: 2.07 M primary rays 0.153 ms against 0.346 with 256-ray pools, whose 8,100 waves all start at once and end with the
-    // slowest; 0.81 M shadow rays 0.192 / 0.202 / 0.230 ms for 64 / 128 / 256; 1.16 M bounce rays 0.332 / 0.320 / 0.321 — the one
-    // case where refill beats the finer grain, by 4 %)
-    uint32_t trace_pool = 64;
-    uint32_t trace_occupancy = 8;            // persistent grids only (oversubscribe >= 1): workgroups per CU
-    // 0: one chunk per workgroup, the hardware dispatcher hands chunks to CUs as they drain (measured 13 % faster than
-    // a persistent grid on the 1 M mesh: per-chunk cost varies 10x between sky and grazing rays);
-    // k >= 1: persistent grid of k x the resident workgroups, static schedule (rt_kernels.hip)
-    uint32_t oversubscribe = 0;
-    bool special_materials = false;          // some material is Mirror_type / Disney_type (albedo.w, Scene.h:111-132): k_segment<MAT>
-    uint32_t waves_per_workgroup = 1;        // 1 = every wave its own workgroup (default), 2, or 4 = 256-thread workgroups
-    uint32_t lanes_per_ray = 8;              // option "lanes_per_ray" (1, 2, 4, 8): how far a ray may spread over the lanes of its draining wave (rt_kernels.hip walk_batch)
-    uint32_t* d_overflow = nullptr;          // dropped stack pushes since scene creation (stays 0 for every accepted tree)
-    float4* d_lfinal = nullptr;              // batched frames on multi-segment paths: per (sample, pixel) final radiance (SegmentArgs::l_final)
-    // bounce rays regrouped by (direction octant, origin cell) between segments (rt_kernels.hpp RayBins).  Tables per segment a ray
-    // can enter (1..16), capacities / offsets twice (frame parity: the launch that consumes a segment's rays reads the layout its
-    // producer used while k_bin_scan already writes the next frame's).
-    // option "ray_bins": 0 (default) = per-group sub-queues in emission order; 1 = bins, the lanes of a wave that share a key take their
-    // places with one atomic; 2 = bins, one atomic per ray; 3 = 1 for the first segment's emission, 2 for the bounce segments'.
-    // Measured on the 1 M-triangle frame, 4 segments, 4 samples per launch: wave-level traversal steps -10 % (lane utilisation of
-    // the closest-hit node block 46.5 -> 51.7 %), frame time +3.6 % / +31 % / +5 % for 1 / 2 / 3 — what the append costs
-    // (a wave of bounce rays holds ~50 different keys) exceeds what the walk gains; profiles/r03_experiments.md.
-    uint32_t ray_bins = 0;
-    bool rows_padded = false;                // d_nodes / d_tris are at the build's stride (CRT_NODE_ROWS / CRT_TRI_ROWS)
-    bool rays_doubled = false;               // the path-ray queues have their overflow half (allocated when the bins are first used)
-    uint32_t* d_bins = nullptr;              // one allocation: count [17][B] | cap [2][17][B] | off [2][17][B] | start [17][B + 1] | ovf [17 x 32]
-    float bounds_lo[3] = {0.f, 0.f, 0.f}, bounds_hi[3] = {1.f, 1.f, 1.f};   // of the vertices: the cell grid of the bins
-    uint32_t* bin_count(uint32_t seg) const { return d_bins + (size_t)seg * CRT_RAY_BINS; }
-    uint32_t* bin_cap(uint32_t par, uint32_t seg) const { return d_bins + (size_t)(17 + par * 17 + seg) * CRT_RAY_BINS; }
-    uint32_t* bin_off(uint32_t par, uint32_t seg) const { return d_bins + (size_t)(17 * 3 + par * 17 + seg) * CRT_RAY_BINS; }
-    uint32_t* bin_start(uint32_t seg) const { return d_bins + (size_t)17 * 5 * CRT_RAY_BINS + (size_t)seg * (CRT_RAY_BINS + 1u); }
-    uint32_t* bin_ovf(uint32_t seg) const { return d_bins + (size_t)17 * 5 * CRT_RAY_BINS + (size_t)17 * (CRT_RAY_BINS + 1u) + (size_t)seg * 32u; }
-    static size_t bins_words() { return (size_t)17 * 5 * CRT_RAY_BINS + (size_t)17 * (CRT_RAY_BINS + 1u) + 17u * 32u; }
-    uint32_t last_build = 1;                 // option "last_build": a one-pass launch that is the path's last segment runs the build compiled as one (k_segment<LAST>)
-    int last_launch_last = 0;                // crt_debug_launch_info: bit 2 of the build word
-    uint32_t lean_build = 1;                 // option "lean_build": such a launch runs that build's LEAN form (k_segment<LAST,LEAN>) where launch_segment finds what the form has compiled in
-    bool tree_validated = false;             // the CWBVH passed crt_scene_create's host validator (validate_cwbvh), whose depth sized the stack: the LEAN form's bare pushes rest on it.
-                                             // A tree built or rebuilt on the device never went through it and keeps the checked pushes
-    int last_launch_lean = 0;                // crt_debug_launch_info: bit 3 of the build word
-    uint32_t debug_fail_batch_alloc = 0;     // test hook (option of the same name): the next growth of the batch buffers fails before it allocates
-    uint32_t batch_cap = 1;                  // samples the path state, the ray queues and d_lfinal are sized for (1 until crt_render_frames needs more)
-    uint32_t samples_in_stats = 1;           // samples per pixel of the launch the pending stats describe (crt_render_frames batches)
-    // event spans behind crt_frame_stats.ms_*: 2 = every launch, 1 = closest-hit launches only, 0 = none (the default: an event-carrying
-    // dispatch cannot overlap its neighbours, ~5 us of stream time per launch — 8 % of a Cornell-box frame, 0.8 % of a 1 M-triangle one)
-    uint32_t timing = 0;
-    bool timing_accumulate = false;          // spans pile up over frames (crt_frame_stats then holds sums) instead of per frame
-
-    // ---- several GPUs behind ONE handle (crt_set_devices): this scene is logical device 0, `peers` are devices 1..n-1, each a
-    // complete scene on its own GPU (replicated buffers, own stream, own shard of the tiles).  Every entry point fans out to them;
-    // crt_read_sum / crt_resolve gather their packed tile buffers to this device and un-tile the whole frame here.
-    std::vector<crt_scene*> peers;           // owned
-    crt_scene* primary = nullptr;            // set in a peer
-    std::vector<std::pair<size_t, size_t>> scene_bufs;   // (offset of the pointer member, bytes): what a replica needs copied
-    uint32_t shard_rank = 0, shard_world = 1; // the caller's shard of the frame (crt_set_shard); rank / world below are this stream's share of it
-    uint32_t streams = 1;                    // option "streams": this many tile shards of the frame on streams of their own, on this one GPU
-    bool shares_scene = false;               // a replica on its primary's own device: the scene buffers are the primary's, not copies
-    std::vector<float*> d_gather;            // per peer, on THIS device: its packed sum buffer as received
-    std::vector<uint2*> d_peer_tiles;        // per peer, on THIS device: its local tile list (for the un-tiling launch)
-    std::vector<hipEvent_t> ev_peer;         // per peer: "your slice has arrived" (copy transport)
-    void* rccl_lib = nullptr;                // dlopen handle; comms[k] = communicator of logical device k
-    std::vector<void*> rccl_comms;
-    uint32_t gather_transport = 0;           // 0 = RCCL send/recv over xGMI, 1 = hipMemcpyPeerAsync (also: virtual devices, RCCL absent)
-    float last_gather_ms = 0.f;
-
-    ~crt_scene() {
-        drop_peers();
-        hipSetDevice(device);
-        if (stream) hipStreamSynchronize(stream);
-        if (inst) crt::instances_unbind(inst, stream);
-        delete refit;
-        delete rebuild;
-        delete intake;
-        delete lit;
-        delete aov;
-        delete denoise;
-        delete temporal;
-        if (shares_scene)                   // borrowed from the primary, which frees them
-            for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
-        void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
-                        d_rays[0], d_rays[1], d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
-                        d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins, d_mesh_base, d_qinst, d_mesh_mtl, d_tex_before};
-        for (void* p : ptrs) if (p) hipFree(p);
-        if (h_tile_cost) hipHostFree(h_tile_cost);
-        if (h_tile_order) hipHostFree(h_tile_order);
-        if (ev_tile_cost) hipEventDestroy(ev_tile_cost);
-        if (ev_tile_order) hipEventDestroy(ev_tile_order);
-        if (h_counts) hipHostFree(h_counts);
-        if (h_rgba) hipHostFree(h_rgba);
-        if (h_visit_totals) hipHostFree(h_visit_totals);
-        for (EventSpan& s : spans) { if (s.a) hipEventDestroy(s.a); if (s.b) hipEventDestroy(s.b); }
-        if (stream) hipStreamDestroy(stream);
-    }
-
-    void drop_peers();      // defined with crt_set_devices
-
-    // grid of a traversal kernel (always a multiple of 8: one slice per XCD group); persistent variant bounded by LDS and registers
-    // (the XCD-aware schedule in rt_kernels.hip groups workgroups by blockIdx & 7)
-    // reg_cap = workgroups per CU the kernel's VGPR count admits (k_segment ~90 VGPRs -> 5, k_trace/k_shadow <= 64 -> 8)
-    // chunk = items one workgroup pass covers: 256 (lock-step kernels) or 1024 (pool kernels)
-    uint32_t trace_grid(uint64_t n, uint32_t reg_cap, uint32_t chunk = CRT_TRACE_BLOCK) const {
-        // every group's share in one pass: group 0 owns ceil(units / 8) units of 4096 items (== sub_capacity for n = P)
-        const uint64_t share = ((n + 4095) / 4096 + 7) / 8 * 4096;
-        uint64_t g = 8 * ((share + chunk - 1) / chunk);
-        if (oversubscribe != 0u) {
-            const uint64_t lds = (uint64_t)(CRT_TRACE_BLOCK / 64) * (stack_entries + CRT_HIT_SLOTS) * 64 * 8;
-            const uint64_t per_cu = std::min<uint64_t>(std::min(trace_occupancy, reg_cap), std::max<uint64_t>(1, (160 * 1024) / lds));
-            g = std::min(g, ((uint64_t)n_cu * per_cu * oversubscribe + 7) / 8 * 8);
-        }
-        return (uint32_t)std::max<uint64_t>(g, 8);
-    }
-    // waves the chip holds at once of a kernel whose wave needs `lds` bytes (handed out in 1,280-byte units) and runs `per_simd` to a SIMD:
-    // the grid of a persistent launch (a multiple of 8: one slice per XCD group)
-    uint32_t resident_waves(size_t lds, uint32_t per_simd) const {
-        const uint64_t units = (lds + 1279) / 1280, by_lds = units ? (160u * 1024u / 1280u) / units : 32u;
-        const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(4ull * per_simd, by_lds));
-        return (uint32_t)((uint64_t)n_cu * per_cu / 8 * 8);
-    }
-    uint32_t flat_grid(uint64_t n) const {
-        uint64_t blocks = (n + 255) / 256;
-        return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cu * 8));
-    }
-    // a span's events are attached to the launches themselves (crt::set_launch_events), not recorded between them
-    EventSpan* new_span(int kind) {
-        if (timing == 0u || (timing == 1u && kind != 1)) return nullptr;
-        if (n_spans >= (int)spans.size()) return nullptr;
-        EventSpan* s = &spans[n_spans];
-        // the events of a span are created the first time it is used: a scene that never asks for timings creates none (272 event creations
-        // were a quarter of a millisecond of every crt_scene_create)
-        if (!s->a && hipEventCreate(&s->a) != hipSuccess) { s->a = nullptr; return nullptr; }
-        if (!s->b && hipEventCreate(&s->b) != hipSuccess) { s->b = nullptr; return nullptr; }
-        ++n_spans;
-        s->kind = kind;
-        return s;
-    }
-};
-
-namespace {
-
 // The tiles of shard `rank` of `world`: the frame's tile x tile squares in Morton order, every world-th one starting at the rank-th
 // (SURVEY 8e).  Pure host arithmetic: crt_set_shard, crt_set_devices, option "streams" and the [host] entry crt_shard_tiles share it.
-void deal_tiles(uint32_t width, uint32_t height, uint32_t T, uint32_t rank, uint32_t world, std::vector<uint2>& tiles, uint64_t* pixels_in_frame) {
+void crt::deal_tiles(uint32_t width, uint32_t height, uint32_t T, uint32_t rank, uint32_t world, std::vector<uint2>& tiles, uint64_t* pixels_in_frame) {
     const uint32_t tx_n = (width + T - 1) / T, ty_n = (height + T - 1) / T;
     struct Item { uint32_t code, x, y; };
     std::vector<Item> all;
@@ -503,6 +76,27 @@ void deal_tiles(uint32_t width, uint32_t height, uint32_t T, uint32_t rank, uint
     }
     if (pixels_in_frame) *pixels_in_frame = in_frame;
 }
+
+crt::FrameArgs crt::frame_args(const crt_scene* s, float rx, float ry) {
+    crt::FrameArgs f{};
+    f.tile_xy = s->d_tile_xy;
+    f.tile_order = s->d_tile_order;
+    f.n_local_pixels = s->n_local_pixels;
+    f.tile = s->tile; f.width = s->width; f.height = s->height;
+    f.tile_log2 = (s->tile & (s->tile - 1u)) == 0u ? (uint32_t)__builtin_ctz(s->tile) : 0u;
+    f.jitter = s->jitter;
+    f.rv = rx * ry;
+    const float W = (float)s->width, H = (float)s->height;
+    f.tan_fov = std::tan(s->cam.fov * 0.5f);
+    f.aspect_tan = W / H * f.tan_fov;
+    for (int k = 0; k < 3; ++k) {
+        f.cam_pos[k] = s->cam.position[k]; f.cam_right[k] = s->cam.right[k];
+        f.cam_up[k] = s->cam.up[k]; f.cam_forward[k] = s->cam.forward[k];
+    }
+    return f;
+}
+
+namespace {
 
 // Logical device k of n_devices, dividing shard base_rank of base_world among themselves (set_devices_of_shard): every n-th tile of that
 // shard's list starting at its k-th, i.e. shard base_rank + k * base_world of base_world * n_devices of the whole frame.
@@ -577,25 +171,6 @@ int alloc_frame_buffers(crt_scene* s) {
     }
     s->frame_buffers_ready = true;
     return CRT_OK;
-}
-
-crt::FrameArgs frame_args(const crt_scene* s, float rx, float ry) {
-    crt::FrameArgs f{};
-    f.tile_xy = s->d_tile_xy;
-    f.tile_order = s->d_tile_order;
-    f.n_local_pixels = s->n_local_pixels;
-    f.tile = s->tile; f.width = s->width; f.height = s->height;
-    f.tile_log2 = (s->tile & (s->tile - 1u)) == 0u ? (uint32_t)__builtin_ctz(s->tile) : 0u;
-    f.jitter = s->jitter;
-    f.rv = rx * ry;
-    const float W = (float)s->width, H = (float)s->height;
-    f.tan_fov = std::tan(s->cam.fov * 0.5f);
-    f.aspect_tan = W / H * f.tan_fov;
-    for (int k = 0; k < 3; ++k) {
-        f.cam_pos[k] = s->cam.position[k]; f.cam_right[k] = s->cam.right[k];
-        f.cam_up[k] = s->cam.up[k]; f.cam_forward[k] = s->cam.forward[k];
-    }
-    return f;
 }
 
 int collect_stats(crt_scene* s) {
@@ -1434,7 +1009,7 @@ int crt_set_shard(crt_scene* s, uint32_t rank, uint32_t world, uint32_t tile) {
     return alloc_frame_buffers(s);
 }
 
-static int ensure_frame(crt_scene* s) {
+extern "C++" int crt::ensure_frame(crt_scene* s) {       // crt_outputs.cpp calls it too (crt_scene.hpp)
     if (!s->frame_buffers_ready) return alloc_frame_buffers(s);
     return CRT_OK;
 }
@@ -2216,140 +1791,6 @@ int crt_copy_packed_device(crt_scene* s, void* d_dst, size_t n_floats, int sync)
     return CRT_OK;
 }
 
-static int gather_peers(crt_scene* s);
-
-static int untile_to_linear(crt_scene* s) {
-    const size_t n = 3 * (size_t)s->width * s->height;
-    if (!s->d_linear) { int rc = dev_alloc(&s->d_linear, n); if (rc) return rc; }
-    HIPCHK(hipMemsetAsync(s->d_linear, 0, n * sizeof(float), s->stream));
-    if (s->n_local_pixels) {
-        const crt::FrameArgs f = frame_args(s, 0.f, 0.f);
-        crt::launch_untile(f, s->d_sum, s->d_linear, s->flat_grid(s->n_local_pixels), s->stream);
-    }
-    if (!s->peers.empty()) {
-        // the other devices' packed tile buffers come to this device ("multi-GPU gather happens inside these"), then
-        // every slice is un-tiled into the one linear frame with its own tile list; tiles are disjoint, so the order does not matter
-        int rc = gather_peers(s);
-        if (rc) return rc;
-        for (size_t k = 0; k < s->peers.size(); ++k) {
-            const crt_scene* p = s->peers[k];
-            if (!p->n_local_pixels) continue;
-            crt::FrameArgs f = frame_args(p, 0.f, 0.f);
-            f.tile_xy = s->d_peer_tiles[k];
-            f.tile_order = nullptr;
-            crt::launch_untile(f, s->d_gather[k], s->d_linear, s->flat_grid(p->n_local_pixels), s->stream);
-        }
-    }
-    return CRT_OK;
-}
-
-int crt_read_sum(crt_scene* s, float* rgb, size_t n_floats) {
-    if (!s || !rgb) return fail(CRT_ERR_INVALID, "crt_read_sum: null argument");
-    if (n_floats != 3 * (size_t)s->width * s->height) return fail(CRT_ERR_INVALID, "crt_read_sum: n_floats must be width*height*3");
-    HIPCHK(hipSetDevice(s->device));
-    int rc = ensure_frame(s);
-    if (rc) return rc;
-    if ((rc = untile_to_linear(s))) return rc;
-    HIPCHK(hipMemcpyAsync(rgb, s->d_linear, n_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return CRT_OK;
-}
-
-int crt_sum_device(crt_scene* s, const float** d_rgb) {
-    if (!s || !d_rgb) return fail(CRT_ERR_INVALID, "crt_sum_device: null argument");
-    *d_rgb = nullptr;
-    HIPCHK(hipSetDevice(s->device));
-    int rc = ensure_frame(s);
-    if (rc) return rc;
-    if ((rc = untile_to_linear(s))) return rc;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    *d_rgb = s->d_linear;
-    return CRT_OK;
-}
-
-// The pinned gamma of the resolve kernels: thr[j] (j = 1..255) = the smallest float x >= 0 whose reference byte
-// (uint8)(clamp01((float)pow((double)x, 1 / 2.2)) * 255 + 0.5) is >= j — pow in double, rounded once.  The byte of any x is then the number of
-// thresholds it has reached, whatever the device's own powf does in its last bits.  (oracle/oracle.c builds the same table by itself.)
-static const float* gamma_thresholds() {
-    static float thr[256];
-    static std::once_flag once;
-    std::call_once(once, [] {
-        auto ref_byte = [](float x) {
-            float v = (float)std::pow((double)x, (double)(1.0f / 2.2f));
-            v = v < 0.f ? 0.f : v > 1.f ? 1.f : v;
-            return (uint32_t)(uint8_t)(v * 255.0f + 0.5f);
-        };
-        thr[0] = 0.f;
-        for (uint32_t j = 1; j < 256u; ++j) {
-            uint32_t lo = 0u, hi = 0x7f800000u;              // bit patterns of the non-negative floats, ordered like their values; ref_byte(+inf) = 255
-            while (lo < hi) {
-                const uint32_t mid = lo + (hi - lo) / 2u;
-                float x; std::memcpy(&x, &mid, 4);
-                if (ref_byte(x) >= j) hi = mid; else lo = mid + 1u;
-            }
-            std::memcpy(&thr[j], &lo, 4);
-        }
-    });
-    return thr;
-}
-
-// tone-mapped RGBA8 of the frame in s->d_rgba (this device), straight from the packed tile buffers: this scene's, and its peers' as gathered
-static int resolve_to_device(crt_scene* s, float inv_count) {
-    const size_t npx = (size_t)s->width * s->height;
-    int rc;
-    if (!s->d_rgba) { if ((rc = dev_alloc(&s->d_rgba, 4 * npx))) return rc; }
-    if (!s->d_gamma) {
-        if ((rc = dev_alloc(&s->d_gamma, 256))) return rc;
-        HIPCHK(hipMemcpy(s->d_gamma, gamma_thresholds(), 256 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    // a shard of a frame (crt_set_shard with world > 1) leaves the other ranks' pixels at 0
-    if (s->shard_world > 1u) HIPCHK(hipMemsetAsync(s->d_rgba, 0, 4 * npx, s->stream));
-    if (s->n_local_pixels) {
-        const crt::FrameArgs f = frame_args(s, 0.f, 0.f);
-        crt::launch_resolve_packed(f, s->d_sum, inv_count, s->d_gamma, s->d_rgba, s->flat_grid(s->n_local_pixels), s->stream);
-    }
-    if (!s->peers.empty()) {
-        if ((rc = gather_peers(s))) return rc;
-        for (size_t k = 0; k < s->peers.size(); ++k) {
-            const crt_scene* p = s->peers[k];
-            if (!p->n_local_pixels) continue;
-            crt::FrameArgs f = frame_args(p, 0.f, 0.f);
-            f.tile_xy = s->d_peer_tiles[k];
-            f.tile_order = nullptr;
-            crt::launch_resolve_packed(f, s->d_gather[k], inv_count, s->d_gamma, s->d_rgba, s->flat_grid(p->n_local_pixels), s->stream);
-        }
-    }
-    return CRT_OK;
-}
-
-int crt_resolve(crt_scene* s, float inv_count, uint8_t* rgba, size_t n_bytes) {
-    if (!s || !rgba) return fail(CRT_ERR_INVALID, "crt_resolve: null argument");
-    const size_t npx = (size_t)s->width * s->height;
-    if (n_bytes != 4 * npx) return fail(CRT_ERR_INVALID, "crt_resolve: n_bytes must be width*height*4");
-    HIPCHK(hipSetDevice(s->device));
-    int rc = ensure_frame(s);
-    if (rc) return rc;
-    if ((rc = resolve_to_device(s, inv_count))) return rc;
-    // through a pinned staging buffer: a copy into pageable memory is staged by the runtime in small pieces (8.3 MB: ~2.5 ms against 0.4)
-    if (!s->h_rgba) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_rgba), 4 * npx));
-    HIPCHK(hipMemcpyAsync(s->h_rgba, s->d_rgba, n_bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    std::memcpy(rgba, s->h_rgba, n_bytes);
-    return CRT_OK;
-}
-
-int crt_resolve_device(crt_scene* s, float inv_count, const uint8_t** d_rgba, int sync) {
-    if (!s || !d_rgba) return fail(CRT_ERR_INVALID, "crt_resolve_device: null argument");
-    *d_rgba = nullptr;
-    HIPCHK(hipSetDevice(s->device));
-    int rc = ensure_frame(s);
-    if (rc) return rc;
-    if ((rc = resolve_to_device(s, inv_count))) return rc;
-    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
-    *d_rgba = s->d_rgba;
-    return CRT_OK;
-}
-
 int crt_get_launch_times(crt_scene* s, float* ms, size_t cap, size_t* n_out) {
     if (!s || !n_out) return fail(CRT_ERR_INVALID, "crt_get_launch_times: null argument");
     HIPCHK(hipSetDevice(s->device));
@@ -2577,7 +2018,7 @@ int crt_get_devices(crt_scene* s, uint32_t* n_devices, int32_t* devices, uint32_
 }
 
 // every peer's packed sum buffer -> d_gather[k] on the primary device, complete in the primary's stream order when this returns
-static int gather_peers(crt_scene* s) {
+extern "C++" int crt::gather_peers(crt_scene* s) {       // for crt_outputs.cpp (crt_scene.hpp)
     const auto t0 = std::chrono::steady_clock::now();
     if (s->gather_transport == 0 && !s->rccl_comms.empty()) {
         // grouped point-to-point: device k sends on its own stream (after its frames), device 0 receives on its stream; each slice
@@ -2734,482 +2175,6 @@ int crt_debug_read_queue(crt_scene* s, int which, uint32_t segment, crt_ray* dst
             done += n;
         }
     }
-    return CRT_OK;
-}
-
-// ---------------------------------------------------------------- crt_render_aov --
-// First-hit feature buffers of the current view: enqueued on the scene's stream behind whatever frames are queued there.
-// Nothing a frame reads or reports is written: not the sum, the counter banks, the spans or the stats.  An instanced scene borrows the
-// frame's segment-0 queue, hit buffers and path state, which every frame writes anew before it reads them.
-
-static int aov_channel_index(uint32_t channel) {
-    switch (channel) {
-        case CRT_AOV_HIT: return 0;
-        case CRT_AOV_IDS: return 1;
-        case CRT_AOV_NORMAL: return 2;
-        case CRT_AOV_ALBEDO: return 3;
-        case CRT_AOV_EMISSION: return 4;
-        default: return -1;
-    }
-}
-
-int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_render_aov: null scene");
-    if (channels == 0u || (channels & ~(uint32_t)CRT_AOV_ALL)) return fail(CRT_ERR_INVALID, "crt_render_aov: channels is a non-empty set of CRT_AOV_* bits");
-    if (!s->have_camera) return fail(CRT_ERR_INVALID, "crt_render_aov: crt_set_camera was never called");
-    if (s->accel != 0u) return fail(CRT_ERR_INVALID, "crt_render_aov: the feature buffers come from the CWBVH walk (option accel is 0): the BVH2 walk has another tie rule");
-    if (s->primary || (!s->peers.empty() && s->streams <= 1u))
-        return fail(CRT_ERR_INVALID, "crt_render_aov: a scene on one device only (crt_set_devices has dealt this one's tiles to several)");
-    HIPCHK(hipSetDevice(s->device));
-    int rc;
-    if (!s->aov) {
-        s->aov = new (std::nothrow) AovState;
-        if (!s->aov) return fail(CRT_ERR_NOMEM, "crt_render_aov: out of host memory");
-    }
-    AovState* const av = s->aov;
-    const size_t n_pixels = (size_t)s->width * s->height;
-    if (n_pixels >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_render_aov: frame too large for 32-bit pixel indices");
-    for (int k = 0; k < 5; ++k)
-        if ((channels >> k & 1u) && !av->d_chan[k]) {
-            float4* p = nullptr;
-            if ((rc = dev_alloc(&p, n_pixels))) return rc;
-            av->d_chan[k] = p;
-        }
-    crt::AovOut out{};
-    out.hit = static_cast<float4*>(av->d_chan[0]); out.ids = static_cast<int4*>(av->d_chan[1]); out.normal = static_cast<float4*>(av->d_chan[2]);
-    out.albedo = static_cast<float4*>(av->d_chan[3]); out.emission = static_cast<float4*>(av->d_chan[4]);
-    if (s->inst) {
-        if ((rc = ensure_frame(s))) return rc;
-        const size_t Q = 8 * (size_t)s->sub_capacity;
-        if (!s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
-        if (!s->d_qinst && (rc = dev_alloc(&s->d_qinst, Q))) return rc;
-        if (!av->d_count && (rc = dev_alloc(&av->d_count, 8 * kCounterStride))) return rc;
-    } else if (!av->d_tile_xy || av->rank != s->shard_rank || av->world != s->shard_world || av->tile != s->tile) {
-        // the caller's shard, dealt as crt_set_shard deals it
-        std::vector<uint2> tiles;
-        try { deal_tiles(s->width, s->height, s->tile, s->shard_rank, s->shard_world, tiles, nullptr); }
-        catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_render_aov: out of host memory (tile list)"); }
-        const uint64_t px = (uint64_t)tiles.size() * s->tile * s->tile;
-        if (px >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_render_aov: shard too large for 32-bit pixel indices");
-        HIPCHK(hipStreamSynchronize(s->stream));                          // an earlier call may still read the old list
-        if (av->d_tile_xy) { (void)hipFree(av->d_tile_xy); av->d_tile_xy = nullptr; }
-        if ((rc = dev_alloc(&av->d_tile_xy, tiles.size()))) return rc;
-        if (!tiles.empty()) HIPCHK(hipMemcpy(av->d_tile_xy, tiles.data(), tiles.size() * sizeof(uint2), hipMemcpyHostToDevice));
-        av->n_local_pixels = (uint32_t)px; av->rank = s->shard_rank; av->world = s->shard_world; av->tile = s->tile;
-    }
-    crt::launch_aov_fill(out, channels, (uint32_t)n_pixels, s->stream);
-    if (s->inst) {
-        if (s->n_local_pixels) {
-            crt::InstancesView v{};
-            crt::instances_view(s->inst, &v);
-            const bool masked = s->instance_masks != 0u;
-            if (masked && (rc = crt::instances_child_masks_for(s->inst, s->stream, &s->cmask_seen))) return rc;
-            HIPCHK(hipMemsetAsync(av->d_count, 0, 8 * kCounterStride * sizeof(uint32_t), s->stream));
-            crt::RaygenArgs ra{};
-            ra.f = frame_args(s, rx, ry);
-            ra.f.tile_order = nullptr;
-            ra.rays = s->d_rays[0]; ra.count = av->d_count; ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
-            ra.zero_counts = nullptr; ra.n_zero = 0;                      // the frames' counter banks stay as the last frame left them
-            crt::launch_raygen(ra, s->stream);
-            crt::InstMaskQueueArgs qa{};
-            qa.nodes = v.nodes; qa.tris = v.tris; qa.inst = v.inst;
-            if (masked) { qa.child_masks = v.child_masks; qa.n_tlas8 = v.tlas_nodes8; qa.ray_mask = s->mask_primary; }
-            qa.rays = s->d_rays[0]; qa.count = av->d_count; qa.hits = s->d_qhits; qa.hit_inst = s->d_qinst;
-            qa.sub_capacity = s->sub_capacity; qa.n_instances = v.n_instances; qa.stack_entries = v.stack_entries;
-            qa.refill_min = 8; qa.tri_min = 2;
-            qa.visit_totals = nullptr; qa.overflow = s->d_overflow;
-            crt::launch_closest_instances_queue(qa, false, masked, s->stream);
-            crt::InstAovArgs a{};
-            a.triangles = s->d_triangles; a.normals = s->d_normals; a.materials = s->d_materials;
-            a.texcoords = s->d_texcoords; a.textures = s->d_textures;
-            a.tex_width = s->tex_width; a.tex_height = s->tex_height; a.n_textures = s->n_textures;
-            a.f = ra.f;
-            a.sub_capacity = s->sub_capacity;
-            a.rays_in = s->d_rays[0]; a.count_in = av->d_count; a.hits_in = s->d_qhits;
-            a.hit_inst = s->d_qinst; a.inst_w2o = v.w2o; a.inst_mesh = v.mesh_of; a.mesh_base = s->d_mesh_base;
-            a.channels = channels; a.out = out;
-            crt::launch_aov_instanced(a, s->stream);
-        }
-    } else if (av->n_local_pixels) {
-        crt::AovArgs a{};
-        a.nodes = s->d_nodes; a.tris = s->d_tris; a.triangles = s->d_triangles; a.normals = s->d_normals; a.materials = s->d_materials;
-        a.stack_entries = s->stack_entries;
-        a.texcoords = s->d_texcoords; a.textures = s->d_textures;
-        a.tex_width = s->tex_width; a.tex_height = s->tex_height; a.n_textures = s->n_textures;
-        a.f = frame_args(s, rx, ry);
-        a.f.tile_xy = av->d_tile_xy; a.f.tile_order = nullptr; a.f.n_local_pixels = av->n_local_pixels;
-        a.overflow = s->d_overflow;
-        a.channels = channels; a.out = out;
-        crt::launch_aov(a, s->stream);
-    }
-    HIPCHK(hipGetLastError());
-    av->rendered |= channels;
-    av->last = channels;
-    if (channels & CRT_AOV_HIT) {                                         // the view crt_temporal reprojects from
-        const crt::FrameArgs f = frame_args(s, rx, ry);
-        for (int k = 0; k < 3; ++k) {
-            s->aov_view.pos[k] = f.cam_pos[k]; s->aov_view.right[k] = f.cam_right[k];
-            s->aov_view.up[k] = f.cam_up[k]; s->aov_view.fwd[k] = f.cam_forward[k];
-        }
-        s->aov_view.aspect_tan = f.aspect_tan; s->aov_view.tan_fov = f.tan_fov; s->aov_view.rv = f.rv; s->aov_view.jitter = f.jitter;
-        s->have_aov_view = true;
-    }
-    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
-    return CRT_OK;
-}
-
-static int aov_channel_of(crt_scene* s, uint32_t channel, const char* who, void** d_ptr) {
-    const int k = aov_channel_index(channel);
-    if (k < 0) return fail(CRT_ERR_INVALID, std::string(who) + ": channel is ONE of the CRT_AOV_* bits");
-    if (!s->aov || !(s->aov->rendered & channel) || !s->aov->d_chan[k]) return fail(CRT_ERR_INVALID, std::string(who) + ": no crt_render_aov call has rendered this channel");
-    *d_ptr = s->aov->d_chan[k];
-    return CRT_OK;
-}
-
-int crt_read_aov(crt_scene* s, uint32_t channel, void* dst, size_t n_bytes) {
-    if (!s || !dst) return fail(CRT_ERR_INVALID, "crt_read_aov: null argument");
-    void* d = nullptr;
-    const int rc = aov_channel_of(s, channel, "crt_read_aov", &d);
-    if (rc) return rc;
-    if (n_bytes != (size_t)s->width * s->height * 16u) return fail(CRT_ERR_INVALID, "crt_read_aov: n_bytes must be width*height*16");
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipMemcpyAsync(dst, d, n_bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return CRT_OK;
-}
-
-int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr) {
-    if (!s || !d_ptr) return fail(CRT_ERR_INVALID, "crt_aov_device: null argument");
-    *d_ptr = nullptr;
-    void* d = nullptr;
-    const int rc = aov_channel_of(s, channel, "crt_aov_device", &d);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    *d_ptr = d;
-    return CRT_OK;
-}
-
-// ---------------------------------------------------------------- crt_denoise --
-// An edge-avoiding a-trous filter over the un-tiled sum, guided by the feature buffers (kernels in denoise.hip): enqueued
-// on the scene's stream behind whatever frames and crt_render_aov calls are queued there.  It reads the sum and four AOV channels and
-// writes only DenoiseState's buffers (and d_linear, which every crt_read_sum / crt_sum_device writes anew).
-
-int crt_denoise(crt_scene* s, float inv_count, const crt_denoise_params* params, int sync) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_denoise: null scene");
-    crt_denoise_params p{};
-    if (params) p = *params;
-    else { p.passes = 5; p.flags = CRT_DENOISE_DEMODULATE; p.sigma_color = 4.0f; p.sigma_depth = 0.05f; p.normal_power_log2 = 7; }
-    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return fail(CRT_ERR_INVALID, "crt_denoise: inv_count must be finite and > 0");
-    if (p.passes < 1u || p.passes > 6u) return fail(CRT_ERR_INVALID, "crt_denoise: passes must be 1..6");
-    if (p.flags & ~(uint32_t)CRT_DENOISE_DEMODULATE) return fail(CRT_ERR_INVALID, "crt_denoise: unknown flag bits");
-    if (p.reserved[0] | p.reserved[1] | p.reserved[2]) return fail(CRT_ERR_INVALID, "crt_denoise: reserved words must be 0");
-    if (p.sigma_color != 0.f && !(std::isfinite(p.sigma_color) && p.sigma_color >= 1e-6f && p.sigma_color <= 1e6f))
-        return fail(CRT_ERR_INVALID, "crt_denoise: sigma_color must be 0 (no colour term) or finite and in [1e-6, 1e6]");
-    if (!(std::isfinite(p.sigma_depth) && p.sigma_depth >= 1e-6f && p.sigma_depth <= 1e6f))
-        return fail(CRT_ERR_INVALID, "crt_denoise: sigma_depth must be finite and in [1e-6, 1e6]");
-    if (p.normal_power_log2 > 10u) return fail(CRT_ERR_INVALID, "crt_denoise: normal_power_log2 must be 0..10");
-    const uint32_t need = CRT_AOV_HIT | CRT_AOV_IDS | CRT_AOV_NORMAL | CRT_AOV_ALBEDO;
-    if (!s->aov || (s->aov->rendered & need) != need)
-        return fail(CRT_ERR_INVALID, "crt_denoise: crt_render_aov must have rendered the HIT, IDS, NORMAL and ALBEDO channels");
-    if (s->shard_world > 1u) return fail(CRT_ERR_INVALID, "crt_denoise: a shard of a frame (crt_set_shard with world > 1) lacks its neighbours' pixels");
-    if (s->primary || (!s->peers.empty() && s->streams <= 1u))
-        return fail(CRT_ERR_INVALID, "crt_denoise: a scene on one device only (crt_set_devices has dealt this one's tiles to several)");
-    int rc = require_device();
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    const size_t n_pixels = (size_t)s->width * s->height;
-    if (n_pixels >= (1ull << 31) / 3u) return fail(CRT_ERR_LIMIT, "crt_denoise: frame too large for 32-bit indices");
-    if ((rc = ensure_frame(s))) return rc;
-    if (!s->denoise) {
-        s->denoise = new (std::nothrow) DenoiseState;
-        if (!s->denoise) return fail(CRT_ERR_NOMEM, "crt_denoise: out of host memory");
-    }
-    DenoiseState* const dn = s->denoise;
-    if (!dn->d_g && (rc = dev_alloc(&dn->d_g, n_pixels))) return rc;
-    if (!dn->d_x[0] && (rc = dev_alloc(&dn->d_x[0], n_pixels))) return rc;
-    if (!dn->d_x[1] && (rc = dev_alloc(&dn->d_x[1], n_pixels))) return rc;
-    if (!dn->d_out && (rc = dev_alloc(&dn->d_out, 3 * n_pixels))) return rc;
-    if ((rc = untile_to_linear(s))) return rc;
-    const uint32_t demodulate = (p.flags & CRT_DENOISE_DEMODULATE) ? 1u : 0u;
-    crt::DenoisePrepareArgs pa{};
-    pa.sum = s->d_linear;
-    pa.hit = static_cast<const float4*>(s->aov->d_chan[0]); pa.ids = static_cast<const int4*>(s->aov->d_chan[1]);
-    pa.normal = static_cast<const float4*>(s->aov->d_chan[2]); pa.albedo = static_cast<const float4*>(s->aov->d_chan[3]);
-    pa.g = dn->d_g; pa.x = dn->d_x[0];
-    pa.n_pixels = (uint32_t)n_pixels; pa.inv_count = inv_count; pa.demodulate = demodulate;
-    crt::launch_denoise_prepare(pa, s->stream);
-    float sigma = p.sigma_color;
-    for (uint32_t i = 0; i < p.passes; ++i) {
-        crt::DenoisePassArgs a{};
-        a.g = dn->d_g; a.x_in = dn->d_x[i & 1u]; a.x_out = dn->d_x[(i & 1u) ^ 1u]; a.out = dn->d_out; a.albedo = pa.albedo;
-        a.width = s->width; a.height = s->height; a.step_log2 = i;
-        a.use_color = p.sigma_color != 0.f ? 1u : 0u;
-        a.inv_c = a.use_color ? 1.0f / (sigma * sigma) : 0.f;
-        a.sigma_depth = p.sigma_depth;
-        a.normal_squarings = p.normal_power_log2;
-        a.demodulate = demodulate;
-        crt::launch_denoise_pass(a, i + 1u == p.passes, s->denoise_form, s->stream);
-        sigma = sigma * 0.5f;
-    }
-    HIPCHK(hipGetLastError());
-    dn->valid = true;
-    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
-    return CRT_OK;
-}
-
-static int denoised_of(crt_scene* s, const char* who) {
-    if (!s->denoise || !s->denoise->valid) return fail(CRT_ERR_INVALID, std::string(who) + ": no crt_denoise call has succeeded on this scene");
-    return CRT_OK;
-}
-
-int crt_read_denoised(crt_scene* s, float* rgb, size_t n_floats) {
-    if (!s || !rgb) return fail(CRT_ERR_INVALID, "crt_read_denoised: null argument");
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = denoised_of(s, "crt_read_denoised"))) return rc;
-    if (n_floats != 3 * (size_t)s->width * s->height) return fail(CRT_ERR_INVALID, "crt_read_denoised: n_floats must be width*height*3");
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipMemcpyAsync(rgb, s->denoise->d_out, n_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return CRT_OK;
-}
-
-int crt_denoised_device(crt_scene* s, const float** d_rgb) {
-    if (!s || !d_rgb) return fail(CRT_ERR_INVALID, "crt_denoised_device: null argument");
-    *d_rgb = nullptr;
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = denoised_of(s, "crt_denoised_device"))) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    *d_rgb = s->denoise->d_out;
-    return CRT_OK;
-}
-
-// the denoised image through crt_resolve's tone map and pinned gamma, into DenoiseState's own RGBA8: crt_resolve_device's stays as it is
-static int resolve_denoised_to_device(crt_scene* s) {
-    DenoiseState* const dn = s->denoise;
-    const size_t npx = (size_t)s->width * s->height;
-    int rc;
-    if (!dn->d_rgba && (rc = dev_alloc(&dn->d_rgba, 4 * npx))) return rc;
-    if (!s->d_gamma) {
-        if ((rc = dev_alloc(&s->d_gamma, 256))) return rc;
-        HIPCHK(hipMemcpy(s->d_gamma, gamma_thresholds(), 256 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    crt::launch_resolve(dn->d_out, (uint32_t)npx, 1.0f, s->d_gamma, dn->d_rgba, s->flat_grid((uint32_t)npx), s->stream);
-    HIPCHK(hipGetLastError());
-    return CRT_OK;
-}
-
-int crt_resolve_denoised(crt_scene* s, uint8_t* rgba, size_t n_bytes) {
-    if (!s || !rgba) return fail(CRT_ERR_INVALID, "crt_resolve_denoised: null argument");
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = denoised_of(s, "crt_resolve_denoised"))) return rc;
-    const size_t npx = (size_t)s->width * s->height;
-    if (n_bytes != 4 * npx) return fail(CRT_ERR_INVALID, "crt_resolve_denoised: n_bytes must be width*height*4");
-    HIPCHK(hipSetDevice(s->device));
-    if ((rc = resolve_denoised_to_device(s))) return rc;
-    if (!s->h_rgba) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_rgba), 4 * npx));
-    HIPCHK(hipMemcpyAsync(s->h_rgba, s->denoise->d_rgba, n_bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    std::memcpy(rgba, s->h_rgba, n_bytes);
-    return CRT_OK;
-}
-
-int crt_resolve_denoised_device(crt_scene* s, const uint8_t** d_rgba, int sync) {
-    if (!s || !d_rgba) return fail(CRT_ERR_INVALID, "crt_resolve_denoised_device: null argument");
-    *d_rgba = nullptr;
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = denoised_of(s, "crt_resolve_denoised_device"))) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    if ((rc = resolve_denoised_to_device(s))) return rc;
-    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
-    *d_rgba = s->denoise->d_rgba;
-    return CRT_OK;
-}
-
-// ---------------------------------------------------------------- crt_temporal --
-// Temporal accumulation by reprojection (kernel in temporal.hip): enqueued on the scene's stream behind whatever frames,
-// crt_render_aov and crt_denoise calls are queued there.  It reads the source image, four AOV channels, its own previous set and an
-// instanced scene's live transforms, and writes only TemporalState's buffers (and d_linear, which every crt_read_sum / crt_sum_device
-// writes anew).  crt_reset never comes here: the history outlives the sum.
-
-int crt_temporal(crt_scene* s, float inv_count, const crt_temporal_params* params, int sync) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_temporal: null scene");
-    crt_temporal_params p{};
-    if (params) p = *params;
-    else { p.flags = CRT_TEMPORAL_DEMODULATE; p.source = CRT_TEMPORAL_SOURCE_SUM; p.max_history = 32; p.sigma_depth = 0.1f; p.normal_min = 0.9f; }
-    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return fail(CRT_ERR_INVALID, "crt_temporal: inv_count must be finite and > 0");
-    if (p.flags & ~(uint32_t)(CRT_TEMPORAL_DEMODULATE | CRT_TEMPORAL_CLAMP)) return fail(CRT_ERR_INVALID, "crt_temporal: unknown flag bits");
-    if (p.source > (uint32_t)CRT_TEMPORAL_SOURCE_DENOISED) return fail(CRT_ERR_INVALID, "crt_temporal: source is CRT_TEMPORAL_SOURCE_SUM or CRT_TEMPORAL_SOURCE_DENOISED");
-    if (p.max_history < 1u || p.max_history > 4096u) return fail(CRT_ERR_INVALID, "crt_temporal: max_history must be 1..4096");
-    if (!(std::isfinite(p.sigma_depth) && p.sigma_depth >= 1e-6f && p.sigma_depth <= 1e6f))
-        return fail(CRT_ERR_INVALID, "crt_temporal: sigma_depth must be finite and in [1e-6, 1e6]");
-    if (!(std::isfinite(p.normal_min) && p.normal_min >= -1.0f && p.normal_min <= 1.0f))
-        return fail(CRT_ERR_INVALID, "crt_temporal: normal_min must be finite and in [-1, 1]");
-    if (p.reserved[0] | p.reserved[1] | p.reserved[2]) return fail(CRT_ERR_INVALID, "crt_temporal: reserved words must be 0");
-    const uint32_t demodulate = (p.flags & CRT_TEMPORAL_DEMODULATE) ? 1u : 0u;
-    const uint32_t need = CRT_AOV_HIT | CRT_AOV_IDS | CRT_AOV_NORMAL | (demodulate ? (uint32_t)CRT_AOV_ALBEDO : 0u);
-    if (!s->aov || (s->aov->rendered & need) != need || !s->have_aov_view)
-        return fail(CRT_ERR_INVALID, "crt_temporal: crt_render_aov must have rendered the HIT, IDS and NORMAL channels, and ALBEDO for CRT_TEMPORAL_DEMODULATE");
-    if (p.source == CRT_TEMPORAL_SOURCE_DENOISED && (!s->denoise || !s->denoise->valid))
-        return fail(CRT_ERR_INVALID, "crt_temporal: source CRT_TEMPORAL_SOURCE_DENOISED needs a successful crt_denoise");
-    if (s->shard_world > 1u) return fail(CRT_ERR_INVALID, "crt_temporal: a shard of a frame (crt_set_shard with world > 1) lacks the rest of the previous frame");
-    if (s->primary || (!s->peers.empty() && s->streams <= 1u))
-        return fail(CRT_ERR_INVALID, "crt_temporal: a scene on one device only (crt_set_devices has dealt this one's tiles to several)");
-    int rc = require_device();
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    const size_t n_pixels = (size_t)s->width * s->height;
-    if (n_pixels >= (1ull << 31) / 3u) return fail(CRT_ERR_LIMIT, "crt_temporal: frame too large for 32-bit indices");
-    if ((rc = ensure_frame(s))) return rc;
-    if (!s->temporal) {
-        s->temporal = new (std::nothrow) TemporalState;
-        if (!s->temporal) return fail(CRT_ERR_NOMEM, "crt_temporal: out of host memory");
-    }
-    TemporalState* const ts = s->temporal;
-    for (int k = 0; k < 2; ++k) {
-        if (!ts->d_hist[k] && (rc = dev_alloc(&ts->d_hist[k], n_pixels))) return rc;
-        if (!ts->d_guide[k] && (rc = dev_alloc(&ts->d_guide[k], n_pixels))) return rc;
-        if (!ts->d_key[k] && (rc = dev_alloc(&ts->d_key[k], n_pixels))) return rc;
-    }
-    if (!ts->d_out && (rc = dev_alloc(&ts->d_out, 3 * n_pixels))) return rc;
-    if (!ts->d_rgba && (rc = dev_alloc(&ts->d_rgba, 4 * n_pixels))) return rc;
-    if (!s->d_gamma) {
-        if ((rc = dev_alloc(&s->d_gamma, 256))) return rc;
-        HIPCHK(hipMemcpy(s->d_gamma, gamma_thresholds(), 256 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    crt::InstancesView v{};
-    if (s->inst) {
-        crt::instances_view(s->inst, &v);                                 // the live arrays, read at enqueue as a frame reads them
-        if (!ts->d_o2w_prev && (rc = dev_alloc(&ts->d_o2w_prev, 12 * (size_t)std::max(v.capacity, 1u)))) return rc;
-    }
-    crt::TemporalArgs a{};
-    if (p.source == CRT_TEMPORAL_SOURCE_SUM) {
-        if ((rc = untile_to_linear(s))) return rc;
-        a.src = s->d_linear; a.scale_source = 1u;
-    } else {
-        a.src = s->denoise->d_out; a.scale_source = 0u;
-    }
-    const uint32_t from = ts->cur, to = ts->cur ^ 1u;
-    a.hit = static_cast<const float4*>(s->aov->d_chan[0]); a.ids = static_cast<const int4*>(s->aov->d_chan[1]);
-    a.normal = static_cast<const float4*>(s->aov->d_chan[2]); a.albedo = static_cast<const float4*>(s->aov->d_chan[3]);
-    a.hist_in = ts->d_hist[from]; a.guide_in = ts->d_guide[from]; a.key_in = ts->d_key[from];
-    a.hist_out = ts->d_hist[to]; a.guide_out = ts->d_guide[to]; a.key_out = ts->d_key[to];
-    a.out = ts->d_out;
-    if (s->inst) {
-        a.o2w = v.o2w; a.w2o = v.w2o; a.o2w_prev = ts->d_o2w_prev;
-        a.n_instances = v.n_instances; a.n_prev_instances = ts->n_prev_instances;
-    }
-    a.width = s->width; a.height = s->height;
-    a.inv_count = inv_count;
-    a.demodulate = demodulate; a.clamp = (p.flags & CRT_TEMPORAL_CLAMP) ? 1u : 0u;
-    // history-less: the first call, after crt_temporal_reset, after a change of the DEMODULATE bit (the history holds the other quantity),
-    // and at max_history 1, where the definition takes y = x
-    a.has_history = (ts->have_history && ts->demodulate == demodulate && p.max_history > 1u) ? 1u : 0u;
-    a.max_history = (float)p.max_history; a.sigma_depth = p.sigma_depth; a.normal_min = p.normal_min;
-    a.cur = s->aov_view; a.prev = ts->prev_view;
-    crt::launch_temporal(a, s->temporal_form, s->stream);
-    HIPCHK(hipGetLastError());
-    if (s->inst && v.n_instances) HIPCHK(hipMemcpyAsync(ts->d_o2w_prev, v.o2w, (size_t)v.n_instances * 48, hipMemcpyDeviceToDevice, s->stream));
-    ts->n_prev_instances = s->inst ? v.n_instances : 0u;
-    ts->cur = to;
-    ts->prev_view = s->aov_view;
-    ts->demodulate = demodulate;
-    ts->have_history = true;
-    ts->valid = true;
-    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
-    return CRT_OK;
-}
-
-int crt_temporal_reset(crt_scene* s) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_temporal_reset: null scene");
-    if (s->temporal) s->temporal->have_history = false;
-    return CRT_OK;
-}
-
-static int temporal_of(crt_scene* s, const char* who) {
-    if (!s->temporal || !s->temporal->valid) return fail(CRT_ERR_INVALID, std::string(who) + ": no crt_temporal call has succeeded on this scene");
-    return CRT_OK;
-}
-
-int crt_read_temporal(crt_scene* s, float* rgb, size_t n_floats) {
-    if (!s || !rgb) return fail(CRT_ERR_INVALID, "crt_read_temporal: null argument");
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = temporal_of(s, "crt_read_temporal"))) return rc;
-    if (n_floats != 3 * (size_t)s->width * s->height) return fail(CRT_ERR_INVALID, "crt_read_temporal: n_floats must be width*height*3");
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipMemcpyAsync(rgb, s->temporal->d_out, n_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    return CRT_OK;
-}
-
-int crt_read_temporal_history(crt_scene* s, float* n, size_t n_floats) {
-    if (!s || !n) return fail(CRT_ERR_INVALID, "crt_read_temporal_history: null argument");
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = temporal_of(s, "crt_read_temporal_history"))) return rc;
-    const size_t npx = (size_t)s->width * s->height;
-    if (n_floats != npx) return fail(CRT_ERR_INVALID, "crt_read_temporal_history: n_floats must be width*height");
-    HIPCHK(hipSetDevice(s->device));
-    std::vector<float4> hist;
-    try { hist.resize(npx); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_read_temporal_history: out of host memory"); }
-    HIPCHK(hipMemcpyAsync(hist.data(), s->temporal->d_hist[s->temporal->cur], npx * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (size_t i = 0; i < npx; ++i) n[i] = hist[i].w;
-    return CRT_OK;
-}
-
-int crt_temporal_device(crt_scene* s, const float** d_rgb) {
-    if (!s || !d_rgb) return fail(CRT_ERR_INVALID, "crt_temporal_device: null argument");
-    *d_rgb = nullptr;
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = temporal_of(s, "crt_temporal_device"))) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    *d_rgb = s->temporal->d_out;
-    return CRT_OK;
-}
-
-// the accumulated image through crt_resolve's tone map and pinned gamma, into TemporalState's own RGBA8
-static int resolve_temporal_to_device(crt_scene* s) {
-    const size_t npx = (size_t)s->width * s->height;
-    crt::launch_resolve(s->temporal->d_out, (uint32_t)npx, 1.0f, s->d_gamma, s->temporal->d_rgba, s->flat_grid((uint32_t)npx), s->stream);
-    HIPCHK(hipGetLastError());
-    return CRT_OK;
-}
-
-int crt_resolve_temporal(crt_scene* s, uint8_t* rgba, size_t n_bytes) {
-    if (!s || !rgba) return fail(CRT_ERR_INVALID, "crt_resolve_temporal: null argument");
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = temporal_of(s, "crt_resolve_temporal"))) return rc;
-    const size_t npx = (size_t)s->width * s->height;
-    if (n_bytes != 4 * npx) return fail(CRT_ERR_INVALID, "crt_resolve_temporal: n_bytes must be width*height*4");
-    HIPCHK(hipSetDevice(s->device));
-    if ((rc = resolve_temporal_to_device(s))) return rc;
-    if (!s->h_rgba) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_rgba), 4 * npx));
-    HIPCHK(hipMemcpyAsync(s->h_rgba, s->temporal->d_rgba, n_bytes, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    std::memcpy(rgba, s->h_rgba, n_bytes);
-    return CRT_OK;
-}
-
-int crt_resolve_temporal_device(crt_scene* s, const uint8_t** d_rgba, int sync) {
-    if (!s || !d_rgba) return fail(CRT_ERR_INVALID, "crt_resolve_temporal_device: null argument");
-    *d_rgba = nullptr;
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = temporal_of(s, "crt_resolve_temporal_device"))) return rc;
-    HIPCHK(hipSetDevice(s->device));
-    if ((rc = resolve_temporal_to_device(s))) return rc;
-    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
-    *d_rgba = s->temporal->d_rgba;
     return CRT_OK;
 }
 

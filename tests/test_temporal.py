@@ -588,3 +588,31 @@ def test_g6_ten_calls_hold_the_memory_of_the_first(cr, cornell, textured, kind):
     sc.close()
     if inst:
         inst.close()
+
+
+@pytest.mark.gpu
+def test_g7_the_three_resolves_share_staging_not_buffers(cr, cornell, textured):
+    """32 x 24 Cornell box, one frame, render_aov, denoise, temporal: the host resolves of the sum, the denoised and the accumulated image
+    go through one pinned staging buffer, each from a device buffer of its own.  Read once each, then again in reverse order with a device
+    resolve between each pair: every host image equals its first reading byte for byte, the three device pointers are pairwise distinct"""
+    mesh, _ = flat_variants(cr, cornell, textured)["cornell"]
+    W, H = 32, 24
+    sc = flat_scene(cr, mesh, cornell[1], "sbvh", W, H, 3)
+    sc.render_frame(*RVS[0])
+    sc.render_aov(*RVS[0])
+    sc.denoise(1.0)
+    sc.temporal(1.0)
+    first = [sc.resolve(1.0), sc.resolve_denoised(), sc.resolve_temporal()]
+    for img in first:
+        assert img.shape == (H, W, 4) and img[..., :3].any()
+    again, pointers = [None, None, None], []
+    again[2] = sc.resolve_temporal()
+    pointers.append(sc.resolve_device(1.0))
+    again[1] = sc.resolve_denoised()
+    pointers.append(sc.resolve_temporal_device())
+    again[0] = sc.resolve(1.0)
+    pointers.append(sc.resolve_denoised_device())
+    for name, a, b in zip(("sum", "denoised", "temporal"), first, again):
+        assert np.array_equal(a, b), name
+    assert all(pointers) and len(set(pointers)) == 3, pointers
+    sc.close()
