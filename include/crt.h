@@ -670,7 +670,10 @@ enum { CRT_TRACE_INSTANCE_MASK = 8 };
  * Numerical contract (tests/test_instances.py holds the kernel to it bit for bit):
  *   - world_to_object (crt_instance_inverse) is computed in double and rounded once to float: the adjugate of A divided by det(A),
  *     det expanded along the first row in the order written, translation 0 - (W_A . t) from the unrounded entries (0 -, so that the
- *     identity maps to the identity bits).
+ *     identity maps to the identity bits).  Written out, with A = (a b c / d e f / g h i), every operation one IEEE double operation:
+ *     c00 = e*i - f*h, c01 = f*g - d*i, c02 = d*h - e*g; det = (a*c00 + b*c01) + c*c02; the adjugate's rows are
+ *     (c00, c*h - b*i, b*f - c*e), (c01, a*i - c*g, c*d - a*f), (c02, b*g - a*h, a*e - b*d); W_A = each entry / det (a division, not a
+ *     multiplication by 1 / det); translation of row (x y z): 0 - ((x*t0 + y*t1) + z*t2) (tests/instanced_ref.py restates it).
  *   - the object ray, each component in fp32 without fma: o'_r = ((W_r0*o.x + W_r1*o.y) + W_r2*o.z) + W_r3,
  *     d'_r = (W_r0*d.x + W_r1*d.y) + W_r2*d.z; d' is NOT renormalised, so t is the same parameter in both spaces and tmax carries over.
  *     An instance whose object_to_world is bitwise the identity uses o' = o, d' = d (signs of zeros kept: exactly a flat trace).

@@ -17,8 +17,9 @@ Shader/path_trace.fs.  What GLSL leaves to the implementation is fixed as DESIGN
   visibility brute force over all triangles: nearest t, equal t to the lowest original id; a shadow ray is blocked by any triangle with
              t < length - eps (hit_shadow, :376-412 and :968)
 
-Scope: Lambert, emissive, textured and Mirror materials of flat (uninstanced) scenes.  Disney materials have no shader text and are not
-restated here.
+Scope: Lambert, emissive, textured and Mirror materials.  Disney materials have no shader text and are not restated here.  `render_frame`
+asks the scene five questions (RefScene.visibility, hit_rows, world_normal, emitter_light, and its light table); RefScene answers them for
+a flat scene, tests/instanced_ref.py for an instanced one, so that one loop serves both.
 """
 import ctypes
 import ctypes.util
@@ -171,6 +172,20 @@ def _pow_double_once(x, e):
 
 # ------------------------------------------------------------------------------------------------ the scene as the shader sees it
 
+def moller_trumbore(o, d, v0, e1, e2):
+    """:322-374 for rays (n, 3) against triangles (m, 3): (u, v, t, accepted) as (n, m) arrays, the bound on t left to the caller"""
+    oo, dd = o[:, None, :], d[:, None, :]
+    v0, e1, e2 = v0[None], e1[None], e2[None]
+    pv = cross(np.broadcast_to(dd, (dd.shape[0],) + e2.shape[1:]), e2)
+    tv = F(oo - v0)
+    qv = cross(tv, e1)
+    u, v, t = dot(tv, pv), dot(dd, qv), dot(e2, qv)
+    inv = F(f32(1.0) / dot(e1, pv))
+    u, v, t = F(u * inv), F(v * inv), F(t * inv)
+    w = F(F(f32(1.0) - u) - v)
+    return u, v, t, (u >= 0) & (v >= 0) & (t >= 0) & (w >= 0)
+
+
 class RefScene:
     """The arrays of a Mesh (source triangle order: a triangle's index is its original id) and a camera."""
 
@@ -199,19 +214,11 @@ class RefScene:
         tri = np.full(n, -1, np.int64)
         tt, uu, vv = np.zeros(n, f32), np.zeros(n, f32), np.zeros(n, f32)
         tmax = np.broadcast_to(F(tmax), (n,))
-        v0, e1, e2 = self.v0[None], self.e1[None], self.e2[None]
         with np.errstate(all="ignore"):
             for a in range(0, n, chunk):
                 sl = slice(a, min(n, a + chunk))
-                oo, dd = o[sl, None, :], d[sl, None, :]
-                pv = cross(np.broadcast_to(dd, (dd.shape[0],) + e2.shape[1:]), e2)
-                tv = F(oo - v0)
-                qv = cross(tv, e1)
-                u, v, t = dot(tv, pv), dot(dd, qv), dot(e2, qv)
-                inv = F(f32(1.0) / dot(e1, pv))
-                u, v, t = F(u * inv), F(v * inv), F(t * inv)
-                w = F(F(f32(1.0) - u) - v)
-                ok = (u >= 0) & (v >= 0) & (t >= 0) & (w >= 0) & (t < tmax[sl, None])
+                u, v, t, ok = moller_trumbore(o[sl], d[sl], self.v0, self.e1, self.e2)
+                ok &= t < tmax[sl, None]
                 key = np.where(ok, t, f32(np.inf))
                 k = np.argmin(key, axis=1)                      # the first index of the minimum: the lowest id among equal t
                 rows = np.arange(k.shape[0])
@@ -219,6 +226,34 @@ class RefScene:
                 tri[sl] = np.where(hit, k, -1)
                 tt[sl], uu[sl], vv[sl] = t[rows, k], u[rows, k], v[rows, k]
         return tri, tt, uu, vv
+
+    # -- what render_frame asks of a scene; tests/instanced_ref.py answers the same questions for an instanced scene.  `hit` is what
+    #    visibility returned: here a triangle's id.  ray_class: 0 the path rays of segment 0, 1 those of later segments, 2 shadow rays.
+    census_keys = ()
+    # True is a deliberate mistake, break 13 of tests/test_instanced_ref.py's sensitivity table (DESIGN.md "Instanced frames as tested"): a
+    # Mirror hit then leaves is_specular as it was, which this module did until that section.  Nothing in the flat tests sets it.
+    mirror_keeps_is_specular = False
+
+    def visibility(self, cen, ray_class, o, d, tmax):
+        return self.closest(o, d, tmax)
+
+    def hit_rows(self, cen, ray_class, hit):
+        """-> (the hit triangles' rows, vn / vt indexing self.N / self.TC; their material indices)"""
+        row = self.tri[hit]
+        return row, row[:, 3]
+
+    def world_normal(self, n_obj, hit):
+        return n_obj
+
+    def shading_ray(self, o, d, hit):
+        return o, d
+
+    def emitter_light(self, cen, ew, hit):
+        """-> (area_pdf rows of the lights an emitter hit names, False where there is no light to weigh against: MIS weight 1)"""
+        return self.lights[ew.astype(np.int64), 15:18], np.ones(ew.shape[0], bool)
+
+    def note(self, cen, what, hit):
+        pass
 
     # -- texture(albedo_textures, vec3(uv, layer)).xyz, the filter as the module docstring defines it
     def sample_albedo(self, u, v, layer):
@@ -302,7 +337,7 @@ def primary_rays(scene, rx, ry, jitter=True):
 # ------------------------------------------------------------------------------------------------ :857-1024
 
 CENSUS_KEYS = ("closest_rays", "shadow_rays", "jitter_x_low", "jitter_x_high", "jitter_y_low", "jitter_y_high", "miss_first", "miss_later",
-               "emitter_direct", "emitter_through_mirror", "emitter_after_bounce_front", "emitter_after_bounce_back",
+               "emitter_direct", "emitter_through_mirror", "emitter_through_mirror_after_bounce", "emitter_after_bounce_front", "emitter_after_bounce_back",
                "emitter_cos_light_le_0", "nee_refused_cos_mtl_flipped_accepts", "nee_refused_cos_mtl", "nee_refused_cos_light",
                "shadow_occluded", "shadow_clear", "flat_normal_hit", "non_unit_normal_hit", "mirror_hit", "textured_hit",
                "onb_singular", "onb_regular", "light_index_clamped")
@@ -326,28 +361,30 @@ def render_frame(scene, rx, ry, max_depth):
     prev_pdf = np.ones(n, f32)
     is_specular = np.ones(n, bool)
     alive = np.ones(n, bool)
-    cen = {k: 0 for k in CENSUS_KEYS}
+    bounced = np.zeros(n, bool)                                                                # census only: the path has left a diffuse surface
+    cen = {k: 0 for k in CENSUS_KEYS + tuple(scene.census_keys)}
     cen.update(jc)
     frames, censuses = [], []
     with np.errstate(all="ignore"):
         for seg in range(max_depth):
             ids = np.nonzero(alive)[0]
             cen["closest_rays"] += int(ids.size)
-            tri, t, u, v = scene.closest(o[ids], d[ids], _INF)
+            tri, t, u, v = scene.visibility(cen, min(seg, 1), o[ids], d[ids], _INF)
             miss = tri < 0
             cen["miss_first" if seg == 0 else "miss_later"] += int(miss.sum())
             alive[ids[miss]] = False                                                        # :1020-1021
             ids, tri, t, u, v = ids[~miss], tri[~miss], t[~miss], u[~miss], v[~miss]
             ro, rd = o[ids], d[ids]
             # ---- :414-489
-            row = scene.tri[tri]
+            row, mtl = scene.hit_rows(cen, min(seg, 1), tri)
             flat = row[:, 7] == 0
             nrm = np.where(flat[:, None], row[:, 4:7].astype(f32),
                            _interp(scene.N[np.where(flat, 0, row[:, 4])], scene.N[np.where(flat, 0, row[:, 5])],
                                    scene.N[np.where(flat, 0, row[:, 6])], u, v) if scene.N.shape[0] else row[:, 4:7].astype(f32)).astype(f32)
+            nrm = scene.world_normal(nrm, tri)
             cen["flat_normal_hit"] += int(flat.sum())
             cen["non_unit_normal_hit"] += int((np.abs(dot(nrm, nrm).astype(f64) - 1.0) > 1e-3).sum())
-            m = scene.mat[row[:, 3]]
+            m = scene.mat[mtl]
             albedo, emission, specular, tex_ind = m[:, 0:4].copy(), m[:, 4:8], m[:, 8:12], m[:, 12:16]
             textured = (tex_ind[:, 0] != f32(-1.0)) & (scene.tex is not None) & (scene.TC.shape[0] > 0)
             if textured.any():
@@ -357,6 +394,7 @@ def render_frame(scene, rx, ry, max_depth):
                 c = scene.sample_albedo(tc[:, 0], tc[:, 1], tex_ind[k, 0].astype(np.int64))
                 albedo[k, 0:3] = _pow_double_once(c, 2.2)                                      # :482
             cen["textured_hit"] += int(textured.sum())
+            scene.note(cen, "textured", tri[textured])
             # ---- :872-877
             original_n = nrm
             cos_incident = dot(rd, nrm)
@@ -368,6 +406,7 @@ def render_frame(scene, rx, ry, max_depth):
             e1 = emit & spec_here
             L[ids[e1]] = F(L[ids[e1]] + F(T[ids[e1]] * emission[e1, 0:3]))
             cen["emitter_direct" if seg == 0 else "emitter_through_mirror"] += int(e1.sum())
+            cen["emitter_through_mirror_after_bounce"] += int((e1 & bounced[ids]).sum())
             e2 = emit & ~spec_here
             if e2.any():
                 k = np.nonzero(e2)[0]
@@ -376,22 +415,23 @@ def render_frame(scene, rx, ry, max_depth):
                 ld = normalize(ld)
                 cos_light = F(f32(-1.0) * dot(ld, nrm[k]))
                 length2 = F(ln * ln)
-                li = emission[k, 3].astype(np.int64)
-                ap = scene.lights[li, 15:18]
+                ap, weighed = scene.emitter_light(cen, emission[k, 3], tri[k])
                 pdf_light = F(F(length2 / F(ap[:, 0] * cos_light)) * ap[:, 1])
                 a2 = F(prev_pdf[ids[k]] * prev_pdf[ids[k]])
-                mis = F(a2 / F(F(pdf_light * pdf_light) + a2))                                 # :214-218
+                mis = np.where(weighed, F(a2 / F(F(pdf_light * pdf_light) + a2)), f32(1.0)).astype(f32)   # :214-218
                 L[ids[k]] = F(L[ids[k]] + F(F(T[ids[k]] * emission[k, 0:3]) * mis[:, None]))
                 cen["emitter_cos_light_le_0"] += int((~(cos_light > 0)).sum())
                 cen["emitter_after_bounce_front"] += int(((cos_light > 0) & ~flipped[k]).sum())
                 cen["emitter_after_bounce_back"] += int(((cos_light > 0) & flipped[k]).sum())
             alive[ids[emit]] = False
             keep = ~emit
-            ids, t, ro, rd = ids[keep], t[keep], ro[keep], rd[keep]
+            ids, t, tri = ids[keep], t[keep], tri[keep]
+            ro, rd = scene.shading_ray(ro[keep], rd[keep], tri)
             nrm, original_n, albedo, specular = nrm[keep], original_n[keep], albedo[keep], specular[keep]
             hit_point = F(F(ro + F(rd * t[:, None])) + F(nrm * f32(0.0002)))                  # :930
             mirror = albedo[:, 3] == MIRROR_TYPE
             cen["mirror_hit"] += int(mirror.sum())
+            scene.note(cen, "mirror", tri[mirror])
             # ---- :938-1002 next-event estimation
             nee = (specular[:, 3] == f32(0.0)) & ~mirror
             k = np.nonzero(nee)[0]
@@ -403,6 +443,7 @@ def render_frame(scene, rx, ry, max_depth):
                 li = F(r0 * f32(n_lights)).astype(np.int64)                                  # :940
                 cen["light_index_clamped"] += int((li > n_lights - 1).sum())
                 li = np.minimum(li, n_lights - 1)
+                scene.note(cen, "nee_light", li)
                 lt = scene.lights[li]
                 s = np.sqrt(r1)                                                                # :849-854
                 b0 = F(f32(1.0) - s)
@@ -422,7 +463,7 @@ def render_frame(scene, rx, ry, max_depth):
                 cen["shadow_rays"] += int(sh.size)
                 if sh.size:
                     ks = k[sh]
-                    blocked = scene.closest(hit_point[ks], ld[sh], F(ln[sh] - _EPS))[0] >= 0    # :968
+                    blocked = scene.visibility(cen, 2, hit_point[ks], ld[sh], F(ln[sh] - _EPS))[0] >= 0    # :968
                     cen["shadow_occluded"] += int(blocked.sum())
                     cen["shadow_clear"] += int((~blocked).sum())
                     c = sh[~blocked]
@@ -441,6 +482,8 @@ def render_frame(scene, rx, ry, max_depth):
                 dn = dot(rd[k], nn)
                 refl = F(rd[k] - F(nn * F(f32(2.0) * dn)[:, None]))
                 T[ids[k]] = F(T[ids[k]] * albedo[k, 0:3])
+                if not scene.mirror_keeps_is_specular:
+                    is_specular[ids[k]] = True                                                 # §2: the next emitter hit takes the :896 branch
                 o[ids[k]], d[ids[k]] = hit_point[k], refl
             # ---- :1005-1018 the cosine bounce
             k = np.nonzero(~mirror)[0]
@@ -463,6 +506,7 @@ def render_frame(scene, rx, ry, max_depth):
             prev_pdf[gk] = F(F(dot(sd, nk) * f32(1.0)) / _PI)
             T[gk] = F(T[gk] * albedo[k, 0:3])
             is_specular[gk] = False
+            bounced[gk] = True
             o[gk], d[gk] = hit_point[k], sd
             frames.append(L.reshape(scene.H, scene.W, 3).copy())
             censuses.append(dict(cen))
@@ -481,7 +525,7 @@ def render(scene, rvs, max_depth):
         census.append(cens)
         for k in range(max_depth):
             sums[k] = F(frames[k] + sums[k])
-    total = [{key: sum(c[k][key] for c in census) for key in CENSUS_KEYS} for k in range(max_depth)]
+    total = [{key: sum(c[k][key] for c in census) for key in census[0][k]} for k in range(max_depth)]
     return sums, radiance, total, census
 
 
