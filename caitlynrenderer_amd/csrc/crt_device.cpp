@@ -117,9 +117,10 @@ int build_shard(crt_scene* s) {
 void free_frame_buffers(crt_scene* s) {
     void** ptrs[] = {(void**)&s->d_tile_xy, (void**)&s->d_tile_order, (void**)&s->d_tile_cost, (void**)&s->d_sum, (void**)&s->d_linear, (void**)&s->d_rgba, (void**)&s->d_rays[0],
                      (void**)&s->d_rays[1], (void**)&s->d_nee, (void**)&s->d_contrib, (void**)&s->d_nee_perm, (void**)&s->d_qhits, (void**)&s->pb.L, (void**)&s->pb.T, (void**)&s->pb.seed,
-                     (void**)&s->d_lfinal, (void**)&s->d_qinst};
+                     (void**)&s->d_lfinal, (void**)&s->d_qinst, (void**)&s->d_rays_lens};
     for (void** p : ptrs) { if (*p) hipFree(*p); *p = nullptr; }
     s->batch_cap = 1;
+    s->lens_sub_capacity = 0;
     s->defer_cap = s->defer_regions = s->defer_sub_capacity = s->lfinal_cap = 0;
     // the bins' capacities and offsets describe the queues that were just freed: back to "everything overflows"
     if (s->d_bins) (void)hipMemset(s->d_bins, 0, crt_scene::bins_words() * sizeof(uint32_t));
@@ -983,6 +984,11 @@ int crt_scene_destroy(crt_scene* s) {
 
 int crt_set_camera(crt_scene* s, const crt_camera* cam) {
     if (!s || !cam) return fail(CRT_ERR_INVALID, "crt_set_camera: null argument");
+    // the thin lens (include/crt.h at crt_camera): checked before anything is stored, so that a refused call leaves this scene and every
+    // peer with the camera they had
+    if (!(cam->aperture >= 0.0f) || std::isinf(cam->aperture)) return fail(CRT_ERR_INVALID, "crt_set_camera: aperture must be finite and >= 0");
+    if (cam->aperture > 0.0f && !(cam->focal_dist > 0.0f && std::isfinite(cam->focal_dist)))
+        return fail(CRT_ERR_INVALID, "crt_set_camera: focal_dist must be finite and > 0 when aperture > 0");
     if (!s->have_camera || std::memcmp(&s->cam, cam, sizeof *cam) != 0) s->tile_state = crt_scene::TILES_WANT;   // a new view: new tile costs
     s->cam = *cam;
     s->have_camera = true;
@@ -1212,8 +1218,25 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
     int rc = ensure_frame(s);
     if (rc) return rc;
     if (s->n_local_pixels == 0) return CRT_OK;
-    const bool batched_paths = n_samples > 1u && s->max_depth > 1u;       // finished paths leave their radiance in d_lfinal
+    const bool lens = s->lens() && !s->inst;                              // a flat scene's frame through a lens: every segment queue-fed
+    const bool batched_paths = n_samples > 1u && (s->max_depth > 1u || lens);     // finished paths leave their radiance in d_lfinal
+    if (lens && !s->d_rays[0]) {
+        // a one-segment scene held no queues and no path state until its camera got an aperture: one sample's worth, as alloc_frame_buffers sizes them
+        const size_t P = s->n_local_pixels, Q1 = 8 * (size_t)s->sub_capacity;
+        if ((rc = dev_alloc(&s->d_rays[0], 2 * Q1)) || (rc = dev_alloc(&s->d_rays[1], 2 * Q1))) return rc;
+        s->rays_doubled = false;
+        if (!s->pb.L && (rc = dev_alloc(&s->pb.L, P))) return rc;
+        if (!s->pb.T && (rc = dev_alloc(&s->pb.T, P))) return rc;
+        if (!s->pb.seed && (rc = dev_alloc(&s->pb.seed, P))) return rc;
+    }
     if (batched_paths && (rc = ensure_batch_buffers(s, n_samples))) return rc;   // grows to the largest batch ever asked for
+    if (lens && (!s->d_rays_lens || s->lens_sub_capacity != s->sub_capacity)) {
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (s->d_rays_lens) { (void)hipFree(s->d_rays_lens); s->d_rays_lens = nullptr; }
+        if ((rc = dev_alloc(&s->d_rays_lens, 2 * 8 * (size_t)s->sub_capacity))) return rc;
+        s->lens_sub_capacity = s->sub_capacity;
+    }
+    if (lens && (rc = ensure_lfinal(s))) return rc;                       // a lens frame always folds
     if (first_deferred_segment(s) < s->max_depth && ((rc = ensure_lfinal(s)) || (rc = ensure_defer_buffers(s)))) return rc;
     if (s->count_visits && !s->d_visit_totals) {
         if ((rc = dev_alloc(&s->d_visit_totals, 16))) return rc;
@@ -1221,7 +1244,7 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
     }
     // the hit buffer of the bounce pools (bounce_refill = 1): allocated by the first frame that needs it
     const size_t Q = 8 * (size_t)s->sub_capacity;
-    if (((s->bounce_refill && s->max_depth > 1) || s->inst) && !s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
+    if (((s->bounce_refill && (s->max_depth > 1 || lens)) || s->inst) && !s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
     if (s->inst && !s->d_qinst && (rc = dev_alloc(&s->d_qinst, Q))) return rc;
     if (uses_ray_bins(s)) {
         if (!s->d_bins) {
@@ -1273,7 +1296,14 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
     ra.f.tile_order = nullptr;                      // the adaptive tile order belongs to the fused first-segment kernel
     ra.rays = s->d_rays[0]; ra.count = cnt + counter_index(0, 0, 0); ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
     ra.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; ra.n_zero = kCounters;
-    timed(0, [&] { crt::launch_raygen(ra, s->stream); });
+    if (s->lens()) {                                // the thin-lens form of it, one sample per chain as every instanced frame
+        crt::LensRaygenArgs la{};
+        static_cast<crt::RaygenArgs&>(la) = ra;
+        la.aperture = s->cam.aperture; la.focal_dist = s->cam.focal_dist; la.n_samples = 1u; la.rv_s[0] = rx * ry;
+        timed(0, [&] { crt::launch_raygen_lens(la, s->stream); });
+    } else {
+        timed(0, [&] { crt::launch_raygen(ra, s->stream); });
+    }
     for (uint32_t b = 0; b < s->max_depth; ++b) {
         crt::InstMaskQueueArgs qa{};
         qa.nodes = v.nodes; qa.tris = v.tris; qa.inst = v.inst;
@@ -1325,7 +1355,7 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
     s->stats_pending = true;
     s->stats_from_frame = true;
     s->samples_in_stats = 1;
-    s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0; s->last_launch_last = 0; s->last_launch_lean = 0;
+    s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0; s->last_launch_last = 0; s->last_launch_lean = 0; s->last_launch_lens = s->lens() ? 1 : 0;
     return CRT_OK;
 }
 
@@ -1337,10 +1367,13 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
     if (s->n_local_pixels == 0) return CRT_OK;
     if (s->inst) return render_instanced_async(s, rxs[0], rys[0]);      // one sample per launch chain (batch_limit)
     const uint32_t P = s->n_local_pixels;
-    const bool batched_paths = n_samples > 1u && s->max_depth > 1u;
+    // A camera with an aperture: k_raygen_lens writes segment 0's rays and path state, and EVERY segment runs in its
+    // queue-fed form; the fused first-segment kernels, their tile order and their sample forms are not involved
+    const bool lens = s->lens();
+    const bool batched_paths = n_samples > 1u && (s->max_depth > 1u || lens);
     const uint32_t first_deferred = first_deferred_segment(s);         // segments from here on leave their shadow rays to k_shadow_deferred
     const bool any_deferred = first_deferred < s->max_depth;
-    const bool folds = batched_paths || any_deferred;                   // finished paths leave their radiance in d_lfinal, k_fold_paths adds it to the sum
+    const bool folds = batched_paths || any_deferred || lens;           // finished paths leave their radiance in d_lfinal, k_fold_paths adds it to the sum
     const size_t n_paths = (size_t)P * n_samples;
     const float rx = rxs[0], ry = rys[0];
     const crt::FrameArgs f = frame_args(s, rx, ry);
@@ -1350,7 +1383,7 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
     // memset is only needed for the very first frame (or after a failed launch left the banks in an unknown state)
     // tile order: adopt a finished measurement, start one if the view is new
     bool measure_tiles = false;
-    if (s->adaptive_tiles && s->n_local_tiles > 1 && !s->capturing) {
+    if (s->adaptive_tiles && s->n_local_tiles > 1 && !s->capturing && !lens) {      // a lens frame leaves the tile order and its measurement as they are
         const bool arrived = s->tile_state == crt_scene::TILES_PENDING && hipEventQuery(s->ev_tile_cost) == hipSuccess;
         (void)hipGetLastError();                                    // "not ready" is an answer, not an error to report later
         if (arrived) {
@@ -1402,7 +1435,21 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
     s->counts_clean = false;
     uint32_t* const cnt = s->counts();
 
+    if (lens) {
+        crt::LensRaygenArgs ra{};
+        ra.f = f;
+        ra.f.tile_order = nullptr;                      // storage order: the tile order belongs to the fused first-segment kernels
+        ra.rays = s->d_rays_lens; ra.count = cnt + counter_index(0, 0, 0); ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
+        ra.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; ra.n_zero = kCounters;
+        ra.aperture = s->cam.aperture; ra.focal_dist = s->cam.focal_dist; ra.n_samples = n_samples;
+        for (uint32_t k = 0; k < 8u; ++k) ra.rv_s[k] = k < n_samples ? rxs[k] * rys[k] : 0.f;
+        EventSpan* sp = s->new_span(0);                 // the kernel carries no events of its own: recorded around it, as for an instanced frame
+        if (sp) (void)hipEventRecord(sp->a, s->stream);
+        crt::launch_raygen_lens(ra, s->stream);
+        if (sp) (void)hipEventRecord(sp->b, s->stream);
+    }
     for (uint32_t b = 0; b < s->max_depth; ++b) {
+        const bool first = b == 0 && !lens;             // the fused first-segment kernels; false = a queue-fed segment
         crt::SegmentArgs sa{};
         sa.nodes = s->d_nodes; sa.planes = s->d_planes; sa.tris = s->d_tris; sa.triangles = s->d_triangles; sa.normals = s->d_normals;
         sa.materials = s->d_materials; sa.lights = s->d_lights; sa.n_lights = (int32_t)s->n_lights;
@@ -1434,7 +1481,7 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
             }
         }
         if (bins && b > 0) { sa.bin_start = s->bin_start(b); sa.bin_off_in = s->bin_off(s->bank, b); sa.ovf_base_in = Qe; }
-        sa.rays_in = s->d_rays[b & 1]; sa.count_in = cnt + counter_index(b, 0, 0);
+        sa.rays_in = (lens && b == 0) ? s->d_rays_lens : s->d_rays[b & 1]; sa.count_in = cnt + counter_index(b, 0, 0);
         sa.rays_next = s->d_rays[(b + 1) & 1]; sa.count_next = cnt + counter_index(b + 1, 0, 0);
         sa.count_shadow = cnt + counter_index(b, 1, 0);
         if (!inplace) {
@@ -1448,17 +1495,17 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         sa.last_segment = (b + 1 == s->max_depth) ? 1u : 0u;
         sa.visit_totals = s->d_visit_totals;
         sa.overflow = s->d_overflow;
-        if (b == 0) { sa.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; sa.n_zero = kCounters; }
+        if (first) { sa.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; sa.n_zero = kCounters; }
         sa.l_final = folds ? s->d_lfinal : nullptr;
-        sa.tile_cost = (b == 0 && measure_tiles) ? s->d_tile_cost : nullptr;
-        sa.n_samples = b == 0 ? n_samples : 1u;
+        sa.tile_cost = (first && measure_tiles) ? s->d_tile_cost : nullptr;
+        sa.n_samples = first ? n_samples : 1u;
         // how the samples of a batched launch sit on the hardware (option "wave_samples"): 2 = four samples of a 4 x 4 pixel quadrant in
         // the lanes of one wave — the 64 rays of a wave leave a quarter of the area and agree on their nodes like the rays of a frame of
         // twice the resolution (1 M triangles, 1080p: +8.5 % at 4 samples per launch, +12 % at 8; shards gain as well; trees of a few
         // nodes lose 9 %: more, shorter waves) —, 1 = the samples on the waves of a workgroup, 0 = one after the other in each wave
         const bool lanes_ok = (n_samples & 3u) == 0u && !small_tree && !bvh2;
         sa.wave_samples = 0u;
-        if (b == 0 && n_samples > 1u) {
+        if (first && n_samples > 1u) {
             if (lanes_ok && s->wave_samples >= 2u) sa.wave_samples = 2u;
             else if (s->wave_samples != 3u && s->use_wave_samples()) sa.wave_samples = 1u;
         }
@@ -1470,13 +1517,13 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         bool wide_auto = !s->bound_by_longest_waves();
         if (sa.wave_samples == 2u)
             wide_auto = (double)(s->n_local_pixels / 16u) * (double)(n_samples / 4u) >= 8.0 * (double)s->n_cu * 4.0 * 6.0;
-        sa.wide_first = (b == 0 && (s->wide_first == 2u ? wide_auto : s->wide_first != 0u)) ? 1u : 0u;
+        sa.wide_first = (first && (s->wide_first == 2u ? wide_auto : s->wide_first != 0u)) ? 1u : 0u;
         if (b == 0) { s->last_launch_form = (int)sa.wave_samples; s->last_launch_samples = (int)n_samples; }
         for (uint32_t k = 0; k < 8u; ++k) sa.rv_s[k] = k < n_samples ? rxs[k] * rys[k] : 0.f;
         sa.last_build = s->last_build;
         EventSpan* sp = s->new_span(1);
         // option bounce_refill: the closest hits of a bounce segment through lane-refill pools (k_closest_queue), then a shade-only pass
-        const bool pretraced = b > 0 && s->bounce_refill && !small_tree && !bvh2 && s->tri_min != 0u && !bins;
+        const bool pretraced = !first && s->bounce_refill && !small_tree && !bvh2 && s->tri_min != 0u && !bins;
         if (pretraced) {
             crt::QueueTraceArgs qa{};
             qa.nodes = s->d_nodes; qa.tris = s->d_tris; qa.rays = sa.rays_in; qa.count = sa.count_in; qa.hits = s->d_qhits;
@@ -1494,9 +1541,9 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         // sub-queue gets the rays of that group's units of 4096 pixels — ceil(units / 8) of them — times the samples of the launch.
         // (P * n_samples spread evenly over the 8 groups is fewer chunks than that when the units do not divide by 8.)
         uint32_t grid = s->trace_grid(P, sa.wide_first ? 6 : 5);
-        if (b > 0 && batched_paths) grid *= n_samples;
-        const int build = crt::launch_segment(sa, b == 0, pretraced, inplace, bvh2, s->special_materials, s->count_visits, s->lean_build != 0u && s->tree_validated, grid, s->waves_per_workgroup, s->stream);
-        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; s->last_launch_last = (build >> 2) & 1; s->last_launch_lean = (build >> 3) & 1; }
+        if (!first && batched_paths) grid *= n_samples;
+        const int build = crt::launch_segment(sa, first, pretraced, inplace, bvh2, s->special_materials, s->count_visits, s->lean_build != 0u && s->tree_validated, grid, s->waves_per_workgroup, s->stream);
+        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; s->last_launch_last = (build >> 2) & 1; s->last_launch_lean = (build >> 3) & 1; s->last_launch_lens = lens ? 1 : 0; }
         if (sa.bins_out.count) {
             // fill counts -> the next launch's index space and ray count, and the next frame's capacities (the other parity)
             crt::BinScanArgs ba{};
@@ -1595,6 +1642,14 @@ static int ensure_batch_buffers(crt_scene* s, uint32_t cap) {
 // how many samples one launch may render: more than one only when nothing travels between launches (one path segment, shadow
 // rays walked in place) — bounce queues and the shadow queue hold one entry per pixel
 static uint32_t batch_limit(const crt_scene* s) {
+    if (s->lens() && !s->inst) {
+        // a frame through a lens: every segment is queue-fed, so the samples of a chain keep their own path state and queue
+        // entries whatever the depth and wherever the shadow rays are walked — the rule for multi-segment paths below.  Counting frames and
+        // the BVH2 frame mode run one by one, as without a lens
+        if (s->count_visits || s->accel != 0u) return 1u;
+        const uint64_t fit = s->n_local_pixels ? 0x7fffffffull / s->n_local_pixels : 8ull;
+        return (uint32_t)std::min<uint64_t>(8ull, std::max<uint64_t>(1ull, fit));
+    }
     // the batched builds of the first segment walk its shadow rays in place; counting frames run one by one
     if (first_deferred_segment(s) == 0u || (s->count_visits && !s->count_batched)) return 1u;
     if (s->accel != 0u) return 1u;                                     // the BVH2 frame mode (a comparison aid) has no batched build
@@ -1637,7 +1692,7 @@ int crt_render_frames_async(crt_scene* s, uint32_t n, const float* rx, const flo
     if (!s) return fail(CRT_ERR_INVALID, "crt_render_frames: null scene");
     if (n && (!rx || !ry)) return fail(CRT_ERR_INVALID, "crt_render_frames: null argument");
     const uint32_t lim = batch_limit(s);
-    const bool fours = s->wave_samples >= 2u && s->info.n_nodes8 >= 64 && s->accel == 0u;     // launches that can put 4 samples in the lanes of a wave
+    const bool fours = s->wave_samples >= 2u && s->info.n_nodes8 >= 64 && s->accel == 0u && !s->lens();     // launches that can put 4 samples in the lanes of a wave
     for (uint32_t i = 0; i < n;) {
         uint32_t k = std::min(lim, n - i);
         if (fours && k > 4u && (k & 3u)) k &= ~3u;                       // 7 frames = 4 + 3, not 7 one after the other
@@ -2090,7 +2145,7 @@ int crt_debug_step_hist(crt_scene* s, unsigned long long* hist) {
 
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]) {
     if (!s || !info) return fail(CRT_ERR_INVALID, "crt_debug_launch_info: null argument");
-    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1) | (s->last_launch_last << 2) | (s->last_launch_lean << 3); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
+    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1) | (s->last_launch_last << 2) | (s->last_launch_lean << 3) | (s->last_launch_lens << 4); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
     return CRT_OK;
 }
 
@@ -2157,7 +2212,7 @@ int crt_debug_read_queue(crt_scene* s, int which, uint32_t segment, crt_ray* dst
     if (which != 2 && s->d_bins && s->ray_bins) return fail(CRT_ERR_INVALID, "crt_debug_read_queue: the path-ray queue is binned (option ray_bins 0 gives the sub-queue form this reads)");
     const uint32_t first_def = first_deferred_segment(s);
     const float4* src = which == 2 ? ((s->d_nee && segment >= first_def && segment - first_def < s->defer_regions) ? s->d_nee + 2 * (size_t)(segment - first_def) * 8u * s->sub_capacity : nullptr)
-                                   : s->d_rays[segment & 1];
+                                   : (segment == 0 && s->lens() && !s->inst) ? s->d_rays_lens : s->d_rays[segment & 1];      // a lens frame's primary rays keep a queue of their own
     if (!src) return fail(CRT_ERR_INVALID, "crt_debug_read_queue: that queue does not exist (shadow rays: only of segments that defer them, inplace_shadow 0 / 2; path queues: max_depth > 1)");
     const size_t entry = sizeof(crt_ray);        // a deferred shadow ray is (o, tmax) (d, contribution slot)
     size_t total = 0;

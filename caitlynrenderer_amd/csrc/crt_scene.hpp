@@ -228,7 +228,12 @@ struct crt_scene {
     uint8_t* d_rgba = nullptr;
     uint8_t* h_rgba = nullptr;           // pinned staging buffer of crt_resolve
     float* d_gamma = nullptr;            // the 256 thresholds of the pinned gamma (resolve kernels)
-    float4* d_rays[2] = {nullptr, nullptr};   // path-ray queues, only for max_depth > 1
+    float4* d_rays[2] = {nullptr, nullptr};   // path-ray queues: max_depth > 1, instanced scenes, and from the first frame through a lens on
+    // the primary rays of a frame through a lens (camera aperture > 0; k_raygen_lens): a queue of their own, which no later segment of the
+    // frame writes over, sized like one of d_rays for the sub_capacity in force (crt_debug_read_queue(0, 0) reads it)
+    float4* d_rays_lens = nullptr;
+    uint32_t lens_sub_capacity = 0;
+    bool lens() const { return cam.aperture > 0.0f; }     // crt_set_camera has checked the two fields
     // DEFERRED NEE shadow rays (option "inplace_shadow" 0 / 2, rt_kernels.hip k_segment<!INPLACE>): the frame's NEE queue — one region per
     // deferring segment, 8 sub-queues each, 2 x float4 per ray: (o, tmax) (d, contribution slot) — and the contribution slots, one per
     // (deferring segment, path): (C | T e, visibility word)
@@ -352,6 +357,7 @@ struct crt_scene {
     bool tree_validated = false;             // the CWBVH passed crt_scene_create's host validator (validate_cwbvh), whose depth sized the stack: the LEAN form's bare pushes rest on it.
                                              // A tree built or rebuilt on the device never went through it and keeps the checked pushes
     int last_launch_lean = 0;                // crt_debug_launch_info: bit 3 of the build word
+    int last_launch_lens = 0;                // crt_debug_launch_info: bit 4 of the build word: segment 0 was fed by the lens ray generator
     uint32_t debug_fail_batch_alloc = 0;     // test hook (option of the same name): the next growth of the batch buffers fails before it allocates
     uint32_t batch_cap = 1;                  // samples the path state, the ray queues and d_lfinal are sized for (1 until crt_render_frames needs more)
     uint32_t samples_in_stats = 1;           // samples per pixel of the launch the pending stats describe (crt_render_frames batches)
@@ -392,7 +398,7 @@ struct crt_scene {
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
-                        d_rays[0], d_rays[1], d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
+                        d_rays[0], d_rays[1], d_rays_lens, d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
                         d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins, d_mesh_base, d_qinst, d_mesh_mtl, d_tex_before};
         for (void* p : ptrs) if (p) hipFree(p);
         if (h_tile_cost) hipHostFree(h_tile_cost);

@@ -132,7 +132,7 @@ struct Scene {
     void update(float /*second*/) {                  // Scene.h:1233-1246
         if (!gpu) return;
         const crt_camera c = camera.abi();
-        crt_set_camera(gpu, &c);
+        if (crt_set_camera(gpu, &c) != CRT_OK) error = crt_last_error();      // a lens crt_set_camera refuses (crt.h at crt_camera): the previous camera stays
     }
 
     // output pass (Shader/output.fs:9-20 with invSampleCounter = 1/frame_count, Scene.h:1224-1230); rows bottom-up

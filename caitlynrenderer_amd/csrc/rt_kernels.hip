@@ -1900,6 +1900,69 @@ __global__ void __launch_bounds__(256) k_raygen(RaygenArgs a) {
     }
 }
 
+// The thin-lens primary ray (include/crt.h at crt_camera): primary_ray's lines up to the direction before normalize(),
+// restated operation for operation — that function is inlined into the pinhole AOV kernels and stays as it is —, then two more draws of
+// the shader RNG for a point of the lens disc (the bounce sampler's sqrt / pinned cosine / pinned sine) and the ray from that point
+// through the pinhole ray's point of the plane of focus.  (sx, sy) leaves as the state behind the second lens draw.
+__device__ __forceinline__ void lens_ray(const FrameArgs& f, uint32_t px, uint32_t py, float rv, float aperture, float focal_dist, float& sx, float& sy, vec3& o, vec3& d) {
+    sx = (float)px + 0.5f; sy = (float)py + 0.5f;
+    const float W = (float)here(f.width), H = (float)here(f.height);
+    float jx = 0.f, jy = 0.f;
+    if (f.jitter) {
+        const float r1 = 2.0f * shader_rand(sx, sy, rv);
+        const float r2 = 2.0f * shader_rand(sx, sy, rv);
+        jx = r1 < 1.0f ? sqrt_ieee(r1) - 1.0f : 1.0f - sqrt_ieee(2.0f - r1);
+        jy = r2 < 1.0f ? sqrt_ieee(r2) - 1.0f : 1.0f - sqrt_ieee(2.0f - r2);
+        jx = __fdiv_rn(jx, W * 0.5f);
+        jy = __fdiv_rn(jy, H * 0.5f);
+    }
+    const float tx = __fdiv_rn((float)px + 0.5f, W), ty = __fdiv_rn((float)py + 0.5f, H);
+    float dx = (2.0f * tx - 1.0f) + jx;
+    float dy = (2.0f * ty - 1.0f) + jy;
+    dx = dx * f.aspect_tan;
+    dy = dy * f.tan_fov;
+    const vec3 right = V3(f.cam_right[0], f.cam_right[1], f.cam_right[2]);
+    const vec3 up = V3(f.cam_up[0], f.cam_up[1], f.cam_up[2]);
+    const vec3 fwd = V3(f.cam_forward[0], f.cam_forward[1], f.cam_forward[2]);
+    const vec3 v = (right * dx + up * dy) + fwd;
+    const float u1 = shader_rand(sx, sy, rv);
+    const float u2 = shader_rand(sx, sy, rv);
+    const float r = aperture * sqrt_ieee(u1);
+    const float phi = CRT_PI2 * u2;
+    const float lx = r * pinned_cos(phi), ly = r * pinned_sin(phi);
+    const vec3 lo = right * lx + up * ly;
+    o = V3(f.cam_pos[0], f.cam_pos[1], f.cam_pos[2]) + lo;
+    d = normalize(v * focal_dist - lo);
+}
+
+// Segment 0 of a frame whose camera has an aperture, flat and instanced scenes alike: k_raygen with lens_ray in the place
+// of primary_ray, and up to 8 samples of every local pixel in one launch.  Workgroup b renders sample b / blocks_per_sample of the 256
+// local pixels from (b % blocks_per_sample) * 256 on; the path's id is sample * n_local_pixels + local pixel, as the batched multi-segment
+// paths number theirs, and its ray goes to the sub-queue of the PIXEL's unit of 4096.  The segment itself then runs as a queue-fed one.
+__global__ void __launch_bounds__(256) k_raygen_lens(LensRaygenArgs a) {
+    if (a.zero_counts && blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < a.n_zero; i += blockDim.x) a.zero_counts[i] = 0u;
+    const uint32_t per_sample = (a.f.n_local_pixels + 255u) / 256u;
+    const uint32_t smp = blockIdx.x / per_sample;          // uniform over the workgroup; < n_samples by the grid
+    const uint32_t e = (blockIdx.x - smp * per_sample) * blockDim.x + threadIdx.x;
+    const uint32_t g = (e >> 12) & 7u;                     // uniform over the workgroup: 256 divides 4096
+    uint32_t px = 0, py = 0;
+    const bool active = smp < a.n_samples && e < a.f.n_local_pixels && pixel_of(a.f, e, px, py);
+    float sx = 0.f, sy = 0.f;
+    vec3 o = V3(0.f, 0.f, 0.f), d = V3(0.f, 0.f, 1.f);
+    if (active) lens_ray(a.f, px, py, a.rv_s[smp & 7u], a.aperture, a.focal_dist, sx, sy, o, d);
+    const uint32_t ni = wave_append(active, a.count + g * CRT_COUNTER_STRIDE);
+    if (active && ni < a.sub_capacity) {
+        const uint32_t path = smp * a.f.n_local_pixels + e;
+        float4* const q = a.rays + 2 * ((size_t)g * a.sub_capacity + ni);
+        q[0] = make_float4(o.x, o.y, o.z, CRT_INF);
+        q[1] = make_float4(d.x, d.y, d.z, __uint_as_float(path));
+        a.pb.L[path] = make_float4(0.f, 0.f, 0.f, 1.0f);
+        a.pb.T[path] = make_float4(1.f, 1.f, 1.f, __uint_as_float(1u));
+        a.pb.seed[path] = make_float2(sx, sy);
+    }
+}
+
 // Closest hit for a device-written path-ray queue (segments >= 1; option bounce_refill): lane refill (walk_pool: a finished lane takes the
 // next ray, the last eight rays get eight lanes each); hits go to a buffer parallel to the queue and k_segment<PRETRACED> shades them.
 // a.persistent: a grid of as many single-wave workgroups as the chip holds waves, every wave drawing rays from the eight sub-queues through
@@ -2331,6 +2394,9 @@ int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplac
 #undef CRT_K
 void launch_raygen(const RaygenArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(k_raygen, dim3((a.f.n_local_pixels + 255u) / 256u), dim3(256), 0, stream, a);
+}
+void launch_raygen_lens(const LensRaygenArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_raygen_lens, dim3(((a.f.n_local_pixels + 255u) / 256u) * a.n_samples), dim3(256), 0, stream, a);
 }
 // the full feature level, like the other shade-only forms (the branches are decided per material at run time)
 void launch_segment_instanced(const InstSegmentArgs& a, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream) {

@@ -208,6 +208,13 @@ struct RaygenArgs {            // k_raygen: segment 0's path-ray queue and path 
     uint32_t* zero_counts;     // the other frame's counter bank, cleared here as k_segment<FIRST> does
     uint32_t n_zero;
 };
+// k_raygen_lens, the thin-lens camera.  A type of its own behind RaygenArgs, so that k_raygen keeps its argument block.
+struct LensRaygenArgs : RaygenArgs {
+    float aperture;            // lens radius in world units, > 0
+    float focal_dist;          // the plane of focus: coordinate along forward, finite and > 0
+    uint32_t n_samples;        // 1..8 samples per pixel in this launch: path = sample * n_local_pixels + local pixel
+    float rv_s[8];             // randomVector.x * randomVector.y of each of them
+};
 
 struct QueueTraceArgs {        // k_closest_queue: closest hit for a device-written path-ray queue
     const uint4* nodes;
@@ -272,6 +279,8 @@ void launch_trace_bvh2(const Bvh2Args& a, int any, bool stats, uint32_t grid, ui
 int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplace_shadow, bool bvh2, bool mat, bool stats, bool lean_ok, uint32_t grid, uint32_t waves, hipStream_t stream);
 // the frames of an instanced scene: ray generation, and the shade-only pass behind k_closest_instances_queue (shadow rays deferred)
 void launch_raygen(const RaygenArgs& a, hipStream_t stream);
+// the thin-lens form of it (camera aperture > 0; flat scenes too, up to 8 samples per launch)
+void launch_raygen_lens(const LensRaygenArgs& a, hipStream_t stream);
 void launch_segment_instanced(const InstSegmentArgs& a, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);
 void launch_closest_queue(const QueueTraceArgs& a, bool stats, uint32_t grid_waves, hipStream_t stream);
 void launch_shadow_deferred(const ShadowArgs& a, bool stats, uint32_t grid_waves, hipStream_t stream);

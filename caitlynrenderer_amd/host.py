@@ -60,6 +60,16 @@ class Camera:
     up = property(lambda s: np.array(s.c.up[:], dtype=np.float32))
     forward = property(lambda s: np.array(s.c.forward[:], dtype=np.float32))
     fov = property(lambda s: float(s.c.fov))
+    focal_dist = property(lambda s: float(s.c.focal_dist))
+    aperture = property(lambda s: float(s.c.aperture))
+
+    def set_lens(self, aperture, focal_dist):
+        """The thin lens of include/crt.h's crt_camera: a lens of radius `aperture` (world units) in the plane of right and up through
+        position, focused on the plane at `focal_dist` along forward.  aperture 0 is the pinhole.  Takes effect at the next
+        Scene.update(camera), which refuses a negative or non-finite aperture and, with an aperture, a focal_dist that is not finite and > 0."""
+        self.c.aperture = float(aperture)
+        self.c.focal_dist = float(focal_dist)
+        return self
 
     def translate(self, t):
         """Scene.h:924: camera.position += transformation_vector (fp32 add)."""

@@ -319,6 +319,13 @@ class Scene:
         check(lib().crt_debug_launch_info(self._h, info))
         return {"form": info[0], "wide": bool(info[1] & 1), "one_pass": bool(info[1] & 2), "samples": info[2], "shards": info[3]}
 
+    def launch_info(self):
+        """crt_debug_launch_info's four words as they are: [form, build word, samples per launch chain, shards].  Bit 4 of the build word
+        (16): segment 0 was fed by the lens ray generator (camera aperture > 0), and bits 0-3 are then clear."""
+        info = (C.c_int32 * 4)()
+        check(lib().crt_debug_launch_info(self._h, info))
+        return [int(x) for x in info]
+
     def debug_last_build(self):
         """True when the last first-segment launch ran a one-pass build compiled as a path's last segment (bit 2 of
         crt_debug_launch_info's build word; option "last_build")"""

@@ -1,7 +1,10 @@
 // Minimal host program with the reference's frame-loop shape (Caitlyn/main.cpp:244 init, :262-300 loop)
 // on top of crt::Scene: load an OBJ, render N progressive frames on the GPU, write the tone-mapped image.
 //
-//   render_obj scene.obj out.ppm|out.png [width height frames max_depth [sum.f32]]
+//   render_obj scene.obj out.ppm|out.png [width height frames max_depth [sum.f32 [aperture focal_dist]]]
+//
+// aperture focal_dist: a thin lens of that radius (world units) focused at that distance along the view (crt.h at crt_camera);
+// without them, or with aperture 0, the pinhole camera.
 //
 // Build: make -C caitlynrenderer_amd/csrc example   (g++, links libcrt.so)
 #include <cstdio>
@@ -12,7 +15,7 @@
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s scene.obj out.ppm|out.png [width height frames max_depth [sum.f32]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s scene.obj out.ppm|out.png [width height frames max_depth [sum.f32 [aperture focal_dist]]]\n", argv[0]);
         return 2;
     }
     const uint32_t w = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 700, h = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 700;
@@ -23,7 +26,12 @@ int main(int argc, char** argv) {
     const bool batched = std::getenv("RENDER_OBJ_BATCHED") != nullptr;   // all frames through one crt_render_frames call
     if (const char* k = std::getenv("RENDER_OBJ_STREAMS"))               // tile shards of the frame side by side on k streams of the GPU
         if (!scn.set_option("streams", std::atoi(k))) { std::fprintf(stderr, "streams refused: %s\n", scn.error.c_str()); return 1; }
+    if (argc > 9) {                                       // depth of field: Camera.h's two fields, which crt_set_camera checks
+        scn.camera.aperture = (float)std::atof(argv[8]);
+        scn.camera.focalDist = (float)std::atof(argv[9]);
+    }
     scn.update(0.0f);
+    if (!scn.error.empty()) { std::fprintf(stderr, "camera refused: %s\n", scn.error.c_str()); return 1; }
     if (batched) scn.RenderFrames(frames);
     else for (int i = 0; i < frames; ++i) {               // main.cpp:262-300: update(dt); render();
         scn.update(0.0f);

@@ -77,7 +77,27 @@ typedef struct crt_material { float albedo[4]; float emission[4]; float specular
  * p,u,v,n,e,(area,pdf,0). */
 typedef struct crt_light { float p[3], u[3], v[3], n[3], e[3], area_pdf[3]; } crt_light;
 
-/* camera uniform block, Scene.h:1143-1149 / :1237-1243 (fov = vertical, radians). */
+/* camera uniform block, Scene.h:1143-1149 / :1237-1243 (fov = vertical, radians).
+ * aperture == 0 is the pinhole camera of path_trace.fs:1026-1047; focal_dist is then not looked at.
+ * aperture > 0 is a thin lens (no reference counterpart: the shader uploads the two uniforms and never reads them).  The lens
+ * is a disc of radius `aperture`, in world units, in the plane spanned by right and up through position; the plane of focus is the plane
+ * whose coordinate along forward equals focal_dist.  Per pixel-sample, every step one IEEE float32 operation under DESIGN.md §3's rules (no
+ * contraction; dot, normalize, the correctly rounded sqrt and the pinned sine / cosine as the bounce sampler uses them):
+ *   v   = (right*dx + up*dy) + forward     the pinhole's direction before normalize(), jitter included (path_trace.fs:1041-1046)
+ *   u1  = rand();  u2 = rand();            two MORE draws of the shader RNG, directly behind the two jitter draws (option "jitter" 0: the
+ *                                          path's first two draws)
+ *   r   = aperture * sqrt(u1);  phi = 6.2831853f * u2;
+ *   lx  = r * cos(phi);  ly = r * sin(phi);
+ *   lo  = right*lx + up*ly;                per component (right.k*lx) + (up.k*ly)
+ *   o   = position + lo;
+ *   d   = normalize(v*focal_dist - lo);    per component (v.k*focal_dist) - lo.k
+ * and the path's RNG state goes on behind u2; everything after the primary ray is unchanged.  No case is special: a basis that is not
+ * orthonormal gives what this arithmetic gives, as for the pinhole.  crt_render_frame(s) through a lens adds what the definition above
+ * gives, bit for bit, on flat and instanced scenes, for every option that does not change a pinhole frame's sums either; frames run as a
+ * chain of queue-fed segments behind a ray-generation launch (crt_debug_launch_info bit 4) and take no part in the adaptive tile order.
+ * crt_set_camera refuses (CRT_ERR_INVALID, crt_last_error names the field, the previous camera stays, on every device of the scene): an
+ * aperture that is NaN, infinite or negative; with aperture > 0, a focal_dist that is not finite and > 0.
+ * The feature buffers, the denoiser's guides and the temporal reprojection keep the PINHOLE view through position (see there). */
 typedef struct crt_camera {
     float position[3]; float right[3]; float up[3]; float forward[3];
     float fov; float focal_dist; float aperture;
@@ -312,7 +332,10 @@ int crt_trace_device(crt_scene* s, const void* d_rays, size_t n, void* d_hits, i
  * (a rank fills its own pixels); option "streams" is ignored.  CRT_ERR_INVALID, nothing written: channels 0 or with other bits; option
  * "accel" not 0; a scene on several devices (crt_set_devices); crt_read_aov / crt_aov_device with a channel never rendered, more than
  * one bit, or n_bytes other than width*height*16.  crt_aov_device waits for the stream and leaves the array on the device; the pointer
- * stays valid until the scene is destroyed. */
+ * stays valid until the scene is destroyed.
+ * The view is the PINHOLE through the camera's position whatever its aperture: every channel is byte for byte independent of
+ * crt_camera.aperture and focal_dist.  Behind a lens the buffers are therefore sharper than the image: they show the surface on the
+ * central ray of each pixel, not the mix of surfaces an out-of-focus pixel gathers (lens-aware feature buffers are out of scope). */
 enum { CRT_AOV_HIT = 1, CRT_AOV_IDS = 2, CRT_AOV_NORMAL = 4, CRT_AOV_ALBEDO = 8, CRT_AOV_EMISSION = 16, CRT_AOV_ALL = 31 };
 int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync);
 int crt_read_aov(crt_scene* s, uint32_t channel, void* dst, size_t n_bytes);
@@ -341,7 +364,10 @@ int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr);
  * CRT_ERR_INVALID, nothing written: null scene; inv_count not finite or <= 0; passes outside 1..6; unknown flag bits; non-zero reserved;
  * a sigma outside its range or not finite; normal_power_log2 > 10; one of the four channels never rendered; a shard of a frame
  * (crt_set_shard with world > 1) or a scene on several devices (a filter needs its neighbours); a read, device or resolve call before any
- * successful crt_denoise, or with a wrong size. */
+ * successful crt_denoise, or with a wrong size.
+ * A camera with an aperture: the guides are crt_render_aov's, i.e. the pinhole view through the camera's position.  Out-of-focus regions
+ * are therefore filtered against guides sharper than the image: the edge-stopping terms hold the blur back at edges the pinhole sees.
+ * A stated limitation; lens-aware guides are out of scope. */
 enum { CRT_DENOISE_DEMODULATE = 1 };
 typedef struct crt_denoise_params {      /* 32 bytes */
     uint32_t passes;             /* 1..6; pass i (from 0) has tap spacing s = 2^i */
@@ -398,7 +424,10 @@ int crt_resolve_denoised_device(crt_scene* s, const uint8_t** d_rgba, int sync);
  * CRT_ERR_INVALID, nothing written and the history unchanged: null scene; inv_count not finite or <= 0; unknown flag bits; source > 1;
  * max_history outside 1..4096; sigma_depth or normal_min out of range or not finite; non-zero reserved; HIT, IDS or NORMAL never rendered,
  * or ALBEDO with CRT_TEMPORAL_DEMODULATE; source DENOISED before any successful crt_denoise; a shard of a frame (crt_set_shard with
- * world > 1) or a scene on several devices; a read, device or resolve call before any successful crt_temporal, or with a wrong size. */
+ * world > 1) or a scene on several devices; a read, device or resolve call before any successful crt_temporal, or with a wrong size.
+ * A camera with an aperture: the reprojection and its guides keep the pinhole view through the camera's position (crt_render_aov's), so
+ * out-of-focus regions are reprojected and tested against guides sharper than the image.  A stated limitation; lens-aware motion
+ * vectors are out of scope. */
 enum { CRT_TEMPORAL_DEMODULATE = 1, CRT_TEMPORAL_CLAMP = 2 };
 enum { CRT_TEMPORAL_SOURCE_SUM = 0, CRT_TEMPORAL_SOURCE_DENOISED = 1 };
 typedef struct crt_temporal_params {   /* 32 bytes */
@@ -491,7 +520,8 @@ int crt_debug_read_accel(crt_scene* s, int which, void* dst, size_t cap_bytes, s
  * in launch order; ms may be NULL to query the count */
 int crt_get_launch_times(crt_scene* s, float* ms, size_t cap, size_t* n_out);
 /* test hook: read back a ray queue of the last rendered frame (which: 0 = path rays entering
- * `segment`, 2 = that segment's shadow rays).  dst may be NULL to query the count. */
+ * `segment`, 2 = that segment's shadow rays).  dst may be NULL to query the count.  (0, 0) after a frame of a flat scene through a lens
+ * (crt_camera.aperture > 0): the lens primary rays, tmax 1e9f, pad = the path's id, at every max_depth. */
 int crt_debug_read_queue(crt_scene* s, int which, uint32_t segment, crt_ray* dst, size_t cap, size_t* n_out);
 /* measurement aid: the same n_frames (rxy = n_frames pairs) queued `reps` times on the stream and replayed `reps`
  * times as one captured hipGraph; device milliseconds per frame of either way ("hipGraph") */
@@ -501,7 +531,9 @@ int crt_debug_time_graph(crt_scene* s, uint32_t n_frames, const float* rxy, uint
 int crt_debug_launch_form(crt_scene* s, int32_t* form);
 /* test hook: the same launch in full: info[0] = form as above (2 = four samples of a 4 x 4 pixel quadrant in the lanes of a wave),
  * info[1] = bit 0: the first segment ran its 6-waves-per-SIMD build (option "wide_first"), bit 1: a one-pass build (no sample loop), bit 2: that
- * build compiled as a last segment (option "last_build"), bit 3: that build's LEAN form (option "lean_build"), info[2] = samples per pixel of the launch,
+ * build compiled as a last segment (option "last_build"), bit 3: that build's LEAN form (option "lean_build"), bit 4: segment 0 was fed by the
+ * lens ray generator (crt_camera.aperture > 0: every segment ran in its queue-fed form; info[0] is then 0 and bits 0-3 are clear),
+ * info[2] = samples per pixel of the launch (a lens frame: of the launch chain),
  * info[3] = tile shards rendering side by side (option "streams" / crt_set_devices) */
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]);
 /* measurement aid: hist[130] receives, for the counting frames ("count_visits") rendered since the previous call, how many node steps ran
