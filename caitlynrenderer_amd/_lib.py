@@ -20,6 +20,7 @@ CRT_DENOISE_DEMODULATE = 1               # crt_denoise_params.flags
 DENOISE_DEMODULATE = CRT_DENOISE_DEMODULATE
 CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_CLAMP = 1, 2                       # crt_temporal_params.flags
 CRT_TEMPORAL_SOURCE_SUM, CRT_TEMPORAL_SOURCE_DENOISED = 0, 1             # crt_temporal_params.source
+CRT_ENV_HIDE_FROM_CAMERA = 1             # crt_environment.flags
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
 CRT_INSTANCES_UPDATABLE = 1 << 16
@@ -34,6 +35,12 @@ class CrtError(RuntimeError):
 class crt_camera(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3),
                 ("forward", C.c_float * 3), ("fov", C.c_float), ("focal_dist", C.c_float), ("aperture", C.c_float)]
+
+
+class crt_environment(C.Structure):
+    # struct crt_environment: crt_set_environment's octahedral map, rotation and scale
+    _fields_ = [("texels", C.c_void_p), ("size", C.c_uint32), ("flags", C.c_uint32), ("rotation", C.c_float * 9), ("scale", C.c_float * 3),
+                ("reserved", C.c_uint32 * 2)]
 
 
 class crt_scene_desc(C.Structure):
@@ -139,6 +146,7 @@ SYMBOLS = {
     "crt_scene_create": (_I, [C.POINTER(crt_scene_desc), C.POINTER(_P)]),
     "crt_scene_destroy": (_I, [_P]),
     "crt_set_camera": (_I, [_P, C.POINTER(crt_camera)]),
+    "crt_set_environment": (_I, [_P, C.POINTER(crt_environment)]),
     "crt_render_frame": (_I, [_P, _F, _F]),
     "crt_render_frame_async": (_I, [_P, _F, _F]),
     "crt_render_frames": (_I, [_P, C.c_uint32, _P, _P]),

@@ -996,6 +996,68 @@ int crt_set_camera(crt_scene* s, const crt_camera* cam) {
     return CRT_OK;
 }
 
+// The environment (include/crt.h).  Everything is checked, and every device's copy of the map allocated and filled, before
+// any device's state changes: a refused or failed call leaves the scene and its peers with the environment they had.
+int crt_set_environment(crt_scene* s, const crt_environment* env) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_set_environment: null scene");
+    if (s->primary) return fail(CRT_ERR_INVALID, "crt_set_environment: not on a replica");
+    std::vector<crt_scene*> all;
+    std::vector<float4> texels;
+    std::vector<float4*> fresh;
+    size_t n = 0;
+    try {
+        all.push_back(s);
+        all.insert(all.end(), s->peers.begin(), s->peers.end());
+        if (env) {
+            if (!env->texels) return fail(CRT_ERR_INVALID, "crt_set_environment: texels is null");
+            if (env->size < 1u || env->size > 4096u) return fail(CRT_ERR_INVALID, "crt_set_environment: size must be 1..4096");
+            if (env->flags & ~CRT_ENV_HIDE_FROM_CAMERA) return fail(CRT_ERR_INVALID, "crt_set_environment: unknown flags bits");
+            if (env->reserved[0] != 0u || env->reserved[1] != 0u) return fail(CRT_ERR_INVALID, "crt_set_environment: reserved must be 0");
+            for (int k = 0; k < 9; ++k)
+                if (!std::isfinite(env->rotation[k])) return fail(CRT_ERR_INVALID, "crt_set_environment: rotation has an entry that is not finite");
+            for (int k = 0; k < 3; ++k)
+                if (!std::isfinite(env->scale[k]) || env->scale[k] < 0.0f) return fail(CRT_ERR_INVALID, "crt_set_environment: scale must be finite and >= 0");
+            if (s->accel != 0u) return fail(CRT_ERR_INVALID, "crt_set_environment: the BVH2 frame mode (option accel) has no environment");
+            n = (size_t)env->size * env->size;
+            texels.resize(n);
+            for (size_t i = 0; i < n; ++i) {
+                const float r = env->texels[3 * i], g = env->texels[3 * i + 1], b = env->texels[3 * i + 2];
+                if (!std::isfinite(r) || !std::isfinite(g) || !std::isfinite(b) || r < 0.0f || g < 0.0f || b < 0.0f)
+                    return fail(CRT_ERR_INVALID, "crt_set_environment: texels must be finite and >= 0");
+                texels[i] = make_float4(r, g, b, 0.0f);
+            }
+            fresh.assign(all.size(), nullptr);
+        }
+    } catch (const std::exception&) {
+        return fail(CRT_ERR_NOMEM, "crt_set_environment: out of host memory");
+    }
+    int rc = CRT_OK;
+    for (size_t k = 0; env && k < all.size() && !rc; ++k) {
+        if (hipSetDevice(all[k]->device) != hipSuccess) { rc = fail(CRT_ERR_HIP, "crt_set_environment: hipSetDevice failed"); break; }
+        if ((rc = dev_alloc(&fresh[k], n))) break;
+        if (hipMemcpy(fresh[k], texels.data(), n * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess) rc = fail(CRT_ERR_HIP, "crt_set_environment: hipMemcpy H2D failed");
+    }
+    // frames in flight read the map they were enqueued with: every stream drains before its device's copy is replaced
+    for (size_t k = 0; k < all.size() && !rc; ++k)
+        if (hipSetDevice(all[k]->device) != hipSuccess || hipStreamSynchronize(all[k]->stream) != hipSuccess) rc = fail(CRT_ERR_HIP, "crt_set_environment: hipStreamSynchronize failed");
+    if (rc) {
+        for (size_t k = 0; k < fresh.size(); ++k) if (fresh[k]) { (void)hipSetDevice(all[k]->device); (void)hipFree(fresh[k]); }
+        (void)hipSetDevice(s->device);
+        return rc;
+    }
+    for (size_t k = 0; k < all.size(); ++k) {
+        crt_scene* x = all[k];
+        (void)hipSetDevice(x->device);
+        if (x->d_env) (void)hipFree(x->d_env);
+        x->d_env = env ? fresh[k] : nullptr;
+        x->env_size = env ? env->size : 0u; x->env_flags = env ? env->flags : 0u;
+        for (int j = 0; j < 9; ++j) x->env_rotation[j] = env ? env->rotation[j] : (j % 4 == 0 ? 1.0f : 0.0f);
+        for (int j = 0; j < 3; ++j) x->env_scale[j] = env ? env->scale[j] : 1.0f;
+    }
+    (void)hipSetDevice(s->device);
+    return CRT_OK;
+}
+
 static int set_devices_of_shard(crt_scene* s, const int32_t* devices, uint32_t n_devices, uint32_t tile, uint32_t base_rank, uint32_t base_world);
 
 int crt_set_shard(crt_scene* s, uint32_t rank, uint32_t world, uint32_t tile) {
@@ -1113,6 +1175,7 @@ int crt_set_option(crt_scene* s, const char* name, int value) {
     else if (!std::strcmp(name, "accel")) {
         if (value < 0 || value > 2) return fail(CRT_ERR_INVALID, "crt_set_option: accel is 0 (CWBVH), 1 (BVH2, reference order) or 2 (BVH2, lowest-id ties)");
         if (value != 0 && !s->d_bvh2) return fail(CRT_ERR_INVALID, "crt_set_option: the scene was created without a BVH2 (desc.bvh)");
+        if (value != 0 && s->env()) return fail(CRT_ERR_INVALID, "crt_set_option: accel stays 0 while an environment is set (crt_set_environment): the BVH2 frame mode has none");
         if (value != 0 && s->special_materials)
             return fail(CRT_ERR_INVALID, "crt_set_option: the BVH2 frame mode is the shipped shader, which is Lambert only; this scene has Mirror / Disney materials");
         s->accel = (uint32_t)value;
@@ -1169,11 +1232,12 @@ int crt_set_option(crt_scene* s, const char* name, int value) {
 static int ensure_batch_buffers(crt_scene* s, uint32_t cap);
 static bool uses_ray_bins(const crt_scene* s) {
     // bounce rays binned between the segments (option "ray_bins"): big trees, CWBVH walks, the lock-step segment kernels
-    return s->ray_bins != 0u && s->max_depth > 1u && s->info.n_nodes8 >= 64 && s->accel == 0u && !s->bounce_refill;
+    return s->ray_bins != 0u && s->max_depth > 1u && s->info.n_nodes8 >= 64 && s->accel == 0u && !s->bounce_refill && !s->env();
 }
 // Segments [first, max_depth) defer their NEE shadow rays (option "inplace_shadow"); first = max_depth: none does.  BVH2 frames walk in place.
 static uint32_t first_deferred_segment(const crt_scene* s) {
     if (s->inst) return 0u;                  // an instanced scene's frames defer every segment's shadow rays (k_shadow_instances_deferred)
+    if (s->env()) return 0u;                 // a frame with an environment: every segment has a slot region, whatever "inplace_shadow" says
     const uint32_t mode = s->inplace_shadow == 3u ? (s->info.n_nodes8 >= 64 ? 2u : 1u) : s->inplace_shadow;
     if (s->accel != 0u || mode == 1u) return s->max_depth;
     return mode == 0u ? 0u : std::min(1u, s->max_depth);
@@ -1219,9 +1283,10 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
     if (rc) return rc;
     if (s->n_local_pixels == 0) return CRT_OK;
     const bool lens = s->lens() && !s->inst;                              // a flat scene's frame through a lens: every segment queue-fed
-    const bool batched_paths = n_samples > 1u && (s->max_depth > 1u || lens);     // finished paths leave their radiance in d_lfinal
-    if (lens && !s->d_rays[0]) {
-        // a one-segment scene held no queues and no path state until its camera got an aperture: one sample's worth, as alloc_frame_buffers sizes them
+    const bool queue_fed = lens || (s->env() && !s->inst);                // ... and so is one with an environment
+    const bool batched_paths = n_samples > 1u && (s->max_depth > 1u || queue_fed);     // finished paths leave their radiance in d_lfinal
+    if (queue_fed && !s->d_rays[0]) {
+        // a one-segment scene held no queues and no path state until its camera got an aperture or the scene an environment: one sample's worth, as alloc_frame_buffers sizes them
         const size_t P = s->n_local_pixels, Q1 = 8 * (size_t)s->sub_capacity;
         if ((rc = dev_alloc(&s->d_rays[0], 2 * Q1)) || (rc = dev_alloc(&s->d_rays[1], 2 * Q1))) return rc;
         s->rays_doubled = false;
@@ -1236,7 +1301,7 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
         if ((rc = dev_alloc(&s->d_rays_lens, 2 * 8 * (size_t)s->sub_capacity))) return rc;
         s->lens_sub_capacity = s->sub_capacity;
     }
-    if (lens && (rc = ensure_lfinal(s))) return rc;                       // a lens frame always folds
+    if (queue_fed && (rc = ensure_lfinal(s))) return rc;                  // such a frame always folds
     if (first_deferred_segment(s) < s->max_depth && ((rc = ensure_lfinal(s)) || (rc = ensure_defer_buffers(s)))) return rc;
     if (s->count_visits && !s->d_visit_totals) {
         if ((rc = dev_alloc(&s->d_visit_totals, 16))) return rc;
@@ -1244,7 +1309,7 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
     }
     // the hit buffer of the bounce pools (bounce_refill = 1): allocated by the first frame that needs it
     const size_t Q = 8 * (size_t)s->sub_capacity;
-    if (((s->bounce_refill && (s->max_depth > 1 || lens)) || s->inst) && !s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
+    if (((s->bounce_refill && (s->max_depth > 1 || lens)) || s->inst || s->env()) && !s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
     if (s->inst && !s->d_qinst && (rc = dev_alloc(&s->d_qinst, Q))) return rc;
     if (uses_ray_bins(s)) {
         if (!s->d_bins) {
@@ -1269,6 +1334,17 @@ static int prepare_batch(crt_scene* s, uint32_t n_samples) {
 // One frame of an instanced scene, buffers prepared: k_raygen, then per segment the two-level closest-hit walk over the
 // segment's queue and the shade-only pass, then ONE two-level any-hit launch for every segment's shadow rays and the fold — the
 // bounce_refill 1 + inplace_shadow 0 sequence below with segment 0 included.  The handle's live arrays are read HERE, at enqueue time.
+// k_env_miss' arguments for the segment whose path rays sit in `rays` / `count` and whose hits sit in d_qhits
+static crt::EnvMissArgs env_miss_args(const crt_scene* s, const float4* rays, const uint32_t* count, size_t n_paths, uint32_t slot_first, uint32_t slot_bit) {
+    crt::EnvMissArgs ea{};
+    ea.rays = rays; ea.count = count; ea.hits = s->d_qhits; ea.sub_capacity = s->sub_capacity; ea.n_paths = (uint32_t)n_paths;
+    ea.T = s->pb.T; ea.contrib = s->d_contrib; ea.slot_first = slot_first; ea.slot_bit = slot_bit;
+    ea.texels = s->d_env; ea.size = s->env_size;
+    for (int k = 0; k < 9; ++k) ea.rotation[k] = s->env_rotation[k];
+    for (int k = 0; k < 3; ++k) ea.scale[k] = s->env_scale[k];
+    return ea;
+}
+
 static int render_instanced_async(crt_scene* s, float rx, float ry) {
     if (s->lit) { const int rc = ensure_light_table(s); if (rc) return rc; }      // lights that follow the instances
     crt::InstancesView v{};
@@ -1313,6 +1389,11 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
         qa.refill_min = 8; qa.tri_min = 2;          // crt_instances_trace's
         qa.visit_totals = s->d_visit_totals; qa.overflow = s->d_overflow;
         timed(1, [&] { crt::launch_closest_instances_queue(qa, s->count_visits, masked, s->stream); });
+        if (s->env() && !(b == 0 && (s->env_flags & CRT_ENV_HIDE_FROM_CAMERA))) {
+            // the paths this walk found to miss take the environment's radiance through their slot of this segment
+            const crt::EnvMissArgs ea = env_miss_args(s, s->d_rays[b & 1], cnt + counter_index(b, 0, 0), n_paths, (uint32_t)((size_t)b * n_paths), 1u << (8u + b));
+            timed(3, [&] { crt::launch_env_miss(ea, s->stream); });
+        }
         crt::InstSegmentArgs sa{};
         sa.triangles = s->d_triangles; sa.normals = s->d_normals; sa.materials = s->d_materials; sa.lights = s->d_lights; sa.n_lights = (int32_t)s->n_lights;
         sa.stack_entries = 2;                       // the shade-only pass walks nothing
@@ -1356,6 +1437,7 @@ static int render_instanced_async(crt_scene* s, float rx, float ry) {
     s->stats_from_frame = true;
     s->samples_in_stats = 1;
     s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0; s->last_launch_last = 0; s->last_launch_lean = 0; s->last_launch_lens = s->lens() ? 1 : 0;
+    s->last_launch_env = s->env() ? 1 : 0;
     return CRT_OK;
 }
 
@@ -1370,10 +1452,15 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
     // A camera with an aperture: k_raygen_lens writes segment 0's rays and path state, and EVERY segment runs in its
     // queue-fed form; the fused first-segment kernels, their tile order and their sample forms are not involved
     const bool lens = s->lens();
-    const bool batched_paths = n_samples > 1u && (s->max_depth > 1u || lens);
+    // An environment: the same chain — k_raygen in the lens generator's place when the camera is a pinhole —, every segment's
+    // closest hits through k_closest_queue, then k_env_miss for the paths that missed, then the shade-only pass; every segment's shadow rays
+    // deferred (first_deferred_segment is 0), whatever "inplace_shadow", "bounce_refill" and "ray_bins" say
+    const bool env = s->env();
+    const bool queue_fed = lens || env;
+    const bool batched_paths = n_samples > 1u && (s->max_depth > 1u || queue_fed);
     const uint32_t first_deferred = first_deferred_segment(s);         // segments from here on leave their shadow rays to k_shadow_deferred
     const bool any_deferred = first_deferred < s->max_depth;
-    const bool folds = batched_paths || any_deferred || lens;           // finished paths leave their radiance in d_lfinal, k_fold_paths adds it to the sum
+    const bool folds = batched_paths || any_deferred || queue_fed;           // finished paths leave their radiance in d_lfinal, k_fold_paths adds it to the sum
     const size_t n_paths = (size_t)P * n_samples;
     const float rx = rxs[0], ry = rys[0];
     const crt::FrameArgs f = frame_args(s, rx, ry);
@@ -1383,7 +1470,7 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
     // memset is only needed for the very first frame (or after a failed launch left the banks in an unknown state)
     // tile order: adopt a finished measurement, start one if the view is new
     bool measure_tiles = false;
-    if (s->adaptive_tiles && s->n_local_tiles > 1 && !s->capturing && !lens) {      // a lens frame leaves the tile order and its measurement as they are
+    if (s->adaptive_tiles && s->n_local_tiles > 1 && !s->capturing && !queue_fed) {      // a lens or environment frame leaves the tile order and its measurement as they are
         const bool arrived = s->tile_state == crt_scene::TILES_PENDING && hipEventQuery(s->ev_tile_cost) == hipSuccess;
         (void)hipGetLastError();                                    // "not ready" is an answer, not an error to report later
         if (arrived) {
@@ -1447,9 +1534,19 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         if (sp) (void)hipEventRecord(sp->a, s->stream);
         crt::launch_raygen_lens(ra, s->stream);
         if (sp) (void)hipEventRecord(sp->b, s->stream);
+    } else if (env) {
+        crt::RaygenArgs ra{};                           // the pinhole's primary rays as an instanced frame generates them: one sample per chain (batch_limit)
+        ra.f = f;
+        ra.f.tile_order = nullptr;
+        ra.rays = s->d_rays[0]; ra.count = cnt + counter_index(0, 0, 0); ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
+        ra.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; ra.n_zero = kCounters;
+        EventSpan* sp = s->new_span(0);
+        if (sp) (void)hipEventRecord(sp->a, s->stream);
+        crt::launch_raygen(ra, s->stream);
+        if (sp) (void)hipEventRecord(sp->b, s->stream);
     }
     for (uint32_t b = 0; b < s->max_depth; ++b) {
-        const bool first = b == 0 && !lens;             // the fused first-segment kernels; false = a queue-fed segment
+        const bool first = b == 0 && !queue_fed;        // the fused first-segment kernels; false = a queue-fed segment
         crt::SegmentArgs sa{};
         sa.nodes = s->d_nodes; sa.planes = s->d_planes; sa.tris = s->d_tris; sa.triangles = s->d_triangles; sa.normals = s->d_normals;
         sa.materials = s->d_materials; sa.lights = s->d_lights; sa.n_lights = (int32_t)s->n_lights;
@@ -1523,11 +1620,11 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         sa.last_build = s->last_build;
         EventSpan* sp = s->new_span(1);
         // option bounce_refill: the closest hits of a bounce segment through lane-refill pools (k_closest_queue), then a shade-only pass
-        const bool pretraced = !first && s->bounce_refill && !small_tree && !bvh2 && s->tri_min != 0u && !bins;
+        const bool pretraced = env || (!first && s->bounce_refill && !small_tree && !bvh2 && s->tri_min != 0u && !bins);
         if (pretraced) {
             crt::QueueTraceArgs qa{};
             qa.nodes = s->d_nodes; qa.tris = s->d_tris; qa.rays = sa.rays_in; qa.count = sa.count_in; qa.hits = s->d_qhits;
-            qa.stack_entries = s->stack_entries; qa.sub_capacity = s->sub_capacity; qa.refill_min = s->refill_min; qa.tri_min = s->tri_min;
+            qa.stack_entries = s->stack_entries; qa.sub_capacity = s->sub_capacity; qa.refill_min = s->refill_min; qa.tri_min = s->tri_min ? s->tri_min : 1u;      // (0 only on an environment frame: the pools vote, as k_shadow_deferred's do)
             qa.pool = s->refill_pool; qa.lanes_log2 = sa.lanes_log2;
             qa.persistent = s->persistent; qa.cursors = cnt + cursor_index_closest(b);
             qa.visit_totals = s->d_visit_totals; qa.overflow = s->d_overflow;
@@ -1535,6 +1632,13 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
             const size_t lds_q = (size_t)(s->stack_entries + CRT_HIT_SLOTS) * 64 * sizeof(uint2);
             crt::launch_closest_queue(qa, s->count_visits, s->persistent ? s->resident_waves(lds_q, 8) : 8u * ((s->sub_capacity + qa.pool - 1u) / qa.pool), s->stream);
             sa.hits_in = s->d_qhits;
+            if (env && !(b == 0 && (s->env_flags & CRT_ENV_HIDE_FROM_CAMERA))) {
+                // option "timing" 2: a span of its own (recorded around it, inside the segment's span; crt_frame_stats counts it under ms_shade)
+                EventSpan* es = s->new_span(3);
+                if (es) (void)hipEventRecord(es->a, s->stream);
+                crt::launch_env_miss(env_miss_args(s, sa.rays_in, sa.count_in, n_paths, sa.slot_first, sa.slot_bit), s->stream);
+                if (es) (void)hipEventRecord(es->b, s->stream);
+            }
             if (sp) crt::set_launch_events(nullptr, sp->b);
         } else if (sp) crt::set_launch_events(sp->a, sp->b);
         // A workgroup renders ONE chunk (CRT_CHUNK_LOOP), so the grid has to cover every chunk a sub-queue can hold: a group's
@@ -1543,7 +1647,7 @@ static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs
         uint32_t grid = s->trace_grid(P, sa.wide_first ? 6 : 5);
         if (!first && batched_paths) grid *= n_samples;
         const int build = crt::launch_segment(sa, first, pretraced, inplace, bvh2, s->special_materials, s->count_visits, s->lean_build != 0u && s->tree_validated, grid, s->waves_per_workgroup, s->stream);
-        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; s->last_launch_last = (build >> 2) & 1; s->last_launch_lean = (build >> 3) & 1; s->last_launch_lens = lens ? 1 : 0; }
+        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; s->last_launch_last = (build >> 2) & 1; s->last_launch_lean = (build >> 3) & 1; s->last_launch_lens = lens ? 1 : 0; s->last_launch_env = env ? 1 : 0; }
         if (sa.bins_out.count) {
             // fill counts -> the next launch's index space and ray count, and the next frame's capacities (the other parity)
             crt::BinScanArgs ba{};
@@ -1950,6 +2054,16 @@ static int replicate_scene(const crt_scene* src, int device, crt_scene** out) {
         if (e != hipSuccess) return fail(CRT_ERR_NOMEM, std::string("crt_set_devices: hipMalloc: ") + hipGetErrorString(e));
         if (b.second) HIPCHK(hipMemcpyPeer(*to, device, from, src->device, b.second));
     }
+    if (src->d_env) {                     // the environment is scene state like the camera: a copy of its own on every logical device
+        const size_t n = (size_t)src->env_size * src->env_size;
+        int erc = dev_alloc(&r->d_env, n);
+        if (erc) return erc;
+        if (device == src->device) HIPCHK(hipMemcpy(r->d_env, src->d_env, n * sizeof(float4), hipMemcpyDeviceToDevice));
+        else HIPCHK(hipMemcpyPeer(r->d_env, device, src->d_env, src->device, n * sizeof(float4)));
+        r->env_size = src->env_size; r->env_flags = src->env_flags;
+        for (int k = 0; k < 9; ++k) r->env_rotation[k] = src->env_rotation[k];
+        for (int k = 0; k < 3; ++k) r->env_scale[k] = src->env_scale[k];
+    }
     int rc = finish_scene_setup(r);
     if (rc) return rc;
     *out = owner.release();
@@ -2145,7 +2259,7 @@ int crt_debug_step_hist(crt_scene* s, unsigned long long* hist) {
 
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]) {
     if (!s || !info) return fail(CRT_ERR_INVALID, "crt_debug_launch_info: null argument");
-    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1) | (s->last_launch_last << 2) | (s->last_launch_lean << 3) | (s->last_launch_lens << 4); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
+    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1) | (s->last_launch_last << 2) | (s->last_launch_lean << 3) | (s->last_launch_lens << 4) | (s->last_launch_env << 5); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
     return CRT_OK;
 }
 

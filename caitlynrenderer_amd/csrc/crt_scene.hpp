@@ -234,6 +234,14 @@ struct crt_scene {
     float4* d_rays_lens = nullptr;
     uint32_t lens_sub_capacity = 0;
     bool lens() const { return cam.aperture > 0.0f; }     // crt_set_camera has checked the two fields
+    // The environment (crt_set_environment): scene state like the camera, on every device of the scene a copy of its own.
+    // d_env: size x size texels (r, g, b, 0), row 0 first; null = none, and every frame is launched as without this member.  With one, a
+    // flat scene's frame runs every segment queue-fed and pretraced, k_env_miss between the closest-hit launch and the shade-only pass.
+    float4* d_env = nullptr;
+    uint32_t env_size = 0, env_flags = 0;
+    float env_rotation[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, env_scale[3] = {1.f, 1.f, 1.f};
+    bool env() const { return d_env != nullptr; }
+    int last_launch_env = 0;                 // crt_debug_launch_info: bit 5 of the build word: the frame ran k_env_miss behind its closest-hit launches
     // DEFERRED NEE shadow rays (option "inplace_shadow" 0 / 2, rt_kernels.hip k_segment<!INPLACE>): the frame's NEE queue — one region per
     // deferring segment, 8 sub-queues each, 2 x float4 per ray: (o, tmax) (d, contribution slot) — and the contribution slots, one per
     // (deferring segment, path): (C | T e, visibility word)
@@ -398,7 +406,7 @@ struct crt_scene {
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
-                        d_rays[0], d_rays[1], d_rays_lens, d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
+                        d_rays[0], d_rays[1], d_rays_lens, d_env, d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
                         d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins, d_mesh_base, d_qinst, d_mesh_mtl, d_tex_before};
         for (void* p : ptrs) if (p) hipFree(p);
         if (h_tile_cost) hipHostFree(h_tile_cost);

@@ -1963,6 +1963,74 @@ __global__ void __launch_bounds__(256) k_raygen_lens(LensRaygenArgs a) {
     }
 }
 
+// One texel of the octahedral environment map with the edge identification of include/crt.h (at crt_set_environment): a tap beyond an edge
+// of the square is the texel the neighbouring direction of the lower hemisphere maps to, so the bilinear filter has no seam.
+__device__ __forceinline__ float4 env_tap(const float4* __restrict__ texels, int size, int i, int j) {
+    const int m = size - 1;
+    if (i < 0) { i = 0; j = m - j; } else if (i > m) { i = m; j = m - j; }
+    if (j < 0) { i = m - i; j = 0; } else if (j > m) { i = m - i; j = m; }
+    i = i < 0 ? 0 : i > m ? m : i;
+    j = j < 0 ? 0 : j > m ? m : j;
+    return texels[(size_t)j * (size_t)size + (size_t)i];
+}
+
+// E(d) of include/crt.h (at crt_set_environment): the direction through the rotation, the octahedral map's square, four taps
+// and the bilinear blend, times the scale — every line one float32 operation in the written order (the unit is compiled without contraction).
+// false: the direction has no image (s is not a positive finite number) and the radiance is 0.
+__device__ __forceinline__ bool env_radiance(const EnvMissArgs& a, vec3 d, vec3& E) {
+    const float ex = (a.rotation[0] * d.x + a.rotation[1] * d.y) + a.rotation[2] * d.z;
+    const float ey = (a.rotation[3] * d.x + a.rotation[4] * d.y) + a.rotation[5] * d.z;
+    const float ez = (a.rotation[6] * d.x + a.rotation[7] * d.y) + a.rotation[8] * d.z;
+    const float s = (fabsf(ex) + fabsf(ey)) + fabsf(ez);
+    if (!(s > 0.0f) || !(s <= 3.4028235e38f)) return false;
+    float px = __fdiv_rn(ex, s), py = __fdiv_rn(ey, s);
+    if (ez < 0.0f) {
+        const float qx = (1.0f - fabsf(py)) * (px < 0.0f ? -1.0f : 1.0f);
+        const float qy = (1.0f - fabsf(px)) * (py < 0.0f ? -1.0f : 1.0f);
+        px = qx; py = qy;
+    }
+    const float fs = (float)a.size;
+    const float fx = (px * 0.5f + 0.5f) * fs - 0.5f;
+    const float fy = (py * 0.5f + 0.5f) * fs - 0.5f;
+    const float x0 = floorf(fx), y0 = floorf(fy);
+    const float tx = fx - x0, ty = fy - y0;
+    const int i0 = (int)x0, j0 = (int)y0, n = (int)a.size;          // |fx|, |fy| <= size: the conversions are exact
+    const float4 t00 = env_tap(a.texels, n, i0, j0), t10 = env_tap(a.texels, n, i0 + 1, j0);
+    const float4 t01 = env_tap(a.texels, n, i0, j0 + 1), t11 = env_tap(a.texels, n, i0 + 1, j0 + 1);
+    const float ux = 1.0f - tx, uy = 1.0f - ty;
+    const vec3 c = (V3(t00.x, t00.y, t00.z) * ux + V3(t10.x, t10.y, t10.z) * tx) * uy + (V3(t01.x, t01.y, t01.z) * ux + V3(t11.x, t11.y, t11.z) * tx) * ty;
+    E = V3(c.x * a.scale[0], c.y * a.scale[1], c.z * a.scale[2]);
+    return true;
+}
+
+// The environment's radiance for the paths whose closest-hit ray of this segment missed, between the segment's closest-hit
+// launch and its shade-only pass.  Workgroup b covers the 256 entries from (b % per_group) * 256 of sub-queue b / per_group.  A miss with
+// radiance to add writes (T * E, 1) into the path's contribution slot of this segment and ORs the segment's bit into the flag word of the
+// path's throughput; the shade-only pass then finds the miss, leaves that mask in l_final, and k_fold_paths adds the slot in segment order
+// — behind every earlier segment's terms: the path's last addition.  A zero contribution writes nothing.
+__global__ void __launch_bounds__(256) k_env_miss(EnvMissArgs a) {
+    const uint32_t per_group = (a.sub_capacity + 255u) / 256u;
+    const uint32_t g = blockIdx.x / per_group;              // uniform over the workgroup; < 8 by the grid
+    const uint32_t first = (blockIdx.x - g * per_group) * 256u;
+    uint32_t n = a.count[g * CRT_COUNTER_STRIDE];
+    n = n < a.sub_capacity ? n : a.sub_capacity;            // appends beyond the capacity were dropped by their writers
+    if (first >= n) return;
+    const uint32_t e = first + threadIdx.x;
+    if (e >= n) return;
+    const size_t q = (size_t)g * a.sub_capacity + e;
+    if (__float_as_int(reinterpret_cast<const float*>(a.hits + q)[3]) >= 0) return;
+    const float4 r1 = a.rays[2 * q + 1];
+    const uint32_t path = __float_as_uint(r1.w);
+    if (path >= a.n_paths) return;
+    vec3 E;
+    if (!env_radiance(a, V3(r1.x, r1.y, r1.z), E)) return;
+    const float4 Tp = a.T[path];
+    const vec3 c = V3(Tp.x * E.x, Tp.y * E.y, Tp.z * E.z);
+    if (c.x == 0.0f && c.y == 0.0f && c.z == 0.0f) return;
+    a.contrib[(size_t)a.slot_first + path] = make_float4(c.x, c.y, c.z, 1.0f);
+    reinterpret_cast<uint32_t*>(a.T + path)[3] = __float_as_uint(Tp.w) | a.slot_bit;
+}
+
 // Closest hit for a device-written path-ray queue (segments >= 1; option bounce_refill): lane refill (walk_pool: a finished lane takes the
 // next ray, the last eight rays get eight lanes each); hits go to a buffer parallel to the queue and k_segment<PRETRACED> shades them.
 // a.persistent: a grid of as many single-wave workgroups as the chip holds waves, every wave drawing rays from the eight sub-queues through
@@ -2397,6 +2465,9 @@ void launch_raygen(const RaygenArgs& a, hipStream_t stream) {
 }
 void launch_raygen_lens(const LensRaygenArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(k_raygen_lens, dim3(((a.f.n_local_pixels + 255u) / 256u) * a.n_samples), dim3(256), 0, stream, a);
+}
+void launch_env_miss(const EnvMissArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_env_miss, dim3(8u * ((a.sub_capacity + 255u) / 256u)), dim3(256), 0, stream, a);
 }
 // the full feature level, like the other shade-only forms (the branches are decided per material at run time)
 void launch_segment_instanced(const InstSegmentArgs& a, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream) {

@@ -216,6 +216,24 @@ struct LensRaygenArgs : RaygenArgs {
     float rv_s[8];             // randomVector.x * randomVector.y of each of them
 };
 
+// k_env_miss, the environment (include/crt.h at crt_set_environment): between a segment's closest-hit launch and its shade-only
+// pass, one lane per entry of the segment's path-ray queue.  An argument block of its own: no other kernel's block moves.
+struct EnvMissArgs {
+    const float4* rays;        // the segment's path-ray queue: 8 sub-queues, 2 x float4 per entry, (d, path) in the second row
+    const uint32_t* count;     // its 8 counters, CRT_COUNTER_STRIDE apart
+    const float4* hits;        // parallel to the queue, from k_closest_queue / k_closest_instances_queue: only w (the triangle, < 0 = miss) is read
+    uint32_t sub_capacity;
+    uint32_t n_paths;          // path ids in the queue are below this (samples of the chain x local pixels)
+    float4* T;                 // PathBuffers::T: (throughput, flag word); a miss with radiance to add gets slot_bit ORed into the flag word
+    float4* contrib;           // the frame's contribution slots (SegmentArgs::contrib of segment 0)
+    uint32_t slot_first;       // this segment's SegmentArgs::slot_first and slot_bit
+    uint32_t slot_bit;
+    const float4* texels;      // size x size (r, g, b, 0), row 0 first
+    uint32_t size;
+    float rotation[9];         // rows; world -> map
+    float scale[3];
+};
+
 struct QueueTraceArgs {        // k_closest_queue: closest hit for a device-written path-ray queue
     const uint4* nodes;
     const float4* tris;
@@ -281,6 +299,8 @@ int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplac
 void launch_raygen(const RaygenArgs& a, hipStream_t stream);
 // the thin-lens form of it (camera aperture > 0; flat scenes too, up to 8 samples per launch)
 void launch_raygen_lens(const LensRaygenArgs& a, hipStream_t stream);
+// the environment's radiance for the paths a segment's closest-hit launch found to miss, through their contribution slots of that segment
+void launch_env_miss(const EnvMissArgs& a, hipStream_t stream);
 void launch_segment_instanced(const InstSegmentArgs& a, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);
 void launch_closest_queue(const QueueTraceArgs& a, bool stats, uint32_t grid_waves, hipStream_t stream);
 void launch_shadow_deferred(const ShadowArgs& a, bool stats, uint32_t grid_waves, hipStream_t stream);

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CRT_ABI_VERSION, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params,
+from ._lib import (CRT_ABI_VERSION, CRT_ENV_HIDE_FROM_CAMERA, crt_environment, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params,
                    crt_scene_desc, crt_tree_cost, lib)
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _cost_dict, _ptr
 
@@ -117,6 +117,26 @@ class Scene:
     def update(self, camera):
         """Scene::update (Scene.h:1233-1246)."""
         check(lib().crt_set_camera(self._h, C.byref(camera.c)))
+
+    def set_environment(self, texels, rotation=None, scale=(1.0, 1.0, 1.0), hide_from_camera=False):
+        """crt_set_environment (include/crt.h): `texels` is a (size, size, 3) float32 octahedral map, row 0 first
+        (caitlynrenderer_amd.environment builds them), `rotation` a 3 x 3 matrix whose rows take world directions to the map's (default: the
+        identity), `scale` an RGB factor.  Rays that leave the scene then return the map's radiance; hide_from_camera keeps the backdrop
+        black.  The sum is not cleared: reset() as after update(camera)."""
+        t = np.ascontiguousarray(texels, np.float32)
+        if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[2] != 3:
+            raise ValueError("texels must be (size, size, 3)")
+        env = crt_environment()
+        env.texels, env.size = _ptr(t), t.shape[0]
+        env.flags = CRT_ENV_HIDE_FROM_CAMERA if hide_from_camera else 0
+        r = np.eye(3, dtype=np.float32) if rotation is None else np.ascontiguousarray(rotation, np.float32).reshape(3, 3)
+        env.rotation[:] = [float(x) for x in r.reshape(-1)]
+        env.scale[:] = [float(np.float32(x)) for x in scale]
+        check(lib().crt_set_environment(self._h, C.byref(env)))
+
+    def clear_environment(self):
+        """crt_set_environment(NULL): frames are again what they were without one"""
+        check(lib().crt_set_environment(self._h, None))
 
     def Render(self):
         """Scene::Render (Scene.h:1158-1231) minus the present pass: draw one sample, ++frame_count."""
@@ -321,7 +341,8 @@ class Scene:
 
     def launch_info(self):
         """crt_debug_launch_info's four words as they are: [form, build word, samples per launch chain, shards].  Bit 4 of the build word
-        (16): segment 0 was fed by the lens ray generator (camera aperture > 0), and bits 0-3 are then clear."""
+        (16): segment 0 was fed by the lens ray generator (camera aperture > 0), and bits 0-3 are then clear.  Bit 5 (32): the frame ran with an
+        environment (set_environment)."""
         info = (C.c_int32 * 4)()
         check(lib().crt_debug_launch_info(self._h, info))
         return [int(x) for x in info]

@@ -162,6 +162,51 @@ int crt_scene_create(const crt_scene_desc* desc, crt_scene** out);
 int crt_scene_destroy(crt_scene* s);
 /* replaces Scene::update, Scene.h:1233-1246 */
 int crt_set_camera(crt_scene* s, const crt_camera* cam);
+/* Environment lighting: radiance for path rays that leave the scene (no reference counterpart: RenderOptions carries environment-map
+ * knobs that nothing reads).  Without an environment such a ray ends its path with nothing.
+ * The environment is a square OCTAHEDRAL map of size x size RGB float texels, a 3x3 matrix and an RGB scale.  The map's +z is the centre
+ * texel and -z the four corners; row 0 is the lowest py.  For a ray direction d, every line one IEEE float32 operation in the written
+ * order under DESIGN.md §3's rules (no contraction):
+ *   e    = (R[0].d, R[1].d, R[2].d)           each (r0*d.x + r1*d.y) + r2*d.z;  R = rotation, rows, world -> map
+ *   s    = (|e.x| + |e.y|) + |e.z|            not (s > 0), or s not finite: the radiance is 0, done
+ *   px   = e.x / s;  py = e.y / s
+ *   if e.z < 0:  (px, py) = ((1 - |py|) * sgn(px), (1 - |px|) * sgn(py))      from the OLD px, py; sgn(x) = x < 0 ? -1 : 1
+ *   fx   = (px * 0.5 + 0.5) * size - 0.5;  fy likewise
+ *   i0   = floor(fx), tx = fx - i0;  j0 = floor(fy), ty = fy - j0;  i1 = i0 + 1, j1 = j0 + 1
+ *   tap(i, j):  if i < 0: (i, j) = (0, size-1-j)   else if i > size-1: (i, j) = (size-1, size-1-j)
+ *               then if j < 0: (i, j) = (size-1-i, 0)   else if j > size-1: (i, j) = (size-1-i, size-1)
+ *               then both clamped to [0, size-1]                 (the octahedral edge identification: the filter has no seam)
+ *   c    = (tap(i0,j0)*(1-tx) + tap(i1,j0)*tx)*(1-ty) + (tap(i0,j1)*(1-tx) + tap(i1,j1)*tx)*ty        per channel
+ *   E(d) = c * scale                                                                                    per channel
+ * Integrator rule: when a path's closest-hit ray misses in segment k, the path adds T * E(d) and ends; T is the throughput it carries into
+ * that segment, d that ray's direction, and the weight is 1 for every path, specular or not.  Nothing samples the environment from a
+ * surface (no environment NEE: a small bright sun is noisy), and misses are disjoint from the emitters of the light table, so the estimator
+ * is unbiased as it stands.  The addition is made in segment order, as the path's last, behind every earlier segment's emitter and NEE
+ * terms.  With CRT_ENV_HIDE_FROM_CAMERA segment 0's misses add nothing: the environment lights the scene without showing as a backdrop.
+ * Nothing else about a frame changes — rays, RNG stream, NEE, MIS, materials, resolve —, and with no environment set every frame is what
+ * it was, through the same launches.
+ * Works on flat scenes and on crt_scene_create_instanced[_lit] scenes, with crt_set_devices (every device gets the map; a refused call
+ * leaves every device's previous environment in place), crt_set_shard and option "streams".  Scene state like the camera: it survives
+ * crt_reset, and changing it does not clear the sum (the caller resets, as after crt_set_camera).  env == NULL removes it.
+ * A frame with an environment runs as a chain of queue-fed segments behind a ray-generation launch, k_env_miss between each segment's
+ * closest-hit launch and its shade-only pass, every segment's shadow rays deferred (crt_debug_launch_info bit 5); a pinhole camera
+ * renders crt_render_frames one sample per chain, a lens keeps its chains of up to 8.  It takes no part in the adaptive tile order.
+ * CRT_ERR_INVALID, crt_last_error names the field, nothing stored: null scene; null texels; size outside 1..4096; a texel, scale or
+ * rotation entry that is not finite; a negative texel or scale; unknown flags bits; non-zero reserved; a scene in the BVH2 frame mode
+ * (option "accel" not 0).
+ * Out of scope: importance-sampled environment NEE with MIS; a fused environment arm in the first-segment kernels; environment-aware
+ * feature buffers or denoiser guides; HDR file decoding (crt_image_decode keeps refusing .hdr); batched pinhole samples in one chain; any
+ * environment in the C oracle or the BVH2 frame mode. */
+#define CRT_ENV_HIDE_FROM_CAMERA 1u
+typedef struct crt_environment {
+    const float* texels;      /* size*size*3 floats, RGB, row 0 first */
+    uint32_t size;            /* 1..4096 */
+    uint32_t flags;           /* CRT_ENV_HIDE_FROM_CAMERA or 0; other bits refused */
+    float rotation[9];        /* rows; world -> map */
+    float scale[3];
+    uint32_t reserved[2];     /* must be 0 */
+} crt_environment;
+int crt_set_environment(crt_scene* s, const crt_environment* env);
 /* replaces the path_trace draw in Scene::Render, Scene.h:1208-1213: adds ONE sample
  * per pixel to the device-resident RGB32F sum buffer; (rx,ry) = randomVector. */
 int crt_render_frame(crt_scene* s, float rx, float ry);
@@ -183,6 +228,8 @@ int crt_render_frames(crt_scene* s, uint32_t n, const float* rx, const float* ry
 int crt_render_frames_async(crt_scene* s, uint32_t n, const float* rx, const float* ry);
 int crt_sync(crt_scene* s);
 /* Options (name, value).  Results never depend on the tuning options: every combination is bit-identical.
+ * A frame with an environment (crt_set_environment) has one launch form: "inplace_shadow", "bounce_refill" and "ray_bins" are accepted and
+ * do not apply to it, and "accel" other than 0 is refused while an environment is set.
  *   behaviour
  *     "jitter"            0/1 tent-filter jitter of path_trace.fs:1030-1037 (default 1)
  *     "accel"             what crt_render_frame walks: 0 = the CWBVH (default); 1 = the BVH2 exactly as the shipped
@@ -335,7 +382,8 @@ int crt_trace_device(crt_scene* s, const void* d_rays, size_t n, void* d_hits, i
  * stays valid until the scene is destroyed.
  * The view is the PINHOLE through the camera's position whatever its aperture: every channel is byte for byte independent of
  * crt_camera.aperture and focal_dist.  Behind a lens the buffers are therefore sharper than the image: they show the surface on the
- * central ray of each pixel, not the mix of surfaces an out-of-focus pixel gathers (lens-aware feature buffers are out of scope). */
+ * central ray of each pixel, not the mix of surfaces an out-of-focus pixel gathers (lens-aware feature buffers are out of scope).
+ * An environment (crt_set_environment) changes no channel: the call is unaware of it and miss pixels keep the values they have without. */
 enum { CRT_AOV_HIT = 1, CRT_AOV_IDS = 2, CRT_AOV_NORMAL = 4, CRT_AOV_ALBEDO = 8, CRT_AOV_EMISSION = 16, CRT_AOV_ALL = 31 };
 int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync);
 int crt_read_aov(crt_scene* s, uint32_t channel, void* dst, size_t n_bytes);
@@ -367,7 +415,9 @@ int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr);
  * successful crt_denoise, or with a wrong size.
  * A camera with an aperture: the guides are crt_render_aov's, i.e. the pinhole view through the camera's position.  Out-of-focus regions
  * are therefore filtered against guides sharper than the image: the edge-stopping terms hold the blur back at edges the pinhole sees.
- * A stated limitation; lens-aware guides are out of scope. */
+ * A stated limitation; lens-aware guides are out of scope.
+ * An environment (crt_set_environment): the filter is unaware of it.  Miss pixels keep the guide values they have without one, so the
+ * backdrop is filtered as one region of equal guides. */
 enum { CRT_DENOISE_DEMODULATE = 1 };
 typedef struct crt_denoise_params {      /* 32 bytes */
     uint32_t passes;             /* 1..6; pass i (from 0) has tap spacing s = 2^i */
@@ -427,7 +477,8 @@ int crt_resolve_denoised_device(crt_scene* s, const uint8_t** d_rgba, int sync);
  * world > 1) or a scene on several devices; a read, device or resolve call before any successful crt_temporal, or with a wrong size.
  * A camera with an aperture: the reprojection and its guides keep the pinhole view through the camera's position (crt_render_aov's), so
  * out-of-focus regions are reprojected and tested against guides sharper than the image.  A stated limitation; lens-aware motion
- * vectors are out of scope. */
+ * vectors are out of scope.
+ * An environment (crt_set_environment): the reprojection is unaware of it; miss pixels keep the guide values they have without one. */
 enum { CRT_TEMPORAL_DEMODULATE = 1, CRT_TEMPORAL_CLAMP = 2 };
 enum { CRT_TEMPORAL_SOURCE_SUM = 0, CRT_TEMPORAL_SOURCE_DENOISED = 1 };
 typedef struct crt_temporal_params {   /* 32 bytes */
@@ -533,6 +584,7 @@ int crt_debug_launch_form(crt_scene* s, int32_t* form);
  * info[1] = bit 0: the first segment ran its 6-waves-per-SIMD build (option "wide_first"), bit 1: a one-pass build (no sample loop), bit 2: that
  * build compiled as a last segment (option "last_build"), bit 3: that build's LEAN form (option "lean_build"), bit 4: segment 0 was fed by the
  * lens ray generator (crt_camera.aperture > 0: every segment ran in its queue-fed form; info[0] is then 0 and bits 0-3 are clear),
+ * bit 5: the frame ran with an environment (crt_set_environment: k_env_miss behind every segment's closest-hit launch; bits 0-3 clear),
  * info[2] = samples per pixel of the launch (a lens frame: of the launch chain),
  * info[3] = tile shards rendering side by side (option "streams" / crt_set_devices) */
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]);
