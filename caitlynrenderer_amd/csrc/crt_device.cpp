@@ -1,8 +1,7 @@
-// Device half of include/crt.h: scene upload, per-frame wavefront dispatch, several GPUs, refit / rebuild, packed read-back.  (The
-// images that leave the library — sum, AOVs, denoised, accumulated, their RGBA8 — are crt_outputs.cpp; the scene itself crt_scene.hpp.)
-// Replaces Scene::gpu_data / Render / update (Caitlyn/Scene.h:1000-1246).  Owns its own HIP
-// stream; every kernel of a frame is enqueued there, queue lengths stay on the device, and the
-// host synchronises once per call (never inside the frame).
+// Device half of include/crt.h: scene upload, camera, environment, shard, options, several GPUs, crt_trace, packed read-back, refit /
+// rebuild.  (Everything that enqueues a frame is crt_frames.cpp; the images that leave the library — sum, AOVs, denoised, accumulated,
+// their RGBA8 — are crt_outputs.cpp; the scene itself crt_scene.hpp.)
+// Replaces Scene::gpu_data / update (Caitlyn/Scene.h:1000-1246).  A scene owns its own HIP stream.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -10,7 +9,6 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -32,9 +30,11 @@
 #include "instances_bind.hpp"
 #include "rt_kernels.hpp"
 
+using crt::alloc_frame_buffers;
 using crt::deal_tiles;
 using crt::dev_alloc;
 using crt::ensure_frame;
+using crt::ensure_planes;
 using crt::fail;
 using crt::frame_args;
 using crt::require_device;
@@ -96,119 +96,12 @@ crt::FrameArgs crt::frame_args(const crt_scene* s, float rx, float ry) {
     return f;
 }
 
-namespace {
-
 // Logical device k of n_devices, dividing shard base_rank of base_world among themselves (set_devices_of_shard): every n-th tile of that
 // shard's list starting at its k-th, i.e. shard base_rank + k * base_world of base_world * n_devices of the whole frame.
-inline void device_share(uint32_t k, uint32_t n_devices, uint32_t base_rank, uint32_t base_world, uint32_t* rank, uint32_t* world) {
+static inline void device_share(uint32_t k, uint32_t n_devices, uint32_t base_rank, uint32_t base_world, uint32_t* rank, uint32_t* world) {
     *rank = base_rank + k * base_world;
     *world = base_world * n_devices;
 }
-
-int build_shard(crt_scene* s) {
-    deal_tiles(s->width, s->height, s->tile, s->rank, s->world, s->tiles, &s->n_local_in_frame);
-    s->n_local_tiles = (uint32_t)s->tiles.size();
-    const uint64_t px = (uint64_t)s->n_local_tiles * s->tile * s->tile;
-    if (px >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "framebuffer shard too large for 32-bit pixel indices");
-    s->n_local_pixels = (uint32_t)px;
-    return CRT_OK;
-}
-
-void free_frame_buffers(crt_scene* s) {
-    void** ptrs[] = {(void**)&s->d_tile_xy, (void**)&s->d_tile_order, (void**)&s->d_tile_cost, (void**)&s->d_sum, (void**)&s->d_linear, (void**)&s->d_rgba, (void**)&s->d_rays[0],
-                     (void**)&s->d_rays[1], (void**)&s->d_nee, (void**)&s->d_contrib, (void**)&s->d_nee_perm, (void**)&s->d_qhits, (void**)&s->pb.L, (void**)&s->pb.T, (void**)&s->pb.seed,
-                     (void**)&s->d_lfinal, (void**)&s->d_qinst, (void**)&s->d_rays_lens};
-    for (void** p : ptrs) { if (*p) hipFree(*p); *p = nullptr; }
-    s->batch_cap = 1;
-    s->lens_sub_capacity = 0;
-    s->defer_cap = s->defer_regions = s->defer_sub_capacity = s->lfinal_cap = 0;
-    // the bins' capacities and offsets describe the queues that were just freed: back to "everything overflows"
-    if (s->d_bins) (void)hipMemset(s->d_bins, 0, crt_scene::bins_words() * sizeof(uint32_t));
-    if (s->h_tile_cost) { (void)hipHostFree(s->h_tile_cost); s->h_tile_cost = nullptr; }
-    if (s->h_tile_order) { (void)hipHostFree(s->h_tile_order); s->h_tile_order = nullptr; }
-    s->frame_buffers_ready = false;
-}
-
-int alloc_frame_buffers(crt_scene* s) {
-    free_frame_buffers(s);
-    int rc = build_shard(s);
-    if (rc) return rc;
-    const size_t P = s->n_local_pixels;
-    if ((rc = dev_alloc(&s->d_tile_xy, s->n_local_tiles))) return rc;
-    HIPCHK(hipMemcpy(s->d_tile_xy, s->tiles.data(), s->tiles.size() * sizeof(uint2), hipMemcpyHostToDevice));
-    {   // processing order: centre-out until a frame has been measured
-        const uint32_t nt = s->n_local_tiles, T = s->tile;
-        const float cx = 0.5f * (float)((s->width + T - 1) / T) - 0.5f, cy = 0.5f * (float)((s->height + T - 1) / T) - 0.5f;
-        std::vector<uint32_t> order(nt);
-        for (uint32_t i = 0; i < nt; ++i) order[i] = i;
-        auto d2 = [&](uint32_t i) { const float dx = (float)s->tiles[i].x - cx, dy = (float)s->tiles[i].y - cy; return dx * dx + dy * dy; };
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return d2(a) < d2(b); });
-        if ((rc = dev_alloc(&s->d_tile_order, std::max<uint32_t>(nt, 1)))) return rc;
-        if ((rc = dev_alloc(&s->d_tile_cost, std::max<uint32_t>(nt, 1)))) return rc;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_tile_cost), std::max<uint32_t>(nt, 1) * sizeof(uint32_t)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_tile_order), std::max<uint32_t>(nt, 1) * sizeof(uint32_t)));
-        if (nt) HIPCHK(hipMemcpy(s->d_tile_order, order.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (!s->ev_tile_cost) HIPCHK(hipEventCreateWithFlags(&s->ev_tile_cost, hipEventDisableTiming));
-        if (!s->ev_tile_order) HIPCHK(hipEventCreateWithFlags(&s->ev_tile_order, hipEventDisableTiming));
-        s->tile_state = crt_scene::TILES_WANT;
-        s->tile_order_uploading = false;
-        s->tiles_measured_once = false;
-        s->tile_cost_spread = 0.f;
-    }
-    if ((rc = dev_alloc(&s->d_sum, 3 * std::max<size_t>(P, 1)))) return rc;     // a shard may hold no tile at all (more devices or streams than tiles)
-    HIPCHK(hipMemset(s->d_sum, 0, 3 * std::max<size_t>(P, 1) * sizeof(float)));
-    // a workgroup group handles every 8th unit of 4096 pixels/rays, so it can emit at most this many rays per segment
-    s->sub_capacity = (uint32_t)(((P + 4095) / 4096 + 7) / 8 * 4096);
-    const size_t Q = 8 * (size_t)s->sub_capacity;
-    // the deferred shadow rays' buffers (inplace_shadow 0 / 2) and the hit buffer of the bounce pools (bounce_refill = 1) are allocated
-    // by the first frame that needs them
-    if (s->max_depth > 1 || s->inst) {           // path state and ray queues exist only for multi-segment paths, and for the queue-fed frames of an instanced scene
-        if ((rc = dev_alloc(&s->d_rays[0], 2 * Q))) return rc;
-        if ((rc = dev_alloc(&s->d_rays[1], 2 * Q))) return rc;
-        s->rays_doubled = false;
-        if ((rc = dev_alloc(&s->pb.L, P))) return rc;
-        if ((rc = dev_alloc(&s->pb.T, P))) return rc;
-        if ((rc = dev_alloc(&s->pb.seed, P))) return rc;
-    }
-    s->frame_buffers_ready = true;
-    return CRT_OK;
-}
-
-int collect_stats(crt_scene* s) {
-    if (!s->stats_pending) return CRT_OK;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    crt_frame_stats st{};
-    for (int i = 0; i < s->n_spans; ++i) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, s->spans[i].a, s->spans[i].b) != hipSuccess) continue;
-        switch (s->spans[i].kind) {
-            case 0: st.ms_raygen += ms; break;
-            case 1: st.ms_trace_closest += ms; st.n_trace_launches++; break;
-            case 2: st.ms_trace_any += ms; st.n_trace_launches++; break;
-            default: st.ms_shade += ms; break;
-        }
-    }
-    if (s->n_spans > 0) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, s->spans[0].a, s->spans[s->n_spans - 1].b) == hipSuccess) st.ms_total = ms;
-    }
-    st.closest_rays = s->stats.closest_rays;
-    st.any_rays = s->stats.any_rays;
-    if (s->stats_from_frame && s->stats_counted && s->h_visit_totals) {
-        st.nodes_closest = s->h_visit_totals[0];
-        st.tris_closest = s->h_visit_totals[1];
-        st.nodes_any = s->h_visit_totals[2]; st.tris_any = s->h_visit_totals[3];
-        st.wave_steps_closest_nodes = s->h_visit_totals[4]; st.wave_steps_closest_tris = s->h_visit_totals[5];
-        st.wave_steps_any_nodes = s->h_visit_totals[6]; st.wave_steps_any_tris = s->h_visit_totals[7];
-        st.closest_hits = s->h_visit_totals[8];
-        st.nodes_closest_uniform = s->h_visit_totals[10]; st.nodes_any_uniform = s->h_visit_totals[11];
-    }
-    s->stats = st;
-    s->stats_pending = false;
-    return CRT_OK;
-}
-
-}  // namespace
 
 // device, stream, environment overrides and the descriptor's scalars: shared by both ways of creating a scene
 static int init_scene_common(crt_scene* s, const crt_scene_desc* d) {
@@ -260,7 +153,7 @@ static int pad_rows(hipStream_t st, const char* who, T** buf, uint32_t rows_in, 
 // The nodes' child planes as floats (uniform node steps, rt_kernels.hip node8_intersect_planes): 192 B per node, 2.4 x the node array — built
 // when a frame first walks the CWBVH, so a scene that only ever renders through its BVH2 (option accel 1 / 2) or only serves crt_trace never
 // holds them.  In stream order before the frame's kernels: no host wait.  A replica made later gets its copy with the other scene buffers.
-static int ensure_planes(crt_scene* s) {
+int crt::ensure_planes(crt_scene* s) {                    // crt_frames.cpp calls it too (crt_scene.hpp)
     if (s->d_planes || !s->d_nodes || !s->info.n_nodes8) return CRT_OK;
     int rc;
     if (s->primary && s->shares_scene) {
@@ -606,7 +499,7 @@ int crt_scene_create_instanced_lit(const crt_instanced_scene_desc* d, const stru
 // it): counts and scan, ONE small read for the total (the host's wait: everything queued on the stream before is then done, so a table
 // that has to grow can be freed), then transform, tree sum and pdf column on the scene's stream.  The mutators of the handle return done
 // and wait for this stream first, so the live arrays are complete and nothing in flight reads the table.
-static int ensure_light_table(crt_scene* s) {
+extern "C++" int crt::ensure_light_table(crt_scene* s) {      // crt_frames.cpp calls it too (crt_scene.hpp)
     SceneLights* L = s->lit;
     if (!L) return CRT_OK;
     crt::InstancesView v{};
@@ -666,7 +559,7 @@ int crt_scene_read_lights(crt_scene* s, crt_light* dst, size_t cap, size_t* n_ou
     if (!s) return fail(CRT_ERR_INVALID, who + "null scene");
     if (!s->inst) return fail(CRT_ERR_INVALID, who + "not an instanced scene");
     try {
-        const int rc = ensure_light_table(s);
+        const int rc = crt::ensure_light_table(s);
         if (rc) return rc;
     } catch (const std::exception& e) {
         return fail(CRT_ERR_NOMEM, who + e.what());
@@ -1077,11 +970,6 @@ int crt_set_shard(crt_scene* s, uint32_t rank, uint32_t world, uint32_t tile) {
     return alloc_frame_buffers(s);
 }
 
-extern "C++" int crt::ensure_frame(crt_scene* s) {       // crt_outputs.cpp calls it too (crt_scene.hpp)
-    if (!s->frame_buffers_ready) return alloc_frame_buffers(s);
-    return CRT_OK;
-}
-
 int crt_reset(crt_scene* s) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_reset: null scene");
     HIPCHK(hipSetDevice(s->device));
@@ -1226,652 +1114,6 @@ int crt_set_option(crt_scene* s, const char* name, int value) {
     return CRT_OK;
 }
 
-// One sample per pixel: raygen -> [closest, shade, any, resolve] x max_depth -> accumulate.  n_samples > 1 (a one-segment path
-// whose shadow rays are walked in place: nothing is queued between launches): the same launch renders that many samples of
-// every pixel one after the other — what n_samples calls would do, bit for bit, without their launch gaps and kernel tails.
-static int ensure_batch_buffers(crt_scene* s, uint32_t cap);
-static bool uses_ray_bins(const crt_scene* s) {
-    // bounce rays binned between the segments (option "ray_bins"): big trees, CWBVH walks, the lock-step segment kernels
-    return s->ray_bins != 0u && s->max_depth > 1u && s->info.n_nodes8 >= 64 && s->accel == 0u && !s->bounce_refill && !s->env();
-}
-// Segments [first, max_depth) defer their NEE shadow rays (option "inplace_shadow"); first = max_depth: none does.  BVH2 frames walk in place.
-static uint32_t first_deferred_segment(const crt_scene* s) {
-    if (s->inst) return 0u;                  // an instanced scene's frames defer every segment's shadow rays (k_shadow_instances_deferred)
-    if (s->env()) return 0u;                 // a frame with an environment: every segment has a slot region, whatever "inplace_shadow" says
-    const uint32_t mode = s->inplace_shadow == 3u ? (s->info.n_nodes8 >= 64 ? 2u : 1u) : s->inplace_shadow;
-    if (s->accel != 0u || mode == 1u) return s->max_depth;
-    return mode == 0u ? 0u : std::min(1u, s->max_depth);
-}
-// d_lfinal for the samples the path buffers are sized for (frames that fold: several samples of multi-segment paths, deferred shadow rays)
-static int ensure_lfinal(crt_scene* s) {
-    if (s->d_lfinal && s->lfinal_cap >= s->batch_cap) return CRT_OK;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->d_lfinal) { (void)hipFree(s->d_lfinal); s->d_lfinal = nullptr; }
-    const size_t n = (size_t)s->n_local_pixels * s->batch_cap;
-    int rc = dev_alloc(&s->d_lfinal, n);
-    if (rc) return rc;
-    HIPCHK(hipMemset(s->d_lfinal, 0, n * sizeof(float4)));      // pixels outside the frame are never written: they stay zero
-    s->lfinal_cap = s->batch_cap;
-    return CRT_OK;
-}
-// The NEE queue and the contribution slots of the deferring segments, for the samples per launch the path buffers are sized for
-static int ensure_defer_buffers(crt_scene* s) {
-    const uint32_t regions = s->max_depth - first_deferred_segment(s);
-    if (regions == 0u) return CRT_OK;
-    if (s->d_nee && s->defer_cap == s->batch_cap && s->defer_regions >= regions && s->defer_sub_capacity == s->sub_capacity) return CRT_OK;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (void** p : {(void**)&s->d_nee, (void**)&s->d_contrib, (void**)&s->d_nee_perm}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    s->defer_cap = s->defer_regions = 0;
-    const uint64_t slots = (uint64_t)regions * s->n_local_pixels * s->batch_cap;
-    if (slots >= (1ull << 32)) return fail(CRT_ERR_LIMIT, "deferred shadow rays: more than 2^32 contribution slots (segments x pixels x samples per launch); use inplace_shadow 1");
-    int rc;
-    if ((rc = dev_alloc(&s->d_nee, 2 * 8 * (size_t)s->sub_capacity * regions)) || (rc = dev_alloc(&s->d_contrib, (size_t)slots))) return rc;
-    if ((uint64_t)8 * s->sub_capacity * regions >= (1ull << 32)) return fail(CRT_ERR_LIMIT, "deferred shadow rays: more than 2^32 queue entries; use inplace_shadow 1");
-    if ((rc = dev_alloc(&s->d_nee_perm, 8 * (size_t)s->sub_capacity * regions))) return rc;
-    if (!s->d_nee_bins) {
-        if ((rc = dev_alloc(&s->d_nee_bins, 2 * 4096 + 9 * kCounterStride))) return rc;
-        HIPCHK(hipMemset(s->d_nee_bins, 0, (2 * 4096 + 9 * kCounterStride) * sizeof(uint32_t)));
-    }
-    s->defer_cap = s->batch_cap; s->defer_regions = regions; s->defer_sub_capacity = s->sub_capacity;
-    return CRT_OK;
-}
-// Everything a batch of n_samples needs ALLOCATED on this device, and nothing enqueued: a scene on several devices or streams prepares
-// all of them before the first launch of any, so that an allocation failing on one leaves no device with half a batch in its sums.
-static int prepare_batch(crt_scene* s, uint32_t n_samples) {
-    HIPCHK(hipSetDevice(s->device));
-    int rc = ensure_frame(s);
-    if (rc) return rc;
-    if (s->n_local_pixels == 0) return CRT_OK;
-    const bool lens = s->lens() && !s->inst;                              // a flat scene's frame through a lens: every segment queue-fed
-    const bool queue_fed = lens || (s->env() && !s->inst);                // ... and so is one with an environment
-    const bool batched_paths = n_samples > 1u && (s->max_depth > 1u || queue_fed);     // finished paths leave their radiance in d_lfinal
-    if (queue_fed && !s->d_rays[0]) {
-        // a one-segment scene held no queues and no path state until its camera got an aperture or the scene an environment: one sample's worth, as alloc_frame_buffers sizes them
-        const size_t P = s->n_local_pixels, Q1 = 8 * (size_t)s->sub_capacity;
-        if ((rc = dev_alloc(&s->d_rays[0], 2 * Q1)) || (rc = dev_alloc(&s->d_rays[1], 2 * Q1))) return rc;
-        s->rays_doubled = false;
-        if (!s->pb.L && (rc = dev_alloc(&s->pb.L, P))) return rc;
-        if (!s->pb.T && (rc = dev_alloc(&s->pb.T, P))) return rc;
-        if (!s->pb.seed && (rc = dev_alloc(&s->pb.seed, P))) return rc;
-    }
-    if (batched_paths && (rc = ensure_batch_buffers(s, n_samples))) return rc;   // grows to the largest batch ever asked for
-    if (lens && (!s->d_rays_lens || s->lens_sub_capacity != s->sub_capacity)) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->d_rays_lens) { (void)hipFree(s->d_rays_lens); s->d_rays_lens = nullptr; }
-        if ((rc = dev_alloc(&s->d_rays_lens, 2 * 8 * (size_t)s->sub_capacity))) return rc;
-        s->lens_sub_capacity = s->sub_capacity;
-    }
-    if (queue_fed && (rc = ensure_lfinal(s))) return rc;                  // such a frame always folds
-    if (first_deferred_segment(s) < s->max_depth && ((rc = ensure_lfinal(s)) || (rc = ensure_defer_buffers(s)))) return rc;
-    if (s->count_visits && !s->d_visit_totals) {
-        if ((rc = dev_alloc(&s->d_visit_totals, 16))) return rc;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s->h_visit_totals), 16 * sizeof(unsigned long long)));
-    }
-    // the hit buffer of the bounce pools (bounce_refill = 1): allocated by the first frame that needs it
-    const size_t Q = 8 * (size_t)s->sub_capacity;
-    if (((s->bounce_refill && (s->max_depth > 1 || lens)) || s->inst || s->env()) && !s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
-    if (s->inst && !s->d_qinst && (rc = dev_alloc(&s->d_qinst, Q))) return rc;
-    if (uses_ray_bins(s)) {
-        if (!s->d_bins) {
-            if ((rc = dev_alloc(&s->d_bins, crt_scene::bins_words()))) return rc;
-            HIPCHK(hipMemsetAsync(s->d_bins, 0, crt_scene::bins_words() * sizeof(uint32_t), s->stream));     // capacities 0: a first launch overflows entirely
-        }
-        if (!s->rays_doubled) {
-            // twice the entries any launch can emit: the bins' places in the first half, the overflow region — in the worst case every
-            // ray of a launch, e.g. the first one after the view changed — in the second.  Between two frames the queues hold nothing.
-            const uint32_t Qe = 8u * s->sub_capacity;
-            HIPCHK(hipStreamSynchronize(s->stream));
-            float4 *r0 = nullptr, *r1 = nullptr;
-            if ((rc = dev_alloc(&r0, 4 * (size_t)Qe)) || (rc = dev_alloc(&r1, 4 * (size_t)Qe))) { if (r0) (void)hipFree(r0); return rc; }
-            (void)hipFree(s->d_rays[0]); (void)hipFree(s->d_rays[1]);
-            s->d_rays[0] = r0; s->d_rays[1] = r1;
-            s->rays_doubled = true;
-        }
-    }
-    return CRT_OK;
-}
-
-// One frame of an instanced scene, buffers prepared: k_raygen, then per segment the two-level closest-hit walk over the
-// segment's queue and the shade-only pass, then ONE two-level any-hit launch for every segment's shadow rays and the fold — the
-// bounce_refill 1 + inplace_shadow 0 sequence below with segment 0 included.  The handle's live arrays are read HERE, at enqueue time.
-// k_env_miss' arguments for the segment whose path rays sit in `rays` / `count` and whose hits sit in d_qhits
-static crt::EnvMissArgs env_miss_args(const crt_scene* s, const float4* rays, const uint32_t* count, size_t n_paths, uint32_t slot_first, uint32_t slot_bit) {
-    crt::EnvMissArgs ea{};
-    ea.rays = rays; ea.count = count; ea.hits = s->d_qhits; ea.sub_capacity = s->sub_capacity; ea.n_paths = (uint32_t)n_paths;
-    ea.T = s->pb.T; ea.contrib = s->d_contrib; ea.slot_first = slot_first; ea.slot_bit = slot_bit;
-    ea.texels = s->d_env; ea.size = s->env_size;
-    for (int k = 0; k < 9; ++k) ea.rotation[k] = s->env_rotation[k];
-    for (int k = 0; k < 3; ++k) ea.scale[k] = s->env_scale[k];
-    return ea;
-}
-
-static int render_instanced_async(crt_scene* s, float rx, float ry) {
-    if (s->lit) { const int rc = ensure_light_table(s); if (rc) return rc; }      // lights that follow the instances
-    crt::InstancesView v{};
-    crt::instances_view(s->inst, &v);
-    const uint32_t P = s->n_local_pixels;
-    const size_t n_paths = P;
-    const bool masked = s->instance_masks != 0u;
-    // a masked frame walks by the handle's TLAS child masks: renewed on the handle's stream if stale, this stream ordered behind that
-    if (masked) { const int rc = crt::instances_child_masks_for(s->inst, s->stream, &s->cmask_seen); if (rc) return rc; }
-    if (!s->timing_accumulate) s->n_spans = 0;
-    if (s->count_visits) HIPCHK(hipMemsetAsync(s->d_visit_totals, 0, 16 * sizeof(unsigned long long), s->stream));
-    s->bank ^= 1u;
-    if (!s->counts_clean) HIPCHK(hipMemsetAsync(s->d_counts, 0, 2 * kCounters * sizeof(uint32_t), s->stream));
-    s->counts_clean = false;
-    uint32_t* const cnt = s->counts();
-    // the instanced kernels carry no events of their own: a timed launch sits between two recorded events
-    auto timed = [&](int kind, auto&& enqueue) {
-        EventSpan* sp = s->new_span(kind);
-        if (sp) (void)hipEventRecord(sp->a, s->stream);
-        enqueue();
-        if (sp) (void)hipEventRecord(sp->b, s->stream);
-    };
-    crt::RaygenArgs ra{};
-    ra.f = frame_args(s, rx, ry);
-    ra.f.tile_order = nullptr;                      // the adaptive tile order belongs to the fused first-segment kernel
-    ra.rays = s->d_rays[0]; ra.count = cnt + counter_index(0, 0, 0); ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
-    ra.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; ra.n_zero = kCounters;
-    if (s->lens()) {                                // the thin-lens form of it, one sample per chain as every instanced frame
-        crt::LensRaygenArgs la{};
-        static_cast<crt::RaygenArgs&>(la) = ra;
-        la.aperture = s->cam.aperture; la.focal_dist = s->cam.focal_dist; la.n_samples = 1u; la.rv_s[0] = rx * ry;
-        timed(0, [&] { crt::launch_raygen_lens(la, s->stream); });
-    } else {
-        timed(0, [&] { crt::launch_raygen(ra, s->stream); });
-    }
-    for (uint32_t b = 0; b < s->max_depth; ++b) {
-        crt::InstMaskQueueArgs qa{};
-        qa.nodes = v.nodes; qa.tris = v.tris; qa.inst = v.inst;
-        if (masked) { qa.child_masks = v.child_masks; qa.n_tlas8 = v.tlas_nodes8; qa.ray_mask = b == 0 ? s->mask_primary : s->mask_bounce; }
-        qa.rays = s->d_rays[b & 1]; qa.count = cnt + counter_index(b, 0, 0); qa.hits = s->d_qhits; qa.hit_inst = s->d_qinst;
-        qa.sub_capacity = s->sub_capacity; qa.n_instances = v.n_instances; qa.stack_entries = v.stack_entries;
-        qa.refill_min = 8; qa.tri_min = 2;          // crt_instances_trace's
-        qa.visit_totals = s->d_visit_totals; qa.overflow = s->d_overflow;
-        timed(1, [&] { crt::launch_closest_instances_queue(qa, s->count_visits, masked, s->stream); });
-        if (s->env() && !(b == 0 && (s->env_flags & CRT_ENV_HIDE_FROM_CAMERA))) {
-            // the paths this walk found to miss take the environment's radiance through their slot of this segment
-            const crt::EnvMissArgs ea = env_miss_args(s, s->d_rays[b & 1], cnt + counter_index(b, 0, 0), n_paths, (uint32_t)((size_t)b * n_paths), 1u << (8u + b));
-            timed(3, [&] { crt::launch_env_miss(ea, s->stream); });
-        }
-        crt::InstSegmentArgs sa{};
-        sa.triangles = s->d_triangles; sa.normals = s->d_normals; sa.materials = s->d_materials; sa.lights = s->d_lights; sa.n_lights = (int32_t)s->n_lights;
-        sa.stack_entries = 2;                       // the shade-only pass walks nothing
-        sa.texcoords = s->d_texcoords; sa.textures = s->d_textures;
-        sa.tex_width = s->tex_width; sa.tex_height = s->tex_height; sa.n_textures = s->n_textures;
-        sa.f = ra.f;
-        sa.sub_capacity = s->sub_capacity;
-        sa.rays_in = s->d_rays[b & 1]; sa.count_in = cnt + counter_index(b, 0, 0); sa.hits_in = s->d_qhits;
-        sa.rays_next = s->d_rays[(b + 1) & 1]; sa.count_next = cnt + counter_index(b + 1, 0, 0);
-        sa.count_shadow = cnt + counter_index(b, 1, 0);
-        sa.shadow = s->d_nee + 2 * (size_t)b * 8u * s->sub_capacity;      // region = segment: every segment defers
-        sa.contrib = s->d_contrib + (size_t)b * n_paths;
-        sa.slot_first = (uint32_t)((size_t)b * n_paths);
-        sa.slot_bit = 1u << (8u + b);
-        sa.pb = s->pb; sa.sum = s->d_sum;
-        sa.last_segment = (b + 1 == s->max_depth) ? 1u : 0u;
-        sa.visit_totals = s->d_visit_totals; sa.overflow = s->d_overflow;
-        sa.l_final = s->d_lfinal;
-        sa.n_samples = 1u; sa.rv_s[0] = rx * ry;
-        sa.hit_inst = s->d_qinst; sa.inst_w2o = v.w2o; sa.inst_mesh = v.mesh_of; sa.mesh_base = s->d_mesh_base;
-        sa.light_first = s->lit ? s->lit->d_first : nullptr;
-        timed(3, [&] { crt::launch_segment_instanced(sa, s->count_visits, s->trace_grid(P, 5), s->waves_per_workgroup, s->stream); });
-    }
-    crt::InstMaskShadowArgs sh{};
-    sh.nodes = v.nodes; sh.tris = v.tris; sh.inst = v.inst;
-    if (masked) { sh.child_masks = v.child_masks; sh.n_tlas8 = v.tlas_nodes8; sh.ray_mask = s->mask_shadow; }
-    sh.shadow = s->d_nee; sh.count = cnt + counter_index(0, 1, 0); sh.count_stride = counter_index(1, 1, 0) - counter_index(0, 1, 0);
-    sh.contrib = s->d_contrib; sh.n_slots = (uint32_t)(n_paths * s->max_depth);
-    sh.pools_per_region = (s->sub_capacity + 63u) / 64u; sh.n_regions = s->max_depth;
-    sh.sub_capacity = s->sub_capacity; sh.n_instances = v.n_instances; sh.stack_entries = v.stack_entries;
-    sh.refill_min = 8; sh.tri_min = 2;
-    sh.visit_totals = s->d_visit_totals ? s->d_visit_totals + 2 : nullptr; sh.overflow = s->d_overflow;
-    timed(2, [&] { crt::launch_shadow_instances_deferred(sh, s->count_visits, masked, s->stream); });
-    crt::launch_fold_paths(s->d_sum, s->d_lfinal, s->d_contrib, P, 1u, 0u, s->stream);
-    if (s->count_visits)
-        HIPCHK(hipMemcpyAsync(s->h_visit_totals, s->d_visit_totals, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    s->stats_counted = s->count_visits;
-    HIPCHK(hipGetLastError());
-    s->counts_clean = true;
-    s->stats_pending = true;
-    s->stats_from_frame = true;
-    s->samples_in_stats = 1;
-    s->last_launch_form = 0; s->last_launch_samples = 1; s->last_launch_wide = 0; s->last_launch_one_pass = 0; s->last_launch_last = 0; s->last_launch_lean = 0; s->last_launch_lens = s->lens() ? 1 : 0;
-    s->last_launch_env = s->env() ? 1 : 0;
-    return CRT_OK;
-}
-
-static int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs, const float* rys) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_render_frame: null scene");
-    if (!s->have_camera) return fail(CRT_ERR_INVALID, "crt_render_frame: crt_set_camera was never called");
-    int rc = prepare_batch(s, n_samples);            // sets the device; a no-op when render_batch_all has prepared every device already
-    if (rc) return rc;
-    if (s->n_local_pixels == 0) return CRT_OK;
-    if (s->inst) return render_instanced_async(s, rxs[0], rys[0]);      // one sample per launch chain (batch_limit)
-    const uint32_t P = s->n_local_pixels;
-    // A camera with an aperture: k_raygen_lens writes segment 0's rays and path state, and EVERY segment runs in its
-    // queue-fed form; the fused first-segment kernels, their tile order and their sample forms are not involved
-    const bool lens = s->lens();
-    // An environment: the same chain — k_raygen in the lens generator's place when the camera is a pinhole —, every segment's
-    // closest hits through k_closest_queue, then k_env_miss for the paths that missed, then the shade-only pass; every segment's shadow rays
-    // deferred (first_deferred_segment is 0), whatever "inplace_shadow", "bounce_refill" and "ray_bins" say
-    const bool env = s->env();
-    const bool queue_fed = lens || env;
-    const bool batched_paths = n_samples > 1u && (s->max_depth > 1u || queue_fed);
-    const uint32_t first_deferred = first_deferred_segment(s);         // segments from here on leave their shadow rays to k_shadow_deferred
-    const bool any_deferred = first_deferred < s->max_depth;
-    const bool folds = batched_paths || any_deferred || queue_fed;           // finished paths leave their radiance in d_lfinal, k_fold_paths adds it to the sum
-    const size_t n_paths = (size_t)P * n_samples;
-    const float rx = rxs[0], ry = rys[0];
-    const crt::FrameArgs f = frame_args(s, rx, ry);
-    if (!s->timing_accumulate) s->n_spans = 0;
-    if (s->count_visits) HIPCHK(hipMemsetAsync(s->d_visit_totals, 0, 16 * sizeof(unsigned long long), s->stream));
-    // counter banks alternate per frame; k_segment<FIRST> clears the other bank for the frame after this one, so a
-    // memset is only needed for the very first frame (or after a failed launch left the banks in an unknown state)
-    // tile order: adopt a finished measurement, start one if the view is new
-    bool measure_tiles = false;
-    if (s->adaptive_tiles && s->n_local_tiles > 1 && !s->capturing && !queue_fed) {      // a lens or environment frame leaves the tile order and its measurement as they are
-        const bool arrived = s->tile_state == crt_scene::TILES_PENDING && hipEventQuery(s->ev_tile_cost) == hipSuccess;
-        (void)hipGetLastError();                                    // "not ready" is an answer, not an error to report later
-        if (arrived) {
-            if (s->tile_order_uploading) HIPCHK(hipEventSynchronize(s->ev_tile_order));     // the pinned order buffer is free again
-            const uint32_t nt = s->n_local_tiles;
-            // Most expensive first.  A unit of work is 4096 pixels = spu tiles (1 for the default 64x64 tile); unit U belongs to
-            // workgroup group U & 7 (one group per XCD, no rebalancing between them) and a group renders its units in order.
-            // So group g's k-th tile sits in slot ((k / spu) * 8 + g) * spu + k % spu, and the sorted list is dealt to the
-            // groups' k-th places in snake order — 0..7, 7..0, ... — which keeps the groups' sums level and every group's
-            // own sequence descending.
-            std::vector<uint32_t> sorted, row;
-            try { sorted.resize(nt); row.reserve(8); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_render_frame: out of host memory (tile order)"); }
-            for (uint32_t i = 0; i < nt; ++i) sorted[i] = i;
-            const uint32_t* cost = s->h_tile_cost;
-            std::sort(sorted.begin(), sorted.end(), [cost](uint32_t a, uint32_t b) { return cost[a] > cost[b] || (cost[a] == cost[b] && a < b); });
-            const uint32_t tile_px = s->tile * s->tile, spu = tile_px < 4096u && 4096u % tile_px == 0u ? 4096u / tile_px : 1u;
-            // how far the expensive tiles stand above the rest (99th percentile over mean): what wave_samples = 2 decides on
-            uint64_t cost_sum = 0;
-            for (uint32_t i = 0; i < nt; ++i) cost_sum += cost[i];
-            s->tile_cost_spread = cost_sum ? (float)((double)cost[sorted[nt / 100u]] * nt / (double)cost_sum) : 0.f;
-            uint32_t next = 0;
-            for (uint32_t k = 0; next < nt; ++k) {
-                row.clear();
-                for (uint32_t g = 0; g < 8u; ++g) {
-                    const uint64_t slot = ((uint64_t)(k / spu) * 8u + g) * spu + k % spu;
-                    if (slot < nt) row.push_back((uint32_t)slot);
-                }
-                if (k & 1u) std::reverse(row.begin(), row.end());
-                for (uint32_t slot : row) s->h_tile_order[slot] = sorted[next++];
-            }
-            HIPCHK(hipMemcpyAsync(s->d_tile_order, s->h_tile_order, nt * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-            HIPCHK(hipEventRecord(s->ev_tile_order, s->stream));
-            s->tile_order_uploading = true;
-            s->tile_state = crt_scene::TILES_DONE;
-        }
-        ++s->frames_since_tile_measure;
-        // a camera that moves every frame would otherwise sort the tiles on the host every frame: at most one measurement per 16
-        // frames (the first one at once); the counting kernels have another cost profile (measured: a worse order) and do not measure
-        if (s->tile_state == crt_scene::TILES_WANT && !s->count_visits && (!s->tiles_measured_once || s->frames_since_tile_measure >= 16u)) {
-            s->tiles_measured_once = true;
-            s->frames_since_tile_measure = 0;
-            HIPCHK(hipMemsetAsync(s->d_tile_cost, 0, s->n_local_tiles * sizeof(uint32_t), s->stream));
-            measure_tiles = true;
-        }
-    }
-    s->bank ^= 1u;
-    if (s->accel == 0u) { const int prc = ensure_planes(s); if (prc) return prc; }
-    if (!s->counts_clean) HIPCHK(hipMemsetAsync(s->d_counts, 0, 2 * kCounters * sizeof(uint32_t), s->stream));
-    s->counts_clean = false;
-    uint32_t* const cnt = s->counts();
-
-    if (lens) {
-        crt::LensRaygenArgs ra{};
-        ra.f = f;
-        ra.f.tile_order = nullptr;                      // storage order: the tile order belongs to the fused first-segment kernels
-        ra.rays = s->d_rays_lens; ra.count = cnt + counter_index(0, 0, 0); ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
-        ra.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; ra.n_zero = kCounters;
-        ra.aperture = s->cam.aperture; ra.focal_dist = s->cam.focal_dist; ra.n_samples = n_samples;
-        for (uint32_t k = 0; k < 8u; ++k) ra.rv_s[k] = k < n_samples ? rxs[k] * rys[k] : 0.f;
-        EventSpan* sp = s->new_span(0);                 // the kernel carries no events of its own: recorded around it, as for an instanced frame
-        if (sp) (void)hipEventRecord(sp->a, s->stream);
-        crt::launch_raygen_lens(ra, s->stream);
-        if (sp) (void)hipEventRecord(sp->b, s->stream);
-    } else if (env) {
-        crt::RaygenArgs ra{};                           // the pinhole's primary rays as an instanced frame generates them: one sample per chain (batch_limit)
-        ra.f = f;
-        ra.f.tile_order = nullptr;
-        ra.rays = s->d_rays[0]; ra.count = cnt + counter_index(0, 0, 0); ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
-        ra.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; ra.n_zero = kCounters;
-        EventSpan* sp = s->new_span(0);
-        if (sp) (void)hipEventRecord(sp->a, s->stream);
-        crt::launch_raygen(ra, s->stream);
-        if (sp) (void)hipEventRecord(sp->b, s->stream);
-    }
-    for (uint32_t b = 0; b < s->max_depth; ++b) {
-        const bool first = b == 0 && !queue_fed;        // the fused first-segment kernels; false = a queue-fed segment
-        crt::SegmentArgs sa{};
-        sa.nodes = s->d_nodes; sa.planes = s->d_planes; sa.tris = s->d_tris; sa.triangles = s->d_triangles; sa.normals = s->d_normals;
-        sa.materials = s->d_materials; sa.lights = s->d_lights; sa.n_lights = (int32_t)s->n_lights;
-        sa.stack_entries = s->stack_entries;
-        sa.texcoords = s->d_texcoords; sa.textures = s->d_textures;
-        sa.tex_width = s->tex_width; sa.tex_height = s->tex_height; sa.n_textures = s->n_textures;
-        sa.f = f;
-        sa.sub_capacity = s->sub_capacity;
-        const bool bvh2 = s->accel != 0u;
-        // trees of a few nodes: plain per-lane closest-hit loop (tri_min = 0) and no bounce pools
-        const bool small_tree = s->info.n_nodes8 < 64;
-        const bool inplace = b < first_deferred;            // shadow rays walked inside k_segment (else: left to k_shadow_deferred)
-        sa.tri_min = small_tree ? 0u : s->tri_min;
-        sa.lanes_log2 = s->lanes_per_ray >= 8u ? 3u : s->lanes_per_ray >= 4u ? 2u : s->lanes_per_ray >= 2u ? 1u : 0u;
-        sa.nodes2 = s->d_bvh2; sa.tris2 = s->d_tris2; sa.stack_entries2 = s->bvh2_stack; sa.tie = s->accel == 2u ? 1u : 0u;
-        const bool bins = uses_ray_bins(s);              // tables and the queues' overflow halves exist (prepare_batch)
-        const uint32_t Qe = 8u * s->sub_capacity;        // entries of the bins' half of a queue = what the sub-queue form holds
-        if (bins && b + 1 < s->max_depth) {
-            crt::RayBins& o = sa.bins_out;
-            o.count = s->bin_count(b + 1); o.cap = s->bin_cap(s->bank, b + 1); o.off = s->bin_off(s->bank, b + 1);
-            o.ovf_count = s->bin_ovf(b + 1); o.ovf_base = Qe;
-            // option "ray_bins": 1 ballots, 2 per-ray atomics, 3 ballots for the first segment's emission and per-ray atomics after, 4 ranking
-            // through LDS, 5 ballots for the first segment's emission (a handful of keys per wave) and LDS ranking after
-            o.per_lane = s->ray_bins == 2u ? 1u : s->ray_bins == 3u ? (b > 0 ? 1u : 0u) : s->ray_bins == 4u ? 2u : s->ray_bins == 5u ? (b > 0 ? 2u : 0u) : 0u;
-            for (int k = 0; k < 3; ++k) {
-                const float ext = s->bounds_hi[k] - s->bounds_lo[k];
-                o.origin[k] = s->bounds_lo[k];
-                o.scale[k] = ext > 0.f ? 8.0f / ext : 0.f;
-            }
-        }
-        if (bins && b > 0) { sa.bin_start = s->bin_start(b); sa.bin_off_in = s->bin_off(s->bank, b); sa.ovf_base_in = Qe; }
-        sa.rays_in = (lens && b == 0) ? s->d_rays_lens : s->d_rays[b & 1]; sa.count_in = cnt + counter_index(b, 0, 0);
-        sa.rays_next = s->d_rays[(b + 1) & 1]; sa.count_next = cnt + counter_index(b + 1, 0, 0);
-        sa.count_shadow = cnt + counter_index(b, 1, 0);
-        if (!inplace) {
-            const uint32_t r = b - first_deferred;           // this segment's region of the NEE queue and of the slot array
-            sa.shadow = s->d_nee + 2 * (size_t)r * 8u * s->sub_capacity;
-            sa.contrib = s->d_contrib + (size_t)r * n_paths;
-            sa.slot_first = (uint32_t)((size_t)r * n_paths);
-            sa.slot_bit = 1u << (8u + b);
-        }
-        sa.pb = s->pb; sa.sum = s->d_sum;
-        sa.last_segment = (b + 1 == s->max_depth) ? 1u : 0u;
-        sa.visit_totals = s->d_visit_totals;
-        sa.overflow = s->d_overflow;
-        if (first) { sa.zero_counts = s->d_counts + (size_t)(s->bank ^ 1u) * kCounters; sa.n_zero = kCounters; }
-        sa.l_final = folds ? s->d_lfinal : nullptr;
-        sa.tile_cost = (first && measure_tiles) ? s->d_tile_cost : nullptr;
-        sa.n_samples = first ? n_samples : 1u;
-        // how the samples of a batched launch sit on the hardware (option "wave_samples"): 2 = four samples of a 4 x 4 pixel quadrant in
-        // the lanes of one wave — the 64 rays of a wave leave a quarter of the area and agree on their nodes like the rays of a frame of
-        // twice the resolution (1 M triangles, 1080p: +8.5 % at 4 samples per launch, +12 % at 8; shards gain as well; trees of a few
-        // nodes lose 9 %: more, shorter waves) —, 1 = the samples on the waves of a workgroup, 0 = one after the other in each wave
-        const bool lanes_ok = (n_samples & 3u) == 0u && !small_tree && !bvh2;
-        sa.wave_samples = 0u;
-        if (first && n_samples > 1u) {
-            if (lanes_ok && s->wave_samples >= 2u) sa.wave_samples = 2u;
-            else if (s->wave_samples != 3u && s->use_wave_samples()) sa.wave_samples = 1u;
-        }
-        // the first segment's 6-wave build where the launch is bound by throughput, the 5-wave build where its longest waves set its length
-        // (with four samples in the lanes of a wave a launch has four times the waves, each a quarter as long, and the measure above —
-        // made for samples that follow each other in a wave — flips too early: the 6-wave build wins down to about a million pixels,
-        // i.e. while the launch fills the chip's 6,144 wave slots eight times over; an eighth of the 4K frame 0.405 -> 0.396 ms, half a
-        // 1080p frame 0.435 -> 0.421, a quarter 0.225 against 0.231 the other way)
-        bool wide_auto = !s->bound_by_longest_waves();
-        if (sa.wave_samples == 2u)
-            wide_auto = (double)(s->n_local_pixels / 16u) * (double)(n_samples / 4u) >= 8.0 * (double)s->n_cu * 4.0 * 6.0;
-        sa.wide_first = (first && (s->wide_first == 2u ? wide_auto : s->wide_first != 0u)) ? 1u : 0u;
-        if (b == 0) { s->last_launch_form = (int)sa.wave_samples; s->last_launch_samples = (int)n_samples; }
-        for (uint32_t k = 0; k < 8u; ++k) sa.rv_s[k] = k < n_samples ? rxs[k] * rys[k] : 0.f;
-        sa.last_build = s->last_build;
-        EventSpan* sp = s->new_span(1);
-        // option bounce_refill: the closest hits of a bounce segment through lane-refill pools (k_closest_queue), then a shade-only pass
-        const bool pretraced = env || (!first && s->bounce_refill && !small_tree && !bvh2 && s->tri_min != 0u && !bins);
-        if (pretraced) {
-            crt::QueueTraceArgs qa{};
-            qa.nodes = s->d_nodes; qa.tris = s->d_tris; qa.rays = sa.rays_in; qa.count = sa.count_in; qa.hits = s->d_qhits;
-            qa.stack_entries = s->stack_entries; qa.sub_capacity = s->sub_capacity; qa.refill_min = s->refill_min; qa.tri_min = s->tri_min ? s->tri_min : 1u;      // (0 only on an environment frame: the pools vote, as k_shadow_deferred's do)
-            qa.pool = s->refill_pool; qa.lanes_log2 = sa.lanes_log2;
-            qa.persistent = s->persistent; qa.cursors = cnt + cursor_index_closest(b);
-            qa.visit_totals = s->d_visit_totals; qa.overflow = s->d_overflow;
-            if (sp) crt::set_launch_events(sp->a, nullptr);                 // span = both launches of the segment
-            const size_t lds_q = (size_t)(s->stack_entries + CRT_HIT_SLOTS) * 64 * sizeof(uint2);
-            crt::launch_closest_queue(qa, s->count_visits, s->persistent ? s->resident_waves(lds_q, 8) : 8u * ((s->sub_capacity + qa.pool - 1u) / qa.pool), s->stream);
-            sa.hits_in = s->d_qhits;
-            if (env && !(b == 0 && (s->env_flags & CRT_ENV_HIDE_FROM_CAMERA))) {
-                // option "timing" 2: a span of its own (recorded around it, inside the segment's span; crt_frame_stats counts it under ms_shade)
-                EventSpan* es = s->new_span(3);
-                if (es) (void)hipEventRecord(es->a, s->stream);
-                crt::launch_env_miss(env_miss_args(s, sa.rays_in, sa.count_in, n_paths, sa.slot_first, sa.slot_bit), s->stream);
-                if (es) (void)hipEventRecord(es->b, s->stream);
-            }
-            if (sp) crt::set_launch_events(nullptr, sp->b);
-        } else if (sp) crt::set_launch_events(sp->a, sp->b);
-        // A workgroup renders ONE chunk (CRT_CHUNK_LOOP), so the grid has to cover every chunk a sub-queue can hold: a group's
-        // sub-queue gets the rays of that group's units of 4096 pixels — ceil(units / 8) of them — times the samples of the launch.
-        // (P * n_samples spread evenly over the 8 groups is fewer chunks than that when the units do not divide by 8.)
-        uint32_t grid = s->trace_grid(P, sa.wide_first ? 6 : 5);
-        if (!first && batched_paths) grid *= n_samples;
-        const int build = crt::launch_segment(sa, first, pretraced, inplace, bvh2, s->special_materials, s->count_visits, s->lean_build != 0u && s->tree_validated, grid, s->waves_per_workgroup, s->stream);
-        if (b == 0) { s->last_launch_wide = build & 1; s->last_launch_one_pass = (build >> 1) & 1; s->last_launch_last = (build >> 2) & 1; s->last_launch_lean = (build >> 3) & 1; s->last_launch_lens = lens ? 1 : 0; s->last_launch_env = env ? 1 : 0; }
-        if (sa.bins_out.count) {
-            // fill counts -> the next launch's index space and ray count, and the next frame's capacities (the other parity)
-            crt::BinScanArgs ba{};
-            ba.count = s->bin_count(b + 1); ba.cap = s->bin_cap(s->bank, b + 1); ba.start = s->bin_start(b + 1); ba.ovf_count = s->bin_ovf(b + 1);
-            ba.n_in = cnt + counter_index(b + 1, 0, 0);
-            ba.cap_next = s->bin_cap(s->bank ^ 1u, b + 1); ba.off_next = s->bin_off(s->bank ^ 1u, b + 1);
-            ba.queue_entries = Qe;
-            crt::launch_bin_scan(ba, s->stream);
-        }
-
-    }
-    if (any_deferred) {
-        // ONE any-hit launch for the shadow rays of every deferring segment: full waves from the first step
-        crt::ShadowArgs sh{};
-        sh.nodes = s->d_nodes; sh.tris = s->d_tris; sh.shadow = s->d_nee; sh.contrib = s->d_contrib;
-        sh.count = cnt + counter_index(first_deferred, 1, 0); sh.count_stride = counter_index(1, 1, 0) - counter_index(0, 1, 0);
-        sh.stack_entries = s->stack_entries; sh.sub_capacity = s->sub_capacity;
-        sh.pool = s->shadow_pool; sh.refill_min = s->shadow_refill_min; sh.tri_min = s->tri_min ? s->tri_min : 1u;
-        sh.lanes_log2 = s->lanes_per_ray >= 8u ? 3u : 0u;
-        sh.pools_per_region = (s->sub_capacity + sh.pool - 1u) / sh.pool;
-        sh.persistent = s->persistent; sh.n_regions = s->max_depth - first_deferred; sh.cursors = cnt + kCursorShadow;
-        if (s->sort_shadow && s->info.n_nodes8 >= 64) {
-            // sorted by the cell the rays start in: three small launches (histogram, scan, scatter), then a persistent grid over the sorted order
-            crt::NeeSortArgs na{};
-            na.shadow = s->d_nee; na.count = sh.count; na.count_stride = sh.count_stride; na.sub_capacity = s->sub_capacity; na.n_queues = sh.n_regions * 8u;
-            for (int k = 0; k < 3; ++k) {
-                const float ext = s->bounds_hi[k] - s->bounds_lo[k];
-                na.origin[k] = s->bounds_lo[k];
-                na.scale[k] = ext > 0.f ? 16.0f / ext : 0.f;
-            }
-            na.hist = s->d_nee_bins; na.cursor = s->d_nee_bins + 4096; na.perm = s->d_nee_perm; na.meta = s->d_nee_bins + 2 * 4096;
-            crt::launch_nee_sort(na, (uint32_t)s->n_cu * 2u, s->stream);
-            sh.perm = s->d_nee_perm; sh.sort_meta = na.meta; sh.persistent = 1u;
-        }
-        sh.visit_totals = s->d_visit_totals ? s->d_visit_totals + 2 : nullptr;
-        sh.overflow = s->d_overflow;
-        EventSpan* sp = s->new_span(2);
-        if (sp) crt::set_launch_events(sp->a, sp->b);
-        const size_t lds_q = (size_t)(s->stack_entries + CRT_HIT_SLOTS) * 64 * sizeof(uint2);
-        crt::launch_shadow_deferred(sh, s->count_visits, sh.persistent ? s->resident_waves(lds_q, s->shadow_waves) : 8u * sh.n_regions * sh.pools_per_region, s->stream);
-    }
-    if (folds) crt::launch_fold_paths(s->d_sum, s->d_lfinal, any_deferred ? s->d_contrib : nullptr, P, n_samples, first_deferred, s->stream);
-    if (s->count_visits)
-        HIPCHK(hipMemcpyAsync(s->h_visit_totals, s->d_visit_totals, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    if (measure_tiles) {
-        HIPCHK(hipMemcpyAsync(s->h_tile_cost, s->d_tile_cost, s->n_local_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipEventRecord(s->ev_tile_cost, s->stream));
-        s->tile_state = crt_scene::TILES_PENDING;
-    }
-    s->stats_counted = s->count_visits;
-    HIPCHK(hipGetLastError());
-    s->counts_clean = true;
-    s->stats_pending = true;
-    s->stats_from_frame = true;   // ray counts come from h_counts at the next sync
-    s->samples_in_stats = n_samples;
-    return CRT_OK;
-}
-
-// Path state, ray queues and the final-radiance buffer for `cap` samples per launch (multi-segment paths).  The per-group queue
-// capacity grows with it, so the lazily allocated shadow queue / hit buffer are dropped and come back at the new size.
-static int ensure_batch_buffers(crt_scene* s, uint32_t cap) {
-    if (s->batch_cap >= cap) return CRT_OK;
-    HIPCHK(hipStreamSynchronize(s->stream));
-    // The lazily allocated hit buffer and the deferred shadow rays' buffers follow the per-group capacity: dropped now (null pointers the
-    // next frame re-allocates at the size then in force), whatever happens below.
-    for (void** p : {(void**)&s->d_nee, (void**)&s->d_contrib, (void**)&s->d_nee_perm, (void**)&s->d_qhits}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    s->defer_cap = s->defer_regions = 0;
-    // Everything else is allocated at the new size FIRST and swapped in only when all of it exists: a failed growth (~250 B per
-    // pixel and sample: 16 GB for a 4K frame at 8 samples) leaves the scene exactly as it was, able to render frame by frame.
-    const size_t P = s->n_local_pixels;
-    const uint32_t sub_capacity = (uint32_t)(((P + 4095) / 4096 + 7) / 8 * 4096) * cap;
-    const size_t Q = 8 * (size_t)sub_capacity;
-    float4 *rays0 = nullptr, *rays1 = nullptr, *L = nullptr, *T = nullptr, *lfinal = nullptr;
-    float2* seed = nullptr;
-    auto undo = [&](int code) {
-        for (void* p : {(void*)rays0, (void*)rays1, (void*)L, (void*)T, (void*)seed, (void*)lfinal}) if (p) (void)hipFree(p);
-        return code;
-    };
-    int rc;
-    if (s->debug_fail_batch_alloc) { s->debug_fail_batch_alloc = 0; return fail(CRT_ERR_NOMEM, "hipMalloc: injected failure (debug_fail_batch_alloc)"); }
-    if ((rc = dev_alloc(&rays0, 2 * Q)) || (rc = dev_alloc(&rays1, 2 * Q)) || (rc = dev_alloc(&L, P * cap)) || (rc = dev_alloc(&T, P * cap)) ||
-        (rc = dev_alloc(&seed, P * cap)) || (rc = dev_alloc(&lfinal, P * cap)))
-        return undo(rc);
-    if (hipMemset(lfinal, 0, P * cap * sizeof(float4)) != hipSuccess)      // pixels outside the frame are never written: they stay zero
-        return undo(fail(CRT_ERR_HIP, "hipMemset failed"));
-    for (void* p : {(void*)s->d_rays[0], (void*)s->d_rays[1], (void*)s->pb.L, (void*)s->pb.T, (void*)s->pb.seed, (void*)s->d_lfinal}) if (p) (void)hipFree(p);
-    s->d_rays[0] = rays0; s->d_rays[1] = rays1; s->pb.L = L; s->pb.T = T; s->pb.seed = seed; s->d_lfinal = lfinal;
-    s->sub_capacity = sub_capacity;
-    s->batch_cap = cap;
-    s->lfinal_cap = cap;
-    s->rays_doubled = false;
-    if (s->d_bins) HIPCHK(hipMemset(s->d_bins, 0, crt_scene::bins_words() * sizeof(uint32_t)));     // new queues: the bins start empty-handed again
-    return CRT_OK;
-}
-
-// how many samples one launch may render: more than one only when nothing travels between launches (one path segment, shadow
-// rays walked in place) — bounce queues and the shadow queue hold one entry per pixel
-static uint32_t batch_limit(const crt_scene* s) {
-    if (s->lens() && !s->inst) {
-        // a frame through a lens: every segment is queue-fed, so the samples of a chain keep their own path state and queue
-        // entries whatever the depth and wherever the shadow rays are walked — the rule for multi-segment paths below.  Counting frames and
-        // the BVH2 frame mode run one by one, as without a lens
-        if (s->count_visits || s->accel != 0u) return 1u;
-        const uint64_t fit = s->n_local_pixels ? 0x7fffffffull / s->n_local_pixels : 8ull;
-        return (uint32_t)std::min<uint64_t>(8ull, std::max<uint64_t>(1ull, fit));
-    }
-    // the batched builds of the first segment walk its shadow rays in place; counting frames run one by one
-    if (first_deferred_segment(s) == 0u || (s->count_visits && !s->count_batched)) return 1u;
-    if (s->accel != 0u) return 1u;                                     // the BVH2 frame mode (a comparison aid) has no batched build
-    if (s->count_visits) {
-        // counting in the timed form: exactly the launch of four samples in the lanes of a wave has a counting build (launch_segment)
-        const bool lanes_form = s->wave_samples >= 2u && s->info.n_nodes8 >= 64 && s->tri_min != 0u && s->lanes_per_ray >= 8u;
-        const uint64_t fit4 = s->n_local_pixels ? 0x7fffffffull / s->n_local_pixels : 4ull;
-        return lanes_form && fit4 >= 4ull ? 4u : 1u;
-    }
-    if (s->max_depth == 1u) return 8u;
-    // several segments: every sample keeps its own path state and queue entries (ensure_batch_buffers) and the samples' radiance is
-    // added in frame order by k_fold_paths
-    // path ids are sample * n_local_pixels + pixel and must stay below 2^31 (bit 31 tags queue entries)
-    const uint64_t fit = s->n_local_pixels ? 0x7fffffffull / s->n_local_pixels : 8ull;
-    return (uint32_t)std::min<uint64_t>(8ull, std::max<uint64_t>(1ull, fit));         // 1 M triangles, 4 segments: 1.78 / 1.61 / 1.50 / 1.45 ms per frame at 1 / 2 / 4 / 8 frames per launch
-}
-
-// one batch on every device of the scene: each enqueues on its own stream and returns, so the devices render concurrently
-static int render_batch_all(crt_scene* s, uint32_t n_samples, const float* rxs, const float* rys) {
-    int rc = CRT_OK;
-    if (!s->peers.empty()) {
-        // phase 1: every device's buffers for this batch exist before any device renders (a failed growth leaves every sum as it was)
-        if (!s->have_camera) return fail(CRT_ERR_INVALID, "crt_render_frame: crt_set_camera was never called");
-        if ((rc = prepare_batch(s, n_samples))) { (void)hipSetDevice(s->device); return rc; }
-        for (crt_scene* p : s->peers) if ((rc = prepare_batch(p, n_samples))) { (void)hipSetDevice(s->device); return rc; }
-    }
-    // phase 2: enqueue everywhere
-    rc = render_batch_async(s, n_samples, rxs, rys);
-    for (size_t k = 0; !rc && k < s->peers.size(); ++k) rc = render_batch_async(s->peers[k], n_samples, rxs, rys);
-    if (!s->peers.empty()) (void)hipSetDevice(s->device);      // the caller's thread keeps the device the scene lives on
-    return rc;
-}
-
-int crt_render_frame_async(crt_scene* s, float rx, float ry) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_render_frame: null scene");
-    return render_batch_all(s, 1u, &rx, &ry);
-}
-
-int crt_render_frames_async(crt_scene* s, uint32_t n, const float* rx, const float* ry) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_render_frames: null scene");
-    if (n && (!rx || !ry)) return fail(CRT_ERR_INVALID, "crt_render_frames: null argument");
-    const uint32_t lim = batch_limit(s);
-    const bool fours = s->wave_samples >= 2u && s->info.n_nodes8 >= 64 && s->accel == 0u && !s->lens();     // launches that can put 4 samples in the lanes of a wave
-    for (uint32_t i = 0; i < n;) {
-        uint32_t k = std::min(lim, n - i);
-        if (fours && k > 4u && (k & 3u)) k &= ~3u;                       // 7 frames = 4 + 3, not 7 one after the other
-        if (s->count_visits && k != 4u) k = 1u;                          // counting launches: four samples in the lanes form, or one
-        const int rc = render_batch_all(s, k, rx + i, ry + i);
-        if (rc) return rc;
-        i += k;
-    }
-    return CRT_OK;
-}
-
-int crt_render_frames(crt_scene* s, uint32_t n, const float* rx, const float* ry) {
-    const int rc = crt_render_frames_async(s, n, rx, ry);
-    if (rc) return rc;
-    return crt_sync(s);
-}
-
-int crt_sync(crt_scene* s) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_sync: null scene");
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipGetLastError());
-    for (crt_scene* p : s->peers) { const int rc = crt_sync(p); if (rc) return rc; }
-    if (!s->peers.empty()) HIPCHK(hipSetDevice(s->device));
-    return CRT_OK;
-}
-
-int crt_render_frame(crt_scene* s, float rx, float ry) {
-    int rc = crt_render_frame_async(s, rx, ry);
-    if (rc) return rc;
-    return crt_sync(s);
-}
-
-int crt_get_frame_stats(crt_scene* s, crt_frame_stats* out) {
-    if (!s || !out) return fail(CRT_ERR_INVALID, "crt_get_frame_stats: null argument");
-    HIPCHK(hipSetDevice(s->device));
-    if (s->stats_pending) {
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->stats_from_frame) {
-            // the queue counters stay valid until the next frame's memset: fetch them only when asked
-            if (!s->h_counts && hipHostMalloc(reinterpret_cast<void**>(&s->h_counts), kCounters * sizeof(uint32_t)) != hipSuccess)
-                return fail(CRT_ERR_NOMEM, "hipHostMalloc failed");
-            HIPCHK(hipMemcpy(s->h_counts, s->counts(), kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            uint64_t closest = 0, any = 0;
-            closest = (uint64_t)s->n_local_in_frame * s->samples_in_stats;   // segment 0: one primary ray per in-frame pixel and sample
-            for (uint32_t b = 0; b < s->max_depth; ++b)
-                for (uint32_t g = 0; g < 8; ++g) {
-                    if (b) closest += s->h_counts[counter_index(b, 0, g)];
-                    any += s->h_counts[counter_index(b, 1, g)];
-                }
-            s->stats.closest_rays = closest; s->stats.any_rays = any;
-        }
-        int rc = collect_stats(s);
-        if (rc) return rc;
-        HIPCHK(hipMemcpy(&s->stats.stack_overflows, s->d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    *out = s->stats;
-    // several devices: ray and visit counts are sums over the devices, times the slowest device's (they run side by side)
-    for (crt_scene* p : s->peers) {
-        crt_frame_stats ps{};
-        const int rc = crt_get_frame_stats(p, &ps);
-        if (rc) return rc;
-        out->closest_rays += ps.closest_rays; out->any_rays += ps.any_rays;
-        out->nodes_closest += ps.nodes_closest; out->tris_closest += ps.tris_closest; out->nodes_any += ps.nodes_any; out->tris_any += ps.tris_any;
-        out->wave_steps_closest_nodes += ps.wave_steps_closest_nodes; out->wave_steps_closest_tris += ps.wave_steps_closest_tris;
-        out->wave_steps_any_nodes += ps.wave_steps_any_nodes; out->wave_steps_any_tris += ps.wave_steps_any_tris;
-        out->closest_hits += ps.closest_hits; out->stack_overflows += ps.stack_overflows;
-        out->nodes_closest_uniform += ps.nodes_closest_uniform; out->nodes_any_uniform += ps.nodes_any_uniform;
-        out->ms_total = std::max(out->ms_total, ps.ms_total); out->ms_trace_closest = std::max(out->ms_trace_closest, ps.ms_trace_closest);
-        out->ms_trace_any = std::max(out->ms_trace_any, ps.ms_trace_any); out->ms_shade = std::max(out->ms_shade, ps.ms_shade);
-    }
-    if (!s->peers.empty()) HIPCHK(hipSetDevice(s->device));
-    return CRT_OK;
-}
-
 int crt_get_bvh_info(crt_scene* s, crt_bvh_info* out) {
     if (!s || !out) return fail(CRT_ERR_INVALID, "crt_get_bvh_info: null argument");
     if (s->inst) {                           // the handle's live totals, as crt_instances_get_info reports them
@@ -1947,21 +1189,6 @@ int crt_copy_packed_device(crt_scene* s, void* d_dst, size_t n_floats, int sync)
     if (n_floats != 3 * (size_t)s->n_local_pixels) return fail(CRT_ERR_INVALID, "crt_copy_packed_device: size mismatch");
     HIPCHK(hipMemcpyAsync(d_dst, s->d_sum, n_floats * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     if (sync) HIPCHK(hipStreamSynchronize(s->stream));
-    return CRT_OK;
-}
-
-int crt_get_launch_times(crt_scene* s, float* ms, size_t cap, size_t* n_out) {
-    if (!s || !n_out) return fail(CRT_ERR_INVALID, "crt_get_launch_times: null argument");
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    size_t n = 0;
-    for (int i = 0; i < s->n_spans; ++i) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, s->spans[i].a, s->spans[i].b) != hipSuccess) continue;
-        if (ms && n < cap) ms[n] = t;
-        ++n;
-    }
-    *n_out = n;
     return CRT_OK;
 }
 
@@ -2231,14 +1458,6 @@ extern "C++" int crt::gather_peers(crt_scene* s) {       // for crt_outputs.cpp 
     return CRT_OK;
 }
 
-// Debug/test hook: copy out one of the frame's ray queues as left by the last crt_render_frame.
-// which: 0/1 = path-ray queue written for an even/odd segment, 2 = shadow-ray queue of the last segment.
-int crt_debug_launch_form(crt_scene* s, int32_t* form) {
-    if (!s || !form) return fail(CRT_ERR_INVALID, "crt_debug_launch_form: null argument");
-    *form = s->last_launch_form;
-    return CRT_OK;
-}
-
 // Measurement aid: enabled lanes per node step of the counting kernels (option count_visits), closest-hit walks in hist[0..64], any-hit
 // walks in hist[65..129], accumulated since the previous call (which zeroes it).  Process-wide (one device symbol); null stops it.
 int crt_debug_step_hist(crt_scene* s, unsigned long long* hist) {
@@ -2254,96 +1473,6 @@ int crt_debug_step_hist(crt_scene* s, unsigned long long* hist) {
     HIPCHK(hipMemcpy(hist, d_hist, 130 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     HIPCHK(hipMemset(d_hist, 0, 130 * sizeof(unsigned long long)));
     crt::set_step_hist(d_hist, s->step_hist_mode);
-    return CRT_OK;
-}
-
-int crt_debug_launch_info(crt_scene* s, int32_t info[4]) {
-    if (!s || !info) return fail(CRT_ERR_INVALID, "crt_debug_launch_info: null argument");
-    info[0] = s->last_launch_form; info[1] = s->last_launch_wide | (s->last_launch_one_pass << 1) | (s->last_launch_last << 2) | (s->last_launch_lean << 3) | (s->last_launch_lens << 4) | (s->last_launch_env << 5); info[2] = s->last_launch_samples; info[3] = (int32_t)s->peers.size() + 1;
-    return CRT_OK;
-}
-
-int crt_debug_time_graph(crt_scene* s, uint32_t n_frames, const float* rxy, uint32_t reps, float* ms_stream, float* ms_graph) {
-    if (!s || !rxy || !ms_stream || !ms_graph || n_frames == 0 || (n_frames & 1u) || reps == 0)
-        return fail(CRT_ERR_INVALID, "crt_debug_time_graph: bad argument (n_frames must be even: the counter banks alternate)");
-    if (s->inst) return fail(CRT_ERR_INVALID, "crt_debug_time_graph: not offered for an instanced scene");
-    if (!s->peers.empty() || s->primary)
-        return fail(CRT_ERR_INVALID, "crt_debug_time_graph: one stream only (option streams 1, no crt_set_devices): the capture records this scene's stream, not its peers'");
-    HIPCHK(hipSetDevice(s->device));
-    const uint32_t timing0 = s->timing;
-    s->timing = 0;                                         // event-carrying launches are not capturable
-    int rc = crt_render_frame(s, rxy[0], rxy[1]);          // allocates, clears the counter banks once
-    if (!rc) rc = crt_render_frame(s, rxy[0], rxy[1]);
-    if (rc) { s->timing = timing0; return rc; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    auto done = [&](int code) {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        s->timing = timing0;
-        return code;
-    };
-#define G_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return done(fail(CRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); } while (0)
-    G_CHK(hipEventCreate(&e0));
-    G_CHK(hipEventCreate(&e1));
-    G_CHK(hipEventRecord(e0, s->stream));
-    for (uint32_t r = 0; r < reps; ++r)
-        for (uint32_t f = 0; f < n_frames; ++f)
-            if ((rc = crt_render_frame_async(s, rxy[2 * f], rxy[2 * f + 1]))) return done(rc);
-    G_CHK(hipEventRecord(e1, s->stream));
-    G_CHK(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    G_CHK(hipEventElapsedTime(&ms, e0, e1));
-    *ms_stream = ms / (float)(reps * n_frames);
-    G_CHK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    s->capturing = true;
-    for (uint32_t f = 0; f < n_frames; ++f)
-        if ((rc = crt_render_frame_async(s, rxy[2 * f], rxy[2 * f + 1]))) { s->capturing = false; (void)hipStreamEndCapture(s->stream, &graph); return done(rc); }
-    s->capturing = false;
-    G_CHK(hipStreamEndCapture(s->stream, &graph));
-    G_CHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    G_CHK(hipGraphLaunch(exec, s->stream));                // warm
-    G_CHK(hipStreamSynchronize(s->stream));
-    G_CHK(hipEventRecord(e0, s->stream));
-    for (uint32_t r = 0; r < reps; ++r) G_CHK(hipGraphLaunch(exec, s->stream));
-    G_CHK(hipEventRecord(e1, s->stream));
-    G_CHK(hipStreamSynchronize(s->stream));
-    G_CHK(hipEventElapsedTime(&ms, e0, e1));
-    *ms_graph = ms / (float)(reps * n_frames);
-#undef G_CHK
-    return done(CRT_OK);
-}
-
-int crt_debug_read_queue(crt_scene* s, int which, uint32_t segment, crt_ray* dst, size_t cap, size_t* n_out) {
-    if (!s || !n_out) return fail(CRT_ERR_INVALID, "crt_debug_read_queue: null argument");
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (!s->frame_buffers_ready || segment > 16) return fail(CRT_ERR_INVALID, "crt_debug_read_queue: no frame rendered");
-    std::vector<uint32_t> counts(kCounters);
-    HIPCHK(hipMemcpy(counts.data(), s->counts(), kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (which != 2 && s->d_bins && s->ray_bins) return fail(CRT_ERR_INVALID, "crt_debug_read_queue: the path-ray queue is binned (option ray_bins 0 gives the sub-queue form this reads)");
-    const uint32_t first_def = first_deferred_segment(s);
-    const float4* src = which == 2 ? ((s->d_nee && segment >= first_def && segment - first_def < s->defer_regions) ? s->d_nee + 2 * (size_t)(segment - first_def) * 8u * s->sub_capacity : nullptr)
-                                   : (segment == 0 && s->lens() && !s->inst) ? s->d_rays_lens : s->d_rays[segment & 1];      // a lens frame's primary rays keep a queue of their own
-    if (!src) return fail(CRT_ERR_INVALID, "crt_debug_read_queue: that queue does not exist (shadow rays: only of segments that defer them, inplace_shadow 0 / 2; path queues: max_depth > 1)");
-    const size_t entry = sizeof(crt_ray);        // a deferred shadow ray is (o, tmax) (d, contribution slot)
-    size_t total = 0;
-    for (uint32_t g = 0; g < 8; ++g) total += counts[counter_index(segment, which == 2 ? 1 : 0, g)];
-    *n_out = total;
-    if (dst) {
-        if (!src) return fail(CRT_ERR_INVALID, "crt_debug_read_queue: that queue does not exist at max_depth 1");
-        size_t done = 0;
-        for (uint32_t g = 0; g < 8 && done < cap; ++g) {
-            size_t n = counts[counter_index(segment, which == 2 ? 1 : 0, g)];
-            n = std::min(n, cap - done);
-            if (!n) continue;
-            const char* from = reinterpret_cast<const char*>(src) + (size_t)g * s->sub_capacity * entry;
-            HIPCHK(hipMemcpy2D(dst + done, sizeof(crt_ray), from, entry, sizeof(crt_ray), n, hipMemcpyDeviceToHost));
-            done += n;
-        }
-    }
     return CRT_OK;
 }
 

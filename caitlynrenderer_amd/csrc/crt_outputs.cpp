@@ -1,6 +1,6 @@
 // Everything that leaves the library as an image (include/crt.h): the running sum, the first-hit feature buffers, the
 // denoised image (§22), the accumulated image (§23), and the RGBA8 of the three float images.  The three are described once (Image) and
-// read, exposed and resolved through one path each ("Where an image leaves"); crt_device.cpp renders the frames these read.
+// read, exposed and resolved through one path each ("Where an image leaves"); crt_frames.cpp renders the frames these read.
 #include <cmath>
 #include <cstring>
 #include <exception>
@@ -256,9 +256,7 @@ int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync
     const crt::AovOut out = aov_channels(av);
     if (s->inst) {
         if ((rc = ensure_frame(s))) return rc;
-        const size_t Q = 8 * (size_t)s->sub_capacity;
-        if (!s->d_qhits && (rc = dev_alloc(&s->d_qhits, Q))) return rc;
-        if (!s->d_qinst && (rc = dev_alloc(&s->d_qinst, Q))) return rc;
+        if ((rc = crt::ensure_queue_hits(s, true, true))) return rc;
         if (!av->d_count && (rc = dev_alloc(&av->d_count, 8 * kCounterStride))) return rc;
     } else if (!av->d_tile_xy || av->rank != s->shard_rank || av->world != s->shard_world || av->tile != s->tile) {
         // the caller's shard, dealt as crt_set_shard deals it
@@ -281,20 +279,9 @@ int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync
             const bool masked = s->instance_masks != 0u;
             if (masked && (rc = crt::instances_child_masks_for(s->inst, s->stream, &s->cmask_seen))) return rc;
             HIPCHK(hipMemsetAsync(av->d_count, 0, 8 * kCounterStride * sizeof(uint32_t), s->stream));
-            crt::RaygenArgs ra{};
-            ra.f = frame_args(s, rx, ry);
-            ra.f.tile_order = nullptr;
-            ra.rays = s->d_rays[0]; ra.count = av->d_count; ra.sub_capacity = s->sub_capacity; ra.pb = s->pb;
-            ra.zero_counts = nullptr; ra.n_zero = 0;                      // the frames' counter banks stay as the last frame left them
+            const crt::RaygenArgs ra = crt::raygen_args(s, frame_args(s, rx, ry), s->d_rays[0], av->d_count, false);      // the frames' counter banks stay as the last frame left them
             crt::launch_raygen(ra, s->stream);
-            crt::InstMaskQueueArgs qa{};
-            qa.nodes = v.nodes; qa.tris = v.tris; qa.inst = v.inst;
-            if (masked) { qa.child_masks = v.child_masks; qa.n_tlas8 = v.tlas_nodes8; qa.ray_mask = s->mask_primary; }
-            qa.rays = s->d_rays[0]; qa.count = av->d_count; qa.hits = s->d_qhits; qa.hit_inst = s->d_qinst;
-            qa.sub_capacity = s->sub_capacity; qa.n_instances = v.n_instances; qa.stack_entries = v.stack_entries;
-            qa.refill_min = 8; qa.tri_min = 2;
-            qa.visit_totals = nullptr; qa.overflow = s->d_overflow;
-            crt::launch_closest_instances_queue(qa, false, masked, s->stream);
+            crt::launch_closest_instances_queue(crt::inst_queue_args(s, v, s->d_rays[0], av->d_count, s->mask_primary, nullptr), false, masked, s->stream);
             crt::InstAovArgs a{};
             a.triangles = s->d_triangles; a.normals = s->d_normals; a.materials = s->d_materials;
             a.texcoords = s->d_texcoords; a.textures = s->d_textures;

@@ -1,5 +1,6 @@
 // struct crt_scene and the state structs it points to, shared by the translation units behind the device half of include/crt.h:
-// crt_device.cpp (creation, frame dispatch, several GPUs, refit / rebuild) and crt_outputs.cpp (everything that leaves as an image).
+// crt_device.cpp (creation, options, several GPUs, refit / rebuild), crt_frames.cpp (frame dispatch) and crt_outputs.cpp (everything that
+// leaves as an image).
 // Private to csrc/: not installed, include/crt.h knows crt_scene by name only, and nothing declared here is exported by the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +38,12 @@ constexpr uint32_t kCursorShadow = kQueueCounters + 17 * 8 * kCounterStride;
 constexpr uint32_t kCounters = kCursorShadow + 17 * 8 * kCounterStride;
 
 struct EventSpan { hipEvent_t a = nullptr, b = nullptr; int kind = 0; };   // kind: 0 raygen 1 closest 2 any 3 shade/other
+
+// What segment 0 of the last chain of launches ran (crt_debug_launch_form, crt_debug_launch_info).  form: how its samples sat on the hardware
+// (option "wave_samples").  build: bit 0 the 6-wave build, 1 a build without the sample loop, 2 one compiled as the path's last segment
+// (option "last_build"), 3 its LEAN form (option "lean_build"), 4 segment 0 was fed by the lens ray generator, 5 the frame ran k_env_miss
+// behind its closest-hit launches.  samples: samples per pixel of the chain.
+struct LaunchInfo { int form = 0, build = 0, samples = 1; };
 
 // What crt_render_aov keeps, allocated by a scene's first call: the five channel buffers, each by the first call that asks
 // for it, and what the dispatch needs beside the frame's own buffers.  The scene's stream has drained when this is destroyed.
@@ -241,7 +248,6 @@ struct crt_scene {
     uint32_t env_size = 0, env_flags = 0;
     float env_rotation[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, env_scale[3] = {1.f, 1.f, 1.f};
     bool env() const { return d_env != nullptr; }
-    int last_launch_env = 0;                 // crt_debug_launch_info: bit 5 of the build word: the frame ran k_env_miss behind its closest-hit launches
     // DEFERRED NEE shadow rays (option "inplace_shadow" 0 / 2, rt_kernels.hip k_segment<!INPLACE>): the frame's NEE queue — one region per
     // deferring segment, 8 sub-queues each, 2 x float4 per ray: (o, tmax) (d, contribution slot) — and the contribution slots, one per
     // (deferring segment, path): (C | T e, visibility word)
@@ -276,8 +282,7 @@ struct crt_scene {
     uint32_t wave_samples = 2;
     uint32_t wide_first = 2;            // first-segment kernels built for 6 waves per SIMD: 0 never, 1 always, 2 by the same measure
     float tile_cost_spread = 0.f;       // 99th percentile of the measured tile costs over their mean; 0 = nothing measured yet
-    int last_launch_form = 0;           // crt_debug_launch_form
-    int last_launch_wide = 0, last_launch_samples = 1, last_launch_one_pass = 0;      // crt_debug_launch_info
+    LaunchInfo last_launch;             // set once per chain by the renderer that enqueued it
     bool use_wave_samples() const { return wave_samples == 2u ? bound_by_longest_waves() : wave_samples == 1u; }
     bool bound_by_longest_waves() const {
         // One wave renders the n samples of its 64 pixels one after the other: the launch cannot end before the most expensive
@@ -360,12 +365,9 @@ struct crt_scene {
     uint32_t* bin_ovf(uint32_t seg) const { return d_bins + (size_t)17 * 5 * CRT_RAY_BINS + (size_t)17 * (CRT_RAY_BINS + 1u) + (size_t)seg * 32u; }
     static size_t bins_words() { return (size_t)17 * 5 * CRT_RAY_BINS + (size_t)17 * (CRT_RAY_BINS + 1u) + 17u * 32u; }
     uint32_t last_build = 1;                 // option "last_build": a one-pass launch that is the path's last segment runs the build compiled as one (k_segment<LAST>)
-    int last_launch_last = 0;                // crt_debug_launch_info: bit 2 of the build word
     uint32_t lean_build = 1;                 // option "lean_build": such a launch runs that build's LEAN form (k_segment<LAST,LEAN>) where launch_segment finds what the form has compiled in
     bool tree_validated = false;             // the CWBVH passed crt_scene_create's host validator (validate_cwbvh), whose depth sized the stack: the LEAN form's bare pushes rest on it.
                                              // A tree built or rebuilt on the device never went through it and keeps the checked pushes
-    int last_launch_lean = 0;                // crt_debug_launch_info: bit 3 of the build word
-    int last_launch_lens = 0;                // crt_debug_launch_info: bit 4 of the build word: segment 0 was fed by the lens ray generator
     uint32_t debug_fail_batch_alloc = 0;     // test hook (option of the same name): the next growth of the batch buffers fails before it allocates
     uint32_t batch_cap = 1;                  // samples the path state, the ray queues and d_lfinal are sized for (1 until crt_render_frames needs more)
     uint32_t samples_in_stats = 1;           // samples per pixel of the launch the pending stats describe (crt_render_frames batches)
@@ -444,6 +446,7 @@ struct crt_scene {
         const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(4ull * per_simd, by_lds));
         return (uint32_t)((uint64_t)n_cu * per_cu / 8 * 8);
     }
+    size_t pool_lds() const { return (size_t)(stack_entries + CRT_HIT_SLOTS) * 64 * sizeof(uint2); }     // LDS of a wave of the pool kernels (k_closest_queue, k_shadow_deferred)
     uint32_t flat_grid(uint64_t n) const {
         uint64_t blocks = (n + 255) / 256;
         return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)n_cu * 8));
@@ -463,12 +466,21 @@ struct crt_scene {
     }
 };
 
-// What crt_outputs.cpp needs of crt_device.cpp
+// What crosses between the three translation units
 namespace crt {
+// crt_device.cpp
 void deal_tiles(uint32_t width, uint32_t height, uint32_t T, uint32_t rank, uint32_t world, std::vector<uint2>& tiles, uint64_t* pixels_in_frame);
 crt::FrameArgs frame_args(const crt_scene* s, float rx, float ry);
-int ensure_frame(crt_scene* s);          // the shard's frame buffers, allocated by the first call that needs them
+int ensure_planes(crt_scene* s);         // the nodes' child planes as floats, built in stream order before the first frame that walks the CWBVH
+int ensure_light_table(crt_scene* s);    // the world light table of a scene with mesh lights, rebuilt if its handle has changed
 // every peer's packed sum buffer -> d_gather[k] on the primary device, complete in the primary's stream order when this returns
 int gather_peers(crt_scene* s);
+// crt_frames.cpp
+int alloc_frame_buffers(crt_scene* s);   // the frame buffers of the shard (rank, world, tile) as they stand, anew
+int ensure_frame(crt_scene* s);          // the shard's frame buffers, allocated by the first call that needs them
+int ensure_queue_hits(crt_scene* s, bool hits, bool instances);     // d_qhits / d_qinst beside the path-ray queue
+crt::RaygenArgs raygen_args(const crt_scene* s, const crt::FrameArgs& f, float4* rays, uint32_t* count, bool zero_bank);
+crt::InstMaskQueueArgs inst_queue_args(const crt_scene* s, const crt::InstancesView& v, const float4* rays, const uint32_t* count, uint32_t ray_mask,
+                                       unsigned long long* visit_totals);
 }  // namespace crt
 #pragma GCC visibility pop

@@ -1,6 +1,7 @@
 // What a crt_scene whose geometry is a crt_instances handle (crt_scene_create_instanced) needs of that handle: its live
 // device arrays, read when a frame is enqueued, and the binding that makes the handle's mutators wait for the scene's stream and refuse
-// what would leave the scene's per-mesh shading tables stale.  crt_instances.cpp defines these, crt_device.cpp calls them.
+// what would leave the scene's per-mesh shading tables stale.  crt_instances.cpp defines these; crt_device.cpp (creation), crt_frames.cpp (frames)
+// and crt_outputs.cpp (AOVs) call them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

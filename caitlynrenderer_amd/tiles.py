@@ -5,7 +5,7 @@ frame is cut into tile x tile squares, dealt round-robin in Morton order to the 
 view misses 44 % of a 16:9 frame, so contiguous bands would be unbalanced), every rank accumulates
 its own tiles locally, and the only communication is one all-gather of the packed RGB32F tile
 buffers at read-back (RCCL over xGMI when the process group is "nccl"; "gloo" in the CPU tests).
-`tile_order` must stay identical to build_shard() in csrc/crt_device.cpp.
+`tile_order` must stay identical to build_shard() in csrc/crt_frames.cpp.
 """
 import numpy as np
 

@@ -78,7 +78,7 @@ for case in range(n_cases):
         scene.render_frames(rvs)
         tot = np.zeros(2, np.int64)
         last = np.zeros(2, np.int64)
-        per_launch = 8 if (accel == 0 and opts.get("inplace_shadow", 1) != 0) else 1       # crt_device.cpp batch_limit
+        per_launch = 8 if (accel == 0 and opts.get("inplace_shadow", 1) != 0) else 1       # crt_frames.cpp plan_frame (FramePlan::limit)
         # the library's own split of a call into launches (crt_render_frames_async): up to per_launch frames each, and where four samples
         # can sit in the lanes of a wave (wave_samples >= 2, a tree of 64+ nodes, CWBVH) a launch of 5..7 frames goes as 4 + the rest
         fours = opts.get("wave_samples", 2) >= 2 and scene.bvh_info()["n_nodes8"] >= 64 and accel == 0
