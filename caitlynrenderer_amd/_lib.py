@@ -20,6 +20,9 @@ CRT_DENOISE_DEMODULATE = 1               # crt_denoise_params.flags
 DENOISE_DEMODULATE = CRT_DENOISE_DEMODULATE
 CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_CLAMP = 1, 2                       # crt_temporal_params.flags
 CRT_TEMPORAL_SOURCE_SUM, CRT_TEMPORAL_SOURCE_DENOISED = 0, 1             # crt_temporal_params.source
+CRT_DISPLAY_SOURCE_SUM, CRT_DISPLAY_SOURCE_DENOISED, CRT_DISPLAY_SOURCE_TEMPORAL = 0, 1, 2          # crt_display_params.source
+CRT_DISPLAY_CURVE_REFERENCE, CRT_DISPLAY_CURVE_REINHARD, CRT_DISPLAY_CURVE_ACES, CRT_DISPLAY_CURVE_CLAMP = 0, 1, 2, 3    # crt_display_params.curve
+CRT_DISPLAY_AUTO_EXPOSURE = 1            # crt_display_params.flags
 CRT_ENV_HIDE_FROM_CAMERA = 1             # crt_environment.flags
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
@@ -140,6 +143,19 @@ class crt_temporal_params(C.Structure):
                 ("normal_min", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
+class crt_display_params(C.Structure):
+    # struct crt_display_params (48 bytes): crt_display's source, curve and exposure settings
+    _fields_ = [("source", C.c_uint32), ("curve", C.c_uint32), ("flags", C.c_uint32), ("exposure", C.c_float), ("white", C.c_float),
+                ("key", C.c_float), ("adapt", C.c_float), ("exposure_min", C.c_float), ("exposure_max", C.c_float),
+                ("low_permille", C.c_uint32), ("high_permille", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class crt_display_state(C.Structure):
+    # struct crt_display_state (32 bytes): what the last crt_display call left on the device
+    _fields_ = [("exposure", C.c_float), ("metered", C.c_float), ("counted", C.c_uint32), ("q", C.c_uint32), ("calls", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
 # every symbol include/crt.h declares: name -> (restype, argtypes)
 _P, _SZ, _I, _U32, _F = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_float
 SYMBOLS = {
@@ -175,6 +191,12 @@ SYMBOLS = {
     "crt_temporal_device": (_I, [_P, C.POINTER(_P)]),
     "crt_resolve_temporal": (_I, [_P, _P, _SZ]),
     "crt_resolve_temporal_device": (_I, [_P, C.POINTER(_P), _I]),
+    "crt_display": (_I, [_P, _F, C.POINTER(crt_display_params), _I]),
+    "crt_read_display": (_I, [_P, _P, _SZ]),
+    "crt_display_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_display_get_state": (_I, [_P, C.POINTER(crt_display_state)]),
+    "crt_read_display_histogram": (_I, [_P, _P]),
+    "crt_display_reset": (_I, [_P]),
     "crt_get_launch_times": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "crt_update_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),

@@ -9,6 +9,7 @@
 
 #include "crt_scene.hpp"
 #include "denoise.hpp"
+#include "display.hpp"
 #include "instances.hpp"
 
 using crt::dev_alloc;
@@ -166,6 +167,15 @@ int expose_image(crt_scene* s, ImageOf image_of, const char* who, const float** 
     return sync_and_expose<float>(s, *im.rgb, d_rgb);
 }
 
+// the table on the device, from the first resolve or display of any image on
+int ensure_gamma(crt_scene* s) {
+    if (s->d_gamma) return CRT_OK;
+    const int rc = dev_alloc(&s->d_gamma, 256);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(s->d_gamma, gamma_thresholds(), 256 * sizeof(float), hipMemcpyHostToDevice));
+    return CRT_OK;
+}
+
 // tone-mapped RGBA8 of the image in its own buffer (this device), through the pinned gamma: the sum straight from the packed tile buffers,
 // this scene's and its peers' as gathered
 int resolve_image(crt_scene* s, const Image& im, float inv_count) {
@@ -173,10 +183,7 @@ int resolve_image(crt_scene* s, const Image& im, float inv_count) {
     int rc;
     if (im.packed && (rc = ensure_frame(s))) return rc;
     if (!*im.rgba && (rc = dev_alloc(im.rgba, 4 * npx))) return rc;
-    if (!s->d_gamma) {                                       // the table on the device, from the first resolve of any image on
-        if ((rc = dev_alloc(&s->d_gamma, 256))) return rc;
-        HIPCHK(hipMemcpy(s->d_gamma, gamma_thresholds(), 256 * sizeof(float), hipMemcpyHostToDevice));
-    }
+    if ((rc = ensure_gamma(s))) return rc;
     uint8_t* const d_rgba = *im.rgba;
     if (!im.packed) {
         crt::launch_resolve(*im.rgb, (uint32_t)npx, inv_count, s->d_gamma, d_rgba, s->flat_grid((uint32_t)npx), s->stream);
@@ -529,5 +536,144 @@ int crt_read_temporal_history(crt_scene* s, float* n, size_t n_floats) {
     try { hist.resize(npx); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_read_temporal_history: out of host memory"); }
     if ((rc = copy_and_sync(s, hist.data(), s->temporal->d_hist[s->temporal->cur], npx * sizeof(float4)))) return rc;
     for (size_t i = 0; i < npx; ++i) n[i] = hist[i].w;
+    return CRT_OK;
+}
+
+// ---------------------------------------------------------------- crt_display --
+// The display transform (kernels in display.hip): enqueued on the scene's stream behind whatever frames, crt_render_aov,
+// crt_denoise and crt_temporal calls are queued there.  It reads the image it names and writes only DisplayState's buffers.  The exposure
+// is metered, adapted and kept on the device: nothing here waits for it.
+
+namespace {
+
+bool finite_in(float v, float lo, float hi) { return std::isfinite(v) && v >= lo && v <= hi; }
+
+int no_display(const char* who) { return fail(CRT_ERR_INVALID, std::string(who) + ": no crt_display call has succeeded on this scene"); }
+
+}  // namespace
+
+int crt_display(crt_scene* s, float inv_count, const crt_display_params* params, int sync) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_display: null scene");
+    crt_display_params p{};
+    if (params) p = *params;
+    else {
+        p.source = CRT_DISPLAY_SOURCE_SUM; p.curve = CRT_DISPLAY_CURVE_REFERENCE; p.flags = 0u;
+        p.exposure = 1.0f; p.white = 4.0f; p.key = 0.18f; p.adapt = 1.0f; p.exposure_min = 1e-6f; p.exposure_max = 1e6f;
+        p.low_permille = 0u; p.high_permille = 1000u;
+    }
+    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return fail(CRT_ERR_INVALID, "crt_display: inv_count must be finite and > 0");
+    if (p.source > (uint32_t)CRT_DISPLAY_SOURCE_TEMPORAL) return fail(CRT_ERR_INVALID, "crt_display: source is CRT_DISPLAY_SOURCE_SUM, _DENOISED or _TEMPORAL");
+    if (p.curve > (uint32_t)CRT_DISPLAY_CURVE_CLAMP) return fail(CRT_ERR_INVALID, "crt_display: curve is CRT_DISPLAY_CURVE_REFERENCE, _REINHARD, _ACES or _CLAMP");
+    if (p.flags & ~(uint32_t)CRT_DISPLAY_AUTO_EXPOSURE) return fail(CRT_ERR_INVALID, "crt_display: unknown flag bits");
+    if (p.reserved) return fail(CRT_ERR_INVALID, "crt_display: reserved must be 0");
+    if (!finite_in(p.exposure, 1e-9f, 1e9f)) return fail(CRT_ERR_INVALID, "crt_display: exposure must be finite and in [1e-9, 1e9]");
+    if (!finite_in(p.white, 1e-3f, 1e6f)) return fail(CRT_ERR_INVALID, "crt_display: white must be finite and in [1e-3, 1e6]");
+    const bool metered = (p.flags & CRT_DISPLAY_AUTO_EXPOSURE) != 0u;
+    if (metered) {
+        if (!finite_in(p.key, 1e-6f, 1e6f)) return fail(CRT_ERR_INVALID, "crt_display: key must be finite and in [1e-6, 1e6]");
+        if (!(std::isfinite(p.adapt) && p.adapt > 0.f && p.adapt <= 1.0f)) return fail(CRT_ERR_INVALID, "crt_display: adapt must be finite and in (0, 1]");
+        if (!finite_in(p.exposure_min, 1e-9f, 1e9f)) return fail(CRT_ERR_INVALID, "crt_display: exposure_min must be finite and in [1e-9, 1e9]");
+        if (!finite_in(p.exposure_max, 1e-9f, 1e9f)) return fail(CRT_ERR_INVALID, "crt_display: exposure_max must be finite and in [1e-9, 1e9]");
+        if (p.exposure_min > p.exposure_max) return fail(CRT_ERR_INVALID, "crt_display: exposure_min must not exceed exposure_max");
+        if (p.high_permille > 1000u) return fail(CRT_ERR_INVALID, "crt_display: high_permille must be at most 1000");
+        if (p.low_permille >= p.high_permille) return fail(CRT_ERR_INVALID, "crt_display: low_permille must be below high_permille");
+    }
+    const Image im = p.source == CRT_DISPLAY_SOURCE_SUM ? sum_image(s) : p.source == CRT_DISPLAY_SOURCE_DENOISED ? denoised_image(s) : temporal_image(s);
+    int rc = begin_image(s, im, "crt_display");
+    if (rc) return rc;
+    const size_t npx = (size_t)s->width * s->height;
+    if (npx >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_display: frame too large for 32-bit pixel indices");
+    if (im.packed && (rc = ensure_frame(s))) return rc;
+    if (!s->display) {
+        s->display = new (std::nothrow) DisplayState;
+        if (!s->display) return fail(CRT_ERR_NOMEM, "crt_display: out of host memory");
+    }
+    DisplayState* const ds = s->display;
+    if (!ds->d_rgba && (rc = dev_alloc(&ds->d_rgba, 4 * npx))) return rc;
+    if (!ds->d_words) {
+        const size_t n_words = crt::kDisplayWords;
+        if ((rc = dev_alloc(&ds->d_words, n_words))) return rc;
+        HIPCHK(hipMemsetAsync(ds->d_words, 0, n_words * sizeof(uint32_t), s->stream));
+    }
+    if ((rc = ensure_gamma(s))) return rc;
+
+    // the image's slices: the packed tile buffers of this scene and its peers as gathered, or the one linear image
+    std::vector<crt::DisplaySlice> slices;
+    try { slices.reserve(1 + s->peers.size()); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_display: out of host memory"); }
+    if (im.packed) {
+        rc = for_each_slice(s, [&slices](const crt::FrameArgs& f, const float* packed, uint32_t grid) {
+            crt::DisplaySlice sl{};
+            sl.f = f; sl.image = packed; sl.packed = 1u; sl.grid = grid;
+            slices.push_back(sl);
+        });
+        if (rc) return rc;
+    } else {
+        crt::DisplaySlice sl{};
+        sl.image = *im.rgb; sl.n_pixels = (uint32_t)npx; sl.grid = s->flat_grid(npx);
+        slices.push_back(sl);
+    }
+
+    if (metered) for (const crt::DisplaySlice& sl : slices) crt::launch_display_hist(sl, inv_count, (ds->d_words + crt::kDisplayBinsAt), s->stream);
+    crt::DisplayMeterArgs m{};
+    m.bins = (ds->d_words + crt::kDisplayBinsAt); m.last = (ds->d_words + crt::kDisplayLastAt); m.state = ds->d_words;
+    m.metered = metered ? 1u : 0u;
+    m.exposure = p.exposure; m.key = p.key; m.adapt = p.adapt; m.exposure_min = p.exposure_min; m.exposure_max = p.exposure_max;
+    m.low_permille = p.low_permille; m.high_permille = p.high_permille;
+    crt::launch_display_meter(m, s->stream);
+    // a shard of a frame (crt_set_shard with world > 1) leaves the other ranks' pixels at 0
+    if (im.packed && s->shard_world > 1u) HIPCHK(hipMemsetAsync(ds->d_rgba, 0, 4 * npx, s->stream));
+    const float w2 = p.white * p.white;
+    for (const crt::DisplaySlice& sl : slices) crt::launch_display(sl, inv_count, p.curve, w2, ds->d_words, s->d_gamma, ds->d_rgba, s->stream);
+    HIPCHK(hipGetLastError());
+    ds->valid = true;
+    if (metered) ds->metered = true;
+    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_read_display(crt_scene* s, uint8_t* rgba, size_t n_bytes) {
+    if (!s || !rgba) return null_argument("crt_read_display");
+    if (!s->display || !s->display->valid) return no_display("crt_read_display");
+    if (n_bytes != 4 * (size_t)s->width * s->height) return fail(CRT_ERR_INVALID, "crt_read_display: n_bytes must be width*height*4");
+    HIPCHK(hipSetDevice(s->device));
+    return copy_and_sync(s, rgba, s->display->d_rgba, n_bytes);
+}
+
+int crt_display_device(crt_scene* s, const uint8_t** d_rgba) {
+    if (!s || !d_rgba) return null_argument("crt_display_device");
+    *d_rgba = nullptr;
+    if (!s->display || !s->display->valid) return no_display("crt_display_device");
+    HIPCHK(hipSetDevice(s->device));
+    return sync_and_expose<uint8_t>(s, s->display->d_rgba, d_rgba);
+}
+
+int crt_display_get_state(crt_scene* s, crt_display_state* out) {
+    if (!s || !out) return null_argument("crt_display_get_state");
+    if (!s->display || !s->display->valid) return no_display("crt_display_get_state");
+    HIPCHK(hipSetDevice(s->device));
+    uint32_t w[crt::kDisplayStateWords];
+    const int rc = copy_and_sync(s, w, s->display->d_words, sizeof w);
+    if (rc) return rc;
+    std::memset(out, 0, sizeof *out);
+    std::memcpy(&out->exposure, &w[crt::kDisplayExposure], 4);
+    std::memcpy(&out->metered, &w[crt::kDisplayMetered], 4);
+    out->counted = w[crt::kDisplayCounted]; out->q = w[crt::kDisplayQ]; out->calls = w[crt::kDisplayCalls];
+    return CRT_OK;
+}
+
+int crt_read_display_histogram(crt_scene* s, uint32_t hist[256]) {
+    if (!s || !hist) return null_argument("crt_read_display_histogram");
+    if (!s->display || !s->display->valid) return no_display("crt_read_display_histogram");
+    if (!s->display->metered) return fail(CRT_ERR_INVALID, "crt_read_display_histogram: no crt_display call with CRT_DISPLAY_AUTO_EXPOSURE has metered on this scene");
+    HIPCHK(hipSetDevice(s->device));
+    return copy_and_sync(s, hist, (s->display->d_words + crt::kDisplayLastAt), 256 * sizeof(uint32_t));
+}
+
+// in stream order: a queued crt_display still adapts from what it had
+int crt_display_reset(crt_scene* s) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_display_reset: null scene");
+    if (!s->display || !s->display->d_words) return CRT_OK;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipMemsetAsync(s->display->d_words + crt::kDisplayCalls, 0, sizeof(uint32_t), s->stream));
     return CRT_OK;
 }

@@ -97,6 +97,20 @@ struct TemporalState {
     }
 };
 
+// What crt_display keeps, allocated by a scene's first call: the RGBA8 it writes (one buffer, whichever source a call
+// names), and one block of device words: the state the meter kernel writes and the display kernel reads its exposure from, the live
+// luminance bins and the bins of the last metered call.  The exposure never comes back to the host unless crt_display_get_state asks.
+struct DisplayState {
+    uint8_t* d_rgba = nullptr;
+    uint32_t* d_words = nullptr;         // display.hpp's layout: the state block, the live bins (kDisplayBinCopies x 256), 256 bins as last metered
+    bool valid = false;                  // some crt_display has been enqueued
+    bool metered = false;                // some call with CRT_DISPLAY_AUTO_EXPOSURE has been enqueued: the last bins exist
+    ~DisplayState() {
+        if (d_rgba) (void)hipFree(d_rgba);
+        if (d_words) (void)hipFree(d_words);
+    }
+};
+
 // What crt_update_vertices and crt_rebuild_vertices take new positions through, allocated by a scene's first call of either: a scene that
 // never moves holds none of it.  The times are those of the most recent call that succeeded (crt_last_update_ms).
 struct VertexIntake {
@@ -205,6 +219,7 @@ struct crt_scene {
     AovState* aov = nullptr;             // crt_render_aov's buffers, from the first call on
     DenoiseState* denoise = nullptr;     // crt_denoise's buffers, from the first call on
     TemporalState* temporal = nullptr;   // crt_temporal's buffers, from the first call on
+    DisplayState* display = nullptr;     // crt_display's buffers and exposure state, from the first call on
     uint32_t temporal_form = 0;          // option "temporal_form": how a CLAMP call reads its neighbourhood: 0 = the form measured faster, 1 = staged, 2 = direct
     crt::TemporalView aov_view{};        // the view of the most recent crt_render_aov that rendered HIT, recorded at enqueue: crt_temporal's current view
     bool have_aov_view = false;
@@ -405,6 +420,7 @@ struct crt_scene {
         delete aov;
         delete denoise;
         delete temporal;
+        delete display;
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,

@@ -9,7 +9,9 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (CRT_ABI_VERSION, CRT_ENV_HIDE_FROM_CAMERA, crt_environment, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params,
-                   crt_scene_desc, crt_tree_cost, lib)
+                   crt_scene_desc, crt_tree_cost, lib,
+                   CRT_DISPLAY_AUTO_EXPOSURE, CRT_DISPLAY_CURVE_ACES, CRT_DISPLAY_CURVE_CLAMP, CRT_DISPLAY_CURVE_REFERENCE, CRT_DISPLAY_CURVE_REINHARD,
+                   CRT_DISPLAY_SOURCE_DENOISED, CRT_DISPLAY_SOURCE_SUM, CRT_DISPLAY_SOURCE_TEMPORAL, crt_display_params, crt_display_state)
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _cost_dict, _ptr
 
 RAY_DT = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("pad", "<u4")])
@@ -295,6 +297,56 @@ class Scene:
         p = C.c_void_p()
         check(lib().crt_resolve_temporal_device(self._h, C.byref(p), 1 if sync else 0))
         return p.value
+
+    def display(self, inv_count=None, source="sum", curve="reference", exposure=1.0, auto=False, white=4.0, key=0.18, adapt=1.0, exposure_min=1e-6,
+                exposure_max=1e6, low_permille=0, high_permille=1000, sync=True):
+        """crt_display: the display transform of one float image ("sum": the running sum times inv_count, "denoised", "temporal") into RGBA8
+        in device memory: exposure (given, or with auto=True metered on the device from the image's luminance histogram and adapted by
+        `adapt` per call), a tone curve ("reference", "reinhard", "aces", "clamp") and the pinned gamma.  inv_count None =
+        1 / max(frame_count, 1).  The defaults are the header's NULL: resolve()'s bytes.  Returns the (height, width, 4) uint8 image, or None
+        with sync=False (read_display() after sync()).  An unknown source or curve name raises KeyError."""
+        if inv_count is None:
+            inv_count = 1.0 / max(self.frame_count, 1)
+        sources = {"sum": CRT_DISPLAY_SOURCE_SUM, "denoised": CRT_DISPLAY_SOURCE_DENOISED, "temporal": CRT_DISPLAY_SOURCE_TEMPORAL}
+        curves = {"reference": CRT_DISPLAY_CURVE_REFERENCE, "reinhard": CRT_DISPLAY_CURVE_REINHARD, "aces": CRT_DISPLAY_CURVE_ACES,
+                  "clamp": CRT_DISPLAY_CURVE_CLAMP}
+        p = crt_display_params()
+        p.source, p.curve = sources[source], curves[curve]
+        p.flags = CRT_DISPLAY_AUTO_EXPOSURE if bool(auto) else 0
+        p.exposure, p.white, p.key, p.adapt = (float(np.float32(v)) for v in (exposure, white, key, adapt))
+        p.exposure_min, p.exposure_max = float(np.float32(exposure_min)), float(np.float32(exposure_max))
+        p.low_permille, p.high_permille = int(low_permille), int(high_permille)
+        check(lib().crt_display(self._h, float(np.float32(inv_count)), C.byref(p), 1 if sync else 0))
+        return self.read_display() if sync else None
+
+    def read_display(self):
+        """crt_read_display: the RGBA8 of the last display(), (height, width, 4) uint8, rows as resolve has them"""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        check(lib().crt_read_display(self._h, _ptr(out), out.size))
+        return out
+
+    def display_device(self):
+        """crt_display_device: device pointer (int) of display()'s RGBA8, width * height * 4 bytes, valid until the scene is closed"""
+        ptr = C.c_void_p()
+        check(lib().crt_display_device(self._h, C.byref(ptr)))
+        return ptr.value
+
+    def display_state(self):
+        """crt_display_get_state: what the last display() left on the device: dict of exposure (E of that call), metered (L_avg, 0 when
+        nothing was metered), counted (N), q (Q) and calls (metered calls since the last display_reset)"""
+        st = crt_display_state()
+        check(lib().crt_display_get_state(self._h, C.byref(st)))
+        return {"exposure": np.float32(st.exposure), "metered": np.float32(st.metered), "counted": int(st.counted), "q": int(st.q), "calls": int(st.calls)}
+
+    def display_histogram(self):
+        """crt_read_display_histogram: the 256 luminance bins of the last display(auto=True), before trimming, uint32"""
+        out = np.empty(256, np.uint32)
+        check(lib().crt_read_display_histogram(self._h, _ptr(out)))
+        return out
+
+    def display_reset(self):
+        """crt_display_reset: the next display(auto=True) takes its metered exposure at once; the buffers stay"""
+        check(lib().crt_display_reset(self._h))
 
     def launch_times(self):
         """crt_get_launch_times: ms of every event-carrying launch since the spans were restarted (options timing / timing_accumulate)"""

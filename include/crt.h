@@ -497,6 +497,69 @@ int crt_temporal_device(crt_scene* s, const float** d_rgb);
 int crt_resolve_temporal(crt_scene* s, uint8_t* rgba, size_t n_bytes);
 int crt_resolve_temporal_device(crt_scene* s, const uint8_t** d_rgba, int sync);
 
+/* The display transform on the device (no reference counterpart beyond output.fs's fixed curve): one call turns one of the
+ * scene's three float images (the running sum, crt_denoise's image, crt_temporal's image) into RGBA8 in device memory, at an exposure that
+ * is given or metered on the device from the image's luminance histogram and adapted over calls, through one of four tone curves and then
+ * the pinned 2.2 gamma of crt_resolve.  A frame loop may end in crt_display in place of crt_resolve_device.
+ * The definition.  Each line is one IEEE float32 operation in the written order, no contraction; integers are exact.
+ *   Input pixel.  c = image * inv_count per channel for source SUM; c = image for DENOISED and TEMPORAL (inv_count is checked and then
+ *     ignored).  L = (0.3f*c.x + 0.6f*c.y) + 0.1f*c.z.
+ *   Meter (only with CRT_DISPLAY_AUTO_EXPOSURE; integer arithmetic throughout, so neither the order of atomics nor the launch shape can
+ *     change a bit).  A pixel counts iff L is finite and L >= 0x1p-16f: NaN, +-inf, zero, negatives and pixels owned by another shard rank
+ *     do not count.  Its bin is k = min((bits(L) >> 20) - (111 << 3), 255): 256 bins, 8 per octave, from 2^-16 upward, piecewise-linear in
+ *     each octave.  h[k] are uint32 counts, N = sum of h.  lo = floor(N*low_permille/1000), hi = floor(N*high_permille/1000) in 64-bit
+ *     arithmetic; with the counted pixels ordered by bin, ranks [lo, hi) are kept; M = hi - lo; S = the sum of the kept pixels' bin indices
+ *     (uint64).  M == 0: nothing is metered; the exposure keeps the adapted value it had, or takes params.exposure if it had none, and
+ *     `calls` does not advance.  Otherwise Q = floor(S*256 / M) + 128 (the mean bin in 1/256ths, moved to the bin's centre);
+ *     L_avg = float_from_bits(((111 << 3) << 20) + (Q << 12)); E_target = min(max(key / L_avg, exposure_min), exposure_max), one IEEE
+ *     division; the first metered call after create or crt_display_reset, or any call with adapt == 1: E = E_target; otherwise
+ *     E = E_prev + (E_target - E_prev) * adapt, E_prev the E of the previous metered call.
+ *     Without the flag E = params.exposure; no histogram is made and the adaptation (E_prev, calls) is left alone.
+ *   Curve.  x = c * E per channel, lum = (0.3f*x0 + 0.6f*x1) + 0.1f*x2.
+ *     REFERENCE: k = 1 / (1 + lum / 2); y = x * k.  At E = 1 this is crt_resolve's arithmetic.
+ *     REINHARD:  w2 = white*white (once, on the host, in float32); k = (1 + lum / w2) / (1 + lum); y = x * k.
+ *     ACES (Narkowicz's rational fit, per channel): n = x * (2.51f*x + 0.03f); d = x * (2.43f*x + 0.59f) + 0.14f; y = n / d.
+ *     CLAMP: y = x.
+ *   The byte is the number of thresholds of crt_resolve's pinned gamma that y has reached; NaN and negatives give 0; alpha is 255.
+ * crt_display_state: exposure = E of the last call; metered = L_avg, or 0 when nothing was metered (every manual call); counted = N;
+ * q = Q; calls = metered calls (M > 0) since create or the last crt_display_reset.  crt_display_get_state waits for the stream and
+ * reports the state as of the last call.  crt_read_display_histogram: the bins of the last call with CRT_DISPLAY_AUTO_EXPOSURE, before
+ * trimming.  crt_display_reset drops the adaptation (in stream order) and keeps the buffers.  crt_read_display: width*height*4 bytes, rows
+ * as crt_resolve has them.  crt_display_device waits for the stream; the pointer stays valid until the scene is destroyed.
+ * The exposure lives in device memory and the display kernel reads it from there: a sync = 0 call never waits for the GPU.
+ * crt_display is enqueued on the scene's stream behind any *_async frames, crt_render_aov, crt_denoise and crt_temporal calls.  It leaves
+ * the sum, the frame count, crt_get_frame_stats, the launch times, every AOV channel, every other stage's buffers and the three
+ * crt_resolve*_device buffers as they are.  Its own buffers are allocated by a scene's first crt_display and freed with the scene; later
+ * calls allocate nothing.  Source SUM runs on the packed tiles: crt_set_devices works (the histogram takes the gathered peers' slices), and
+ * a shard rank (crt_set_shard) sees its own pixels only: other ranks' bytes are 0 and are not counted.  DENOISED and TEMPORAL keep the
+ * refusals of the image they name.
+ * CRT_ERR_INVALID, nothing written and the exposure state unchanged: null scene; inv_count not finite or <= 0; an unknown source, curve
+ * or flag bits; non-zero reserved; a field out of its range or not finite (with AUTO unset the meter's fields are not looked at); a source
+ * image that does not exist; a read, device, state or histogram call before any successful crt_display, or with a wrong size; a histogram
+ * call when no call has metered.
+ * Out of scope: bloom, colour grading, output transfer functions other than the pinned 2.2 gamma, a float HDR output, spot or
+ * centre-weighted metering, time-based adaptation (adapt is per call; the host scales it by frame time). */
+enum { CRT_DISPLAY_SOURCE_SUM = 0, CRT_DISPLAY_SOURCE_DENOISED = 1, CRT_DISPLAY_SOURCE_TEMPORAL = 2 };
+enum { CRT_DISPLAY_CURVE_REFERENCE = 0, CRT_DISPLAY_CURVE_REINHARD = 1, CRT_DISPLAY_CURVE_ACES = 2, CRT_DISPLAY_CURVE_CLAMP = 3 };
+enum { CRT_DISPLAY_AUTO_EXPOSURE = 1 };
+typedef struct crt_display_params {   /* 48 bytes; NULL = {SUM, REFERENCE, 0, 1.0f, 4.0f, 0.18f, 1.0f, 1e-6f, 1e6f, 0, 1000, 0}: crt_resolve's bytes */
+    uint32_t source, curve, flags;
+    float exposure;                     /* manual E; with AUTO the value used until something has been metered; finite, [1e-9, 1e9] */
+    float white;                        /* REINHARD only; finite, [1e-3, 1e6] */
+    float key;                          /* AUTO: the luminance the metered mean is mapped to; finite, [1e-6, 1e6] */
+    float adapt;                        /* AUTO: share of the way to E_target per call; finite, (0, 1] */
+    float exposure_min, exposure_max;   /* AUTO: finite, [1e-9, 1e9], min <= max */
+    uint32_t low_permille, high_permille;   /* AUTO: 0 <= low < high <= 1000 */
+    uint32_t reserved;                  /* 0 */
+} crt_display_params;
+typedef struct crt_display_state { float exposure, metered; uint32_t counted, q, calls, reserved[3]; } crt_display_state;
+int crt_display(crt_scene* s, float inv_count, const crt_display_params* p, int sync);
+int crt_read_display(crt_scene* s, uint8_t* rgba, size_t n_bytes);
+int crt_display_device(crt_scene* s, const uint8_t** d_rgba);
+int crt_display_get_state(crt_scene* s, crt_display_state* out);
+int crt_read_display_histogram(crt_scene* s, uint32_t hist[256]);
+int crt_display_reset(crt_scene* s);
+
 /* Animated geometry (no reference counterpart: the reference uploads its scene once, Scene.h:1000-1062; DXR / OptiX call this an
  * update build).  New positions for the scene's vertices; triangles, materials, textures and the tree topology are unchanged.
  * n_vertices must equal the count given at create; normals (n_normals == create's) and lights (n_lights == create's) may be NULL =
