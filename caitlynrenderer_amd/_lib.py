@@ -23,6 +23,8 @@ CRT_TEMPORAL_SOURCE_SUM, CRT_TEMPORAL_SOURCE_DENOISED = 0, 1             # crt_t
 CRT_DISPLAY_SOURCE_SUM, CRT_DISPLAY_SOURCE_DENOISED, CRT_DISPLAY_SOURCE_TEMPORAL = 0, 1, 2          # crt_display_params.source
 CRT_DISPLAY_CURVE_REFERENCE, CRT_DISPLAY_CURVE_REINHARD, CRT_DISPLAY_CURVE_ACES, CRT_DISPLAY_CURVE_CLAMP = 0, 1, 2, 3    # crt_display_params.curve
 CRT_DISPLAY_AUTO_EXPOSURE = 1            # crt_display_params.flags
+CRT_BLOOM_SOURCE_SUM, CRT_BLOOM_SOURCE_DENOISED, CRT_BLOOM_SOURCE_TEMPORAL = 0, 1, 2                # crt_bloom_params.source
+CRT_BLOOM_CONSERVE = 1                   # crt_bloom_params.flags
 CRT_ENV_HIDE_FROM_CAMERA = 1             # crt_environment.flags
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
@@ -156,6 +158,12 @@ class crt_display_state(C.Structure):
                 ("reserved", C.c_uint32 * 3)]
 
 
+class crt_bloom_params(C.Structure):
+    # struct crt_bloom_params (32 bytes): crt_bloom's source, pyramid depth and blend settings
+    _fields_ = [("source", C.c_uint32), ("levels", C.c_uint32), ("flags", C.c_uint32), ("threshold", C.c_float), ("clamp", C.c_float),
+                ("scatter", C.c_float), ("strength", C.c_float), ("reserved", C.c_uint32)]
+
+
 # every symbol include/crt.h declares: name -> (restype, argtypes)
 _P, _SZ, _I, _U32, _F = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_float
 SYMBOLS = {
@@ -197,6 +205,12 @@ SYMBOLS = {
     "crt_display_get_state": (_I, [_P, C.POINTER(crt_display_state)]),
     "crt_read_display_histogram": (_I, [_P, _P]),
     "crt_display_reset": (_I, [_P]),
+    "crt_bloom": (_I, [_P, _F, C.POINTER(crt_bloom_params), _I]),
+    "crt_read_bloom": (_I, [_P, _P, _SZ]),
+    "crt_bloom_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_resolve_bloom": (_I, [_P, _P, _SZ]),
+    "crt_resolve_bloom_device": (_I, [_P, C.POINTER(_P), _I]),
+    "crt_display_bloom": (_I, [_P, C.POINTER(crt_display_params), _I]),
     "crt_get_launch_times": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "crt_update_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),

@@ -1,12 +1,13 @@
 // Everything that leaves the library as an image (include/crt.h): the running sum, the first-hit feature buffers, the
-// denoised image (§22), the accumulated image (§23), and the RGBA8 of the three float images.  The three are described once (Image) and
-// read, exposed and resolved through one path each ("Where an image leaves"); crt_frames.cpp renders the frames these read.
+// denoised image (§22), the accumulated image (§23), the bloomed image (§30), and the RGBA8 of the four float images.  The four are described
+// once (Image) and read, exposed and resolved through one path each ("Where an image leaves"); crt_frames.cpp renders the frames these read.
 #include <cmath>
 #include <cstring>
 #include <exception>
 #include <mutex>
 #include <new>
 
+#include "bloom.hpp"
 #include "crt_scene.hpp"
 #include "denoise.hpp"
 #include "display.hpp"
@@ -105,8 +106,8 @@ const float* gamma_thresholds() {
     return thr;
 }
 
-// One of the three float images (width * height * 3, linear pixel order) and its RGBA8.  The running sum lives as packed tiles, on every
-// device of the scene: a read un-tiles (and gathers) it into d_linear first, a resolve tone-maps the tiles directly.  The other two are
+// One of the four float images (width * height * 3, linear pixel order) and its RGBA8.  The running sum lives as packed tiles, on every
+// device of the scene: a read un-tiles (and gathers) it into d_linear first, a resolve tone-maps the tiles directly.  The other three are
 // what their call left on the stream, on a device that must be there, and exist only after such a call.
 struct Image {
     bool packed;             // the running sum
@@ -126,6 +127,11 @@ Image temporal_image(crt_scene* s) {
     TemporalState* const ts = s->temporal;
     if (!ts || !ts->valid) return {false, ": no crt_temporal call has succeeded on this scene", nullptr, nullptr};
     return {false, nullptr, &ts->d_out, &ts->d_rgba};
+}
+Image bloom_image(crt_scene* s) {
+    BloomState* const bl = s->bloom;
+    if (!bl || !bl->valid) return {false, ": no crt_bloom call has succeeded on this scene", nullptr, nullptr};
+    return {false, nullptr, &bl->d_out, &bl->d_rgba};
 }
 
 int null_argument(const char* who) { return fail(CRT_ERR_INVALID, std::string(who) + ": null argument"); }
@@ -552,8 +558,10 @@ int no_display(const char* who) { return fail(CRT_ERR_INVALID, std::string(who) 
 
 }  // namespace
 
-int crt_display(crt_scene* s, float inv_count, const crt_display_params* params, int sync) {
-    if (!s) return fail(CRT_ERR_INVALID, "crt_display: null scene");
+// crt_display and crt_display_bloom: one body, `bloomed` names the image (crt_bloom's in place of the one params.source names)
+static int display_call(crt_scene* s, const char* who, bool bloomed, float inv_count, const crt_display_params* params, int sync) {
+    const auto bad = [who](const char* what) { return fail(CRT_ERR_INVALID, std::string(who) + what); };
+    if (!s) return bad(": null scene");
     crt_display_params p{};
     if (params) p = *params;
     else {
@@ -561,32 +569,33 @@ int crt_display(crt_scene* s, float inv_count, const crt_display_params* params,
         p.exposure = 1.0f; p.white = 4.0f; p.key = 0.18f; p.adapt = 1.0f; p.exposure_min = 1e-6f; p.exposure_max = 1e6f;
         p.low_permille = 0u; p.high_permille = 1000u;
     }
-    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return fail(CRT_ERR_INVALID, "crt_display: inv_count must be finite and > 0");
-    if (p.source > (uint32_t)CRT_DISPLAY_SOURCE_TEMPORAL) return fail(CRT_ERR_INVALID, "crt_display: source is CRT_DISPLAY_SOURCE_SUM, _DENOISED or _TEMPORAL");
-    if (p.curve > (uint32_t)CRT_DISPLAY_CURVE_CLAMP) return fail(CRT_ERR_INVALID, "crt_display: curve is CRT_DISPLAY_CURVE_REFERENCE, _REINHARD, _ACES or _CLAMP");
-    if (p.flags & ~(uint32_t)CRT_DISPLAY_AUTO_EXPOSURE) return fail(CRT_ERR_INVALID, "crt_display: unknown flag bits");
-    if (p.reserved) return fail(CRT_ERR_INVALID, "crt_display: reserved must be 0");
-    if (!finite_in(p.exposure, 1e-9f, 1e9f)) return fail(CRT_ERR_INVALID, "crt_display: exposure must be finite and in [1e-9, 1e9]");
-    if (!finite_in(p.white, 1e-3f, 1e6f)) return fail(CRT_ERR_INVALID, "crt_display: white must be finite and in [1e-3, 1e6]");
+    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return bad(": inv_count must be finite and > 0");
+    if (bloomed && p.source != 0u) return bad(": source must be 0 (the image is crt_bloom's)");
+    if (p.source > (uint32_t)CRT_DISPLAY_SOURCE_TEMPORAL) return bad(": source is CRT_DISPLAY_SOURCE_SUM, _DENOISED or _TEMPORAL");
+    if (p.curve > (uint32_t)CRT_DISPLAY_CURVE_CLAMP) return bad(": curve is CRT_DISPLAY_CURVE_REFERENCE, _REINHARD, _ACES or _CLAMP");
+    if (p.flags & ~(uint32_t)CRT_DISPLAY_AUTO_EXPOSURE) return bad(": unknown flag bits");
+    if (p.reserved) return bad(": reserved must be 0");
+    if (!finite_in(p.exposure, 1e-9f, 1e9f)) return bad(": exposure must be finite and in [1e-9, 1e9]");
+    if (!finite_in(p.white, 1e-3f, 1e6f)) return bad(": white must be finite and in [1e-3, 1e6]");
     const bool metered = (p.flags & CRT_DISPLAY_AUTO_EXPOSURE) != 0u;
     if (metered) {
-        if (!finite_in(p.key, 1e-6f, 1e6f)) return fail(CRT_ERR_INVALID, "crt_display: key must be finite and in [1e-6, 1e6]");
-        if (!(std::isfinite(p.adapt) && p.adapt > 0.f && p.adapt <= 1.0f)) return fail(CRT_ERR_INVALID, "crt_display: adapt must be finite and in (0, 1]");
-        if (!finite_in(p.exposure_min, 1e-9f, 1e9f)) return fail(CRT_ERR_INVALID, "crt_display: exposure_min must be finite and in [1e-9, 1e9]");
-        if (!finite_in(p.exposure_max, 1e-9f, 1e9f)) return fail(CRT_ERR_INVALID, "crt_display: exposure_max must be finite and in [1e-9, 1e9]");
-        if (p.exposure_min > p.exposure_max) return fail(CRT_ERR_INVALID, "crt_display: exposure_min must not exceed exposure_max");
-        if (p.high_permille > 1000u) return fail(CRT_ERR_INVALID, "crt_display: high_permille must be at most 1000");
-        if (p.low_permille >= p.high_permille) return fail(CRT_ERR_INVALID, "crt_display: low_permille must be below high_permille");
+        if (!finite_in(p.key, 1e-6f, 1e6f)) return bad(": key must be finite and in [1e-6, 1e6]");
+        if (!(std::isfinite(p.adapt) && p.adapt > 0.f && p.adapt <= 1.0f)) return bad(": adapt must be finite and in (0, 1]");
+        if (!finite_in(p.exposure_min, 1e-9f, 1e9f)) return bad(": exposure_min must be finite and in [1e-9, 1e9]");
+        if (!finite_in(p.exposure_max, 1e-9f, 1e9f)) return bad(": exposure_max must be finite and in [1e-9, 1e9]");
+        if (p.exposure_min > p.exposure_max) return bad(": exposure_min must not exceed exposure_max");
+        if (p.high_permille > 1000u) return bad(": high_permille must be at most 1000");
+        if (p.low_permille >= p.high_permille) return bad(": low_permille must be below high_permille");
     }
-    const Image im = p.source == CRT_DISPLAY_SOURCE_SUM ? sum_image(s) : p.source == CRT_DISPLAY_SOURCE_DENOISED ? denoised_image(s) : temporal_image(s);
-    int rc = begin_image(s, im, "crt_display");
+    const Image im = bloomed ? bloom_image(s) : p.source == CRT_DISPLAY_SOURCE_SUM ? sum_image(s) : p.source == CRT_DISPLAY_SOURCE_DENOISED ? denoised_image(s) : temporal_image(s);
+    int rc = begin_image(s, im, who);
     if (rc) return rc;
     const size_t npx = (size_t)s->width * s->height;
-    if (npx >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_display: frame too large for 32-bit pixel indices");
+    if (npx >= (1ull << 31)) return fail(CRT_ERR_LIMIT, std::string(who) + ": frame too large for 32-bit pixel indices");
     if (im.packed && (rc = ensure_frame(s))) return rc;
     if (!s->display) {
         s->display = new (std::nothrow) DisplayState;
-        if (!s->display) return fail(CRT_ERR_NOMEM, "crt_display: out of host memory");
+        if (!s->display) return fail(CRT_ERR_NOMEM, std::string(who) + ": out of host memory");
     }
     DisplayState* const ds = s->display;
     if (!ds->d_rgba && (rc = dev_alloc(&ds->d_rgba, 4 * npx))) return rc;
@@ -599,7 +608,7 @@ int crt_display(crt_scene* s, float inv_count, const crt_display_params* params,
 
     // the image's slices: the packed tile buffers of this scene and its peers as gathered, or the one linear image
     std::vector<crt::DisplaySlice> slices;
-    try { slices.reserve(1 + s->peers.size()); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_display: out of host memory"); }
+    try { slices.reserve(1 + s->peers.size()); } catch (const std::exception&) { return fail(CRT_ERR_NOMEM, std::string(who) + ": out of host memory"); }
     if (im.packed) {
         rc = for_each_slice(s, [&slices](const crt::FrameArgs& f, const float* packed, uint32_t grid) {
             crt::DisplaySlice sl{};
@@ -630,6 +639,10 @@ int crt_display(crt_scene* s, float inv_count, const crt_display_params* params,
     if (sync) HIPCHK(hipStreamSynchronize(s->stream));
     return CRT_OK;
 }
+
+int crt_display(crt_scene* s, float inv_count, const crt_display_params* params, int sync) { return display_call(s, "crt_display", false, inv_count, params, sync); }
+// the bloomed image is a mean: there is no inv_count
+int crt_display_bloom(crt_scene* s, const crt_display_params* params, int sync) { return display_call(s, "crt_display_bloom", true, 1.0f, params, sync); }
 
 int crt_read_display(crt_scene* s, uint8_t* rgba, size_t n_bytes) {
     if (!s || !rgba) return null_argument("crt_read_display");
@@ -677,3 +690,90 @@ int crt_display_reset(crt_scene* s) {
     HIPCHK(hipMemsetAsync(s->display->d_words + crt::kDisplayCalls, 0, sizeof(uint32_t), s->stream));
     return CRT_OK;
 }
+
+// ---------------------------------------------------------------- crt_bloom --
+// Bloom (kernels in bloom.hip): enqueued on the scene's stream behind whatever frames, crt_render_aov, crt_denoise and
+// crt_temporal calls are queued there.  It reads the image it names and writes only BloomState's buffers (and d_linear, which every
+// crt_read_sum / crt_sum_device writes anew).
+
+namespace {
+
+// level k of the pyramid of a w x h frame: its size, and where its floats begin in BloomState::d_pyramid (level 1 at 0)
+struct BloomLevels {
+    uint32_t w[crt::kBloomMaxLevels + 1], h[crt::kBloomMaxLevels + 1];
+    size_t at[crt::kBloomMaxLevels + 2];
+    uint32_t n;                                            // levels the frame has, at most `levels`
+    BloomLevels(uint32_t width, uint32_t height, uint32_t levels) {
+        w[0] = width; h[0] = height; at[0] = at[1] = 0; n = 0;
+        for (uint32_t k = 1; k <= crt::kBloomMaxLevels; ++k) {
+            const bool has = n == k - 1u && k <= levels && std::min(w[k - 1], h[k - 1]) >= 2u;
+            w[k] = has ? (w[k - 1] + 1u) >> 1 : 0u; h[k] = has ? (h[k - 1] + 1u) >> 1 : 0u;
+            at[k + 1] = at[k] + 3 * (size_t)w[k] * h[k];
+            if (has) n = k;
+        }
+    }
+    size_t floats(uint32_t from, uint32_t to) const { return at[to + 1] - at[from]; }     // of levels from .. to
+};
+
+}  // namespace
+
+int crt_bloom(crt_scene* s, float inv_count, const crt_bloom_params* params, int sync) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_bloom: null scene");
+    crt_bloom_params p{};
+    if (params) p = *params;
+    else { p.source = CRT_BLOOM_SOURCE_SUM; p.levels = 6; p.flags = CRT_BLOOM_CONSERVE; p.threshold = 0.0f; p.clamp = 0.0f; p.scatter = 0.7f; p.strength = 0.05f; }
+    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return fail(CRT_ERR_INVALID, "crt_bloom: inv_count must be finite and > 0");
+    if (p.source > (uint32_t)CRT_BLOOM_SOURCE_TEMPORAL) return fail(CRT_ERR_INVALID, "crt_bloom: source is CRT_BLOOM_SOURCE_SUM, _DENOISED or _TEMPORAL");
+    if (p.flags & ~(uint32_t)CRT_BLOOM_CONSERVE) return fail(CRT_ERR_INVALID, "crt_bloom: unknown flag bits");
+    if (p.levels < 1u || p.levels > crt::kBloomMaxLevels) return fail(CRT_ERR_INVALID, "crt_bloom: levels must be 1..8");
+    if (p.reserved) return fail(CRT_ERR_INVALID, "crt_bloom: reserved must be 0");
+    if (!finite_in(p.threshold, 0.0f, 1e6f)) return fail(CRT_ERR_INVALID, "crt_bloom: threshold must be finite and in [0, 1e6]");
+    if (p.clamp != 0.0f && !finite_in(p.clamp, 1e-6f, 1e9f)) return fail(CRT_ERR_INVALID, "crt_bloom: clamp must be 0 (none) or finite and in [1e-6, 1e9]");
+    if (!finite_in(p.scatter, 0.0f, 1.0f)) return fail(CRT_ERR_INVALID, "crt_bloom: scatter must be finite and in [0, 1]");
+    const bool conserve = (p.flags & CRT_BLOOM_CONSERVE) != 0u;
+    if (!finite_in(p.strength, 0.0f, conserve ? 1.0f : 1e3f))
+        return fail(CRT_ERR_INVALID, conserve ? "crt_bloom: strength must be finite and in [0, 1] with CRT_BLOOM_CONSERVE" : "crt_bloom: strength must be finite and in [0, 1e3]");
+    if (s->shard_world > 1u) return fail(CRT_ERR_INVALID, "crt_bloom: a shard of a frame (crt_set_shard with world > 1) lacks its neighbours' pixels");
+    const Image im = p.source == CRT_BLOOM_SOURCE_SUM ? sum_image(s) : p.source == CRT_BLOOM_SOURCE_DENOISED ? denoised_image(s) : temporal_image(s);
+    int rc = begin_image(s, im, "crt_bloom");
+    if (rc) return rc;
+    const size_t npx = (size_t)s->width * s->height;
+    if (npx >= (1ull << 31) / 3u) return fail(CRT_ERR_LIMIT, "crt_bloom: frame too large for 32-bit indices");
+    if (im.packed && (rc = ensure_frame(s))) return rc;
+    if (!s->bloom) {
+        s->bloom = new (std::nothrow) BloomState;
+        if (!s->bloom) return fail(CRT_ERR_NOMEM, "crt_bloom: out of host memory");
+    }
+    BloomState* const bl = s->bloom;
+    // sized for every level the frame can have, whatever this call asks for
+    if (!bl->d_pyramid && (rc = dev_alloc(&bl->d_pyramid, std::max<size_t>(BloomLevels(s->width, s->height, crt::kBloomMaxLevels).floats(1, crt::kBloomMaxLevels), 1)))) return rc;
+    if (!bl->d_out && (rc = dev_alloc(&bl->d_out, 3 * npx))) return rc;
+    if (!bl->d_rgba && (rc = dev_alloc(&bl->d_rgba, 4 * npx))) return rc;
+    if (im.packed && (rc = untile_to_linear(s))) return rc;
+
+    crt::BloomSource src{};
+    src.image = *im.rgb; src.width = s->width; src.height = s->height;
+    src.scale = im.packed ? 1u : 0u; src.inv_count = inv_count;
+    src.threshold = p.threshold; src.clamp = p.clamp;
+    const BloomLevels lv(s->width, s->height, p.levels);
+    const uint32_t n = lv.n;
+    if (n == 0u) crt::launch_bloom_copy(src, bl->d_out, s->stream);
+    else {
+        float* const D = bl->d_pyramid;
+        // a launch per step: the forms that took several small levels per launch, or Down through LDS tiles, measured slower
+        crt::launch_bloom_down_first(src, D + lv.at[1], s->stream);
+        for (uint32_t k = 2; k <= n; ++k) crt::launch_bloom_down(D + lv.at[k - 1], lv.w[k - 1], lv.h[k - 1], D + lv.at[k], s->stream);
+        for (uint32_t k = n - 1u; k >= 1u; --k) crt::launch_bloom_up(D + lv.at[k + 1], D + lv.at[k], lv.w[k], lv.h[k], p.scatter, s->stream);
+        crt::launch_bloom_composite(src, D + lv.at[1], conserve ? 1u : 0u, p.strength, bl->d_out, s->stream);
+    }
+    HIPCHK(hipGetLastError());
+    bl->valid = true;
+    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_read_bloom(crt_scene* s, float* rgb, size_t n_floats) { return read_image(s, bloom_image, "crt_read_bloom", rgb, n_floats); }
+int crt_bloom_device(crt_scene* s, const float** d_rgb) { return expose_image(s, bloom_image, "crt_bloom_device", d_rgb); }
+// the bloomed image through crt_resolve's tone map and pinned gamma, into BloomState's own RGBA8
+int crt_resolve_bloom(crt_scene* s, uint8_t* rgba, size_t n_bytes) { return resolve_image_host(s, bloom_image, "crt_resolve_bloom", 1.0f, rgba, n_bytes); }
+int crt_resolve_bloom_device(crt_scene* s, const uint8_t** d_rgba, int sync) { return resolve_image_device(s, bloom_image, "crt_resolve_bloom_device", 1.0f, d_rgba, sync); }

@@ -111,6 +111,19 @@ struct DisplayState {
     }
 };
 
+// What crt_bloom keeps, allocated by a scene's first call: the pyramid (every level the frame can have, one after the
+// other; a level's U is written over its D on the way back up), the bloomed linear image and its RGBA8.
+struct BloomState {
+    float* d_pyramid = nullptr;          // levels 1 .. 8, 3 floats per pixel
+    float* d_out = nullptr;              // the bloomed MEAN radiance, 3 floats per pixel, linear pixel order
+    uint8_t* d_rgba = nullptr;           // crt_resolve_bloom*'s buffer
+    bool valid = false;                  // some crt_bloom has been enqueued
+    ~BloomState() {
+        void* bufs[] = {d_pyramid, d_out, d_rgba};
+        for (void* p : bufs) if (p) (void)hipFree(p);
+    }
+};
+
 // What crt_update_vertices and crt_rebuild_vertices take new positions through, allocated by a scene's first call of either: a scene that
 // never moves holds none of it.  The times are those of the most recent call that succeeded (crt_last_update_ms).
 struct VertexIntake {
@@ -220,6 +233,7 @@ struct crt_scene {
     DenoiseState* denoise = nullptr;     // crt_denoise's buffers, from the first call on
     TemporalState* temporal = nullptr;   // crt_temporal's buffers, from the first call on
     DisplayState* display = nullptr;     // crt_display's buffers and exposure state, from the first call on
+    BloomState* bloom = nullptr;         // crt_bloom's buffers, from the first call on
     uint32_t temporal_form = 0;          // option "temporal_form": how a CLAMP call reads its neighbourhood: 0 = the form measured faster, 1 = staged, 2 = direct
     crt::TemporalView aov_view{};        // the view of the most recent crt_render_aov that rendered HIT, recorded at enqueue: crt_temporal's current view
     bool have_aov_view = false;
@@ -421,6 +435,7 @@ struct crt_scene {
         delete denoise;
         delete temporal;
         delete display;
+        delete bloom;
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,

@@ -11,7 +11,8 @@ import numpy as np
 from ._lib import (CRT_ABI_VERSION, CRT_ENV_HIDE_FROM_CAMERA, crt_environment, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params,
                    crt_scene_desc, crt_tree_cost, lib,
                    CRT_DISPLAY_AUTO_EXPOSURE, CRT_DISPLAY_CURVE_ACES, CRT_DISPLAY_CURVE_CLAMP, CRT_DISPLAY_CURVE_REFERENCE, CRT_DISPLAY_CURVE_REINHARD,
-                   CRT_DISPLAY_SOURCE_DENOISED, CRT_DISPLAY_SOURCE_SUM, CRT_DISPLAY_SOURCE_TEMPORAL, crt_display_params, crt_display_state)
+                   CRT_DISPLAY_SOURCE_DENOISED, CRT_DISPLAY_SOURCE_SUM, CRT_DISPLAY_SOURCE_TEMPORAL, crt_display_params, crt_display_state,
+                   CRT_BLOOM_CONSERVE, CRT_BLOOM_SOURCE_DENOISED, CRT_BLOOM_SOURCE_SUM, CRT_BLOOM_SOURCE_TEMPORAL, crt_bloom_params)
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _cost_dict, _ptr
 
 RAY_DT = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("pad", "<u4")])
@@ -300,14 +301,15 @@ class Scene:
 
     def display(self, inv_count=None, source="sum", curve="reference", exposure=1.0, auto=False, white=4.0, key=0.18, adapt=1.0, exposure_min=1e-6,
                 exposure_max=1e6, low_permille=0, high_permille=1000, sync=True):
-        """crt_display: the display transform of one float image ("sum": the running sum times inv_count, "denoised", "temporal") into RGBA8
+        """crt_display: the display transform of one float image ("sum": the running sum times inv_count, "denoised", "temporal", or "bloom":
+        crt_display_bloom on bloom()'s image, which takes no inv_count) into RGBA8
         in device memory: exposure (given, or with auto=True metered on the device from the image's luminance histogram and adapted by
         `adapt` per call), a tone curve ("reference", "reinhard", "aces", "clamp") and the pinned gamma.  inv_count None =
         1 / max(frame_count, 1).  The defaults are the header's NULL: resolve()'s bytes.  Returns the (height, width, 4) uint8 image, or None
         with sync=False (read_display() after sync()).  An unknown source or curve name raises KeyError."""
         if inv_count is None:
             inv_count = 1.0 / max(self.frame_count, 1)
-        sources = {"sum": CRT_DISPLAY_SOURCE_SUM, "denoised": CRT_DISPLAY_SOURCE_DENOISED, "temporal": CRT_DISPLAY_SOURCE_TEMPORAL}
+        sources = {"sum": CRT_DISPLAY_SOURCE_SUM, "denoised": CRT_DISPLAY_SOURCE_DENOISED, "temporal": CRT_DISPLAY_SOURCE_TEMPORAL, "bloom": 0}
         curves = {"reference": CRT_DISPLAY_CURVE_REFERENCE, "reinhard": CRT_DISPLAY_CURVE_REINHARD, "aces": CRT_DISPLAY_CURVE_ACES,
                   "clamp": CRT_DISPLAY_CURVE_CLAMP}
         p = crt_display_params()
@@ -316,7 +318,10 @@ class Scene:
         p.exposure, p.white, p.key, p.adapt = (float(np.float32(v)) for v in (exposure, white, key, adapt))
         p.exposure_min, p.exposure_max = float(np.float32(exposure_min)), float(np.float32(exposure_max))
         p.low_permille, p.high_permille = int(low_permille), int(high_permille)
-        check(lib().crt_display(self._h, float(np.float32(inv_count)), C.byref(p), 1 if sync else 0))
+        if source == "bloom":
+            check(lib().crt_display_bloom(self._h, C.byref(p), 1 if sync else 0))
+        else:
+            check(lib().crt_display(self._h, float(np.float32(inv_count)), C.byref(p), 1 if sync else 0))
         return self.read_display() if sync else None
 
     def read_display(self):
@@ -347,6 +352,44 @@ class Scene:
     def display_reset(self):
         """crt_display_reset: the next display(auto=True) takes its metered exposure at once; the buffers stay"""
         check(lib().crt_display_reset(self._h))
+
+    def bloom(self, inv_count=None, source="sum", levels=6, conserve=True, threshold=0.0, clamp=0.0, scatter=0.7, strength=0.05, sync=True):
+        """crt_bloom: the light of the bright parts of one float image ("sum": the running sum times inv_count, "denoised", "temporal") spread
+        over an image pyramid of up to `levels` levels and put back on the image: read_bloom(), resolve_bloom() or display(source="bloom")
+        afterwards.  threshold: the luminance below which nothing blooms; clamp (0 = none): the luminance a pixel feeds the pyramid with at
+        most; scatter: the share taken from the coarser level at each step up; conserve: out = c + (G - c) * strength in place of
+        c + G * strength.  inv_count None = 1 / max(frame_count, 1).  The defaults are the header's NULL."""
+        if inv_count is None:
+            inv_count = 1.0 / max(self.frame_count, 1)
+        sources = {"sum": CRT_BLOOM_SOURCE_SUM, "denoised": CRT_BLOOM_SOURCE_DENOISED, "temporal": CRT_BLOOM_SOURCE_TEMPORAL}
+        p = crt_bloom_params()
+        p.source, p.levels, p.flags = sources[source], int(levels), (CRT_BLOOM_CONSERVE if conserve else 0)
+        p.threshold, p.clamp, p.scatter, p.strength = (float(np.float32(v)) for v in (threshold, clamp, scatter, strength))
+        check(lib().crt_bloom(self._h, float(np.float32(inv_count)), C.byref(p), 1 if sync else 0))
+
+    def read_bloom(self):
+        """crt_read_bloom: the bloomed MEAN radiance, (height, width, 3) float32, rows as read_sum has them"""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(lib().crt_read_bloom(self._h, _ptr(out), out.size))
+        return out
+
+    def bloom_device(self):
+        """crt_bloom_device: device pointer (int) of the bloomed image, width * height * 3 floats, valid until the scene is closed"""
+        ptr = C.c_void_p()
+        check(lib().crt_bloom_device(self._h, C.byref(ptr)))
+        return ptr.value
+
+    def resolve_bloom(self):
+        """crt_resolve_bloom: resolve's tone map and pinned gamma on the bloomed image, (height, width, 4) uint8"""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        check(lib().crt_resolve_bloom(self._h, _ptr(out), out.size))
+        return out
+
+    def resolve_bloom_device(self, sync=True):
+        """crt_resolve_bloom_device: the same RGBA8 left in device memory, in a buffer of its own; returns the device pointer"""
+        p = C.c_void_p()
+        check(lib().crt_resolve_bloom_device(self._h, C.byref(p), 1 if sync else 0))
+        return p.value
 
     def launch_times(self):
         """crt_get_launch_times: ms of every event-carrying launch since the spans were restarted (options timing / timing_accumulate)"""

@@ -537,7 +537,7 @@ int crt_resolve_temporal_device(crt_scene* s, const uint8_t** d_rgba, int sync);
  * or flag bits; non-zero reserved; a field out of its range or not finite (with AUTO unset the meter's fields are not looked at); a source
  * image that does not exist; a read, device, state or histogram call before any successful crt_display, or with a wrong size; a histogram
  * call when no call has metered.
- * Out of scope: bloom, colour grading, output transfer functions other than the pinned 2.2 gamma, a float HDR output, spot or
+ * Out of scope (bloom is crt_bloom's, below; crt_display_bloom displays its image): colour grading, output transfer functions other than the pinned 2.2 gamma, a float HDR output, spot or
  * centre-weighted metering, time-based adaptation (adapt is per call; the host scales it by frame time). */
 enum { CRT_DISPLAY_SOURCE_SUM = 0, CRT_DISPLAY_SOURCE_DENOISED = 1, CRT_DISPLAY_SOURCE_TEMPORAL = 2 };
 enum { CRT_DISPLAY_CURVE_REFERENCE = 0, CRT_DISPLAY_CURVE_REINHARD = 1, CRT_DISPLAY_CURVE_ACES = 2, CRT_DISPLAY_CURVE_CLAMP = 3 };
@@ -559,6 +559,63 @@ int crt_display_device(crt_scene* s, const uint8_t** d_rgba);
 int crt_display_get_state(crt_scene* s, crt_display_state* out);
 int crt_read_display_histogram(crt_scene* s, uint32_t hist[256]);
 int crt_display_reset(crt_scene* s);
+
+/* Bloom on the device (no reference counterpart): what an HDR display chain puts between the float image and the tone
+ * curve.  One call takes the light of the bright parts of one of the scene's three float images (the running sum, crt_denoise's image,
+ * crt_temporal's image), spreads it over an image pyramid and puts it back on the image: a fourth float image, the bloomed one, which is
+ * read, exposed and resolved like the others and displayed by crt_display_bloom.
+ * The definition.  Each line is one IEEE float32 operation in the written order, no contraction; the one division is IEEE.
+ *   Input pixel.  c as in crt_display: image * inv_count per channel for source SUM; the image as it is for DENOISED and TEMPORAL
+ *     (inv_count is checked and then ignored).  L = (0.3f*c.x + 0.6f*c.y) + 0.1f*c.z.
+ *   Level sizes.  w_0 = width, h_0 = height, w_k = (w_{k-1} + 1) >> 1, h_k = (h_{k-1} + 1) >> 1.
+ *   Level count.  n = the largest n <= levels such that every level k = 1..n has a parent with min(w_{k-1}, h_{k-1}) >= 2.  n == 0 (a
+ *     frame one pixel wide or high): the result is c, copied.
+ *   Bright pass (level 0 only).  Lc = clamp == 0 ? L : min(L, clamp); k = max(Lc - threshold, 0) / max(L, 0x1p-16f); k = 0 where not
+ *     (L > 0); b = c * k per channel.
+ *   Down(a), from level k-1 (w x h) to level k, per channel.  Horizontal first, on the parent's rows:
+ *     r(x) = ((a[x0-1] + a[x0+2]) + 3.0f * (a[x0] + a[x0+1])) * 0.125f with x0 = 2x, every index clamped to [0, w-1]; then the same
+ *     formula vertically over r at rows 2y-1 .. 2y+2, clamped to [0, h-1].  D_1 = Down(b), D_k = Down(D_{k-1}).
+ *   Up(a, w, h), from level k+1 (ws x hs) to the size of level k, per channel.  Horizontal: near = x >> 1; far = (x & 1) ? near + 1 :
+ *     near - 1, clamped to [0, ws-1]; r = a[near]*0.75f + a[far]*0.25f.  Then the same vertically.
+ *   The way back up.  U_n = D_n; for k = n-1 .. 1: U_k = D_k + (Up(U_{k+1}) - D_k) * scatter.
+ *   Glare.  G = Up(U_1, w_0, h_0).
+ *   Result.  With CRT_BLOOM_CONSERVE: out = c + (G - c) * strength.  Without: out = c + G * strength.
+ *   Non-finite input gives non-finite or unspecified values in the pixels its taps reach; which pixels those are is defined by the
+ *     arithmetic above, only a NaN's payload is unspecified.
+ * crt_read_bloom: width*height*3 floats of mean radiance, rows as crt_read_sum has them.  crt_bloom_device waits for the stream; the
+ * pointer stays valid until the scene is destroyed.  crt_resolve_bloom*: crt_resolve's curve and pinned gamma at inv_count 1, in a
+ * buffer of the stage's own.  crt_display_bloom is crt_display with the bloomed image as its input pixel: the same meter, adaptation
+ * state, RGBA8 buffer, state block, histogram and refusals; p->source must be 0 and names nothing; there is no inv_count, the image is
+ * a mean.
+ * crt_bloom is enqueued on the scene's stream behind any *_async frames, crt_render_aov, crt_denoise and crt_temporal calls; sync = 0
+ * returns at once.  It leaves the sum, the frame count, crt_get_frame_stats, the launch times, every AOV channel, every other stage's
+ * buffers and the crt_resolve*_device buffers as they are: it writes only its own buffers and, for SUM, the un-tiled copy every
+ * crt_read_sum rewrites.  Its buffers (the pyramid, the output, its RGBA8) are allocated by a scene's first crt_bloom and freed with
+ * the scene; later calls allocate nothing.  Source SUM works with crt_set_devices (the un-tiling gathers the peers); a shard of a frame
+ * (crt_set_shard with world > 1) is refused: a filter needs its neighbours.  DENOISED and TEMPORAL keep the refusals of the image they
+ * name.
+ * CRT_ERR_INVALID, nothing written, crt_last_error names the field: null scene; inv_count not finite or <= 0; an unknown source or
+ * unknown flag bits; levels outside 1..8; a field out of its range or not finite; non-zero reserved; a source image that does not
+ * exist; a read, device, resolve or display call before any successful crt_bloom, or with a wrong size.
+ * Out of scope: lens flares and streaks, a spectral or per-channel kernel, a temporal stabiliser, bloom on a shard. */
+enum { CRT_BLOOM_SOURCE_SUM = 0, CRT_BLOOM_SOURCE_DENOISED = 1, CRT_BLOOM_SOURCE_TEMPORAL = 2 };
+enum { CRT_BLOOM_CONSERVE = 1 };
+typedef struct crt_bloom_params {   /* 32 bytes; NULL = {SUM, 6, CONSERVE, 0.0f, 0.0f, 0.7f, 0.05f, 0} */
+    uint32_t source;      /* which float image; others refused */
+    uint32_t levels;      /* 1..8 pyramid levels asked for */
+    uint32_t flags;       /* CRT_BLOOM_CONSERVE or 0; other bits refused */
+    float    threshold;   /* luminance below which nothing blooms; finite, [0, 1e6] */
+    float    clamp;       /* 0 = none; else finite, [1e-6, 1e9]: a pixel feeds the pyramid as if its luminance were at most this (fireflies) */
+    float    scatter;     /* finite, [0, 1]: share taken from the coarser level at each step up */
+    float    strength;    /* finite; [0, 1] with CONSERVE, [0, 1e3] without */
+    uint32_t reserved;    /* 0 */
+} crt_bloom_params;
+int crt_bloom(crt_scene* s, float inv_count, const crt_bloom_params* p, int sync);
+int crt_read_bloom(crt_scene* s, float* rgb, size_t n_floats);           /* w*h*3, mean radiance, rows as crt_read_sum */
+int crt_bloom_device(crt_scene* s, const float** d_rgb);
+int crt_resolve_bloom(crt_scene* s, uint8_t* rgba, size_t n_bytes);      /* crt_resolve's curve + pinned gamma, inv_count 1 */
+int crt_resolve_bloom_device(crt_scene* s, const uint8_t** d_rgba, int sync);
+int crt_display_bloom(crt_scene* s, const crt_display_params* p, int sync);
 
 /* Animated geometry (no reference counterpart: the reference uploads its scene once, Scene.h:1000-1062; DXR / OptiX call this an
  * update build).  New positions for the scene's vertices; triangles, materials, textures and the tree topology are unchanged.
