@@ -26,6 +26,7 @@ CRT_DISPLAY_AUTO_EXPOSURE = 1            # crt_display_params.flags
 CRT_BLOOM_SOURCE_SUM, CRT_BLOOM_SOURCE_DENOISED, CRT_BLOOM_SOURCE_TEMPORAL = 0, 1, 2                # crt_bloom_params.source
 CRT_BLOOM_CONSERVE = 1                   # crt_bloom_params.flags
 CRT_ENV_HIDE_FROM_CAMERA = 1             # crt_environment.flags
+CRT_DEFORM_REBUILD, CRT_DEFORM_KEEP_NORMALS = 1, 2                       # crt_deform_scene's flags
 CRT_BUILD_LBVH_ON_DEVICE = 1
 CRT_BUILD_PLOC, CRT_BUILD_SAH = 2, 4
 CRT_INSTANCES_UPDATABLE = 1 << 16
@@ -164,6 +165,15 @@ class crt_bloom_params(C.Structure):
                 ("scatter", C.c_float), ("strength", C.c_float), ("reserved", C.c_uint32)]
 
 
+class crt_deformer_desc(C.Structure):
+    # struct crt_deformer_desc: crt_deformer_create's rest pose, influences and morph targets
+    _fields_ = [("abi_version", C.c_uint32), ("rest_vertices", C.c_void_p), ("n_vertices", C.c_size_t),
+                ("vertex_bones", C.c_void_p), ("vertex_weights", C.c_void_p),
+                ("rest_normals", C.c_void_p), ("n_normals", C.c_size_t), ("normal_bones", C.c_void_p), ("normal_weights", C.c_void_p),
+                ("n_bones", C.c_uint32), ("n_targets", C.c_uint32),
+                ("target_first", C.c_void_p), ("target_vertex", C.c_void_p), ("target_delta", C.c_void_p), ("device", C.c_int32)]
+
+
 # every symbol include/crt.h declares: name -> (restype, argtypes)
 _P, _SZ, _I, _U32, _F = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_float
 SYMBOLS = {
@@ -217,6 +227,16 @@ SYMBOLS = {
     "crt_last_update_ms": (_I, [_P, C.POINTER(_F), C.POINTER(_F)]),
     "crt_rebuild_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_rebuild_vertices_device": (_I, [_P, _P, _SZ, _I]),
+    "crt_deformer_create": (_I, [C.POINTER(crt_deformer_desc), C.POINTER(_P)]),
+    "crt_deformer_destroy": (_I, [_P]),
+    "crt_deformer_pose": (_I, [_P, _P, _P, _I]),
+    "crt_deformer_sync": (_I, [_P]),
+    "crt_deformer_vertices_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_deformer_normals_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_deformer_read": (_I, [_P, _P, _SZ, _P, _SZ]),
+    "crt_deformer_last_ms": (_I, [_P, C.POINTER(_F)]),
+    "crt_deform_scene": (_I, [_P, _P, _P, _P, _U32, _I]),
+    "crt_deform_host": (_I, [C.POINTER(crt_deformer_desc), _P, _P, _P, _P]),
     "crt_get_tree_cost": (_I, [_P, C.POINTER(crt_tree_cost)]),
     "crt_instances_tree_cost": (_I, [_P, C.c_int32, C.POINTER(crt_tree_cost)]),
     "crt_debug_read_accel": (_I, [_P, _I, _P, _SZ, C.POINTER(_SZ)]),

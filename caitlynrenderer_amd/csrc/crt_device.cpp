@@ -1573,9 +1573,12 @@ static int ensure_refit_state(crt_scene* s) {
 // The front half of crt_update_vertices and crt_rebuild_vertices (`rebuild`): the argument checks under the call's name, the host form's
 // positions staged on the device, and the check kernel with the call's one host wait for its verdict.  *verts: the positions on the device
 // (the scene's own upload, or the caller's d_user); lo / hi: their bounds.  Nothing the scene shows has been written when this refuses.
+// d_normals: new normals already on the scene's device (crt_deform_scene, which passes its name as `caller`), counted by n_normals and
+// checked by the same kernel in the same wait.
 static int take_vertices(crt_scene* s, bool rebuild, const float* h_verts, const float* d_user, size_t n_vertices, const float* normals, size_t n_normals,
-                         const crt_light* lights, size_t n_lights, const float** verts, float lo[3], float hi[3]) {
-    const std::string who = rebuild ? "crt_rebuild_vertices: " : "crt_update_vertices: ";
+                         const crt_light* lights, size_t n_lights, const float** verts, float lo[3], float hi[3], const float* d_normals = nullptr,
+                         const char* caller = nullptr) {
+    const std::string who = caller ? caller : rebuild ? "crt_rebuild_vertices: " : "crt_update_vertices: ";
     if (!s || (!h_verts && !d_user)) return fail(CRT_ERR_INVALID, who + "null argument");
     if (s->inst)
         return fail(CRT_ERR_INVALID, who + "an instanced scene's geometry belongs to its handle: use " +
@@ -1589,7 +1592,7 @@ static int take_vertices(crt_scene* s, bool rebuild, const float* h_verts, const
                 return fail(CRT_ERR_INVALID, who + "a replica on another GPU (crt_set_devices) cannot follow a rebuild: return to one device, rebuild, and set the devices again");
     }
     if (n_vertices != s->n_vertices) return fail(CRT_ERR_INVALID, who + "n_vertices differs from the count given at create");
-    if (normals && n_normals != s->n_normals) return fail(CRT_ERR_INVALID, who + "n_normals differs from the count given at create");
+    if ((normals || d_normals) && n_normals != s->n_normals) return fail(CRT_ERR_INVALID, who + "n_normals differs from the count given at create");
     if (lights && n_lights != s->n_lights) return fail(CRT_ERR_INVALID, who + "n_lights differs from the count given at create");
     if (normals)
         for (size_t i = 0; i < 3 * n_normals; ++i)
@@ -1599,8 +1602,8 @@ static int take_vertices(crt_scene* s, bool rebuild, const float* h_verts, const
     if (!s->intake) {
         std::unique_ptr<VertexIntake> owner(new (std::nothrow) VertexIntake);
         if (!owner) return fail(CRT_ERR_NOMEM, who + "out of memory");
-        if ((rc = dev_alloc(&owner->d_check, 8))) return rc;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&owner->h_check), 8 * sizeof(uint32_t)));
+        if ((rc = dev_alloc(&owner->d_check, 16))) return rc;
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&owner->h_check), 16 * sizeof(uint32_t)));
         HIPCHK(hipEventCreate(&owner->ev_a));
         HIPCHK(hipEventCreate(&owner->ev_b));
         s->intake = owner.release();
@@ -1613,15 +1616,18 @@ static int take_vertices(crt_scene* s, bool rebuild, const float* h_verts, const
         HIPCHK(hipMemcpyAsync(in->d_verts, h_verts, 3 * n_vertices * sizeof(float), hipMemcpyHostToDevice, st));
         *verts = in->d_verts;
     }
-    HIPCHK(hipMemsetAsync(in->d_check, 0, 8 * sizeof(uint32_t), st));
+    const size_t n_check = d_normals ? 16 : 8;    // words 8..15: the same verdict over the device normals
+    HIPCHK(hipMemsetAsync(in->d_check, 0, n_check * sizeof(uint32_t), st));
     crt::launch_check_vertices(*verts, (uint32_t)n_vertices, in->d_check, st);
-    HIPCHK(hipMemcpyAsync(in->h_check, in->d_check, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (d_normals) crt::launch_check_vertices(d_normals, (uint32_t)n_normals, in->d_check + 8, st);
+    HIPCHK(hipMemcpyAsync(in->h_check, in->d_check, n_check * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (in->times_pending) {                      // an unsynchronised update's events have passed by now: read them before this call records its own
         HIPCHK(hipEventElapsedTime(&in->device_ms, in->ev_a, in->ev_b));
         in->times_pending = false;
     }
     if (in->h_check[0]) return fail(CRT_ERR_INVALID, who + "a vertex coordinate is not finite or exceeds 1e18");
+    if (d_normals && in->h_check[8]) return fail(CRT_ERR_INVALID, who + "a normal is not finite or exceeds 1e18");
     for (int k = 0; k < 3; ++k) { hi[k] = crt::rf::key_to_float(in->h_check[1 + k]); lo[k] = crt::rf::key_to_float(~in->h_check[4 + k]); }
     return CRT_OK;
 }
@@ -1637,13 +1643,13 @@ static int refresh_after_geometry(crt_scene* x, const float lo[3], const float h
     return CRT_OK;
 }
 
-// normals / lights: host arrays or null
+// normals / lights: host arrays or null; d_normals: normals on the scene's device or null
 static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, size_t n_vertices, const float* normals, size_t n_normals,
-                       const crt_light* lights, size_t n_lights, int sync) {
+                       const crt_light* lights, size_t n_lights, int sync, const float* d_normals = nullptr, const char* caller = nullptr) {
     const auto t_begin = std::chrono::steady_clock::now();
     const float* verts = nullptr;
     float lo[3], hi[3];
-    int rc = take_vertices(s, false, h_verts, d_user, n_vertices, normals, n_normals, lights, n_lights, &verts, lo, hi);
+    int rc = take_vertices(s, false, h_verts, d_user, n_vertices, normals, n_normals, lights, n_lights, &verts, lo, hi, d_normals, caller);
     if (rc) return rc;
     if ((rc = ensure_refit_state(s))) return rc;
     VertexIntake* in = s->intake;
@@ -1666,6 +1672,7 @@ static int update_impl(crt_scene* s, const float* h_verts, const float* d_user, 
         HIPCHK(hipStreamWaitEvent(st, r->ev_peer[k], 0));
     }
     if (normals && n_normals) HIPCHK(hipMemcpyAsync(s->d_normals, normals, 3 * n_normals * sizeof(float), hipMemcpyHostToDevice, st));
+    if (d_normals && n_normals) HIPCHK(hipMemcpyAsync(s->d_normals, d_normals, 3 * n_normals * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (lights && n_lights) HIPCHK(hipMemcpyAsync(s->d_lights, lights, n_lights * sizeof(crt_light), hipMemcpyHostToDevice, st));
 
     HIPCHK(hipEventRecord(in->ev_a, st));
@@ -1736,11 +1743,11 @@ static int ensure_rebuild_state(crt_scene* s) {
 }
 
 static int rebuild_impl(crt_scene* s, const float* h_verts, const float* d_user, size_t n_vertices, const float* normals, size_t n_normals,
-                        const crt_light* lights, size_t n_lights) {
+                        const crt_light* lights, size_t n_lights, const float* d_normals = nullptr, const char* caller = nullptr) {
     const auto t_begin = std::chrono::steady_clock::now();
     const float* verts = nullptr;
     float lo[3], hi[3];
-    int rc = take_vertices(s, true, h_verts, d_user, n_vertices, normals, n_normals, lights, n_lights, &verts, lo, hi);
+    int rc = take_vertices(s, true, h_verts, d_user, n_vertices, normals, n_normals, lights, n_lights, &verts, lo, hi, d_normals, caller);
     if (rc) return rc;
     if ((rc = ensure_rebuild_state(s))) return rc;
     VertexIntake* in = s->intake;
@@ -1770,6 +1777,7 @@ static int rebuild_impl(crt_scene* s, const float* h_verts, const float* d_user,
 
     // ---- publish: nothing below can refuse ----
     if (normals && n_normals) HIPCHK(hipMemcpyAsync(s->d_normals, normals, 3 * n_normals * sizeof(float), hipMemcpyHostToDevice, st));
+    if (d_normals && n_normals) HIPCHK(hipMemcpyAsync(s->d_normals, d_normals, 3 * n_normals * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (lights && n_lights) HIPCHK(hipMemcpyAsync(s->d_lights, lights, n_lights * sizeof(crt_light), hipMemcpyHostToDevice, st));
     adopt_tree(s, fresh);
     delete s->refit;                              // its level order described the old tree: the next update finds the new tree's
@@ -1791,6 +1799,13 @@ static int rebuild_impl(crt_scene* s, const float* h_verts, const float* d_user,
     in->have_times = true;
     in->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return CRT_OK;
+}
+
+// crt_deform_scene's way in (crt_deform.cpp): positions and, unless null, normals on the scene's device, refitted or rebuilt
+int crt::scene_take_device_geometry(crt_scene* s, const float* d_vertices, size_t n_vertices, const float* d_normals, size_t n_normals, bool rebuild,
+                                    int sync, const char* caller) {
+    if (rebuild) return rebuild_impl(s, nullptr, d_vertices, n_vertices, nullptr, n_normals, nullptr, 0, d_normals, caller);
+    return update_impl(s, nullptr, d_vertices, n_vertices, nullptr, n_normals, nullptr, 0, sync, d_normals, caller);
 }
 
 extern "C" {

@@ -506,6 +506,10 @@ int ensure_planes(crt_scene* s);         // the nodes' child planes as floats, b
 int ensure_light_table(crt_scene* s);    // the world light table of a scene with mesh lights, rebuilt if its handle has changed
 // every peer's packed sum buffer -> d_gather[k] on the primary device, complete in the primary's stream order when this returns
 int gather_peers(crt_scene* s);
+// crt_update_vertices_device / crt_rebuild_vertices_device (`rebuild`) with normals on the device beside the positions (null: the scene's
+// stay), under `caller`'s name in every refusal
+int scene_take_device_geometry(crt_scene* s, const float* d_vertices, size_t n_vertices, const float* d_normals, size_t n_normals, bool rebuild, int sync,
+                               const char* caller);
 // crt_frames.cpp
 int alloc_frame_buffers(crt_scene* s);   // the frame buffers of the shard (rank, world, tile) as they stand, anew
 int ensure_frame(crt_scene* s);          // the shard's frame buffers, allocated by the first call that needs them

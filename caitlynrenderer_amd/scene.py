@@ -12,6 +12,7 @@ from ._lib import (CRT_ABI_VERSION, CRT_ENV_HIDE_FROM_CAMERA, crt_environment, C
                    crt_scene_desc, crt_tree_cost, lib,
                    CRT_DISPLAY_AUTO_EXPOSURE, CRT_DISPLAY_CURVE_ACES, CRT_DISPLAY_CURVE_CLAMP, CRT_DISPLAY_CURVE_REFERENCE, CRT_DISPLAY_CURVE_REINHARD,
                    CRT_DISPLAY_SOURCE_DENOISED, CRT_DISPLAY_SOURCE_SUM, CRT_DISPLAY_SOURCE_TEMPORAL, crt_display_params, crt_display_state,
+                   CRT_DEFORM_KEEP_NORMALS, CRT_DEFORM_REBUILD,
                    CRT_BLOOM_CONSERVE, CRT_BLOOM_SOURCE_DENOISED, CRT_BLOOM_SOURCE_SUM, CRT_BLOOM_SOURCE_TEMPORAL, crt_bloom_params)
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, _cost_dict, _ptr
 
@@ -509,6 +510,15 @@ class Scene:
     def rebuild_vertices_device(self, ptr, n, sync=True):
         """crt_rebuild_vertices_device: positions already on the scene's device (ptr = device address of n x 3 float32)."""
         check(lib().crt_rebuild_vertices_device(self._h, C.c_void_p(int(ptr)), int(n), int(bool(sync))))
+        self.frame_count = 0
+
+    def deform(self, deformer, bones, morph_weights=None, rebuild=False, keep_normals=False, sync=True):
+        """crt_deform_scene: the whole per-frame step of a deforming scene on its stream: the deformer's pose (only `bones` and
+        `morph_weights` cross PCIe), the coordinate check, the new normals into the scene's buffer unless keep_normals, and the refit,
+        or with rebuild=True a rebuild under rebuild_vertices' rules; clears the sum (frame_count restarts).  DESIGN.md §31."""
+        b, w = deformer._d.pose(bones, morph_weights)
+        flags = (CRT_DEFORM_REBUILD if rebuild else 0) | (CRT_DEFORM_KEEP_NORMALS if keep_normals else 0)
+        check(lib().crt_deform_scene(self._h, deformer._h, _ptr(b), _ptr(w), flags, 1 if sync else 0))
         self.frame_count = 0
 
     def tree_cost(self):

@@ -664,6 +664,89 @@ int crt_rebuild_vertices(crt_scene* s, const float* vertices, size_t n_vertices,
                          const float* normals, size_t n_normals, const crt_light* lights, size_t n_lights);
 int crt_rebuild_vertices_device(crt_scene* s, const void* d_vertices, size_t n_vertices, int sync);
 
+/* Deformation on the device (no reference counterpart: the reference's meshes never move): linear blend skinning with
+ * four influences per element, and morph targets on the positions.  A crt_deformer holds the rest pose, the influences and the morph
+ * targets in HBM, uploaded once; a pose is n_bones 3x4 matrices and n_targets weights, a few hundred bytes, and one kernel writes the
+ * deformed positions and normals into buffers the deformer owns, from where they go into crt_update_vertices_device,
+ * crt_rebuild_vertices_device, crt_instances_update_meshes_device, or, with the normals, through crt_deform_scene.
+ * The definition.  Each line is one IEEE float32 operation in the written order, no contraction; square root and division are
+ * correctly rounded.  A bone B[b] is a 3x4 row-major float[12] like crt_instance.object_to_world: the skinning matrix (bone-to-world
+ * times inverse bind), composed by the caller.  An element (a vertex or a normal) has four (b_k, w_k), k = 0..3.
+ *   Morph (positions only).  p = rest[v].  Then for every target t, in ascending t, that lists vertex v with delta d:
+ *     p.c = p.c + mw[t] * d.c for c = x, y, z.  A NULL morph_weights means all zeros, and the arithmetic still applies.
+ *   Blend, for j = 0..11.  M_j = w_0 * B[b_0][j]; then for k = 1, 2, 3: if w_k != 0, M_j = M_j + w_k * B[b_k][j].  A zero weight
+ *     after the first contributes nothing.  Weights are used as given, not normalised.
+ *   Position.  out.x = ((M_0*p.x + M_1*p.y) + M_2*p.z) + M_3; out.y and out.z likewise with M_4..7 and M_8..11.
+ *   Normal (its own four influences; not morphed).  q.x = (M_0*n.x + M_1*n.y) + M_2*n.z, q.y and q.z likewise with rows 1 and 2.
+ *     l2 = (q.x*q.x + q.y*q.y) + q.z*q.z.  If l2 >= 0x1p-126f and l2 is finite: out = q / sqrtf(l2) (three divisions).  Otherwise
+ *     out = q.  This is the linear part of the blended matrix, not its inverse transpose: exact for rigid and uniformly scaled
+ *     bones, an approximation under non-uniform scale or shear.
+ * crt_deformer_create copies every array of the desc (all host pointers) and allocates everything the deformer ever holds: 36 B per
+ * element for rest pose and influences, 12 B per element of output, 16 B per morph entry + 4 B per vertex where there are targets,
+ * 48 B per bone + 4 B per target of pose on the device and pinned on the host, one stream, five events.  The per-target lists become
+ * one list per vertex in target order, so a thread sums its own deltas: there are no floating-point atomics and two poses with the
+ * same input give the same bits.  The kernel reads the palette from a copy in LDS up to 256 bones and through the vector cache above;
+ * CRT_DEFORM_PALETTE=global in the environment at create takes the second way at any count; the bits are the same.
+ * CRT_ERR_INVALID (nothing allocated): a null or inconsistent desc (normal_bones / normal_weights
+ * are required exactly when n_normals > 0); n_vertices 0; n_vertices, n_normals or the number of morph entries >= 2^31; n_bones
+ * outside 1..65536; n_targets above 65535; a rest position, rest normal, weight or delta that is not finite; |rest position| > 1e18;
+ * a bone index >= n_bones; a morph vertex >= n_vertices; target_first not starting at 0 or descending; vertex indices within one
+ * target not strictly ascending; no such device.  The desc is checked first, then the device: CRT_ERR_NO_DEVICE without a GPU.
+ * crt_deformer_pose: bones (12 * n_bones floats) and morph_weights (n_targets floats or NULL) are host arrays, checked finite on the
+ * host (CRT_ERR_INVALID, the outputs as they were), copied, and the kernel runs on the deformer's own stream; sync = 0 returns at
+ * once.  The outputs are NOT checked: a pose can produce non-finite or huge coordinates, which the calls that take them refuse.
+ * crt_deformer_vertices_device / crt_deformer_normals_device: n_vertices x 3 / n_normals x 3 floats (NULL for a deformer without
+ * normals); valid for the deformer's life.  Before handing them to another handle the caller waits (sync != 0 or crt_deformer_sync):
+ * that handle reads them on a stream of its own.  crt_deformer_read copies the last pose's outputs to the host (normals may be NULL;
+ * CRT_ERR_INVALID before the first pose or with wrong sizes).  crt_deformer_last_ms: stream time of the last pose's kernel.
+ * crt_deform_scene is the whole per-frame step of a flat scene, enqueued on the SCENE's stream: the pose; the coordinate check of
+ * crt_update_vertices_device, and the same check over the new normals; the new normals copied device to device into the scene's
+ * normal buffer; the refit.  With CRT_DEFORM_REBUILD the tree is rebuilt instead, under every rule and refusal of
+ * crt_rebuild_vertices_device.  CRT_DEFORM_KEEP_NORMALS (and a deformer without normals) leaves the scene's normals alone.  The
+ * result is that of crt_update_vertices(s, V, n_vertices, N, n_normals, NULL, 0) (or crt_rebuild_vertices) with V, N the definition's
+ * output: every debug read, every walk, every frame.  The one host wait is the check's, as in crt_update_vertices_device; sync = 0
+ * returns with the refit enqueued.  The call orders itself behind the deformer's own stream and the deformer's next pose behind it.
+ * CRT_ERR_INVALID, the scene as it was: a null argument; unknown flag bits; a deformer on another device; an instanced scene or a
+ * replica; n_vertices differing from the scene's; n_normals differing from the scene's unless KEEP_NORMALS or the deformer has none;
+ * a pose that is not finite; an output coordinate or normal component that is not finite or exceeds 1e18 (the deformer's outputs
+ * then hold that pose).  Lights stay as they are: a deforming emissive mesh keeps the lights of its create.
+ * crt_deform_host [host] runs the same checks and the same arithmetic (csrc/host/deform_math.hpp, which the kernel includes) on the
+ * CPU: out_vertices 3 * n_vertices floats, out_normals 3 * n_normals floats or NULL.  desc->device is ignored.  A refusal writes
+ * nothing.
+ * Out of scope: normals recomputed from the deformed triangles, morph deltas for normals, dual-quaternion blending, more than four
+ * influences, moved lights of a deforming emissive mesh, the shading normals of an instanced scene's meshes (the ray-query handle
+ * is served through the raw pointers only), and removing the one host wait of the coordinate check. */
+enum { CRT_DEFORM_REBUILD = 1, CRT_DEFORM_KEEP_NORMALS = 2 };     /* crt_deform_scene's flags */
+typedef struct crt_deformer_desc {
+    uint32_t abi_version;                 /* CRT_ABI_VERSION */
+    const float*    rest_vertices;        /* 3 * n_vertices */
+    size_t          n_vertices;
+    const uint16_t* vertex_bones;         /* 4 * n_vertices */
+    const float*    vertex_weights;       /* 4 * n_vertices */
+    const float*    rest_normals;         /* 3 * n_normals, or NULL */
+    size_t          n_normals;
+    const uint16_t* normal_bones;         /* 4 * n_normals; required exactly when n_normals > 0 */
+    const float*    normal_weights;       /* 4 * n_normals; likewise */
+    uint32_t        n_bones;              /* 1..65536 */
+    uint32_t        n_targets;            /* 0..65535 */
+    const uint32_t* target_first;         /* n_targets + 1: target t owns entries [target_first[t], target_first[t + 1]) */
+    const uint32_t* target_vertex;        /* per entry: the vertex, strictly ascending within one target */
+    const float*    target_delta;         /* 3 per entry */
+    int32_t         device;
+} crt_deformer_desc;
+typedef struct crt_deformer crt_deformer;
+int crt_deformer_create(const crt_deformer_desc* desc, crt_deformer** out);
+int crt_deformer_destroy(crt_deformer* d);
+int crt_deformer_pose(crt_deformer* d, const float* bones, const float* morph_weights, int sync);
+int crt_deformer_sync(crt_deformer* d);
+int crt_deformer_vertices_device(crt_deformer* d, const float** d_vertices);
+int crt_deformer_normals_device(crt_deformer* d, const float** d_normals);
+int crt_deformer_read(crt_deformer* d, float* vertices, size_t n_floats_v, float* normals, size_t n_floats_n);
+int crt_deformer_last_ms(crt_deformer* d, float* device_ms);
+int crt_deform_scene(crt_scene* s, crt_deformer* d, const float* bones, const float* morph_weights, uint32_t flags, int sync);
+int crt_deform_host(const crt_deformer_desc* desc, const float* bones, const float* morph_weights, float* out_vertices,
+                    float* out_normals);                                                                    /* [host] */
+
 /* The SAH cost of a CWBVH.  For every node8 of a range and every slot with meta != 0 the slot's corners are decoded as
  * the walk decodes them, lo = p + q_lo * 2^(e-127) and hi likewise, each rounded once to fp32, then widened to double:
  * A = (dx*dy + dy*dz) + dz*dx, half the slot's surface area.  inner_area sums A over the inner (imask) slots; leaf_area sums
