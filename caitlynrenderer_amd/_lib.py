@@ -134,6 +134,11 @@ class crt_instances_info(C.Structure):
                 ("reserved_f", C.c_float)]
 
 
+class crt_ao_params(C.Structure):
+    # struct crt_ao_params (32 bytes): samples, radius and offset of the ambient-occlusion entries
+    _fields_ = [("samples", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_float), ("offset", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
 class crt_denoise_params(C.Structure):
     # struct crt_denoise_params (32 bytes): crt_denoise's filter settings
     _fields_ = [("passes", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float),
@@ -197,6 +202,11 @@ SYMBOLS = {
     "crt_render_aov": (_I, [_P, _F, _F, _U32, _I]),
     "crt_read_aov": (_I, [_P, _U32, _P, _SZ]),
     "crt_aov_device": (_I, [_P, _U32, C.POINTER(_P)]),
+    "crt_render_ao": (_I, [_P, _F, _F, C.POINTER(crt_ao_params), _I]),
+    "crt_read_ao": (_I, [_P, _P, _SZ]),
+    "crt_ao_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_ao_points": (_I, [_P, _P, _SZ, _F, _F, C.POINTER(crt_ao_params), _P]),
+    "crt_ao_points_device": (_I, [_P, _P, _SZ, _F, _F, C.POINTER(crt_ao_params), _P, _I]),
     "crt_denoise": (_I, [_P, _F, C.POINTER(crt_denoise_params), _I]),
     "crt_read_denoised": (_I, [_P, _P, _SZ]),
     "crt_denoised_device": (_I, [_P, C.POINTER(_P)]),

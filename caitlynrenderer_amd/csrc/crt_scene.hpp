@@ -124,6 +124,28 @@ struct BloomState {
     }
 };
 
+// What the ambient-occlusion entries keep, each buffer allocated by the first call that needs it.  View mode: the first hits
+// of the view (HIT and NORMAL values in buffers of their own: crt_render_aov's channels stay as they are), the points made of them and the
+// image.  Both modes: the visibility words of the call in flight.  Points mode with host pointers: its upload and download buffers.
+struct AoState {
+    float4* d_hit = nullptr;             // width * height each
+    float4* d_normal = nullptr;
+    float4* d_view_points = nullptr;     // 2 rows per pixel
+    float4* d_image = nullptr;           // what crt_read_ao / crt_ao_device hand out
+    bool rendered = false;               // some crt_render_ao has been enqueued
+    uint32_t* d_vis = nullptr;           // n x ceil(K / 32) words
+    float4* d_points = nullptr;          // crt_ao_points: 2 rows per point
+    float4* d_out = nullptr;
+    size_t vis_cap = 0, points_cap = 0, out_cap = 0;
+    uint2* d_tile_xy = nullptr;          // flat scenes: the tiles of the whole frame, for k_aov
+    uint32_t n_local_pixels = 0, tile = 0;
+    uint32_t* d_count = nullptr;         // instanced scenes: the 8 counters of the primary rays' queue
+    ~AoState() {
+        void* bufs[] = {d_hit, d_normal, d_view_points, d_image, d_vis, d_points, d_out, d_tile_xy, d_count};
+        for (void* p : bufs) if (p) (void)hipFree(p);
+    }
+};
+
 // What crt_update_vertices and crt_rebuild_vertices take new positions through, allocated by a scene's first call of either: a scene that
 // never moves holds none of it.  The times are those of the most recent call that succeeded (crt_last_update_ms).
 struct VertexIntake {
@@ -234,6 +256,7 @@ struct crt_scene {
     TemporalState* temporal = nullptr;   // crt_temporal's buffers, from the first call on
     DisplayState* display = nullptr;     // crt_display's buffers and exposure state, from the first call on
     BloomState* bloom = nullptr;         // crt_bloom's buffers, from the first call on
+    AoState* ao = nullptr;               // the ambient-occlusion entries' buffers, from the first call on
     uint32_t temporal_form = 0;          // option "temporal_form": how a CLAMP call reads its neighbourhood: 0 = the form measured faster, 1 = staged, 2 = direct
     crt::TemporalView aov_view{};        // the view of the most recent crt_render_aov that rendered HIT, recorded at enqueue: crt_temporal's current view
     bool have_aov_view = false;
@@ -436,6 +459,7 @@ struct crt_scene {
         delete temporal;
         delete display;
         delete bloom;
+        delete ao;
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,

@@ -8,6 +8,8 @@
 
 #include <type_traits>
 
+#define CRT_AO_DEVICE_MATH 1      // ao.hpp: the generator of the occlusion rays, in device code
+#include "ao.hpp"
 #include "instances.hpp"
 #include "instances_walk.hpp"
 #include "rt_kernels.hpp"
@@ -329,6 +331,8 @@ __device__ __forceinline__ uint32_t launch_mask(const InstMaskQueueArgs& a) { re
 __device__ __forceinline__ uint32_t launch_mask(const InstMaskShadowArgs& a) { return a.ray_mask; }
 __device__ __forceinline__ uint32_t launch_mask(const InstQueueArgs&) { return 0u; }
 __device__ __forceinline__ uint32_t launch_mask(const InstShadowArgs&) { return 0u; }
+__device__ __forceinline__ uint32_t launch_mask(const InstMaskAoArgs& a) { return a.ray_mask; }
+__device__ __forceinline__ uint32_t launch_mask(const InstAoArgs&) { return 0u; }
 
 // Closest hits of a segment's path-ray queue: workgroup (g, c) = one wave walks entries [64 c, 64 c + 64) of sub-queue g, as far as its
 // device-side count goes; hits and hit instances go to buffers parallel to the queue, and k_segment<PRETRACED, INST> shades them.
@@ -388,6 +392,39 @@ __global__ void __launch_bounds__(64) k_shadow_instances_deferred(std::condition
 #undef CRT_WALK_DONE
 #undef CRT_WALK_MASK
     if (STATS) flush_inst_totals(a.visit_totals, tn, tt);
+}
+
+// The occlusion rays of an instanced scene's AO points (ao.hpp): workgroup c = one wave walks entries [64 c, 64 c + 64) of
+// the index space [0, n K); the ray of an entry is built where it is loaded and never stored, an UNoccluded ray sets its bit of its point's
+// visibility words.  A point without rays loads a ray whose origin is not finite, which the walk finishes as a miss at once.
+// MASK: the walk culls by a.ray_mask (the scene's "mask_shadow").
+template <bool MASK>
+__global__ void __launch_bounds__(64) k_ao_walk_instances(std::conditional_t<MASK, InstMaskAoArgs, InstAoArgs> a) {
+    extern __shared__ uint2 s_lds[];
+    constexpr bool ANY = true, STATS = false;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t total = a.g.n * a.g.K;
+    const uint64_t first64 = (uint64_t)blockIdx.x * 64u;
+    if (first64 >= total) return;
+    uint32_t next = (uint32_t)first64;
+    const uint32_t end = total - next < 64u ? total : next + 64u;
+    uint2* const stk = s_lds + lane;
+    const int stack_entries = (int)a.stack_entries;
+#define CRT_WALK_LOAD(idx, r0, r1)                                                         \
+            float4 r0 = make_float4(__builtin_nanf(""), 0.f, 0.f, a.g.radius), r1 = make_float4(0.f, 0.f, 1.f, 0.f); \
+            {                                                                              \
+                vec3 ao_o, ao_d;                                                           \
+                if (ao_ray(a.g, idx, ao_o, ao_d)) {                                        \
+                    r0 = make_float4(ao_o.x, ao_o.y, ao_o.z, a.g.radius);                  \
+                    r1 = make_float4(ao_d.x, ao_d.y, ao_d.z, 0.f);                         \
+                }                                                                          \
+            }
+#define CRT_WALK_DONE(idx, h, hit, inst, nn, nt) (void)(nn); (void)(nt); if (!hit) ao_mark_visible(a.g, a.vis, idx);
+#define CRT_WALK_MASK(lane_mask) ((void)(lane_mask), launch_mask(a))
+#include "instances_walk_loop.hpp"
+#undef CRT_WALK_LOAD
+#undef CRT_WALK_DONE
+#undef CRT_WALK_MASK
 }
 
 static inline dim3 grid_for(uint64_t n) { return dim3((uint32_t)((n + 255u) / 256u)); }
@@ -487,6 +524,16 @@ void launch_shadow_instances_deferred(const InstMaskShadowArgs& a, bool stats, b
         if (stats) hipLaunchKernelGGL((k_shadow_instances_deferred<true, false>), g, b, lds, stream, u);
         else       hipLaunchKernelGGL((k_shadow_instances_deferred<false, false>), g, b, lds, stream, u);
     }
+}
+
+void launch_ao_walk_instances(const InstMaskAoArgs& a, bool mask, hipStream_t stream) {
+    const uint64_t total = (uint64_t)a.g.n * a.g.K;
+    if (!total) return;
+    const dim3 g((uint32_t)((total + 63u) / 64u)), b(64);
+    const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
+    const InstAoArgs& u = a;
+    if (mask) hipLaunchKernelGGL((k_ao_walk_instances<true>), g, b, lds, stream, a);
+    else      hipLaunchKernelGGL((k_ao_walk_instances<false>), g, b, lds, stream, u);
 }
 
 // crt_warmup: load this translation unit's code object on the current device (device_build.hpp)

@@ -16,6 +16,8 @@
 
 #include <algorithm>
 
+#define CRT_AO_DEVICE_MATH 1      // ao.hpp: the generator of the occlusion rays, in device code
+#include "ao.hpp"
 #include "rt_kernels.hpp"
 #include "rt_math.hpp"
 #include "host/flatnode_link.hpp"
@@ -2304,6 +2306,69 @@ __global__ void __launch_bounds__(256) k_aov_instanced(InstAovArgs a) {
     aov_store<true>(a, a.out, a.channels, (size_t)py * a.f.width + px, V3(r1.x, r1.y, r1.z), h.x, h.y, h.z, tri, slot, mtl, inst_id, iw.x, mb.y, mb.z);
 }
 
+// ------------------------------------------------------------------ ambient occlusion (include/crt.h at crt_render_ao) ----
+// Kernels of their own behind the feature buffers': no existing kernel's text or argument block moves.
+
+// The AO points of a view: one lane per pixel of the frame in linear order.  The first hit is what k_aov / k_aov_instanced left in the AO
+// state's own HIT and NORMAL buffers; the primary ray is formed again (primary_ray: the same lines, the same bits) for p = o + d t and for
+// the RNG state behind its jitter draws.  A miss pixel gets a zero normal: the point without rays.
+__global__ void __launch_bounds__(256) k_ao_view_points(AoViewArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_pixels) return;
+    const uint32_t py = i / a.f.width, px = i - py * a.f.width;
+    float sx, sy;
+    vec3 o, d;
+    primary_ray(a.f, px, py, a.f.rv, sx, sy, o, d);
+    const float4 h = a.hit[i];
+    vec3 p = V3(0.f, 0.f, 0.f), n = V3(0.f, 0.f, 0.f);
+    if (__float_as_int(h.w) >= 0) {
+        const float4 nr = a.normal[i];
+        p = o + d * h.x;
+        n = V3(nr.x, nr.y, nr.z);
+    }
+    a.points[2 * (size_t)i] = make_float4(p.x, p.y, p.z, sx);
+    a.points[2 * (size_t)i + 1] = make_float4(n.x, n.y, n.z, sy);
+}
+
+// The occlusion rays of a flat scene: k_shadow_deferred's walk (walk_pool<ANY>, single-wave workgroups, its stack, occupancy bound and
+// eight-lanes-per-ray drain) over the index space [0, n K) in pools of a.pool entries.  `load` builds ray e in registers; `done` sets the bit
+// of an UNoccluded ray.  A point without rays loads as an empty slot, which the same iteration finishes as a miss: its bits are never read.
+__global__ void __launch_bounds__(64, CRT_SHADOW_OCC) k_ao_walk(AoWalkArgs a) {
+    extern __shared__ uint2 s_lds[];
+    const uint32_t total = a.g.n * a.g.K;
+    const uint64_t first64 = (uint64_t)blockIdx.x * a.pool;
+    if (first64 >= total) return;
+    const uint32_t first = (uint32_t)first64, last = total - first < a.pool ? total : first + a.pool;
+    uint32_t nn = 0, nt = 0, wn = 0, wt = 0;
+    auto load = [&](uint32_t e, vec3& o, vec3& d, float& tmax) {
+        tmax = a.g.radius;
+        return ao_ray(a.g, e, o, d);
+    };
+    auto done = [&](uint32_t e, const HitState&, bool occluded) { if (!occluded) ao_mark_visible(a.g, a.vis, e); };
+    walk_pool<true, false>(a.nodes, a.tris, s_lds, (int)a.stack_entries, a.overflow, PoolStatic{first, last}, a.refill_min, a.tri_min, a.lanes_log2, load, done,
+                           nn, nt, wn, wt);
+}
+
+// Step 7, one lane per point: V = the set bits, b = the sum of their directions in k order (formed again from the point: the same lines
+// as the walk's), the result (b, V / K); a point without rays gives (0, 0, 0, -1).
+__global__ void __launch_bounds__(256) k_ao_fold(AoGen g, const uint32_t* __restrict__ vis, float4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.n) return;
+    AoFrame fr;
+    if (!ao_frame(g, i, fr)) { out[i] = make_float4(0.f, 0.f, 0.f, -1.0f); return; }
+    vec3 b = V3(0.f, 0.f, 0.f);
+    uint32_t V = 0u;
+    for (uint32_t w = 0; w < g.words; ++w) {
+        uint32_t bits = vis[(size_t)i * g.words + w];
+        while (bits) {
+            const uint32_t k = 32u * w + (uint32_t)__builtin_ctz(bits);
+            bits &= bits - 1u;
+            if (k < g.K) { b = b + ao_direction(fr, k, g.rv); ++V; }
+        }
+    }
+    out[i] = make_float4(b.x, b.y, b.z, __fdiv_rn((float)V, (float)g.K));
+}
+
 // ------------------------------------------------------------------ launchers --------
 
 // Timing events ride on the dispatch itself (hipExtLaunchKernelGGL): the events take the kernel's own start/stop
@@ -2508,6 +2573,17 @@ void launch_aov(const AovArgs& a, hipStream_t stream) {
 }
 void launch_aov_instanced(const InstAovArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(k_aov_instanced, dim3(8u * (a.sub_capacity / 256u)), dim3(256), 0, stream, a);
+}
+void launch_ao_view_points(const AoViewArgs& a, hipStream_t stream) {
+    if (a.n_pixels) hipLaunchKernelGGL(k_ao_view_points, dim3((a.n_pixels + 255u) / 256u), dim3(256), 0, stream, a);
+}
+// one single-wave workgroup per pool of the n K entries
+void launch_ao_walk(const AoWalkArgs& a, hipStream_t stream) {
+    const uint64_t total = (uint64_t)a.g.n * a.g.K;
+    if (total) hipLaunchKernelGGL(k_ao_walk, dim3((uint32_t)((total + a.pool - 1u) / a.pool)), dim3(64), stack_bytes(a.stack_entries), stream, a);
+}
+void launch_ao_fold(const AoGen& g, const uint32_t* vis, float4* out, hipStream_t stream) {
+    if (g.n) hipLaunchKernelGGL(k_ao_fold, dim3((g.n + 255u) / 256u), dim3(256), 0, stream, g, vis, out);
 }
 void launch_untile(const FrameArgs& f, const float* packed, float* linear, uint32_t grid, hipStream_t stream) {
     hipLaunchKernelGGL(k_untile, dim3(grid), dim3(256), 0, stream, f, packed, linear);

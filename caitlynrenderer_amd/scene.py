@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CRT_ABI_VERSION, CRT_ENV_HIDE_FROM_CAMERA, crt_environment, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params,
+from ._lib import (CRT_ABI_VERSION, CRT_ENV_HIDE_FROM_CAMERA, crt_environment, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params, crt_ao_params,
                    crt_scene_desc, crt_tree_cost, lib,
                    CRT_DISPLAY_AUTO_EXPOSURE, CRT_DISPLAY_CURVE_ACES, CRT_DISPLAY_CURVE_CLAMP, CRT_DISPLAY_CURVE_REFERENCE, CRT_DISPLAY_CURVE_REINHARD,
                    CRT_DISPLAY_SOURCE_DENOISED, CRT_DISPLAY_SOURCE_SUM, CRT_DISPLAY_SOURCE_TEMPORAL, crt_display_params, crt_display_state,
@@ -25,6 +25,16 @@ AOV_IDS_DT = np.dtype([("instance", "<i4"), ("mesh", "<i4"), ("material", "<i4")
 # what Scene.read_aov returns per channel: (dtype, trailing shape behind (height, width))
 AOV_DTYPES = {AOV_HIT: (HIT_DT, ()), AOV_IDS: (AOV_IDS_DT, ()), AOV_NORMAL: (np.dtype("<f4"), (4,)), AOV_ALBEDO: (np.dtype("<f4"), (4,)),
               AOV_EMISSION: (np.dtype("<f4"), (4,))}
+# an AO point of ao_points / ao_points_device (include/crt.h at crt_render_ao): 32 bytes, laid out like RAY_DT
+AO_POINT_DT = np.dtype([("p", "<f4", 3), ("seed_x", "<f4"), ("n", "<f4", 3), ("seed_y", "<f4")])
+
+
+def _ao_params(samples, radius, offset):
+    p = crt_ao_params()
+    p.samples, p.flags = int(samples), 0
+    p.radius = float(np.float32(1e9 if radius is None else radius))
+    p.offset = float(np.float32(offset))
+    return p
 
 
 class SceneData:
@@ -215,6 +225,42 @@ class Scene:
         ptr = C.c_void_p()
         check(lib().crt_aov_device(self._h, int(channel), C.byref(ptr)))
         return ptr.value
+
+    def render_ao(self, rx=0.0, ry=0.0, samples=16, radius=None, offset=2e-4, sync=True):
+        """crt_render_ao: ambient occlusion at the first hits of the current view, `samples` cosine-distributed rays per pixel of length
+        `radius` (None = unbounded), built on the device where they are walked.  Touches nothing a frame or render_aov reads or reports
+        (DESIGN.md §32)."""
+        p = _ao_params(samples, radius, offset)
+        check(lib().crt_render_ao(self._h, float(np.float32(rx)), float(np.float32(ry)), C.byref(p), 1 if sync else 0))
+
+    def read_ao(self):
+        """crt_read_ao: (height, width, 4) float32, rows as read_sum has them: the sum of the unoccluded directions (normalise it for a
+        bent normal) and the unoccluded share; a miss pixel holds (0, 0, 0, -1)"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        check(lib().crt_read_ao(self._h, _ptr(out), out.size))
+        return out
+
+    def ao_device(self):
+        """crt_ao_device: device pointer (int) of render_ao's image, width * height * 16 bytes, valid until the scene is closed"""
+        ptr = C.c_void_p()
+        check(lib().crt_ao_device(self._h, C.byref(ptr)))
+        return ptr.value
+
+    def ao_points(self, points, rx=0.0, ry=0.0, samples=16, radius=None, offset=2e-4):
+        """crt_ao_points: ambient occlusion at the caller's points (an AO_POINT_DT array); returns (n, 4) float32, the bytes render_ao
+        gives for the same points"""
+        pts = np.ascontiguousarray(points, AO_POINT_DT).reshape(-1)
+        out = np.empty((pts.shape[0], 4), np.float32)
+        p = _ao_params(samples, radius, offset)
+        check(lib().crt_ao_points(self._h, _ptr(pts) if pts.shape[0] else None, pts.shape[0], float(np.float32(rx)), float(np.float32(ry)), C.byref(p),
+                                  _ptr(out) if pts.shape[0] else None))
+        return out
+
+    def ao_points_device(self, d_points, n, d_out, rx=0.0, ry=0.0, samples=16, radius=None, offset=2e-4, sync=True):
+        """crt_ao_points_device: the same with device pointers (ints): n AO points of 32 bytes in, n float4 out"""
+        p = _ao_params(samples, radius, offset)
+        check(lib().crt_ao_points_device(self._h, C.c_void_p(d_points), int(n), float(np.float32(rx)), float(np.float32(ry)), C.byref(p),
+                                         C.c_void_p(d_out), 1 if sync else 0))
 
     def denoise(self, inv_count=None, passes=5, demodulate=True, sigma_color=4.0, sigma_depth=0.05, normal_power_log2=7, sync=True):
         """crt_denoise: an edge-avoiding a-trous filter over the running sum, guided by the HIT, IDS, NORMAL and ALBEDO channels of the most
@@ -594,6 +640,6 @@ class Scene:
             pass
 
 
-__all__ = ["Scene", "SceneData", "Camera", "Mesh", "SBVH", "CWBVH", "RAY_DT", "HIT_DT", "STATS_DT", "AOV_IDS_DT", "AOV_DTYPES",
+__all__ = ["Scene", "SceneData", "Camera", "Mesh", "SBVH", "CWBVH", "RAY_DT", "HIT_DT", "STATS_DT", "AO_POINT_DT", "AOV_IDS_DT", "AOV_DTYPES",
            "AOV_HIT", "AOV_IDS", "AOV_NORMAL", "AOV_ALBEDO", "AOV_EMISSION", "AOV_ALL",
            "CRT_TRACE_CLOSEST", "CRT_TRACE_ANY", "CRT_BUILD_LBVH_ON_DEVICE"]

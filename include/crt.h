@@ -389,6 +389,60 @@ int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync
 int crt_read_aov(crt_scene* s, uint32_t channel, void* dst, size_t n_bytes);
 int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr);
 
+/* Ambient occlusion of the scene's current view, or of points the caller names, flat and instanced scenes (no reference counterpart;
+ * DESIGN.md §32): how open a surface point is to its surroundings.  K cosine-distributed rays leave each point; the result is the share
+ * that escapes and the sum of the escaping directions (the caller normalises it for a bent normal).  The rays are built on the device where
+ * they are walked and never stored; the count is an integer, so the result is defined bit for bit:
+ * every line below is ONE IEEE float32 operation in the written order under DESIGN.md §3 (no contraction); dot, normalize, the correctly
+ * rounded sqrt, pinned_sin and pinned_cos are the bounce sampler's.  F(x) = x rounded to float32.
+ *
+ * An AO POINT is crt_ao_point: (p[3], seed_x, n[3], seed_y), 32 bytes, laid out like crt_ray.  crt_ao_params: samples K in 1..256; radius
+ * finite and > 0, 1e9f meaning "unbounded" as the integrator's tmax; offset finite and >= 0 (0.0002f is the integrator's hit-point offset);
+ * flags = 0; reserved = 0.  NULL params mean {16, 0, 1e9f, 0.0002f}.  rv = rx * ry, as in a frame.  Per point:
+ *   1. Normal.  l2 = dot(n, n).  If l2 is not > 0, or l2 or any component of p is not finite, the result is (0, 0, 0, -1) and no ray is
+ *      traced.  Otherwise nn = n * (1 / sqrt(l2)).
+ *   2. Origin.  o = p + nn * offset, per component F(p.k + F(nn.k * offset)).
+ *   3. Basis, a correct Frisvad basis (NOT the integrator's onb(), which keeps path_trace.fs:56-57 as the reference wrote them):
+ *      if nn.z < -0.9999999f: bu = (0, -1, 0), bv = (-1, 0, 0); otherwise a = 1 / (1 + nn.z); b = (-nn.x * nn.y) * a;
+ *      bu = (1 - (nn.x*nn.x)*a, b, -nn.x); bv = (b, 1 - (nn.y*nn.y)*a, -nn.y).
+ *   4. Random numbers, by index.  rand_at(j), j = 1, 2, ...: ax = seed_x - F(F(j) * rv); ay = seed_y - F(F(j) * rv);
+ *      d = F(ax*12.9898f) + F(ay*78.233f); v = pinned_sin(d) * 43758.5453f; the value is v - floor(v).  j = 1 is the shader's first draw
+ *      from that seed.  Sample k (0-based) uses u1 = rand_at(2k+1) and u2 = rand_at(2k+2).
+ *   5. Direction.  r = sqrt(u1); phi = 6.2831853f * u2; sx = r*cos(phi); sy = r*sin(phi); sz = sqrt(1 - u1);
+ *      sd = (bu*sx + bv*sy) + nn*sz.  Ray k is crt_ray{o, tmax = radius, d = sd}.
+ *   6. Occlusion.  Ray k is occluded iff crt_trace(.., CRT_TRACE_ANY) reports a hit for that crt_ray; an instanced scene:
+ *      crt_instances_trace(.., CRT_TRACE_ANY) on the scene's handle as it is at enqueue, with option "instance_masks" 1
+ *      | CRT_TRACE_INSTANCE_MASK with the ray mask "mask_shadow".
+ *   7. Result.  V = the number of unoccluded rays.  b = (+0, +0, +0); for k = 0 .. K-1 in that order, b = b + sd_k for each unoccluded k.
+ *      The output float[4] is (b.x, b.y, b.z, F(V) / F(K)).
+ *
+ * VIEW MODE, crt_render_ao(s, rx, ry, params, sync): the points are the first hits of crt_render_aov(s, rx, ry, ..): the same rays (the
+ * scene's camera, the "jitter" option, the pinhole through `position` whatever the aperture, the masked walk with "mask_primary" where that
+ * applies); p = o_cam + d * t per component F(o.k + F(d.k * t)), in world space; n = the NORMAL channel's value (face-forwarded, through
+ * the instance's transform, not normalised); (seed_x, seed_y) = the pixel's RNG state BEHIND the primary ray's draws: the pixel centre
+ * (px + 0.5, py + 0.5) with "jitter" 0, the state after the two jitter draws with "jitter" 1.  A miss pixel holds (0, 0, 0, -1).  The image
+ * is width*height float[4] in linear pixel order, rows as crt_read_sum has them, allocated by the first call and freed with the scene.
+ * POINTS MODE, crt_ao_points (host pointers; returns when `out`, n x float[4], is written) and crt_ao_points_device (device pointers):
+ * the same bytes as view mode gives for the same points.  n = 0 succeeds and writes nothing.
+ * crt_read_ao wants n_floats = width*height*4.  crt_ao_device waits for the stream; the pointer stays valid until the scene is destroyed.
+ *
+ * The calls are enqueued on the scene's stream behind any *_async frames (sync = 0 returns at once); later frames and reads are ordered
+ * behind them.  The sum, the frame count, crt_get_frame_stats, the launch times, every AOV channel and every frame's path and RNG state stay as
+ * they are.  An instanced scene reads its handle's live arrays at enqueue.  An environment changes nothing.
+ * CRT_ERR_INVALID, crt_last_error names the field, nothing written and an earlier AO image untouched: a null scene; a null points or out
+ * pointer with n > 0; samples outside 1..256; a radius not finite or <= 0; an offset not finite or < 0; flags or reserved not 0; n * K or
+ * width*height*K >= 2^32; option "accel" not 0; a shard of a frame (crt_set_shard with world > 1); a scene on several devices or streams
+ * (crt_set_devices, option "streams"); crt_read_ao / crt_ao_device before any crt_render_ao, or n_floats of another size.
+ * Out of scope: accumulating AO over calls (the caller averages); AO as a source of crt_denoise / crt_temporal / crt_display; lens-aware
+ * points; shards and several devices; distance falloff; any AO in the C oracle. */
+typedef struct crt_ao_point { float p[3]; float seed_x; float n[3]; float seed_y; } crt_ao_point;
+typedef struct crt_ao_params { uint32_t samples; uint32_t flags; float radius; float offset; uint32_t reserved[4]; } crt_ao_params;
+int crt_render_ao(crt_scene* s, float rx, float ry, const crt_ao_params* params, int sync);
+int crt_read_ao(crt_scene* s, float* dst, size_t n_floats);
+int crt_ao_device(crt_scene* s, const float** d_ptr);
+int crt_ao_points(crt_scene* s, const crt_ao_point* points, size_t n, float rx, float ry, const crt_ao_params* params, float* out);
+int crt_ao_points_device(crt_scene* s, const void* d_points, size_t n, float rx, float ry, const crt_ao_params* params, void* d_out, int sync);
+
 /* Denoise a low-sample frame on the device, guided by the feature buffers (no reference counterpart): an edge-avoiding
  * a-trous wavelet filter over the scene's running sum, flat and instanced scenes.  Inputs: the sum, un-tiled as crt_sum_device has it and
  * scaled by inv_count, and the channels HIT, IDS, NORMAL and ALBEDO as the most recent crt_render_aov left them.  Keeping those channels in
