@@ -1,6 +1,6 @@
 // struct crt_scene and the state structs it points to, shared by the translation units behind the device half of include/crt.h:
-// crt_device.cpp (creation, options, several GPUs, refit / rebuild), crt_frames.cpp (frame dispatch) and crt_outputs.cpp (everything that
-// leaves as an image).
+// crt_create.cpp (creation), crt_device.cpp (options, several GPUs, refit / rebuild), crt_frames.cpp (frame dispatch) and crt_outputs.cpp
+// (everything that leaves as an image).
 // Private to csrc/: not installed, include/crt.h knows crt_scene by name only, and nothing declared here is exported by the library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -212,6 +212,16 @@ struct SceneLights {
         for (void* p : bufs) if (p) (void)hipFree(p);
     }
 };
+
+// The scene-level device buffers a replica shares (same GPU: crt_set_devices with a device listed again, option "streams") or copies
+// (another GPU).  crt_scene::shared_slot gives the pointer member of each, shared_bytes its size.  A slot takes part when its pointer is
+// non-null: a flat scene's creators fill nodes .. lights always (an array of no elements, such as the normals of a mesh without any, still
+// gets a small allocation: its pointer is non-null, its size 0, and a replica on another GPU allocates 16 bytes of its own), texcoords and
+// textures with textures, bvh2 and tris2 with a BVH2, planes at the first CWBVH frame (ensure_planes).  That is exactly the set the
+// creators used to list by hand, and each size is written where the buffer is allocated.  An instanced scene never replicates and leaves
+// every size 0.
+enum SharedBuf { kSharedNodes, kSharedPlanes, kSharedTris, kSharedTriangles, kSharedNormals, kSharedMaterials, kSharedLights, kSharedTexcoords,
+                 kSharedTextures, kSharedBvh2, kSharedTris2, kSharedBufs };
 
 struct crt_scene {
     int device = 0;
@@ -433,7 +443,24 @@ struct crt_scene {
     // crt_read_sum / crt_resolve gather their packed tile buffers to this device and un-tile the whole frame here.
     std::vector<crt_scene*> peers;           // owned
     crt_scene* primary = nullptr;            // set in a peer
-    std::vector<std::pair<size_t, size_t>> scene_bufs;   // (offset of the pointer member, bytes): what a replica needs copied
+    size_t shared_bytes[kSharedBufs] = {};   // the replica table (SharedBuf): bytes of each buffer as it stands, read by copies to another GPU
+    void** shared_slot(int k) {
+        switch (k) {
+            case kSharedNodes: return reinterpret_cast<void**>(&d_nodes);
+            case kSharedPlanes: return reinterpret_cast<void**>(&d_planes);
+            case kSharedTris: return reinterpret_cast<void**>(&d_tris);
+            case kSharedTriangles: return reinterpret_cast<void**>(&d_triangles);
+            case kSharedNormals: return reinterpret_cast<void**>(&d_normals);
+            case kSharedMaterials: return reinterpret_cast<void**>(&d_materials);
+            case kSharedLights: return reinterpret_cast<void**>(&d_lights);
+            case kSharedTexcoords: return reinterpret_cast<void**>(&d_texcoords);
+            case kSharedTextures: return reinterpret_cast<void**>(&d_textures);
+            case kSharedBvh2: return reinterpret_cast<void**>(&d_bvh2);
+            case kSharedTris2: return reinterpret_cast<void**>(&d_tris2);
+        }
+        return nullptr;
+    }
+    void* shared_ptr(int k) const { return *const_cast<crt_scene*>(this)->shared_slot(k); }
     uint32_t shard_rank = 0, shard_world = 1; // the caller's shard of the frame (crt_set_shard); rank / world below are this stream's share of it
     uint32_t streams = 1;                    // option "streams": this many tile shards of the frame on streams of their own, on this one GPU
     bool shares_scene = false;               // a replica on its primary's own device: the scene buffers are the primary's, not copies
@@ -461,7 +488,7 @@ struct crt_scene {
         delete bloom;
         delete ao;
         if (shares_scene)                   // borrowed from the primary, which frees them
-            for (const auto& b : scene_bufs) *reinterpret_cast<void**>(reinterpret_cast<char*>(this) + b.first) = nullptr;
+            for (int k = 0; k < kSharedBufs; ++k) *shared_slot(k) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
                         d_rays[0], d_rays[1], d_rays_lens, d_env, d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
                         d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins, d_mesh_base, d_qinst, d_mesh_mtl, d_tex_before};
@@ -521,9 +548,29 @@ struct crt_scene {
     }
 };
 
-// What crosses between the three translation units
+// What crosses between the translation units
 namespace crt {
+// crt_create.cpp
+bool light_finite(const crt_light& l);   // every field of a light is finite
+// what a create and a replica both end with: nodes and records at the traversal's strides, the overflow word, the counter banks, the spans
+int finish_scene_setup(crt_scene* s);
+void adopt_tree(crt_scene* s, DeviceTree& t);     // publishes a built tree into the scene (create on the device, rebuild); cannot fail
+// The traversal's copies of nodes and records at the build's stride (CRT_NODE_ROWS / CRT_TRI_ROWS): packed input -> padded copy.
+template <typename T>
+int pad_rows(hipStream_t st, const char* who, T** buf, uint32_t rows_in, uint32_t rows_out, size_t n_items) {
+    if (rows_in == rows_out || !*buf) return CRT_OK;
+    T* padded = nullptr;
+    int rc = dev_alloc(&padded, n_items * rows_out);
+    if (rc) return rc;
+    launch_restride(*buf, rows_in, padded, rows_out, n_items, st);
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { (void)hipFree(padded); return fail(CRT_ERR_HIP, std::string(who) + "re-striding failed"); }
+    (void)hipFree(*buf);
+    *buf = padded;
+    return CRT_OK;
+}
 // crt_device.cpp
+void warm_start(int device);             // the library's code objects start loading on `device` in the background, once per device (crt_warmup's Warmer)
+int warm_wait();                         // waits for that load; its result (0 = fine)
 void deal_tiles(uint32_t width, uint32_t height, uint32_t T, uint32_t rank, uint32_t world, std::vector<uint2>& tiles, uint64_t* pixels_in_frame);
 crt::FrameArgs frame_args(const crt_scene* s, float rx, float ry);
 int ensure_planes(crt_scene* s);         // the nodes' child planes as floats, built in stream order before the first frame that walks the CWBVH

@@ -1,7 +1,7 @@
 // Scene assembly kernels of crt_scene_create's build-on-device path: the steps the host does with loops over the
 // triangle array for host-built scenes (index validation, re-ordering into leaf order, pre-gathered intersection
 // records), done where the builders left their output.  The record arithmetic is the same two fp32 subtractions per edge
-// as the host loop in crt_device.cpp (path_trace.fs:337-338), so the records are bit-identical to an uploaded scene's.
+// as the host loop in crt_create.cpp, intersection_records (path_trace.fs:337-338), so the records are bit-identical to an uploaded scene's.
 #include <hip/hip_runtime.h>
 
 #include "device_build.hpp"

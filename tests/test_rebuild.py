@@ -299,6 +299,37 @@ def test_g3_frames_after_a_rebuild_equal_a_fresh_scene_and_the_oracle(cr, ob, co
 
 
 @pytest.mark.gpu
+def test_g3_a_rebuild_before_the_first_frame_of_a_scene_with_two_streams(cr, cornell):
+    """the replica of option "streams" 2 has borrowed no planes when the tree is replaced: it borrows the new tree's at its first frame, and
+    lets go of every borrowed buffer when it goes"""
+    import torch
+    mesh, cam = cornell
+    moved = (mesh.vertices.astype(np.float64) * 0.9).astype(np.float32)
+
+    def run(streams):
+        sc = cr.Scene(cr.SceneData.for_device_build(mesh, cam, "sah"), 32, 24, 3)
+        sc.set_option("streams", streams)
+        sc.rebuild_vertices(moved)                                 # before any frame has walked the CWBVH
+        sc.render_frame(RX1, RY1)
+        out = sc.read_sum().copy()
+        assert sc.debug_launch_info()["shards"] == streams
+        sc.close()
+        return out
+
+    def in_use():
+        free, total = torch.cuda.mem_get_info()
+        return total - free
+    run(2), run(1)                                                 # what a process allocates once and keeps (code objects, the runtime's pools)
+    before = in_use()
+    two, one = run(2), run(1)
+    after = in_use()
+    print("device bytes in use before and after:", before, after)
+    assert one.max() > 0.1
+    assert np.array_equal(two.view(np.uint32), one.view(np.uint32))
+    assert after == before
+
+
+@pytest.mark.gpu
 def test_g4_a_sequence_of_updates_and_rebuilds(cr, cornell):
     import torch
     m0, m1 = _pair(cr, cornell)
