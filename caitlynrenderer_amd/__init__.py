@@ -7,7 +7,7 @@ SBVH / CWBVH interface plus tile sharding helpers.  Importing it without a built
 from . import _lib
 from ._lib import CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_CLOSEST, CRT_TRACE_INSTANCE_MASK, CRT_TRACE_TIE_LOWEST_ID, CrtError
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, pcg_hash
-from .scene import (AO_POINT_DT, AOV_ALBEDO, AOV_ALL, AOV_DTYPES, AOV_EMISSION, AOV_HIT, AOV_IDS, AOV_IDS_DT, AOV_NORMAL, HIT_DT, RAY_DT, STATS_DT, Scene,
+from .scene import (AO_POINT_DT, FOG_SEGMENT_DT, AOV_ALBEDO, AOV_ALL, AOV_DTYPES, AOV_EMISSION, AOV_HIT, AOV_IDS, AOV_IDS_DT, AOV_NORMAL, HIT_DT, RAY_DT, STATS_DT, Scene,
                     SceneData)
 from .deform import Deformer, deform_host, normal_influences
 from .environment import constant_environment, octahedral_directions, octahedral_from_equirect, octahedral_from_function
@@ -30,4 +30,4 @@ def warmup():
 __all__ = ["has_experiments", "warmup", "constant_environment", "octahedral_directions", "octahedral_from_equirect", "octahedral_from_function", "Scene", "SceneData", "Deformer", "deform_host", "normal_influences", "InstancedScene", "INSTANCE_DT", "instances_array", "instance_inverse",
            "instance_world_box", "instance_lights", "lights_finish", "set_mesh_lights", "read_lights", "Camera", "Mesh", "SBVH", "CWBVH", "Rnd", "pcg_hash", "CrtError",
            "RAY_DT", "HIT_DT", "STATS_DT", "CRT_TRACE_CLOSEST", "CRT_TRACE_ANY", "CRT_TRACE_BVH2", "CRT_TRACE_TIE_LOWEST_ID",
-           "CRT_TRACE_INSTANCE_MASK", "AOV_HIT", "AOV_IDS", "AOV_NORMAL", "AOV_ALBEDO", "AOV_EMISSION", "AOV_ALL", "AOV_IDS_DT", "AOV_DTYPES", "AO_POINT_DT"]
+           "CRT_TRACE_INSTANCE_MASK", "AOV_HIT", "AOV_IDS", "AOV_NORMAL", "AOV_ALBEDO", "AOV_EMISSION", "AOV_ALL", "AOV_IDS_DT", "AOV_DTYPES", "AO_POINT_DT", "FOG_SEGMENT_DT"]

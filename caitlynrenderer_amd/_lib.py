@@ -139,6 +139,12 @@ class crt_ao_params(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_float), ("offset", C.c_float), ("reserved", C.c_uint32 * 4)]
 
 
+class crt_fog_params(C.Structure):
+    # struct crt_fog_params (64 bytes): samples, density, albedo, anisotropy, range and ambient term of the fog entries
+    _fields_ = [("samples", C.c_uint32), ("flags", C.c_uint32), ("density", C.c_float), ("albedo", C.c_float * 3), ("anisotropy", C.c_float),
+                ("max_distance", C.c_float), ("ambient", C.c_float * 3), ("reserved", C.c_uint32 * 5)]
+
+
 class crt_denoise_params(C.Structure):
     # struct crt_denoise_params (32 bytes): crt_denoise's filter settings
     _fields_ = [("passes", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float),
@@ -231,6 +237,15 @@ SYMBOLS = {
     "crt_resolve_bloom": (_I, [_P, _P, _SZ]),
     "crt_resolve_bloom_device": (_I, [_P, C.POINTER(_P), _I]),
     "crt_display_bloom": (_I, [_P, C.POINTER(crt_display_params), _I]),
+    "crt_render_fog": (_I, [_P, _F, _F, C.POINTER(crt_fog_params), _I]),
+    "crt_read_fog": (_I, [_P, _P, _SZ]),
+    "crt_fog_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_fog_segments": (_I, [_P, _P, _SZ, _F, _F, C.POINTER(crt_fog_params), _P]),
+    "crt_fog_segments_device": (_I, [_P, _P, _SZ, _F, _F, C.POINTER(crt_fog_params), _P, _I]),
+    "crt_fog_composite": (_I, [_P, _F, _U32, _I]),
+    "crt_read_fogged": (_I, [_P, _P, _SZ]),
+    "crt_fogged_device": (_I, [_P, C.POINTER(_P)]),
+    "crt_display_fogged": (_I, [_P, C.POINTER(crt_display_params), _I]),
     "crt_get_launch_times": (_I, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "crt_update_vertices": (_I, [_P, _P, _SZ, _P, _SZ, _P, _SZ]),
     "crt_update_vertices_device": (_I, [_P, _P, _SZ, _I]),

@@ -83,18 +83,9 @@ __device__ __forceinline__ bool ao_frame(const AoGen& g, uint32_t point, AoFrame
     return true;
 }
 
-// step 4: the j-th draw (j = 1, 2, ...) of the shader's RNG from the point's seed, by index
-__device__ __forceinline__ float ao_rand_at(const AoFrame& fr, uint32_t j, float rv) {
-    const float s = (float)j * rv;
-    const float ax = fr.seed_x - s, ay = fr.seed_y - s;
-    const float d = ax * 12.9898f + ay * 78.233f;
-    const float v = pinned_sin(d) * 43758.5453f;
-    return v - __builtin_floorf(v);
-}
-
 // step 5: the direction of sample k
 __device__ __forceinline__ vec3 ao_direction(const AoFrame& fr, uint32_t k, float rv) {
-    const float u1 = ao_rand_at(fr, 2u * k + 1u, rv), u2 = ao_rand_at(fr, 2u * k + 2u, rv);
+    const float u1 = rand_at(fr.seed_x, fr.seed_y, 2u * k + 1u, rv), u2 = rand_at(fr.seed_x, fr.seed_y, 2u * k + 2u, rv);      // step 4
     const float r = sqrt_ieee(u1);
     const float phi = 6.2831853f * u2;
     const float sx = r * pinned_cos(phi), sy = r * pinned_sin(phi), sz = sqrt_ieee(1.0f - u1);

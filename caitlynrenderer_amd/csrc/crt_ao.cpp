@@ -1,7 +1,7 @@
 // Ambient occlusion (include/crt.h at crt_render_ao): the entries, their buffers and the chain of launches.  Both modes end in
 // the same three steps over a buffer of AO points — visibility words cleared, the any-hit walk that builds its rays where it loads them
 // (k_ao_walk, k_ao_walk_instances), the fold (k_ao_fold) — and view mode puts two in front: the first hits of the view through the feature
-// buffers' own kernels into HIT and NORMAL buffers that belong to the AO state, and k_ao_view_points.  Nothing a frame or crt_render_aov
+// buffers' own kernels into HIT and NORMAL buffers that belong to the AO state (first_hits.hpp), and k_ao_view_points.  Nothing a frame or crt_render_aov
 // reads or reports is written, beyond what crt_render_aov itself borrows of an instanced scene's frame (segment 0's queue, its hits, the path state).
 #include <cmath>
 #include <exception>
@@ -9,10 +9,12 @@
 
 #include "ao.hpp"
 #include "crt_scene.hpp"
+#include "first_hits.hpp"
 #include "instances.hpp"
 
 using crt::dev_alloc;
 using crt::fail;
+using crt::grow;
 
 namespace {
 
@@ -44,19 +46,6 @@ int ensure_state(crt_scene* s, const char* who) {
     if (s->ao) return CRT_OK;
     s->ao = new (std::nothrow) AoState;
     return s->ao ? CRT_OK : fail(CRT_ERR_NOMEM, std::string(who) + ": out of host memory");
-}
-
-template <typename T>
-int grow(crt_scene* s, T** p, size_t* cap, size_t need) {
-    if (*p && *cap >= need) return CRT_OK;
-    if (*p) {
-        HIPCHK(hipStreamSynchronize(s->stream));                          // an earlier call may still use the old one
-        (void)hipFree(*p); *p = nullptr; *cap = 0;
-    }
-    const int rc = dev_alloc(p, need);
-    if (rc) return rc;
-    *cap = need;
-    return CRT_OK;
 }
 
 // visibility words cleared, the walk, the fold: n points at d_points -> n results at d_out, on the scene's stream
@@ -96,67 +85,6 @@ int enqueue_points(crt_scene* s, const float4* d_points, uint32_t n, float rv, c
     return CRT_OK;
 }
 
-// the first hits of the view into the AO state's own HIT and NORMAL buffers: crt_render_aov's launches with another destination
-int enqueue_first_hits(crt_scene* s, float rx, float ry, uint32_t n_pixels) {
-    AoState* const ao = s->ao;
-    int rc;
-    crt::AovOut out{};
-    out.hit = ao->d_hit; out.normal = ao->d_normal;
-    const uint32_t channels = CRT_AOV_HIT | CRT_AOV_NORMAL;
-    if (s->inst) {
-        if ((rc = crt::ensure_frame(s))) return rc;
-        if ((rc = crt::ensure_queue_hits(s, true, true))) return rc;
-        if (!ao->d_count && (rc = dev_alloc(&ao->d_count, 8 * kCounterStride))) return rc;
-    } else if (!ao->d_tile_xy || ao->tile != s->tile) {
-        std::vector<uint2> tiles;
-        try { crt::deal_tiles(s->width, s->height, s->tile, 0u, 1u, tiles, nullptr); }
-        catch (const std::exception&) { return fail(CRT_ERR_NOMEM, "crt_render_ao: out of host memory (tile list)"); }
-        const uint64_t px = (uint64_t)tiles.size() * s->tile * s->tile;
-        if (px >= (1ull << 31)) return fail(CRT_ERR_LIMIT, "crt_render_ao: frame too large for 32-bit pixel indices");
-        HIPCHK(hipStreamSynchronize(s->stream));                          // an earlier call may still read the old list
-        if (ao->d_tile_xy) { (void)hipFree(ao->d_tile_xy); ao->d_tile_xy = nullptr; }
-        if ((rc = dev_alloc(&ao->d_tile_xy, tiles.size()))) return rc;
-        if (!tiles.empty()) HIPCHK(hipMemcpy(ao->d_tile_xy, tiles.data(), tiles.size() * sizeof(uint2), hipMemcpyHostToDevice));
-        ao->n_local_pixels = (uint32_t)px; ao->tile = s->tile;
-    }
-    crt::launch_aov_fill(out, channels, n_pixels, s->stream);
-    if (s->inst) {
-        if (s->n_local_pixels) {
-            crt::InstancesView v{};
-            crt::instances_view(s->inst, &v);
-            const bool masked = s->instance_masks != 0u;
-            if (masked && (rc = crt::instances_child_masks_for(s->inst, s->stream, &s->cmask_seen))) return rc;
-            HIPCHK(hipMemsetAsync(ao->d_count, 0, 8 * kCounterStride * sizeof(uint32_t), s->stream));
-            const crt::RaygenArgs ra = crt::raygen_args(s, crt::frame_args(s, rx, ry), s->d_rays[0], ao->d_count, false);
-            crt::launch_raygen(ra, s->stream);
-            crt::launch_closest_instances_queue(crt::inst_queue_args(s, v, s->d_rays[0], ao->d_count, s->mask_primary, nullptr), false, masked, s->stream);
-            crt::InstAovArgs a{};
-            a.triangles = s->d_triangles; a.normals = s->d_normals; a.materials = s->d_materials;
-            a.texcoords = s->d_texcoords; a.textures = s->d_textures;
-            a.tex_width = s->tex_width; a.tex_height = s->tex_height; a.n_textures = s->n_textures;
-            a.f = ra.f;
-            a.sub_capacity = s->sub_capacity;
-            a.rays_in = s->d_rays[0]; a.count_in = ao->d_count; a.hits_in = s->d_qhits;
-            a.hit_inst = s->d_qinst; a.inst_w2o = v.w2o; a.inst_mesh = v.mesh_of; a.mesh_base = s->d_mesh_base;
-            a.channels = channels; a.out = out;
-            crt::launch_aov_instanced(a, s->stream);
-        }
-    } else if (ao->n_local_pixels) {
-        crt::AovArgs a{};
-        a.nodes = s->d_nodes; a.tris = s->d_tris; a.triangles = s->d_triangles; a.normals = s->d_normals; a.materials = s->d_materials;
-        a.stack_entries = s->stack_entries;
-        a.texcoords = s->d_texcoords; a.textures = s->d_textures;
-        a.tex_width = s->tex_width; a.tex_height = s->tex_height; a.n_textures = s->n_textures;
-        a.f = crt::frame_args(s, rx, ry);
-        a.f.tile_xy = ao->d_tile_xy; a.f.tile_order = nullptr; a.f.n_local_pixels = ao->n_local_pixels;
-        a.overflow = s->d_overflow;
-        a.channels = channels; a.out = out;
-        crt::launch_aov(a, s->stream);
-    }
-    HIPCHK(hipGetLastError());
-    return CRT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -177,7 +105,9 @@ int crt_render_ao(crt_scene* s, float rx, float ry, const crt_ao_params* params,
     if (!ao->d_normal && (rc = dev_alloc(&ao->d_normal, n_pixels))) return rc;
     if (!ao->d_view_points && (rc = dev_alloc(&ao->d_view_points, 2 * n_pixels))) return rc;
     if (!ao->d_image && (rc = dev_alloc(&ao->d_image, n_pixels))) return rc;
-    if ((rc = enqueue_first_hits(s, rx, ry, (uint32_t)n_pixels))) return rc;
+    crt::AovOut out{};
+    out.hit = ao->d_hit; out.normal = ao->d_normal;
+    if ((rc = crt::enqueue_first_hits(s, out, CRT_AOV_HIT | CRT_AOV_NORMAL, &ao->first_hits, "crt_render_ao", rx, ry, (uint32_t)n_pixels))) return rc;
     crt::AoViewArgs va{};
     va.f = crt::frame_args(s, rx, ry);
     va.hit = ao->d_hit; va.normal = ao->d_normal; va.points = ao->d_view_points; va.n_pixels = (uint32_t)n_pixels;

@@ -1,5 +1,5 @@
 // Everything that leaves the library as an image (include/crt.h): the running sum, the first-hit feature buffers, the
-// denoised image (§22), the accumulated image (§23), the bloomed image (§30), and the RGBA8 of the four float images.  The four are described
+// denoised image (§22), the accumulated image (§23), the bloomed image (§30), the fogged image (§33), and the RGBA8 of the first four.  The five are described
 // once (Image) and read, exposed and resolved through one path each ("Where an image leaves"); crt_frames.cpp renders the frames these read.
 #include <cmath>
 #include <cstring>
@@ -11,6 +11,7 @@
 #include "crt_scene.hpp"
 #include "denoise.hpp"
 #include "display.hpp"
+#include "fog.hpp"
 #include "instances.hpp"
 
 using crt::dev_alloc;
@@ -106,9 +107,10 @@ const float* gamma_thresholds() {
     return thr;
 }
 
-// One of the four float images (width * height * 3, linear pixel order) and its RGBA8.  The running sum lives as packed tiles, on every
-// device of the scene: a read un-tiles (and gathers) it into d_linear first, a resolve tone-maps the tiles directly.  The other three are
-// what their call left on the stream, on a device that must be there, and exist only after such a call.
+// One of the five float images (width * height * 3, linear pixel order) and its RGBA8.  The running sum lives as packed tiles, on every
+// device of the scene: a read un-tiles (and gathers) it into d_linear first, a resolve tone-maps the tiles directly.  The other four are
+// what their call left on the stream, on a device that must be there, and exist only after such a call.  `rgba` is null for an image
+// without a resolve (the fogged image): no resolve entry names it.
 struct Image {
     bool packed;             // the running sum
     const char* refusal;     // null = it exists; else why not, as it follows the entry's name
@@ -132,6 +134,12 @@ Image bloom_image(crt_scene* s) {
     BloomState* const bl = s->bloom;
     if (!bl || !bl->valid) return {false, ": no crt_bloom call has succeeded on this scene", nullptr, nullptr};
     return {false, nullptr, &bl->d_out, &bl->d_rgba};
+}
+
+Image fogged_image(crt_scene* s) {       // it has no resolve, so no RGBA8 of its own
+    FogState* const fg = s->fog;
+    if (!fg || !fg->composited) return {false, ": no crt_fog_composite call has succeeded on this scene", nullptr, nullptr};
+    return {false, nullptr, &fg->d_fogged, nullptr};
 }
 
 int null_argument(const char* who) { return fail(CRT_ERR_INVALID, std::string(who) + ": null argument"); }
@@ -558,8 +566,9 @@ int no_display(const char* who) { return fail(CRT_ERR_INVALID, std::string(who) 
 
 }  // namespace
 
-// crt_display and crt_display_bloom: one body, `bloomed` names the image (crt_bloom's in place of the one params.source names)
-static int display_call(crt_scene* s, const char* who, bool bloomed, float inv_count, const crt_display_params* params, int sync) {
+// crt_display, crt_display_bloom and crt_display_fogged: one body, `input` names the image (a stage's in place of the one params.source names)
+enum class DisplayInput { SOURCE, BLOOMED, FOGGED };
+static int display_call(crt_scene* s, const char* who, DisplayInput input, float inv_count, const crt_display_params* params, int sync) {
     const auto bad = [who](const char* what) { return fail(CRT_ERR_INVALID, std::string(who) + what); };
     if (!s) return bad(": null scene");
     crt_display_params p{};
@@ -570,7 +579,8 @@ static int display_call(crt_scene* s, const char* who, bool bloomed, float inv_c
         p.low_permille = 0u; p.high_permille = 1000u;
     }
     if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return bad(": inv_count must be finite and > 0");
-    if (bloomed && p.source != 0u) return bad(": source must be 0 (the image is crt_bloom's)");
+    if (input == DisplayInput::BLOOMED && p.source != 0u) return bad(": source must be 0 (the image is crt_bloom's)");
+    if (input == DisplayInput::FOGGED && p.source != 0u) return bad(": source must be 0 (the image is crt_fog_composite's)");
     if (p.source > (uint32_t)CRT_DISPLAY_SOURCE_TEMPORAL) return bad(": source is CRT_DISPLAY_SOURCE_SUM, _DENOISED or _TEMPORAL");
     if (p.curve > (uint32_t)CRT_DISPLAY_CURVE_CLAMP) return bad(": curve is CRT_DISPLAY_CURVE_REFERENCE, _REINHARD, _ACES or _CLAMP");
     if (p.flags & ~(uint32_t)CRT_DISPLAY_AUTO_EXPOSURE) return bad(": unknown flag bits");
@@ -587,7 +597,7 @@ static int display_call(crt_scene* s, const char* who, bool bloomed, float inv_c
         if (p.high_permille > 1000u) return bad(": high_permille must be at most 1000");
         if (p.low_permille >= p.high_permille) return bad(": low_permille must be below high_permille");
     }
-    const Image im = bloomed ? bloom_image(s) : p.source == CRT_DISPLAY_SOURCE_SUM ? sum_image(s) : p.source == CRT_DISPLAY_SOURCE_DENOISED ? denoised_image(s) : temporal_image(s);
+    const Image im = input == DisplayInput::BLOOMED ? bloom_image(s) : input == DisplayInput::FOGGED ? fogged_image(s) : p.source == CRT_DISPLAY_SOURCE_SUM ? sum_image(s) : p.source == CRT_DISPLAY_SOURCE_DENOISED ? denoised_image(s) : temporal_image(s);
     int rc = begin_image(s, im, who);
     if (rc) return rc;
     const size_t npx = (size_t)s->width * s->height;
@@ -640,9 +650,11 @@ static int display_call(crt_scene* s, const char* who, bool bloomed, float inv_c
     return CRT_OK;
 }
 
-int crt_display(crt_scene* s, float inv_count, const crt_display_params* params, int sync) { return display_call(s, "crt_display", false, inv_count, params, sync); }
+int crt_display(crt_scene* s, float inv_count, const crt_display_params* params, int sync) { return display_call(s, "crt_display", DisplayInput::SOURCE, inv_count, params, sync); }
 // the bloomed image is a mean: there is no inv_count
-int crt_display_bloom(crt_scene* s, const crt_display_params* params, int sync) { return display_call(s, "crt_display_bloom", true, 1.0f, params, sync); }
+int crt_display_bloom(crt_scene* s, const crt_display_params* params, int sync) { return display_call(s, "crt_display_bloom", DisplayInput::BLOOMED, 1.0f, params, sync); }
+// so is the fogged image
+int crt_display_fogged(crt_scene* s, const crt_display_params* params, int sync) { return display_call(s, "crt_display_fogged", DisplayInput::FOGGED, 1.0f, params, sync); }
 
 int crt_read_display(crt_scene* s, uint8_t* rgba, size_t n_bytes) {
     if (!s || !rgba) return null_argument("crt_read_display");
@@ -777,3 +789,36 @@ int crt_bloom_device(crt_scene* s, const float** d_rgb) { return expose_image(s,
 // the bloomed image through crt_resolve's tone map and pinned gamma, into BloomState's own RGBA8
 int crt_resolve_bloom(crt_scene* s, uint8_t* rgba, size_t n_bytes) { return resolve_image_host(s, bloom_image, "crt_resolve_bloom", 1.0f, rgba, n_bytes); }
 int crt_resolve_bloom_device(crt_scene* s, const uint8_t** d_rgba, int sync) { return resolve_image_device(s, bloom_image, "crt_resolve_bloom_device", 1.0f, d_rgba, sync); }
+
+// ---------------------------------------------------------------- crt_fog_composite --
+// The fog of the view put on an image (k_fog_composite in rt_kernels.hip): enqueued on the scene's stream like crt_bloom.  It
+// reads the image it names and crt_render_fog's, and writes only the fogged image (and d_linear, which every crt_read_sum writes anew).
+
+int crt_fog_composite(crt_scene* s, float inv_count, uint32_t source, int sync) {
+    if (!s) return fail(CRT_ERR_INVALID, "crt_fog_composite: null scene");
+    if (!std::isfinite(inv_count) || !(inv_count > 0.f)) return fail(CRT_ERR_INVALID, "crt_fog_composite: inv_count must be finite and > 0");
+    if (source > (uint32_t)CRT_DISPLAY_SOURCE_TEMPORAL) return fail(CRT_ERR_INVALID, "crt_fog_composite: source is CRT_DISPLAY_SOURCE_SUM, _DENOISED or _TEMPORAL");
+    if (s->shard_world > 1u) return fail(CRT_ERR_INVALID, "crt_fog_composite: a whole frame only (crt_set_shard has world > 1)");
+    if (s->primary || !s->peers.empty()) return fail(CRT_ERR_INVALID, "crt_fog_composite: a scene on one device and one stream only (crt_set_devices / option streams have dealt this one's tiles)");
+    FogState* const fg = s->fog;
+    if (!fg || !fg->rendered) return fail(CRT_ERR_INVALID, "crt_fog_composite: no crt_render_fog call has succeeded on this scene");
+    const Image im = source == CRT_DISPLAY_SOURCE_SUM ? sum_image(s) : source == CRT_DISPLAY_SOURCE_DENOISED ? denoised_image(s) : temporal_image(s);
+    int rc = begin_image(s, im, "crt_fog_composite");
+    if (rc) return rc;
+    const size_t npx = (size_t)s->width * s->height;
+    if (npx >= (1ull << 31) / 3u) return fail(CRT_ERR_LIMIT, "crt_fog_composite: frame too large for 32-bit indices");
+    if (im.packed && (rc = ensure_frame(s))) return rc;
+    if (!fg->d_fogged && (rc = dev_alloc(&fg->d_fogged, 3 * npx))) return rc;
+    if (im.packed && (rc = untile_to_linear(s))) return rc;
+    crt::FogCompositeArgs a{};
+    a.image = *im.rgb; a.fog = fg->d_image; a.out = fg->d_fogged; a.n_pixels = (uint32_t)npx;
+    a.scale = im.packed ? 1u : 0u; a.inv_count = inv_count;
+    crt::launch_fog_composite(a, s->stream);
+    HIPCHK(hipGetLastError());
+    fg->composited = true;
+    if (sync) HIPCHK(hipStreamSynchronize(s->stream));
+    return CRT_OK;
+}
+
+int crt_read_fogged(crt_scene* s, float* rgb, size_t n_floats) { return read_image(s, fogged_image, "crt_read_fogged", rgb, n_floats); }
+int crt_fogged_device(crt_scene* s, const float** d_rgb) { return expose_image(s, fogged_image, "crt_fogged_device", d_rgb); }

@@ -124,6 +124,18 @@ struct BloomState {
     }
 };
 
+// What the first hits of a view into a stage's own buffers need beside their destination (first_hits.hpp), allocated by the first call
+// that needs it.
+struct FirstHitWork {
+    uint2* d_tile_xy = nullptr;          // flat scenes: the tiles of the whole frame, for k_aov
+    uint32_t n_local_pixels = 0, tile = 0;
+    uint32_t* d_count = nullptr;         // instanced scenes: the 8 counters of the primary rays' queue
+    ~FirstHitWork() {
+        if (d_tile_xy) (void)hipFree(d_tile_xy);
+        if (d_count) (void)hipFree(d_count);
+    }
+};
+
 // What the ambient-occlusion entries keep, each buffer allocated by the first call that needs it.  View mode: the first hits
 // of the view (HIT and NORMAL values in buffers of their own: crt_render_aov's channels stay as they are), the points made of them and the
 // image.  Both modes: the visibility words of the call in flight.  Points mode with host pointers: its upload and download buffers.
@@ -137,11 +149,31 @@ struct AoState {
     float4* d_points = nullptr;          // crt_ao_points: 2 rows per point
     float4* d_out = nullptr;
     size_t vis_cap = 0, points_cap = 0, out_cap = 0;
-    uint2* d_tile_xy = nullptr;          // flat scenes: the tiles of the whole frame, for k_aov
-    uint32_t n_local_pixels = 0, tile = 0;
-    uint32_t* d_count = nullptr;         // instanced scenes: the 8 counters of the primary rays' queue
+    FirstHitWork first_hits;
     ~AoState() {
-        void* bufs[] = {d_hit, d_normal, d_view_points, d_image, d_vis, d_points, d_out, d_tile_xy, d_count};
+        void* bufs[] = {d_hit, d_normal, d_view_points, d_image, d_vis, d_points, d_out};
+        for (void* p : bufs) if (p) (void)hipFree(p);
+    }
+};
+
+// What the fog entries keep, each buffer allocated by the first call that needs it.  View mode: the first hits of the view
+// (HIT values in a buffer of their own: crt_render_aov's channels stay as they are), the segments made of them and the image.  Both
+// modes: the visibility words of the call in flight.  Segments mode with host pointers: its upload and download buffers.  The composite:
+// the fogged image, the fifth float image of crt_outputs.cpp.
+struct FogState {
+    float4* d_hit = nullptr;             // width * height
+    float4* d_view_segments = nullptr;   // 2 rows per pixel
+    float4* d_image = nullptr;           // what crt_read_fog / crt_fog_device hand out
+    bool rendered = false;               // some crt_render_fog has been enqueued
+    uint32_t* d_vis = nullptr;           // n x ceil(K / 32) words
+    float4* d_segments = nullptr;        // crt_fog_segments: 2 rows per segment
+    float4* d_out = nullptr;
+    size_t vis_cap = 0, segments_cap = 0, out_cap = 0;
+    FirstHitWork first_hits;
+    float* d_fogged = nullptr;           // crt_fog_composite's image, width * height * 3
+    bool composited = false;             // some crt_fog_composite has been enqueued
+    ~FogState() {
+        void* bufs[] = {d_hit, d_view_segments, d_image, d_vis, d_segments, d_out, d_fogged};
         for (void* p : bufs) if (p) (void)hipFree(p);
     }
 };
@@ -267,6 +299,7 @@ struct crt_scene {
     DisplayState* display = nullptr;     // crt_display's buffers and exposure state, from the first call on
     BloomState* bloom = nullptr;         // crt_bloom's buffers, from the first call on
     AoState* ao = nullptr;               // the ambient-occlusion entries' buffers, from the first call on
+    FogState* fog = nullptr;             // the fog entries' buffers, from the first call on
     uint32_t temporal_form = 0;          // option "temporal_form": how a CLAMP call reads its neighbourhood: 0 = the form measured faster, 1 = staged, 2 = direct
     crt::TemporalView aov_view{};        // the view of the most recent crt_render_aov that rendered HIT, recorded at enqueue: crt_temporal's current view
     bool have_aov_view = false;
@@ -487,6 +520,7 @@ struct crt_scene {
         delete display;
         delete bloom;
         delete ao;
+        delete fog;
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (int k = 0; k < kSharedBufs; ++k) *shared_slot(k) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
@@ -566,6 +600,19 @@ int pad_rows(hipStream_t st, const char* who, T** buf, uint32_t rows_in, uint32_
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { (void)hipFree(padded); return fail(CRT_ERR_HIP, std::string(who) + "re-striding failed"); }
     (void)hipFree(*buf);
     *buf = padded;
+    return CRT_OK;
+}
+// A device buffer of a stage that follows the size of its calls: at least `need` items at *p, *cap what it holds.
+template <typename T>
+int grow(crt_scene* s, T** p, size_t* cap, size_t need) {
+    if (*p && *cap >= need) return CRT_OK;
+    if (*p) {
+        HIPCHK(hipStreamSynchronize(s->stream));                          // an earlier call may still use the old one
+        (void)hipFree(*p); *p = nullptr; *cap = 0;
+    }
+    const int rc = dev_alloc(p, need);
+    if (rc) return rc;
+    *cap = need;
     return CRT_OK;
 }
 // crt_device.cpp

@@ -10,6 +10,8 @@
 
 #define CRT_AO_DEVICE_MATH 1      // ao.hpp: the generator of the occlusion rays, in device code
 #include "ao.hpp"
+#define CRT_FOG_DEVICE_MATH 1     // fog.hpp: the generator of the fog's shadow rays, in device code
+#include "fog.hpp"
 #include "instances.hpp"
 #include "instances_walk.hpp"
 #include "rt_kernels.hpp"
@@ -333,6 +335,8 @@ __device__ __forceinline__ uint32_t launch_mask(const InstQueueArgs&) { return 0
 __device__ __forceinline__ uint32_t launch_mask(const InstShadowArgs&) { return 0u; }
 __device__ __forceinline__ uint32_t launch_mask(const InstMaskAoArgs& a) { return a.ray_mask; }
 __device__ __forceinline__ uint32_t launch_mask(const InstAoArgs&) { return 0u; }
+__device__ __forceinline__ uint32_t launch_mask(const InstMaskFogArgs& a) { return a.ray_mask; }
+__device__ __forceinline__ uint32_t launch_mask(const InstFogArgs&) { return 0u; }
 
 // Closest hits of a segment's path-ray queue: workgroup (g, c) = one wave walks entries [64 c, 64 c + 64) of sub-queue g, as far as its
 // device-side count goes; hits and hit instances go to buffers parallel to the queue, and k_segment<PRETRACED, INST> shades them.
@@ -420,6 +424,40 @@ __global__ void __launch_bounds__(64) k_ao_walk_instances(std::conditional_t<MAS
                 }                                                                          \
             }
 #define CRT_WALK_DONE(idx, h, hit, inst, nn, nt) (void)(nn); (void)(nt); if (!hit) ao_mark_visible(a.g, a.vis, idx);
+#define CRT_WALK_MASK(lane_mask) ((void)(lane_mask), launch_mask(a))
+#include "instances_walk_loop.hpp"
+#undef CRT_WALK_LOAD
+#undef CRT_WALK_DONE
+#undef CRT_WALK_MASK
+}
+
+// The shadow rays of an instanced scene's fog (fog.hpp): k_ao_walk_instances' form over the index space [0, n K); the ray
+// of an entry is built where it is loaded and never stored, an UNoccluded ray sets its bit of its segment's visibility words.  An entry
+// without a ray (a dark sample, a segment without rays) loads a ray whose origin is not finite, which the walk finishes as a miss at once:
+// the fold never counts its bit.  MASK: the walk culls by a.ray_mask (the scene's "mask_shadow").
+template <bool MASK>
+__global__ void __launch_bounds__(64) k_fog_walk_instances(std::conditional_t<MASK, InstMaskFogArgs, InstFogArgs> a) {
+    extern __shared__ uint2 s_lds[];
+    constexpr bool ANY = true, STATS = false;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t total = a.g.n * a.g.K;
+    const uint64_t first64 = (uint64_t)blockIdx.x * 64u;
+    if (first64 >= total) return;
+    uint32_t next = (uint32_t)first64;
+    const uint32_t end = total - next < 64u ? total : next + 64u;
+    uint2* const stk = s_lds + lane;
+    const int stack_entries = (int)a.stack_entries;
+#define CRT_WALK_LOAD(idx, r0, r1)                                                         \
+            float4 r0 = make_float4(__builtin_nanf(""), 0.f, 0.f, 0.f), r1 = make_float4(0.f, 0.f, 1.f, 0.f); \
+            {                                                                              \
+                vec3 fog_o, fog_d;                                                         \
+                float fog_tmax;                                                            \
+                if (fog_ray(a.g, idx, fog_o, fog_d, fog_tmax)) {                           \
+                    r0 = make_float4(fog_o.x, fog_o.y, fog_o.z, fog_tmax);                 \
+                    r1 = make_float4(fog_d.x, fog_d.y, fog_d.z, 0.f);                      \
+                }                                                                          \
+            }
+#define CRT_WALK_DONE(idx, h, hit, inst, nn, nt) (void)(nn); (void)(nt); if (!hit) fog_mark_visible(a.g, a.vis, idx);
 #define CRT_WALK_MASK(lane_mask) ((void)(lane_mask), launch_mask(a))
 #include "instances_walk_loop.hpp"
 #undef CRT_WALK_LOAD
@@ -524,6 +562,16 @@ void launch_shadow_instances_deferred(const InstMaskShadowArgs& a, bool stats, b
         if (stats) hipLaunchKernelGGL((k_shadow_instances_deferred<true, false>), g, b, lds, stream, u);
         else       hipLaunchKernelGGL((k_shadow_instances_deferred<false, false>), g, b, lds, stream, u);
     }
+}
+
+void launch_fog_walk_instances(const InstMaskFogArgs& a, bool mask, hipStream_t stream) {
+    const uint64_t total = (uint64_t)a.g.n * a.g.K;
+    if (!total) return;
+    const dim3 g((uint32_t)((total + 63u) / 64u)), b(64);
+    const size_t lds = (size_t)a.stack_entries * 64 * sizeof(uint2);
+    const InstFogArgs& u = a;
+    if (mask) hipLaunchKernelGGL((k_fog_walk_instances<true>), g, b, lds, stream, a);
+    else      hipLaunchKernelGGL((k_fog_walk_instances<false>), g, b, lds, stream, u);
 }
 
 void launch_ao_walk_instances(const InstMaskAoArgs& a, bool mask, hipStream_t stream) {

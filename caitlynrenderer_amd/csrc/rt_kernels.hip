@@ -18,6 +18,8 @@
 
 #define CRT_AO_DEVICE_MATH 1      // ao.hpp: the generator of the occlusion rays, in device code
 #include "ao.hpp"
+#define CRT_FOG_DEVICE_MATH 1     // fog.hpp: the generator of the fog's shadow rays, in device code
+#include "fog.hpp"
 #include "rt_kernels.hpp"
 #include "rt_math.hpp"
 #include "host/flatnode_link.hpp"
@@ -2369,6 +2371,80 @@ __global__ void __launch_bounds__(256) k_ao_fold(AoGen g, const uint32_t* __rest
     out[i] = make_float4(b.x, b.y, b.z, __fdiv_rn((float)V, (float)g.K));
 }
 
+// ------------------------------------------------------------------ fog with light shafts (include/crt.h at crt_render_fog) ----
+// Kernels of their own behind ambient occlusion's: no existing kernel's text or argument block moves.
+
+// The fog segments of a view: one lane per pixel of the frame in linear order.  The first hit is what k_aov / k_aov_instanced left in the
+// fog state's own HIT buffer; the primary ray is formed again (primary_ray: the same lines, the same bits) for its origin, its direction
+// and the RNG state behind its jitter draws.  A miss pixel marches to max_distance like any other.
+__global__ void __launch_bounds__(256) k_fog_view_segments(FogViewArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_pixels) return;
+    const uint32_t py = i / a.f.width, px = i - py * a.f.width;
+    float sx, sy;
+    vec3 o, d;
+    primary_ray(a.f, px, py, a.f.rv, sx, sy, o, d);
+    const float4 h = a.hit[i];
+    const float t = __float_as_int(h.w) >= 0 ? h.x : 1e9f;
+    const float Dv = t < a.max_distance ? t : a.max_distance;
+    const vec3 e = d * Dv;
+    a.segments[2 * (size_t)i] = make_float4(o.x, o.y, o.z, sx);
+    a.segments[2 * (size_t)i + 1] = make_float4(e.x, e.y, e.z, sy);
+}
+
+// The shadow rays of a flat scene's fog: k_ao_walk's form (k_shadow_deferred's walk_pool<ANY>, single-wave workgroups, its stack, occupancy
+// bound and eight-lanes-per-ray drain) over the index space [0, n K) in pools of a.pool entries.  `load` builds ray e in registers; `done`
+// sets the bit of an UNoccluded ray.  An entry without a ray (a dark sample, a segment without rays) loads as an empty slot, which the
+// same iteration finishes as a miss: the fold never counts its bit.
+__global__ void __launch_bounds__(64, CRT_SHADOW_OCC) k_fog_walk(FogWalkArgs a) {
+    extern __shared__ uint2 s_lds[];
+    const uint32_t total = a.g.n * a.g.K;
+    const uint64_t first64 = (uint64_t)blockIdx.x * a.pool;
+    if (first64 >= total) return;
+    const uint32_t first = (uint32_t)first64, last = total - first < a.pool ? total : first + a.pool;
+    uint32_t nn = 0, nt = 0, wn = 0, wt = 0;
+    auto load = [&](uint32_t e, vec3& o, vec3& d, float& tmax) {
+        tmax = 0.f;
+        return fog_ray(a.g, e, o, d, tmax);
+    };
+    auto done = [&](uint32_t e, const HitState&, bool occluded) { if (!occluded) fog_mark_visible(a.g, a.vis, e); };
+    walk_pool<true, false>(a.nodes, a.tris, s_lds, (int)a.stack_entries, a.overflow, PoolStatic{first, last}, a.refill_min, a.tri_min, a.lanes_log2, load, done,
+                           nn, nt, wn, wt);
+}
+
+// Steps 2, 6 and 7, one lane per segment: b = the ambient term, then the contributions of the set bits in j order (each sample formed
+// again from the segment: the same lines as the walk's), the result (b, TD); a segment without rays gives (0, 0, 0, -1).
+__global__ void __launch_bounds__(256) k_fog_fold(FogGen g, const uint32_t* __restrict__ vis, float4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.n) return;
+    FogFrame fr;
+    if (!fog_frame(g, i, fr)) { out[i] = make_float4(0.f, 0.f, 0.f, -1.0f); return; }
+    const float TD = exp_neg(g.sigma * fr.D);
+    const float away = 1.0f - TD;
+    vec3 b = V3((g.ambient[0] * g.albedo[0]) * away, (g.ambient[1] * g.albedo[1]) * away, (g.ambient[2] * g.albedo[2]) * away);
+    for (uint32_t w = 0; w < g.words; ++w) {
+        uint32_t bits = vis[(size_t)i * g.words + w];
+        while (bits) {
+            const uint32_t j = 32u * w + (uint32_t)__builtin_ctz(bits);
+            bits &= bits - 1u;
+            FogSample sm;
+            if (j < g.K && fog_sample(g, fr, j, sm)) b = b + fog_contribution(g, fr, sm);
+        }
+    }
+    out[i] = make_float4(b.x, b.y, b.z, TD);
+}
+
+// The composite, one lane per pixel: out = c * TD + S; a pixel without a segment (fog word 3 = -1) keeps c.
+__global__ void __launch_bounds__(256) k_fog_composite(FogCompositeArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_pixels) return;
+    float c0 = a.image[3 * (size_t)i], c1 = a.image[3 * (size_t)i + 1], c2 = a.image[3 * (size_t)i + 2];
+    if (a.scale) { c0 = c0 * a.inv_count; c1 = c1 * a.inv_count; c2 = c2 * a.inv_count; }
+    const float4 f = a.fog[i];
+    if (f.w != -1.0f) { c0 = c0 * f.w + f.x; c1 = c1 * f.w + f.y; c2 = c2 * f.w + f.z; }
+    a.out[3 * (size_t)i] = c0; a.out[3 * (size_t)i + 1] = c1; a.out[3 * (size_t)i + 2] = c2;
+}
+
 // ------------------------------------------------------------------ launchers --------
 
 // Timing events ride on the dispatch itself (hipExtLaunchKernelGGL): the events take the kernel's own start/stop
@@ -2584,6 +2660,20 @@ void launch_ao_walk(const AoWalkArgs& a, hipStream_t stream) {
 }
 void launch_ao_fold(const AoGen& g, const uint32_t* vis, float4* out, hipStream_t stream) {
     if (g.n) hipLaunchKernelGGL(k_ao_fold, dim3((g.n + 255u) / 256u), dim3(256), 0, stream, g, vis, out);
+}
+void launch_fog_view_segments(const FogViewArgs& a, hipStream_t stream) {
+    if (a.n_pixels) hipLaunchKernelGGL(k_fog_view_segments, dim3((a.n_pixels + 255u) / 256u), dim3(256), 0, stream, a);
+}
+// one single-wave workgroup per pool of the n K entries
+void launch_fog_walk(const FogWalkArgs& a, hipStream_t stream) {
+    const uint64_t total = (uint64_t)a.g.n * a.g.K;
+    if (total) hipLaunchKernelGGL(k_fog_walk, dim3((uint32_t)((total + a.pool - 1u) / a.pool)), dim3(64), stack_bytes(a.stack_entries), stream, a);
+}
+void launch_fog_fold(const FogGen& g, const uint32_t* vis, float4* out, hipStream_t stream) {
+    if (g.n) hipLaunchKernelGGL(k_fog_fold, dim3((g.n + 255u) / 256u), dim3(256), 0, stream, g, vis, out);
+}
+void launch_fog_composite(const FogCompositeArgs& a, hipStream_t stream) {
+    if (a.n_pixels) hipLaunchKernelGGL(k_fog_composite, dim3((a.n_pixels + 255u) / 256u), dim3(256), 0, stream, a);
 }
 void launch_untile(const FrameArgs& f, const float* packed, float* linear, uint32_t grid, hipStream_t stream) {
     hipLaunchKernelGGL(k_untile, dim3(grid), dim3(256), 0, stream, f, packed, linear);

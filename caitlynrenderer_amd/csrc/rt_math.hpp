@@ -157,6 +157,32 @@ __device__ __forceinline__ float pinned_cos(float xf) {
     }
 }
 
+// ---- pinned e^-x of the fog entries (include/crt.h at crt_render_fog, step 6): Cody-Waite by ln 2 in double, the Taylor
+// polynomial to x^13 / 13!, one rounding to float.  Plain multiplies and adds in the written order (the library is built with
+// -ffp-contract=off), so float64 numpy gives the same bits.  k <= 150, so k times the 32-bit high part of ln 2 is exact and 2^-k is a normal double.
+__device__ __forceinline__ float exp_neg(float xf) {
+    const double x = (double)xf;
+    if (!(x < 104.0)) return 0.0f;
+    const double k = __builtin_rint(x * 0x1.71547652b82fep+0);
+    const double r = (x - k * 0x1.62e42feep-1) - k * 0x1.a39ef35793c76p-33;
+    const double q = -r;
+    double p = 1.0 / 6227020800.0;
+    p = p * q + 1.0 / 479001600.0;
+    p = p * q + 1.0 / 39916800.0;
+    p = p * q + 1.0 / 3628800.0;
+    p = p * q + 1.0 / 362880.0;
+    p = p * q + 1.0 / 40320.0;
+    p = p * q + 1.0 / 5040.0;
+    p = p * q + 1.0 / 720.0;
+    p = p * q + 1.0 / 120.0;
+    p = p * q + 1.0 / 24.0;
+    p = p * q + 1.0 / 6.0;
+    p = p * q + 0.5;
+    p = p * q + 1.0;
+    p = p * q + 1.0;
+    return (float)(p * __longlong_as_double((long long)(1023 - (int)k) << 52));
+}
+
 // Shader/path_trace.fs:38-42
 template <bool LEAN = false>
 __device__ __forceinline__ float shader_rand(float& sx, float& sy, float rv) {
@@ -164,6 +190,16 @@ __device__ __forceinline__ float shader_rand(float& sx, float& sy, float rv) {
     sy -= rv;
     float d = sx * 12.9898f + sy * 78.233f;
     float v = pinned_sin<LEAN>(d) * 43758.5453f;
+    return v - __builtin_floorf(v);
+}
+
+// The j-th draw (j = 1, 2, ...) of shader_rand from the state (seed_x, seed_y), by index, so that any lane can form any draw of a point or
+// a segment (include/crt.h at crt_render_ao, step 4).
+__device__ __forceinline__ float rand_at(float seed_x, float seed_y, uint32_t j, float rv) {
+    const float s = (float)j * rv;
+    const float ax = seed_x - s, ay = seed_y - s;
+    const float d = ax * 12.9898f + ay * 78.233f;
+    const float v = pinned_sin(d) * 43758.5453f;
     return v - __builtin_floorf(v);
 }
 

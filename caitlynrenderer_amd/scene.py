@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CRT_ABI_VERSION, CRT_ENV_HIDE_FROM_CAMERA, crt_environment, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params, crt_ao_params,
+from ._lib import (CRT_ABI_VERSION, CRT_ENV_HIDE_FROM_CAMERA, crt_environment, CRT_AOV_ALBEDO, CRT_AOV_ALL, CRT_AOV_EMISSION, CRT_AOV_HIT, CRT_AOV_IDS, CRT_AOV_NORMAL, CRT_BUILD_LBVH_ON_DEVICE, CRT_DENOISE_DEMODULATE, CRT_TEMPORAL_CLAMP, CRT_TEMPORAL_DEMODULATE, CRT_TEMPORAL_SOURCE_DENOISED, CRT_TEMPORAL_SOURCE_SUM, CRT_TRACE_ANY, CRT_TRACE_CLOSEST, check, crt_bvh_info, crt_denoise_params, crt_frame_stats, crt_temporal_params, crt_ao_params, crt_fog_params,
                    crt_scene_desc, crt_tree_cost, lib,
                    CRT_DISPLAY_AUTO_EXPOSURE, CRT_DISPLAY_CURVE_ACES, CRT_DISPLAY_CURVE_CLAMP, CRT_DISPLAY_CURVE_REFERENCE, CRT_DISPLAY_CURVE_REINHARD,
                    CRT_DISPLAY_SOURCE_DENOISED, CRT_DISPLAY_SOURCE_SUM, CRT_DISPLAY_SOURCE_TEMPORAL, crt_display_params, crt_display_state,
@@ -34,6 +34,19 @@ def _ao_params(samples, radius, offset):
     p.samples, p.flags = int(samples), 0
     p.radius = float(np.float32(1e9 if radius is None else radius))
     p.offset = float(np.float32(offset))
+    return p
+
+
+# a fog segment of fog_segments / fog_segments_device (include/crt.h at crt_render_fog): 32 bytes, laid out like RAY_DT
+FOG_SEGMENT_DT = np.dtype([("o", "<f4", 3), ("seed_x", "<f4"), ("e", "<f4", 3), ("seed_y", "<f4")])
+
+
+def _fog_params(samples, density, albedo, anisotropy, max_distance, ambient):
+    p = crt_fog_params()
+    p.samples, p.flags = int(samples), 0
+    p.density, p.anisotropy, p.max_distance = (float(np.float32(v)) for v in (density, anisotropy, max_distance))
+    for k in range(3):
+        p.albedo[k], p.ambient[k] = float(np.float32(albedo[k])), float(np.float32(ambient[k]))
     return p
 
 
@@ -262,6 +275,69 @@ class Scene:
         check(lib().crt_ao_points_device(self._h, C.c_void_p(d_points), int(n), float(np.float32(rx)), float(np.float32(ry)), C.byref(p),
                                          C.c_void_p(d_out), 1 if sync else 0))
 
+    def render_fog(self, rx=0.0, ry=0.0, samples=16, density=0.05, albedo=(1.0, 1.0, 1.0), anisotropy=0.0, max_distance=100.0, ambient=(0.0, 0.0, 0.0),
+                   sync=True):
+        """crt_render_fog: homogeneous fog with shadowed single scattering along the primary rays of the current view, each cut into
+        `samples` strata that aim one shadow ray each at the scene's area lights, built on the device where they are walked.  A miss pixel
+        marches to `max_distance`.  Touches nothing a frame, render_aov or render_ao reads or reports."""
+        p = _fog_params(samples, density, albedo, anisotropy, max_distance, ambient)
+        check(lib().crt_render_fog(self._h, float(np.float32(rx)), float(np.float32(ry)), C.byref(p), 1 if sync else 0))
+
+    def read_fog(self):
+        """crt_read_fog: (height, width, 4) float32, rows as read_sum has them: the in-scattered radiance S and the transmittance TD of what
+        lies at the segment's end (a fogged pixel is c * TD + S)"""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        check(lib().crt_read_fog(self._h, _ptr(out), out.size))
+        return out
+
+    def fog_device(self):
+        """crt_fog_device: device pointer (int) of render_fog's image, width * height * 16 bytes, valid until the scene is closed"""
+        ptr = C.c_void_p()
+        check(lib().crt_fog_device(self._h, C.byref(ptr)))
+        return ptr.value
+
+    def fog_segments(self, segments, rx=0.0, ry=0.0, samples=16, density=0.05, albedo=(1.0, 1.0, 1.0), anisotropy=0.0, ambient=(0.0, 0.0, 0.0)):
+        """crt_fog_segments: the fog along the caller's segments (a FOG_SEGMENT_DT array); returns (n, 4) float32, the bytes render_fog
+        gives for the same segments; a segment without length or with a non-finite end holds (0, 0, 0, -1)"""
+        seg = np.ascontiguousarray(segments, FOG_SEGMENT_DT).reshape(-1)
+        out = np.empty((seg.shape[0], 4), np.float32)
+        p = _fog_params(samples, density, albedo, anisotropy, 100.0, ambient)
+        check(lib().crt_fog_segments(self._h, _ptr(seg) if seg.shape[0] else None, seg.shape[0], float(np.float32(rx)), float(np.float32(ry)), C.byref(p),
+                                     _ptr(out) if seg.shape[0] else None))
+        return out
+
+    def fog_segments_device(self, d_segments, n, d_out, rx=0.0, ry=0.0, samples=16, density=0.05, albedo=(1.0, 1.0, 1.0), anisotropy=0.0,
+                            ambient=(0.0, 0.0, 0.0), sync=True):
+        """crt_fog_segments_device: the same with device pointers (ints): n fog segments of 32 bytes in, n float4 out"""
+        p = _fog_params(samples, density, albedo, anisotropy, 100.0, ambient)
+        check(lib().crt_fog_segments_device(self._h, C.c_void_p(d_segments), int(n), float(np.float32(rx)), float(np.float32(ry)), C.byref(p),
+                                            C.c_void_p(d_out), 1 if sync else 0))
+
+    def fog_composite(self, inv_count=None, source="sum", sync=True):
+        """crt_fog_composite: render_fog's image put on one float image ("sum": the running sum times inv_count, "denoised", "temporal"):
+        c * TD + S per pixel, the fogged image that read_fogged, fogged_device and display_fogged hand on.  inv_count None =
+        1 / max(frame_count, 1).  An unknown source name raises KeyError."""
+        if inv_count is None:
+            inv_count = 1.0 / max(self.frame_count, 1)
+        sources = {"sum": CRT_DISPLAY_SOURCE_SUM, "denoised": CRT_DISPLAY_SOURCE_DENOISED, "temporal": CRT_DISPLAY_SOURCE_TEMPORAL}
+        check(lib().crt_fog_composite(self._h, float(np.float32(inv_count)), sources[source], 1 if sync else 0))
+
+    def read_fogged(self):
+        """crt_read_fogged: the fogged MEAN radiance, (height, width, 3) float32, rows as read_sum has them"""
+        out = np.empty((self.height, self.width, 3), np.float32)
+        check(lib().crt_read_fogged(self._h, _ptr(out), out.size))
+        return out
+
+    def fogged_device(self):
+        """crt_fogged_device: device pointer (int) of the fogged image, width * height * 3 floats, valid until the scene is closed"""
+        ptr = C.c_void_p()
+        check(lib().crt_fogged_device(self._h, C.byref(ptr)))
+        return ptr.value
+
+    def display_fogged(self, **display_options):
+        """crt_display_fogged: display() on fog_composite()'s image, which takes no inv_count; the options are display()'s"""
+        return self.display(source="fogged", **display_options)
+
     def denoise(self, inv_count=None, passes=5, demodulate=True, sigma_color=4.0, sigma_depth=0.05, normal_power_log2=7, sync=True):
         """crt_denoise: an edge-avoiding a-trous filter over the running sum, guided by the HIT, IDS, NORMAL and ALBEDO channels of the most
         recent render_aov (the caller keeps them in step with the view and the geometry).  inv_count None = 1 / max(frame_count, 1), as in
@@ -348,15 +424,16 @@ class Scene:
 
     def display(self, inv_count=None, source="sum", curve="reference", exposure=1.0, auto=False, white=4.0, key=0.18, adapt=1.0, exposure_min=1e-6,
                 exposure_max=1e6, low_permille=0, high_permille=1000, sync=True):
-        """crt_display: the display transform of one float image ("sum": the running sum times inv_count, "denoised", "temporal", or "bloom":
-        crt_display_bloom on bloom()'s image, which takes no inv_count) into RGBA8
+        """crt_display: the display transform of one float image ("sum": the running sum times inv_count, "denoised", "temporal", "bloom":
+        crt_display_bloom on bloom()'s image, or "fogged": crt_display_fogged on fog_composite()'s; those two take no inv_count) into RGBA8
         in device memory: exposure (given, or with auto=True metered on the device from the image's luminance histogram and adapted by
         `adapt` per call), a tone curve ("reference", "reinhard", "aces", "clamp") and the pinned gamma.  inv_count None =
         1 / max(frame_count, 1).  The defaults are the header's NULL: resolve()'s bytes.  Returns the (height, width, 4) uint8 image, or None
         with sync=False (read_display() after sync()).  An unknown source or curve name raises KeyError."""
         if inv_count is None:
             inv_count = 1.0 / max(self.frame_count, 1)
-        sources = {"sum": CRT_DISPLAY_SOURCE_SUM, "denoised": CRT_DISPLAY_SOURCE_DENOISED, "temporal": CRT_DISPLAY_SOURCE_TEMPORAL, "bloom": 0}
+        sources = {"sum": CRT_DISPLAY_SOURCE_SUM, "denoised": CRT_DISPLAY_SOURCE_DENOISED, "temporal": CRT_DISPLAY_SOURCE_TEMPORAL, "bloom": 0,
+                   "fogged": 0}
         curves = {"reference": CRT_DISPLAY_CURVE_REFERENCE, "reinhard": CRT_DISPLAY_CURVE_REINHARD, "aces": CRT_DISPLAY_CURVE_ACES,
                   "clamp": CRT_DISPLAY_CURVE_CLAMP}
         p = crt_display_params()
@@ -367,6 +444,8 @@ class Scene:
         p.low_permille, p.high_permille = int(low_permille), int(high_permille)
         if source == "bloom":
             check(lib().crt_display_bloom(self._h, C.byref(p), 1 if sync else 0))
+        elif source == "fogged":
+            check(lib().crt_display_fogged(self._h, C.byref(p), 1 if sync else 0))
         else:
             check(lib().crt_display(self._h, float(np.float32(inv_count)), C.byref(p), 1 if sync else 0))
         return self.read_display() if sync else None
@@ -640,6 +719,6 @@ class Scene:
             pass
 
 
-__all__ = ["Scene", "SceneData", "Camera", "Mesh", "SBVH", "CWBVH", "RAY_DT", "HIT_DT", "STATS_DT", "AO_POINT_DT", "AOV_IDS_DT", "AOV_DTYPES",
+__all__ = ["Scene", "SceneData", "Camera", "Mesh", "SBVH", "CWBVH", "RAY_DT", "HIT_DT", "STATS_DT", "AO_POINT_DT", "FOG_SEGMENT_DT", "AOV_IDS_DT", "AOV_DTYPES",
            "AOV_HIT", "AOV_IDS", "AOV_NORMAL", "AOV_ALBEDO", "AOV_EMISSION", "AOV_ALL",
            "CRT_TRACE_CLOSEST", "CRT_TRACE_ANY", "CRT_BUILD_LBVH_ON_DEVICE"]

@@ -671,6 +671,97 @@ int crt_resolve_bloom(crt_scene* s, uint8_t* rgba, size_t n_bytes);      /* crt_
 int crt_resolve_bloom_device(crt_scene* s, const uint8_t** d_rgba, int sync);
 int crt_display_bloom(crt_scene* s, const crt_display_params* p, int sync);
 
+/* Homogeneous fog with shadowed single scattering ("light shafts") between the camera and the surfaces of the scene's current view, or
+ * along segments the caller names, flat and instanced scenes (no reference counterpart).  Each eye segment is cut into K
+ * strata; one jittered point per stratum aims one shadow ray at a sampled point of the scene's area lights, as the integrator's next-event
+ * estimation does from a surface.  The rays are built on the device where they are walked and never stored; which of them arrive is a bit
+ * per ray, so the result is defined bit for bit: every line below is ONE IEEE float32 operation in the written order under DESIGN.md §3
+ * (no contraction); dot, normalize, the correctly rounded sqrt and 1/x, pinned_sin and rand_at(j) (crt_render_ao's step 4) are the
+ * library's.  F(x) = x rounded to float32.
+ *
+ * A FOG SEGMENT is crt_fog_segment: (o[3], seed_x, e[3], seed_y), 32 bytes, laid out like crt_ray: o is where the eye ray starts, e the
+ * vector to where it ends.  crt_fog_params (64 bytes): samples K in 1..256; flags = 0; density sigma (extinction per world unit) finite,
+ * in [0, 1e6]; albedo[3] each finite, in [0, 1]; anisotropy g finite, in [-0.99, 0.99]; max_distance finite and > 0; ambient[3] each
+ * finite and >= 0 (a uniform in-scattered radiance that needs no rays); reserved = 0.  NULL params mean
+ * {16, 0, 0.05f, {1, 1, 1}, 0.0f, 100.0f, {0, 0, 0}}.  rv = rx * ry, as in a frame.  Per segment:
+ *   1. Length.  D2 = dot(e, e).  If D2 is not > 0, or D2 or any component of o is not finite, the result is (0, 0, 0, -1) and no ray is
+ *      traced.  Otherwise D = sqrt(D2); dir = e * (1 / D); h = D / F(K) (IEEE division).
+ *   2. Transmittance to the end.  TD = exp_neg(F(sigma * D)).
+ *   3. Sample j (0-based) uses four draws: u0 = rand_at(4j+1), r0 = rand_at(4j+2), r1 = rand_at(4j+3), r2 = rand_at(4j+4);
+ *      s = F(F(j) + u0) * h; x = o + dir * s, per component F(o.k + F(dir.k * s)).
+ *   4. Light sample (path_trace.fs:940, :849-854).  li = min((int)F(r0 * F(n_lights)), n_lights - 1); sq = sqrt(r1); b0 = 1 - sq;
+ *      b1 = r2 * sq; pos = (p + u*b0) + v*b1 of light li; ld = pos - x; ln = length(ld); ld = ld * (1 / ln); cos_light = dot(ld, n_light).
+ *      The light table is the one a frame reads at enqueue; for a scene from crt_scene_create_instanced_lit, the world table that
+ *      crt_scene_read_lights returns.  A sample whose cos_light is not < 0 is DARK: no ray, nothing added.  With n_lights == 0 every
+ *      sample is dark.
+ *   5. Occlusion.  The ray is crt_ray{x, tmax = ln - 1e-4f, d = ld}.  It is occluded iff crt_trace(.., CRT_TRACE_ANY) reports a hit for
+ *      that crt_ray; an instanced scene: crt_instances_trace(.., CRT_TRACE_ANY) on the scene's handle as it is at enqueue, with option
+ *      "instance_masks" 1 | CRT_TRACE_INSTANCE_MASK with the ray mask "mask_shadow".
+ *   6. Contribution of an unoccluded sample.  pdf = F(F(F(ln*ln) / F(area * -cos_light)) * pdf_choice) (path_trace.fs:986);
+ *      ct = dot(dir, ld); den = F(F(1 + F(g*g)) - F(F(2*g) * ct)); ph = F(F(F(1 - F(g*g)) * 0.07957747f) / F(den * sqrt(den)))
+ *      (Henyey-Greenstein; g = 0 gives 1 / 4 pi); att = exp_neg(F(sigma * F(s + ln))); w = F(F(F(att * ph) * F(sigma * h)) / pdf);
+ *      per channel c: F(F(emission.c * albedo.c) * w).
+ *      exp_neg(xf), xf a float that is never negative here, is e^-x in double with ONE rounding to float32, plain multiplies and adds,
+ *      nothing fused: x = (double)xf; the value is +0.0f unless x < 104.0; k = rint(x * 0x1.71547652b82fep+0);
+ *      r = (x - k * 0x1.62e42feep-1) - k * 0x1.a39ef35793c76p-33; q = -r; p = 1/13!; then p = p*q + 1/i! for i = 12, 11, .. 1 and
+ *      p = p*q + 1 (each 1/i! the double nearest to the quotient); the value is (float)(p * 2^-k), 2^-k exact.  It is within 1 ulp of
+ *      the correctly rounded e^-x, exactly 1 at 0, and never increases with x.
+ *   7. Result.  Per channel A.c = F(F(ambient.c * albedo.c) * F(1 - TD)); b = A; for j = 0 .. K-1 in that order, b = b + contribution_j
+ *      for each unoccluded (and not dark) j.  The output float[4] is (b.x, b.y, b.z, TD): the in-scattered radiance S and the
+ *      transmittance of whatever lies at the segment's end.
+ *
+ * VIEW MODE, crt_render_fog(s, rx, ry, params, sync): the segments come from the primary rays of crt_render_aov(s, rx, ry, ..): the same
+ * rays (the scene's camera, the "jitter" option, the pinhole through `position` whatever the aperture, the masked walk with
+ * "mask_primary" where that applies).  o = the ray's origin; t = the HIT channel's t, 1e9f for a miss; Dv = min(t, max_distance);
+ * e = d * Dv per component; (seed_x, seed_y) = the pixel's RNG state BEHIND the primary ray's draws, as in crt_render_ao.  A miss pixel
+ * marches to max_distance; it is no special case.  The image is width*height float[4] in linear pixel order, rows as crt_read_sum has
+ * them, allocated by the first call and freed with the scene; the first hits go into a buffer of the fog state's own.
+ * SEGMENTS MODE, crt_fog_segments (host pointers; returns when `out`, n x float[4], is written) and crt_fog_segments_device (device
+ * pointers): the same bytes as view mode gives for the same segments.  n = 0 succeeds and writes nothing.
+ * crt_read_fog wants n_floats = width*height*4.  crt_fog_device waits for the stream; the pointer stays valid until the scene is destroyed.
+ * COMPOSITE, crt_fog_composite(s, inv_count, source, sync): per pixel and channel out.c = F(F(c.c * TD) + S.c), c being crt_display's
+ * input pixel of `source` (CRT_DISPLAY_SOURCE_SUM: the sum times inv_count; _DENOISED, _TEMPORAL: the image as it is) and (S, TD) the
+ * pixel of the most recent crt_render_fog; a pixel whose fog word 3 is -1 copies c.  The result is a fifth float image, width*height*3
+ * floats of mean radiance: crt_read_fogged, crt_fogged_device (as crt_read_bloom, crt_bloom_device), and crt_display_fogged, which is
+ * crt_display with the fogged image as its input pixel: the same meter, adaptation state, RGBA8 buffer, state block, histogram and
+ * refusals as crt_display_bloom; p->source must be 0 and names nothing; there is no inv_count.  There is no crt_resolve_fogged.
+ *
+ * The calls are enqueued on the scene's stream behind any *_async frames (sync = 0 returns at once); later frames and reads are ordered
+ * behind them.  The sum, the frame count, crt_get_frame_stats, the launch times, every AOV channel, the AO image, every other stage's
+ * buffers and every frame's path and RNG state stay as they are (the composite of SUM rewrites the un-tiled copy every crt_read_sum
+ * rewrites).  An instanced scene reads its handle's live arrays and its live light table at enqueue.  An environment and a lens change
+ * no byte.
+ * CRT_ERR_INVALID, crt_last_error names the field, nothing written and earlier images untouched: a null scene; a null segments or out
+ * pointer with n > 0; samples outside 1..256; flags or reserved not 0; density, albedo, anisotropy, max_distance or ambient outside the
+ * ranges above or not finite; n * K or width*height*K >= 2^32; option "accel" not 0; a shard of a frame (crt_set_shard with world > 1);
+ * a scene on several devices or streams (crt_set_devices, option "streams"); crt_render_fog before crt_set_camera; crt_fog_composite
+ * before a successful crt_render_fog, with an inv_count not finite or <= 0, or of a source that is unknown or does not exist;
+ * crt_read_fog / crt_fog_device before any crt_render_fog, crt_read_fogged / crt_fogged_device / crt_display_fogged before any
+ * crt_fog_composite, or n_floats of another size.
+ * Out of scope: fog on bounce segments or inside the integrator; heterogeneous density or a coloured extinction; the environment as a
+ * fog light; accumulation over calls (the caller averages S over frames); fog as a source of crt_denoise / crt_temporal / crt_bloom;
+ * shards and several devices; any fog in the C oracle. */
+typedef struct crt_fog_segment { float o[3]; float seed_x; float e[3]; float seed_y; } crt_fog_segment;
+typedef struct crt_fog_params {     /* 64 bytes; NULL = {16, 0, 0.05f, {1, 1, 1}, 0.0f, 100.0f, {0, 0, 0}, 0} */
+    uint32_t samples;      /* K: 1..256 strata, one shadow ray each at most */
+    uint32_t flags;        /* 0 */
+    float    density;      /* sigma: extinction per world unit; finite, [0, 1e6] */
+    float    albedo[3];    /* scattering albedo; each finite, [0, 1] */
+    float    anisotropy;   /* g of Henyey-Greenstein; finite, [-0.99, 0.99] */
+    float    max_distance; /* finite, > 0: where a view segment ends at the latest */
+    float    ambient[3];   /* uniform in-scattered radiance; each finite, >= 0 */
+    uint32_t reserved[5];  /* 0 */
+} crt_fog_params;
+int crt_render_fog(crt_scene* s, float rx, float ry, const crt_fog_params* params, int sync);
+int crt_read_fog(crt_scene* s, float* dst, size_t n_floats);             /* w*h*4: (S.rgb, TD) */
+int crt_fog_device(crt_scene* s, const float** d_ptr);
+int crt_fog_segments(crt_scene* s, const crt_fog_segment* segments, size_t n, float rx, float ry, const crt_fog_params* params, float* out);
+int crt_fog_segments_device(crt_scene* s, const void* d_segments, size_t n, float rx, float ry, const crt_fog_params* params, void* d_out, int sync);
+int crt_fog_composite(crt_scene* s, float inv_count, uint32_t source, int sync);   /* source: CRT_DISPLAY_SOURCE_* */
+int crt_read_fogged(crt_scene* s, float* rgb, size_t n_floats);          /* w*h*3, mean radiance, rows as crt_read_sum */
+int crt_fogged_device(crt_scene* s, const float** d_rgb);
+int crt_display_fogged(crt_scene* s, const crt_display_params* p, int sync);
+
 /* Animated geometry (no reference counterpart: the reference uploads its scene once, Scene.h:1000-1062; DXR / OptiX call this an
  * update build).  New positions for the scene's vertices; triangles, materials, textures and the tree topology are unchanged.
  * n_vertices must equal the count given at create; normals (n_normals == create's) and lights (n_lights == create's) may be NULL =
