@@ -9,6 +9,7 @@ from ._lib import CRT_TRACE_ANY, CRT_TRACE_BVH2, CRT_TRACE_CLOSEST, CRT_TRACE_IN
 from .host import CWBVH, SBVH, Camera, Mesh, Rnd, pcg_hash
 from .scene import (AO_POINT_DT, FOG_SEGMENT_DT, AOV_ALBEDO, AOV_ALL, AOV_DTYPES, AOV_EMISSION, AOV_HIT, AOV_IDS, AOV_IDS_DT, AOV_NORMAL, HIT_DT, RAY_DT, STATS_DT, Scene,
                     SceneData)
+from .cameras import fisheye_rays, orthographic_rays, panorama_rays, pinhole_rays
 from .deform import Deformer, deform_host, normal_influences
 from .environment import constant_environment, octahedral_directions, octahedral_from_equirect, octahedral_from_function
 from .instances import (INSTANCE_DT, InstancedScene, instance_inverse, instance_lights, instance_world_box, instances_array, lights_finish,
@@ -27,7 +28,7 @@ def warmup():
     _lib.check(_lib.lib().crt_warmup())
 
 
-__all__ = ["has_experiments", "warmup", "constant_environment", "octahedral_directions", "octahedral_from_equirect", "octahedral_from_function", "Scene", "SceneData", "Deformer", "deform_host", "normal_influences", "InstancedScene", "INSTANCE_DT", "instances_array", "instance_inverse",
+__all__ = ["has_experiments", "warmup", "pinhole_rays", "panorama_rays", "orthographic_rays", "fisheye_rays", "constant_environment", "octahedral_directions", "octahedral_from_equirect", "octahedral_from_function", "Scene", "SceneData", "Deformer", "deform_host", "normal_influences", "InstancedScene", "INSTANCE_DT", "instances_array", "instance_inverse",
            "instance_world_box", "instance_lights", "lights_finish", "set_mesh_lights", "read_lights", "Camera", "Mesh", "SBVH", "CWBVH", "Rnd", "pcg_hash", "CrtError",
            "RAY_DT", "HIT_DT", "STATS_DT", "CRT_TRACE_CLOSEST", "CRT_TRACE_ANY", "CRT_TRACE_BVH2", "CRT_TRACE_TIE_LOWEST_ID",
            "CRT_TRACE_INSTANCE_MASK", "AOV_HIT", "AOV_IDS", "AOV_NORMAL", "AOV_ALBEDO", "AOV_EMISSION", "AOV_ALL", "AOV_IDS_DT", "AOV_DTYPES", "AO_POINT_DT", "FOG_SEGMENT_DT"]

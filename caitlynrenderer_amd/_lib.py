@@ -192,6 +192,9 @@ SYMBOLS = {
     "crt_scene_destroy": (_I, [_P]),
     "crt_set_camera": (_I, [_P, C.POINTER(crt_camera)]),
     "crt_set_environment": (_I, [_P, C.POINTER(crt_environment)]),
+    "crt_set_camera_rays": (_I, [_P, _P, _SZ]),
+    "crt_set_camera_rays_device": (_I, [_P, _P, _SZ]),
+    "crt_clear_camera_rays": (_I, [_P]),
     "crt_render_frame": (_I, [_P, _F, _F]),
     "crt_render_frame_async": (_I, [_P, _F, _F]),
     "crt_render_frames": (_I, [_P, C.c_uint32, _P, _P]),

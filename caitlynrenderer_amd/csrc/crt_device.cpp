@@ -726,6 +726,8 @@ static int replicate_scene(const crt_scene* src, int device, crt_scene** out) {
 int crt_set_devices(crt_scene* s, const int32_t* devices, uint32_t n_devices, uint32_t tile) {
     if (s && s->inst && n_devices > 1)
         return fail(CRT_ERR_INVALID, "crt_set_devices: an instanced scene renders on the one device its crt_instances handle lives on");
+    if (s && s->camera_rays() && n_devices > 1)
+        return fail(CRT_ERR_INVALID, "crt_set_devices: n_devices: a scene with camera rays set (crt_set_camera_rays) renders on one device: crt_clear_camera_rays first");
     const int rc = set_devices_of_shard(s, devices, n_devices, tile, 0u, 1u);
     if (rc == CRT_OK) { s->shard_rank = 0u; s->shard_world = 1u; }      // the devices divide the whole frame (a refused call changes nothing)
     return rc;

@@ -118,6 +118,7 @@ extern "C" {
 
 int crt_render_fog(crt_scene* s, float rx, float ry, const crt_fog_params* params, int sync) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_render_fog: null scene");
+    if (s->camera_rays()) return fail(CRT_ERR_INVALID, "crt_render_fog: the scene is seen along the caller's camera rays, which this call cannot follow (it looks through the pinhole): crt_clear_camera_rays first");
     FogCall c{};
     int rc = check_params(params, "crt_render_fog", &c);
     if (rc || (rc = check_scene(s, "crt_render_fog"))) return rc;

@@ -124,7 +124,7 @@ namespace {
 // per chain by plan_frame, where each field is explained.  prepare_batch allocates what `need_*`, `defer_regions` and `bins` name, the
 // two renderers launch what the rest says, and crt_render_frames' chunking and crt_debug_read_queue ask the same record.
 struct FramePlan {
-    bool instanced, lens, env, queue_fed, bvh2, small_tree, bins, refill, batched_paths, any_deferred, folds, lanes4;
+    bool instanced, lens, rays, env, queue_fed, bvh2, small_tree, bins, refill, batched_paths, any_deferred, folds, lanes4;
     uint32_t first_deferred, defer_regions, limit;
     bool need_queues, need_lens_queue, need_lfinal, need_qhits, need_qinst, need_visit_totals;
     bool first(uint32_t b) const { return b == 0 && !queue_fed && !instanced; }     // the fused first-segment kernels; false = a queue-fed segment
@@ -136,9 +136,11 @@ struct FramePlan {
 FramePlan plan_frame(const crt_scene* s, uint32_t n_samples) {
     FramePlan p{};
     p.instanced = s->inst != nullptr;   // the two-level walk of a crt_instances handle: every segment queue-fed, every shadow ray deferred
-    p.lens = s->lens();                 // segment 0's rays come from k_raygen_lens (camera aperture > 0)
+    p.rays = s->camera_rays();          // segment 0's rays are the caller's, through k_raygen_rays (crt_set_camera_rays): the camera is not read
+    p.lens = s->lens() && !p.rays;      // segment 0's rays come from k_raygen_lens (camera aperture > 0)
+    const bool fed = p.lens || p.rays;  // a ray generator of up to 8 samples per launch feeds segment 0, from a queue of its own on a flat scene
     p.env = s->env();                   // k_env_miss behind every closest-hit launch
-    p.queue_fed = !p.instanced && (p.lens || p.env);    // a flat frame whose segment 0 is queue-fed too: no fused first-segment kernel, tile order untouched
+    p.queue_fed = !p.instanced && (fed || p.env);    // a flat frame whose segment 0 is queue-fed too: no fused first-segment kernel, tile order untouched
     p.bvh2 = s->accel != 0u;            // the BVH2 frame mode (a comparison aid): shadow rays in place, one sample per chain
     p.small_tree = s->info.n_nodes8 < 64;               // plain per-lane closest-hit loop (tri_min = 0) and no bounce pools
     // bounce rays binned between the segments (option "ray_bins"): big trees, CWBVH walks, the lock-step segment kernels
@@ -154,23 +156,23 @@ FramePlan plan_frame(const crt_scene* s, uint32_t n_samples) {
     p.any_deferred = p.first_deferred < s->max_depth;
     p.defer_regions = s->max_depth - p.first_deferred;  // regions of the NEE queue and of the slot array
     p.folds = p.batched_paths || p.any_deferred || p.queue_fed;     // finished paths leave their radiance in d_lfinal, k_fold_paths adds it to the sum
-    p.lanes4 = s->wave_samples >= 2u && !p.small_tree && !p.bvh2 && !p.lens;    // a launch of 4 k samples can put four in the lanes of a wave
+    p.lanes4 = s->wave_samples >= 2u && !p.small_tree && !p.bvh2 && !fed;    // a launch of 4 k samples can put four in the lanes of a wave
     // More than one sample per chain only when nothing travels between launches (one path segment, shadow rays walked in place) or every
     // sample keeps its own path state and queue entries (ensure_batch_buffers); path ids are sample * n_local_pixels + pixel and must
     // stay below 2^31 (bit 31 tags queue entries).  1 M triangles, 4 segments: 1.78 / 1.61 / 1.50 / 1.45 ms per frame at 1 / 2 / 4 / 8.
     const uint64_t fit = s->n_local_pixels ? 0x7fffffffull / s->n_local_pixels : 8ull;
     const uint32_t by_paths = (uint32_t)std::min<uint64_t>(8ull, std::max<uint64_t>(1ull, fit));
-    if (p.lens && !p.instanced) p.limit = (s->count_visits || p.bvh2) ? 1u : by_paths;     // queue-fed whatever the depth; counting and BVH2 frames one by one
+    if (fed && !p.instanced) p.limit = (s->count_visits || p.bvh2) ? 1u : by_paths;     // queue-fed whatever the depth; counting and BVH2 frames one by one
     else if (p.first_deferred == 0u || (s->count_visits && !s->count_batched) || p.bvh2) p.limit = 1u;      // the batched first-segment builds walk their shadow rays in place
     else if (s->count_visits)       // counting in the timed form: exactly the launch of four samples in the lanes of a wave has a counting build
         p.limit = (s->wave_samples >= 2u && !p.small_tree && s->tri_min != 0u && s->lanes_per_ray >= 8u && fit >= 4ull) ? 4u : 1u;
     else p.limit = s->max_depth == 1u ? 8u : by_paths;
     // what must exist before the first launch, beside what reads it
     p.need_queues = p.queue_fed;                       // a one-segment flat scene holds none until its camera gets an aperture or the scene an environment
-    p.need_lens_queue = p.lens && !p.instanced;        // segment 0 of such a frame reads d_rays_lens, which no later segment writes over
+    p.need_lens_queue = fed && !p.instanced;           // segment 0 of such a frame reads d_rays_lens, which no later segment writes over
     p.need_lfinal = p.queue_fed || p.any_deferred;     // (with batched_paths, ensure_batch_buffers brings it): read where `folds`
     // d_qhits is read where pretraced(b), and by every instanced segment; allocated for this superset of those frames
-    p.need_qhits = (s->bounce_refill && (s->max_depth > 1u || (p.lens && !p.instanced))) || p.instanced || p.env;
+    p.need_qhits = (s->bounce_refill && (s->max_depth > 1u || (fed && !p.instanced))) || p.instanced || p.env;
     p.need_qinst = p.instanced; p.need_visit_totals = s->count_visits;
     return p;
 }
@@ -328,9 +330,17 @@ int end_chain(crt_scene* s, uint32_t n_samples) {
     return CRT_OK;
 }
 
-// segment 0's rays and path state from a ray generator: k_raygen_lens through a lens, else the pinhole's k_raygen
+// segment 0's rays and path state from a ray generator: k_raygen_rays along the caller's rays, k_raygen_lens through a
+// lens, else the pinhole's k_raygen
 void launch_primary_rays(crt_scene* s, const Chain& c, float4* rays) {
     const crt::RaygenArgs ra = crt::raygen_args(s, c.f, rays, c.cnt + counter_index(0, 0, 0), true);
+    if (c.p.rays) {
+        crt::RaysRaygenArgs ca{};
+        static_cast<crt::RaygenArgs&>(ca) = ra;
+        ca.cam_rays = s->camera_rays_buffer(); ca.l_final = s->d_lfinal; ca.n_samples = c.n_samples;
+        timed(s, 0, [&] { crt::launch_raygen_rays(ca, s->stream); });
+        return;
+    }
     if (!c.p.lens) { timed(s, 0, [&] { crt::launch_raygen(ra, s->stream); }); return; }
     crt::LensRaygenArgs la{};
     static_cast<crt::RaygenArgs&>(la) = ra;
@@ -425,7 +435,7 @@ int render_instanced_async(crt_scene* s, Chain& c) {
     sh.visit_totals = s->d_visit_totals ? s->d_visit_totals + 2 : nullptr; sh.overflow = s->d_overflow;
     timed(s, 2, [&] { crt::launch_shadow_instances_deferred(sh, s->count_visits, masked, s->stream); });
     crt::launch_fold_paths(s->d_sum, s->d_lfinal, s->d_contrib, P, 1u, 0u, s->stream);
-    s->last_launch = LaunchInfo{0, (c.p.lens ? 16 : 0) | (c.p.env ? 32 : 0), 1};
+    s->last_launch = LaunchInfo{0, (c.p.lens ? 16 : 0) | (c.p.env ? 32 : 0) | (c.p.rays ? 64 : 0), 1};
     return end_chain(s, 1u);
 }
 
@@ -551,7 +561,7 @@ void launch_flat_segment(crt_scene* s, const Chain& c, uint32_t b) {
     uint32_t grid = s->trace_grid(s->n_local_pixels, sa.wide_first ? 6 : 5);
     if (!first && p.batched_paths) grid *= c.n_samples;
     const int build = crt::launch_segment(sa, first, pretraced, p.inplace(b), p.bvh2, s->special_materials, s->count_visits, s->lean_build != 0u && s->tree_validated, grid, s->waves_per_workgroup, s->stream);
-    if (b == 0) s->last_launch = LaunchInfo{(int)sa.wave_samples, (build & 15) | (p.lens ? 16 : 0) | (p.env ? 32 : 0), (int)c.n_samples};
+    if (b == 0) s->last_launch = LaunchInfo{(int)sa.wave_samples, (build & 15) | (p.lens ? 16 : 0) | (p.env ? 32 : 0) | (p.rays ? 64 : 0), (int)c.n_samples};
     if (sa.bins_out.count) {
         // fill counts -> the next launch's index space and ray count, and the next frame's capacities (the other parity)
         crt::BinScanArgs ba{};
@@ -595,11 +605,11 @@ void launch_deferred_shadows(crt_scene* s, const Chain& c) {
 int render_flat_async(crt_scene* s, Chain& c) {
     const FramePlan& p = c.p;
     int rc;
-    // a lens or environment frame leaves the tile order and its measurement as they are
+    // a frame through a lens, along the caller's rays or with an environment leaves the tile order and its measurement as they are
     if (!p.queue_fed && (rc = adopt_tile_order(s, &c.measure_tiles))) return rc;
     if (!p.bvh2 && (rc = crt::ensure_planes(s))) return rc;
     if ((rc = begin_chain(s, &c.cnt))) return rc;
-    if (p.queue_fed) launch_primary_rays(s, c, p.lens ? s->d_rays_lens : s->d_rays[0]);
+    if (p.queue_fed) launch_primary_rays(s, c, p.need_lens_queue ? s->d_rays_lens : s->d_rays[0]);
     for (uint32_t b = 0; b < s->max_depth; ++b) launch_flat_segment(s, c, b);
     if (p.any_deferred) launch_deferred_shadows(s, c);
     if (p.folds) crt::launch_fold_paths(s->d_sum, s->d_lfinal, p.any_deferred ? s->d_contrib : nullptr, s->n_local_pixels, c.n_samples, p.first_deferred, s->stream);
@@ -612,13 +622,14 @@ int render_flat_async(crt_scene* s, Chain& c) {
 }
 
 int render_batch_async(crt_scene* s, uint32_t n_samples, const float* rxs, const float* rys) {
-    if (!s->have_camera) return fail(CRT_ERR_INVALID, "crt_render_frame: crt_set_camera was never called");
+    if (!s->have_camera && !s->camera_rays()) return fail(CRT_ERR_INVALID, "crt_render_frame: crt_set_camera was never called");      // (the caller's rays need no camera)
     Chain c{plan_frame(s, n_samples), n_samples, rxs, rys, {}, nullptr, 0, false};
     const int rc = prepare_batch(s, c.p, n_samples);          // sets the device; a no-op when render_batch_all has prepared every device already
     if (rc) return rc;
     if (s->n_local_pixels == 0) return CRT_OK;
     c.f = crt::frame_args(s, rxs[0], rys[0]);
     c.n_paths = (size_t)s->n_local_pixels * n_samples;
+    s->stats_seg0_counted = c.p.rays;       // entries without a path emit no ray: segment 0's count comes from its queue counters
     return c.p.instanced ? render_instanced_async(s, c) : render_flat_async(s, c);      // an instanced chain is one sample (FramePlan::limit)
 }
 
@@ -627,7 +638,7 @@ int render_batch_all(crt_scene* s, uint32_t n_samples, const float* rxs, const f
     int rc = CRT_OK;
     if (!s->peers.empty()) {
         // phase 1: every device's buffers for this batch exist before any device renders (a failed growth leaves every sum as it was)
-        if (!s->have_camera) return fail(CRT_ERR_INVALID, "crt_render_frame: crt_set_camera was never called");
+        if (!s->have_camera && !s->camera_rays()) return fail(CRT_ERR_INVALID, "crt_render_frame: crt_set_camera was never called");      // (the caller's rays need no camera)
         if ((rc = prepare_batch(s, plan_frame(s, n_samples), n_samples))) { (void)hipSetDevice(s->device); return rc; }
         for (crt_scene* p : s->peers) if ((rc = prepare_batch(p, plan_frame(p, n_samples), n_samples))) { (void)hipSetDevice(s->device); return rc; }
     }
@@ -725,10 +736,10 @@ int crt_get_frame_stats(crt_scene* s, crt_frame_stats* out) {
             if (!s->h_counts && hipHostMalloc(reinterpret_cast<void**>(&s->h_counts), kCounters * sizeof(uint32_t)) != hipSuccess)
                 return fail(CRT_ERR_NOMEM, "hipHostMalloc failed");
             HIPCHK(hipMemcpy(s->h_counts, s->counts(), kCounters * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            uint64_t any = 0, closest = (uint64_t)s->n_local_in_frame * s->samples_in_stats;   // segment 0: one primary ray per in-frame pixel and sample
+            uint64_t any = 0, closest = s->stats_seg0_counted ? 0u : (uint64_t)s->n_local_in_frame * s->samples_in_stats;   // segment 0: one primary ray per in-frame pixel and sample (the caller's rays: those that have a path)
             for (uint32_t b = 0; b < s->max_depth; ++b)
                 for (uint32_t g = 0; g < 8; ++g) {
-                    if (b) closest += s->h_counts[counter_index(b, 0, g)];
+                    if (b || s->stats_seg0_counted) closest += s->h_counts[counter_index(b, 0, g)];
                     any += s->h_counts[counter_index(b, 1, g)];
                 }
             s->stats.closest_rays = closest; s->stats.any_rays = any;

@@ -255,6 +255,7 @@ static int aov_channel_index(uint32_t channel) {                            // b
 
 int crt_render_aov(crt_scene* s, float rx, float ry, uint32_t channels, int sync) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_render_aov: null scene");
+    if (s->camera_rays()) return fail(CRT_ERR_INVALID, "crt_render_aov: the scene is seen along the caller's camera rays, which this call cannot follow (it looks through the pinhole): crt_clear_camera_rays first");
     if (channels == 0u || (channels & ~(uint32_t)CRT_AOV_ALL)) return fail(CRT_ERR_INVALID, "crt_render_aov: channels is a non-empty set of CRT_AOV_* bits");
     if (!s->have_camera) return fail(CRT_ERR_INVALID, "crt_render_aov: crt_set_camera was never called");
     if (s->accel != 0u) return fail(CRT_ERR_INVALID, "crt_render_aov: the feature buffers come from the CWBVH walk (option accel is 0): the BVH2 walk has another tie rule");
@@ -377,6 +378,7 @@ int crt_aov_device(crt_scene* s, uint32_t channel, const void** d_ptr) {
 
 int crt_denoise(crt_scene* s, float inv_count, const crt_denoise_params* params, int sync) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_denoise: null scene");
+    if (s->camera_rays()) return fail(CRT_ERR_INVALID, "crt_denoise: the scene is seen along the caller's camera rays, which this call cannot follow (it looks through the pinhole): crt_clear_camera_rays first");
     crt_denoise_params p{};
     if (params) p = *params;
     else { p.passes = 5; p.flags = CRT_DENOISE_DEMODULATE; p.sigma_color = 4.0f; p.sigma_depth = 0.05f; p.normal_power_log2 = 7; }
@@ -450,6 +452,7 @@ int crt_resolve_denoised_device(crt_scene* s, const uint8_t** d_rgba, int sync) 
 
 int crt_temporal(crt_scene* s, float inv_count, const crt_temporal_params* params, int sync) {
     if (!s) return fail(CRT_ERR_INVALID, "crt_temporal: null scene");
+    if (s->camera_rays()) return fail(CRT_ERR_INVALID, "crt_temporal: the scene is seen along the caller's camera rays, which this call cannot follow (it looks through the pinhole): crt_clear_camera_rays first");
     crt_temporal_params p{};
     if (params) p = *params;
     else { p.flags = CRT_TEMPORAL_DEMODULATE; p.source = CRT_TEMPORAL_SOURCE_SUM; p.max_history = 32; p.sigma_depth = 0.1f; p.normal_min = 0.9f; }

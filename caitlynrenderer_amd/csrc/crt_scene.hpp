@@ -42,7 +42,7 @@ struct EventSpan { hipEvent_t a = nullptr, b = nullptr; int kind = 0; };   // ki
 // What segment 0 of the last chain of launches ran (crt_debug_launch_form, crt_debug_launch_info).  form: how its samples sat on the hardware
 // (option "wave_samples").  build: bit 0 the 6-wave build, 1 a build without the sample loop, 2 one compiled as the path's last segment
 // (option "last_build"), 3 its LEAN form (option "lean_build"), 4 segment 0 was fed by the lens ray generator, 5 the frame ran k_env_miss
-// behind its closest-hit launches.  samples: samples per pixel of the chain.
+// behind its closest-hit launches, 6 segment 0 was fed by the caller's camera rays (k_raygen_rays).  samples: samples per pixel of the chain.
 struct LaunchInfo { int form = 0, build = 0, samples = 1; };
 
 // What crt_render_aov keeps, allocated by a scene's first call: the five channel buffers, each by the first call that asks
@@ -336,6 +336,13 @@ struct crt_scene {
     float4* d_rays_lens = nullptr;
     uint32_t lens_sub_capacity = 0;
     bool lens() const { return cam.aperture > 0.0f; }     // crt_set_camera has checked the two fields
+    // The caller's own camera rays (crt_set_camera_rays): width x height entries of crt_ray, a copy the scene owns, allocated
+    // by the first set, reused by later ones and freed with the scene.  While set, segment 0 of a frame is fed by k_raygen_rays and the
+    // camera is not read.  A stream replica (option "streams") reads its primary's buffer: every shard the same one.
+    float4* d_cam_rays = nullptr;
+    bool cam_rays_set = false;
+    bool camera_rays() const { return primary ? primary->cam_rays_set : cam_rays_set; }
+    const float4* camera_rays_buffer() const { return primary ? primary->d_cam_rays : d_cam_rays; }
     // The environment (crt_set_environment): scene state like the camera, on every device of the scene a copy of its own.
     // d_env: size x size texels (r, g, b, 0), row 0 first; null = none, and every frame is launched as without this member.  With one, a
     // flat scene's frame runs every segment queue-fed and pretraced, k_env_miss between the closest-hit launch and the shade-only pass.
@@ -465,6 +472,7 @@ struct crt_scene {
                                              // A tree built or rebuilt on the device never went through it and keeps the checked pushes
     uint32_t debug_fail_batch_alloc = 0;     // test hook (option of the same name): the next growth of the batch buffers fails before it allocates
     uint32_t batch_cap = 1;                  // samples the path state, the ray queues and d_lfinal are sized for (1 until crt_render_frames needs more)
+    bool stats_seg0_counted = false;         // the launch the pending stats describe ran along the caller's camera rays: segment 0's ray count is its queue's
     uint32_t samples_in_stats = 1;           // samples per pixel of the launch the pending stats describe (crt_render_frames batches)
     // event spans behind crt_frame_stats.ms_*: 2 = every launch, 1 = closest-hit launches only, 0 = none (the default: an event-carrying
     // dispatch cannot overlap its neighbours, ~5 us of stream time per launch — 8 % of a Cornell-box frame, 0.8 % of a 1 M-triangle one)
@@ -524,7 +532,7 @@ struct crt_scene {
         if (shares_scene)                   // borrowed from the primary, which frees them
             for (int k = 0; k < kSharedBufs; ++k) *shared_slot(k) = nullptr;
         void* ptrs[] = {d_gamma, d_texcoords, d_textures, d_bvh2, d_tris2, d_nodes, d_planes, d_tris, d_triangles, d_normals, d_materials, d_lights, d_tile_xy, d_sum, d_linear, d_rgba,
-                        d_rays[0], d_rays[1], d_rays_lens, d_env, d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
+                        d_rays[0], d_rays[1], d_rays_lens, d_cam_rays, d_env, d_nee, d_contrib, d_nee_perm, d_nee_bins, d_qhits, pb.L, pb.T, pb.seed, d_counts,
                         d_t_rays, d_t_hits, d_t_stats, d_visit_totals, d_overflow, d_tile_order, d_tile_cost, d_lfinal, d_bins, d_mesh_base, d_qinst, d_mesh_mtl, d_tex_before};
         for (void* p : ptrs) if (p) hipFree(p);
         if (h_tile_cost) hipHostFree(h_tile_cost);

@@ -1967,6 +1967,47 @@ __global__ void __launch_bounds__(256) k_raygen_lens(LensRaygenArgs a) {
     }
 }
 
+// Segment 0 of a frame along the caller's own camera rays (include/crt.h at crt_set_camera_rays), flat and instanced scenes
+// alike: k_raygen_lens' numbering of workgroups, samples and paths, with the ray read from HBM in lens_ray's place.  The entry of pixel
+// (px, py) is the two float4 at py * width + px: (o, tmax) (d, pad), of which tmax and pad are not looked at; o and d go into the queue as
+// given, with CRT_INF.  The RNG state is the pixel centre with no draw taken (primary_ray's with jitter 0), for every sample.  An entry
+// without a path — a component of o or d that is not finite, or d == (0, 0, 0) — emits nothing and clears its path's place of l_final, which
+// k_fold_paths would otherwise read as the last frame left it: the fold then adds nothing for it.  No sine, no cosine, no division:
+// 32 B read and 72 B written per path.
+__global__ void __launch_bounds__(256) k_raygen_rays(RaysRaygenArgs a) {
+    if (a.zero_counts && blockIdx.x == 0)
+        for (uint32_t i = threadIdx.x; i < a.n_zero; i += blockDim.x) a.zero_counts[i] = 0u;
+    const uint32_t per_sample = (a.f.n_local_pixels + 255u) / 256u;
+    const uint32_t smp = blockIdx.x / per_sample;          // uniform over the workgroup; < n_samples by the grid
+    const uint32_t e = (blockIdx.x - smp * per_sample) * blockDim.x + threadIdx.x;
+    const uint32_t g = (e >> 12) & 7u;                     // uniform over the workgroup: 256 divides 4096
+    uint32_t px = 0, py = 0;
+    const bool active = smp < a.n_samples && e < a.f.n_local_pixels && pixel_of(a.f, e, px, py);
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (active) {                                          // in the frame: py * width + px < width * height, the entries the scene holds
+        const float4* const entry = a.cam_rays + 2 * ((size_t)py * a.f.width + px);
+        const u32x4* const words = reinterpret_cast<const u32x4*>(entry);      // two 128-bit loads; an entry is read once per sample and never written: non-temporal
+        const u32x4 w0 = __builtin_nontemporal_load(words), w1 = __builtin_nontemporal_load(words + 1);
+        r0 = make_float4(__uint_as_float(w0.x), __uint_as_float(w0.y), __uint_as_float(w0.z), 0.f);
+        r1 = make_float4(__uint_as_float(w1.x), __uint_as_float(w1.y), __uint_as_float(w1.z), 0.f);
+    }
+    const float big = 3.4028235e38f;                       // |x| <= FLT_MAX: false for an infinity and for a NaN
+    const bool finite = fabsf(r0.x) <= big && fabsf(r0.y) <= big && fabsf(r0.z) <= big && fabsf(r1.x) <= big && fabsf(r1.y) <= big && fabsf(r1.z) <= big;
+    const bool valid = active && finite && (r1.x != 0.f || r1.y != 0.f || r1.z != 0.f);
+    const uint32_t path = smp * a.f.n_local_pixels + e;
+    const uint32_t ni = wave_append(valid, a.count + g * CRT_COUNTER_STRIDE);
+    if (valid && ni < a.sub_capacity) {
+        float4* const q = a.rays + 2 * ((size_t)g * a.sub_capacity + ni);
+        q[0] = make_float4(r0.x, r0.y, r0.z, CRT_INF);
+        q[1] = make_float4(r1.x, r1.y, r1.z, __uint_as_float(path));
+        a.pb.L[path] = make_float4(0.f, 0.f, 0.f, 1.0f);
+        a.pb.T[path] = make_float4(1.f, 1.f, 1.f, __uint_as_float(1u));
+        a.pb.seed[path] = make_float2((float)px + 0.5f, (float)py + 0.5f);
+    } else if (active) {
+        a.l_final[path] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
 // One texel of the octahedral environment map with the edge identification of include/crt.h (at crt_set_environment): a tap beyond an edge
 // of the square is the texel the neighbouring direction of the lower hemisphere maps to, so the bilinear filter has no seam.
 __device__ __forceinline__ float4 env_tap(const float4* __restrict__ texels, int size, int i, int j) {
@@ -2606,6 +2647,9 @@ void launch_raygen(const RaygenArgs& a, hipStream_t stream) {
 }
 void launch_raygen_lens(const LensRaygenArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(k_raygen_lens, dim3(((a.f.n_local_pixels + 255u) / 256u) * a.n_samples), dim3(256), 0, stream, a);
+}
+void launch_raygen_rays(const RaysRaygenArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_raygen_rays, dim3(((a.f.n_local_pixels + 255u) / 256u) * a.n_samples), dim3(256), 0, stream, a);
 }
 void launch_env_miss(const EnvMissArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(k_env_miss, dim3(8u * ((a.sub_capacity + 255u) / 256u)), dim3(256), 0, stream, a);

@@ -215,6 +215,13 @@ struct LensRaygenArgs : RaygenArgs {
     uint32_t n_samples;        // 1..8 samples per pixel in this launch: path = sample * n_local_pixels + local pixel
     float rv_s[8];             // randomVector.x * randomVector.y of each of them
 };
+// k_raygen_rays, the caller's own camera rays (include/crt.h at crt_set_camera_rays).  A type of its own behind RaygenArgs,
+// as the lens's: no existing kernel's argument block moves.
+struct RaysRaygenArgs : RaygenArgs {
+    const float4* cam_rays;    // width x height entries of crt_ray (2 x float4), entry of pixel (px, py) at py * width + px
+    float4* l_final;           // the frame's final-radiance buffer: an entry without a path leaves (0, 0, 0, 0) at its path's place
+    uint32_t n_samples;        // 1..8 samples per pixel in this launch: path = sample * n_local_pixels + local pixel
+};
 
 // k_env_miss, the environment (include/crt.h at crt_set_environment): between a segment's closest-hit launch and its shade-only
 // pass, one lane per entry of the segment's path-ray queue.  An argument block of its own: no other kernel's block moves.
@@ -299,6 +306,8 @@ int launch_segment(const SegmentArgs& a, bool first, bool pretraced, bool inplac
 void launch_raygen(const RaygenArgs& a, hipStream_t stream);
 // the thin-lens form of it (camera aperture > 0; flat scenes too, up to 8 samples per launch)
 void launch_raygen_lens(const LensRaygenArgs& a, hipStream_t stream);
+// segment 0 from the caller's rays (crt_set_camera_rays; flat and instanced scenes, up to 8 samples per launch)
+void launch_raygen_rays(const RaysRaygenArgs& a, hipStream_t stream);
 // the environment's radiance for the paths a segment's closest-hit launch found to miss, through their contribution slots of that segment
 void launch_env_miss(const EnvMissArgs& a, hipStream_t stream);
 void launch_segment_instanced(const InstSegmentArgs& a, bool stats, uint32_t grid, uint32_t waves, hipStream_t stream);

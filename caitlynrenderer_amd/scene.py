@@ -165,6 +165,36 @@ class Scene:
         """crt_set_environment(NULL): frames are again what they were without one"""
         check(lib().crt_set_environment(self._h, None))
 
+    def set_camera_rays(self, o, d):
+        """crt_set_camera_rays (include/crt.h): frames follow the caller's own rays until clear_camera_rays().  `d` is
+        (height, width, 3) float32, rows as read_sum()'s; `o` the same shape, or (3,) for one origin (caitlynrenderer_amd.cameras builds
+        both).  Directions are taken as given: supply unit vectors.  An entry whose o or d has a component that is not finite, or whose d is
+        zero, has no path: its pixel gets +0.  The rays are copied; the sum is not cleared: reset() as after update(camera)."""
+        rays = self.camera_rays_array(o, d)
+        check(lib().crt_set_camera_rays(self._h, _ptr(rays), rays.shape[0]))
+
+    def camera_rays_array(self, o, d):
+        """the width * height RAY_DT entries set_camera_rays(o, d) hands over, entry of pixel (px, py) at py * width + px (tmax and pad, which
+        the library does not read, are 0): what a caller copies to the device for set_camera_rays_device"""
+        d = np.asarray(d, np.float32)
+        if d.shape != (self.height, self.width, 3):
+            raise ValueError("d must be (height, width, 3)")
+        o = np.asarray(o, np.float32)
+        if o.shape not in ((3,), d.shape):
+            raise ValueError("o must be (3,) or (height, width, 3)")
+        rays = np.zeros(self.height * self.width, RAY_DT)
+        rays["o"] = np.broadcast_to(o, d.shape).reshape(-1, 3)
+        rays["d"] = d.reshape(-1, 3)
+        return rays
+
+    def set_camera_rays_device(self, ptr, n=None):
+        """crt_set_camera_rays_device: width * height entries of 32 bytes (RAY_DT) at the device pointer `ptr` (an int), copied"""
+        check(lib().crt_set_camera_rays_device(self._h, C.c_void_p(ptr), self.width * self.height if n is None else int(n)))
+
+    def clear_camera_rays(self):
+        """crt_clear_camera_rays: the next frame is the camera's again"""
+        check(lib().crt_clear_camera_rays(self._h))
+
     def Render(self):
         """Scene::Render (Scene.h:1158-1231) minus the present pass: draw one sample, ++frame_count."""
         r1, r2 = self.rnd.randf2(), self.rnd.randf2()          # Scene.h:1208
@@ -563,7 +593,7 @@ class Scene:
     def launch_info(self):
         """crt_debug_launch_info's four words as they are: [form, build word, samples per launch chain, shards].  Bit 4 of the build word
         (16): segment 0 was fed by the lens ray generator (camera aperture > 0), and bits 0-3 are then clear.  Bit 5 (32): the frame ran with an
-        environment (set_environment)."""
+        environment (set_environment).  Bit 6 (64): segment 0 was fed by the caller's camera rays (set_camera_rays); bits 0-4 are then clear."""
         info = (C.c_int32 * 4)()
         check(lib().crt_debug_launch_info(self._h, info))
         return [int(x) for x in info]

@@ -207,6 +207,44 @@ typedef struct crt_environment {
     uint32_t reserved[2];     /* must be 0 */
 } crt_environment;
 int crt_set_environment(crt_scene* s, const crt_environment* env);
+/* Frames along the CALLER's camera rays: replaces the shader's ray set-up, path_trace.fs:1026-1047, with rays read from memory (no reference
+ * counterpart: the shader has the one pinhole).  For a panorama, an orthographic or fisheye view, a stereo pair, a cube face,
+ * radiance at lightmap texels or probe directions (a probe or a bake is a scene of width = n, height = 1), or the caller's own sub-pixel
+ * filter: everything behind the primary ray — integrator, RNG, materials, lights, environment — stays the library's.
+ *   `rays` holds width*height entries of crt_ray (32 bytes); the entry of pixel (px, py) is at py*width + px, rows as crt_read_sum's.
+ *   The call COPIES the entries into a buffer the scene owns: allocated by the first call, reused by later ones, freed with the scene.
+ *   Both set entries wait for the scene's stream(s) before the copy and for the copy after it: the caller's memory is free on return, and
+ *   a frame enqueued earlier keeps the rays it was enqueued with.  crt_clear_camera_rays waits the same way.
+ * While camera rays are set, crt_render_frame[s][_async] takes the primary ray of pixel-sample (px, py) as
+ *   o = entry.o;  d = entry.d;  tmax = 1e9f
+ * AS GIVEN: d is not normalised (the caller supplies unit directions; a non-unit d gives what the arithmetic gives), entry.tmax and
+ * entry.pad are not read.  The path's RNG state is the pixel's initial state (px + 0.5, py + 0.5) with NO draw consumed, whatever option
+ * "jitter" says — the state the pinhole's ray set-up leaves with "jitter" 0 —, and every sample of a chain uses the same rays with its own
+ * rv = rx*ry.  The path starts as every path does: L = 0, pdf = 1, T = 1, the specular flag.  The camera's position, basis, fov, aperture
+ * and focal_dist are not read by such a frame: crt_set_camera still stores them and changes no byte of it, and need not have been called.  Camera rays equal to the
+ * pinhole's "jitter" 0 rays give the pinhole's "jitter" 0 frames, bit for bit.
+ * An entry WITHOUT A PATH: if any component of o or d is not finite, or d == (0, 0, 0), that pixel-sample emits no ray, adds +0 to the
+ * pixel's sum and counts in no ray statistic (crt_frame_stats.closest_rays of such a frame counts segment 0's emitted rays).  The outside
+ * of a fisheye circle, uncovered lightmap texels, garbage in device memory that no host check can see.
+ * crt_clear_camera_rays is always allowed; the next frame is the camera's again: the fused first-segment path, with a fresh scene's launch
+ * form and bytes.
+ * A frame along camera rays runs as a chain of queue-fed segments behind a ray-generation launch, as a lens frame does, up to 8 samples per
+ * chain (crt_debug_launch_info bit 6; bits 0-4 clear), on flat and instanced scenes, with crt_set_shard, option "streams", an environment,
+ * and every option that does not change a lens frame's sums; it takes no part in the adaptive tile order.  The rays win over aperture > 0.
+ * CRT_ERR_INVALID, crt_last_error names the field, nothing stored, an earlier ray set stays in force: null scene; null rays;
+ * n != width*height; a scene on several devices (crt_set_devices with more than one) — and while camera rays are set, crt_set_devices with
+ * more than one device is refused too.
+ * The calls that see the scene through the pinhole — crt_render_aov, crt_render_ao, crt_render_fog, crt_denoise (its guides are those
+ * buffers) and crt_temporal (it reprojects through the camera) — are refused with CRT_ERR_INVALID ("camera rays") while camera rays are
+ * set, and leave their earlier images untouched: a panorama filtered against pinhole guides would be a silent wrong answer.
+ * crt_ao_points*, crt_fog_segments*, crt_trace*, crt_resolve*, crt_display, crt_bloom, crt_fog_composite, refit, rebuild and deform are
+ * unaffected.
+ * Out of scope: feature buffers, AO and fog view modes, denoising and temporal accumulation along camera rays; a per-entry tmax; borrowing
+ * the caller's buffer instead of copying; several devices; a fused first-segment arm; batched samples for instanced frames; any of it in
+ * the C oracle. */
+int crt_set_camera_rays(crt_scene* s, const crt_ray* rays, size_t n);          /* host pointer */
+int crt_set_camera_rays_device(crt_scene* s, const void* d_rays, size_t n);    /* device pointer, same layout */
+int crt_clear_camera_rays(crt_scene* s);
 /* replaces the path_trace draw in Scene::Render, Scene.h:1208-1213: adds ONE sample
  * per pixel to the device-resident RGB32F sum buffer; (rx,ry) = randomVector. */
 int crt_render_frame(crt_scene* s, float rx, float ry);
@@ -933,7 +971,8 @@ int crt_debug_launch_form(crt_scene* s, int32_t* form);
  * build compiled as a last segment (option "last_build"), bit 3: that build's LEAN form (option "lean_build"), bit 4: segment 0 was fed by the
  * lens ray generator (crt_camera.aperture > 0: every segment ran in its queue-fed form; info[0] is then 0 and bits 0-3 are clear),
  * bit 5: the frame ran with an environment (crt_set_environment: k_env_miss behind every segment's closest-hit launch; bits 0-3 clear),
- * info[2] = samples per pixel of the launch (a lens frame: of the launch chain),
+ * bit 6: segment 0 was fed by the caller's camera rays (crt_set_camera_rays: every segment ran in its queue-fed form; bits 0-4 clear),
+ * info[2] = samples per pixel of the launch (a lens frame or one along camera rays: of the launch chain),
  * info[3] = tile shards rendering side by side (option "streams" / crt_set_devices) */
 int crt_debug_launch_info(crt_scene* s, int32_t info[4]);
 /* measurement aid: hist[130] receives, for the counting frames ("count_visits") rendered since the previous call, how many node steps ran
