@@ -362,6 +362,7 @@ static int scene_create_impl(const crt_scene_desc* d, crt_scene** out) {
         }
         s->bvh2_stack = crt::bvh2_stack_entries(depth2);
         if (!s->bvh2_stack) return fail(CRT_ERR_LIMIT, who + "BVH2 deeper than 94 levels");
+        s->info.bvh2_depth = depth2;              // a scene built on the device reports its own (adopt_tree)
         const std::vector<float4> rec2 = intersection_records(d->vertices, d->triangles, d->tri_orig_ids, nullptr, d->n_triangles);
         if ((rc = upload_shared<float4>(s, kSharedBvh2, d->bvh, d->n_bvh * 2)) || (rc = upload_shared<float4>(s, kSharedTris2, rec2.data(), rec2.size()))) return rc;
     }

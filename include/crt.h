@@ -1033,7 +1033,10 @@ typedef struct crt_frame_stats {
      * "count_visits" is on (the counting kernels are slower: never time such a frame) */
     uint64_t nodes_closest, tris_closest, nodes_any, tris_any;
     /* traversal-stack pushes dropped since the scene was created.  crt_scene_create sizes the LDS stack from the
-     * validated depth of the tree, so this is 0 for every scene it accepts; the GPU tests assert it */
+     * validated depth of the tree, so this is 0 for every scene it accepts.  tests/test_walk_ref.py asserts it after every
+     * crt_trace mode, frame form, crt_ao_points and crt_fog_segments call on trees whose walks fill that stack to the last
+     * entry (DESIGN.md "The walks as tested"); tests/test_lean_build.py, test_camera_rays.py and test_instances_oracle.py
+     * assert it on their own scenes */
     uint32_t stack_overflows;
     /* with "count_visits": how many times a WAVE executed the node block / the triangle block of the closest-hit and the
      * any-hit walks (each execution offers 64 lane slots), so nodes_closest / (64 * wave_steps_closest_nodes) is the lane
@@ -1053,7 +1056,7 @@ typedef struct crt_bvh_info {
     uint64_t n_nodes8, n_tris8, n_bvh2_nodes, max_depth8;
     /* build-on-device scenes (CRT_BUILD_LBVH_ON_DEVICE): wall milliseconds of crt_scene_create and of its parts (upload of
      * the input arrays; LBVH and CWBVH conversion as device time); zero for scenes created from host-built arrays */
-    uint32_t built_on_device, bvh2_depth;
+    uint32_t built_on_device, bvh2_depth;   /* bvh2_depth: deepest leaf level of the BVH2 the scene was given or built, root = 0 */
     float build_wall_ms, build_upload_ms, build_lbvh_device_ms, build_convert_device_ms;
 } crt_bvh_info;
 int crt_get_bvh_info(crt_scene* s, crt_bvh_info* out);
